@@ -64,7 +64,15 @@ def parse_args():
                     help="embed (default): BASELINE.json's metric; train: the RecNet training iteration of configs[4] "
                          '(128 image pairs per GPU unless --batch is given), data parallel with one all-reduce of the '
                          'flat gradient buffer')
-    return ap.parse_args()
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one returned to its caller as DIR/<name>.npy (float32; at '
+                         'most 64 MB in all, a fixed seeded sample of the rows beyond that): embed: f_new, f (every rank\'s, '
+                         'after the exchange) and the pair scores; train: the four losses, the accuracy and the flat RecNet '
+                         'parameters after the step')
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
 
 
 # ---- self launch ------------------------------------------------------------------------------------
@@ -124,6 +132,28 @@ def so_sha256():
     with open(native.lib_path(), 'rb') as f:
         h.update(f.read())
     return h.hexdigest()
+
+
+DUMP_BUDGET_BYTES = 60 << 20       # --dump-outputs: array data of all files (npy headers add ~128 B each), under 64 MB
+
+
+def dump_outputs(path, tensors):
+    """{name: tensor} -> path/<name>.npy, float32 (float64 stays float64).  Over DUMP_BUDGET_BYTES in all, arrays above 1 MiB
+    share what the smaller ones leave: each keeps the same fraction of its rows, chosen by a fixed seed -- the same rows for
+    the same shapes, so two builds compare row for row."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {}
+    for name, t in tensors.items():
+        a = t.detach().cpu().numpy()
+        arrays[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+    small = sum(a.nbytes for a in arrays.values() if a.nbytes <= 1 << 20)
+    big = sum(a.nbytes for a in arrays.values()) - small
+    for name, a in arrays.items():
+        if small + big > DUMP_BUDGET_BYTES and a.nbytes > 1 << 20:
+            keep = a.shape[0] * (DUMP_BUDGET_BYTES - small) // big
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(path, name + '.npy'), np.ascontiguousarray(a))
 
 
 def under_profiler():
@@ -548,6 +578,8 @@ def train_workload(args, world, rank, local, dist):
         items = tr.step(non, ocl, label)
     fence()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:         # before the profiled iterations below move the parameters on
+        dump_outputs(args.dump_outputs, {'losses': torch.stack(items), 'accuracy': tr.accuracy.reshape(1), 'params': tr.flat_params})
     if world > 1:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -692,6 +724,9 @@ def main():
         evs.append((e0, e1))
     fence()
     dt_local = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:         # before the profiled forwards below rewrite the buffers
+        dump_outputs(args.dump_outputs, {'f_new': gathered[:, 0].reshape(-1, 512), 'f': gathered[:, 1].reshape(-1, 512),
+                                         'scores': scores})
     dt = dt_local
     per_rank = None
     if world > 1:

@@ -891,13 +891,14 @@ def test_bench_and_trainer_two_ranks_on_one_gpu():
             assert fh['full_batch_bytes'] == 2 * 2 * 40 * 3 * 112 * 112 * 4
         else:
             assert d['secondary'] is None
-    # eight handles + arenas + ranks side by side on one device (what an 8-GPU node runs, minus the links)
-    cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '8', '--steps', '2', '--warmup', '1', '--batch', '8',
+    # more than two handles + arenas + ranks side by side on one device: four, because this process holds the device too
+    # and no more than six processes may have one device open at a time
+    cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '4', '--steps', '2', '--warmup', '1', '--batch', '8',
            '--no-roofline', '--no-cpu-baseline']
     out = _Sub.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith('{')][-1])
-    assert d['n_gpus'] == 8 and d['config']['global_batch'] == 64 and len(d['per_rank']['wall_ms_per_step']) == 8
+    assert d['n_gpus'] == 4 and d['config']['global_batch'] == 32 and len(d['per_rank']['wall_ms_per_step']) == 4
     # and under torch.distributed.run, as the driver launches the multi-GPU runs
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
            '--master-port', str(free_port()), os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--batch', '16',

@@ -401,3 +401,30 @@ def test_shard_feeder_slices_before_it_copies():
         assert fd.stats['batches'] == 3 and fd.stats['h2d_bytes'] == 0
         assert fd.stats['shard_bytes'] == 2 * sum(b - a for a, b in seen[r]) * 3 * 4 * 4 * 4
     assert sorted(x for r in seen for a, b in r for x in range(a, b)) == list(range(21))
+
+
+def test_bench_dump_outputs_stays_under_64_mb_with_the_same_rows(tmp_path):
+    """bench.py --dump-outputs: float32 .npy per output; small outputs whole, and above the budget every large output keeps
+    the same seeded rows in every run (two builds compare row for row), under 64 MB in all."""
+    import bench
+    g = torch.Generator().manual_seed(0)
+    small = {'f_new': torch.randn(256, 512, generator=g), 'scores': torch.randn(128, generator=g, dtype=torch.float64)}
+    bench.dump_outputs(str(tmp_path / 'small'), small)
+    for k, v in small.items():
+        a = np.load(tmp_path / 'small' / (k + '.npy'))
+        assert a.dtype == v.numpy().dtype and np.array_equal(a, v.numpy())
+    big = {'losses': torch.randn(4, generator=g), 'params': torch.randn(20_000_000, generator=g),
+           'f': torch.randn(3000, 2048, generator=g)}
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), big)
+    files = sorted(os.listdir(tmp_path / 'a'))
+    assert files == ['f.npy', 'losses.npy', 'params.npy']
+    assert sum(os.path.getsize(tmp_path / 'a' / n) for n in files) < 64e6
+    for n in files:
+        a, b = np.load(tmp_path / 'a' / n), np.load(tmp_path / 'b' / n)
+        assert a.dtype == np.float32 and np.array_equal(a, b)
+    assert np.array_equal(np.load(tmp_path / 'a' / 'losses.npy'), big['losses'].numpy())
+    for k in ('params', 'f'):
+        a, full = np.load(tmp_path / 'a' / (k + '.npy')), big[k].numpy()
+        assert 0 < a.shape[0] < full.shape[0] and a.shape[1:] == full.shape[1:]
+        assert np.isin(a.reshape(a.shape[0], -1)[:, 0], full.reshape(full.shape[0], -1)[:, 0]).all()

@@ -1,5 +1,6 @@
 import os, sys, torch
-sys.path.insert(0, os.environ.get('GRAFT_REPO_ROOT', '/root/repo'))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
 import ffrnet_amd
 eng = ffrnet_amd.Engine(0); eng.reserve(256)
 N, cin, cout = 256, 25088, 512
