@@ -473,6 +473,67 @@ hipError_t launch_cosine(const float* a, const float* b, int n, int dim, float* 
 }
 
 // ---------------------------------------------------------------------------------------
+// Distance of two fp32 tensors for the arithmetic calibration (engine.cpp, ffr_calibrate): max|a - b| and max|b| over
+// rows x cols of pitched rows.  Pass 1: every block folds its grid-stride share into one pair (wave shuffles, then the
+// four waves through LDS); pass 2: one block folds the block pairs into table[0..1].  Max is order free: the result does
+// not depend on the grid.  A NaN difference counts as +inf, so a broken forward can never look close.
+// ---------------------------------------------------------------------------------------
+#define ABSDIFF_BLOCKS 1024
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+    return v;
+}
+
+__device__ __forceinline__ void block_max2(float& d, float& m, float* s_red /* [2][4] */) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    d = wave_max(d);
+    m = wave_max(m);
+    if (lane == 0) { s_red[wave] = d; s_red[4 + wave] = m; }
+    __syncthreads();
+    d = fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));
+    m = fmaxf(fmaxf(s_red[4], s_red[5]), fmaxf(s_red[6], s_red[7]));
+}
+
+__global__ __launch_bounds__(256) void k_absdiff_max(const float* __restrict__ a, int a_pitch, const float* __restrict__ b,
+                                                    int b_pitch, int rows, int cols, float* __restrict__ part) {
+    __shared__ float s_red[8];
+    const long long total = (long long)rows * cols;
+    float d = 0.f, m = 0.f;
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
+        const long long r = e / cols;
+        const int c = (int)(e - r * cols);
+        const float bv = b[r * b_pitch + c];
+        const float dv = fabsf(a[r * a_pitch + c] - bv);
+        d = fmaxf(d, dv != dv ? INFINITY : dv);
+        m = fmaxf(m, fabsf(bv));
+    }
+    block_max2(d, m, s_red);
+    if (threadIdx.x == 0) { part[2 * blockIdx.x] = d; part[2 * blockIdx.x + 1] = m; }
+}
+
+__global__ __launch_bounds__(256) void k_absdiff_fold(const float* __restrict__ part, int nblocks, float* __restrict__ out) {
+    __shared__ float s_red[8];
+    float d = 0.f, m = 0.f;
+    for (int i = threadIdx.x; i < nblocks; i += 256) { d = fmaxf(d, part[2 * i]); m = fmaxf(m, part[2 * i + 1]); }
+    block_max2(d, m, s_red);
+    if (threadIdx.x == 0) { out[0] = d; out[1] = m; }
+}
+
+int absdiff_scratch_floats() { return 2 * ABSDIFF_BLOCKS; }
+
+hipError_t launch_absdiff_max(const float* a, int a_pitch, const float* b, int b_pitch, int rows, int cols, float* part,
+                              float* out, hipStream_t stream) {
+    if (rows <= 0 || cols <= 0 || a_pitch < cols || b_pitch < cols) return hipErrorInvalidValue;
+    const long long total = (long long)rows * cols;
+    long long blocks = (total + 1023) / 1024;          // >= 4 elements per thread
+    if (blocks > ABSDIFF_BLOCKS) blocks = ABSDIFF_BLOCKS;
+    hipLaunchKernelGGL(k_absdiff_max, dim3((unsigned)blocks), dim3(256), 0, stream, a, a_pitch, b, b_pitch, rows, cols, part);
+    hipLaunchKernelGGL(k_absdiff_fold, dim3(1), dim3(256), 0, stream, part, (int)blocks, out);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------
 // LFW fold protocol on the device (lfw/lfw_eval.py:110-118,137-162,255-270): thresholds
 // np.arange(-1, 1, 0.005) bit for bit (numpy fills start + i*delta with delta = (start+step)-start
 // in double, which is 0.005 + 4.4e-18), same iff score > thr, contiguous test folds,

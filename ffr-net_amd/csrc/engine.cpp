@@ -108,6 +108,8 @@ int pack_conv(ffr_handle* h, std::vector<void*>& owner, const float* W, int cout
     L->wu = nullptr;
     L->wuc = nullptr;
     for (int tau = 0; tau < 4; ++tau) L->wum[tau] = nullptr;
+    L->direct = false;          // new weights: the layer's plan returns to Winograd, its calibration is void
+    L->sensitivity = -1.0;
     const int wino_min_cin = h->opt.wino_mincin;
     if (R == 3 && S == 3 && stride == 1 && pad == 1 && L->cin_pad >= wino_min_cin && wino_min_cin > 0) {
         // U[xi = i*6+j][co][ci] = (G g G^T)[i][j], same BN folds as the direct weights
@@ -219,7 +221,7 @@ bool wino_mixed_eligible(const ffr_handle* h, const ConvW& L, int N, int H, int 
     WinoMixedGeom g;
     if (!wino_mixed_geom(H, W, &g) || wino_mixed_v_floats(g, N, L.cin_pad, nullptr) > wino_cap) return false;
     if (wino_mode == 4) return true;
-    if (wino_mode >= 0 || !h->opt.wino || !h->opt.wino_fused || !h->opt.wf_mixed) return false;
+    if (wino_mode >= 0 || !layer_wino(h, L) || !h->opt.wino_fused || !h->opt.wf_mixed) return false;
     // >= 2 blocks per CU: a long block pairs with a short one (16 instead of 18 slots per CU).  With ONE block per CU the (4,4) blocks
     // set the time: a single launch still wins 7 % there because V is 16 % smaller (round 5, tools/mixed7_experiment.py: 256 -> 256
     // at 128 images: 95.1 + 31.8 us padded vs 92.9 + 24.9 us exact), but in the forward, where the transform rides in the combine
@@ -299,7 +301,7 @@ int prepare_mixed_weights(ffr_handle* h, int N, int H, int W, size_t wino_cap) {
 // lies in winoV in fragment order (run_conv with wino_stage 2 / v_chunked): not the in-kernel transform, no split-off
 // remainder, scratch large enough.  run_conv applies the same tests.
 bool wino_accepts_ready_v(const ffr_handle* h, const ConvW& L, int N, int H, int W, int in_pitch, size_t wino_cap) {
-    if (!L.wu || !L.wuc || !h->opt.wino || L.pad_mode != 0) return false;
+    if (!L.wu || !L.wuc || !layer_wino(h, L) || L.pad_mode != 0) return false;
     if (wino_mixed_applies(h, L, N, H, W, in_pitch, wino_cap, -1)) return false;     // that path transforms its own V (for now)
     const int th = (H + 3) / 4, tw = (W + 3) / 4;
     const long long T = (long long)N * th * tw;
@@ -441,7 +443,7 @@ int run_conv(ffr_handle* h, const ConvW& L, const ConvCall& c, hipStream_t st) {
     a.nbatch = 1;
     const double flops = 2.0 * M * L.cout * (double)L.R * L.S * L.cin;
     const double bytes = 4.0 * ((double)c.N * c.H * c.W * L.cin + (double)M * L.cout + (double)L.cout * L.R * L.S * L.cin);
-    const bool wino_on = h->opt.wino != 0;
+    const bool wino_on = layer_wino(h, L);       // option wino and the layer's plan (a pinned layer runs as under wino = 0)
     if (wino_mixed_applies(h, L, c.N, c.H, c.W, c.in_pitch, c.wino_cap, c.wino_mode) && c.winoV && c.tile == 0 &&
         (c.wino_stage == 0 || (c.wino_stage == 2 && c.v_mixed)) &&
         ((c.out_pitch | c.out_coff | c.res_pitch | c.cout_store) & 3) == 0) {
@@ -844,7 +846,7 @@ int run_trunk(ffr_handle* h, const Work& w, const float* x_nchw, int N, int H, i
         const long long Tt = (long long)N * ((ch + 3) / 4) * ((cw + 3) / 4);
         bool chained = false;
         const bool fused_on = h->opt.wino_fused != 0;
-        if (!fused_on && b.stride == 1 && b.c1.wu && b.c2.wu && b.c1.cout_pad == b.c2.cin_pad && b.c2.pad_mode == 0 &&
+        if (!fused_on && b.stride == 1 && b.c1.wu && b.c2.wu && !b.c1.direct && !b.c2.direct && b.c1.cout_pad == b.c2.cin_pad && b.c2.pad_mode == 0 &&
             wino_out_in_supported(ch, cw, b.c1.cout_pad) && (size_t)36 * Tt * b.c1.cout_pad <= w.wino_cap &&
             (size_t)36 * Tt * b.c1.cin_pad <= w.wino_cap && (size_t)36 * Tt * b.c2.cout_pad <= w.wino_cap) {
             c1.wino_stage = 1; c1.took_wino = &chained;
@@ -1044,6 +1046,34 @@ int check_fwd(ffr_handle* h, bool need_enc, bool need_rec, int N) {
     return FFR_OK;
 }
 
+struct PlanLayer { ConvW* L; std::string name; int net; };
+
+// The Winograd-eligible convolutions of the loaded nets (those the handle packed wu for), in ffr_layer_get order.
+std::vector<PlanLayer> plan_layers(const ffr_handle* hc) {
+    ffr_handle* h = const_cast<ffr_handle*>(hc);
+    std::vector<PlanLayer> v;
+    if (h->enc_loaded)
+        for (size_t i = 0; i < h->blocks.size(); ++i) {
+            Block& b = h->blocks[i];
+            const std::string p = "body." + std::to_string(i) + ".res_layer.";
+            if (b.c1.wu) v.push_back({&b.c1, p + "1", 0});
+            if (b.c2.wu) v.push_back({&b.c2, p + "3", 0});
+        }
+    if (h->rec_loaded) {
+        static const char* SP[9] = {"Conv4Space.0", "Conv4Space.1.conv1", "Conv4Space.1.conv2", "Conv4Space.2", "Conv4Space.3.conv1",
+                                    "Conv4Space.3.conv2", "Conv4Space.4", "Conv4Space.5.conv1", "Conv4Space.5.conv2"};
+        static const char* FM[3] = {"ChannelFlipMerge.0", "ChannelFlipMerge.1.conv1", "ChannelFlipMerge.1.conv2"};
+        static const char* MG[3] = {"Conv4Merge.0", "Conv4Merge.1.conv1", "Conv4Merge.1.conv2"};
+        for (int i = 0; i < 9; ++i) if (h->sp[i].wu) v.push_back({&h->sp[i], std::string(SP[i]) + ".conv2d", 1});
+        for (int i = 0; i < 3; ++i) if (h->fm[i].wu) v.push_back({&h->fm[i], std::string(FM[i]) + ".conv2d", 1});
+        for (int i = 0; i < 3; ++i) if (h->mg[i].wu) v.push_back({&h->mg[i], std::string(MG[i]) + ".conv2d", 1});
+    }
+    return v;
+}
+
+// A plan change invalidates captured graphs, and the exact-tiling weight sets of a layer that returns to Winograd may not
+// exist yet: the next encoder call walks the layers again (prepare_mixed_weights).
+void plan_changed(ffr_handle* h) { ++h->generation; h->mixed_ready_n = 0; }
 }  // namespace ffr_eng
 
 // =========================================================================================
@@ -1420,6 +1450,170 @@ int ffr_lfw_fold_accuracy(ffr_handle* h, const float* score, const int32_t* labe
 }
 
 unsigned long long ffr_generation(const ffr_handle* h) { return h ? h->generation : 0; }
+
+// ---- per-layer arithmetic plan --------------------------------------------------------------------------------------
+int ffr_layer_count(const ffr_handle* h, int* n) {
+    if (!h || !n) return fail(const_cast<ffr_handle*>(h), FFR_ERR_ARG, "ffr_layer_count: null argument");
+    *n = (int)plan_layers(h).size();
+    return FFR_OK;
+}
+
+int ffr_layer_get(const ffr_handle* h, int i, ffr_layer_info* out) {
+    if (!h || !out) return fail(const_cast<ffr_handle*>(h), FFR_ERR_ARG, "ffr_layer_get: null argument");
+    const std::vector<PlanLayer> v = plan_layers(h);
+    if (i < 0 || i >= (int)v.size()) return fail(const_cast<ffr_handle*>(h), FFR_ERR_ARG, "ffr_layer_get: index %d outside [0, %d)", i, (int)v.size());
+    memset(out, 0, sizeof *out);
+    snprintf(out->name, sizeof out->name, "%s", v[i].name.c_str());
+    out->net = v[i].net;
+    out->arith = v[i].L->direct ? FFR_ARITH_DIRECT : FFR_ARITH_WINOGRAD;
+    out->sensitivity = v[i].L->sensitivity;
+    return FFR_OK;
+}
+
+int ffr_layer_set_arith(ffr_handle* h, int i, int arith) {
+    if (!h) return fail(nullptr, FFR_ERR_ARG, "null handle");
+    if (arith != FFR_ARITH_DIRECT && arith != FFR_ARITH_WINOGRAD) return fail(h, FFR_ERR_ARG, "ffr_layer_set_arith: arith %d is neither 0 (direct) nor 1 (Winograd)", arith);
+    const std::vector<PlanLayer> v = plan_layers(h);
+    if (i < 0 || i >= (int)v.size()) return fail(h, FFR_ERR_ARG, "ffr_layer_set_arith: index %d outside [0, %d)", i, (int)v.size());
+    const bool direct = arith == FFR_ARITH_DIRECT;
+    if (v[i].L->direct != direct) { v[i].L->direct = direct; plan_changed(h); }
+    return FFR_OK;
+}
+
+int ffr_calibrate(ffr_handle* h, const float* x, const float* featmap, int N, int H, int W, double tol, double* achieved,
+                  void* stream) {
+    if (!h) return fail(nullptr, FFR_ERR_ARG, "null handle");
+    hipStream_t st = (hipStream_t)stream;
+    {   // first, before anything is enqueued: a calibration synchronises, which a capture cannot hold
+        FFR_DEVICE_SCOPE(h);
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        HIPCK(h, hipStreamIsCapturing(st, &cs));
+        if (cs != hipStreamCaptureStatusNone) return fail(h, FFR_ERR_ARG, "ffr_calibrate: the stream is capturing (the call synchronises)");
+    }
+    if (!(tol > 0.0)) return fail(h, FFR_ERR_ARG, "ffr_calibrate: tol must be > 0 (got %g)", tol);
+    if ((x != nullptr) == (featmap != nullptr)) return fail(h, FFR_ERR_ARG, "ffr_calibrate: pass images (x) or a featmap, exactly one of them");
+    const bool enc = x != nullptr;
+    FFR_DEVICE_SCOPE(h); RC(check_fwd(h, enc, !enc, N));
+    if (enc && (H < 32 || W < 32 || (H & 15) || (W & 15))) return fail(h, FFR_ERR_ARG, "H and W must be multiples of 16, >= 32");
+    if (!enc && (H != 7 || W != 7)) return fail(h, FFR_ERR_ARG, "ffr_calibrate: a featmap is [N,512,7,7] (H = W = 7)");
+    const bool is112 = enc && H == 112 && W == 112;
+    const bool rec = !enc || (h->rec_loaded && is112);
+    const int P = enc ? (H / 16) * (W / 16) : 49;
+
+    // candidates: the layers this forward runs; the plan of the others stays as it is
+    std::vector<ConvW*> cand;
+    for (const PlanLayer& pl : plan_layers(h))
+        if ((pl.net == 0 && enc) || (pl.net == 1 && rec)) cand.push_back(pl.L);
+    const int L = (int)cand.size();
+    struct Saved {      // the plan and the profiling switch come back on every path; device buffers are released
+        ffr_handle* h; std::vector<std::pair<ConvW*, bool>> plan; bool prof; void* buf = nullptr; bool keep = false;
+        ~Saved() {
+            if (buf) { hipDeviceSynchronize(); hipFree(buf); }
+            h->prof = prof;
+            if (!keep) for (auto& p : plan) p.first->direct = p.second;
+        }
+    } sv{h, {}, h->prof};
+    for (ConvW* c : cand) sv.plan.push_back({c, c->direct});
+    h->prof = false;          // calibration forwards are not part of any measurement
+
+    // every candidate on Winograd while the workspace is prepared: the exact-tiling weight sets of all eligible layers are
+    // derived now (synchronous, once), so that no forward below needs them derived
+    for (ConvW* c : cand) c->direct = false;
+    h->mixed_ready_n = 0;
+    Work w;
+    if (enc) RC(ensure_arena_encoder(h, N, H, W, &w));
+    else RC(ensure_arena(h, N, 112, 112, &w));
+
+    // outputs: 0 f, 1 featmap, 2 f_new, 3 feat_new (NHWC rows of 512); where the current forward leaves them / the anchor copy
+    const bool have[4] = {is112, enc, rec, rec};
+    const size_t rows[4] = {(size_t)N, (size_t)N * P, (size_t)N, (size_t)N * 49};
+    float* featmap_nhwc = rec ? w.X : w.trunk_bn;
+    const int max_trials = 2 * L + 4;
+    const size_t scratch = (size_t)absdiff_scratch_floats();
+    size_t floats = scratch + (size_t)max_trials * 4 * 2 + 2 * (size_t)N * 512;        // scratch, table, f / f_new of the forward
+    size_t off_anchor[4];
+    for (int t = 0; t < 4; ++t) { off_anchor[t] = floats; floats += have[t] ? rows[t] * 512 : 0; }
+    HIPCK(h, hipMalloc(&sv.buf, floats * sizeof(float)));
+    float* base = (float*)sv.buf;
+    float* part = base;
+    float* table = base + scratch;
+    float* f_cur = table + (size_t)max_trials * 8;
+    float* fnew_cur = f_cur + (size_t)N * 512;
+    const float* cur[4] = {f_cur, featmap_nhwc, fnew_cur, w.m512c};
+    float* anchor[4];
+    for (int t = 0; t < 4; ++t) anchor[t] = base + off_anchor[t];
+    HIPCK(h, hipMemsetAsync(table, 0, (size_t)max_trials * 8 * sizeof(float), st));
+
+    auto forward = [&]() -> int {
+        if (enc) {
+            RC(run_encoder(h, w, x, N, H, W, featmap_nhwc, is112 ? f_cur : nullptr, st));
+        } else {
+            HIPCK(h, launch_nchw_to_nhwc(featmap, w.X, 512, N, 49, 512, st));
+        }
+        if (rec) RC(run_recnet(h, w, N, fnew_cur, nullptr, st));
+        return FFR_OK;
+    };
+    auto compare = [&](int slot) -> int {
+        for (int t = 0; t < 4; ++t)
+            if (have[t]) HIPCK(h, launch_absdiff_max(cur[t], 512, anchor[t], 512, (int)rows[t], 512, part, table + ((size_t)slot * 4 + t) * 2, st));
+        return FFR_OK;
+    };
+    std::vector<float> host((size_t)max_trials * 8);
+    auto read = [&]() -> int {          // the phase's one copy to the host
+        HIPCK(h, hipMemcpyAsync(host.data(), table, host.size() * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIPCK(h, hipStreamSynchronize(st));
+        return FFR_OK;
+    };
+    auto rel = [&](int slot, int t) { const float* q = &host[((size_t)slot * 4 + t) * 2]; return q[1] > 0.f ? (double)q[0] / q[1] : (double)q[0]; };
+    auto err = [&](int slot) { double e = 0.0; for (int t = 0; t < 4; ++t) if (have[t]) e = std::max(e, rel(slot, t)); return e; };
+    auto set_plan = [&](const std::vector<char>& wino) { for (int k = 0; k < L; ++k) cand[k]->direct = !wino[k]; };
+
+    // phase 1: anchor (all direct), slot 0 = all Winograd, slot 1 + k = only layer k on Winograd
+    set_plan(std::vector<char>(L, 0));
+    RC(forward());
+    for (int t = 0; t < 4; ++t)
+        if (have[t]) HIPCK(h, hipMemcpyAsync(anchor[t], cur[t], rows[t] * 512 * sizeof(float), hipMemcpyDeviceToDevice, st));
+    set_plan(std::vector<char>(L, 1));
+    RC(forward()); RC(compare(0));
+    for (int k = 0; k < L; ++k) {
+        std::vector<char> one(L, 0);
+        one[k] = 1;
+        set_plan(one);
+        RC(forward()); RC(compare(1 + k));
+    }
+    RC(read());
+    const double half = 0.5 * tol;
+    for (int k = 0; k < L; ++k) cand[k]->sensitivity = err(1 + k);
+    std::vector<int> order(L);
+    for (int k = 0; k < L; ++k) order[k] = k;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return cand[a]->sensitivity < cand[b]->sensitivity; });
+    auto prefix_plan = [&](int p) { std::vector<char> v(L, 0); for (int i = 0; i < p; ++i) v[order[i]] = 1; return v; };
+
+    // phase 2: the passing prefixes of the sensitivity order (p = L is slot 0 above; p = 0 is the anchor itself)
+    std::vector<int> passing;           // prefix lengths <= tol / 2, longest first
+    if (err(0) <= half) passing.push_back(L);
+    else if (L > 1) {
+        for (int p = 1; p < L; ++p) { set_plan(prefix_plan(p)); RC(forward()); RC(compare(p)); }
+        RC(read());
+        for (int p = L - 1; p >= 1; --p) if (err(p) <= half) passing.push_back(p);
+    }
+    passing.push_back(0);
+
+    // phase 3: verify the chosen plan with one more forward; should it fail, the next shorter passing prefix is verified
+    for (int p : passing) {
+        set_plan(prefix_plan(p));
+        RC(forward()); RC(compare(0));
+        RC(read());
+        if (err(0) <= half || p == 0) break;
+    }
+    if (achieved) for (int t = 0; t < 4; ++t) achieved[t] = have[t] ? rel(0, t) : -1.0;
+    sv.keep = true;
+    bool changed = false;
+    for (auto& pr : sv.plan) changed |= pr.first->direct != pr.second;
+    if (changed) plan_changed(h);
+    else h->mixed_ready_n = 0;
+    return FFR_OK;
+}
 
 namespace {
 struct OptEntry { const char* name; int ffr_eng::Options::*i; long long ffr_eng::Options::*l; long long lo, hi; };

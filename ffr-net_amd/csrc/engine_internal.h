@@ -36,6 +36,10 @@ struct ConvW {
                              // (engine.cpp, ensure_mixed_weights), null before
     bool wum_gave_up = false;   // the device could not hold this layer's extra sets: it stays on padded F(4x4) tiles (never retried)
     float* wuc = nullptr;    // the same in the K-chunk order k_wino_fused streams ([cout_pad/64][cin_pad/8][36][128][4]) or null
+    // per-layer arithmetic plan (ffr_layer_set_arith / ffr_calibrate): a layer with wu pinned to direct runs exactly
+    // what it runs under option wino = 0.  ffr_load_* reset it (pack_conv).
+    bool direct = false;
+    double sensitivity = -1.0;   // last ffr_calibrate: end-to-end difference with only this layer on Winograd (-1: none)
 };
 
 struct Block {
@@ -212,6 +216,8 @@ struct ConvCall {
     bool* tile_sums_written = nullptr;             // set to true when the Winograd path wrote them
 };
 
+// Does layer L run Winograd when the caller leaves the choice to the planner (wino_mode -1)?  Option wino and the layer's plan.
+inline bool layer_wino(const ffr_handle* h, const ConvW& L) { return h->opt.wino != 0 && !L.direct; }
 int wino_fused_choice(const ffr_handle* h, int cin_pad, int cout_pad, long long T, double x_bytes, int wino_mode);
 bool wino_accepts_ready_v(const ffr_handle* h, const ConvW& L, int N, int H, int W, int in_pitch, size_t wino_cap);
 bool wino_mixed_applies(const ffr_handle* h, const ConvW& L, int N, int H, int W, int in_pitch, size_t wino_cap, int wino_mode);

@@ -176,6 +176,11 @@ hipError_t launch_copy_slice(const float* in, float* out, int M, int C, int pitc
                              hipStream_t stream);
 hipError_t launch_cosine(const float* a, const float* b, int n, int dim, float* score,
                          hipStream_t stream);
+// calibration distance: out[0] = max|a - b|, out[1] = max|b| over rows x cols (pitched rows; a NaN difference counts as
+// +inf); part: absdiff_scratch_floats() floats of scratch.  Two launches, deterministic
+int absdiff_scratch_floats();
+hipError_t launch_absdiff_max(const float* a, int a_pitch, const float* b, int b_pitch, int rows, int cols, float* part,
+                              float* out, hipStream_t stream);
 
 // LFW fold protocol on device; scratch = 400*32 ints, best_thr/test_acc = nf doubles (device)
 hipError_t launch_fold_protocol(const float* score, const int* label, int n, int nf, int* scratch, double* best_thr,

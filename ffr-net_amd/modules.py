@@ -123,7 +123,74 @@ class _NativeModule(nn.Module):
             getattr(eng, 'load_' + self._kind)(self.state_dict())
             cache[device.index] = (sig, eng, lst)
             ent = cache[device.index]
+            self._arith_apply(eng)           # new weights void the plan: recalibrate (or re-apply a plan that was set)
         return ent[1]
+
+    # -- per-layer arithmetic (Engine.calibrate) ------------------------------------------------------
+    # The shell keeps the calibration batch and tol (or an explicitly set plan) in `_arith` and applies it to every handle
+    # it packs, so the guard follows the weights: a re-pack after a weight change recalibrates.  No parameter or buffer is
+    # added (the state_dict key set is the contract); copy.deepcopy carries `_arith`.
+    _calib_input = None
+
+    def _arith_apply(self, eng):
+        st = self.__dict__.get('_arith')
+        if st is None:
+            return
+        if st['x'] is not None:
+            with torch.no_grad():
+                rep = eng.calibrate(tol=st['tol'], **{self._calib_input: st['x'].to(eng.device)})
+            rep['layers'] = [l for l in rep['layers'] if l['net'] == self._kind]
+            st['report'], st['plan'] = rep, eng.arithmetic_plan(self._kind)
+            st['calibrations'] += 1
+        else:
+            eng.set_arithmetic_plan(st['plan'], net=self._kind)
+
+    def _plan_engine(self):
+        cache = self.__dict__.get('_native_cache', {})
+        dev = next((k for k in cache if isinstance(k, int)), None)
+        return self._engine(torch.device('cuda', dev if dev is not None else torch.cuda.current_device()))
+
+    def calibrate_arithmetic(self, x, tol=1e-4):
+        """Pin layers to direct convolution only as far as needed for this module's forward on `x` (this batch size) to stay
+        within tol * abs-max of its all-direct forward, per output tensor (Engine.calibrate).  The batch and tol are kept:
+        whenever the packed weights are rebuilt (a weight changed) the module recalibrates.  -> the report."""
+        self._require_native(x, self.__class__.__name__)
+        st = dict(x=x.detach().clone(), tol=float(tol), plan=None, report=None, calibrations=0)
+        self.__dict__['_arith'] = st
+        eng = self._engine(x.device)
+        if st['calibrations'] == 0:
+            self._arith_apply(eng)
+        return st['report']
+
+    def calibration_report(self):
+        """The report of the last calibration (regenerated on every recalibration), or None."""
+        st = self.__dict__.get('_arith')
+        return st['report'] if st else None
+
+    def arithmetic_plan(self):
+        """{conv state_dict prefix: 'direct' | 'winograd'} of this module's Winograd-eligible convolutions."""
+        return self._plan_engine().arithmetic_plan(self._kind)
+
+    def set_arithmetic_plan(self, plan):
+        """Run this plan (e.g. rank 0's arithmetic_plan()); layers it does not name run Winograd.  Replaces a calibration
+        unless the plan is the calibrated one."""
+        st = self.__dict__.get('_arith')
+        plan = dict(plan)
+        if st is not None and st['x'] is not None and st['plan'] == plan:
+            return
+        eng = self._plan_engine()
+        eng.set_arithmetic_plan(plan, net=self._kind)          # validates the names
+        self.__dict__['_arith'] = dict(x=None, tol=None, plan=plan, report=None, calibrations=0)
+        for k, ent in self.__dict__.get('_native_cache', {}).items():
+            if isinstance(k, int):
+                ent[1].set_arithmetic_plan(plan, net=self._kind)
+
+    def clear_calibration(self):
+        """Back to the default arithmetic (every eligible layer on Winograd); the kept batch is dropped."""
+        self.__dict__.pop('_arith', None)
+        for k, ent in self.__dict__.get('_native_cache', {}).items():
+            if isinstance(k, int):
+                ent[1].set_arithmetic_plan({}, net=self._kind)
 
     def _reject_replica(self, what):
         if getattr(self, '_is_replica', False):
@@ -163,6 +230,7 @@ class _NativeModule(nn.Module):
 
 class Backbone(_NativeModule):
     _kind = 'encoder'
+    _calib_input = 'x'
 
     def __init__(self, num_layers, drop_ratio, mode='ir'):
         super().__init__()
@@ -236,6 +304,7 @@ class AddMarginProduct(_Holder):
 
 class RecNet(_NativeModule):
     _kind = 'recnet'
+    _calib_input = 'featmap'
 
     def __init__(self, channel=512, shape=7, norm_type='bn', relu_type='prelu'):
         super().__init__()

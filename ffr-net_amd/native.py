@@ -48,6 +48,14 @@ class ConvDesc(C.Structure):
                 ('tile', C.c_int), ('splitk', C.c_int)]
 
 
+class LayerInfo(C.Structure):
+    _fields_ = [('name', C.c_char * 64), ('net', C.c_int), ('arith', C.c_int), ('sensitivity', C.c_double)]
+
+
+ARITH = {'direct': 0, 'winograd': 1}
+CALIB_TENSORS = ('f', 'featmap', 'f_new', 'feat_new')
+
+
 _LIB_PATH = os.path.join(_HERE, 'libffrnet_hip.so')
 
 
@@ -82,6 +90,10 @@ SYMBOLS = [
     ('ffr_workspace_bytes', C.c_size_t, [_P, C.c_int, C.c_int, C.c_int]),
     ('ffr_reserve', C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
     ('ffr_generation', C.c_ulonglong, [_P]),
+    ('ffr_layer_count', C.c_int, [_P, C.POINTER(C.c_int)]),
+    ('ffr_layer_get', C.c_int, [_P, C.c_int, C.POINTER(LayerInfo)]),
+    ('ffr_layer_set_arith', C.c_int, [_P, C.c_int, C.c_int]),
+    ('ffr_calibrate', C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_double), _P]),
     ('ffr_memory_stats', C.c_int, [_P, _P]),
     ('ffr_set_option', C.c_int, [_P, C.c_char_p, C.c_longlong]),
     ('ffr_get_option', C.c_int, [_P, C.c_char_p, C.POINTER(C.c_longlong)]),
@@ -361,6 +373,80 @@ class Engine(object):
     def generation(self):
         """Changes whenever the handle released device memory a captured hipGraph may point into."""
         return int(self.lib.ffr_generation(self._h))
+
+    # -- per-layer arithmetic (include/ffrnet.h: ffr_layer_*, ffr_calibrate; DESIGN.md 3.3) ----------------------------
+    def layers(self):
+        """The Winograd-eligible convolutions of the loaded nets: [{index, name, net, arith, sensitivity}], name = the
+        conv's state_dict prefix, net 'encoder' | 'recnet', arith 'direct' | 'winograd', sensitivity from the last
+        calibrate() (None before)."""
+        n = C.c_int(0)
+        self._ck(self.lib.ffr_layer_count(self._h, C.byref(n)))
+        out = []
+        for i in range(n.value):
+            li = LayerInfo()
+            self._ck(self.lib.ffr_layer_get(self._h, i, C.byref(li)))
+            out.append(dict(index=i, name=li.name.decode(), net=('encoder', 'recnet')[li.net],
+                            arith='direct' if li.arith == 0 else 'winograd',
+                            sensitivity=li.sensitivity if li.sensitivity >= 0 else None))
+        return out
+
+    def _layer_index(self, name_or_index):
+        if isinstance(name_or_index, int):
+            return name_or_index
+        for l in self.layers():
+            if l['name'] == name_or_index:
+                return l['index']
+        raise KeyError('ffrnet_amd: no Winograd-eligible layer named %r' % (name_or_index,))
+
+    def set_layer_arith(self, name_or_index, arith):
+        """Pin one layer to 'direct' or return it to 'winograd'.  Changes generation() (captured graphs re-capture)."""
+        if arith not in ARITH:
+            raise ValueError("ffrnet_amd: arith must be 'direct' or 'winograd', got %r" % (arith,))
+        self._ck(self.lib.ffr_layer_set_arith(self._h, self._layer_index(name_or_index), ARITH[arith]))
+
+    def arithmetic_plan(self, net=None):
+        """{layer name: 'direct' | 'winograd'} of the loaded nets (or of one net: 'encoder' | 'recnet')."""
+        return {l['name']: l['arith'] for l in self.layers() if net is None or l['net'] == net}
+
+    def set_arithmetic_plan(self, plan, net=None):
+        """Apply a {name: 'direct' | 'winograd'} mapping; the layers it does not name (of `net`, or of every loaded net)
+        return to Winograd.  Unknown names raise KeyError."""
+        known = {l['name']: l for l in self.layers()}
+        for name, arith in plan.items():
+            if name not in known:
+                raise KeyError('ffrnet_amd: no Winograd-eligible layer named %r' % (name,))
+            if arith not in ARITH:
+                raise ValueError("ffrnet_amd: arith must be 'direct' or 'winograd', got %r" % (arith,))
+        for name, l in known.items():
+            if net is None or l['net'] == net:
+                want = plan.get(name, 'winograd')
+                if want != l['arith']:
+                    self._ck(self.lib.ffr_layer_set_arith(self._h, l['index'], ARITH[want]))
+
+    def calibrate(self, x=None, featmap=None, tol=1e-4):
+        """Pin layers to direct only as far as needed for this handle's forward on these inputs (x[N,3,H,W] images or
+        featmap[N,512,7,7], exactly one) to stay within tol * abs-max of its all-direct forward, per output tensor
+        (ffr_calibrate).  Synchronises.  -> {'tol', 'n', 'layers': [{name, net, sensitivity, arith}], 'achieved':
+        {f, featmap, f_new, feat_new: value or None where the forward has no such output}}.  Calibrate at the batch size
+        you will run: the Winograd kernels depend on it."""
+        if (x is None) == (featmap is None):
+            with torch.cuda.device(self.device):
+                self._ck(self.lib.ffr_calibrate(self._h, _ptr(x), _ptr(featmap), 1, 112, 112, float(tol), None, self._stream()))
+        t = x if x is not None else featmap
+        _check_dev(t, 'x' if x is not None else 'featmap', device=self.device)
+        t = t.contiguous()
+        if x is not None and (t.dim() != 4 or t.size(1) != 3):
+            raise RuntimeError('ffrnet_amd: calibration images must be [N,3,H,W], got %s' % list(t.shape))
+        if featmap is not None and (t.dim() != 4 or tuple(t.shape[1:]) != (512, 7, 7)):
+            raise RuntimeError('ffrnet_amd: a calibration featmap must be [N,512,7,7], got %s' % list(t.shape))
+        n, _, h, w = t.shape
+        ach = (C.c_double * 4)()
+        with torch.cuda.device(self.device):
+            self._ck(self.lib.ffr_calibrate(self._h, _ptr(x if x is None else t), _ptr(featmap if featmap is None else t),
+                                            n, h, w, float(tol), ach, self._stream()))
+        return dict(tol=float(tol), n=int(n),
+                    layers=[dict(name=l['name'], net=l['net'], sensitivity=l['sensitivity'], arith=l['arith']) for l in self.layers()],
+                    achieved={k: (ach[i] if ach[i] >= 0 else None) for i, k in enumerate(CALIB_TENSORS)})
 
     def memory_stats(self):
         """Device bytes and packing seconds of the handle (include/ffrnet.h: ffr_mem_stats)."""

@@ -194,9 +194,48 @@ int ffr_profile_enable(ffr_handle* h, int on);
 int ffr_set_option(ffr_handle* h, const char* name, long long value);
 int ffr_get_option(const ffr_handle* h, const char* name, long long* value);
 /* Allocation generation: changes whenever device memory that a caller may have captured into a hipGraph (workspace
- * arena, stream-K tickets, packed weights, training buffers) has been released and re-allocated.  A graph captured
- * around ffr_embed must be re-captured when this value differs from the one read at capture time.               */
+ * arena, stream-K tickets, packed weights, training buffers) has been released and re-allocated, and whenever the
+ * per-layer arithmetic plan changes (ffr_layer_set_arith, ffr_calibrate): a graph captured before a plan change would
+ * replay the old plan.  A graph captured around ffr_embed must be re-captured when this value differs from the one read
+ * at capture time.                                                                                                   */
 unsigned long long ffr_generation(const ffr_handle* h);
+
+/* ---- per-layer arithmetic ----------------------------------------------------------------------
+ * Every 3x3 stride-1 convolution packed for Winograd F(4x4,3x3) (padded cin >= option wino_mincin) is a "layer" of the
+ * plan: the encoder's body.i.res_layer.1 of every bottleneck and res_layer.3 of the stride-1 ones (44 for IR-SE50), and
+ * RecNet's ConvLayers (Conv4Space, ChannelFlipMerge, Conv4Merge).  Each runs Winograd (the default) or direct; a layer
+ * pinned to direct runs exactly the arithmetic it runs under option wino = 0 (which still overrides every plan), so an
+ * all-direct plan is bit-identical to wino = 0 and an all-Winograd plan to the default.  The plan applies to every
+ * inference forward of the handle (ffr_encoder_forward, ffr_recnet_forward, ffr_embed*, ffr_encoder_trunk_nhwc and the
+ * frozen encoder of ffr_train_iteration); RecNet's training step keeps its own ffr_train_option("winograd").
+ * ffr_load_encoder / ffr_load_recnet reset that net's layers to Winograd and clear their sensitivities. Index order:
+ * encoder layers by bottleneck (res_layer.1 before res_layer.3), then RecNet's in state_dict order.                 */
+enum { FFR_ARITH_DIRECT = 0, FFR_ARITH_WINOGRAD = 1 };
+typedef struct {
+    char   name[64];     /* state_dict prefix of the conv: "body.7.res_layer.1", "Conv4Space.1.conv1.conv2d", ...          */
+    int    net;          /* 0 encoder, 1 RecNet                                                                            */
+    int    arith;        /* FFR_ARITH_DIRECT / FFR_ARITH_WINOGRAD                                                          */
+    double sensitivity;  /* last ffr_calibrate: end-to-end difference with ONLY this layer on Winograd; -1 if none          */
+} ffr_layer_info;
+int ffr_layer_count(const ffr_handle* h, int* n);
+int ffr_layer_get(const ffr_handle* h, int i, ffr_layer_info* out);          /* FFR_ERR_ARG for i outside [0, n)       */
+int ffr_layer_set_arith(ffr_handle* h, int i, int arith);                   /* FFR_ERR_ARG for a bad i or arith       */
+/* Calibrated arithmetic: pins layers to direct only as far as needed for the handle's forward ON THESE INPUTS, AT THIS N,
+ * to differ from its own all-direct forward by at most `tol` of each output tensor's abs-max.
+ *   x_nchw [N,3,H,W] (device): the encoder's layers (outputs featmap, and f at 112x112) plus RecNet's when it is loaded and
+ *   H = W = 112 (outputs f_new, feat_new) -- XOR -- featmap_nchw [N,512,7,7] (device, H = W = 7): RecNet's layers only.
+ *   achieved[4] (host, may be NULL): per output tensor (f, featmap, f_new, feat_new; -1 where absent) the final plan's
+ *   max|calibrated - direct| / max|direct| on these inputs.
+ * Method: one all-direct forward as the anchor; one forward per layer with only that layer on Winograd (its sensitivity);
+ * the layers sorted by sensitivity, the longest low-sensitivity prefix that stays <= tol / 2 keeps Winograd (every prefix
+ * is measured: no monotonicity is assumed); one more forward verifies the plan (the margin of 1/2 is for other images of
+ * the same distribution).  Comparisons run on the device; each phase copies one small table to the host.
+ * The Winograd kernels depend on N (the exact 4+4+3+3 tiling of stage 3 appears only at large batches): calibrate at the
+ * batch size you will run.  Unlike every forward entry point this call SYNCHRONISES `stream` (up to 3 times), allocates and
+ * frees device memory, and refuses to run while `stream` is capturing.  Errors: FFR_ERR_ARG for tol <= 0 or NaN, both or
+ * neither input, a capturing stream; FFR_ERR_STATE when the net it needs is not loaded.  On error the plan is unchanged. */
+int ffr_calibrate(ffr_handle* h, const float* x_nchw, const float* featmap_nchw, int N, int H, int W,
+                  double tol, double* achieved, void* stream);
 /* Device memory and packing time of the handle (round 5; the reference's counterpart is `net.load_state_dict(...)` +
  * `.to(device)`, models/trainer.py:98-113, which has no packing step).  mixed_tile_* are the three extra Winograd weight
  * sets of the exact 14x14 tiling: derived on the device the first time a batch large enough to use them arrives
