@@ -113,6 +113,8 @@ struct ffr_handle {
     std::vector<hipEvent_t> ev_pool;
     // RecNet training state (train.cpp), or null
     ffr_eng::TrainState* train = nullptr;
+    // weight-gradient launch plans of the most recent backward (ffr_train_wgrad_plan)
+    std::vector<ffr_wgrad_launch> wgrad_log;
     // bumped whenever device memory a caller may have captured (hipGraph) is released: workspace regrowth, weight
     // reload, ffr_train_init
     unsigned long long generation = 1;

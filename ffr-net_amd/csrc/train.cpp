@@ -20,6 +20,7 @@ const float BN_MOMENTUM = 0.1f, BN_EPS_F = 1e-5f;
 // One ConvLayer (reflect-pad -> conv3x3 no bias -> BatchNorm2d -> PReLU) in training form.
 // Weights stay in the kernel layout [cout_pad][9][cin_pad] (no BN fold: the statistics are the batch's).
 struct TLayer {
+    std::string name = "op";                       // state_dict prefix (the weight-gradient plan record)
     int cin = 0, cin_pad = 0, cout = 0, cout_pad = 0;
     float *w = nullptr, *gamma = nullptr, *beta = nullptr, *slope = nullptr;      // parameters
     float *gw = nullptr, *ggamma = nullptr, *gbeta = nullptr, *gslope = nullptr;  // gradients
@@ -52,6 +53,16 @@ struct TScratch {
 int gemm_rows(ffr_handle* h, const Work& w, const float* A, int a_pitch, int K_pad, const float* W, const float* bias,
               int N_pad, float* out, int out_pitch, long long rows, const float* resid, int res_pitch, int flags,
               hipStream_t st);
+
+// one entry of the weight-gradient plan record (ffr_train_wgrad_plan): the launcher's arguments as it ran them
+void log_wgrad(ffr_handle* h, const std::string& name, int path, const WgradArgs& a, int accumulate) {
+    ffr_wgrad_launch r{};
+    snprintf(r.name, sizeof r.name, "%s", name.c_str());
+    r.path = path; r.rows = a.rows; r.cout_pad = a.cout_pad; r.Ng = a.Ng; r.nbatch = a.nbatch; r.nkt = a.nkt;
+    r.splits = a.splits; r.kt_per_split = a.kt_per_split;
+    r.full_tiles = a.full_tiles; r.tail_splits = a.tail_splits; r.tail_kt = a.tail_kt; r.accumulate = accumulate;
+    h->wgrad_log.push_back(r);
+}
 
 int gemm_batched(ffr_handle* h, const Work& w, const float* A, long long a_bstride, int K_pad, const float* W,
                  long long w_bstride, int N_pad, float* out, int out_pitch, long long out_bstride, int M, int nbatch,
@@ -118,7 +129,9 @@ int layer_backward(ffr_handle* h, const Work& w, const TLayer& L, const TSaved& 
             const double fx = 2.0 * 36.0 * (double)T * L.cout_pad * L.cin_pad;
             Scope sc(h, st, FFR_KC_WGRAD, 2.0 * rows * 9.0 * L.cout * L.cin, 4.0 * 36.0 * T * (L.cout_pad + L.cin_pad), fx,
                      2.0 * rows * 9.0 * L.cout * L.cin / 4.0);
-            HIPCK(h, launch_wgrad_batched(a, s.U, 36, T * L.cout_pad, T * L.cin_pad, s.slabs, s.slab_floats, st));
+            WgradArgs pl{};
+            HIPCK(h, launch_wgrad_batched(a, s.U, 36, T * L.cout_pad, T * L.cin_pad, s.slabs, s.slab_floats, st, &pl));
+            log_wgrad(h, L.name, 2, pl, 0);
         }
         TLAUNCH(FFR_KC_TRAIN_XFORM, launch_wino_dweights(s.U, L.gw, L.cout_pad, L.cin_pad, accumulate, st));
     } else {
@@ -127,7 +140,9 @@ int layer_backward(ffr_handle* h, const Work& w, const TLayer& L, const TSaved& 
         a.dy_pitch = L.cout_pad; a.cin_pad = L.cin_pad; a.taps = 9; a.pad_mode = 1; a.cout_pad = L.cout_pad;
         const double fx = 2.0 * rows * 9.0 * L.cout_pad * L.cin_pad;
         Scope sc(h, st, FFR_KC_WGRAD, 2.0 * rows * 9.0 * L.cout * L.cin, 4.0 * rows * (L.cout_pad + L.cin_pad), fx);
-        HIPCK(h, launch_wgrad(a, L.gw, accumulate, s.slabs, s.slab_floats, st));
+        WgradArgs pl{};
+        HIPCK(h, launch_wgrad(a, L.gw, accumulate, s.slabs, s.slab_floats, st, &pl));
+        log_wgrad(h, L.name, 0, pl, accumulate);
     }
     if (!dx) return FFR_OK;
     const int need_pad = round_up(cin_need, 64);
@@ -269,6 +284,7 @@ struct Seg {
 };
 
 struct Lin {
+    std::string name;                       // state_dict prefix (the weight-gradient plan record)
     int in = 0, out = 0, in_pad = 0, out_pad = 0;
     float *w = nullptr, *b = nullptr, *gw = nullptr, *gb = nullptr;
 };
@@ -526,7 +542,9 @@ int lin_backward(ffr_handle* h, TrainState* t, const Work& w, const Lin& ln, con
     a.cin_pad = ln.in_pad; a.taps = 1; a.pad_mode = 0; a.cout_pad = ln.out_pad;
     {
         Scope sc(h, st, FFR_KC_WGRAD, 2.0 * rows * ln.out * ln.in, 4.0 * rows * (ln.out_pad + ln.in_pad), 2.0 * rows * ln.out_pad * ln.in_pad);
-        HIPCK(h, launch_wgrad(a, ln.gw, 1, t->sc.slabs, t->sc.slab_floats, st));
+        WgradArgs pl{};
+        HIPCK(h, launch_wgrad(a, ln.gw, 1, t->sc.slabs, t->sc.slab_floats, st, &pl));
+        log_wgrad(h, ln.name, 1, pl, 1);
     }
     TLAUNCH(FFR_KC_TRAIN_ELEM, launch_colsum(dy, dy_pitch, (int)rows, ln.out_pad, ln.gb, 1, t->sc.part, st));
     if (dx) {
@@ -544,6 +562,7 @@ int train_backward(ffr_handle* h, TrainState* t, Ctx& c, const Work& w, const Ou
     const int G = c.G, N = c.N, imgs = G * N, rows = imgs * 49;
     const long long crow = (long long)imgs * 512;
     TScratch& s = t->sc;
+    h->wgrad_log.clear();
     auto LB = [&](const TLayer& Ly, const TSaved& sv, const float* da, int da_pitch, int da_coff, float* dx, int dx_pitch,
                   int width, const float* add, int add_pitch, int add_coff) -> int {
         return layer_backward(h, w, Ly, sv, G, N, da, da_pitch, da_coff, 1, s, dx, dx_pitch, 0, width, add, add_pitch, add_coff, st);
@@ -560,7 +579,9 @@ int train_backward(ffr_handle* h, TrainState* t, Ctx& c, const Work& w, const Ou
         a.cin_pad = 512; a.taps = 1; a.pad_mode = 0; a.cout_pad = CLS_PAD;
         {
             Scope sc(h, st, FFR_KC_WGRAD, 2.0 * imgs * 512.0 * N_CLASSES, 4.0 * imgs * (CLS_PAD + 512.0), 2.0 * imgs * 512.0 * CLS_PAD);
-            HIPCK(h, launch_wgrad(a, t->dwn, 0, s.slabs, s.slab_floats, st));
+            WgradArgs pl{};
+            HIPCK(h, launch_wgrad(a, t->dwn, 0, s.slabs, s.slab_floats, st, &pl));
+            log_wgrad(h, "classifier", 1, pl, 0);
         }
         TLAUNCH(FFR_KC_TRAIN_LOSS, launch_normalize_bwd(t->dwn, 512, c.wn, c.wnorm, nullptr, t->gclsW, 512, 1, N_CLASSES, st));
         TLAUNCH(FFR_KC_TRAIN_LOSS, launch_normalize_bwd(t->dfn, 512, c.fn, c.fnorm, df_in, t->df, 512, 0, imgs, st));
@@ -600,6 +621,7 @@ int train_backward(ffr_handle* h, TrainState* t, Ctx& c, const Work& w, const Ou
     // a folded pair: gradient of the 32x32 product, then its adjoint onto the two linears
     auto pair_backward = [&](int q, const Lin& lb, const Lin& la, const float* dy, const float* x, float* dx) -> int {
         Lin f;
+        f.name = "Conv4Channel.fold" + std::to_string(q);
         f.in = 32; f.out = 32; f.in_pad = 32; f.out_pad = 64; f.w = t->foldA[q]; f.b = t->foldd[q]; f.gw = t->gfoldA; f.gb = t->gfoldd;
         HIPCK(h, hipMemsetAsync(t->gfoldA, 0, 64 * 32 * sizeof(float), st));
         HIPCK(h, hipMemsetAsync(t->gfoldd, 0, 64 * sizeof(float), st));
@@ -722,6 +744,8 @@ int ffr_op_convlayer_train(ffr_handle* h, const float* x_nhwc, int G, int N, int
     RC(dev_alloc_t(h, own, (size_t)rows * L.cout_pad, &sv.y));
     RC(alloc_bn(h, own, G, L.cout_pad, &sv.bn));
     TScratch s;
+    if (h->train) { s.wino = h->train->sc.wino; s.fused = h->train->sc.fused; }     // ffr_train_option, when a training state exists
+    h->wgrad_log.clear();
     RC(dev_alloc_t(h, own, bn_part_doubles(G, N * 49, L.cout_pad), &s.part));
     const int need_pad = round_up(cin, 64);
     s.wd_floats = (size_t)need_pad * 9 * L.cout_pad; RC(dev_alloc_t(h, own, s.wd_floats, &s.wd));
@@ -758,6 +782,7 @@ int ffr_train_init(ffr_handle* h, const ffr_tensor_desc* td, int n) {
     auto def_layers = [&](const LayerDef* defs, int cnt, TLayer* out) {
         for (int i = 0; i < cnt; ++i) {
             TLayer& L = out[i];
+            L.name = defs[i].p;
             L.cin = defs[i].cin; L.cout = defs[i].cout; L.cin_pad = round_up(L.cin, 32); L.cout_pad = round_up(L.cout, 64);
             const std::string p = defs[i].p;
             add_seg(t, p + ".conv2d.weight", SEG_CONV, L.cout, L.cin, L.cout_pad, L.cin_pad);
@@ -778,6 +803,7 @@ int ffr_train_init(ffr_handle* h, const ffr_tensor_desc* td, int n) {
         Lin& l = t->lin[i];
         l.in = LIN_IN[i]; l.out = LIN_OUT[i]; l.in_pad = round_up(l.in, 32); l.out_pad = round_up(l.out, 64);
         const std::string p = "Conv4Channel." + std::to_string(LIN_IDX[i]);
+        l.name = p;
         add_seg(t, p + ".weight", SEG_LIN, l.out, l.in, l.out_pad, l.in_pad, i == 0 ? 1 : 0);
         add_seg(t, p + ".bias", SEG_VEC, l.out, 1, l.out_pad, 1);
     }
@@ -1026,6 +1052,13 @@ int ffr_train_bucket_wait(ffr_handle* h, int i, void* stream) {
     FFR_DEVICE_SCOPE(h); RC(get_train(h, &t));
     if (i < 0 || i >= TrainState::NBUCKET) return fail(h, FFR_ERR_ARG, "ffr_train_bucket_wait: bad bucket");
     HIPCK(h, hipStreamWaitEvent((hipStream_t)stream, t->bucket_ev[i], 0));
+    return FFR_OK;
+}
+
+int ffr_train_wgrad_plan(ffr_handle* h, ffr_wgrad_launch* out, int max, int* n) {
+    if (!h || !n || max < 0 || (max > 0 && !out)) return fail(h, FFR_ERR_ARG, "ffr_train_wgrad_plan: bad arguments");
+    *n = (int)h->wgrad_log.size();
+    for (int i = 0; i < *n && i < max; ++i) out[i] = h->wgrad_log[i];
     return FFR_OK;
 }
 

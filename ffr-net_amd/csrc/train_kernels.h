@@ -25,14 +25,15 @@ struct WgradArgs {
     int full_tiles, tail_splits, tail_kt;
     float* tail_out;
 };
-// grad[cout_pad][taps*cin_pad] (+)= dy^T * gather(x); scratch holds the split-K slabs
+// grad[cout_pad][taps*cin_pad] (+)= dy^T * gather(x); scratch holds the split-K slabs.
+// planned (may be null): the arguments as launched (Ng .. tail_kt filled in by the planner)
 hipError_t launch_wgrad(WgradArgs a, float* grad, int accumulate, float* scratch, size_t scratch_floats,
-                        hipStream_t stream);
+                        hipStream_t stream, WgradArgs* planned = nullptr);
 
 // out[b][cout_pad][cin_pad] = dy[b]^T x[b] for b < nbatch (taps = 1, H = W = 1, plain rows); split-K through
 // `scratch` only when the launch would under-fill the chip
 hipError_t launch_wgrad_batched(WgradArgs a, float* out, int nbatch, long long dy_bstride, long long x_bstride,
-                                float* scratch, size_t scratch_floats, hipStream_t stream);
+                                float* scratch, size_t scratch_floats, hipStream_t stream, WgradArgs* planned = nullptr);
 
 // ---- BatchNorm (batch statistics) + PReLU, forward and backward (train_ops.hip) -------------------
 struct BnBuffers {       // per layer, [G][Cp] floats each unless noted

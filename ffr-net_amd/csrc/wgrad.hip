@@ -306,7 +306,7 @@ static void wgrad_dispatch(const WgradArgs& a, int bm, int bn, unsigned grid, bo
 }
 
 hipError_t launch_wgrad(WgradArgs a, float* grad, int accumulate, float* scratch, size_t scratch_floats,
-                        hipStream_t stream) {
+                        hipStream_t stream, WgradArgs* planned) {
     if (a.cout_pad % 64 || a.cin_pad % 4 || (a.taps != 1 && a.taps != 9) || a.rows <= 0) return hipErrorInvalidValue;
     a.Ng = a.taps * a.cin_pad;
     if (a.Ng % 4) return hipErrorInvalidValue;
@@ -332,6 +332,7 @@ hipError_t launch_wgrad(WgradArgs a, float* grad, int accumulate, float* scratch
     a.full_tiles = 0; a.tail_splits = 0; a.tail_kt = 0; a.tail_out = nullptr;
     if (a.taps == 1 && a.H == 1 && a.W == 1 && ((double)a.rows * a.dy_pitch * 4.0 >= 2147483648.0 || (double)a.rows * a.x_pitch * 4.0 >= 2147483648.0))
         return hipErrorInvalidValue;           // plain operands are read through 32-bit buffer offsets
+    if (planned) *planned = a;
     const unsigned grid = (unsigned)(tiles * splits);
     wgrad_dispatch(a, bm, bn, grid, a.taps == 1 && a.H == 1 && a.W == 1, stream);
     const long long n4 = (long long)per / 4;
@@ -343,7 +344,7 @@ hipError_t launch_wgrad(WgradArgs a, float* grad, int accumulate, float* scratch
 // dU[xi] = dM[xi]^T V[xi].  Launches that would leave the chip under-filled are cut along K into slabs
 // scratch[split][b][..] that k_wgrad_reduce adds in order; otherwise the result is written to `out` directly.
 hipError_t launch_wgrad_batched(WgradArgs a, float* out, int nbatch, long long dy_bstride, long long x_bstride,
-                                float* scratch, size_t scratch_floats, hipStream_t stream) {
+                                float* scratch, size_t scratch_floats, hipStream_t stream, WgradArgs* planned) {
     if (a.cout_pad % 64 || a.cin_pad % 4 || a.taps != 1 || a.rows <= 0 || nbatch <= 0 || a.H != 1 || a.W != 1)
         return hipErrorInvalidValue;
     a.Ng = a.cin_pad;
@@ -381,12 +382,14 @@ hipError_t launch_wgrad_batched(WgradArgs a, float* out, int nbatch, long long d
             a.tail_kt = (a.nkt + ts - 1) / ts;
             a.tail_splits = (a.nkt + a.tail_kt - 1) / a.tail_kt;
             a.tail_out = scratch;
+            if (planned) *planned = a;
             wgrad_dispatch(a, bm, 128, (unsigned)(full + tail * a.tail_splits), true, stream);
             if (bm == 128) hipLaunchKernelGGL((k_wgrad_tail_reduce<128, 128>), dim3((unsigned)tail * 16), dim3(256), 0, stream, a);
             else hipLaunchKernelGGL((k_wgrad_tail_reduce<64, 128>), dim3((unsigned)tail * 8), dim3(256), 0, stream, a);
             return hipGetLastError();
         }
     }
+    if (planned) *planned = a;
     const unsigned grid = (unsigned)(blocks * splits);
     wgrad_dispatch(a, bm, 128, grid, true, stream);
     if (splits > 1) {

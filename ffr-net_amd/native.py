@@ -52,6 +52,13 @@ class LayerInfo(C.Structure):
     _fields_ = [('name', C.c_char * 64), ('net', C.c_int), ('arith', C.c_int), ('sensitivity', C.c_double)]
 
 
+class WgradLaunch(C.Structure):
+    _fields_ = [('name', C.c_char * 48)] + [(f, C.c_int) for f in (
+        'path', 'rows', 'cout_pad', 'Ng', 'nbatch', 'nkt', 'splits', 'kt_per_split', 'full_tiles', 'tail_splits', 'tail_kt',
+        'accumulate')]
+
+
+WGRAD_PATHS = ('plain-taps9', 'plain-taps1', 'batched')
 ARITH = {'direct': 0, 'winograd': 1}
 CALIB_TENSORS = ('f', 'featmap', 'f_new', 'feat_new')
 
@@ -117,6 +124,7 @@ SYMBOLS = [
     ('ffr_train_adam_step', C.c_int, [_P, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _P]),
     ('ffr_train_debug_copy', C.c_int, [_P, C.c_int, C.c_char_p, _P, C.c_size_t]),
     ('ffr_train_option', C.c_int, [_P, C.c_char_p, C.c_int]),
+    ('ffr_train_wgrad_plan', C.c_int, [_P, C.POINTER(WgradLaunch), C.c_int, C.POINTER(C.c_int)]),
     ('ffr_train_buckets', C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
     ('ffr_train_bucket_wait', C.c_int, [_P, C.c_int, _P]),
     ('ffr_train_export', C.c_int, [_P, C.c_int, C.c_char_p, _P, _P]),
@@ -684,6 +692,22 @@ class Engine(object):
     def train_debug(self, name, shape, slot=0):
         out = torch.empty(shape, dtype=torch.float32)
         self._ck(self.lib.ffr_train_debug_copy(self._h, slot, name.encode(), C.c_void_p(out.data_ptr()), out.numel()))
+        return out
+
+    def train_wgrad_plan(self):
+        """The weight-gradient launches of the most recent backward (training backward or op_convlayer_train), in launch
+        order (test hook): [{layer, name, path ('plain-taps9' | 'plain-taps1' | 'batched'), rows, cout_pad, Ng, nbatch, nkt,
+        splits, kt_per_split, full_tiles, tail_splits, tail_kt, accumulate}], layer = position in the backward."""
+        n = C.c_int(0)
+        self._ck(self.lib.ffr_train_wgrad_plan(self._h, None, 0, C.byref(n)))
+        arr = (WgradLaunch * max(n.value, 1))()
+        self._ck(self.lib.ffr_train_wgrad_plan(self._h, arr, n.value, C.byref(n)))
+        out = []
+        for i in range(n.value):
+            r = arr[i]
+            d = {f: getattr(r, f) for f, _ in WgradLaunch._fields_[1:]}
+            d.update(layer=i, name=r.name.decode(), path=WGRAD_PATHS[r.path])
+            out.append(d)
         return out
 
     def train_adam_step(self, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, clip_value=1.0):

@@ -27,7 +27,8 @@ extern "C" {
  *   dw_packed [cout_pad][9][cin_pad] weight gradient in the kernel layout (tap = r*3+s)
  *   dvec [5][cout_pad]: dgamma, dbeta, dslope, running_mean, running_var (running stats start at 0)
  *   stats [2][G][cout_pad]: batch mean, 1/sqrt(var+eps) per group
- * G groups of N images are separate BatchNorm batches.  Synchronises the stream before returning. */
+ * G groups of N images are separate BatchNorm batches.  Runs under the handle's "winograd" and "fused" training options
+ * (ffr_train_option) when it has a training state, under their defaults otherwise.  Synchronises the stream before returning. */
 int ffr_op_convlayer_train(ffr_handle* h, const float* x_nhwc, int G, int N, int cin, int cout,
                            const float* w_host, const float* gamma_host, const float* beta_host,
                            const float* slope_host, const float* da_nhwc, float* out_nhwc, float* dx_nhwc,
@@ -130,6 +131,25 @@ int ffr_train_option(ffr_handle* h, const char* name, int value);
  * "shift.<layer>" the batch-norm scale and shift [G][cout_pad] -- the PReLU pre-activation is y * scale + shift)
  * copied to host memory, in the kernel layouts.  Synchronises the device.                                       */
 int ffr_train_debug_copy(ffr_handle* h, int slot, const char* name, float* host_out, size_t n);
+
+/* Test hook: the plan of every weight-gradient launch of the handle's most recent backward (ffr_train_backward,
+ * ffr_train_backward_losses, ffr_train_iteration or ffr_op_convlayer_train), in launch order, as the launcher ran it.
+ * path: 0 direct 3x3 (taps 9, reflect-gathered rows), 1 plain rows (taps 1: the Linear layers, the classifier), 2 batched
+ * (the 36 Winograd-domain products dU = dM^T V of a ConvLayer).  splits > 1: split-K slabs added by a reduction;
+ * tail_splits > 0: blocks [full_tiles, ...) of a batched launch are cut along K into tail_splits slabs of tail_kt K-tiles. */
+typedef struct {
+    char name[48];       /* the layer's state_dict prefix ("Conv4Merge.1.conv2", "Conv4Channel.8", "classifier"); a folded
+                            Conv4Channel pair "Conv4Channel.fold0" / ".fold1"; "op" for ffr_op_convlayer_train              */
+    int  path;
+    int  rows;           /* reduction length: image rows (path 0, 1) or Winograd tiles (path 2)                            */
+    int  cout_pad, Ng;   /* output rows and columns of one product (Ng = taps * cin_pad)                                   */
+    int  nbatch, nkt;    /* products per launch, K-tiles of 32 rows                                                        */
+    int  splits, kt_per_split;
+    int  full_tiles, tail_splits, tail_kt;
+    int  accumulate;     /* 1: added to the gradient buffer, 0: overwrites it (path 2 writes dU, always 0)                  */
+} ffr_wgrad_launch;
+/* *n = the number of launches; the first min(*n, max) are copied to out (may be NULL with max = 0).  Host only. */
+int ffr_train_wgrad_plan(ffr_handle* h, ffr_wgrad_launch* out, int max, int* n);
 
 #ifdef __cplusplus
 }

@@ -69,6 +69,114 @@ def test_convlayer_train_forward_backward(engine, case):
     assert rel(res['dslope'], sr.grad) < GRAD_TOL
 
 
+# The weight-gradient launchers (csrc/wgrad.hip) choose split-K and the tail split from the row count, so their branches only
+# run at production batches.  Each case names the branch it must reach; the plan record (Engine.train_wgrad_plan) proves it ran.
+#   (G, N, cin, cout, winograd, branch)
+#   plain-1       launch_wgrad, one slab                        plain-ragged  launch_wgrad, splits > 1, short last split
+#   bat-split     batched, split-K (36 .. 360 blocks)            bat-1         batched, one slab, no tail split
+#   tail-<ts>     batched, tail split of ts slabs (+ 'short': the last tail slab has fewer K-tiles)
+WGRAD_CASES = [
+    (1, 3, 49, 49, 1, 'plain-1'),                    # 147 rows
+    (2, 65, 49, 49, 1, 'plain-ragged'),              # 6370 rows; BatchNorm: 32 slices of 100 rows, the last 85
+    (2, 64, 256, 256, 0, 'plain-ragged'),            # direct at cin_pad >= 128; BatchNorm: 32 slices of exactly 98 rows
+    (2, 64, 256, 256, 1, 'bat-split'),               # the same layer in the Winograd domain
+    (2, 64, 128, 49, 1, 'bat-split'),                # 36 blocks
+    (2, 128, 256, 128, 1, 'bat-split'),              # 72 blocks
+    (2, 128, 561, 256, 1, 'bat-split-ragged'),       # Conv4Space.0: 360 blocks, 32 K-tiles in 3 splits of 11
+    (2, 128, 512, 512, 1, 'tail-8'),                 # ChannelFlipMerge.1 / Conv4Merge.1: 576 blocks
+    (2, 150, 512, 512, 1, 'tail-8-short'),           # 1200 tiles: 38 K-tiles, tail slabs of 5, the last 3
+    (2, 128, 1024, 512, 1, 'tail-4'),                # ChannelFlipMerge.0: 1152 blocks
+    (2, 122, 1536, 512, 1, 'tail-2-short'),          # Conv4Merge.0: 1728 blocks, 31 K-tiles in tail slabs of 16 and 15
+    (1, 2, 2048, 1024, 1, 'bat-1'),                  # 4608 blocks = 9 x 512: whole rounds, no tail
+    (2, 1, 256, 256, 1, 'bat-1'),                    # one image per BatchNorm batch, 8 tiles
+]
+
+
+def check_wgrad_branch(p, branch):
+    """The single plan entry `p` of an op_convlayer_train backward took `branch` (WGRAD_CASES)."""
+    if branch.startswith('plain'):
+        assert p['path'] == 'plain-taps9' and p['tail_splits'] == 0, p
+        if branch == 'plain-1':
+            assert p['splits'] == 1, p
+        else:
+            assert p['splits'] > 1 and p['nkt'] % p['kt_per_split'] != 0, p
+        return
+    assert p['path'] == 'batched' and p['nbatch'] == 36, p
+    if branch.startswith('bat-split'):
+        assert p['splits'] > 1 and p['tail_splits'] == 0, p
+        if branch.endswith('ragged'):
+            assert p['nkt'] % p['kt_per_split'] != 0, p
+    elif branch == 'bat-1':
+        assert p['splits'] == 1 and p['tail_splits'] == 0, p
+    else:
+        ts = int(branch.split('-')[1])
+        assert p['splits'] == 1 and p['tail_splits'] == ts and p['full_tiles'] % 512 == 0, p
+        assert (p['nkt'] - (ts - 1) * p['tail_kt'] < p['tail_kt']) == branch.endswith('short'), p
+
+
+def convlayer_reference(x, w, gamma, beta, slope, da, G, device, mask):
+    """models/recnet.py:78-85 in train() mode, one BatchNorm batch per group, by torch autograd in float64 on `device`, with
+    every PReLU element on the side `mask` [G*N,7,7,cout] says (True = identity; see "PReLU kinks" below).
+    x [G*N,7,7,cin], da [G*N,7,7,cout] (NHWC).  -> dict of the op_convlayer_train results and the pre-activation z, float64
+    on the CPU."""
+    f64 = dict(device=device, dtype=torch.float64)
+    mask = mask.permute(0, 3, 1, 2).to(device)
+    xr = x.permute(0, 3, 1, 2).to(**f64).requires_grad_(True)
+    wr, gr, br, sr = (t.to(**f64).requires_grad_(True) for t in (w, gamma, beta, slope))
+    rm, rv = torch.zeros(w.size(0), **f64), torch.zeros(w.size(0), **f64)
+    n = x.size(0) // G
+    outs = []
+    for gi in range(G):
+        y = F.conv2d(F.pad(xr[gi * n:(gi + 1) * n], (1,) * 4, mode='reflect'), wr)
+        outs.append(F.batch_norm(y, rm, rv, gr, br, True, 0.1, 1e-5))
+    z = torch.cat(outs)
+    out = torch.where(mask, z, z * sr.view(1, -1, 1, 1))
+    out.backward(da.permute(0, 3, 1, 2).to(**f64))
+    return {k: v.detach().cpu() for k, v in dict(out=out.permute(0, 2, 3, 1), z=z.permute(0, 2, 3, 1), running_mean=rm, running_var=rv,
+                                                  dx=xr.grad.permute(0, 2, 3, 1), dw=wr.grad, dgamma=gr.grad, dbeta=br.grad,
+                                                  dslope=sr.grad).items()}
+
+
+@pytest.mark.parametrize('case', WGRAD_CASES, ids=['%dx%d-%d-%d-w%d-%s' % c for c in WGRAD_CASES])
+def test_convlayer_train_wgrad_branches(engine, specs, case):
+    """Every branch of the weight-gradient launchers and of the BatchNorm backward's slicing, at the RecNet shapes and the
+    128-pair batch where they arise, against torch autograd in float64 (on the device): outputs, running statistics, data
+    gradient and all four parameter gradients.  The plan record must show the branch the case names.  At these sizes a
+    Winograd forward (2e-5 .. 4e-5 from float64) puts a few of the 6.4 M PReLU inputs on the other side of zero, so the
+    reference takes the GPU's side of every kink (the sign of the output) and each element whose side differs from its own
+    must lie within the forward tolerance of zero: 2e-5 direct, 1e-4 Winograd, as for the whole network below."""
+    G, N, cin, cout, wino, branch = case
+    engine.train_init(synth.synth_state_dict(specs['recnet'], seed=0))     # op_convlayer_train follows the training options
+    engine.train_option('winograd', wino)
+    g = torch.Generator().manual_seed(1000 + 7 * N + cin + cout)
+    x = torch.randn(G * N, 7, 7, cin, generator=g)
+    w = torch.randn(cout, cin, 3, 3, generator=g) / (cin * 9) ** 0.5
+    gamma = torch.rand(cout, generator=g) * 0.5 + 0.75
+    beta = torch.randn(cout, generator=g) * 0.1
+    slope = torch.rand(cout, generator=g) * 0.3 + 0.1
+    da = torch.randn(G * N, 7, 7, cout, generator=g)
+    try:
+        res = engine.op_convlayer_train(x.cuda(), G, w, gamma, beta, slope, da.cuda())
+        torch.cuda.synchronize()
+        plan = engine.train_wgrad_plan()
+    finally:
+        engine.train_option('winograd', 1)
+    assert len(plan) == 1 and plan[0]['name'] == 'op', plan
+    check_wgrad_branch(plan[0], branch)
+    mask = (res['out'] > 0).cpu()
+    ref = convlayer_reference(x, w, gamma, beta, slope, da, G, engine.device, mask)
+    z = ref.pop('z')
+    flipped = mask != (z > 0)
+    margin = (z[flipped].abs().max() / z.abs().max()).item() if flipped.any() else 0.0
+    errs = {k: rel(res[k], ref[k]) for k in ref}
+    print(branch, plan[0], '%d kinks transplanted (margin %.1e)' % (int(flipped.sum()), margin),
+          ' '.join('%s %.1e' % kv for kv in errs.items()))
+    fwd_tol = 1e-4 if branch.startswith(('bat', 'tail')) else 2e-5
+    assert margin < fwd_tol, (int(flipped.sum()), margin)
+    for k, e in errs.items():
+        assert e < (fwd_tol if k == 'out' else 2e-5 if k.startswith('running') else GRAD_TOL), (k, e)
+
+
 # ---- PReLU kinks ------------------------------------------------------------------------------------------
 # RecNet has 2.1 M PReLU inputs in an 8-image step; a forward that differs from the reference's by 1e-5 (F(4x4,3x3) in fp32,
 # another encoder) puts a few dozen of them on the other side of zero, and each such element changes its own gradient by
@@ -99,13 +207,18 @@ def gpu_kink_masks(eng, groups, n, slot=0):
     return masks
 
 
-def oracle_grads_on_masks(sd_r, fm, f_enc, label, masks, n):
+def oracle_grads_on_masks(sd_r, fm, f_enc, label, masks, n, device='cpu', dtype=torch.float32):
     """The oracle's parameter gradients of Trainer.backward's loss with every PReLU element on the side `masks` says
-    (None: its own side).  fm / f_enc: [2 n, ...] clean then occluded.  -> ({key: grad}, natural pre-activations, items)"""
+    (None: its own side).  fm / f_enc: [2 n, ...] clean then occluded.  Evaluated on `device` in `dtype` (weights, feature
+    maps, embeddings converted).  -> ({key: grad}, natural pre-activations, items), tensors on `device`"""
     import ffr_oracle_train as OT
     keys = OT.trainable_keys(sd_r)
-    params = {k: sd_r[k].clone().requires_grad_(True) for k in keys}
-    running = {k: v.clone() for k, v in sd_r.items() if k not in params}
+    conv = dict(device=device, dtype=dtype)
+    fm, f_enc, label = fm.to(**conv), f_enc.to(**conv), label.to(device)
+    masks = {k: m.to(device) for k, m in masks.items()} if masks else masks
+    params = {k: sd_r[k].to(**conv, copy=True).requires_grad_(True) for k in keys}
+    running = {k: v.to(**conv, copy=True) if v.is_floating_point() else v.to(device, copy=True) for k, v in sd_r.items()
+               if k not in params}
     ctl = [{'mask': {k: m[:n] for k, m in masks.items()}} if masks else {}, {'mask': {k: m[n:] for k, m in masks.items()}} if masks else {}]
     out_non = OT.recnet_train_forward(params, fm[:n], label, running, ctl[0])
     out_ocl = OT.recnet_train_forward(params, fm[n:], label, running, ctl[1])
@@ -496,9 +609,10 @@ def test_native_loss_items_and_their_gradients(engine, train_case):
 
 
 def test_training_full_size_properties(specs):
-    """BASELINE configs[4] per-GPU shape (128 pairs per iteration), where the oracle is too slow: properties.
+    """BASELINE configs[4] per-GPU shape (128 pairs per iteration), whole iterations with the encoder: properties.
     Bitwise reproducibility of a whole iteration, direct vs Winograd mode agree on the loss items, a few Adam steps
-    on a fixed batch lower the total loss, everything stays finite."""
+    on a fixed batch lower the total loss, everything stays finite.  The per-tensor values at this shape are held to the
+    oracle by test_train_backward_full_size_per_tensor."""
     sd_e = synth.synth_state_dict(specs['encoder'], seed=0)
     sd_r = synth.synth_state_dict(specs['recnet'], seed=0)
     non, ocl, label = synth.synth_train_batch(128, seed=77)
@@ -592,6 +706,64 @@ def test_train_forward_full_size_values(specs):
             for name, got, want in zip(names, outs, ref):
                 got = got[128 * g:128 * (g + 1)]
                 assert rel(got.reshape(want.shape), want) < 2e-4, (g, name, rel(got.reshape(want.shape), want))
+
+
+def test_train_backward_full_size_per_tensor(specs):
+    """BASELINE configs[4] per-GPU shape, 128 pairs: the iteration's kernels without the encoder (train_forward ->
+    train_losses -> train_zero_grad -> train_backward_losses) on the native encoder's feature maps and embeddings, held
+    per tensor to the oracle's autograd in float64 on the device, on the GPU's side of every PReLU kink ("PReLU kinks"
+    above), in both arithmetics.  The weight-gradient plan record must show the branches that only this size reaches
+    (tail split, batched split-K, split plain launches), so that a heuristic change cannot silently drop them."""
+    import ffr_oracle_train as OT
+    n = 128
+    oracle = dict(device=torch.device('cuda', 0), dtype=torch.float64)
+    sd_e = synth.synth_state_dict(specs['encoder'], seed=0)
+    sd_r = synth.synth_state_dict(specs['recnet'], seed=0)
+    non, ocl, label = synth.synth_train_batch(n, seed=79)
+    eng = ffrnet_amd.Engine(0)
+    eng.load_encoder(sd_e)
+    with torch.no_grad():
+        fm, f_enc = eng.encoder_forward(torch.cat((non, ocl)).cuda())
+    lab = label.cuda()
+    keys = OT.trainable_keys(sd_r)
+    _, pre, _ = oracle_grads_on_masks(sd_r, fm, f_enc, lab, None, n, **oracle)
+    # accuracy of the occluded half: classes whose cosines the oracle separates by less than 1e-5 may swap
+    with torch.no_grad():
+        cos = OT.recnet_train_forward({k: v.to(**oracle) for k, v in sd_r.items()}, fm[n:].to(**oracle), lab, None)[2]
+        top2 = cos.topk(2, dim=1).values
+        hits = int((cos.argmax(1) == lab).sum())
+        near_ties = int(((top2[:, 0] - top2[:, 1]) < 1e-5).sum())
+    for mode, fwd_tol in ((1, 1e-4), (0, 1e-5)):
+        eng.train_init(sd_r)
+        eng.train_option('winograd', mode)
+        eng.train_forward(fm, torch.cat((lab, lab)), groups=2, want=())
+        out5 = eng.train_losses(f_enc).cpu()
+        masks = gpu_kink_masks(eng, 2, n)
+        flipped = check_kinks({k: m.to(oracle['device']) for k, m in masks.items()}, pre, fwd_tol)
+        eng.train_zero_grad()
+        eng.train_backward_losses()
+        torch.cuda.synchronize()
+        plan = eng.train_wgrad_plan()
+        ref, _, items = oracle_grads_on_masks(sd_r, fm, f_enc, lab, masks, n, **oracle)
+        assert np.allclose(out5[:4].numpy(), items, rtol=1e-4), (mode, out5, items)
+        assert abs(round(float(out5[4]) * n) - hits) <= near_ties, (mode, float(out5[4]), hits, near_ties)
+        errs = {k: grad_err(eng.train_get(k, 'grad'), ref[k].cpu()) for k in keys}
+        worst = max(errs, key=errs.get)
+        print('128 pairs, winograd=%d: %d kinks transplanted (all within %.0e of zero), worst gradient error %.2e (%s)'
+              % (mode, flipped, fwd_tol, errs[worst], worst))
+        for k in keys:
+            assert errs[k] < 1e-4, (mode, k, errs[k])
+        # the plan: every ConvLayer, Linear and the classifier once, in backward order
+        convs = [p for p in plan if not p['name'].startswith(('Conv4Channel', 'classifier'))]
+        assert plan[0]['name'] == 'classifier' and len(convs) == 15 and convs[-1]['name'] == 'Conv4Space.0', plan
+        if mode == 1:
+            assert any(p['path'] == 'batched' and p['tail_splits'] > 0 for p in plan), plan
+            assert any(p['path'] == 'batched' and p['splits'] > 1 for p in plan), plan
+            assert any(p['path'] == 'plain-taps9' and p['splits'] > 1 for p in plan), plan
+            assert any(p['path'] == 'plain-taps1' and p['splits'] > 1 for p in plan), plan
+        else:
+            assert all(p['path'] == 'plain-taps9' and p['splits'] > 1 for p in convs), plan
+    eng.train_option('winograd', 1)
 
 
 @pytest.mark.parametrize('n', [1, 3])
