@@ -181,56 +181,65 @@ bool block_table(int n_blocks, std::vector<int>& cin, std::vector<int>& depth, s
 }
 
 // ---- convolution dispatch --------------------------------------------------------------
-// Which form of k_wino_fused a Winograd convolution of T tiles takes: 0 = none (transform kernels + batched GEMM),
-// 1 = blocks of 32 tiles x 64 channels, 2 = blocks of 32 tiles x 32 channels.  wino_mode as in ConvCall.
-int wino_fused_choice(const ffr_handle* h, int cin_pad, int cout_pad, long long T, double x_bytes, int wino_mode) {
-    if (!h->opt.wino_fused || wino_mode == 0 || wino_mode == 2) return 0;
-    if (wino_mode == 1) return 1;
-    if (wino_mode == 3) return 2;
-    const bool phased = cin_pad <= h->opt.wf_phased_maxk && x_bytes <= 1073741824.0;
+// K <= 128: k_wino_fused transforms its own input (V never exists in memory); larger K: a separate transform kernel
+// (measured at batch 256: 17.99 / 18.04 / 18.78 ms per forward for a limit of 64 / 128 / 256, 18.67 without)
+static bool wino_phased(const ffr_handle* h, int cin_pad, double x_bytes) {
+    return cin_pad <= h->opt.wf_phased_maxk && x_bytes <= 1073741824.0;
+}
+
+// The fused launch runs in rounds of one block tile per CU, all of the same duration: a last round with few block tiles leaves
+// most of the chip idle for a whole block time (784 block tiles of a 128 -> 128 layer at 28x28 = 3.06 rounds took 4: 245 us
+// where 3 rounds are 178).  When the last round would be less than a quarter full, the images whose block tiles fill whole
+// rounds run fused and the remaining few images (2 % of the batch) on the transform-kernel + batched-GEMM path, whose small
+// tiles spread over every CU (the tail split).  Option wf_tailsplit = 0: off.
+static bool short_last_round(const ffr_handle* h, long long block_tiles) {
+    const long long full = block_tiles / h->num_cus * h->num_cus, rem = block_tiles - full;
+    return h->opt.wf_tailsplit != 0 && !h->opt.wf_trace && full > 0 && rem > 0 && rem * 4 <= h->num_cus;
+}
+
+// Which form of k_wino_fused a Winograd convolution of T tiles takes: Fused (blocks of 32 tiles x 64 channels), FusedHalf
+// (32 x 32) or Unfused (transform kernels + batched GEMM).  A forced form is kept while option wino_fused is on.
+ConvForce wino_fused_form(const ffr_handle* h, int cin_pad, int cout_pad, long long T, double x_bytes, ConvForce ask) {
+    if (!h->opt.wino_fused || ask == ConvForce::Direct || ask == ConvForce::Unfused) return ConvForce::Unfused;
+    if (ask == ConvForce::Fused || ask == ConvForce::FusedHalf) return ask;
     // One block tile (all 36 xi) occupies a whole CU and cannot be cut: a launch with fewer block tiles than CUs leaves matrix
     // cores idle, where the batched-GEMM path balances K-tiles over every CU (Conv4Space at batch 256: 32..128 block tiles of
     // 32 x 64, 1.07 ms fused vs 0.55 ms unfused).
     const long long min_blocks = h->opt.wf_minblocks;
     const long long mbn = (T + 31) / 32;
     const long long bt_full = mbn * (cout_pad / 64);
-    const bool tail_split = h->opt.wf_tailsplit != 0 && !h->opt.wf_trace;
     // Second block shape, 32 tiles x 32 channels (half the accumulators and half the work per block, twice the blocks):
     // for launches whose 32 x 64 block tiles cannot fill the chip (stage 4 / RecNet at 128 images: 128 block tiles) or
     // fill their last round badly.  Not with the in-kernel input transform, which every block of a tile group would repeat.
     auto fit = [&](long long bt) {          // share of the launch's rounds that carries work
         const long long full = bt / h->num_cus * h->num_cus, rem = bt - full;
-        if (rem == 0 || (tail_split && full > 0 && rem * 4 <= h->num_cus)) return 1.0;
+        if (rem == 0 || short_last_round(h, bt)) return 1.0;
         return (double)bt / (double)(full + h->num_cus);
     };
     bool half_n = false;
-    if (!phased) {
+    if (!wino_phased(h, cin_pad, x_bytes)) {
         if (bt_full < min_blocks) half_n = 2 * bt_full >= min_blocks;
         else half_n = 0.92 * fit(2 * bt_full) > fit(bt_full);       // a half block costs ~8 % more per unit of work
     }
-    if (mbn * (cout_pad / (half_n ? 32 : 64)) < min_blocks) return 0;
-    return half_n ? 2 : 1;
+    if (mbn * (cout_pad / (half_n ? 32 : 64)) < min_blocks) return ConvForce::Unfused;
+    return half_n ? ConvForce::FusedHalf : ConvForce::Fused;
 }
 
 // True when the convolution WOULD run on the exact 4+4+3+3 tiling (k_wino_fused_mixed) once the three extra weight sets exist:
 // 14x14 map, zero padding, scratch large enough, and every CU gets at least two blocks.
-// wino_mode 4 forces it (tests, experiments; 7x7 maps = 4+3 too).
-bool wino_mixed_eligible(const ffr_handle* h, const ConvW& L, int N, int H, int W, int in_pitch, size_t wino_cap, int wino_mode) {
+// ConvForce::Mixed forces it (tests, experiments; 7x7 maps = 4+3 too).
+bool wino_mixed_eligible(const ffr_handle* h, const ConvW& L, int N, int H, int W, int in_pitch, size_t wino_cap, ConvForce force) {
     if (!L.wuc || !L.w || L.R != 3 || L.S != 3 || L.stride != 1 || L.pad_mode != 0 || in_pitch != L.cin_pad) return false;
-    if (!(H == 14 && W == 14) && !(wino_mode == 4 && H == 7 && W == 7)) return false;
+    if (!(H == 14 && W == 14) && !(force == ConvForce::Mixed && H == 7 && W == 7)) return false;
     WinoMixedGeom g;
     if (!wino_mixed_geom(H, W, &g) || wino_mixed_v_floats(g, N, L.cin_pad, nullptr) > wino_cap) return false;
-    if (wino_mode == 4) return true;
-    if (wino_mode >= 0 || !layer_wino(h, L) || !h->opt.wino_fused || !h->opt.wf_mixed) return false;
+    if (force == ConvForce::Mixed) return true;
+    if (force != ConvForce::Auto || !layer_wino(h, L) || !h->opt.wino_fused || !h->opt.wf_mixed) return false;
     // >= 2 blocks per CU: a long block pairs with a short one (16 instead of 18 slots per CU).  With ONE block per CU the (4,4) blocks
     // set the time: a single launch still wins 7 % there because V is 16 % smaller (round 5, tools/mixed7_experiment.py: 256 -> 256
     // at 128 images: 95.1 + 31.8 us padded vs 92.9 + 24.9 us exact), but in the forward, where the transform rides in the combine
     // kernel, it is a tie (14.68 k vs 14.70 k embeddings/s at 128 images) and would cost the 0.7 GB of extra weight sets
     return wino_mixed_blocks(N, H, W, L.cout_pad) >= 2 * h->num_cus;
-}
-// ... and does: the weight sets are there (prepare_mixed_weights ran for this layer)
-bool wino_mixed_applies(const ffr_handle* h, const ConvW& L, int N, int H, int W, int in_pitch, size_t wino_cap, int wino_mode) {
-    return L.wum[1] && wino_mixed_eligible(h, L, N, H, W, in_pitch, wino_cap, wino_mode);
 }
 
 // The weights of the tile types (4,3), (3,4), (3,3) of one layer, derived ON THE DEVICE from its packed direct weights the first
@@ -289,31 +298,63 @@ int prepare_mixed_weights(ffr_handle* h, int N, int H, int W, size_t wino_cap) {
     if (h->mixed_ready_n >= N && h->mixed_ready_h == H && h->mixed_ready_w == W) return FFR_OK;     // the common case: one comparison per forward
     int ch = H, cw = W;
     for (Block& b : h->blocks) {
-        if (wino_mixed_eligible(h, b.c1, N, ch, cw, b.cin, wino_cap, -1)) RC(ensure_mixed_weights(h, b.c1, h->enc_allocs, false));
-        if (b.stride == 1 && wino_mixed_eligible(h, b.c2, N, ch, cw, b.depth, wino_cap, -1)) RC(ensure_mixed_weights(h, b.c2, h->enc_allocs, false));
+        if (wino_mixed_eligible(h, b.c1, N, ch, cw, b.cin, wino_cap, ConvForce::Auto)) RC(ensure_mixed_weights(h, b.c1, h->enc_allocs, false));
+        if (b.stride == 1 && wino_mixed_eligible(h, b.c2, N, ch, cw, b.depth, wino_cap, ConvForce::Auto)) RC(ensure_mixed_weights(h, b.c2, h->enc_allocs, false));
         ch /= b.stride; cw /= b.stride;
     }
     h->mixed_ready_n = N; h->mixed_ready_h = H; h->mixed_ready_w = W;
     return FFR_OK;
 }
 
-// True when the Winograd convolution (L on N x H x W) will run k_wino_fused over the WHOLE batch from a V that already
-// lies in winoV in fragment order (run_conv with wino_stage 2 / v_chunked): not the in-kernel transform, no split-off
-// remainder, scratch large enough.  run_conv applies the same tests.
-bool wino_accepts_ready_v(const ffr_handle* h, const ConvW& L, int N, int H, int W, int in_pitch, size_t wino_cap) {
-    if (!L.wu || !L.wuc || !layer_wino(h, L) || L.pad_mode != 0) return false;
-    if (wino_mixed_applies(h, L, N, H, W, in_pitch, wino_cap, -1)) return false;     // that path transforms its own V (for now)
-    const int th = (H + 3) / 4, tw = (W + 3) / 4;
-    const long long T = (long long)N * th * tw;
-    const double x_bytes = 4.0 * N * H * W * in_pitch;
-    if (L.cin_pad <= h->opt.wf_phased_maxk && x_bytes <= 1073741824.0) return false;
-    const int choice = wino_fused_choice(h, L.cin_pad, L.cout_pad, T, x_bytes, -1);
-    if (choice == 0 || wino_chunked_floats(T, L.cin_pad) > wino_cap || T >= 0x7fffffffLL || in_pitch != L.cin_pad) return false;
-    const long long bt = ((T + 31) / 32) * (L.cout_pad / (choice == 2 ? 32 : 64));
-    const long long full = bt / h->num_cus * h->num_cus, rem = bt - full;
-    const bool tail_split = h->opt.wf_tailsplit != 0 && !h->opt.wf_trace;
-    if (tail_split && full > 0 && rem > 0 && rem * 4 <= h->num_cus) return false;
-    return true;
+// The one place the path rules live: which kernels the convolution L launches for call c, with which block
+// shape and split.  Launches, allocates and writes nothing: run_conv executes the plan, run_trunk asks it ahead of the launch.
+ConvPlan plan_conv(const ffr_handle* h, const ConvW& L, const ConvCall& c) {
+    ConvPlan p;
+    if (c.wino_stage == 2 && c.v_chunked) {     // V lies in winoV in k_wino_fused's order: the whole conv must run fused from it
+        ConvCall whole = c;
+        whole.wino_stage = 0; whole.v_chunked = false;
+        p = plan_conv(h, L, whole);
+        if (!p.takes_v) { p = ConvPlan{}; p.refused = "a ready V was announced for a convolution that cannot take it"; }
+        return p;
+    }
+    const ConvForce f = c.force;
+    // exact tiling 4+4+3+3 of a 14x14 map (wino_mixed.hip): the weight sets exist (prepare_mixed_weights), the stores are 4-aligned
+    if (L.wum[1] && wino_mixed_eligible(h, L, c.N, c.H, c.W, c.in_pitch, c.wino_cap, f) && c.winoV && c.tile == 0 &&
+        (c.wino_stage == 0 || (c.wino_stage == 2 && c.v_mixed)) && ((c.out_pitch | c.out_coff | c.res_pitch | c.cout_store) & 3) == 0)
+        { p.path = ConvPlan::Mixed; return p; }
+    // Winograd F(4x4,3x3) when the layer has the weights and the caller asks for it or leaves it to option wino / the layer's plan
+    if (!L.wu || !c.winoV || c.tile != 0 || (f == ConvForce::Auto ? !layer_wino(h, L) : f == ConvForce::Direct)) return p;
+    const int tiles_img = ((c.H + 3) / 4) * ((c.W + 3) / 4);
+    const long long T = (long long)c.N * tiles_img;
+    const double x_bytes = 4.0 * c.N * c.H * c.W * c.in_pitch;
+    const bool phased = wino_phased(h, L.cin_pad, x_bytes);
+    const ConvForce form = wino_fused_form(h, L.cin_pad, L.cout_pad, T, x_bytes, f);
+    if (form != ConvForce::Unfused && L.wuc && c.wino_stage == 0 && (phased || wino_chunked_floats(T, L.cin_pad) <= c.wino_cap) &&
+        T < 0x7fffffffLL) {
+        p.path = ConvPlan::Fused;
+        p.phased = phased;
+        p.half_n = form == ConvForce::FusedHalf;
+        const int nbn = L.cout_pad / (p.half_n ? 32 : 64);
+        const long long block_tiles = (T + 31) / 32 * nbn;
+        if (f == ConvForce::Auto && short_last_round(h, block_tiles)) {
+            // (leaving 8..64 CUs without a block tile in the last round for the remainder's kernels did not help: 16.78 ms
+            // per forward with none, 16.79 / 16.81 / 16.83 / 17.04 with 8 / 16 / 32 / 64)
+            const long long full = block_tiles / h->num_cus * h->num_cus;
+            const int n_main = (int)((full / nbn) * 32 / tiles_img);       // images whose tiles fit into full / nbn tile groups
+            const size_t rem_floats = (size_t)36 * (c.N - n_main) * tiles_img * (L.cin_pad > L.cout_pad ? L.cin_pad : L.cout_pad);
+            if (n_main >= 1 && n_main < c.N && rem_floats <= c.wino_cap) {
+                p.n_main = n_main;
+                // the remainder needs none of the main launch's buffers when that transforms its own input (phased): it
+                // runs on the second stream, its short blocks slot in between the rounds of the main launch
+                p.side = phased ? h->side : nullptr;
+            }
+        }
+        p.takes_v = !phased && p.n_main == 0 && L.pad_mode == 0 && c.in_pitch == L.cin_pad;
+        return p;
+    }
+    if (L.wu == L.wuc) p.refused = "Winograd weights exist in the fused kernel's order only, but this launch cannot run fused";
+    else if ((size_t)36 * T * L.cin_pad <= c.wino_cap && (size_t)36 * T * L.cout_pad <= c.wino_cap && T < 0x7fffffffLL) p.path = ConvPlan::Unfused;
+    return p;
 }
 
 // Tile shape and block count of one launch.
@@ -322,7 +363,7 @@ bool wino_accepts_ready_v(const ffr_handle* h, const ConvW& L, int N, int H, int
 //    efficiency measured on the MI355X: 128x128 > 128x64 > 64x64, profiles/r01_conv_sweep*);
 //  * small problems: 64x64 tiles; whole tiles per block when they fill 160..1024 blocks
 //    (nothing is cut), else stream-K with at least `min_units` K-tiles per block.
-void plan_conv(long long M, int cout_pad, int nkt, int nbatch, int force_tile, int min_units, int* tile, int* nblocks, int* granule) {
+void plan_igemm(long long M, int cout_pad, int nkt, int nbatch, int force_tile, int min_units, int* tile, int* nblocks, int* granule) {
     auto ntiles = [&](int t) {
         int bm, bn;
         igemm_tile_shape(t, &bm, &bn);
@@ -367,6 +408,149 @@ void plan_conv(long long M, int cout_pad, int nkt, int nbatch, int force_tile, i
 }
 
 
+#ifdef FFR_TRACE
+// ---- diagnostics (options igemm_trace / wf_trace): the launch with in-kernel clock stamps, a stream sync, a summary on stderr
+// k_igemm: per-block clock sums
+int trace_igemm(ffr_handle* h, IgemmArgs& a, int tile, int nblocks, long long units, hipStream_t st) {
+    unsigned long long* dbuf = nullptr;
+    HIPCK(h, hipMalloc((void**)&dbuf, (size_t)nblocks * 8 * sizeof(unsigned long long)));
+    a.trace = dbuf;
+    HIPCK(h, launch_igemm(a, tile, nblocks, st));
+    HIPCK(h, hipStreamSynchronize(st));
+    std::vector<unsigned long long> t((size_t)nblocks * 8);
+    HIPCK(h, hipMemcpy(t.data(), dbuf, t.size() * 8, hipMemcpyDeviceToHost));
+    HIPCK(h, hipFree(dbuf));
+    a.trace = nullptr;
+    double acc[4] = {0, 0, 0, 0}, segs = 0, e1 = 0, e2 = 0, ghz = 0;
+    unsigned long long r0 = ~0ull, r1 = 0, smax = 0;
+    for (int b = 0; b < nblocks; ++b) {
+        const unsigned long long* q = &t[(size_t)b * 8];
+        for (int k = 0; k < 4; ++k) acc[k] += (double)q[k];
+        segs += (double)q[4];
+        ghz += (double)(q[0] + q[1] + q[2] + q[3]) / ((double)(q[6] - q[5]) * 10.0);
+        e1 += (double)(q[7] >> 32); e2 += (double)(q[7] & 0xffffffffull);
+        if (q[5] < r0) r0 = q[5];
+        if (q[5] > smax) smax = q[5];
+        if (q[6] > r1) r1 = q[6];
+    }
+    fprintf(stderr, "[igemm trace] tile %d blocks %d units %lld nkt %d segs/blk %.2f | per segment: setup %.0f prologue %.0f "
+                    "loop %.0f (%.0f per K-tile) epilogue %.0f (first barrier at %.0f, C in LDS at %.0f) cyc | span %.1f us, starts within %.1f us, shader clock %.2f GHz\n",
+            tile, nblocks, units, a.nkt, segs / nblocks, acc[0] / segs, acc[1] / segs, acc[2] / segs,
+            acc[2] / ((double)units), acc[3] / segs, e1 / segs, e2 / segs, (double)(r1 - r0) / 100.0, (double)(smax - r0) / 100.0, ghz / nblocks);
+    return FFR_OK;
+}
+
+// k_wino_fused_mixed: per-block phase stamps and which CU ran which tile types
+int trace_wino_mixed(ffr_handle* h, WinoMixedArgs& f, const ConvW& L, const ConvCall& c, hipStream_t st) {
+    const int nbm = wino_mixed_blocks_launched(c.N, c.H, c.W, L.cout_pad, f.xcd_pairs);
+    unsigned long long* dbuf = nullptr;
+    HIPCK(h, hipMalloc((void**)&dbuf, (size_t)nbm * 12 * sizeof(unsigned long long)));
+    HIPCK(h, hipMemsetAsync(dbuf, 0, (size_t)nbm * 12 * sizeof(unsigned long long), st));
+    f.trace = dbuf;
+    hipEvent_t e0, e1;
+    HIPCK(h, hipEventCreate(&e0)); HIPCK(h, hipEventCreate(&e1));
+    HIPCK(h, hipEventRecord(e0, st));
+    HIPCK(h, launch_wino_fused_mixed(f, st));
+    HIPCK(h, hipEventRecord(e1, st));
+    HIPCK(h, hipStreamSynchronize(st));
+    float ev_ms = 0.f;
+    HIPCK(h, hipEventElapsedTime(&ev_ms, e0, e1));
+    hipEventDestroy(e0); hipEventDestroy(e1);
+    std::vector<unsigned long long> tr((size_t)nbm * 12);
+    HIPCK(h, hipMemcpy(tr.data(), dbuf, tr.size() * 8, hipMemcpyDeviceToHost));
+    HIPCK(h, hipFree(dbuf));
+    double pro[4] = {0, 0, 0, 0}, loop[4] = {0, 0, 0, 0}, ep1[4] = {0, 0, 0, 0}, ep2[4] = {0, 0, 0, 0}, clk[4] = {0, 0, 0, 0};
+    int cnt[4] = {0, 0, 0, 0};
+    unsigned long long r_first = ~0ull, r_last = 0;
+    struct Run { unsigned long long start, end; int tau; };
+    std::map<unsigned long long, std::vector<Run>> per_cu;
+    for (int b = 0; b < nbm; ++b) {
+        const unsigned long long* q = &tr[(size_t)b * 12];
+        if (!q[9]) continue;
+        const int tau = (int)q[8];
+        pro[tau] += (double)(q[1] - q[0]); loop[tau] += (double)(q[2] - q[1]); ep1[tau] += (double)(q[3] - q[2]); ep2[tau] += (double)(q[4] - q[3]);
+        clk[tau] += (double)(q[4] - q[0]) / (double)(q[6] - q[5]) * 0.1;       // shader cycles per 10 ns tick -> GHz
+        ++cnt[tau];
+        if (q[5] < r_first) r_first = q[5];
+        if (q[6] > r_last) r_last = q[6];
+        per_cu[q[7]].push_back(Run{q[5], q[6], tau});
+    }
+    static const char* tname[4] = {"(4,4)", "(4,3)", "(3,4)", "(3,3)"};
+    fprintf(stderr, "[wf trace] mixed %dx%d cin %d cout %d, %d images: hipEvent %.1f us, first block start to last block end %.1f us\n",
+            c.H, c.W, L.cin_pad, L.cout_pad, c.N, ev_ms * 1e3, (double)(r_last - r_first) / 100.0);
+    for (int tau = 0; tau < 4; ++tau) {
+        if (!cnt[tau]) continue;
+        const int S = wino_mixed_xp(tau) / 4;
+        fprintf(stderr, "[wf trace]   type %s: %d blocks of %d slots | per block (wave 0): prologue %.0f loop %.0f (%.0f per K chunk, floor %d) "
+                        "epilogue %.0f + %.0f = block %.0f cyc at %.2f GHz = %.1f us\n", tname[tau], cnt[tau], S, pro[tau] / cnt[tau], loop[tau] / cnt[tau],
+                loop[tau] / cnt[tau] / f.nkc, S * 8 * 64, ep1[tau] / cnt[tau], ep2[tau] / cnt[tau],
+                (pro[tau] + loop[tau] + ep1[tau] + ep2[tau]) / cnt[tau], clk[tau] / cnt[tau],
+                (pro[tau] + loop[tau] + ep1[tau] + ep2[tau]) / cnt[tau] / (clk[tau] / cnt[tau]) * 1e-3);
+    }
+    // which block types did each CU run, in order; how long was it busy, how long idle between / after its blocks
+    std::map<std::string, int> hist;
+    double busy = 0, gap = 0, tail = 0, lead = 0;
+    for (auto& kv : per_cu) {
+        auto& v = kv.second;
+        std::sort(v.begin(), v.end(), [](const Run& x, const Run& y) { return x.start < y.start; });
+        std::string key;
+        for (size_t i = 0; i < v.size(); ++i) {
+            key += tname[v[i].tau];
+            busy += (double)(v[i].end - v[i].start);
+            if (i) gap += (double)(v[i].start - v[i - 1].end);
+        }
+        lead += (double)(v.front().start - r_first);
+        tail += (double)(r_last - v.back().end);
+        ++hist[key];
+    }
+    const double ncu = (double)per_cu.size();
+    fprintf(stderr, "[wf trace]   %d CUs ran blocks; per CU: busy %.1f us, idle before its first block %.1f, between blocks %.1f, after its last block %.1f us | sequences:",
+            (int)per_cu.size(), busy / ncu / 100.0, lead / ncu / 100.0, gap / ncu / 100.0, tail / ncu / 100.0);
+    for (auto& kv : hist) fprintf(stderr, "  %s x %d", kv.first.c_str(), kv.second);
+    fprintf(stderr, "\n");
+    return FFR_OK;
+}
+
+// k_wino_fused: per-block phase stamps
+int trace_wino_fused(ffr_handle* h, WinoFusedArgs& f, const ConvW& L, const ConvCall& c, const ConvPlan& p, hipStream_t st) {
+    const int nb = wino_fused_blocks(f);
+    unsigned long long* dbuf = nullptr;
+    HIPCK(h, hipMalloc((void**)&dbuf, (size_t)nb * 40 * sizeof(unsigned long long)));
+    HIPCK(h, hipMemsetAsync(dbuf, 0, (size_t)nb * 40 * sizeof(unsigned long long), st));
+    f.trace = dbuf;
+    HIPCK(h, launch_wino_fused(f, st));
+    HIPCK(h, hipStreamSynchronize(st));
+    std::vector<unsigned long long> tr((size_t)nb * 40);
+    HIPCK(h, hipMemcpy(tr.data(), dbuf, tr.size() * 8, hipMemcpyDeviceToHost));
+    HIPCK(h, hipFree(dbuf));
+    double pro = 0, loop = 0, epi = 0, ep[5] = {0, 0, 0, 0, 0}; int cnt = 0;
+    unsigned long long r0 = ~0ull, r1 = 0;
+    for (int b = 0; b < nb; ++b) {
+        const unsigned long long* q = &tr[(size_t)b * 40];
+        if (!q[3]) continue;
+        ep[0] += (double)(q[6] - q[2]); ep[1] += (double)(q[7] - q[6]); ep[2] += (double)(q[8] - q[7]);
+        ep[3] += (double)(q[9] - q[8]); ep[4] += (double)(q[3] - q[9]);
+        pro += (double)(q[1] - q[0]); loop += (double)(q[2] - q[1]); epi += (double)(q[3] - q[2]); ++cnt;
+        if (q[4] > r1) r1 = q[4];
+        if (q[4] < r0) r0 = q[4];
+    }
+    if (p.phased) {    // the kernel reports per phase: input transform, wait at the barrier behind it
+        const int cpp = 4, nph = f.nkc / cpp;                      // K chunks per phase, phases
+        fprintf(stderr, "[wf trace] %dx%d cin %d cout %d (input transform in the kernel, %d-channel blocks%s): %d live blocks of %d | per block (wave 0): "
+                        "prologue %.0f loop %.0f = %d phases x (transform %.0f + barrier %.0f + %d K chunks of %.0f) epilogue %.0f cyc | "
+                        "block ends spread over %.1f us\n", c.H, c.W, L.cin_pad, L.cout_pad, p.half_n ? 32 : 64, "", cnt, nb,
+                pro / cnt, loop / cnt, nph, ep[0] / cnt, ep[1] / cnt, cpp, (loop / cnt / nph - ep[0] / cnt - ep[1] / cnt) / cpp, epi / cnt,
+                (double)(r1 - r0) / 100.0);
+    }
+    else
+        fprintf(stderr, "[wf trace] %dx%d cin %d cout %d: %d live blocks of %d | per block (wave 0): prologue %.0f loop %.0f (%.0f per K chunk) "
+                        "epilogue %.0f cyc (to LDS %.0f, transform+store %.0f, barrier+to LDS %.0f, transform+store %.0f, end %.0f) | block ends spread over %.1f us\n",
+                c.H, c.W, L.cin_pad, L.cout_pad, cnt, nb, pro / cnt, loop / cnt, loop / cnt / f.nkc, epi / cnt, ep[0] / cnt, ep[1] / cnt,
+                ep[2] / cnt, ep[3] / cnt, ep[4] / cnt, (double)(r1 - r0) / 100.0);
+    return FFR_OK;
+}
+#endif
+
 // plan + launch one (possibly batched) implicit-GEMM described by `a` (M, nkt, cout_pad, nbatch set)
 int run_gemm(ffr_handle* h, IgemmArgs& a, const ConvCall& c, double flops, double bytes, hipStream_t st, double fuse) {
     int tile, nblocks;
@@ -376,7 +560,7 @@ int run_gemm(ffr_handle* h, IgemmArgs& a, const ConvCall& c, double flops, doubl
         igemm_tile_shape(force, &fbm, &fbn);
         if (a.cout_pad % fbn) return fail(h, FFR_ERR_ARG, "conv: forced tile %d (%d x %d) does not divide cout_pad %d", force, fbm, fbn, a.cout_pad);
     }
-    plan_conv(a.M, a.cout_pad, a.nkt, a.nbatch, force, h->opt.sk_minunits, &tile, &nblocks, &a.granule);
+    plan_igemm(a.M, a.cout_pad, a.nkt, a.nbatch, force, h->opt.sk_minunits, &tile, &nblocks, &a.granule);
     int bm, bn;
     igemm_tile_shape(tile, &bm, &bn);
     a.mtiles = (a.M + bm - 1) / bm;
@@ -388,356 +572,169 @@ int run_gemm(ffr_handle* h, IgemmArgs& a, const ConvCall& c, double flops, doubl
     a.tickets = c.tickets;
     if ((size_t)a.nbatch * a.mtiles * a.ntiles > c.tickets_cap) return fail(h, FFR_ERR_NOMEM, "stream-K ticket array too small");
 #ifdef FFR_TRACE
-    if (h->opt.igemm_trace) {   // diagnostic: per-block clock sums, printed after a stream sync
-        unsigned long long* dbuf = nullptr;
-        HIPCK(h, hipMalloc((void**)&dbuf, (size_t)nblocks * 8 * sizeof(unsigned long long)));
-        a.trace = dbuf;
-        HIPCK(h, launch_igemm(a, tile, nblocks, st));
-        HIPCK(h, hipStreamSynchronize(st));
-        std::vector<unsigned long long> t((size_t)nblocks * 8);
-        HIPCK(h, hipMemcpy(t.data(), dbuf, t.size() * 8, hipMemcpyDeviceToHost));
-        HIPCK(h, hipFree(dbuf));
-        a.trace = nullptr;
-        double acc[4] = {0, 0, 0, 0}, segs = 0, e1 = 0, e2 = 0, ghz = 0;
-        unsigned long long r0 = ~0ull, r1 = 0, smax = 0;
-        for (int b = 0; b < nblocks; ++b) {
-            const unsigned long long* q = &t[(size_t)b * 8];
-            for (int k = 0; k < 4; ++k) acc[k] += (double)q[k];
-            segs += (double)q[4];
-            ghz += (double)(q[0] + q[1] + q[2] + q[3]) / ((double)(q[6] - q[5]) * 10.0);
-            e1 += (double)(q[7] >> 32); e2 += (double)(q[7] & 0xffffffffull);
-            if (q[5] < r0) r0 = q[5];
-            if (q[5] > smax) smax = q[5];
-            if (q[6] > r1) r1 = q[6];
-        }
-        fprintf(stderr, "[igemm trace] tile %d blocks %d units %lld nkt %d segs/blk %.2f | per segment: setup %.0f prologue %.0f "
-                        "loop %.0f (%.0f per K-tile) epilogue %.0f (first barrier at %.0f, C in LDS at %.0f) cyc | span %.1f us, starts within %.1f us, shader clock %.2f GHz\n",
-                tile, nblocks, units, a.nkt, segs / nblocks, acc[0] / segs, acc[1] / segs, acc[2] / segs,
-                acc[2] / ((double)units), acc[3] / segs, e1 / segs, e2 / segs, (double)(r1 - r0) / 100.0, (double)(smax - r0) / 100.0, ghz / nblocks);
-        return FFR_OK;
-    }
+    if (h->opt.igemm_trace) return trace_igemm(h, a, tile, nblocks, units, st);
 #endif
-    {
-        const double fexec = 2.0 * a.nbatch * (double)a.mtiles * bm * (double)a.cout_pad * a.KK;
-        Scope s(h, st, FFR_KC_CONV_IGEMM, flops, bytes, fexec, fuse);
-        HIPCK(h, launch_igemm(a, tile, nblocks, st));
-    }
+    const double fexec = 2.0 * a.nbatch * (double)a.mtiles * bm * (double)a.cout_pad * a.KK;
+    Scope s(h, st, FFR_KC_CONV_IGEMM, flops, bytes, fexec, fuse);
+    HIPCK(h, launch_igemm(a, tile, nblocks, st));
     return FFR_OK;
 }
 
+// exact tiling 4+4+3+3 of a 14x14 map (wino_mixed.hip): one transform launch and one fused launch for all four tile types
+static int conv_mixed(ffr_handle* h, const ConvW& L, const ConvCall& c, double flops, double bytes, hipStream_t st) {
+    WinoMixedGeom g;
+    wino_mixed_geom(c.H, c.W, &g);
+    if (c.wino_stage == 0) {
+        Scope s(h, st, FFR_KC_WINO, 0, 4.0 * ((double)c.N * c.H * c.W * L.cin + (double)wino_mixed_v_floats(g, c.N, L.cin_pad, nullptr)));
+        HIPCK(h, launch_wino_in_mixed(c.x, c.winoV, c.N, c.H, c.W, c.in_pitch, L.cin_pad, st));
+    }
+    WinoMixedArgs f{};
+    f.V[0] = c.winoV;
+    for (int tau = 0; tau < 4; ++tau) f.U[tau] = L.wum[tau];
+    f.bias = L.bias; f.slope = L.slope; f.resid = c.resid; f.out = c.out; f.tile_sums = c.tile_sums;
+    f.N = c.N; f.H = c.H; f.W = c.W; f.nkc = L.cin_pad / 8;
+    f.cout_pad = L.cout_pad; f.cout_store = c.cout_store; f.out_pitch = c.out_pitch; f.out_coff = c.out_coff;
+    f.res_pitch = c.res_pitch; f.border_bias = L.border; f.flags = c.flags;
+    f.xcd_pairs = 1;       // XCDs specialise in pairs of tile types (round 5; the uniform map measured slower: EXPERIMENTS.md)
+    double fexec = 0.0, fuse = 0.0;
+    for (int tau = 0; tau < 4; ++tau) {
+        const int nr = tau >= 2 ? g.n3 : g.n4, nc = (tau & 1) ? g.n3 : g.n4;
+        const double Tt = (double)c.N * nr * nc;
+        fexec += 2.0 * wino_mixed_xp(tau) * std::ceil(Tt / 32.0) * 32.0 * L.cout_pad * L.cin_pad;
+        fuse += 2.0 * wino_mixed_x(tau) * Tt * L.cout * L.cin;
+    }
+#ifdef FFR_TRACE
+    if (h->opt.wf_trace) return trace_wino_mixed(h, f, L, c, st);
+#endif
+    Scope s(h, st, FFR_KC_WINO_FUSED, flops, bytes, fexec, fuse);
+    HIPCK(h, launch_wino_fused_mixed(f, st));
+    return FFR_OK;
+}
+
+// Winograd F(4x4,3x3), GEMM + output transform in one kernel (wino_fused.hip): M never exists in memory
+static int conv_fused(ffr_handle* h, const ConvW& L, const ConvCall& c, const ConvPlan& p, double flops, double bytes, hipStream_t st) {
+    const long long T = (long long)c.N * ((c.H + 3) / 4) * ((c.W + 3) / 4);
+    if (!p.phased && c.wino_stage == 0) {
+        Scope s(h, st, FFR_KC_WINO, 0, 4.0 * ((double)c.N * c.H * c.W * L.cin + 36.0 * T * L.cin_pad));
+        HIPCK(h, launch_wino_in_chunked(c.x, c.winoV, c.N, c.H, c.W, c.in_pitch, L.cin_pad, L.pad_mode, st));
+    }
+    WinoFusedArgs f{};
+    f.Vc = p.phased ? nullptr : c.winoV; f.x = c.x; f.in_pitch = c.in_pitch; f.pad_mode = L.pad_mode;
+    f.x_bytes = p.phased ? (unsigned)(4.0 * c.N * c.H * c.W * c.in_pitch) : 0u;
+    // block -> tile mapping: the channel groups of a tile group next to each other on ONE XCD (V is fetched into that
+    // L2 once instead of once per channel group: 59.5 -> 45.7 GB fetched + written per forward, 17.53 -> 17.32 ms at
+    // batch 256); with the in-kernel transform an XCD owns a contiguous range of tile groups (halo rows shared in its L2).
+    // The alternatives (one channel group per XCD; XCD quads splitting the channel groups) measured slower: EXPERIMENTS.md
+    f.map_v = p.phased ? 2 : 1; f.half_n = p.half_n ? 1 : 0;
+    f.Uc = L.wuc; f.bias = L.bias; f.slope = L.slope; f.resid = c.resid; f.out = c.out; f.tile_sums = c.tile_sums;
+    f.N = c.N; f.H = c.H; f.W = c.W; f.nkc = L.cin_pad / 8;
+    f.cout_pad = L.cout_pad; f.cout_store = c.cout_store; f.out_pitch = c.out_pitch; f.out_coff = c.out_coff;
+    f.res_pitch = c.res_pitch; f.border_bias = L.border; f.flags = c.flags;
+    const double fexec = 2.0 * 36.0 * (double)((T + 31) / 32 * 32) * (double)L.cout_pad * L.cin_pad;
+#ifdef FFR_TRACE
+    if (h->opt.wf_trace) return trace_wino_fused(h, f, L, c, p, st);
+#endif
+    Scope s(h, st, FFR_KC_WINO_FUSED, flops, bytes, fexec, flops / 4.0);
+    HIPCK(h, launch_wino_fused(f, st));
+    return FFR_OK;
+}
+
+// Winograd F(4x4,3x3): input transform -> 36 batched GEMMs [T x cin] * [cin x cout] -> output transform
+static int conv_unfused(ffr_handle* h, const ConvW& L, const ConvCall& c, long long M, double flops, double bytes, hipStream_t st) {
+    const long long T = (long long)c.N * ((c.H + 3) / 4) * ((c.W + 3) / 4);
+    if (c.wino_stage != 2) {
+        Scope s(h, st, FFR_KC_WINO, 0, 4.0 * ((double)c.N * c.H * c.W * L.cin + 36.0 * T * L.cin_pad));
+        HIPCK(h, launch_wino_in(c.x, c.winoV, c.N, c.H, c.W, c.in_pitch, L.cin_pad, L.pad_mode, st));
+    }
+    // the roofline numerator of the GEMM stays the DIRECT convolution's algorithmic FLOPs
+    if (h->opt.gemm_stream) {
+        // 36 GEMMs in one persistent launch with a continuous K-tile stream; tile shape: fewest rounds of whole tiles over
+        // the resident blocks, weighted by loop efficiency
+        int gtile = IGEMM_TILE_128x64, gblocks = 768;
+        double best = 1e300;
+        for (int tt = IGEMM_TILE_128x128; tt <= IGEMM_TILE_128x64; ++tt) {
+            int bm, bn;
+            igemm_tile_shape(tt, &bm, &bn);
+            if (L.cout_pad % bn) continue;
+            const long long tiles = 36LL * ((T + bm - 1) / bm) * (L.cout_pad / bn);
+            const long long pmax = 256LL * igemm_resident_blocks(tt);
+            const long long p = pmax > tiles ? tiles : pmax;
+            const double rounds = (double)((tiles + p - 1) / p);
+            // a block gets 1/R of its CU (R co-resident blocks), so a round of tiles costs bm*bn*R;
+            // the 128x64 loop runs at ~92% of the 128x128 loop's rate (measured per layer, r01 traces)
+            const double share = (double)((p + 255) / 256);
+            const double cost = rounds * bm * bn * share / (tt == IGEMM_TILE_128x128 ? 1.0 : 0.92);
+            if (cost < best) { best = cost; gtile = tt; gblocks = (int)p; }
+        }
+        GemmStreamArgs g{};
+        g.A = c.winoV; g.W = L.wu; g.C = c.winoM; g.M = (int)T; g.K = L.cin_pad; g.Npad = L.cout_pad; g.nbatch = 36;
+        int bm, bn;
+        igemm_tile_shape(gtile, &bm, &bn);
+        const double fexec = 2.0 * 36.0 * (double)((T + bm - 1) / bm) * bm * (double)L.cout_pad * L.cin_pad;
+        Scope s(h, st, FFR_KC_CONV_IGEMM, flops, bytes, fexec, flops / 4.0);
+        HIPCK(h, launch_gemm_stream(g, gtile, gblocks, st));
+    } else {
+        IgemmArgs g{};
+        g.x = c.winoV; g.w = L.wu; g.bias = h->zero; g.slope = nullptr; g.resid = nullptr; g.out = c.winoM; g.zero = h->zero;
+        g.N = 1; g.H = 1; g.W = (int)T; g.Ho = 1; g.Wo = (int)T;
+        g.in_pitch = L.cin_pad; g.cin_pad = L.cin_pad; g.R = 1; g.S = 1; g.stride = 1; g.pad = 0; g.pad_mode = 0;
+        g.M = (int)T; g.KK = L.cin_pad; g.nkt = L.cin_pad / 32;
+        g.cout_pad = L.cout_pad; g.cout_store = L.cout_pad; g.out_pitch = L.cout_pad; g.out_coff = 0; g.res_pitch = 0;
+        g.border_bias = 0; g.flags = 0;
+        g.nbatch = 36;
+        g.x_bstride = T * L.cin_pad; g.w_bstride = (long long)L.cout_pad * L.cin_pad; g.out_bstride = T * L.cout_pad;
+        RC(run_gemm(h, g, c, flops, bytes, st, flops / 4.0));
+    }
+    if (c.wino_stage == 1) return FFR_OK;        // the caller transforms M itself (k_wino_out_in)
+    Scope s(h, st, FFR_KC_WINO, 0, 4.0 * (36.0 * T * L.cout_pad + (double)M * L.cout));
+    HIPCK(h, launch_wino_out(c.winoM, L.bias, L.slope, c.resid, c.res_pitch, c.out, c.out_pitch, c.out_coff,
+                             c.cout_store, L.cout_pad, c.N, c.H, c.W, L.border, c.flags, st, c.tile_sums));
+    return FFR_OK;
+}
+
+// Runs the convolution L on call c as plan_conv plans it
 int run_conv(ffr_handle* h, const ConvW& L, const ConvCall& c, hipStream_t st) {
-    IgemmArgs a{};
-    a.x = c.x; a.w = L.w; a.bias = L.bias; a.slope = L.slope; a.resid = c.resid; a.out = c.out; a.zero = h->zero;
-    a.N = c.N; a.H = c.H; a.W = c.W;
-    a.Ho = (c.H + 2 * L.pad - L.R) / L.stride + 1;
-    a.Wo = (c.W + 2 * L.pad - L.S) / L.stride + 1;
-    a.in_pitch = c.in_pitch; a.cin_pad = L.cin_pad; a.R = L.R; a.S = L.S; a.stride = L.stride; a.pad = L.pad;
-    a.pad_mode = L.pad_mode;
-    const long long M = (long long)c.N * a.Ho * a.Wo;
+    const int Ho = (c.H + 2 * L.pad - L.R) / L.stride + 1, Wo = (c.W + 2 * L.pad - L.S) / L.stride + 1;
+    const long long M = (long long)c.N * Ho * Wo;
     if (M <= 0 || M > 0x7fffffffLL) return fail(h, FFR_ERR_ARG, "conv: bad M");
-    a.M = (int)M; a.KK = L.R * L.S * L.cin_pad; a.nkt = a.KK / 32;
-    a.cout_pad = L.cout_pad; a.cout_store = c.cout_store; a.out_pitch = c.out_pitch; a.out_coff = c.out_coff;
-    a.res_pitch = c.res_pitch; a.border_bias = L.border; a.flags = c.flags;
     if (L.pad_mode == 1 && (c.H < 2 || c.W < 2)) return fail(h, FFR_ERR_UNSUPPORTED, "reflect pad needs H,W >= 2");
     if (L.border && (c.H < 2 || c.W < 2)) return fail(h, FFR_ERR_UNSUPPORTED, "border-class bias needs H,W >= 2");
-    a.nbatch = 1;
     const double flops = 2.0 * M * L.cout * (double)L.R * L.S * L.cin;
     const double bytes = 4.0 * ((double)c.N * c.H * c.W * L.cin + (double)M * L.cout + (double)L.cout * L.R * L.S * L.cin);
-    const bool wino_on = layer_wino(h, L);       // option wino and the layer's plan (a pinned layer runs as under wino = 0)
-    if (wino_mixed_applies(h, L, c.N, c.H, c.W, c.in_pitch, c.wino_cap, c.wino_mode) && c.winoV && c.tile == 0 &&
-        (c.wino_stage == 0 || (c.wino_stage == 2 && c.v_mixed)) &&
-        ((c.out_pitch | c.out_coff | c.res_pitch | c.cout_store) & 3) == 0) {
-        // exact tiling 4+4+3+3 of a 14x14 map (wino_mixed.hip): one transform launch and one fused launch for all four tile types
-        WinoMixedGeom g;
-        wino_mixed_geom(c.H, c.W, &g);
-        if (c.took_wino) *c.took_wino = true;
-        if (c.wino_stage == 0) {
-            Scope s(h, st, FFR_KC_WINO, 0, 4.0 * ((double)c.N * c.H * c.W * L.cin + (double)wino_mixed_v_floats(g, c.N, L.cin_pad, nullptr)));
-            HIPCK(h, launch_wino_in_mixed(c.x, c.winoV, c.N, c.H, c.W, c.in_pitch, L.cin_pad, st));
-        }
-        WinoMixedArgs f{};
-        f.V[0] = c.winoV;
-        for (int tau = 0; tau < 4; ++tau) f.U[tau] = L.wum[tau];
-        f.bias = L.bias; f.slope = L.slope; f.resid = c.resid; f.out = c.out; f.tile_sums = c.tile_sums;
-        f.N = c.N; f.H = c.H; f.W = c.W; f.nkc = L.cin_pad / 8;
-        f.cout_pad = L.cout_pad; f.cout_store = c.cout_store; f.out_pitch = c.out_pitch; f.out_coff = c.out_coff;
-        f.res_pitch = c.res_pitch; f.border_bias = L.border; f.flags = c.flags;
-        f.xcd_pairs = 1;       // XCDs specialise in pairs of tile types (round 5; the uniform map measured slower: EXPERIMENTS.md)
-        double fexec = 0.0, fuse = 0.0;
-        for (int tau = 0; tau < 4; ++tau) {
-            const int nr = tau >= 2 ? g.n3 : g.n4, nc = (tau & 1) ? g.n3 : g.n4;
-            const double Tt = (double)c.N * nr * nc;
-            fexec += 2.0 * wino_mixed_xp(tau) * std::ceil(Tt / 32.0) * 32.0 * L.cout_pad * L.cin_pad;
-            fuse += 2.0 * wino_mixed_x(tau) * Tt * L.cout * L.cin;
-        }
-#ifdef FFR_TRACE
-        if (h->opt.wf_trace) {      // diagnostics: per-block phase stamps and which CU ran which tile types, printed after a stream sync
-            const int nbm = wino_mixed_blocks_launched(c.N, c.H, c.W, L.cout_pad, f.xcd_pairs);
-            unsigned long long* dbuf = nullptr;
-            HIPCK(h, hipMalloc((void**)&dbuf, (size_t)nbm * 12 * sizeof(unsigned long long)));
-            HIPCK(h, hipMemsetAsync(dbuf, 0, (size_t)nbm * 12 * sizeof(unsigned long long), st));
-            f.trace = dbuf;
-            hipEvent_t e0, e1;
-            HIPCK(h, hipEventCreate(&e0)); HIPCK(h, hipEventCreate(&e1));
-            HIPCK(h, hipEventRecord(e0, st));
-            HIPCK(h, launch_wino_fused_mixed(f, st));
-            HIPCK(h, hipEventRecord(e1, st));
-            HIPCK(h, hipStreamSynchronize(st));
-            float ev_ms = 0.f;
-            HIPCK(h, hipEventElapsedTime(&ev_ms, e0, e1));
-            hipEventDestroy(e0); hipEventDestroy(e1);
-            std::vector<unsigned long long> tr((size_t)nbm * 12);
-            HIPCK(h, hipMemcpy(tr.data(), dbuf, tr.size() * 8, hipMemcpyDeviceToHost));
-            HIPCK(h, hipFree(dbuf));
-            double pro[4] = {0, 0, 0, 0}, loop[4] = {0, 0, 0, 0}, ep1[4] = {0, 0, 0, 0}, ep2[4] = {0, 0, 0, 0}, clk[4] = {0, 0, 0, 0};
-            int cnt[4] = {0, 0, 0, 0};
-            unsigned long long r_first = ~0ull, r_last = 0;
-            struct Run { unsigned long long start, end; int tau; };
-            std::map<unsigned long long, std::vector<Run>> per_cu;
-            for (int b = 0; b < nbm; ++b) {
-                const unsigned long long* q = &tr[(size_t)b * 12];
-                if (!q[9]) continue;
-                const int tau = (int)q[8];
-                pro[tau] += (double)(q[1] - q[0]); loop[tau] += (double)(q[2] - q[1]); ep1[tau] += (double)(q[3] - q[2]); ep2[tau] += (double)(q[4] - q[3]);
-                clk[tau] += (double)(q[4] - q[0]) / (double)(q[6] - q[5]) * 0.1;       // shader cycles per 10 ns tick -> GHz
-                ++cnt[tau];
-                if (q[5] < r_first) r_first = q[5];
-                if (q[6] > r_last) r_last = q[6];
-                per_cu[q[7]].push_back(Run{q[5], q[6], tau});
-            }
-            static const char* tname[4] = {"(4,4)", "(4,3)", "(3,4)", "(3,3)"};
-            fprintf(stderr, "[wf trace] mixed %dx%d cin %d cout %d, %d images: hipEvent %.1f us, first block start to last block end %.1f us\n",
-                    c.H, c.W, L.cin_pad, L.cout_pad, c.N, ev_ms * 1e3, (double)(r_last - r_first) / 100.0);
-            for (int tau = 0; tau < 4; ++tau) {
-                if (!cnt[tau]) continue;
-                const int S = wino_mixed_xp(tau) / 4;
-                fprintf(stderr, "[wf trace]   type %s: %d blocks of %d slots | per block (wave 0): prologue %.0f loop %.0f (%.0f per K chunk, floor %d) "
-                                "epilogue %.0f + %.0f = block %.0f cyc at %.2f GHz = %.1f us\n", tname[tau], cnt[tau], S, pro[tau] / cnt[tau], loop[tau] / cnt[tau],
-                        loop[tau] / cnt[tau] / f.nkc, S * 8 * 64, ep1[tau] / cnt[tau], ep2[tau] / cnt[tau],
-                        (pro[tau] + loop[tau] + ep1[tau] + ep2[tau]) / cnt[tau], clk[tau] / cnt[tau],
-                        (pro[tau] + loop[tau] + ep1[tau] + ep2[tau]) / cnt[tau] / (clk[tau] / cnt[tau]) * 1e-3);
-            }
-            // which block types did each CU run, in order; how long was it busy, how long idle between / after its blocks
-            std::map<std::string, int> hist;
-            double busy = 0, gap = 0, tail = 0, lead = 0;
-            for (auto& kv : per_cu) {
-                auto& v = kv.second;
-                std::sort(v.begin(), v.end(), [](const Run& x, const Run& y) { return x.start < y.start; });
-                std::string key;
-                for (size_t i = 0; i < v.size(); ++i) {
-                    key += tname[v[i].tau];
-                    busy += (double)(v[i].end - v[i].start);
-                    if (i) gap += (double)(v[i].start - v[i - 1].end);
-                }
-                lead += (double)(v.front().start - r_first);
-                tail += (double)(r_last - v.back().end);
-                ++hist[key];
-            }
-            const double ncu = (double)per_cu.size();
-            fprintf(stderr, "[wf trace]   %d CUs ran blocks; per CU: busy %.1f us, idle before its first block %.1f, between blocks %.1f, after its last block %.1f us | sequences:",
-                    (int)per_cu.size(), busy / ncu / 100.0, lead / ncu / 100.0, gap / ncu / 100.0, tail / ncu / 100.0);
-            for (auto& kv : hist) fprintf(stderr, "  %s x %d", kv.first.c_str(), kv.second);
-            fprintf(stderr, "\n");
-            if (c.tile_sums && c.tile_sums_written) *c.tile_sums_written = true;
+    const ConvPlan p = plan_conv(h, L, c);
+    if (p.refused) return fail(h, FFR_ERR_STATE, "%s", p.refused);
+    if (p.path == ConvPlan::Mixed) return conv_mixed(h, L, c, flops, bytes, st);
+    if (p.path == ConvPlan::Unfused) return conv_unfused(h, L, c, M, flops, bytes, st);
+    if (p.path == ConvPlan::Fused && !p.n_main) return conv_fused(h, L, c, p, flops, bytes, st);
+    if (p.path == ConvPlan::Fused) {
+        // tail split: the first n_main images fused, the rest through the transform kernels + batched GEMM
+        ConvCall c1 = c, c2 = c;
+        c1.N = p.n_main; c1.force = p.half_n ? ConvForce::FusedHalf : ConvForce::Fused;
+        c2.N = c.N - p.n_main; c2.force = ConvForce::Unfused;
+        const size_t px = (size_t)p.n_main * c.H * c.W;
+        c2.x = c.x + px * c.in_pitch;
+        c2.out = c.out + px * c.out_pitch;
+        if (c.resid) c2.resid = c.resid + px * c.res_pitch;
+        if (c.tile_sums) c2.tile_sums = c.tile_sums + (size_t)p.n_main * ((c.H + 3) / 4) * ((c.W + 3) / 4) * L.cout_pad;
+        if (p.side) {
+            HIPCK(h, hipEventRecord(h->ev_fork, st));
+            HIPCK(h, hipStreamWaitEvent(p.side, h->ev_fork, 0));
+            RC(run_conv(h, L, c2, p.side));
+            HIPCK(h, hipEventRecord(h->ev_join, p.side));
+            RC(run_conv(h, L, c1, st));
+            HIPCK(h, hipStreamWaitEvent(st, h->ev_join, 0));
             return FFR_OK;
         }
-#endif
-        Scope s(h, st, FFR_KC_WINO_FUSED, flops, bytes, fexec, fuse);
-        HIPCK(h, launch_wino_fused_mixed(f, st));
-        if (c.tile_sums && c.tile_sums_written) *c.tile_sums_written = true;
-        return FFR_OK;
+        RC(run_conv(h, L, c1, st));
+        return run_conv(h, L, c2, st);
     }
-    if (L.wu && c.winoV && c.tile == 0 && (c.wino_mode >= 1 || (c.wino_mode < 0 && wino_on))) {
-        // Winograd F(4x4,3x3): input transform -> 36 batched GEMMs [T x cin] * [cin x cout] -> output transform
-        const int th = (c.H + 3) / 4, tw = (c.W + 3) / 4;
-        const long long T = (long long)c.N * th * tw;
-        // GEMM + output transform in one kernel (wino_fused.hip): M never exists in memory
-        // K <= 128: the fused kernel transforms its own input (V never exists in memory); larger K: separate transform
-        // kernel (measured at batch 256: 17.99 / 18.04 / 18.78 ms per forward for a limit of 64 / 128 / 256, 18.67 without)
-        const int phased_maxk = h->opt.wf_phased_maxk;
-        const double x_bytes = 4.0 * c.N * c.H * c.W * c.in_pitch;
-        const bool phased = L.cin_pad <= phased_maxk && x_bytes <= 1073741824.0;
-        // One block tile (32 tiles x 64 channels, all 36 xi) occupies a whole CU and cannot be cut: a launch with fewer
-        // block tiles than CUs leaves matrix cores idle, where the batched-GEMM path balances K-tiles over every CU
-        // (Conv4Space at batch 256: 32..128 block tiles, 1.07 ms fused vs 0.55 ms unfused).  wino_mode 1 forces fused.
-        const int choice = wino_fused_choice(h, L.cin_pad, L.cout_pad, T, x_bytes, c.wino_mode);
-        const bool half_n = choice == 2;
-        const bool tail_split = h->opt.wf_tailsplit != 0 && !h->opt.wf_trace;
-        const long long mbn = (T + 31) / 32;
-        const int nbn = L.cout_pad / (half_n ? 32 : 64);
-        const long long block_tiles = mbn * nbn;
-        const bool v_ready = c.wino_stage == 2 && c.v_chunked;
-        if (v_ready && !wino_accepts_ready_v(h, L, c.N, c.H, c.W, c.in_pitch, c.wino_cap))
-            return fail(h, FFR_ERR_STATE, "a ready V was announced for a convolution that cannot take it");
-        if (choice != 0 && L.wuc && (c.wino_stage == 0 || v_ready) && (phased || wino_chunked_floats(T, L.cin_pad) <= c.wino_cap) && T < 0x7fffffffLL) {
-            // The launch runs in rounds of one block tile per CU, all of the same duration: a last round with few block
-            // tiles leaves most of the chip idle for a whole block time (784 block tiles of a 128 -> 128 layer at 28x28 =
-            // 3.06 rounds took 4: 245 us where 3 rounds are 178).  When the last round would be less than a quarter full,
-            // the images whose block tiles fill whole rounds run here and the remaining few images (2 % of the batch) on the
-            // transform-kernel + batched-GEMM path, whose small tiles spread over every CU.  Option wf_tailsplit = 0: off.
-            const long long full = block_tiles / h->num_cus * h->num_cus, rem = block_tiles - full;
-            if (tail_split && c.wino_mode < 0 && full > 0 && rem > 0 && rem * 4 <= h->num_cus && !v_ready) {
-                const int tiles_img = th * tw;
-                // (leaving 8..64 CUs without a block tile in the last round for the remainder's kernels did not help: 16.78 ms
-                // per forward with none, 16.79 / 16.81 / 16.83 / 17.04 with 8 / 16 / 32 / 64)
-                const int n_main = (int)((full / nbn) * 32 / tiles_img);       // images whose tiles fit into full / nbn tile groups
-                const size_t rem_floats = (size_t)36 * (c.N - n_main) * tiles_img * (L.cin_pad > L.cout_pad ? L.cin_pad : L.cout_pad);
-                if (n_main >= 1 && n_main < c.N && rem_floats <= c.wino_cap) {
-                    ConvCall c1 = c, c2 = c;
-                    c1.N = n_main; c1.wino_mode = half_n ? 3 : 1;
-                    c2.N = c.N - n_main; c2.wino_mode = 2;
-                    const size_t px = (size_t)n_main * c.H * c.W;
-                    c2.x = c.x + px * c.in_pitch;
-                    c2.out = c.out + px * c.out_pitch;
-                    if (c.resid) c2.resid = c.resid + px * c.res_pitch;
-                    if (c.tile_sums) c2.tile_sums = c.tile_sums + (size_t)n_main * tiles_img * L.cout_pad;
-                    // the remainder needs none of the main launch's buffers when that transforms its own input (phased): it
-                    // runs on the second stream, its short blocks slot in between the rounds of the main launch
-                    if (phased && h->side) {
-                        HIPCK(h, hipEventRecord(h->ev_fork, st));
-                        HIPCK(h, hipStreamWaitEvent(h->side, h->ev_fork, 0));
-                        RC(run_conv(h, L, c2, h->side));
-                        HIPCK(h, hipEventRecord(h->ev_join, h->side));
-                        RC(run_conv(h, L, c1, st));
-                        HIPCK(h, hipStreamWaitEvent(st, h->ev_join, 0));
-                        return FFR_OK;
-                    }
-                    RC(run_conv(h, L, c1, st));
-                    return run_conv(h, L, c2, st);
-                }
-            }
-            if (c.took_wino) *c.took_wino = true;
-            if (!phased && !v_ready) {
-                Scope s(h, st, FFR_KC_WINO, 0, 4.0 * ((double)c.N * c.H * c.W * L.cin + 36.0 * T * L.cin_pad));
-                HIPCK(h, launch_wino_in_chunked(c.x, c.winoV, c.N, c.H, c.W, c.in_pitch, L.cin_pad, L.pad_mode, st));
-            }
-            WinoFusedArgs f{};
-            f.Vc = phased ? nullptr : c.winoV; f.x = c.x; f.x_bytes = phased ? (unsigned)x_bytes : 0u; f.in_pitch = c.in_pitch; f.pad_mode = L.pad_mode;
-            // block -> tile mapping: the channel groups of a tile group next to each other on ONE XCD (V is fetched into that
-            // L2 once instead of once per channel group: 59.5 -> 45.7 GB fetched + written per forward, 17.53 -> 17.32 ms at
-            // batch 256); with the in-kernel transform an XCD owns a contiguous range of tile groups (halo rows shared in its L2).
-            // The alternatives (one channel group per XCD; XCD quads splitting the channel groups) measured slower: EXPERIMENTS.md
-            f.map_v = phased ? 2 : 1;
-            f.half_n = half_n ? 1 : 0;
-            f.Uc = L.wuc; f.bias = L.bias; f.slope = L.slope; f.resid = c.resid; f.out = c.out;
-            f.tile_sums = c.tile_sums;
-            f.N = c.N; f.H = c.H; f.W = c.W; f.nkc = L.cin_pad / 8;
-            f.cout_pad = L.cout_pad; f.cout_store = c.cout_store; f.out_pitch = c.out_pitch; f.out_coff = c.out_coff;
-            f.res_pitch = c.res_pitch; f.border_bias = L.border; f.flags = c.flags;
-            const double fexec = 2.0 * 36.0 * (double)((T + 31) / 32 * 32) * (double)L.cout_pad * L.cin_pad;
-#ifdef FFR_TRACE
-            if (h->opt.wf_trace) {     // diagnostics: per-block phase stamps, printed after a stream sync
-                const int nb = wino_fused_blocks(f);
-                unsigned long long* dbuf = nullptr;
-                HIPCK(h, hipMalloc((void**)&dbuf, (size_t)nb * 40 * sizeof(unsigned long long)));
-                HIPCK(h, hipMemsetAsync(dbuf, 0, (size_t)nb * 40 * sizeof(unsigned long long), st));
-                f.trace = dbuf;
-                HIPCK(h, launch_wino_fused(f, st));
-                HIPCK(h, hipStreamSynchronize(st));
-                std::vector<unsigned long long> tr((size_t)nb * 40);
-                HIPCK(h, hipMemcpy(tr.data(), dbuf, tr.size() * 8, hipMemcpyDeviceToHost));
-                HIPCK(h, hipFree(dbuf));
-                double pro = 0, loop = 0, epi = 0, ep[5] = {0, 0, 0, 0, 0}; int cnt = 0;
-                unsigned long long r0 = ~0ull, r1 = 0;
-                for (int b = 0; b < nb; ++b) {
-                    const unsigned long long* q = &tr[(size_t)b * 40];
-                    if (!q[3]) continue;
-                    ep[0] += (double)(q[6] - q[2]); ep[1] += (double)(q[7] - q[6]); ep[2] += (double)(q[8] - q[7]);
-                    ep[3] += (double)(q[9] - q[8]); ep[4] += (double)(q[3] - q[9]);
-                    pro += (double)(q[1] - q[0]); loop += (double)(q[2] - q[1]); epi += (double)(q[3] - q[2]); ++cnt;
-                    if (q[4] > r1) r1 = q[4];
-                    if (q[4] < r0) r0 = q[4];
-                }
-                if (phased) {    // the kernel reports per phase: input transform, wait at the barrier behind it
-                    const int cpp = 4, nph = f.nkc / cpp;                      // K chunks per phase, phases
-                    fprintf(stderr, "[wf trace] %dx%d cin %d cout %d (input transform in the kernel, %d-channel blocks%s): %d live blocks of %d | per block (wave 0): "
-                                    "prologue %.0f loop %.0f = %d phases x (transform %.0f + barrier %.0f + %d K chunks of %.0f) epilogue %.0f cyc | "
-                                    "block ends spread over %.1f us\n", c.H, c.W, L.cin_pad, L.cout_pad, half_n ? 32 : 64, "", cnt, nb,
-                            pro / cnt, loop / cnt, nph, ep[0] / cnt, ep[1] / cnt, cpp, (loop / cnt / nph - ep[0] / cnt - ep[1] / cnt) / cpp, epi / cnt,
-                            (double)(r1 - r0) / 100.0);
-                }
-                else
-                    fprintf(stderr, "[wf trace] %dx%d cin %d cout %d: %d live blocks of %d | per block (wave 0): prologue %.0f loop %.0f (%.0f per K chunk) "
-                                    "epilogue %.0f cyc (to LDS %.0f, transform+store %.0f, barrier+to LDS %.0f, transform+store %.0f, end %.0f) | block ends spread over %.1f us\n",
-                            c.H, c.W, L.cin_pad, L.cout_pad, cnt, nb, pro / cnt, loop / cnt, loop / cnt / f.nkc, epi / cnt, ep[0] / cnt, ep[1] / cnt,
-                            ep[2] / cnt, ep[3] / cnt, ep[4] / cnt, (double)(r1 - r0) / 100.0);
-                if (c.tile_sums && c.tile_sums_written) *c.tile_sums_written = true;
-                return FFR_OK;
-            }
-#endif
-            Scope s(h, st, FFR_KC_WINO_FUSED, flops, bytes, fexec, flops / 4.0);
-            HIPCK(h, launch_wino_fused(f, st));
-            if (c.tile_sums && c.tile_sums_written) *c.tile_sums_written = true;
-            return FFR_OK;
-        }
-        if (L.wu == L.wuc) return fail(h, FFR_ERR_STATE, "Winograd weights exist in the fused kernel's order only, but this launch cannot run fused");
-        if ((size_t)36 * T * L.cin_pad <= c.wino_cap && (size_t)36 * T * L.cout_pad <= c.wino_cap && T < 0x7fffffffLL) {
-            // sub-batches: V and M of one slice (36 * tiles * channels * 4 B each) should stay in the
-            // 256 MiB Infinity Cache between the transform that writes them and the kernel that reads them
-            const int nslice = 1;       // (round 1 ran this path in Infinity-Cache-sized sub-batches: no gain once the fused kernel existed)
-            const int Ns = c.N / nslice;
-            const long long Ts = (long long)Ns * th * tw;
-            for (int sl = 0; sl < nslice; ++sl) {
-                const float* xs = c.x + (size_t)sl * Ns * c.H * c.W * c.in_pitch;
-                const float* rs = c.resid ? c.resid + (size_t)sl * Ns * c.H * c.W * c.res_pitch : nullptr;
-                float* os = c.out + (size_t)sl * Ns * c.H * c.W * c.out_pitch;
-                if (c.took_wino) *c.took_wino = true;
-                if (c.wino_stage != 2) {
-                    Scope s(h, st, FFR_KC_WINO, 0, 4.0 * ((double)Ns * c.H * c.W * L.cin + 36.0 * Ts * L.cin_pad));
-                    HIPCK(h, launch_wino_in(xs, c.winoV, Ns, c.H, c.W, c.in_pitch, L.cin_pad, L.pad_mode, st));
-                }
-                // 36 GEMMs [Ts x cin] * [cin x cout] in one persistent launch with a continuous K-tile stream;
-                // tile shape: fewest rounds of whole tiles over the resident blocks, weighted by loop efficiency
-                const bool use_stream = h->opt.gemm_stream != 0;
-                if (use_stream) {
-                    int gtile = IGEMM_TILE_128x64, gblocks = 768;
-                    double best = 1e300;
-                    for (int tt = IGEMM_TILE_128x128; tt <= IGEMM_TILE_128x64; ++tt) {
-                        int bm, bn;
-                        igemm_tile_shape(tt, &bm, &bn);
-                        if (L.cout_pad % bn) continue;
-                        const long long tiles = 36LL * ((Ts + bm - 1) / bm) * (L.cout_pad / bn);
-                        const long long pmax = 256LL * igemm_resident_blocks(tt);
-                        const long long p = pmax > tiles ? tiles : pmax;
-                        const double rounds = (double)((tiles + p - 1) / p);
-                        // a block gets 1/R of its CU (R co-resident blocks), so a round of tiles costs bm*bn*R;
-                        // the 128x64 loop runs at ~92% of the 128x128 loop's rate (measured per layer, r01 traces)
-                        const double share = (double)((p + 255) / 256);
-                        const double cost = rounds * bm * bn * share / (tt == IGEMM_TILE_128x128 ? 1.0 : 0.92);
-                        if (cost < best) { best = cost; gtile = tt; gblocks = (int)p; }
-                    }
-                    GemmStreamArgs g{};
-                    g.A = c.winoV; g.W = L.wu; g.C = c.winoM; g.M = (int)Ts; g.K = L.cin_pad; g.Npad = L.cout_pad; g.nbatch = 36;
-                    int bm, bn;
-                    igemm_tile_shape(gtile, &bm, &bn);
-                    const double fexec = 2.0 * 36.0 * (double)((Ts + bm - 1) / bm) * bm * (double)L.cout_pad * L.cin_pad;
-                    // the roofline numerator stays the DIRECT convolution's algorithmic FLOPs
-                    Scope s(h, st, FFR_KC_CONV_IGEMM, flops / nslice, bytes / nslice, fexec, flops / nslice / 4.0);
-                    HIPCK(h, launch_gemm_stream(g, gtile, gblocks, st));
-                } else {
-                IgemmArgs g{};
-                g.x = c.winoV; g.w = L.wu; g.bias = h->zero; g.slope = nullptr; g.resid = nullptr; g.out = c.winoM; g.zero = h->zero;
-                g.N = 1; g.H = 1; g.W = (int)Ts; g.Ho = 1; g.Wo = (int)Ts;
-                g.in_pitch = L.cin_pad; g.cin_pad = L.cin_pad; g.R = 1; g.S = 1; g.stride = 1; g.pad = 0; g.pad_mode = 0;
-                g.M = (int)Ts; g.KK = L.cin_pad; g.nkt = L.cin_pad / 32;
-                g.cout_pad = L.cout_pad; g.cout_store = L.cout_pad; g.out_pitch = L.cout_pad; g.out_coff = 0; g.res_pitch = 0;
-                g.border_bias = 0; g.flags = 0;
-                g.nbatch = 36;
-                g.x_bstride = Ts * L.cin_pad; g.w_bstride = (long long)L.cout_pad * L.cin_pad; g.out_bstride = Ts * L.cout_pad;
-                // the roofline numerator stays the DIRECT convolution's algorithmic FLOPs
-                RC(run_gemm(h, g, c, flops / nslice, bytes / nslice, st, flops / nslice / 4.0));
-                }
-                if (c.wino_stage == 1) continue;        // the caller transforms M itself (k_wino_out_in)
-                Scope s(h, st, FFR_KC_WINO, 0, 4.0 * (36.0 * Ts * L.cout_pad + (double)M / nslice * L.cout));
-                const bool sums = c.tile_sums && nslice == 1;
-                HIPCK(h, launch_wino_out(c.winoM, L.bias, L.slope, rs, c.res_pitch, os, c.out_pitch, c.out_coff,
-                                         c.cout_store, L.cout_pad, Ns, c.H, c.W, L.border, c.flags, st,
-                                         sums ? c.tile_sums : nullptr));
-                if (sums && c.tile_sums_written) *c.tile_sums_written = true;
-            }
-            return FFR_OK;
-        }
-    }
+    IgemmArgs a{};
+    a.x = c.x; a.w = L.w; a.bias = L.bias; a.slope = L.slope; a.resid = c.resid; a.out = c.out; a.zero = h->zero;
+    a.N = c.N; a.H = c.H; a.W = c.W; a.Ho = Ho; a.Wo = Wo;
+    a.in_pitch = c.in_pitch; a.cin_pad = L.cin_pad; a.R = L.R; a.S = L.S; a.stride = L.stride; a.pad = L.pad; a.pad_mode = L.pad_mode;
+    a.M = (int)M; a.KK = L.R * L.S * L.cin_pad; a.nkt = a.KK / 32; a.nbatch = 1;
+    a.cout_pad = L.cout_pad; a.cout_store = c.cout_store; a.out_pitch = c.out_pitch; a.out_coff = c.out_coff;
+    a.res_pitch = c.res_pitch; a.border_bias = L.border; a.flags = c.flags;
     return run_gemm(h, a, c, flops, bytes, st);
 }
 
@@ -834,42 +831,40 @@ int run_trunk(ffr_handle* h, const Work& w, const float* x_nchw, int N, int H, i
     float* cur = w.bufA;
     float* nxt = w.bufB;
     int ch = H, cw = W, cc = 64;
+    auto conv1_call = [&](const Block& b, const float* x, int hh, int ww) {
+        ConvCall c = conv_call(w);
+        c.x = x; c.N = N; c.H = hh; c.W = ww; c.in_pitch = b.cin;
+        c.out = w.t1; c.out_pitch = b.depth; c.cout_store = b.depth;
+        return c;
+    };
     bool v_ready = false, v_mixed = false;  // winoV holds the transform of `cur` in the order k_wino_fused (/ k_wino_fused_mixed) streams
     for (int i = 0; i < n_blocks; ++i) {
         const Block& b = h->blocks[i];
         const int ho = ch / b.stride, wo = cw / b.stride;
-        ConvCall c1{};
-        c1.x = cur; c1.N = N; c1.H = ch; c1.W = cw; c1.in_pitch = b.cin;
-        c1.out = w.t1; c1.out_pitch = b.depth; c1.cout_store = b.depth;
-        c1.partial = w.partial; c1.partial_cap = w.partial_cap; c1.tickets = w.tickets; c1.tickets_cap = w.tickets_cap; c1.winoV = w.winoV; c1.winoM = w.winoM; c1.wino_cap = w.wino_cap;
+        ConvCall c1 = conv1_call(b, cur, ch, cw);
         // conv1 -> conv2 without the activation round trip when both run as Winograd on a map of <= 4x4 tiles
         const long long Tt = (long long)N * ((ch + 3) / 4) * ((cw + 3) / 4);
-        bool chained = false;
-        const bool fused_on = h->opt.wino_fused != 0;
-        if (!fused_on && b.stride == 1 && b.c1.wu && b.c2.wu && !b.c1.direct && !b.c2.direct && b.c1.cout_pad == b.c2.cin_pad && b.c2.pad_mode == 0 &&
-            wino_out_in_supported(ch, cw, b.c1.cout_pad) && (size_t)36 * Tt * b.c1.cout_pad <= w.wino_cap &&
-            (size_t)36 * Tt * b.c1.cin_pad <= w.wino_cap && (size_t)36 * Tt * b.c2.cout_pad <= w.wino_cap) {
-            c1.wino_stage = 1; c1.took_wino = &chained;
-        }
+        if (!h->opt.wino_fused && b.stride == 1 && b.c1.wu && b.c2.wu && !b.c1.direct && !b.c2.direct && b.c1.cout_pad == b.c2.cin_pad &&
+            b.c2.pad_mode == 0 && wino_out_in_supported(ch, cw, b.c1.cout_pad) && (size_t)36 * Tt * b.c1.cout_pad <= w.wino_cap &&
+            (size_t)36 * Tt * b.c1.cin_pad <= w.wino_cap && (size_t)36 * Tt * b.c2.cout_pad <= w.wino_cap)
+            c1.wino_stage = 1;
         if (v_ready) { c1.wino_stage = 2; c1.v_chunked = !v_mixed; c1.v_mixed = v_mixed; }
+        const bool chained = c1.wino_stage == 1 && plan_conv(h, b.c1, c1).path == ConvPlan::Unfused;
         RC(run_conv(h, b.c1, c1, st));
         if (chained) {
             Scope s(h, st, FFR_KC_WINO, 0, 4.0 * 72.0 * Tt * b.c1.cout_pad);
             HIPCK(h, launch_wino_out_in(w.winoM, b.c1.bias, b.c1.slope, w.winoV, N, ch, cw, b.c1.cout_pad, b.c1.border, st));
         }
-        ConvCall c2{};
+        ConvCall c2 = conv_call(w);
         c2.x = w.t1; c2.N = N; c2.H = ch; c2.W = cw; c2.in_pitch = b.depth;
         c2.out = w.res; c2.out_pitch = b.depth; c2.cout_store = b.depth;
-        c2.partial = w.partial; c2.partial_cap = w.partial_cap; c2.tickets = w.tickets; c2.tickets_cap = w.tickets_cap; c2.winoV = w.winoV; c2.winoM = w.winoM; c2.wino_cap = w.wino_cap;
+        if (chained) c2.wino_stage = 2;
         // SE squeeze: the Winograd output transform of conv2 leaves one partial sum per 4x4 tile in se_part
         // ([N][tiles][C], the layout k_se_fc reads); the direct path (stride 2, 64 channels) pools separately
-        bool pooled = false;
         const int tiles = ((ho + 3) / 4) * ((wo + 3) / 4);
-        const int se_maxtiles = h->opt.se_maxtiles;
-        if (b.fc1 && b.stride == 1 && tiles <= se_maxtiles && (size_t)tiles * b.depth <= (size_t)32 * 512 && b.c2.cout_pad == b.depth) {
-            c2.tile_sums = w.se_part; c2.tile_sums_written = &pooled;
-        }
-        if (chained) c2.wino_stage = 2;
+        if (b.fc1 && b.stride == 1 && tiles <= h->opt.se_maxtiles && (size_t)tiles * b.depth <= (size_t)32 * 512 && b.c2.cout_pad == b.depth)
+            c2.tile_sums = w.se_part;
+        const bool pooled = c2.tile_sums && plan_conv(h, b.c2, c2).path != ConvPlan::Direct;
         RC(run_conv(h, b.c2, c2, st));
         const float* se_scale = nullptr;          // bottleneck_IR (mode 'ir'): no SEModule, the combine is res + shortcut
         if (b.fc1) {
@@ -881,32 +876,29 @@ int run_trunk(ffr_handle* h, const Work& w, const float* x_nchw, int N, int H, i
         }
         const float* scp = nullptr;
         if (b.has_sc) {
-            ConvCall cs{};
+            ConvCall cs = conv_call(w);
             cs.x = cur; cs.N = N; cs.H = ch; cs.W = cw; cs.in_pitch = b.cin;
             cs.out = w.sc; cs.out_pitch = b.depth; cs.cout_store = b.depth;
-            cs.partial = w.partial; cs.partial_cap = w.partial_cap; cs.tickets = w.tickets; cs.tickets_cap = w.tickets_cap; cs.winoV = w.winoV; cs.winoM = w.winoM; cs.wino_cap = w.wino_cap;
             RC(run_conv(h, b.sc, cs, st));
             scp = w.sc;
         }
         // the next unit's conv1 reads this unit's output through its Winograd transform: when that conv runs k_wino_fused
         // from V (cin >= 256: stage 3 and 4), the combine writes V itself and the separate transform pass is skipped
-        v_ready = false; v_mixed = false;
-        if (h->opt.combine_v && i + 1 < n_blocks && (scp || b.stride == 1) && b.depth % 32 == 0 &&
-            wino_mixed_applies(h, h->blocks[i + 1].c1, N, ho, wo, b.depth, w.wino_cap, -1)) {
+        ConvPlan next;
+        if (h->opt.combine_v && i + 1 < n_blocks && (scp || b.stride == 1))
+            next = plan_conv(h, h->blocks[i + 1].c1, conv1_call(h->blocks[i + 1], nxt, ho, wo));
+        v_mixed = next.path == ConvPlan::Mixed && b.depth % 32 == 0;
+        v_ready = v_mixed || (next.takes_v && combine_in_c_supported(ho, wo, b.depth));
+        const double e = (double)N * ho * wo * b.depth;
+        if (v_mixed) {
             WinoMixedGeom mg;
             wino_mixed_geom(ho, wo, &mg);
-            const double e = (double)N * ho * wo * b.depth;
             Scope s(h, st, FFR_KC_COMBINE, 2.0 * e, 4.0 * (3.0 * e + (double)wino_mixed_v_floats(mg, N, b.depth, nullptr)));
             HIPCK(h, launch_combine_in_mixed(w.res, se_scale, scp ? scp : cur, nxt, w.winoV, N, ho, wo, b.depth, st));
-            v_ready = true; v_mixed = true;
-        } else if (h->opt.combine_v && i + 1 < n_blocks && (scp || b.stride == 1) && combine_in_c_supported(ho, wo, b.depth) &&
-            wino_accepts_ready_v(h, h->blocks[i + 1].c1, N, ho, wo, b.depth, w.wino_cap)) {
-            const double e = (double)N * ho * wo * b.depth;
+        } else if (v_ready) {
             Scope s(h, st, FFR_KC_COMBINE, 2.0 * e, 4.0 * (3.0 * e + 36.0 * N * ((ho + 3) / 4) * ((wo + 3) / 4) * b.depth));
             HIPCK(h, launch_combine_in_c(w.res, se_scale, scp ? scp : cur, nxt, w.winoV, N, ho, wo, b.depth, st));
-            v_ready = true;
         } else {
-            const double e = (double)N * ho * wo * b.depth;
             Scope s(h, st, FFR_KC_COMBINE, 2.0 * e, 12.0 * e);
             HIPCK(h, launch_combine(w.res, se_scale, scp, cur, nxt, N, ho, wo, b.depth, b.stride, st));
         }
@@ -929,10 +921,9 @@ int run_encoder(ffr_handle* h, const Work& w, const float* x, int N, int H, int 
     }
     if (f) {
         if (P != 49) return fail(h, FFR_ERR_UNSUPPORTED, "output_layer needs a 7x7 trunk map (112x112 input)");
-        ConvCall c{};
+        ConvCall c = conv_call(w);
         c.x = t; c.N = N; c.H = 1; c.W = 1; c.in_pitch = 25088;
         c.out = w.scale; c.out_pitch = 512; c.cout_store = 512;     // SE scale buffer is free here
-        c.partial = w.partial; c.partial_cap = w.partial_cap; c.tickets = w.tickets; c.tickets_cap = w.tickets_cap; c.winoV = w.winoV; c.winoM = w.winoM; c.wino_cap = w.wino_cap;
         RC(run_conv(h, h->fc, c, st));
         Scope s(h, st, FFR_KC_HEAD, 3.0 * N * 512, 8.0 * N * 512);
         HIPCK(h, launch_head_finish(w.scale, 1, N, 512, nullptr, f, st));
@@ -944,10 +935,9 @@ int run_encoder(ffr_handle* h, const Work& w, const float* x, int N, int H, int 
 
 int conv_rec(ffr_handle* h, const Work& w, const ConvW& L, const float* x, int in_pitch, const float* resid,
              int res_pitch, float* out, int out_pitch, int out_coff, int flags, int N, hipStream_t st) {
-    ConvCall c{};
+    ConvCall c = conv_call(w);
     c.x = x; c.N = N; c.H = 7; c.W = 7; c.in_pitch = in_pitch; c.resid = resid; c.res_pitch = res_pitch;
     c.out = out; c.out_pitch = out_pitch; c.out_coff = out_coff; c.cout_store = L.cout_pad; c.flags = flags;
-    c.partial = w.partial; c.partial_cap = w.partial_cap; c.tickets = w.tickets; c.tickets_cap = w.tickets_cap; c.winoV = w.winoV; c.winoM = w.winoM; c.wino_cap = w.wino_cap;
     return run_conv(h, L, c, st);
 }
 
@@ -1733,10 +1723,10 @@ int ffr_op_conv(ffr_handle* h, const ffr_conv_desc* d, void* stream) {
     L.cin = L.cin_pad = d->cin_pad; L.cout = d->cout_store; L.cout_pad = d->cout_pad; L.R = d->R; L.S = d->S;
     L.stride = d->stride; L.pad = d->pad; L.pad_mode = d->pad_mode; L.border = d->border_bias;
     L.w = (float*)d->w; L.bias = (float*)d->bias; L.slope = (float*)d->slope;
-    ConvCall c{};
+    ConvCall c = conv_call(w);
     c.x = d->x; c.N = d->N; c.H = d->H; c.W = d->W; c.in_pitch = d->in_pitch; c.resid = d->resid; c.res_pitch = d->res_pitch;
     c.out = d->out; c.out_pitch = d->out_pitch; c.out_coff = d->out_coff; c.cout_store = d->cout_store; c.flags = d->flags;
-    c.tile = d->tile; c.partial = w.partial; c.partial_cap = w.partial_cap; c.tickets = w.tickets; c.tickets_cap = w.tickets_cap; c.winoV = w.winoV; c.winoM = w.winoM; c.wino_cap = w.wino_cap;
+    c.tile = d->tile;
     return run_conv(h, L, c, (hipStream_t)stream);
 }
 
@@ -1746,6 +1736,7 @@ int ffr_op_conv3x3(ffr_handle* h, const float* x, int N, int H, int W, int cin, 
     FFR_DEVICE_SCOPE(h); RC(check_fwd(h, false, false, N));
     if (!x || !w_host || !bias_host || !out || cin % 32 || cout % 4 || cin <= 0 || cout <= 0)
         return fail(h, FFR_ERR_ARG, "ffr_op_conv3x3: bad arguments (cin %% 32, cout %% 4)");
+    if (use_wino < 0 || use_wino > 4) return fail(h, FFR_ERR_ARG, "ffr_op_conv3x3: use_wino must be 0..4");
     hipStream_t st = (hipStream_t)stream;
     Work w;
     RC(ensure_arena(h, N > 8 ? N : 8, 112, 112, &w));
@@ -1757,16 +1748,13 @@ int ffr_op_conv3x3(ffr_handle* h, const float* x, int N, int H, int W, int cin, 
     int rc = pack_conv(h, own, w_host, cout, cin, 3, 3, nullptr, &ob, slope_host, 1, 1, pad_mode, &L);
     if (rc == FFR_OK && use_wino && !L.wu) rc = fail(h, FFR_ERR_UNSUPPORTED, "layer not eligible for the Winograd path (cin < FFR_WINO_MINCIN)");
     if (rc == FFR_OK && use_wino == 4) {
-        if (!wino_mixed_eligible(h, L, N, H, W, cin, w.wino_cap, 4)) rc = fail(h, FFR_ERR_UNSUPPORTED, "layer / map not eligible for the mixed-tile path");
+        if (!wino_mixed_eligible(h, L, N, H, W, cin, w.wino_cap, ConvForce::Mixed)) rc = fail(h, FFR_ERR_UNSUPPORTED, "layer / map not eligible for the mixed-tile path");
         else rc = ensure_mixed_weights(h, L, own, true);
     }
     if (rc == FFR_OK) {
-        ConvCall c{};
+        ConvCall c = conv_call(w, (ConvForce)use_wino);
         c.x = x; c.N = N; c.H = H; c.W = W; c.in_pitch = cin; c.resid = resid; c.res_pitch = cout;
         c.out = out; c.out_pitch = cout; c.out_coff = 0; c.cout_store = cout;
-        c.partial = w.partial; c.partial_cap = w.partial_cap; c.tickets = w.tickets; c.tickets_cap = w.tickets_cap;
-        c.winoV = w.winoV; c.winoM = w.winoM; c.wino_cap = w.wino_cap;
-        c.wino_mode = use_wino;        // 0 direct, 1 Winograd fused (k_wino_fused, 32 x 64 blocks), 2 Winograd as batched GEMM + transform kernels, 3 fused with 32 x 32 blocks
         rc = run_conv(h, L, c, st);
         if (rc == FFR_OK && use_wino && (size_t)36 * N * ((H + 3) / 4) * ((W + 3) / 4) * (L.cin_pad > L.cout_pad ? L.cin_pad : L.cout_pad) > w.wino_cap)
             rc = fail(h, FFR_ERR_NOMEM, "Winograd scratch too small for this test shape");

@@ -201,29 +201,42 @@ bool bn_fold(SD& sd, const std::string& p, int C, BNFold& o);
 int upload(ffr_handle* h, std::vector<void*>& owner, const std::vector<float>& v, float** out);
 void free_list(std::vector<void*>& v);
 
+// What a caller asks of a convolution's arithmetic; the values are those of use_wino in ffr_op_conv3x3.  Auto: the planner
+// decides (option wino, the layer's plan, wino_fused_form, the tail split).  Fused / FusedHalf: k_wino_fused with 32 x 64 /
+// 32 x 32 blocks.  Unfused: transform kernels + batched GEMM.  Mixed: the exact 4+4+3+3 tiling of a 14x14 map.
+enum class ConvForce { Auto = -1, Direct = 0, Fused = 1, Unfused = 2, FusedHalf = 3, Mixed = 4 };
+
 struct ConvCall {
     const float* x; int N, H, W, in_pitch;
     const float* resid; int res_pitch;
     float* out; int out_pitch, out_coff, cout_store;
-    int flags; int tile; int splitk;      // splitk: ignored (stream-K balances K itself)
+    int flags; int tile;
     float* partial; size_t partial_cap;   // floats
     int* tickets; size_t tickets_cap;
     float* winoV; float* winoM; size_t wino_cap;   // Winograd scratch (floats each), or null
-    int wino_mode = -1;                            // -1 auto (option "wino"; the form of the fused kernel from wino_fused_choice), 0 never, 1 Winograd in k_wino_fused (32 x 64 blocks), 2 Winograd as transform kernels + batched GEMM, 3 k_wino_fused with 32 x 32 blocks, 4 the exact 4+4+3+3 tiling of a 14x14 map (k_wino_fused_mixed; cin_pad 256, zero padding)
+    ConvForce force = ConvForce::Auto;
     int wino_stage = 0;                            // 0 whole conv; 1 stop after the GEMM (M stays in winoM); 2 V is ready in winoV
     bool v_mixed = false;                          // with wino_stage 2: V is in the four-region layout of wino_mixed.hip (k_combine_in_mixed wrote it)
-    bool v_chunked = false;                        // with wino_stage 2: V is in the K-chunked fragment order of k_wino_fused (wino_accepts_ready_v)
-    bool* took_wino = nullptr;                     // set to true when the Winograd path ran
-    float* tile_sums = nullptr;                    // Winograd path only: per-tile sums of the stored outputs [T][cout_pad]
-    bool* tile_sums_written = nullptr;             // set to true when the Winograd path wrote them
+    bool v_chunked = false;                        // with wino_stage 2: V is in the K-chunked fragment order of k_wino_fused (ConvPlan::takes_v)
+    float* tile_sums = nullptr;                    // Winograd paths only: per-tile sums of the stored outputs [T][cout_pad]
 };
 
-// Does layer L run Winograd when the caller leaves the choice to the planner (wino_mode -1)?  Option wino and the layer's plan.
+// Which kernels one convolution launches and how (plan_conv; run_conv's conv_* launch each path)
+struct ConvPlan {
+    enum Path { Direct, Mixed, Fused, Unfused } path = Direct;
+    bool half_n = false;            // Fused: blocks of 32 tiles x 32 channels (else 32 x 64)
+    bool phased = false;            // Fused: the kernel transforms its own input, V never exists in memory
+    int n_main = 0;                 // Fused: the first n_main images run fused and the rest Unfused (0: no split)
+    hipStream_t side = nullptr;     // ... the rest is enqueued first, on this stream (null: after the main part on the launch stream)
+    bool takes_v = false;           // the whole conv runs fused from a V in k_wino_fused's order (a combine may write it)
+    const char* refused = nullptr;  // the call cannot run as asked: why (run_conv fails with FFR_ERR_STATE)
+};
+
+// Does layer L run Winograd when the caller leaves the choice to the planner (ConvForce::Auto)?  Option wino and the layer's plan.
 inline bool layer_wino(const ffr_handle* h, const ConvW& L) { return h->opt.wino != 0 && !L.direct; }
-int wino_fused_choice(const ffr_handle* h, int cin_pad, int cout_pad, long long T, double x_bytes, int wino_mode);
-bool wino_accepts_ready_v(const ffr_handle* h, const ConvW& L, int N, int H, int W, int in_pitch, size_t wino_cap);
-bool wino_mixed_applies(const ffr_handle* h, const ConvW& L, int N, int H, int W, int in_pitch, size_t wino_cap, int wino_mode);
-bool wino_mixed_eligible(const ffr_handle* h, const ConvW& L, int N, int H, int W, int in_pitch, size_t wino_cap, int wino_mode);
+ConvForce wino_fused_form(const ffr_handle* h, int cin_pad, int cout_pad, long long T, double x_bytes, ConvForce ask);
+bool wino_mixed_eligible(const ffr_handle* h, const ConvW& L, int N, int H, int W, int in_pitch, size_t wino_cap, ConvForce force);
+ConvPlan plan_conv(const ffr_handle* h, const ConvW& L, const ConvCall& c);
 int ensure_mixed_weights(ffr_handle* h, ConvW& L, std::vector<void*>& owner, bool strict);
 int prepare_mixed_weights(ffr_handle* h, int N, int H, int W, size_t wino_cap);
 int run_gemm(ffr_handle* h, IgemmArgs& a, const ConvCall& c, double flops, double bytes, hipStream_t st, double fuse = -1.0);
@@ -253,6 +266,12 @@ struct Work {
 };
 
 Work layout(const Options& opt, char* base, int N, int H, int W);
+inline ConvCall conv_call(const Work& w, ConvForce force = ConvForce::Auto) {     // a call with the scratch of w; the rest to fill in
+    ConvCall c{};
+    c.partial = w.partial; c.partial_cap = w.partial_cap; c.tickets = w.tickets; c.tickets_cap = w.tickets_cap;
+    c.winoV = w.winoV; c.winoM = w.winoM; c.wino_cap = w.wino_cap; c.force = force;
+    return c;
+}
 int ensure_arena(ffr_handle* h, int N, int H, int W, Work* w);
 int ensure_arena_encoder(ffr_handle* h, int N, int H, int W, Work* w);     // + the exact-tiling weight sets an encoder forward of this size uses
 struct U8In { const unsigned char* img; const unsigned char* flip; };

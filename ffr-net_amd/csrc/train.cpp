@@ -68,12 +68,6 @@ int gemm_batched(ffr_handle* h, const Work& w, const float* A, long long a_bstri
                  long long w_bstride, int N_pad, float* out, int out_pitch, long long out_bstride, int M, int nbatch,
                  hipStream_t st);
 
-void conv_call_common(ConvCall& c, const Work& w, bool wino = false) {
-    c.partial = w.partial; c.partial_cap = w.partial_cap; c.tickets = w.tickets; c.tickets_cap = w.tickets_cap;
-    c.winoV = wino ? w.winoV : nullptr; c.winoM = wino ? w.winoM : nullptr; c.wino_cap = wino ? w.wino_cap : 0;
-    c.wino_mode = wino ? 1 : 0;
-}
-
 // y = conv(reflect_pad(x)); batch statistics; out = PReLU(BN(y)) (+ resid) (sigmoid when flags & 1)
 int layer_forward(ffr_handle* h, const Work& w, const TLayer& L, TSaved& sv, int G, int N, const float* resid,
                   int res_pitch, float* out, int out_pitch, int out_coff, int flags, bool update_running, TScratch& s,
@@ -85,19 +79,19 @@ int layer_forward(ffr_handle* h, const Work& w, const TLayer& L, TSaved& sv, int
     // Winograd F(4x4,3x3) as the inference path; U = G g G^T from the live weights
     const bool wino = s.wino && L.cin_pad >= 128 && s.U && (size_t)36 * L.cout_pad * L.cin_pad <= s.U_floats;
     // ... emitted in the order k_wino_fused streams when the launch can run fused (the kernel of the inference path: GEMMs +
-    // output transform in one launch, raw convolution output for the batch statistics)
-    int fused = 0;
+    // output transform in one launch, raw convolution output for the batch statistics).  The planner's form of the fused
+    // kernel (option "fused" 1; 2: always fused, 0: never), never Auto: the training step splits off no tail.
+    ConvCall c = conv_call(w, ConvForce::Direct);
     if (wino) {
-        fused = s.fused ? wino_fused_choice(h, L.cin_pad, L.cout_pad, (long long)G * N * 4, 4.0 * G * N * 49 * sv.x_pitch, s.fused == 2 ? 1 : -1) : 0;
+        c.force = s.fused ? wino_fused_form(h, L.cin_pad, L.cout_pad, (long long)G * N * 4, 4.0 * G * N * 49 * sv.x_pitch,
+                                            s.fused == 2 ? ConvForce::Fused : ConvForce::Auto) : ConvForce::Unfused;
+        const bool fused = c.force != ConvForce::Unfused;
         TLAUNCH(FFR_KC_TRAIN_XFORM, launch_wino_weights(L.w, s.U, L.cout_pad, L.cin_pad, st, fused ? 1 : 0));
         cw.wu = s.U;
         if (fused) cw.wuc = s.U;
     }
-    ConvCall c{};
     c.x = sv.x; c.N = G * N; c.H = 7; c.W = 7; c.in_pitch = sv.x_pitch;
     c.out = sv.y; c.out_pitch = L.cout_pad; c.out_coff = 0; c.cout_store = L.cout_pad;
-    conv_call_common(c, w, wino);
-    if (wino) c.wino_mode = fused == 2 ? 3 : (fused == 1 ? 1 : 2);
     RC(run_conv(h, cw, c, st));
     TLAUNCH(FFR_KC_TRAIN_BN, launch_bn_stats(sv.y, L.cout_pad, G, N * 49, L.gamma, L.beta, update_running ? L.rmean : nullptr,
                              update_running ? L.rvar : nullptr, BN_MOMENTUM, BN_EPS_F, sv.bn, part, st));
@@ -152,7 +146,7 @@ int layer_backward(ffr_handle* h, const Work& w, const TLayer& L, const TSaved& 
     ConvW cw;
     cw.cin = L.cout_pad; cw.cin_pad = L.cout_pad; cw.cout = need_pad; cw.cout_pad = need_pad; cw.R = 3; cw.S = 3;
     cw.stride = 1; cw.pad = 2; cw.pad_mode = 0; cw.border = 0; cw.w = s.wd; cw.bias = h->zero; cw.slope = nullptr; cw.wu = nullptr;
-    ConvCall c{};
+    ConvCall c = conv_call(w, ConvForce::Direct);
     c.x = s.dy; c.N = G * N; c.H = 7; c.W = 7; c.in_pitch = L.cout_pad;
     c.out = s.dxp; c.out_pitch = need_pad; c.out_coff = 0; c.cout_store = need_pad;
     const int imgs = G * N;
@@ -163,14 +157,14 @@ int layer_backward(ffr_handle* h, const Work& w, const TLayer& L, const TSaved& 
         // The 9x9 padded gradient in three pieces: rows/columns 0..7 as the 'same' F(4x4,3x3) convolution of dy embedded at
         // (1,1) of an 8x8 map (2x2 tiles instead of the 3x3 a 9x9 output would need), row 8 and column 8 (only the last
         // weight row / column reaches them) as two GEMMs with K = 3*cout.
-        const int fused = s.fused ? wino_fused_choice(h, L.cout_pad, need_pad, (long long)imgs * 4, 4.0 * imgs * 64 * L.cout_pad, s.fused == 2 ? 1 : -1) : 0;
+        c.force = s.fused ? wino_fused_form(h, L.cout_pad, need_pad, (long long)imgs * 4, 4.0 * imgs * 64 * L.cout_pad,
+                                            s.fused == 2 ? ConvForce::Fused : ConvForce::Auto) : ConvForce::Unfused;
+        const bool fused = c.force != ConvForce::Unfused;
         TLAUNCH(FFR_KC_TRAIN_XFORM, launch_wino_weights(s.wd, s.U, need_pad, L.cout_pad, st, fused ? 1 : 0));
         TLAUNCH(FFR_KC_TRAIN_XFORM, launch_embed_8x8(s.dy, s.canvas, imgs, L.cout_pad, st));
         cw.wu = s.U; cw.pad = 1;
         if (fused) cw.wuc = s.U;
         c.x = s.canvas; c.H = 8; c.W = 8;
-        conv_call_common(c, w, true);
-        c.wino_mode = fused == 2 ? 3 : (fused == 1 ? 1 : 2);
         RC(run_conv(h, cw, c, st));
         float* Eb = s.edgeA;
         float* Er = s.edgeA + (size_t)imgs * 9 * 3 * L.cout_pad;
@@ -189,7 +183,6 @@ int layer_backward(ffr_handle* h, const Work& w, const TLayer& L, const TSaved& 
                                       dx_coff, st));
         return FFR_OK;
     }
-    conv_call_common(c, w, false);
     RC(run_conv(h, cw, c, st));
     const int cfold = round_up(cin_need, 4);
     TLAUNCH(FFR_KC_TRAIN_XFORM, launch_fold_reflect(s.dxp, need_pad, G * N, cfold, add, add_pitch, add_coff, dx, dx_pitch, dx_coff, st));
@@ -239,10 +232,9 @@ int gemm_rows(ffr_handle* h, const Work& w, const float* A, int a_pitch, int K_p
     cw.cin = K_pad; cw.cin_pad = K_pad; cw.cout = N_pad; cw.cout_pad = N_pad; cw.R = 1; cw.S = 1; cw.stride = 1; cw.pad = 0;
     cw.pad_mode = 0; cw.border = 0; cw.w = const_cast<float*>(W); cw.bias = bias ? const_cast<float*>(bias) : h->zero;
     cw.slope = nullptr; cw.wu = nullptr;
-    ConvCall c{};
+    ConvCall c = conv_call(w, ConvForce::Direct);
     c.x = A; c.N = 1; c.H = 1; c.W = (int)rows; c.in_pitch = a_pitch; c.resid = resid; c.res_pitch = res_pitch;
     c.out = out; c.out_pitch = out_pitch; c.out_coff = 0; c.cout_store = N_pad; c.flags = flags;
-    conv_call_common(c, w);
     return run_conv(h, cw, c, st);
 }
 
@@ -258,8 +250,7 @@ int gemm_batched(ffr_handle* h, const Work& w, const float* A, long long a_bstri
     g.cout_pad = N_pad; g.cout_store = N_pad; g.out_pitch = out_pitch; g.out_coff = 0; g.res_pitch = 0;
     g.border_bias = 0; g.flags = 0;
     g.nbatch = nbatch; g.x_bstride = a_bstride; g.w_bstride = w_bstride; g.out_bstride = out_bstride;
-    ConvCall c{};
-    conv_call_common(c, w);
+    const ConvCall c = conv_call(w, ConvForce::Direct);
     const double fl = 2.0 * nbatch * (double)M * N_pad * K_pad;
     return run_gemm(h, g, c, fl, 4.0 * nbatch * ((double)M * K_pad + (double)N_pad * K_pad + (double)M * N_pad), st);
 }
