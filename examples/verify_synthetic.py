@@ -2,7 +2,7 @@
 """Verification end to end on synthetic LFW-shaped pairs (needs an MI355X): the counterpart of
 `python train.py --phase test` -> eval_lfw -> lfw_eval.get_avg_accuracy (train.py:101-113, lfw/lfw_eval.py:272-287).
 
-    python examples/verify_synthetic.py [--pairs 600] [--batch 100]
+    python examples/verify_synthetic.py [--pairs 600] [--batch 100] [--uint8]
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/verify_synthetic.py
 
 With real weights: replace the synthetic state_dicts by torch.load('pretrain/se50.pth') and
@@ -20,6 +20,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--pairs', type=int, default=600)
     ap.add_argument('--batch', type=int, default=100)
+    ap.add_argument('--uint8', action='store_true', help='a host loader of decoded uint8 images + per-pair flip flags (the '
+                    'input step runs in the stem kernel) instead of device-resident fp32 tensors')
     a = ap.parse_args()
     world, local = int(os.environ.get('WORLD_SIZE', '1')), int(os.environ.get('LOCAL_RANK', '0'))
     torch.cuda.set_device(local)
@@ -30,10 +32,15 @@ def main():
     eng = ffrnet_amd.Engine(local)
     eng.load_encoder(synth.synth_state_dict(specs['encoder']))
     eng.load_recnet(synth.synth_state_dict(specs['recnet']))
-    i1, i2, lab = synth.synth_pairs(a.pairs, seed=7, block=max(2, a.pairs // 10))     # 10 blocks: half same, half different
     dev = torch.device('cuda', local)
-    loader = [dict(img1=i1[s:s + a.batch].to(dev), img2=i2[s:s + a.batch].to(dev), label=lab[s:s + a.batch],
-                   idx=torch.arange(s, min(s + a.batch, a.pairs))) for s in range(0, a.pairs, a.batch)]
+    if a.uint8:
+        i1, i2, lab, flip = synth.synth_pairs_u8(a.pairs, seed=7, block=max(2, a.pairs // 10))
+        loader = [dict(img1=i1[s:s + a.batch], img2=i2[s:s + a.batch], label=lab[s:s + a.batch], flip=flip[s:s + a.batch],
+                       idx=torch.arange(s, min(s + a.batch, a.pairs))) for s in range(0, a.pairs, a.batch)]
+    else:
+        i1, i2, lab = synth.synth_pairs(a.pairs, seed=7, block=max(2, a.pairs // 10))     # 10 blocks: half same, half different
+        loader = [dict(img1=i1[s:s + a.batch].to(dev), img2=i2[s:s + a.batch].to(dev), label=lab[s:s + a.batch],
+                       idx=torch.arange(s, min(s + a.batch, a.pairs))) for s in range(0, a.pairs, a.batch)]
     # pairs sharded over the ranks, ONE all-gather of the embeddings per batch, scores and the 10-fold threshold protocol on
     # the device (ffr_cosine_scores, ffr_lfw_fold_accuracy); with the two nn.Module shells the call is the reference's:
     #     acc_new, acc = ffrnet_amd.lfw.get_avg_accuracy(encoder, recnet, data_loader)

@@ -27,17 +27,27 @@ __device__ __forceinline__ float wave_sum(float v) {
 #define STEM_TLD 36
 // U8 = true: the input is the decoded image itself, uint8 [N,H,W,3] RGB, and the reference's input
 // step is applied on the fly (data/dataset.py:70-79, data/dataloader.py:24-28): RGB->BGR channel
-// swap, optional horizontal flip (one flag per image), ToTensor (/255) and Normalize(0.5, 0.5),
-// each in fp32 with the same roundings as torch -> bit-identical stem input, 4x less input traffic.
+// swap, optional horizontal flip, ToTensor (/255) and Normalize(0.5, 0.5), each in fp32 with the
+// same roundings as torch -> bit-identical stem input, 4x less input traffic.
+// Both forms read images [0, n_split) from the first buffer (x / xu8) and [n_split, N) from the second
+// (x2 / xu8b) -- the clean | occluded halves of a training batch.  The flip flag of image n is
+// flip[n mod n_split]: one flag per image of a single buffer, one per PAIR (image n and n + n_split,
+// data/dataset.py:139-151 flips img and mask together) of a training batch.
 template <bool U8>
 __global__ __launch_bounds__(256) void k_stem(const float* __restrict__ x, const unsigned char* __restrict__ xu8,
                                              const unsigned char* __restrict__ flip, const float* __restrict__ w,
                                              const float* __restrict__ bias, const float* __restrict__ slope,
                                              float* __restrict__ out, int N, int H, int W,
-                                             const float* __restrict__ x2, int n_split) {
+                                             const float* __restrict__ x2, int n_split,
+                                             const unsigned char* __restrict__ xu8b) {
     __shared__ __attribute__((aligned(16))) float patch[STEM_PIX * 28];
     __shared__ __attribute__((aligned(16))) float otile[4 * 32 * STEM_TLD];      // per wave: its output tile [32 pixels][32 channels (+4)]
+    __shared__ float lut[U8 ? 257 : 1];               // U8: the input step of every byte value; [256] = 0, the zero padding
     const int tid = threadIdx.x;
+    if constexpr (U8) {
+        lut[tid] = __fdiv_rn(__fsub_rn(__fdiv_rn((float)tid, 255.0f), 0.5f), 0.5f);      // blockDim 256: one entry per thread
+        if (tid == 0) lut[256] = 0.f;
+    }
     const int lane = tid & 63, wave = tid >> 6;
     const int mt = wave >> 1, nt = wave & 1;          // this wave's 32-pixel x 32-channel output tile
     const int half = lane >> 5, ch = nt * 32 + (lane & 31);
@@ -65,21 +75,40 @@ __global__ __launch_bounds__(256) void k_stem(const float* __restrict__ x, const
         f_ds[i] = k % 3 - 1;
     }
     float nv[7];
+    // U8: the fill keeps the raw bytes (nu, 256 = zero padding) and converts them through lut[] when it writes the patch, so
+    // the loads of step s + 1 stay in flight while step s multiplies; the flip flag a fetch needs for its addresses was
+    // loaded by the fetch before it (fnext)
+    unsigned nu[7];
+    unsigned fnext = 0;
+    auto flip_of = [&](int step) -> unsigned {
+        const long long p = ((long long)blockIdx.x * STEM_STEPS + step) * STEM_PIX + lane;
+        if (!flip || p >= total) return 0u;
+        const int n = (int)((unsigned)p / (unsigned)HW);
+        return flip[n >= n_split ? n - n_split : n];
+    };
+    if constexpr (U8) fnext = flip_of(0);
     auto fetch = [&](int step) {
         const long long p = ((long long)blockIdx.x * STEM_STEPS + step) * STEM_PIX + lane;
         const bool pv = p < total;
         const int n = pv ? (int)((unsigned)p / (unsigned)HW) : 0;      // p < N * H * W < 2^31 (launch_stem): 32-bit divisions
         const int rem = pv ? (int)((unsigned)p - (unsigned)n * (unsigned)HW) : 0;
         const int h = (int)((unsigned)rem / (unsigned)W), wq = rem - h * W;
+        const unsigned char* us = nullptr;   // U8: this pixel's image in its source buffer, and its flip
+        bool fl = false;
+        if constexpr (U8) {
+            const int nn = n >= n_split ? n - n_split : n;
+            us = (n >= n_split ? xu8b : xu8) + (long long)nn * HW * 3;
+            fl = fnext != 0;
+        }
 #pragma unroll
         for (int i = 0; i < 7; ++i) {
             float v = 0.f;
+            unsigned u = 256u;
             const int hi = h + f_dr[i], wi = wq + f_ds[i];
             if (pv && f_ci[i] < 3 && (unsigned)hi < (unsigned)H && (unsigned)wi < (unsigned)W) {
-                if (U8) {
-                    const int ws = (flip && flip[n]) ? W - 1 - wi : wi;
-                    const float u = (float)xu8[(((long long)n * H + hi) * W + ws) * 3 + (2 - f_ci[i])];
-                    v = __fdiv_rn(__fsub_rn(__fdiv_rn(u, 255.0f), 0.5f), 0.5f);
+                if constexpr (U8) {
+                    const int ws = fl ? W - 1 - wi : wi;
+                    u = us[(unsigned)(hi * W + ws) * 3u + (unsigned)(2 - f_ci[i])];
                 } else {
                     // images [n_split, N) come from a second buffer (clean | occluded halves of a training batch)
                     const float* xs = n >= n_split ? x2 : x;
@@ -87,8 +116,11 @@ __global__ __launch_bounds__(256) void k_stem(const float* __restrict__ x, const
                     v = xs[((long long)(nn * 3 + f_ci[i]) * H + hi) * W + wi];
                 }
             }
-            nv[i] = v;
+            if constexpr (U8) nu[i] = u;
+            else nv[i] = v;
         }
+        if constexpr (U8)
+            if (step + 1 < STEM_STEPS) fnext = flip_of(step + 1);
     };
     fetch(0);
     for (int step = 0; step < STEM_STEPS; ++step) {
@@ -96,7 +128,10 @@ __global__ __launch_bounds__(256) void k_stem(const float* __restrict__ x, const
         if (p0 >= total) break;
         __syncthreads();
 #pragma unroll
-        for (int i = 0; i < 7; ++i) patch[(wave * 7 + i) * STEM_PIX + lane] = nv[i];
+        for (int i = 0; i < 7; ++i) {
+            if constexpr (U8) patch[(wave * 7 + i) * STEM_PIX + lane] = lut[nu[i]];
+            else patch[(wave * 7 + i) * STEM_PIX + lane] = nv[i];
+        }
         __syncthreads();
         if (step + 1 < STEM_STEPS) fetch(step + 1);
         f32x16 acc;
@@ -133,14 +168,16 @@ __global__ __launch_bounds__(256) void k_stem(const float* __restrict__ x, const
 }
 
 hipError_t launch_stem(const float* x, const unsigned char* xu8, const unsigned char* flip, const float* w,
-                       const float* bias, const float* slope, float* out, int N, int H, int W, hipStream_t stream, const float* x2, int n_split) {
+                       const float* bias, const float* slope, float* out, int N, int H, int W, hipStream_t stream, const float* x2, int n_split,
+                       const unsigned char* xu8b) {
     const long long total = (long long)N * H * W;
     const long long per_block = (long long)STEM_PIX * STEM_STEPS;
     if (total >= 0x7fffffffLL) return hipErrorInvalidValue;      // the kernel decomposes pixel indices with 32-bit divisions
     const unsigned blocks = (unsigned)((total + per_block - 1) / per_block);
-    if (!x2) n_split = N;
-    if (xu8) hipLaunchKernelGGL(k_stem<true>, dim3(blocks), dim3(256), 0, stream, x, xu8, flip, w, bias, slope, out, N, H, W, x2, n_split);
-    else hipLaunchKernelGGL(k_stem<false>, dim3(blocks), dim3(256), 0, stream, x, xu8, flip, w, bias, slope, out, N, H, W, x2, n_split);
+    if (xu8 ? !xu8b : !x2) n_split = N;
+    else if (n_split <= 0 || n_split >= N) return hipErrorInvalidValue;
+    if (xu8) hipLaunchKernelGGL(k_stem<true>, dim3(blocks), dim3(256), 0, stream, x, xu8, flip, w, bias, slope, out, N, H, W, x2, n_split, xu8b);
+    else hipLaunchKernelGGL(k_stem<false>, dim3(blocks), dim3(256), 0, stream, x, xu8, flip, w, bias, slope, out, N, H, W, x2, n_split, xu8b);
     return hipGetLastError();
 }
 

@@ -826,7 +826,7 @@ int run_trunk(ffr_handle* h, const Work& w, const float* x_nchw, int N, int H, i
     {
         Scope s(h, st, FFR_KC_STEM, 2.0 * N * H * W * 64 * 27, 4.0 * N * H * W * (3 + 64));
         HIPCK(h, launch_stem(x_nchw, u8 ? u8->img : nullptr, u8 ? u8->flip : nullptr, h->stem_w, h->stem_b, h->stem_s,
-                             w.bufA, N, H, W, st, x2, n_split));
+                             w.bufA, N, H, W, st, x2, n_split, u8 ? u8->img2 : nullptr));
     }
     float* cur = w.bufA;
     float* nxt = w.bufB;
@@ -1361,20 +1361,32 @@ int ffr_reserve(ffr_handle* h, int N, int H, int W) {
     return ensure_arena_encoder(h, N, H, W, &w);
 }
 
-int ffr_encoder_forward(ffr_handle* h, const float* x, int N, int H, int W, float* featmap_nchw, float* f, void* stream) {
+// ffr_encoder_forward and its uint8 twin: the input is x (fp32 NCHW) or u8 (uint8 HWC RGB)
+static int encoder_forward(ffr_handle* h, const float* x, const U8In* u8, int N, int H, int W, float* featmap_nchw, float* f,
+                           void* stream) {
     FFR_DEVICE_SCOPE(h); RC(check_fwd(h, true, false, N));
-    if (!x) return fail(h, FFR_ERR_ARG, "x is null");
+    if (u8 ? !u8->img : !x) return fail(h, FFR_ERR_ARG, u8 ? "img is null" : "x is null");
     if (H < 32 || W < 32 || (H & 15) || (W & 15)) return fail(h, FFR_ERR_ARG, "H and W must be multiples of 16, >= 32");
     if (f && (H != 112 || W != 112)) return fail(h, FFR_ERR_UNSUPPORTED, "f needs a 112x112 input (Linear(512*7*7,512))");
     hipStream_t st = (hipStream_t)stream;
     Work w;
     RC(ensure_arena_encoder(h, N, H, W, &w));
-    RC(run_encoder(h, w, x, N, H, W, featmap_nchw ? w.trunk_bn : nullptr, f, st));
+    RC(run_encoder(h, w, x, N, H, W, featmap_nchw ? w.trunk_bn : nullptr, f, st, u8));
     if (featmap_nchw) {
         Scope s(h, st, FFR_KC_LAYOUT, 0, 8.0 * N * (H / 16) * (W / 16) * 512);
         HIPCK(h, launch_nhwc_to_nchw(w.trunk_bn, 512, featmap_nchw, N, (H / 16) * (W / 16), 512, st));
     }
     return FFR_OK;
+}
+
+int ffr_encoder_forward(ffr_handle* h, const float* x, int N, int H, int W, float* featmap_nchw, float* f, void* stream) {
+    return encoder_forward(h, x, nullptr, N, H, W, featmap_nchw, f, stream);
+}
+
+int ffr_encoder_forward_u8(ffr_handle* h, const uint8_t* img_hwc_rgb, const uint8_t* flip, int N, int H, int W,
+                           float* featmap_nchw, float* f, void* stream) {
+    const U8In u8{img_hwc_rgb, flip};
+    return encoder_forward(h, nullptr, &u8, N, H, W, featmap_nchw, f, stream);
 }
 
 int ffr_recnet_forward(ffr_handle* h, const float* featmap_nchw, int N, float* f_new, float* feat_new_nchw, void* stream) {

@@ -274,7 +274,8 @@ inline ConvCall conv_call(const Work& w, ConvForce force = ConvForce::Auto) {   
 }
 int ensure_arena(ffr_handle* h, int N, int H, int W, Work* w);
 int ensure_arena_encoder(ffr_handle* h, int N, int H, int W, Work* w);     // + the exact-tiling weight sets an encoder forward of this size uses
-struct U8In { const unsigned char* img; const unsigned char* flip; };
+// uint8 HWC RGB input of the stem; with img2, images [n_split, N) come from img2 and flip[] has one flag per pair
+struct U8In { const unsigned char* img; const unsigned char* flip; const unsigned char* img2 = nullptr; };
 int run_encoder(ffr_handle* h, const Work& w, const float* x, int N, int H, int W, float* featmap_nhwc, float* f,
                 hipStream_t st, const U8In* u8 = nullptr, const float* x2 = nullptr, int n_split = 0);
 struct RecDebug { float *ss_space, *M_space, *feat_space, *feat_channel_raw, *feat_channel, *ss_channel0, *M_channel0; };

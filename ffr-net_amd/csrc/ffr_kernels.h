@@ -146,10 +146,11 @@ hipError_t launch_mfma_probe(int iters, int blocks, unsigned long long* stamps, 
 // ---- trunk elementwise (elementwise.hip) -------------------------------------------
 // stem: x_nchw[N,3,H,W] -> out[N,H,W,64] = PReLU(conv3x3(x)*bnscale + bias); w [27][64] folded
 // input: x_nchw fp32, OR (xu8 != null) uint8 [N,H,W,3] RGB images preprocessed on the fly
-// (BGR swap, per-image h-flip flags, /255, (x-0.5)/0.5)
+// (BGR swap, h-flip where flip[n mod n_split] != 0, /255, (x-0.5)/0.5)
+// With a second buffer (x2, or xu8b on the uint8 path) images [n_split, N) are read from it, 0 < n_split < N.
 hipError_t launch_stem(const float* x_nchw, const unsigned char* xu8, const unsigned char* flip, const float* w27x64,
                        const float* bias, const float* slope, float* out, int N, int H, int W, hipStream_t stream,
-                       const float* x2 = nullptr, int n_split = 0);   // images [n_split, N) read from x2 (fp32 path)
+                       const float* x2 = nullptr, int n_split = 0, const unsigned char* xu8b = nullptr);
 // SE: scale[n][c] = sigmoid(fc2(relu(fc1(mean_hw res[n]))))   fc1 [C/16][C], fc2 [C][C/16]
 // part: scratch [N][se_slices(N,HW)][C] floats (<= N*32*512)
 int se_slices(int N, int HW);

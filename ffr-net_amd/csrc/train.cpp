@@ -1135,12 +1135,14 @@ int ffr_train_backward_losses(ffr_handle* h, int slot, void* stream) {
 // One iteration up to the gradients (train.py:46-54 without the optimiser step): encoder on both halves (frozen, eval),
 // RecNet train-mode forward, the four loss items, zero_grad, backward.  The caller averages the flat gradient buffer
 // over the ranks (if any) and calls ffr_train_adam_step.
-int ffr_train_iteration(ffr_handle* h, const float* img_non, const float* img_ocl, const int32_t* label, int N,
-                        const double* loss_weight, float* out5, void* stream) {
+// The images are fp32 NCHW (img_non / img_ocl) or, with u8 (img = clean, img2 = occluded), uint8 HWC RGB.
+static int train_iteration(ffr_handle* h, const float* img_non, const float* img_ocl, const U8In* u8, const int32_t* label,
+                           int N, const double* loss_weight, float* out5, void* stream, const char* who) {
     TrainState* t;
     FFR_DEVICE_SCOPE(h); RC(get_train(h, &t));
     RC(check_fwd(h, true, false, N));
-    if (!img_non || !img_ocl || !label || !loss_weight) return fail(h, FFR_ERR_ARG, "ffr_train_iteration: null argument");
+    if ((u8 ? !u8->img || !u8->img2 : !img_non || !img_ocl) || !label || !loss_weight)
+        return fail(h, FFR_ERR_ARG, "%s: null argument", who);
     hipStream_t st = (hipStream_t)stream;
     const int imgs = 2 * N;
     Work w;
@@ -1150,8 +1152,8 @@ int ffr_train_iteration(ffr_handle* h, const float* img_non, const float* img_oc
     RC(ensure_ctx(h, t, c, 2, N));
     // the encoder writes the NHWC feature maps straight into the context (no NCHW round trip); f -> dfn/df scratch rows
     float* f_enc = t->d512a;    // [2N][512]; this scratch is free until the backward starts
-    // both halves in one pass of 2N images: the stem reads the second half from img_ocl
-    RC(run_encoder(h, w, img_non, imgs, 112, 112, c.X, f_enc, st, nullptr, img_ocl, N));
+    // both halves in one pass of 2N images: the stem reads the second half from img_ocl (u8->img2)
+    RC(run_encoder(h, w, img_non, imgs, 112, 112, c.X, f_enc, st, u8, img_ocl, N));
     HIPCK(h, hipMemcpyAsync(c.label, label, (size_t)N * 4, hipMemcpyDeviceToDevice, st));
     HIPCK(h, hipMemcpyAsync(c.label + N, label, (size_t)N * 4, hipMemcpyDeviceToDevice, st));
     RC(train_forward(h, t, c, w, st));
@@ -1163,6 +1165,17 @@ int ffr_train_iteration(ffr_handle* h, const float* img_non, const float* img_oc
     c.valid = false;
     t->loss_grads_ready = false;
     return FFR_OK;
+}
+
+int ffr_train_iteration(ffr_handle* h, const float* img_non, const float* img_ocl, const int32_t* label, int N,
+                        const double* loss_weight, float* out5, void* stream) {
+    return train_iteration(h, img_non, img_ocl, nullptr, label, N, loss_weight, out5, stream, "ffr_train_iteration");
+}
+
+int ffr_train_iteration_u8(ffr_handle* h, const uint8_t* img_non, const uint8_t* img_ocl, const uint8_t* pair_flip,
+                           const int32_t* label, int N, const double* loss_weight, float* out5, void* stream) {
+    const U8In u8{img_non, pair_flip, img_ocl};
+    return train_iteration(h, nullptr, nullptr, &u8, label, N, loss_weight, out5, stream, "ffr_train_iteration_u8");
 }
 
 }  // extern "C"

@@ -147,7 +147,15 @@ class pair_embed(object):
             self._bind(device)
         return self
 
-    def __call__(self, img):
+    def __call__(self, img, flip=None):
+        if img.dtype == torch.uint8:
+            if not self.native:
+                raise RuntimeError(_U8_FOREIGN % 'this (encoder, recnet) pair')
+            if self.encoder.training or self.recnet.training:
+                raise NotImplementedError('ffrnet_amd.lfw: verification runs the eval() forward (train.py:103-104); '
+                                          'call encoder.eval() / recnet.eval() first')
+            self.encoder._require_native(img, 'lfw.calculate_distance', allow_u8=True)
+            return self._bind(img.device).embed_u8(img, flip)
         if not self.native:
             featmap, f = self.encoder(img)
             f_new, _ = self.recnet(featmap)
@@ -157,6 +165,37 @@ class pair_embed(object):
                                       'call encoder.eval() / recnet.eval() first')
         self.encoder._require_native(img, 'lfw.calculate_distance')
         return self._bind(img.device).embed(img)
+
+
+_U8_FOREIGN = ('ffrnet_amd.lfw: the loader yields uint8 images but %s does not declare accepts_uint8 = True.  Either '
+               'keep ToTensor/Normalize in the loader, pass a native embed function (Engine.embed, the Backbone + RecNet '
+               'shells), or set accepts_uint8 = True on the function: it is then called as fn(img_u8[N,H,W,3], flip[N] '
+               'or None)')
+
+
+def embed_uint8(embed_fn, img, flip=None):
+    """embed_fn on uint8 images [N,H,W,3] (HWC RGB) with per-image flip flags (or None): the native input step of
+    Engine.embed_u8 whenever a native Engine is behind embed_fn; a foreign function must declare accepts_uint8."""
+    route = _uint8_route(embed_fn)
+    if route == 'engine':
+        return engine_of(embed_fn).embed_u8(img, flip)
+    return embed_fn(img, flip)
+
+
+def _uint8_route(embed_fn):
+    """How embed_fn takes uint8 images: 'engine' (Engine.embed_u8), 'call' (the shell pair, or a foreign function that
+    declares accepts_uint8); raises for anything else."""
+    from .native import GraphedEmbed
+    if isinstance(embed_fn, GraphedEmbed) or isinstance(getattr(embed_fn, '__self__', None), GraphedEmbed):
+        raise RuntimeError('ffrnet_amd.lfw: GraphedEmbed replays the fp32 forward only; with a uint8 loader pass '
+                           'engine.embed (Engine.embed_u8 runs the input step in the stem)')
+    if isinstance(embed_fn, pair_embed) and embed_fn.native:
+        return 'call'
+    if engine_of(embed_fn) is not None:
+        return 'engine'
+    if getattr(embed_fn, 'accepts_uint8', False):
+        return 'call'
+    raise RuntimeError(_U8_FOREIGN % ('the embed function %r' % (embed_fn,)))
 
 
 def _embed_of(encoder, recnet=None):
@@ -192,61 +231,86 @@ class ShardFeeder(object):
     Tensors that already live on the device are sliced there (and must be on `device`).  `device=None`: no copies at
     all (foreign embed functions, CPU tests).  Yields (data, both[2m,3,H,W], m, n).
 
+    Decoded images: img1 / img2 may be uint8 [B,H,W,3] (HWC RGB, `np.asarray(pil_img)` without ToTensor / Normalize);
+    they are staged and copied as uint8 (a quarter of the fp32 bytes) and `both` is [2m,H,W,3] uint8.  An optional
+    data['flip'] [B] (bool / uint8, one horizontal-flip decision per pair, data/dataset.py:76-79) is sharded with them
+    and rides in the same copy; while a batch is yielded, `pair_flip` holds its [m] flags and `flip` the [2m] flags of
+    the rows of `both` (None without data['flip']).  Float images arrive preprocessed: their data['flip'] is ignored.
+    The same feeder is the host input side of training: ShardFeeder(loader, 0, 1, device) over CASIA-shaped
+    {img1, img2, label} batches yields `both` = [clean; occluded] for NativeTrainer.step(both[:m], both[m:],
+    data['label'], feeder.pair_flip).
+
     `stats`: batches, shard_bytes (bytes of image data handed to the embed function), h2d_bytes (bytes this rank
-    copied host -> device), full_batch_bytes (what copying whole pair batches would have moved)."""
+    copied host -> device, flip flags included), full_batch_bytes (what copying whole pair batches would have moved)."""
 
     def __init__(self, data_loader, rank=0, world=1, device=None, prefetch=True):
         self.loader, self.rank, self.world, self.device = data_loader, rank, world, device
         self.prefetch = prefetch and device is not None
         self.stats = dict(batches=0, shard_bytes=0, h2d_bytes=0, full_batch_bytes=0)
+        self.flip = self.pair_flip = None
         self._stage = [None, None]       # pinned host buffers
         self._free = [None, None]        # event after which a staging buffer may be overwritten
         self._side = None
 
     def _produce(self, k, data):
-        """Slice, stage and start the copy of one batch; -> (data, both, m, n, ready_event | None)."""
+        """Slice, stage and start the copy of one batch; -> (data, both, m, n, ready_event | None, pair_flip | None)."""
         img1, img2 = data['img1'], data['img2']
+        if img1.dtype != img2.dtype:
+            raise RuntimeError('ffrnet_amd.lfw: img1 is %s but img2 is %s; a pair batch holds one image type'
+                               % (img1.dtype, img2.dtype))
         n = img1.size(0)
         lo, hi = shard_bounds(n, self.rank, self.world)
         m = hi - lo
+        fs = None
+        if img1.dtype == torch.uint8 and data.get('flip') is not None:
+            flip = torch.as_tensor(data['flip'])
+            if flip.numel() != n or flip.dtype not in (torch.bool, torch.uint8):
+                raise RuntimeError('ffrnet_amd.lfw: flip must hold one bool / uint8 flag per pair (%d), got %s %s'
+                                   % (n, flip.dtype, list(flip.shape)))
+            fs = flip.reshape(-1)[lo:hi].to(torch.uint8)
         st = self.stats
         st['batches'] += 1
         st['full_batch_bytes'] += (img1.numel() + img2.numel()) * img1.element_size()
         a, b = img1[lo:hi], img2[lo:hi]                   # the shard is cut BEFORE anything is copied anywhere
         st['shard_bytes'] += (a.numel() + b.numel()) * a.element_size()
         if m == 0:
-            return data, None, 0, n, None
+            return data, None, 0, n, None, None
         dev = self.device
         if dev is None:
-            return data, torch.cat((a, b), 0), m, n, None
+            return data, torch.cat((a, b), 0), m, n, None, fs
         if a.is_cuda or b.is_cuda:
             for t, nm in ((a, 'img1'), (b, 'img2')):
                 if not t.is_cuda or t.device.index != dev.index:
                     raise RuntimeError('ffrnet_amd.lfw: %s is on %s but the embed function computes on %s'
                                        % (nm, t.device, dev))
-            return data, torch.cat((a, b), 0), m, n, None
-        # host tensors: one pinned block [2m,...], one asynchronous copy on the side stream
+            if fs is not None and not fs.is_cuda:
+                st['h2d_bytes'] += fs.numel()
+            return data, torch.cat((a, b), 0), m, n, None, fs.to(dev) if fs is not None else None
+        # host tensors: one pinned block [2m,...] (+ the m flip flags), one asynchronous copy on the side stream
         slot = k & 1
         shape = (2 * m,) + tuple(a.shape[1:])
-        need = 2 * m * a[0].numel()
+        nimg = 2 * m * a[0].numel()
+        need = nimg + (m if fs is not None else 0)
         buf = self._stage[slot]
         if buf is None or buf.numel() < need or buf.dtype != a.dtype:
             buf = torch.empty(need, dtype=a.dtype, pin_memory=True)
             self._stage[slot] = buf
         elif self._free[slot] is not None:
             self._free[slot].synchronize()                # the copy that last read this buffer (two batches ago) is done
-        host = buf[:need].view(shape)
+        host = buf[:nimg].view(shape)
         host[:m].copy_(a)
         host[m:].copy_(b)
+        if fs is not None:
+            buf[nimg:need].copy_(fs)
         if self._side is None:
             self._side = torch.cuda.Stream(device=dev)
         with torch.cuda.stream(self._side):
-            both = host.to(dev, non_blocking=True)
+            block = buf[:need].to(dev, non_blocking=True)
             ev = torch.cuda.Event()
             ev.record(self._side)
         self._free[slot] = ev
         st['h2d_bytes'] += need * a.element_size()
-        return data, both, m, n, ev
+        return data, block[:nimg].view(shape), m, n, ev, block[nimg:] if fs is not None else None
 
     def __iter__(self):
         it = iter(self.loader)
@@ -262,11 +326,13 @@ class ShardFeeder(object):
                     nxt = self._produce(k + 1, next(it))
                 except StopIteration:
                     nxt = False
-            data, both, m, n, ev = cur
+            data, both, m, n, ev, fl = cur
             if ev is not None:
                 main = torch.cuda.current_stream(self.device)
                 main.wait_event(ev)
                 both.record_stream(main)                  # allocated on the side stream, consumed on this one
+            self.pair_flip = fl
+            self.flip = torch.cat((fl, fl)) if fl is not None else None
             yield data, both, m, n
             if nxt is None:
                 try:
@@ -309,8 +375,11 @@ def calculate_distance(data_loader, encoder, recnet=None, flag=0, use_flip=False
     feeder = ShardFeeder(data_loader, rank, world, dev)
     last_feed_stats = feeder.stats
     for data, both, m, n in feeder:
+        u8 = data['img1'].dtype == torch.uint8
+        if u8:
+            _uint8_route(embed_fn)                       # every rank refuses alike, one with an empty shard included
         if m:
-            f_new, f = embed_fn(both)
+            f_new, f = embed_uint8(embed_fn, both, feeder.flip) if u8 else embed_fn(both)
             e = torch.cat((f_new[:m], f_new[m:], f[:m], f[m:]), 1)        # [m, 4*512]
         else:
             e = torch.zeros((0, 2048), dtype=torch.float32, device=dev if dev is not None else data['img1'].device)

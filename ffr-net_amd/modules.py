@@ -203,7 +203,7 @@ class _NativeModule(nn.Module):
                 'directly on its own device and pass gpu_ids of length 1 to the reference Trainer (INTEGRATION.md 1)'
                 % what)
 
-    def _require_native(self, x, what):
+    def _require_native(self, x, what, allow_u8=False):
         self._reject_replica(what)
         if self.training:
             raise NotImplementedError(
@@ -213,8 +213,8 @@ class _NativeModule(nn.Module):
         if not (torch.is_tensor(x) and x.is_cuda):
             raise RuntimeError('ffrnet_amd.%s: input must be a ROCm device tensor; this package has '
                                'no CPU path' % what)
-        if x.dtype != torch.float32:
-            raise RuntimeError('ffrnet_amd.%s: input must be float32' % what)
+        if x.dtype != torch.float32 and not (allow_u8 and x.dtype == torch.uint8):
+            raise RuntimeError('ffrnet_amd.%s: input must be float32%s' % (what, ' (or uint8 images [N,H,W,3])' if allow_u8 else ''))
 
     def __deepcopy__(self, memo):
         import copy
@@ -245,9 +245,16 @@ class Backbone(_NativeModule):
         self.bn = nn.BatchNorm2d(512)
         self.body = nn.Sequential(*[unit(c, d, s) for c, d, s in ir_blocks(num_layers)])
 
-    def forward(self, x):
-        """-> (featmap[N,512,7,7], l2_norm(feat)[N,512]); model_ir_se50.py:136-141."""
-        self._require_native(x, 'Backbone')
+    def forward(self, x, flip=None):
+        """-> (featmap[N,512,7,7], l2_norm(feat)[N,512]); model_ir_se50.py:136-141.
+        x: fp32 [N,3,H,W] as the reference's loader makes it, or the decoded images themselves, uint8 [N,H,W,3] HWC RGB
+        with optional per-image flip flags: the loader's BGR swap, flip, ToTensor and Normalize then run in the stem
+        (Engine.encoder_forward_u8, the same bits)."""
+        self._require_native(x, 'Backbone', allow_u8=True)
+        if x.dtype == torch.uint8:
+            return self._engine(x.device).encoder_forward_u8(x, flip)
+        if flip is not None:
+            raise RuntimeError('ffrnet_amd.Backbone: flip applies to uint8 images only (float input arrives flipped)')
         return self._engine(x.device).encoder_forward(x)
 
 

@@ -92,6 +92,7 @@ SYMBOLS = [
     ('ffr_recnet_forward', C.c_int, [_P, _P, C.c_int, _P, _P, _P]),
     ('ffr_embed', C.c_int, [_P, _P, C.c_int, _P, _P, _P]),
     ('ffr_embed_u8', C.c_int, [_P, _P, _P, C.c_int, _P, _P, _P]),
+    ('ffr_encoder_forward_u8', C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     ('ffr_cosine_scores', C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P]),
     ('ffr_lfw_fold_accuracy', C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, _P]),
     ('ffr_workspace_bytes', C.c_size_t, [_P, C.c_int, C.c_int, C.c_int]),
@@ -132,6 +133,7 @@ SYMBOLS = [
     ('ffr_train_losses', C.c_int, [_P, C.c_int, _P, C.POINTER(C.c_double), _P, _P]),
     ('ffr_train_backward_losses', C.c_int, [_P, C.c_int, _P]),
     ('ffr_train_iteration', C.c_int, [_P, _P, _P, _P, C.c_int, C.POINTER(C.c_double), _P, _P]),
+    ('ffr_train_iteration_u8', C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.POINTER(C.c_double), _P, _P]),
 ]
 
 
@@ -177,6 +179,36 @@ def _check_dev(t, name, shape_tail=None, device=None):
     if shape_tail is not None and tuple(t.shape[1:]) != tuple(shape_tail):
         raise RuntimeError('ffrnet_amd: %s expected shape [N,%s], got %s'
                            % (name, ','.join(map(str, shape_tail)), list(t.shape)))
+
+
+def _check_u8(t, name, device, hw=None):
+    """Boundary check of a decoded-image tensor: uint8 [N,H,W,3] (HWC, RGB) on the handle's device."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError('%s must be a torch.Tensor' % name)
+    if not t.is_cuda:
+        raise RuntimeError('ffrnet_amd: %s is on %s; the native HIP path needs a ROCm device tensor (there is no CPU '
+                           'fallback)' % (name, t.device))
+    if t.device.index != device.index:
+        raise RuntimeError('ffrnet_amd: %s is on %s but this Engine lives on %s' % (name, t.device, device))
+    if t.dtype != torch.uint8:
+        raise RuntimeError('ffrnet_amd: %s must be uint8 images [N,H,W,3], got %s' % (name, t.dtype))
+    if t.dim() != 4 or t.size(3) != 3 or (hw is not None and tuple(t.shape[1:3]) != tuple(hw)):
+        raise RuntimeError('ffrnet_amd: %s expected shape [N,%s,3] (HWC, RGB), got %s'
+                           % (name, '%d,%d' % tuple(hw) if hw is not None else 'H,W', list(t.shape)))
+
+
+def _flip_flags(flip, n, device, name='flip'):
+    """uint8 [n] device copy of per-image / per-pair flip flags (bool or uint8; nonzero = mirror), or None."""
+    if flip is None:
+        return None
+    if not isinstance(flip, torch.Tensor) or flip.dtype not in (torch.bool, torch.uint8):
+        raise RuntimeError('ffrnet_amd: %s must be a bool or uint8 tensor, got %s'
+                           % (name, flip.dtype if isinstance(flip, torch.Tensor) else type(flip)))
+    if flip.numel() != n:
+        raise RuntimeError('ffrnet_amd: %s must hold %d flags, got %d' % (name, n, flip.numel()))
+    if flip.is_cuda and flip.device.index != device.index:
+        raise RuntimeError('ffrnet_amd: %s is on %s but this Engine lives on %s' % (name, flip.device, device))
+    return flip.reshape(-1).to(device, torch.uint8).contiguous()
 
 
 class Engine(object):
@@ -267,6 +299,27 @@ class Engine(object):
         with torch.cuda.device(self.device):
             self._ck(self.lib.ffr_encoder_forward(self._h, _ptr(x), n, h, w, _ptr(fm), _ptr(f),
                                                   self._stream()))
+        return fm, f
+
+    def encoder_forward_u8(self, img, flip=None, want_f=True, want_featmap=True):
+        """encoder_forward from decoded images: img[N,H,W,3] uint8 HWC RGB (device), flip: optional bool / uint8 [N]
+        per-image h-flip flags.  The input step (BGR swap, flip, ToTensor, Normalize(0.5, 0.5)) runs in the stem
+        -> (featmap[N,512,H/16,W/16], f[N,512]), bit-identical to encoder_forward(O.preprocess_u8(img, flip))."""
+        _check_u8(img, 'img', self.device)
+        img = img.contiguous()
+        n, h, w, _ = img.shape
+        if h % 16 or w % 16:
+            raise RuntimeError('ffrnet_amd: H and W must be multiples of 16, got %dx%d' % (h, w))
+        if want_f and (h, w) != (112, 112):
+            raise RuntimeError('mat1 and mat2 shapes cannot be multiplied (%dx%d and 25088x512)'
+                               % (n, 512 * (h // 16) * (w // 16)))
+        fl = _flip_flags(flip, n, self.device)
+        fm = torch.empty((n, 512, h // 16, w // 16), device=img.device, dtype=torch.float32) \
+            if want_featmap else None
+        f = torch.empty((n, 512), device=img.device, dtype=torch.float32) if want_f else None
+        with torch.cuda.device(self.device):
+            self._ck(self.lib.ffr_encoder_forward_u8(self._h, _ptr(img), _ptr(fl), n, h, w, _ptr(fm), _ptr(f),
+                                                     self._stream()))
         return fm, f
 
     def recnet_forward(self, featmap, want_feat_new=True):
@@ -674,6 +727,24 @@ class Engine(object):
                                                   lw, _ptr(out), self._stream()))
         return out
 
+    def train_iteration_u8(self, img_non, img_ocl, label, flip=None, loss_weight=(1, 1, 1, 1)):
+        """train_iteration from decoded images: img_non / img_ocl [N,112,112,3] uint8 HWC RGB (device); flip: optional
+        bool / uint8 [N], one h-flip flag per PAIR (the clean and the occluded image are mirrored together)."""
+        _check_u8(img_non, 'img_non', self.device, (112, 112))
+        _check_u8(img_ocl, 'img_ocl', self.device, (112, 112))
+        n = img_non.size(0)
+        if img_ocl.shape != img_non.shape:
+            raise RuntimeError('ffrnet_amd: training images must be [N,112,112,3] pairs, got %s and %s'
+                               % (list(img_non.shape), list(img_ocl.shape)))
+        fl = _flip_flags(flip, n, self.device)
+        lab = self._labels(label, n, img_non.device)
+        out = torch.empty(5, device=img_non.device, dtype=torch.float32)
+        lw = (C.c_double * 4)(*[float(x) for x in loss_weight])
+        with torch.cuda.device(self.device):
+            self._ck(self.lib.ffr_train_iteration_u8(self._h, _ptr(img_non.contiguous()), _ptr(img_ocl.contiguous()),
+                                                     _ptr(fl), _ptr(lab), n, lw, _ptr(out), self._stream()))
+        return out
+
     def train_buckets(self):
         """[(offset, count)] of the gradient buckets in the order the backward finishes them, with their ids."""
         n = C.c_int(0)
@@ -780,6 +851,9 @@ class GraphedEmbed(object):
         self.captures += 1
 
     def __call__(self, x):
+        if isinstance(x, torch.Tensor) and x.dtype == torch.uint8:
+            raise RuntimeError('GraphedEmbed replays the fp32 forward only: for uint8 images call Engine.embed_u8 (or '
+                               'pass engine.embed to lfw.calculate_distance)')
         _check_dev(x, 'x', (3, 112, 112), device=self.engine.device)
         if x.size(0) != self.n:
             raise RuntimeError('GraphedEmbed was captured for batch %d, got %d' % (self.n, x.size(0)))

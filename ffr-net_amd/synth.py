@@ -220,3 +220,33 @@ def synth_train_batch(n, seed=301, n_classes=10575):
     g = np.random.Generator(np.random.Philox(key=(int(seed) << 32) | 0x1ABE1))
     label = torch.from_numpy(g.integers(0, n_classes, n)).long()
     return non, ocl, label
+
+
+def _to_u8(x):
+    """[n,3,h,w] in [-1,1] -> [n,h,w,3] uint8 (a decoded image's layout; channel order irrelevant for random data)."""
+    return ((x + 1.0) * 127.5).round().clamp(0, 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous()
+
+
+def _flips(n, seed, salt):
+    g = np.random.Generator(np.random.Philox(key=(int(seed) << 32) | salt))
+    return torch.from_numpy(g.random(n) < 0.5)
+
+
+def synth_images_u8(n, h=112, w=112, seed=123):
+    """[n,h,w,3] uint8: decoded images as the reference's loaders open them (data/dataset.py:68-79), before ToTensor."""
+    g = np.random.Generator(np.random.Philox(key=(int(seed) << 32) | 0x1A6E8))
+    return torch.from_numpy(g.integers(0, 256, (n, h, w, 3), dtype=np.uint8))
+
+
+def synth_pairs_u8(n_pairs, h=112, w=112, seed=7, block=600):
+    """synth_pairs as decoded uint8 images [n,h,w,3] plus one seeded horizontal-flip decision per pair
+    (data/dataset.py:76-79) -> img1, img2, labels, flip (bool [n])."""
+    img1, img2, labels = synth_pairs(n_pairs, h, w, seed, block)
+    return _to_u8(img1), _to_u8(img2), labels, _flips(n_pairs, seed, 0xF11B5)
+
+
+def synth_train_batch_u8(n, seed=301, n_classes=10575):
+    """synth_train_batch as decoded uint8 images [n,112,112,3] plus one seeded flip per pair (CASIA flips the clean
+    and the occluded image together, data/dataset.py:139-151) -> non, ocl, label, flip (bool [n])."""
+    non, ocl, label = synth_train_batch(n, seed, n_classes)
+    return _to_u8(non), _to_u8(ocl), label, _flips(n, seed, 0xF11B7)

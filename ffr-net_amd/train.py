@@ -102,11 +102,19 @@ class NativeTrainer(object):
         if self.world_size() > 1:
             dist.broadcast(self._params, src, group=self.group)
 
-    def step(self, img_non, img_ocl, label):
+    def step(self, img_non, img_ocl, label, flip=None):
         """Trainer.set_input + forward + optimizer_parameters (models/trainer.py:131-187), everything native:
         one launch-only call up to the gradients (ffr_train_iteration), the gradient exchange, clip + Adam.
+        The images are fp32 [N,3,112,112] as the reference's loader makes them, or the decoded images, uint8
+        [N,112,112,3] HWC RGB, with optional per-pair flip flags (ffr_train_iteration_u8: the loader's BGR swap, flip,
+        ToTensor and Normalize run in the stem, the same bits).  Host batches: lfw.ShardFeeder(loader, 0, 1, device).
         Returns the four weighted loss items as a device tensor view (no host sync)."""
-        out5 = self.engine.train_iteration(img_non, img_ocl, label, self.loss_weight)
+        if img_non.dtype == torch.uint8 or img_ocl.dtype == torch.uint8:
+            out5 = self.engine.train_iteration_u8(img_non, img_ocl, label, flip, self.loss_weight)
+        elif flip is not None:
+            raise RuntimeError('ffrnet_amd: flip applies to uint8 images only (float input arrives flipped)')
+        else:
+            out5 = self.engine.train_iteration(img_non, img_ocl, label, self.loss_weight)
         if self.overlap and self.world_size() > 1:
             if self._comm is None:
                 self._comm = torch.cuda.Stream(device=self.engine.device)

@@ -79,6 +79,11 @@ int ffr_load_recnet(ffr_handle* h, const ffr_tensor_desc* t, int n);
  *   featmap or f may be NULL when not wanted.                                        */
 int ffr_encoder_forward(ffr_handle* h, const float* x_nchw, int N, int H, int W,
                         float* featmap_nchw, float* f, void* stream);
+/* The same from decoded images: img[N,H,W,3] uint8, HWC, RGB as PIL gives them (device), with the input step of
+ * ffr_embed_u8 inside the stem (flip[N] per image, may be NULL).  Bit-identical to ffr_encoder_forward fed with the
+ * float tensor torch would build.  f needs H = W = 112; any other size multiple of 16 runs the trunk only.        */
+int ffr_encoder_forward_u8(ffr_handle* h, const uint8_t* img_hwc_rgb, const uint8_t* flip, int N, int H, int W,
+                           float* featmap_nchw, float* f, void* stream);
 
 /* RecNet.forward(input, label=None), models/recnet.py:398-426:
  *   featmap[N,512,7,7] -> f_new[N,512], feat_new[N,512,7,7] (either may be NULL).    */

@@ -98,6 +98,13 @@ int ffr_train_backward_losses(ffr_handle* h, int slot, void* stream);
  * and calls ffr_train_adam_step.  label int32 [N] (device); out5 as for ffr_train_losses.                      */
 int ffr_train_iteration(ffr_handle* h, const float* img_non, const float* img_ocl, const int32_t* label, int N,
                         const double* loss_weight, float* out5, void* stream);
+/* The same from decoded images: img_non / img_ocl [N,112,112,3] uint8, HWC, RGB as PIL gives them (device).  The
+ * reference's input step (data/dataset.py:139-151, data/dataloader.py:24-28: RGB->BGR swap, horizontal flip, ToTensor,
+ * Normalize(0.5, 0.5)) runs inside the stem, in one pass over the 2N images.  pair_flip[N] (device, may be NULL = no
+ * flip): pair n is mirrored where pair_flip[n] != 0 -- the clean image n and the occluded image n together, as CASIA
+ * flips img and mask.  Bit-identical to ffr_train_iteration fed with the float tensors torch would build.        */
+int ffr_train_iteration_u8(ffr_handle* h, const uint8_t* img_non, const uint8_t* img_ocl, const uint8_t* pair_flip,
+                           const int32_t* label, int N, const double* loss_weight, float* out5, void* stream);
 
 /* clip_grad_value_(clip_value) (<= 0: no clipping) followed by one torch.optim.Adam step on every
  * parameter (models/trainer.py:182-187); one fused elementwise launch over the flat buffers.           */
