@@ -16,12 +16,17 @@ Workload = BASELINE.json configs[2] (IR-SE50 + RecBlock forward, batch 256 per G
 cannot produce an embedding in the reference -- the 112x96 TRUNK is timed as a
 secondary line.
 
-Prints ONE JSON line (rank 0).  `roofline` describes the dominant kernel (k_wino_fused: the fp32-MFMA
-GEMMs + output transform of every Winograd convolution) with EXECUTED FLOPs over hipEvent time on the
-launch stream, so `frac` <= 1; `cpu_baseline` is the oracle (stock-torch CPU restatement of the
-reference) timed on this host's cores (rank 0, N = 1).  Before anything is timed the 8 images of golden
-G1 are embedded and compared with the reference's own outputs (`parity_checked`); the run fails if the
-error exceeds the 1e-3 contract.
+Prints ONE JSON line (rank 0).  A plain run does only what the headline figure needs: set-up, the W
+warm-up and K timed steps, --dump-outputs, the line; its `parity_checked`, `roofline`, `cpu_baseline` and
+`secondary` are null.  `--full` adds everything else, each part still switched off by its --no-* option:
+    parity gate: before anything is timed the 8 images of golden G1 are embedded and compared with the
+        reference's own outputs (`parity_checked`); the run fails if the error exceeds the 1e-3 contract.
+    `roofline`: the dominant kernel (k_wino_fused: the fp32-MFMA GEMMs + output transform of every
+        Winograd convolution) with EXECUTED FLOPs over hipEvent time on the launch stream, so `frac` <= 1.
+    `cpu_baseline`: the oracle (stock-torch CPU restatement of the reference) timed on this host's cores
+        (rank 0, N = 1).
+    `secondary`: the other configurations (N = 1: backbone only, the 112x96 trunk, the LFW protocol, the
+        training iteration; N > 1: configs[3]'s strong scaling).
 """
 import argparse
 import hashlib
@@ -43,7 +48,7 @@ PEAK_HBM_TBS = 8.0                 # MI355X_MICROARCH.md: HBM3E spec (6.3 TB/s m
 PARITY_TOL = 1e-3                  # BASELINE.json north_star
 
 
-def parse_args():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=50)
@@ -58,8 +63,8 @@ def parse_args():
     ap.add_argument('--no-roofline', action='store_true')
     ap.add_argument('--no-secondary', action='store_true')
     ap.add_argument('--strong-pairs', type=int, default=512,
-                    help='N > 1 only: pairs per step of the configs[3] strong-scaling measurement appended as a `secondary` entry of the '
-                         'default weak-scaling line (split over the ranks; 0: off)')
+                    help='N > 1 with --full only: pairs per step of the configs[3] strong-scaling measurement appended as a '
+                         '`secondary` entry of the weak-scaling line (split over the ranks; 0: off)')
     ap.add_argument('--workload', choices=('embed', 'train'), default='embed',
                     help="embed (default): BASELINE.json's metric; train: the RecNet training iteration of configs[4] "
                          '(128 image pairs per GPU unless --batch is given), data parallel with one all-reduce of the '
@@ -69,9 +74,14 @@ def parse_args():
                          'most 64 MB in all, a fixed seeded sample of the rows beyond that): embed: f_new, f (every rank\'s, '
                          'after the exchange) and the pair scores; train: the four losses, the accuracy and the flat RecNet '
                          'parameters after the step')
-    args = ap.parse_args()
+    ap.add_argument('--full', action='store_true',
+                    help='also the parity gate on golden G1, roofline, cpu_baseline and the secondary lines (each still '
+                         'switched off by its --no-* option); without it a run does only what the headline figure needs')
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error('--steps must be at least 1')
+    if not args.full:
+        args.no_cpu_baseline = args.no_roofline = args.no_secondary = True
     return args
 
 
@@ -511,7 +521,7 @@ def train_roofline(eng, step_fn, B, fence, instrument=True, nprof=2, pmc=True):
 
 
 def train_step_line(eng, sd_r, dev, pairs=128, warm=2, iters=5):
-    """SURVEY 8 row N3 / BASELINE configs[4] in the DEFAULT run: whole training iterations of
+    """SURVEY 8 row N3 / BASELINE configs[4] in the --full run: whole training iterations of
     models/trainer.py:139-187 through NativeTrainer on the engine the embedding benchmark just used (its frozen encoder is
     the one already loaded) -- frozen-encoder forward of clean + occluded images, RecNet train-mode forward, four losses,
     full backward, clip + Adam -- `warm` untimed + `iters` timed iterations of `pairs` image pairs, then two instrumented
@@ -671,17 +681,19 @@ def main():
     eng.reserve(max(B, 8))           # workspace arena + (first time a batch can use them) the exact-tiling weight sets, derived on the device
     t_res = time.perf_counter() - t_res
 
-    # ---- parity gate: the reference's own outputs for the 8 images of golden G1 (tests/golden/make_golden.py) ----
-    g1 = np.load(os.path.join(ROOT, 'tests', 'golden', 'g1_config1.npz'))
-    f_new8, f8 = eng.embed(synth.synth_images(8, 112, 112, seed=123).to(dev))
-    torch.cuda.synchronize()
-    parity = 0.0
-    for got, ref in ((f_new8, g1['f_new']), (f8, g1['f'])):
-        ref = torch.from_numpy(ref).double()
-        parity = max(parity, ((got.double().cpu() - ref).abs().max() / ref.abs().max()).item())
-    if not parity < PARITY_TOL:
-        print(json.dumps({'error': 'parity check failed', 'parity_checked': parity, 'tolerance': PARITY_TOL}))
-        sys.exit(3)
+    # ---- parity gate (--full): the reference's own outputs for the 8 images of golden G1 (tests/golden/make_golden.py) ----
+    parity = None
+    if args.full:
+        g1 = np.load(os.path.join(ROOT, 'tests', 'golden', 'g1_config1.npz'))
+        f_new8, f8 = eng.embed(synth.synth_images(8, 112, 112, seed=123).to(dev))
+        torch.cuda.synchronize()
+        parity = 0.0
+        for got, ref in ((f_new8, g1['f_new']), (f8, g1['f'])):
+            ref = torch.from_numpy(ref).double()
+            parity = max(parity, ((got.double().cpu() - ref).abs().max() / ref.abs().max()).item())
+        if not parity < PARITY_TOL:
+            print(json.dumps({'error': 'parity check failed', 'parity_checked': parity, 'tolerance': PARITY_TOL}))
+            sys.exit(3)
 
     x = synth.synth_images(B, seed=124 + rank).to(dev)
     # the engine writes f_new and f into the two halves of ONE packed buffer, so the exchange is ONE collective
@@ -710,7 +722,7 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    startup_s = time.perf_counter() - t_start      # process start -> first step: imports, rendezvous, weight synthesis, packing, parity gate
+    startup_s = time.perf_counter() - t_start      # process start -> first step: imports, rendezvous, weight synthesis, packing, parity gate (--full)
     for _ in range(args.warmup):
         step()
     fence()
@@ -745,7 +757,7 @@ def main():
                     'all_gather_bytes_per_rank': 2 * B * 512 * 4,
                     'startup_s': [round(v, 2) for v in allr[:, 3].tolist()],
                     'startup_note': 'process start -> first step (imports, rendezvous, weight synthesis with host_cores // world torch '
-                                    'threads, single-threaded packing, parity gate); the rendezvous / collective timeout is '
+                                    'threads, single-threaded packing, parity gate with --full); the rendezvous / collective timeout is '
                                     'FFR_BENCH_DIST_TIMEOUT (default 600 s)',
                     'note': 'the all-gather event pair also waits for the slowest rank to arrive'}
         # the exchange put every rank's rows where the scoring reads them: this rank's slice is its own output
@@ -919,7 +931,7 @@ def main():
                           'batch_per_gpu': B, 'global_batch': world * B, 'gflop_per_image': GFLOP_PER_IMAGE,
                           'parallelism': 'image-sharded x%d, RCCL all-gather of embeddings' % world},
                'step_ms_hipevents': step_ms, 'per_rank': per_rank, 'options': args.opt or None,
-               'parity_checked': {'max_rel_err_vs_reference_golden_G1': parity, 'tolerance': PARITY_TOL},
+               'parity_checked': {'max_rel_err_vs_reference_golden_G1': parity, 'tolerance': PARITY_TOL} if args.full else None,
                'load': load, 'roofline': roof, 'cpu_baseline': cpu, 'secondary': secondary}
         print(json.dumps(out))
     if world > 1:

@@ -868,7 +868,7 @@ def test_bench_and_trainer_two_ranks_on_one_gpu():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     # from a plain shell, as the driver calls it: bench.py spawns its own ranks
     for extra, batch, scaling in ((['--batch', '16', '--strong-pairs', '40'], 16, 'weak'), (['--pairs-per-step', '24'], 24, 'strong')):
-        cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1',
+        cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--full',
                '--no-roofline', '--no-cpu-baseline'] + extra
         out = _Sub.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=300)
         assert out.returncode == 0, out.stderr[-2000:]
@@ -893,7 +893,7 @@ def test_bench_and_trainer_two_ranks_on_one_gpu():
             assert d['secondary'] is None
     # more than two handles + arenas + ranks side by side on one device: four, because this process holds the device too
     # and no more than six processes may have one device open at a time
-    cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '4', '--steps', '2', '--warmup', '1', '--batch', '8',
+    cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '4', '--steps', '2', '--warmup', '1', '--batch', '8', '--full',
            '--no-roofline', '--no-cpu-baseline']
     out = _Sub.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -902,7 +902,7 @@ def test_bench_and_trainer_two_ranks_on_one_gpu():
     # and under torch.distributed.run, as the driver launches the multi-GPU runs
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
            '--master-port', str(free_port()), os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--batch', '16',
-           '--no-roofline', '--no-cpu-baseline']
+           '--full', '--no-roofline', '--no-cpu-baseline']
     out = _Sub.run(cmd, env=dict(env, MASTER_ADDR='127.0.0.1'), cwd=root, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith('{')][-1])
@@ -910,7 +910,7 @@ def test_bench_and_trainer_two_ranks_on_one_gpu():
     # the training workload with its roofline block ON: the profiled iterations contain the gradient all-reduce, so every
     # rank must run them (rank 0 alone would wait in the collective for ever)
     cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--workload', 'train', '--steps', '1', '--warmup', '1',
-           '--batch', '8', '--no-cpu-baseline']
+           '--batch', '8', '--full', '--no-cpu-baseline']
     out = _Sub.run(cmd, env=dict(env, FFR_BENCH_LIVE_PMC='0'), cwd=root, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith('{')][-1])
@@ -948,7 +948,7 @@ def test_bench_line_carries_the_three_roofline_fractions():
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK'):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--batch', '128', '--steps', '3', '--warmup', '2',
-                          '--no-cpu-baseline', '--no-secondary'], cwd=root, env=env, capture_output=True, text=True, timeout=600)
+                          '--full', '--no-cpu-baseline', '--no-secondary'], cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     r = json.loads([l for l in out.stdout.splitlines() if l.startswith('{')][-1])['roofline']
     assert 0 < r['frac_useful'] < r['frac'] < 1.0
@@ -956,6 +956,30 @@ def test_bench_line_carries_the_three_roofline_fractions():
     assert 'traffic' in r and (r['traffic'] is None or r['traffic'] > 0)
     assert 'traffic_ratio_vs_compulsory' in r and r['gflop_useful_per_launch'] < r['gflop_executed_per_launch']
     assert 0 < r['per_bound']['whole_step']['frac_useful'] < r['per_bound']['whole_step']['frac_of_mfma_peak']
+
+
+def test_plain_bench_run_is_the_headline_line_only(state_dicts, tmp_path):
+    """bench.py without --full: set-up, warm-up, timed steps, --dump-outputs and the result line -- no parity gate, roofline,
+    CPU baseline or secondary lines.  What it dumped is held to the oracle here, since the run itself no longer checks."""
+    import json
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK'):
+        env.pop(k, None)
+    out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--batch', '16', '--steps', '2', '--warmup', '1',
+                          '--dump-outputs', str(tmp_path)], cwd=root, env=env, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = json.loads([l for l in out.stdout.splitlines() if l.startswith('{')][-1])
+    assert d['unit'] == 'embeddings/s' and d['higher_is_better'] is True and d['dtype'] == 'f32'
+    assert d['value'] > 0 and d['ms_per_step'] > 0 and d['steps'] == 2 and d['warmup'] == 1 and d['step_ms_hipevents']['n'] == 2
+    assert d['parity_checked'] is None and d['roofline'] is None and d['cpu_baseline'] is None and d['secondary'] is None
+    assert sorted(os.listdir(tmp_path)) == ['f.npy', 'f_new.npy', 'scores.npy']
+    sd_e, sd_r = state_dicts
+    rf_new, rf = O.embed(sd_e, sd_r, synth.synth_images(16, seed=124))          # bench.py's input of rank 0
+    f_new, f = torch.from_numpy(np.load(tmp_path / 'f_new.npy')), torch.from_numpy(np.load(tmp_path / 'f.npy'))
+    assert rel(f_new, rf_new) < REG_TOL and rel(f, rf) < REG_TOL
+    assert np.load(tmp_path / 'scores.npy').shape == (8,)
 
 
 def test_options_api(engine):

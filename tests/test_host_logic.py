@@ -428,3 +428,16 @@ def test_bench_dump_outputs_stays_under_64_mb_with_the_same_rows(tmp_path):
         a, full = np.load(tmp_path / 'a' / (k + '.npy')), big[k].numpy()
         assert 0 < a.shape[0] < full.shape[0] and a.shape[1:] == full.shape[1:]
         assert np.isin(a.reshape(a.shape[0], -1)[:, 0], full.reshape(full.shape[0], -1)[:, 0]).all()
+
+
+def test_bench_extras_only_with_full():
+    """bench.py: a plain run switches off everything beyond the headline figure; --full turns the extras on, each still
+    switched off by its own --no-* option."""
+    import bench
+    a = bench.parse_args(['--steps', '3', '--warmup', '1'])
+    assert not a.full and a.no_cpu_baseline and a.no_roofline and a.no_secondary
+    assert (a.steps, a.warmup, a.batch, a.gpus) == (3, 1, 256, 1)
+    a = bench.parse_args(['--full'])
+    assert a.full and not (a.no_cpu_baseline or a.no_roofline or a.no_secondary)
+    a = bench.parse_args(['--full', '--no-roofline'])
+    assert a.no_roofline and not (a.no_cpu_baseline or a.no_secondary)

@@ -14,7 +14,7 @@ if [ "$WL" = train ]; then B="${FFR_PMC_BATCH:-128}"; else B="${FFR_PMC_BATCH:-2
 PT="${FFR_PMC_PASS_TIMEOUT:-200}"
 for c in FETCH_SIZE WRITE_SIZE "SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE"; do
   d=$(echo $c | cut -d' ' -f1)
-  timeout "$PT" rocprofv3 --pmc $c --kernel-trace --output-format csv -d "$OUT/$d" -- python3 "$R/bench.py" --workload "$WL" --batch "$B" --steps 2 --warmup 1 --no-cpu-baseline --no-roofline --no-secondary > /dev/null 2>"$OUT/$d.err"
+  timeout "$PT" rocprofv3 --pmc $c --kernel-trace --output-format csv -d "$OUT/$d" -- python3 "$R/bench.py" --workload "$WL" --batch "$B" --steps 2 --warmup 1 --full --no-cpu-baseline --no-roofline --no-secondary > /dev/null 2>"$OUT/$d.err"
 done
 python3 - <<PY
 import csv, glob, collections, json, hashlib
