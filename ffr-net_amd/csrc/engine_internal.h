@@ -1,5 +1,6 @@
-// Types and helpers shared by the host translation units of libffrnet_hip.so (engine.cpp: inference
-// pipelines and the C ABI; train.cpp: the RecNet training step).  Not part of the public interface.
+// Types and helpers shared by the host translation units of libffrnet_hip.so: plan.cpp (convolution planner), conv.cpp
+// (launchers), pack.cpp (weight packer, ffr_load_*), forward.cpp (workspace and forward pipelines), engine.cpp (the rest of
+// the C ABI) and train.cpp (the RecNet training step).  Not part of the public interface.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -33,7 +34,7 @@ struct ConvW {
     float* wu = nullptr;     // Winograd F(4,3) weights [36][cout_pad][cin_pad] (G g G^T, BN folded) or null
     float* wum[4] = {nullptr, nullptr, nullptr, nullptr};   // mixed tile sizes (wino_mixed.hip): weights of the tile types (4,3), (3,4), (3,3) in fragment
                              // order at [1..3] ([0] = wuc); derived on the device from `w` the first time a launch of this layer is eligible
-                             // (engine.cpp, ensure_mixed_weights), null before
+                             // (pack.cpp, ensure_mixed_weights), null before
     bool wum_gave_up = false;   // the device could not hold this layer's extra sets: it stays on padded F(4x4) tiles (never retried)
     float* wuc = nullptr;    // the same in the K-chunk order k_wino_fused streams ([cout_pad/64][cin_pad/8][36][128][4]) or null
     // per-layer arithmetic plan (ffr_layer_set_arith / ffr_calibrate): a layer with wu pinned to direct runs exactly
@@ -196,10 +197,18 @@ struct SD {
     }
 };
 
+// pack.cpp
 struct BNFold { std::vector<double> s, t; };
 bool bn_fold(SD& sd, const std::string& p, int C, BNFold& o);
 int upload(ffr_handle* h, std::vector<void*>& owner, const std::vector<float>& v, float** out);
+int pack_conv(ffr_handle* h, std::vector<void*>& owner, const float* W, int cout, int cin, int R, int S,
+              const BNFold* in_bn, const BNFold* out_bn, const float* slope, int stride, int pad, int pad_mode, ConvW* L);
 void free_list(std::vector<void*>& v);
+int ensure_mixed_weights(ffr_handle* h, ConvW& L, std::vector<void*>& owner, bool strict);
+int prepare_mixed_weights(ffr_handle* h, int N, int H, int W, size_t wino_cap);
+struct RecLayer { const char* prefix; int cin, cout; };
+extern const RecLayer REC_LAYERS[15];       // RecNet's ConvLayers: h->sp[0..8], h->fm[0..2], h->mg[0..2]
+inline ConvW& rec_conv(ffr_handle* h, int i) { return i < 9 ? h->sp[i] : i < 12 ? h->fm[i - 9] : h->mg[i - 12]; }
 
 // What a caller asks of a convolution's arithmetic; the values are those of use_wino in ffr_op_conv3x3.  Auto: the planner
 // decides (option wino, the layer's plan, wino_fused_form, the tail split).  Fused / FusedHalf: k_wino_fused with 32 x 64 /
@@ -234,11 +243,12 @@ struct ConvPlan {
 
 // Does layer L run Winograd when the caller leaves the choice to the planner (ConvForce::Auto)?  Option wino and the layer's plan.
 inline bool layer_wino(const ffr_handle* h, const ConvW& L) { return h->opt.wino != 0 && !L.direct; }
+// plan.cpp
 ConvForce wino_fused_form(const ffr_handle* h, int cin_pad, int cout_pad, long long T, double x_bytes, ConvForce ask);
 bool wino_mixed_eligible(const ffr_handle* h, const ConvW& L, int N, int H, int W, int in_pitch, size_t wino_cap, ConvForce force);
 ConvPlan plan_conv(const ffr_handle* h, const ConvW& L, const ConvCall& c);
-int ensure_mixed_weights(ffr_handle* h, ConvW& L, std::vector<void*>& owner, bool strict);
-int prepare_mixed_weights(ffr_handle* h, int N, int H, int W, size_t wino_cap);
+void plan_igemm(long long M, int cout_pad, int nkt, int nbatch, int force_tile, int min_units, int* tile, int* nblocks, int* granule);
+// conv.cpp
 int run_gemm(ffr_handle* h, IgemmArgs& a, const ConvCall& c, double flops, double bytes, hipStream_t st, double fuse = -1.0);
 int run_conv(ffr_handle* h, const ConvW& L, const ConvCall& c, hipStream_t st);
 
@@ -265,6 +275,7 @@ struct Work {
     size_t total;
 };
 
+// forward.cpp
 Work layout(const Options& opt, char* base, int N, int H, int W);
 inline ConvCall conv_call(const Work& w, ConvForce force = ConvForce::Auto) {     // a call with the scratch of w; the rest to fill in
     ConvCall c{};
@@ -276,6 +287,8 @@ int ensure_arena(ffr_handle* h, int N, int H, int W, Work* w);
 int ensure_arena_encoder(ffr_handle* h, int N, int H, int W, Work* w);     // + the exact-tiling weight sets an encoder forward of this size uses
 // uint8 HWC RGB input of the stem; with img2, images [n_split, N) come from img2 and flip[] has one flag per pair
 struct U8In { const unsigned char* img; const unsigned char* flip; const unsigned char* img2 = nullptr; };
+int run_trunk(ffr_handle* h, const Work& w, const float* x_nchw, int N, int H, int W, int n_blocks, hipStream_t st,
+              float** out_ptr, int* oh, int* ow, int* oc, const U8In* u8 = nullptr, const float* x2 = nullptr, int n_split = 0);
 int run_encoder(ffr_handle* h, const Work& w, const float* x, int N, int H, int W, float* featmap_nhwc, float* f,
                 hipStream_t st, const U8In* u8 = nullptr, const float* x2 = nullptr, int n_split = 0);
 struct RecDebug { float *ss_space, *M_space, *feat_space, *feat_channel_raw, *feat_channel, *ss_channel0, *M_channel0; };
@@ -283,6 +296,13 @@ int conv_rec(ffr_handle* h, const Work& w, const ConvW& L, const float* x, int i
              int res_pitch, float* out, int out_pitch, int out_coff, int flags, int N, hipStream_t st);
 int run_recnet(ffr_handle* h, const Work& w, int N, float* f_new, const RecDebug* dbg, hipStream_t st);
 int check_fwd(ffr_handle* h, bool need_enc, bool need_rec, int N);
+// conv.cpp: plain GEMMs through k_igemm (the training step)
+int gemm_rows(ffr_handle* h, const Work& w, const float* A, int a_pitch, int K_pad, const float* W, const float* bias,
+              int N_pad, float* out, int out_pitch, long long rows, const float* resid, int res_pitch, int flags,
+              hipStream_t st);
+int gemm_batched(ffr_handle* h, const Work& w, const float* A, long long a_bstride, int K_pad, const float* W,
+                 long long w_bstride, int N_pad, float* out, int out_pitch, long long out_bstride, int M, int nbatch,
+                 hipStream_t st);
 // train.cpp
 void train_free(ffr_handle* h);
 

@@ -192,7 +192,7 @@ hipError_t launch_fold_protocol(const float* score, const int* label, int n, int
 // zeros in channels [561,576), optional dense copy ss_out[N,49,49]
 hipError_t launch_selfsim_space(const float* X, float* bufS, int pitchS, float* ss_out, int N,
                                 hipStream_t stream);
-struct ChannelPathWeights {   // device pointers, see engine.cpp pack_recnet()
+struct ChannelPathWeights {   // device pointers, see pack.cpp ffr_load_recnet()
     const float* w1a;   // [32][49]   Conv4Channel.0.weight[:, :49]
     const float* w1b;   // [32][512]  Conv4Channel.0.weight[:, 49:]
     const float* b1;    // [32]

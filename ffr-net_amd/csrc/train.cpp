@@ -50,10 +50,6 @@ struct TScratch {
     bool fold = true;                              // ffr_train_option("fold_channel")
 };
 
-int gemm_rows(ffr_handle* h, const Work& w, const float* A, int a_pitch, int K_pad, const float* W, const float* bias,
-              int N_pad, float* out, int out_pitch, long long rows, const float* resid, int res_pitch, int flags,
-              hipStream_t st);
-
 // one entry of the weight-gradient plan record (ffr_train_wgrad_plan): the launcher's arguments as it ran them
 void log_wgrad(ffr_handle* h, const std::string& name, int path, const WgradArgs& a, int accumulate) {
     ffr_wgrad_launch r{};
@@ -63,10 +59,6 @@ void log_wgrad(ffr_handle* h, const std::string& name, int path, const WgradArgs
     r.full_tiles = a.full_tiles; r.tail_splits = a.tail_splits; r.tail_kt = a.tail_kt; r.accumulate = accumulate;
     h->wgrad_log.push_back(r);
 }
-
-int gemm_batched(ffr_handle* h, const Work& w, const float* A, long long a_bstride, int K_pad, const float* W,
-                 long long w_bstride, int N_pad, float* out, int out_pitch, long long out_bstride, int M, int nbatch,
-                 hipStream_t st);
 
 // y = conv(reflect_pad(x)); batch statistics; out = PReLU(BN(y)) (+ resid) (sigmoid when flags & 1)
 int layer_forward(ffr_handle* h, const Work& w, const TLayer& L, TSaved& sv, int G, int N, const float* resid,
@@ -222,39 +214,6 @@ std::vector<float> pack3x3(const float* W, int cout, int cin, int cout_pad, int 
     return p;
 }
 
-
-// ---- plain GEMMs through the implicit-GEMM kernel ---------------------------------------------------
-// out[rows][N_pad] = A[rows][K_pad] * W[N_pad][K_pad]^T + bias (+ resid) (sigmoid when flags & 1)
-int gemm_rows(ffr_handle* h, const Work& w, const float* A, int a_pitch, int K_pad, const float* W, const float* bias,
-              int N_pad, float* out, int out_pitch, long long rows, const float* resid, int res_pitch, int flags,
-              hipStream_t st) {
-    ConvW cw;
-    cw.cin = K_pad; cw.cin_pad = K_pad; cw.cout = N_pad; cw.cout_pad = N_pad; cw.R = 1; cw.S = 1; cw.stride = 1; cw.pad = 0;
-    cw.pad_mode = 0; cw.border = 0; cw.w = const_cast<float*>(W); cw.bias = bias ? const_cast<float*>(bias) : h->zero;
-    cw.slope = nullptr; cw.wu = nullptr;
-    ConvCall c = conv_call(w, ConvForce::Direct);
-    c.x = A; c.N = 1; c.H = 1; c.W = (int)rows; c.in_pitch = a_pitch; c.resid = resid; c.res_pitch = res_pitch;
-    c.out = out; c.out_pitch = out_pitch; c.out_coff = 0; c.cout_store = N_pad; c.flags = flags;
-    return run_conv(h, cw, c, st);
-}
-
-// nbatch independent GEMMs out[b][M][out_pitch] = A[b][M][K_pad] * W[b][N_pad][K_pad]^T
-int gemm_batched(ffr_handle* h, const Work& w, const float* A, long long a_bstride, int K_pad, const float* W,
-                 long long w_bstride, int N_pad, float* out, int out_pitch, long long out_bstride, int M, int nbatch,
-                 hipStream_t st) {
-    IgemmArgs g{};
-    g.x = A; g.w = W; g.bias = h->zero; g.slope = nullptr; g.resid = nullptr; g.out = out; g.zero = h->zero;
-    g.N = 1; g.H = 1; g.W = M; g.Ho = 1; g.Wo = M;
-    g.in_pitch = K_pad; g.cin_pad = K_pad; g.R = 1; g.S = 1; g.stride = 1; g.pad = 0; g.pad_mode = 0;
-    g.M = M; g.KK = K_pad; g.nkt = K_pad / 32;
-    g.cout_pad = N_pad; g.cout_store = N_pad; g.out_pitch = out_pitch; g.out_coff = 0; g.res_pitch = 0;
-    g.border_bias = 0; g.flags = 0;
-    g.nbatch = nbatch; g.x_bstride = a_bstride; g.w_bstride = w_bstride; g.out_bstride = out_bstride;
-    const ConvCall c = conv_call(w, ConvForce::Direct);
-    const double fl = 2.0 * nbatch * (double)M * N_pad * K_pad;
-    return run_gemm(h, g, c, fl, 4.0 * nbatch * ((double)M * K_pad + (double)N_pad * K_pad + (double)M * N_pad), st);
-}
-
 enum SegKind { SEG_CONV, SEG_VEC, SEG_LIN };
 struct Seg {
     std::string key;
@@ -333,13 +292,6 @@ struct TrainState {
 
 namespace {
 
-struct LayerDef { const char* p; int cin, cout; };
-const LayerDef SP_DEF[9] = {{"Conv4Space.0", 561, 256}, {"Conv4Space.1.conv1", 256, 256}, {"Conv4Space.1.conv2", 256, 256},
-                            {"Conv4Space.2", 256, 128}, {"Conv4Space.3.conv1", 128, 128}, {"Conv4Space.3.conv2", 128, 128},
-                            {"Conv4Space.4", 128, 49}, {"Conv4Space.5.conv1", 49, 49}, {"Conv4Space.5.conv2", 49, 49}};
-const LayerDef FM_DEF[3] = {{"ChannelFlipMerge.0", 1024, 512}, {"ChannelFlipMerge.1.conv1", 512, 512},
-                            {"ChannelFlipMerge.1.conv2", 512, 512}};
-const LayerDef MG_DEF[3] = {{"Conv4Merge.0", 1536, 512}, {"Conv4Merge.1.conv1", 512, 512}, {"Conv4Merge.1.conv2", 512, 512}};
 const int LIN_IDX[6] = {0, 2, 3, 5, 6, 8};
 const int LIN_IN[6] = {561, 32, 512, 32, 512, 32}, LIN_OUT[6] = {32, 512, 32, 512, 32, 512};
 const int ACT_IDX[3] = {1, 4, 7};
@@ -770,12 +722,12 @@ int ffr_train_init(ffr_handle* h, const ffr_tensor_desc* td, int n) {
     for (int i = 0; i < n; ++i) if (td[i].name) sd.m[td[i].name] = &td[i];
     // ---- layout of the flat parameter buffer --------------------------------------------------
     size_t running_floats = 0;
-    auto def_layers = [&](const LayerDef* defs, int cnt, TLayer* out) {
+    auto def_layers = [&](const RecLayer* defs, int cnt, TLayer* out) {
         for (int i = 0; i < cnt; ++i) {
             TLayer& L = out[i];
-            L.name = defs[i].p;
+            L.name = defs[i].prefix;
             L.cin = defs[i].cin; L.cout = defs[i].cout; L.cin_pad = round_up(L.cin, 32); L.cout_pad = round_up(L.cout, 64);
-            const std::string p = defs[i].p;
+            const std::string p = defs[i].prefix;
             add_seg(t, p + ".conv2d.weight", SEG_CONV, L.cout, L.cin, L.cout_pad, L.cin_pad);
             add_seg(t, p + ".relu.func.weight", SEG_VEC, L.cout, 1, L.cout_pad, 1);
             add_seg(t, p + ".norm.norm.weight", SEG_VEC, L.cout, 1, L.cout_pad, 1);
@@ -784,11 +736,11 @@ int ffr_train_init(ffr_handle* h, const ffr_tensor_desc* td, int n) {
         }
     };
     t->bucket_off[0] = t->n_flat;
-    def_layers(SP_DEF, 9, t->sp);
+    def_layers(REC_LAYERS, 9, t->sp);
     t->bucket_off[1] = t->n_flat;
-    def_layers(FM_DEF, 3, t->fm);
+    def_layers(REC_LAYERS + 9, 3, t->fm);
     t->bucket_off[2] = t->n_flat;
-    def_layers(MG_DEF, 3, t->mg);
+    def_layers(REC_LAYERS + 12, 3, t->mg);
     t->bucket_off[3] = t->n_flat;
     for (int i = 0; i < 6; ++i) {
         Lin& l = t->lin[i];
@@ -826,10 +778,10 @@ int ffr_train_init(ffr_handle* h, const ffr_tensor_desc* td, int n) {
     HIPCK(h, hipMemcpy(t->P, flat.data(), t->n_flat * 4, hipMemcpyHostToDevice));
     std::vector<float> run(running_floats, 0.f);
     size_t roff = 0;
-    auto bind_layers = [&](const LayerDef* defs, int cnt, TLayer* out) -> int {
+    auto bind_layers = [&](const RecLayer* defs, int cnt, TLayer* out) -> int {
         for (int i = 0; i < cnt; ++i) {
             TLayer& L = out[i];
-            const std::string p = defs[i].p;
+            const std::string p = defs[i].prefix;
             auto ptr = [&](const std::string& k, float* base) { return base + t->segs[t->seg_of[k]].off; };
             L.w = ptr(p + ".conv2d.weight", t->P); L.gw = ptr(p + ".conv2d.weight", t->Gr);
             L.slope = ptr(p + ".relu.func.weight", t->P); L.gslope = ptr(p + ".relu.func.weight", t->Gr);
@@ -846,9 +798,9 @@ int ffr_train_init(ffr_handle* h, const ffr_tensor_desc* td, int n) {
         }
         return FFR_OK;
     };
-    RC(bind_layers(SP_DEF, 9, t->sp));
-    RC(bind_layers(FM_DEF, 3, t->fm));
-    RC(bind_layers(MG_DEF, 3, t->mg));
+    RC(bind_layers(REC_LAYERS, 9, t->sp));
+    RC(bind_layers(REC_LAYERS + 9, 3, t->fm));
+    RC(bind_layers(REC_LAYERS + 12, 3, t->mg));
     HIPCK(h, hipMemcpy(t->running, run.data(), running_floats * 4, hipMemcpyHostToDevice));
     for (int i = 0; i < 6; ++i) {
         Lin& l = t->lin[i];

@@ -206,7 +206,7 @@ __global__ __launch_bounds__(256) void k_combine_in_mixed(const float* __restric
 // ---- weights of the tile types (4,3), (3,4), (3,3): U = G_r g G_c^T from the packed direct weights, on the device ----------
 // (round 5: these three sets -- 24-48 MB per layer, 0.7 GB per handle -- were packed by the host at load time whether or not a
 // batch that uses them ever arrived; now the engine derives them from W[cout_pad][9][cin_pad] (BatchNorm already folded) the
-// first time a launch is eligible: engine.cpp, prepare_mixed_weights.)  One thread per (output channel, input channel); fp64
+// first time a launch is eligible: pack.cpp, prepare_mixed_weights.)  One thread per (output channel, input channel); fp64
 // arithmetic, rounded once.  Output in fragment order [cout_pad/64][K chunk][XP][128 pieces][4]; padded xi stay zero (memset).
 __global__ __launch_bounds__(256) void k_wino_weights_mixed(const float* __restrict__ w, float* __restrict__ um, int cout_pad, int cin_pad,
                                                            int mr, int mc, int xp) {

@@ -329,7 +329,7 @@ def test_mixed_tile_sizes_match_direct_and_torch(engine, case):
     it) vs torch conv2d, vs the direct implicit GEMM and vs the padded F(4x4) kernel: whole tile groups, a partly empty last
     group (70 images: 280 tiles per type), PReLU, residual, 256 and 512 output channels; and the 4+3 tiling of 7x7 maps (one
     tile of each type per image; round 5: only reachable through use_wino = 4, tools/mixed7_experiment.py measures it).  The
-    three extra weight sets are derived on the device for the call (engine.cpp: ensure_mixed_weights)."""
+    three extra weight sets are derived on the device for the call (pack.cpp: ensure_mixed_weights)."""
     N, cout, prelu, resid, H, cin = case
     g = torch.Generator().manual_seed(4242 + N)
     x = torch.randn(N, H, H, cin, generator=g)
