@@ -12,6 +12,9 @@ from . import lfw  # noqa: F401
 from . import checkpoint  # noqa: F401
 from . import train  # noqa: F401
 from .train import NativeTrainer  # noqa: F401
+from . import search  # noqa: F401
+from .search import Gallery, search_sharded, identification_rates  # noqa: F401
 
 __all__ = ['Backbone', 'RecNet', 'ir_se_50_512', 'l2_norm', 'Engine', 'GraphedEmbed',
-           'NativeLibraryMissing', 'lib_path', 'synth', 'lfw', 'checkpoint', 'train', 'NativeTrainer']
+           'NativeLibraryMissing', 'lib_path', 'synth', 'lfw', 'checkpoint', 'train', 'NativeTrainer',
+           'search', 'Gallery', 'search_sharded', 'identification_rates']

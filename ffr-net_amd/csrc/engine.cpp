@@ -105,6 +105,7 @@ void ffr_destroy(ffr_handle* h) {
     if (h->side) hipStreamDestroy(h->side);
     if (h->arena) hipFree(h->arena);
     if (h->tickets) hipFree(h->tickets);
+    if (h->search_buf) hipFree(h->search_buf);
     if (h->zero) hipFree(h->zero);
     for (auto& r : h->prof_log) { hipEventDestroy(r.e0); hipEventDestroy(r.e1); }
     for (auto e : h->ev_pool) hipEventDestroy(e);
@@ -225,6 +226,71 @@ int ffr_lfw_fold_accuracy(ffr_handle* h, const float* score, const int32_t* labe
 }
 
 unsigned long long ffr_generation(const ffr_handle* h) { return h ? h->generation : 0; }
+
+// ---- 1:N identification (search.hip) ---------------------------------------------------------------------------------
+static bool misaligned16(const void* p) { return ((uintptr_t)p & 15) != 0; }
+
+int ffr_row_norms(ffr_handle* h, const float* x, long long n, int dim, float* norms, void* stream) {
+    FFR_DEVICE_SCOPE(h); RC(check_fwd(h, false, false, 1));
+    if (dim != 512) return fail(h, FFR_ERR_UNSUPPORTED, "ffr_row_norms: dim must be 512, got %d", dim);
+    if (!x || !norms || n < 1) return fail(h, FFR_ERR_ARG, "ffr_row_norms: bad arguments");
+    hipStream_t st = (hipStream_t)stream;
+    Scope s(h, st, FFR_KC_SCORE, 2.0 * n * dim, 4.0 * n * (dim + 1));
+    HIPCK(h, launch_row_norms(x, n, norms, st));
+    return FFR_OK;
+}
+
+int ffr_search_topk(ffr_handle* h, const float* query, int Q, const float* gallery, const float* gallery_norms, long long G,
+                    int dim, int k, long long index_base, float* top_score, int64_t* top_index, void* stream) {
+    FFR_DEVICE_SCOPE(h); RC(check_fwd(h, false, false, 1));
+    if (dim != 512) return fail(h, FFR_ERR_UNSUPPORTED, "ffr_search_topk: dim must be 512, got %d", dim);
+    if (!query || !top_score || !top_index || Q < 1 || k < 1 || k > 128 || G < 0 || (G > 0 && (!gallery || !gallery_norms)))
+        return fail(h, FFR_ERR_ARG, "ffr_search_topk: bad arguments (Q >= 1, 1 <= k <= 128, G >= 0, non-null pointers)");
+    if (misaligned16(query) || (G > 0 && misaligned16(gallery)))
+        return fail(h, FFR_ERR_ARG, "ffr_search_topk: query and gallery rows must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    if (G == 0) {                 // k slots of padding per probe: the merge of no list
+        Scope s(h, st, FFR_KC_SCORE, 0.0, 12.0 * Q * k);
+        HIPCK(h, launch_topk_merge(nullptr, nullptr, 0, Q, k, top_score, top_index, st));
+        return FFR_OK;
+    }
+    int T = 0, S = 0;
+    long long chunk_rows = 0;
+    search_plan(Q, G, h->num_cus, &T, &S, &chunk_rows);
+    // scratch: probe norms [Q], then the chunk lists [S][Q][k] (scores, indices) when there is more than one chunk
+    const size_t norm_bytes = ((size_t)Q * 4 + 255) & ~(size_t)255;
+    const size_t list_s = S > 1 ? (((size_t)S * Q * k * 4 + 255) & ~(size_t)255) : 0;
+    const size_t need = norm_bytes + list_s + (S > 1 ? (size_t)S * Q * k * 8 : 0);
+    if (need > h->search_bytes) {
+        if (h->search_buf) { hipDeviceSynchronize(); hipFree(h->search_buf); h->search_buf = nullptr; h->search_bytes = 0; }
+        void* p = nullptr;
+        if (hipMalloc(&p, need) != hipSuccess) return fail(h, FFR_ERR_NOMEM, "hipMalloc of %zu search bytes failed", need);
+        h->search_buf = (char*)p;
+        h->search_bytes = need;
+        ++h->generation;          // a graph captured around an earlier call points at the old scratch
+    }
+    float* qnorm = (float*)h->search_buf;
+    float* part_s = S > 1 ? (float*)(h->search_buf + norm_bytes) : top_score;
+    int64_t* part_i = S > 1 ? (int64_t*)(h->search_buf + norm_bytes + list_s) : top_index;
+    Scope s(h, st, FFR_KC_SCORE, 2.0 * Q * (double)G * dim, 4.0 * (double)G * (dim + 1) + 4.0 * Q * dim + 12.0 * Q * k);
+    HIPCK(h, launch_row_norms(query, Q, qnorm, st));
+    HIPCK(h, launch_search_topk(query, qnorm, Q, gallery, gallery_norms, G, k, index_base, T, S, chunk_rows, part_s, part_i,
+                                st));
+    if (S > 1) HIPCK(h, launch_topk_merge(part_s, part_i, S, Q, k, top_score, top_index, st));
+    return FFR_OK;
+}
+
+int ffr_topk_merge(ffr_handle* h, const float* score, const int64_t* index, int S, int Q, int k, float* out_score,
+                   int64_t* out_index, void* stream) {
+    FFR_DEVICE_SCOPE(h); RC(check_fwd(h, false, false, 1));
+    if (!score || !index || !out_score || !out_index || S < 1 || S > 4096 || Q < 1 || k < 1 || k > 128)
+        return fail(h, FFR_ERR_ARG, "ffr_topk_merge: bad arguments (1 <= S <= 4096, Q >= 1, 1 <= k <= 128, non-null pointers)");
+    hipStream_t st = (hipStream_t)stream;
+    Scope s(h, st, FFR_KC_SCORE, 0.0, 12.0 * (double)S * Q * k + 12.0 * Q * k);
+    HIPCK(h, launch_topk_merge(score, index, S, Q, k, out_score, out_index, st));
+    return FFR_OK;
+}
+
 
 // ---- per-layer arithmetic plan --------------------------------------------------------------------------------------
 int ffr_layer_count(const ffr_handle* h, int* n) {

@@ -116,6 +116,9 @@ struct ffr_handle {
     ffr_eng::TrainState* train = nullptr;
     // weight-gradient launch plans of the most recent backward (ffr_train_wgrad_plan)
     std::vector<ffr_wgrad_launch> wgrad_log;
+    // 1:N search scratch (ffr_search_topk): probe norms + per-chunk top-k lists; grows on demand
+    char* search_buf = nullptr;
+    size_t search_bytes = 0;
     // bumped whenever device memory a caller may have captured (hipGraph) is released: workspace regrowth, weight
     // reload, ffr_train_init
     unsigned long long generation = 1;

@@ -183,6 +183,20 @@ int absdiff_scratch_floats();
 hipError_t launch_absdiff_max(const float* a, int a_pitch, const float* b, int b_pitch, int rows, int cols, float* part,
                               float* out, hipStream_t stream);
 
+// ---- 1:N identification (search.hip) -------------------------------------------------
+// norms[r] = |x[r]| of [n][512] rows (the sum of squares of k_cosine)
+hipError_t launch_row_norms(const float* x, long long n, float* norms, hipStream_t stream);
+// chunking of a search: probe tiles x gallery chunks (chunk_rows <= search_max_chunk_rows()); G >= 1
+long long search_max_chunk_rows();
+void search_plan(int Q, long long G, int num_cus, int* ntiles, int* nchunks, long long* chunk_rows);
+// top-k lists [nchunks][Q][k] of every gallery chunk (one launch); k <= 128, dim 512, rows 16-byte aligned
+hipError_t launch_search_topk(const float* query, const float* qnorm, int Q, const float* gallery, const float* gnorm,
+                              long long G, int k, long long index_base, int ntiles, int nchunks, long long chunk_rows,
+                              float* out_s, int64_t* out_i, hipStream_t stream);
+// S sorted lists [S][Q][k] -> [Q][k] (descending score, ties by ascending index; index < 0 = padding); S <= 4096
+hipError_t launch_topk_merge(const float* score, const int64_t* index, int S, int Q, int k, float* out_s, int64_t* out_i,
+                             hipStream_t stream);
+
 // LFW fold protocol on device; scratch = 400*32 ints, best_thr/test_acc = nf doubles (device)
 hipError_t launch_fold_protocol(const float* score, const int* label, int n, int nf, int* scratch, double* best_thr,
                                 double* test_acc, hipStream_t stream);

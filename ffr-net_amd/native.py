@@ -95,6 +95,9 @@ SYMBOLS = [
     ('ffr_encoder_forward_u8', C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     ('ffr_cosine_scores', C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P]),
     ('ffr_lfw_fold_accuracy', C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, _P]),
+    ('ffr_row_norms', C.c_int, [_P, _P, C.c_longlong, C.c_int, _P, _P]),
+    ('ffr_search_topk', C.c_int, [_P, _P, C.c_int, _P, _P, C.c_longlong, C.c_int, C.c_int, C.c_longlong, _P, _P, _P]),
+    ('ffr_topk_merge', C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     ('ffr_workspace_bytes', C.c_size_t, [_P, C.c_int, C.c_int, C.c_int]),
     ('ffr_reserve', C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
     ('ffr_generation', C.c_ulonglong, [_P]),
@@ -402,6 +405,67 @@ class Engine(object):
                                                     _ptr(thr), _ptr(acc), self._stream()))
         thr, acc = thr.cpu().tolist(), acc.cpu().tolist()
         return sum(acc) / n_folds, list(zip(thr, acc))
+
+    # -- 1:N identification (include/ffrnet.h: ffr_row_norms, ffr_search_topk, ffr_topk_merge) -------------------------
+    def row_norms(self, x):
+        """|x[r]| of x[n,512] rows (device fp32), the norms the search divides by -> norms[n]."""
+        _check_dev(x, 'x', device=self.device)
+        if x.dim() != 2:
+            raise RuntimeError('ffrnet_amd: row_norms expects [n,dim], got %s' % list(x.shape))
+        x = x.contiguous()
+        out = torch.empty((x.size(0),), device=x.device, dtype=torch.float32)
+        if x.size(0) == 0:
+            return out
+        with torch.cuda.device(self.device):
+            self._ck(self.lib.ffr_row_norms(self._h, _ptr(x), x.size(0), x.size(1), _ptr(out), self._stream()))
+        return out
+
+    def search(self, query, gallery, k, gallery_norms=None, index_base=0):
+        """Exact cosine top-k: query[Q,512], gallery[G,512] (device fp32) -> (scores[Q,k] fp32, index[Q,k] int64), per
+        probe by descending score, ties by ascending index; index = index_base + gallery row; (-inf, -1) pads G < k.
+        gallery_norms[G]: row_norms(gallery), computed here when not given (pass them when the gallery is reused)."""
+        _check_dev(query, 'query', device=self.device)
+        _check_dev(gallery, 'gallery', device=self.device)
+        if query.dim() != 2 or gallery.dim() != 2 or query.size(1) != gallery.size(1):
+            raise RuntimeError('ffrnet_amd: search expects query [Q,dim] and gallery [G,dim], got %s and %s'
+                               % (list(query.shape), list(gallery.shape)))
+        query, gallery = query.contiguous(), gallery.contiguous()
+        G = gallery.size(0)
+        if gallery_norms is None:
+            gallery_norms = self.row_norms(gallery) if G else None
+        else:
+            _check_dev(gallery_norms, 'gallery_norms', device=self.device)
+            if tuple(gallery_norms.shape) != (G,):
+                raise RuntimeError('ffrnet_amd: gallery_norms must be [%d], got %s' % (G, list(gallery_norms.shape)))
+            gallery_norms = gallery_norms.contiguous()
+        Q, k = query.size(0), int(k)
+        scores = torch.empty((Q, max(k, 0)), device=query.device, dtype=torch.float32)
+        index = torch.empty((Q, max(k, 0)), device=query.device, dtype=torch.int64)
+        with torch.cuda.device(self.device):
+            self._ck(self.lib.ffr_search_topk(self._h, _ptr(query), Q, _ptr(gallery if G else None), _ptr(gallery_norms),
+                                              G, query.size(1), k, int(index_base), _ptr(scores), _ptr(index),
+                                              self._stream()))
+        return scores, index
+
+    def topk_merge(self, scores, index):
+        """Merge S sorted lists per probe, scores[S,Q,k] fp32 and index[S,Q,k] int64 (device; index < 0 = padding), in
+        the order of search() -> (scores[Q,k], index[Q,k])."""
+        _check_dev(scores, 'scores', device=self.device)
+        if not isinstance(index, torch.Tensor) or not index.is_cuda or index.device.index != self.device.index:
+            raise RuntimeError('ffrnet_amd: index must be a tensor on %s' % self.device)
+        if index.dtype != torch.int64:
+            raise RuntimeError('ffrnet_amd: index must be int64, got %s' % index.dtype)
+        if scores.dim() != 3 or tuple(index.shape) != tuple(scores.shape):
+            raise RuntimeError('ffrnet_amd: topk_merge expects scores and index [S,Q,k], got %s and %s'
+                               % (list(scores.shape), list(index.shape)))
+        S, Q, k = scores.shape
+        scores, index = scores.contiguous(), index.contiguous()
+        out_s = torch.empty((Q, k), device=scores.device, dtype=torch.float32)
+        out_i = torch.empty((Q, k), device=scores.device, dtype=torch.int64)
+        with torch.cuda.device(self.device):
+            self._ck(self.lib.ffr_topk_merge(self._h, _ptr(scores), _ptr(index), S, Q, k, _ptr(out_s), _ptr(out_i),
+                                             self._stream()))
+        return out_s, out_i
 
     # -- arena / measurement --------------------------------------------------
     def workspace_bytes(self, n, h=112, w=112):

@@ -1,0 +1,119 @@
+"""1:N identification on top of the library's exact cosine top-k (include/ffrnet.h: ffr_search_topk).
+
+FFR-Net matches masked probes against mask-free enrolments with one model; the reference's harness only scores
+aligned pairs (lfw/lfw_eval.py).  This module answers "which of my G enrolled people is this?":
+
+  gallery = Gallery(engine); first = gallery.add(f_enrol)        # embeddings [n,512], e.g. Engine.embed(...)[0]
+  scores, index = gallery.search(f_probe, k=10)                  # [Q,k] each, descending score, ties by index
+  rates = identification_rates(index, probe_labels, gallery_labels)   # CMC rank-1 / 5 / 10
+
+A gallery spread over several processes (one per GPU) searches its shards with search_sharded().
+"""
+import torch
+
+try:
+    import torch.distributed as dist
+except ImportError:            # pragma: no cover
+    dist = None
+
+DIM = 512
+
+
+class Gallery(object):
+    """Enrolled embeddings [n,512] and their norms on the Engine's device, in a grow-only buffer: add() appends, rows
+    keep their index for ever (the index search() returns)."""
+
+    def __init__(self, engine, capacity=0):
+        self.engine = engine
+        self._n = 0
+        self._emb = torch.empty((int(capacity), DIM), device=engine.device, dtype=torch.float32)
+        self._norms = torch.empty((int(capacity),), device=engine.device, dtype=torch.float32)
+
+    def __len__(self):
+        return self._n
+
+    @property
+    def embeddings(self):
+        return self._emb[:self._n]
+
+    @property
+    def norms(self):
+        return self._norms[:self._n]
+
+    def add(self, emb):
+        """Append emb[n,512] (fp32, on the Engine's device) -> the index of its first row."""
+        if not isinstance(emb, torch.Tensor) or emb.dim() != 2 or emb.size(1) != DIM:
+            raise RuntimeError('ffrnet_amd: Gallery.add expects [n,%d] embeddings, got %s'
+                               % (DIM, list(emb.shape) if isinstance(emb, torch.Tensor) else type(emb)))
+        n = emb.size(0)
+        first = self._n
+        if first + n > self._emb.size(0):
+            cap = max(first + n, 2 * self._emb.size(0), 1024)
+            emb_new = torch.empty((cap, DIM), device=self._emb.device, dtype=torch.float32)
+            norms_new = torch.empty((cap,), device=self._emb.device, dtype=torch.float32)
+            emb_new[:first] = self._emb[:first]
+            norms_new[:first] = self._norms[:first]
+            self._emb, self._norms = emb_new, norms_new
+        if n:
+            self._emb[first:first + n] = emb
+            self._norms[first:first + n] = self.engine.row_norms(self._emb[first:first + n])
+        self._n = first + n
+        return first
+
+    def search(self, query, k, self_index=None, index_base=0):
+        """Top-k enrolled rows of every probe query[Q,512] -> (scores[Q,k], index[Q,k]).  self_index[Q] (gallery
+        indices of the probes themselves): leave-one-out search, the probe's own row is never returned."""
+        if self_index is None:
+            return self.engine.search(query, self.embeddings, k, gallery_norms=self.norms, index_base=index_base)
+        s, i = self.engine.search(query, self.embeddings, int(k) + 1, gallery_norms=self.norms, index_base=index_base)
+        return drop_self(s, i, torch.as_tensor(self_index, device=i.device) + int(index_base))
+
+
+def drop_self(scores, index, self_index):
+    """Leave-one-out trimming of top-(k+1) lists [Q,k+1]: drop the entry whose index is the probe's own self_index[q]
+    (or the last entry when the probe's row is not in the list) -> (scores[Q,k], index[Q,k]), order kept."""
+    Q, k1 = index.shape
+    drop = index == self_index.reshape(-1, 1).to(index.dtype)
+    drop[:, -1] |= ~drop.any(1)
+    keep = ~drop
+    return scores[keep].view(Q, k1 - 1), index[keep].view(Q, k1 - 1)
+
+
+def search_sharded(gallery_shard, query, k, group=None):
+    """Search a gallery split in contiguous shards over the ranks of `group` (rank r holds rows that follow those of
+    ranks < r): every rank passes its own Gallery and the SAME probes query[Q,512] and gets the global top-k.
+    Index bases come from the gathered shard sizes; the per-rank [Q,k] lists travel in one all_gather_into_tensor and
+    every rank merges them (ffr_topk_merge).  Bitwise equal to one search over the concatenated gallery."""
+    eng = gallery_shard.engine
+    if dist is None or not dist.is_available() or not dist.is_initialized() or dist.get_world_size(group) == 1:
+        return gallery_shard.search(query, k)
+    world, rank = dist.get_world_size(group), dist.get_rank(group)
+    sizes = torch.empty((world,), device=query.device, dtype=torch.int64)
+    dist.all_gather_into_tensor(sizes, torch.tensor([len(gallery_shard)], device=query.device, dtype=torch.int64),
+                                group=group)
+    base = int(sizes[:rank].sum().item())
+    s, i = gallery_shard.search(query, k, index_base=base)
+    Q, kk = s.shape
+    # one exchange: per slot the score's bits and the two halves of the index, as int32 words
+    mine = torch.cat((s.contiguous().view(torch.int32).view(Q, kk, 1), i.contiguous().view(torch.int32).view(Q, kk, 2)), 2)
+    allw = torch.empty((world * Q, kk, 3), device=query.device, dtype=torch.int32)      # rank-major along dim 0
+    dist.all_gather_into_tensor(allw, mine.contiguous(), group=group)
+    allw = allw.view(world, Q, kk, 3)
+    all_s = allw[..., 0].contiguous().view(torch.float32)
+    all_i = allw[..., 1:].contiguous().view(torch.int64).view(world, Q, kk)
+    return eng.topk_merge(all_s, all_i)
+
+
+def identification_rates(index, probe_labels, gallery_labels, ranks=(1, 5, 10)):
+    """CMC: the fraction of probes whose label appears among their first r results, for every r in ranks.
+    index[Q,k] (gallery indices, -1 = padding), probe_labels[Q], gallery_labels[G] -> {r: rate}."""
+    index = torch.as_tensor(index)
+    gl = torch.as_tensor(gallery_labels).to(index.device)
+    pl = torch.as_tensor(probe_labels).to(index.device)
+    valid = index >= 0
+    lab = gl[index.clamp(min=0)]
+    hit = (lab == pl.reshape(-1, 1)) & valid
+    out = {}
+    for r in ranks:
+        out[r] = float(hit[:, :r].any(1).double().mean().item()) if index.size(0) else 0.0
+    return out

@@ -108,6 +108,38 @@ int ffr_embed_u8(ffr_handle* h, const uint8_t* img_hwc_rgb, const uint8_t* flip,
 int ffr_cosine_scores(ffr_handle* h, const float* a, const float* b, int n, int dim,
                       float* score, void* stream);
 
+/* ---- 1:N identification (exact cosine top-k over a gallery) --------------------------------------------------------
+ * What the reference's harness lacks: "which of my G enrolled people is this probe?" for masked probes against
+ * mask-free enrolments.  Exact brute force in fp32; no approximate index.
+ *   score  s(q, g) = dot(q, g) / (|q| |g| + 1e-8), the formula of ffr_cosine_scores and lfw/lfw_eval.py:246; the norms
+ *          are fp32 square roots of fp32 sums of squares (ffr_row_norms, as k_cosine computes them); a zero row scores 0.
+ *   shapes dim = 512 only (FFR_ERR_UNSUPPORTED otherwise); 1 <= k <= 128, Q >= 1, G >= 0 (FFR_ERR_ARG otherwise).
+ *          Rows are contiguous [n][512] fp32, device, 16-byte aligned (FFR_ERR_ARG otherwise); gallery and gallery_norms
+ *          may be NULL only when G = 0.
+ *   result top_score[Q][k] fp32, top_index[Q][k] int64 (= index_base + gallery row), per probe ordered by DESCENDING
+ *          score, ties by ASCENDING index.  When G < k the last k - G slots hold (-inf, -1): they sort after every real
+ *          entry, so lists of small or empty shards merge without a special case.
+ *   bitwise every (q, g) score is the same fp32 MFMA chain over k wherever it is computed, so repeated calls agree, row q
+ *          of a Q-probe call equals the 1-probe call of that probe, and searching contiguous shards of the gallery (each
+ *          with its index_base) and merging with ffr_topk_merge equals one search over the whole gallery.
+ *   memory the Q x G score matrix never leaves the chip; no host synchronisation; the handle's search scratch (probe norms,
+ *          per-chunk lists) grows on demand -- hipMalloc on the first call at a larger shape, which bumps ffr_generation
+ *          -- and is reused afterwards, so a call can be captured into a hipGraph once it has run at that shape.
+ *          Galleries of 2 GiB and more are supported (64-bit chunk bases, 32-bit offsets inside a chunk).
+ *   NaN    inputs holding NaN or inf give unspecified (in-bounds) results.
+ * No weights need to be loaded.  Launches are profiled under FFR_KC_SCORE; a search counts flops = 2*Q*G*512.        */
+/* norms[n] = |x[r]| of x[n][dim] rows (device); n >= 1.                                                              */
+int ffr_row_norms(ffr_handle* h, const float* x, long long n, int dim, float* norms, void* stream);
+/* top-k gallery rows of every probe.  query[Q][dim], gallery[G][dim], gallery_norms[G] (ffr_row_norms of the gallery,
+ * computed once at enrolment); the probe norms are computed per call.                                                */
+int ffr_search_topk(ffr_handle* h, const float* query, int Q, const float* gallery, const float* gallery_norms,
+                    long long G, int dim, int k, long long index_base,
+                    float* top_score, int64_t* top_index, void* stream);
+/* Merge S sorted lists per probe (score[S][Q][k], index[S][Q][k], e.g. one per rank of a sharded search) into one
+ * [Q][k] list in the same total order; slots with index < 0 are padding.  1 <= S <= 4096, 1 <= k <= 128, Q >= 1.     */
+int ffr_topk_merge(ffr_handle* h, const float* score, const int64_t* index, int S, int Q, int k,
+                   float* out_score, int64_t* out_index, void* stream);
+
 /* Fold protocol of lfw/lfw_eval.py:110-118,137-162,255-270 on the device: thresholds
  * np.arange(-1, 1, 0.005), same iff score > thr, n_folds contiguous test folds (KFold, no shuffle),
  * best threshold = LAST one reaching the best train accuracy, accuracy on the held-out fold.
