@@ -106,6 +106,7 @@ void ffr_destroy(ffr_handle* h) {
     if (h->arena) hipFree(h->arena);
     if (h->tickets) hipFree(h->tickets);
     if (h->search_buf) hipFree(h->search_buf);
+    if (h->align_buf) hipFree(h->align_buf);
     if (h->zero) hipFree(h->zero);
     for (auto& r : h->prof_log) { hipEventDestroy(r.e0); hipEventDestroy(r.e1); }
     for (auto e : h->ev_pool) hipEventDestroy(e);
@@ -291,6 +292,88 @@ int ffr_topk_merge(ffr_handle* h, const float* score, const int64_t* index, int 
     return FFR_OK;
 }
 
+
+// ---- face alignment (align.hip) --------------------------------------------------------------------------------------
+static int align_tfm_check(ffr_handle* h, const float* landmarks, const float* tmpl, int K) {
+    if (!landmarks || !tmpl || K < 2 || K > 16)
+        return fail(h, FFR_ERR_ARG, "alignment transforms: bad arguments (non-null landmarks and template, 2 <= K <= 16)");
+    return FFR_OK;
+}
+
+static int align_warp_check(ffr_handle* h, const uint8_t* frames, int F, int H, int W, long long pitch,
+                            const int32_t* frame_index, int oh, int ow) {
+    if (!frames || !frame_index || F < 1 || H < 1 || W < 1)
+        return fail(h, FFR_ERR_ARG, "alignment warp: bad arguments (non-null frames and frame_index, F, H, W >= 1)");
+    if (oh < 1 || oh > 256 || ow < 1 || ow > 256 || (ow & 3))
+        return fail(h, FFR_ERR_ARG, "alignment warp: out_h and out_w must be in 1..256 and out_w a multiple of 4, got %d x %d", oh, ow);
+    if (pitch < 3ll * W) return fail(h, FFR_ERR_ARG, "alignment warp: pitch_bytes %lld < 3 * W = %d", pitch, 3 * W);
+    if (pitch * H >= (1ll << 31))
+        return fail(h, FFR_ERR_ARG, "alignment warp: a frame of %lld bytes is over the 2 GiB offset limit", pitch * H);
+    return FFR_OK;
+}
+
+static int align_tfm(ffr_handle* h, const float* landmarks, const float* tmpl, int N, int K, const int32_t* frame_index, int F,
+                     double* A, uint8_t* valid, hipStream_t st) {
+    Scope s(h, st, FFR_KC_LAYOUT, 40.0 * N * K, 8.0 * N * K + 49.0 * N);
+    HIPCK(h, launch_align_tfm(landmarks, tmpl, N, K, (const int*)frame_index, F, A, valid, st));
+    return FFR_OK;
+}
+
+static int align_warp(ffr_handle* h, const uint8_t* frames, int F, int H, int W, long long pitch, const int32_t* frame_index,
+                      const double* A, const uint8_t* valid, int N, int oh, int ow, uint8_t* crop, hipStream_t st) {
+    Scope s(h, st, FFR_KC_LAYOUT, 0, 15.0 * N * oh * ow);      // 4 taps read + 1 byte written per output byte
+    HIPCK(h, launch_align_warp(frames, F, H, W, (int)pitch, (const int*)frame_index, A, valid, N, oh, ow, crop, st));
+    return FFR_OK;
+}
+
+int ffr_align_transforms(ffr_handle* h, const float* landmarks, const float* tmpl, int N, int K, double* A, uint8_t* valid,
+                         void* stream) {
+    FFR_DEVICE_SCOPE(h); RC(check_fwd(h, false, false, N));
+    RC(align_tfm_check(h, landmarks, tmpl, K));
+    if (!A || !valid) return fail(h, FFR_ERR_ARG, "ffr_align_transforms: A / valid is null");
+    return align_tfm(h, landmarks, tmpl, N, K, nullptr, 0, A, valid, (hipStream_t)stream);
+}
+
+int ffr_align_warp(ffr_handle* h, const uint8_t* frames, int F, int H, int W, long long pitch_bytes, const int32_t* frame_index,
+                   const double* A, const uint8_t* valid, int N, int out_h, int out_w, uint8_t* crop, void* stream) {
+    FFR_DEVICE_SCOPE(h); RC(check_fwd(h, false, false, N));
+    RC(align_warp_check(h, frames, F, H, W, pitch_bytes, frame_index, out_h, out_w));
+    if (!A || !crop) return fail(h, FFR_ERR_ARG, "ffr_align_warp: A / crop is null");
+    if ((uintptr_t)crop & 3) return fail(h, FFR_ERR_ARG, "ffr_align_warp: crop must be 4-byte aligned");
+    return align_warp(h, frames, F, H, W, pitch_bytes, frame_index, A, valid, N, out_h, out_w, crop, (hipStream_t)stream);
+}
+
+int ffr_embed_aligned(ffr_handle* h, const uint8_t* frames, int F, int H, int W, long long pitch_bytes,
+                      const int32_t* frame_index, const float* landmarks, const float* tmpl, int K, const uint8_t* flip, int N,
+                      float* f_new, float* f, uint8_t* valid, void* stream) {
+    FFR_DEVICE_SCOPE(h); RC(check_fwd(h, true, true, N));
+    if (!f_new) return fail(h, FFR_ERR_ARG, "f_new is null");
+    RC(align_tfm_check(h, landmarks, tmpl, K));
+    RC(align_warp_check(h, frames, F, H, W, pitch_bytes, frame_index, 112, 112));
+    hipStream_t st = (hipStream_t)stream;
+    // scratch: transforms [N][6] fp64, valid [N], crops [N][112][112][3]
+    const size_t a_bytes = ((size_t)N * 48 + 255) & ~(size_t)255, v_bytes = ((size_t)N + 255) & ~(size_t)255;
+    const size_t need = a_bytes + v_bytes + (size_t)N * 112 * 112 * 3;
+    if (need > h->align_bytes) {
+        if (h->align_buf) { hipDeviceSynchronize(); hipFree(h->align_buf); h->align_buf = nullptr; h->align_bytes = 0; }
+        void* p = nullptr;
+        if (hipMalloc(&p, need) != hipSuccess) return fail(h, FFR_ERR_NOMEM, "hipMalloc of %zu alignment bytes failed", need);
+        h->align_buf = (char*)p;
+        h->align_bytes = need;
+        ++h->generation;          // a graph captured around an earlier call points at the old scratch
+    }
+    double* A = (double*)h->align_buf;
+    uint8_t* v = (uint8_t*)(h->align_buf + a_bytes);
+    uint8_t* crop = (uint8_t*)(h->align_buf + a_bytes + v_bytes);
+    Work w;
+    RC(ensure_arena_encoder(h, N, 112, 112, &w));
+    RC(align_tfm(h, landmarks, tmpl, N, K, frame_index, F, A, v, st));
+    RC(align_warp(h, frames, F, H, W, pitch_bytes, frame_index, A, v, N, 112, 112, crop, st));
+    if (valid) HIPCK(h, hipMemcpyAsync(valid, v, (size_t)N, hipMemcpyDeviceToDevice, st));
+    U8In u8{crop, flip};
+    RC(run_encoder(h, w, nullptr, N, 112, 112, w.X, f, st, &u8));
+    return run_recnet(h, w, N, f_new, nullptr, st);
+}
 
 // ---- per-layer arithmetic plan --------------------------------------------------------------------------------------
 int ffr_layer_count(const ffr_handle* h, int* n) {

@@ -119,6 +119,9 @@ struct ffr_handle {
     // 1:N search scratch (ffr_search_topk): probe norms + per-chunk top-k lists; grows on demand
     char* search_buf = nullptr;
     size_t search_bytes = 0;
+    // alignment scratch (ffr_embed_aligned): transforms [N][6] fp64, valid flags [N], crops [N][112][112][3]; grows on demand
+    char* align_buf = nullptr;
+    size_t align_bytes = 0;
     // bumped whenever device memory a caller may have captured (hipGraph) is released: workspace regrowth, weight
     // reload, ffr_train_init
     unsigned long long generation = 1;

@@ -197,6 +197,16 @@ hipError_t launch_search_topk(const float* query, const float* qnorm, int Q, con
 hipError_t launch_topk_merge(const float* score, const int64_t* index, int S, int Q, int k, float* out_s, int64_t* out_i,
                              hipStream_t stream);
 
+// ---- face alignment (align.hip) --------------------------------------------------------
+// landmarks[N][K][2], tmpl[K][2] fp32 -> A[N][6] fp64 (row-major 2x3, crop -> frame), valid[N]; 2 <= K <= 16; with a
+// frame_index[N] (may be null) a face whose frame is outside [0,F) is invalid too
+hipError_t launch_align_tfm(const float* landmarks, const float* tmpl, int N, int K, const int* frame_index, int F, double* A,
+                            uint8_t* valid, hipStream_t stream);
+// frames[F][H][W][3] uint8 (row pitch in bytes, pitch*H < 2^31) -> crop[N][oh][ow][3]; valid may be null; ow % 4 == 0,
+// oh, ow <= 256, crop 4-byte aligned
+hipError_t launch_align_warp(const uint8_t* frames, int F, int H, int W, int pitch, const int* frame_index, const double* A,
+                             const uint8_t* valid, int N, int oh, int ow, uint8_t* crop, hipStream_t stream);
+
 // LFW fold protocol on device; scratch = 400*32 ints, best_thr/test_acc = nf doubles (device)
 hipError_t launch_fold_protocol(const float* score, const int* label, int n, int nf, int* scratch, double* best_thr,
                                 double* test_acc, hipStream_t stream);

@@ -8,6 +8,8 @@ import os
 
 import torch
 
+from . import align as _align
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
 
@@ -98,6 +100,10 @@ SYMBOLS = [
     ('ffr_row_norms', C.c_int, [_P, _P, C.c_longlong, C.c_int, _P, _P]),
     ('ffr_search_topk', C.c_int, [_P, _P, C.c_int, _P, _P, C.c_longlong, C.c_int, C.c_int, C.c_longlong, _P, _P, _P]),
     ('ffr_topk_merge', C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    ('ffr_align_transforms', C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, _P]),
+    ('ffr_align_warp', C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_longlong, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
+    ('ffr_embed_aligned', C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_longlong, _P, _P, _P, C.c_int, _P, C.c_int, _P, _P, _P,
+                                    _P]),
     ('ffr_workspace_bytes', C.c_size_t, [_P, C.c_int, C.c_int, C.c_int]),
     ('ffr_reserve', C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
     ('ffr_generation', C.c_ulonglong, [_P]),
@@ -466,6 +472,86 @@ class Engine(object):
             self._ck(self.lib.ffr_topk_merge(self._h, _ptr(scores), _ptr(index), S, Q, k, _ptr(out_s), _ptr(out_i),
                                              self._stream()))
         return out_s, out_i
+
+    # -- face alignment (include/ffrnet.h: ffr_align_transforms, ffr_align_warp, ffr_embed_aligned) -------------------
+    def _align_points(self, landmarks, template):
+        """device copies of landmarks [N,K,2] and the template [K,2] -> (landmarks, template, N, K)"""
+        tmpl = _align.as_template(template)
+        K = tmpl.size(0)
+        N = _align.check_landmarks(landmarks, K)
+        _check_dev(landmarks, 'landmarks', device=self.device)
+        return landmarks.contiguous(), tmpl.to(self.device), N, K
+
+    def _align_frames(self, frames, frame_index, N):
+        """frames [F,H,W,3] uint8 (rows may be padded) and frame_index [N] -> (frames, pitch_bytes, int32 frame_index)"""
+        _check_u8(frames, 'frames', self.device)
+        if frames.size(0) < 1 or frames.size(1) < 1 or frames.size(2) < 1:
+            raise RuntimeError('ffrnet_amd: frames must not be empty, got %s' % list(frames.shape))
+        pitch = _align.frame_pitch(frames)
+        if pitch is None:
+            frames = frames.contiguous()
+            pitch = 3 * frames.size(2)
+        _align.check_frame_bytes(pitch, frames.size(1))
+        if not isinstance(frame_index, torch.Tensor) or frame_index.dtype not in (torch.int32, torch.int64):
+            raise RuntimeError('ffrnet_amd: frame_index must be an int32 or int64 tensor')
+        if frame_index.numel() != N:
+            raise RuntimeError('ffrnet_amd: frame_index must hold %d entries, got %d' % (N, frame_index.numel()))
+        if frame_index.is_cuda and frame_index.device.index != self.device.index:
+            raise RuntimeError('ffrnet_amd: frame_index is on %s but this Engine lives on %s' % (frame_index.device, self.device))
+        return frames, pitch, frame_index.reshape(-1).to(self.device, torch.int32).contiguous()
+
+    def align_transforms(self, landmarks, template=_align.TEMPLATE_112x112):
+        """landmarks[N,K,2] fp32 (device; (x, y) in the face's frame) and the template's K points in the crop ->
+        (A float64 [N,6], valid uint8 [N]): the row-major 2x3 similarity crop -> frame of the reference's cp2tform fit,
+        valid = 0 (and A = 0) for degenerate or non-finite landmarks."""
+        landmarks, tmpl, N, K = self._align_points(landmarks, template)
+        A = torch.empty((N, 6), device=self.device, dtype=torch.float64)
+        valid = torch.empty((N,), device=self.device, dtype=torch.uint8)
+        with torch.cuda.device(self.device):
+            self._ck(self.lib.ffr_align_transforms(self._h, _ptr(landmarks), _ptr(tmpl), N, K, _ptr(A), _ptr(valid),
+                                                   self._stream()))
+        return A, valid
+
+    def align_warp(self, frames, frame_index, A, valid=None, out_hw=(112, 112)):
+        """frames[F,H,W,3] uint8 (device; rows may be padded: the pitch is its row stride), frame_index[N], A[N,6]
+        float64 -> crops uint8 [N,h,w,3] by the exact 1/32-pixel bilinear rule of include/ffrnet.h; zeros where
+        valid[n] == 0 or frame_index[n] is outside [0,F)."""
+        oh, ow = _align.check_out_hw(out_hw)
+        if not isinstance(A, torch.Tensor) or not A.is_cuda or A.device.index != self.device.index:
+            raise RuntimeError('ffrnet_amd: A must be a tensor on %s' % self.device)
+        if A.dtype != torch.float64 or A.dim() != 2 or A.size(1) != 6 or A.size(0) < 1:
+            raise RuntimeError('ffrnet_amd: A must be float64 [N,6] with N >= 1, got %s %s' % (A.dtype, list(A.shape)))
+        N = A.size(0)
+        frames, pitch, fidx = self._align_frames(frames, frame_index, N)
+        v = _flip_flags(valid, N, self.device, 'valid')
+        crop = torch.empty((N, oh, ow, 3), device=self.device, dtype=torch.uint8)
+        with torch.cuda.device(self.device):
+            self._ck(self.lib.ffr_align_warp(self._h, _ptr(frames), frames.size(0), frames.size(1), frames.size(2), pitch,
+                                             _ptr(fidx), _ptr(A.contiguous()), _ptr(v), N, oh, ow, _ptr(crop),
+                                             self._stream()))
+        return crop
+
+    def align_crops(self, frames, frame_index, landmarks, template=_align.TEMPLATE_112x112, out_hw=(112, 112)):
+        """align_transforms + align_warp -> crops uint8 [N,h,w,3] (zeros for a face that is not valid)."""
+        A, valid = self.align_transforms(landmarks, template)
+        return self.align_warp(frames, frame_index, A, valid, out_hw)
+
+    def embed_aligned(self, frames, frame_index, landmarks, template=_align.TEMPLATE_112x112, flip=None, want_f=True):
+        """Detector output to embeddings in one call: transforms, the 112x112 warp into the handle's scratch and the
+        embed_u8 pipeline -> (f_new[N,512], f[N,512] or None, valid uint8 [N]); bit-identical to
+        embed_u8(align_crops(...), flip).  valid[n] == 0 (degenerate landmarks, or a frame_index outside [0,F)): the row is
+        the embedding of a zero crop, to be dropped."""
+        landmarks, tmpl, N, K = self._align_points(landmarks, template)
+        frames, pitch, fidx = self._align_frames(frames, frame_index, N)
+        fl = _flip_flags(flip, N, self.device)
+        f_new = torch.empty((N, 512), device=self.device, dtype=torch.float32)
+        f = torch.empty((N, 512), device=self.device, dtype=torch.float32) if want_f else None
+        valid = torch.empty((N,), device=self.device, dtype=torch.uint8)
+        with torch.cuda.device(self.device):
+            self._ck(self.lib.ffr_embed_aligned(self._h, _ptr(frames), frames.size(0), frames.size(1), frames.size(2), pitch,
+                                                _ptr(fidx), _ptr(landmarks), _ptr(tmpl), K, _ptr(fl), N, _ptr(f_new),
+                                                _ptr(f), _ptr(valid), self._stream()))
+        return f_new, f, valid
 
     # -- arena / measurement --------------------------------------------------
     def workspace_bytes(self, n, h=112, w=112):

@@ -140,6 +140,53 @@ int ffr_search_topk(ffr_handle* h, const float* query, int Q, const float* galle
 int ffr_topk_merge(ffr_handle* h, const float* score, const int64_t* index, int S, int Q, int k,
                    float* out_score, int64_t* out_index, void* stream);
 
+/* ---- face alignment (landmarks -> similarity transform -> aligned uint8 crop) ---------------------------------------
+ * Replaces the reference's host preprocessing, lfw/gen_lfw112x96.py:6-17 (align) with lfw/matlab_cp2tform.py
+ * (get_similarity_transform_for_cv2) in front of cv2.warpAffine: frames and detector landmarks already on the device
+ * become the crops ffr_embed_u8 reads, without a host round trip.
+ *   fit    landmarks[N][K][2] and tmpl[K][2] are fp32 (x, y) points, 2 <= K <= 16: s = the face's landmarks in its
+ *          frame, r = the template points in the crop.  In fp64, with p = r - mean(r), q = s - mean(s), den = sum |p|^2:
+ *          a = sum(p . q) / den, b = sum(p.x q.y - p.y q.x) / den, A1 = [a -b tx; b a ty], t = mean(s) - L mean(r) -- the
+ *          least squares of the map crop -> frame that findNonreflectiveSimilarity solves (cv2's matrix is its inverse).
+ *          The reflective candidate A2 is the same fit with r.x negated and the first column of the result negated.  The
+ *          landmarks mapped through each candidate's inverse are compared with r; the non-reflective candidate wins when
+ *          the L2 norm of its residual is <= the other's (findSimilarity); a candidate whose linear part is exactly
+ *          singular counts as an infinite norm.
+ *   A      A[N][6] fp64, row-major 2 x 3, maps crop pixel (x, y) to frame coordinates (dst -> src: the inverse of the
+ *          matrix the reference hands to cv2.warpAffine).
+ *   valid  valid[N] uint8.  den == 0, both candidates singular (all landmarks equal) or anything not finite -- where the
+ *          reference raises -- gives valid = 0 and A = 0; nothing faults.
+ *   warp   frames[F][H][W][3] uint8 HWC with pitch_bytes between rows (frame f starts at f * pitch_bytes * H);
+ *          frame_index[N] int32 names each face's frame (faces may share one).  crop[N][out_h][out_w][3] uint8,
+ *          contiguous: the input of ffr_embed_u8 at 112 x 112.  Output pixel (x, y) samples
+ *            sx = (A0 x + A1 y) + A2, sy = (A3 x + A4 y) + A5   in fp64, in this order, without fused multiply-add,
+ *                                                               clamped to +-2^20;
+ *            fx = (int)floor(sx * 32 + 0.5), ix = fx >> 5, ax = fx & 31 (the same for y): a 1/32-pixel grid;
+ *            v  = (sum over the 4 taps of w p + 512) >> 10 per channel, w = (32-ax)(32-ay), ax(32-ay), (32-ax)ay, ax ay;
+ *          a tap outside [0,W) x [0,H) contributes 0, decided per tap (constant-0 border).  An exact integer rule in
+ *          cv2's manner, bit-reproducible; equality with cv2.warpAffine is NOT claimed.  A face with valid == 0 or a
+ *          frame_index outside [0,F) gets an all-zero crop.
+ *   errors FFR_ERR_ARG: a null pointer (where not allowed below), N <= 0, K outside 2..16, out_h or out_w outside 1..256,
+ *          out_w % 4 != 0, pitch_bytes < 3 W, pitch_bytes * H >= 2^31 (64-bit frame bases, 32-bit offsets inside a
+ *          frame), F, H or W < 1, a crop that is not 4-byte aligned.
+ * All pointers are device pointers; nothing synchronises with the host.  ffr_align_transforms and ffr_align_warp need
+ * no weights.  Launches are profiled under FFR_KC_LAYOUT.                                                            */
+int ffr_align_transforms(ffr_handle* h, const float* landmarks, const float* tmpl, int N, int K,
+                         double* A, uint8_t* valid, void* stream);
+/* valid may be NULL: every face with a frame_index in range is warped.                                               */
+int ffr_align_warp(ffr_handle* h, const uint8_t* frames, int F, int H, int W, long long pitch_bytes,
+                   const int32_t* frame_index, const double* A, const uint8_t* valid, int N,
+                   int out_h, int out_w, uint8_t* crop, void* stream);
+/* transforms -> warp to 112 x 112 into the handle's alignment scratch -> the pipeline of ffr_embed_u8, all on `stream`:
+ * f_new[N][512], f[N][512] (f may be NULL), bit-identical to ffr_embed_u8 fed with ffr_align_warp's crop (an invalid
+ * face embeds its zero crop); flip[N] as in ffr_embed_u8 (may be NULL); valid[N] receives the flags, 0 also for a
+ * frame_index outside [0,F) (may be NULL).
+ * The scratch (transforms, flags, crops) grows on demand -- hipMalloc on the first call at a larger N, which bumps
+ * ffr_generation -- and is reused afterwards, so a call can be captured into a hipGraph once it has run at that shape. */
+int ffr_embed_aligned(ffr_handle* h, const uint8_t* frames, int F, int H, int W, long long pitch_bytes,
+                      const int32_t* frame_index, const float* landmarks, const float* tmpl, int K,
+                      const uint8_t* flip, int N, float* f_new, float* f, uint8_t* valid, void* stream);
+
 /* Fold protocol of lfw/lfw_eval.py:110-118,137-162,255-270 on the device: thresholds
  * np.arange(-1, 1, 0.005), same iff score > thr, n_folds contiguous test folds (KFold, no shuffle),
  * best threshold = LAST one reaching the best train accuracy, accuracy on the held-out fold.
