@@ -157,7 +157,7 @@ int run_gemm(ffr_handle* h, IgemmArgs& a, const ConvCall& c, double flops, doubl
         igemm_tile_shape(force, &fbm, &fbn);
         if (a.cout_pad % fbn) return fail(h, FFR_ERR_ARG, "conv: forced tile %d (%d x %d) does not divide cout_pad %d", force, fbm, fbn, a.cout_pad);
     }
-    plan_igemm(a.M, a.cout_pad, a.nkt, a.nbatch, force, h->opt.sk_minunits, &tile, &nblocks, &a.granule);
+    plan_igemm(a.M, a.cout_pad, a.nkt, a.nbatch, force, h->opt.sk_minunits, &tile, &nblocks, &a.granule, a.w3 != nullptr);
     int bm, bn;
     igemm_tile_shape(tile, &bm, &bn);
     a.mtiles = (a.M + bm - 1) / bm;
@@ -340,6 +340,9 @@ int run_conv(ffr_handle* h, const ConvW& L, const ConvCall& c, hipStream_t st) {
     a.M = (int)M; a.KK = L.R * L.S * L.cin_pad; a.nkt = a.KK / 32; a.nbatch = 1;
     a.cout_pad = L.cout_pad; a.cout_store = c.cout_store; a.out_pitch = c.out_pitch; a.out_coff = c.out_coff;
     a.res_pitch = c.res_pitch; a.border_bias = L.border; a.flags = c.flags;
+    // split-operand form: the layer's weights were split at load time (or by ffr_op_conv's flag) and option igemm_split is on.
+    // flops_executed of the launch stays the fp32-equivalent count (run_gemm)
+    if (L.w3 && h->opt.igemm_split) { a.w3 = L.w3; a.w3_pstride = (long long)L.cout_pad * a.KK; }
     return run_gemm(h, a, c, flops, bytes, st);
 }
 

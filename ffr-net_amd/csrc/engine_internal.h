@@ -36,6 +36,8 @@ struct ConvW {
                              // order at [1..3] ([0] = wuc); derived on the device from `w` the first time a launch of this layer is eligible
                              // (pack.cpp, ensure_mixed_weights), null before
     bool wum_gave_up = false;   // the device could not hold this layer's extra sets: it stays on padded F(4x4) tiles (never retried)
+    unsigned short* w3 = nullptr;   // `w` as three bf16 planes [3][cout_pad][KK] for k_igemm's split-operand form (layers that always run
+                             // direct, and the FC; split from the double-precision fold at load time), or null: the fp32 form
     float* wuc = nullptr;    // the same in the K-chunk order k_wino_fused streams ([cout_pad/64][cin_pad/8][36][128][4]) or null
     // per-layer arithmetic plan (ffr_layer_set_arith / ffr_calibrate): a layer with wu pinned to direct runs exactly
     // what it runs under option wino = 0.  ffr_load_* reset it (pack_conv).
@@ -65,6 +67,7 @@ struct Options {
     int sk_minunits = 18;         // smallest number of K-tiles a stream-K block may own
     int wf_mixed = 1;             // 1: 14x14 maps are tiled 4+4+3+3 (k_wino_fused_mixed) when the launch gives every CU two blocks or more
     int channel_rows = 0;         // k_channel_path: blocks per image (1, 2, 4); 0 = from the batch and the CU count (round 5)
+    int igemm_split = 1;          // 1: direct convolutions whose weights were split at load time run k_igemm's split-operand form (bf16 matrix cores)
     int combine_v = 1;            // 1: a bottleneck's combine also writes V for the next conv1 when that runs k_wino_fused from V
     int wf_trace = 0, igemm_trace = 0;   // -DFFR_TRACE builds only: per-launch phase stamps on stderr (synchronises)
     // Retired in round 6, their A/B settled (EXPERIMENTS.md): wino_112, wf_halfblocks, wf_mapv, wf_mapx, wf_maph, wm_xcdpairs,
@@ -93,7 +96,8 @@ struct ffr_handle {
     size_t enc_weight_bytes = 0, rec_weight_bytes = 0;      // device bytes of the packed weights (ffr_memory_stats)
     size_t mixed_weight_bytes = 0;                          // of them: the lazily derived weight sets of the exact 14x14 tiling
     double enc_load_s = 0.0, rec_load_s = 0.0, mixed_pack_s = 0.0;   // wall seconds of the last ffr_load_* / of all lazy packs
-    bool mixed_gave_up_logged = false;
+    size_t split_weight_bytes = 0;                          // of enc_weight_bytes: the bf16 planes of the split-operand form
+    bool mixed_gave_up_logged = false, split_gave_up_logged = false;
     int mixed_ready_n = 0, mixed_ready_h = 0, mixed_ready_w = 0;     // prepare_mixed_weights ran for batches up to n of h x w (a shortcut only:
                                                                      // readiness itself is per layer, ConvW::wum / wum_gave_up)
     float *stem_w = nullptr, *stem_b = nullptr, *stem_s = nullptr;
@@ -253,7 +257,8 @@ inline bool layer_wino(const ffr_handle* h, const ConvW& L) { return h->opt.wino
 ConvForce wino_fused_form(const ffr_handle* h, int cin_pad, int cout_pad, long long T, double x_bytes, ConvForce ask);
 bool wino_mixed_eligible(const ffr_handle* h, const ConvW& L, int N, int H, int W, int in_pitch, size_t wino_cap, ConvForce force);
 ConvPlan plan_conv(const ffr_handle* h, const ConvW& L, const ConvCall& c);
-void plan_igemm(long long M, int cout_pad, int nkt, int nbatch, int force_tile, int min_units, int* tile, int* nblocks, int* granule);
+void plan_igemm(long long M, int cout_pad, int nkt, int nbatch, int force_tile, int min_units, int* tile, int* nblocks, int* granule,
+                bool split = false);
 // conv.cpp
 int run_gemm(ffr_handle* h, IgemmArgs& a, const ConvCall& c, double flops, double bytes, hipStream_t st, double fuse = -1.0);
 int run_conv(ffr_handle* h, const ConvW& L, const ConvCall& c, hipStream_t st);

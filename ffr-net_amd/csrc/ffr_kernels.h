@@ -35,12 +35,18 @@ struct IgemmArgs {
     int cout_pad, cout_store, out_pitch, out_coff, res_pitch;
     int border_bias, flags;      // flags bit0: sigmoid at the end
     int mtiles, ntiles;
+    // split-operand form (igemm.hip): three bf16 planes of w, plane p at w3 + p * w3_pstride, each [cout_pad][KK];
+    // non-null selects the form (nbatch must be 1)
+    const unsigned short* w3;
+    long long w3_pstride;
 };
 enum { IGEMM_TILE_128x128 = 1, IGEMM_TILE_128x64 = 2, IGEMM_TILE_64x64 = 3, IGEMM_TILE_256x64 = 4,
        IGEMM_NTILES = 4 };
 void igemm_tile_shape(int tile, int* bm, int* bn);
 hipError_t igemm_init();   // raises the dynamic-LDS limit of the instantiations
-int igemm_resident_blocks(int tile);
+int igemm_resident_blocks(int tile, bool split = false);
+// planes[p][i], p = 0..2: the bf16 pieces of w[i] (round to nearest even; w[i] = their sum up to 2^-26 |w[i]|)
+hipError_t launch_split_weights(const float* w, unsigned short* planes, size_t n, hipStream_t stream);
 // persistent stream-K launch over `nblocks` blocks; tiles that are cut are finished inside
 // the launch by the last contributor (a.partial / a.tickets)
 hipError_t launch_igemm(const IgemmArgs& a, int tile, int nblocks, hipStream_t stream);

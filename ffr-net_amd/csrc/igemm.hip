@@ -17,25 +17,46 @@
 //   operand row feeds 4 MFMAs (lanes 0-31 hold k..k+3, lanes 32-63 hold k+4..k+7).
 // * 2-stage LDS ring, one barrier per K-tile: the DMA of tile t+1 is in flight while
 //   tile t is multiplied.
+// * Split-operand form (template parameter SPLIT, launches with IgemmArgs::w3): the same fp32 product
+//   as six exact bf16 x bf16 products per term on v_mfma_f32_32x32x16_bf16 -- see the comment at k_igemm.
 // * Epilogue in registers: bias (optionally one of 9 border classes, for the BN that
 //   precedes a zero-padded conv), PReLU, residual add, sigmoid; NHWC store with pitch /
 //   channel offset so concatenations are just addressing.
 #include "ffr_kernels.h"
 
+#include <utility>
+
 namespace ffr {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 #define LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
 #define GLB_PTR(p) ((const __attribute__((address_space(1))) void*)(p))
 
-template <int BM, int BN, int WARPS_M, int WARPS_N, int PAD_MODE>
+// two bf16 (round to nearest even) of two floats in one register: lo in bits 0-15
+__device__ __forceinline__ unsigned cvt_pk_bf16(float lo, float hi) {
+    unsigned r;
+    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
+    return r;
+}
+
+// SPLIT (split-operand form): the same fp32 product on v_mfma_f32_32x32x16_bf16.  Every fp32 value is the sum
+// of three bf16 pieces (a1 = bf16(a), a2 = bf16(a - a1), a3 = bf16(a - a1 - a2)); the six products ai*bj with i + j <= 4, each
+// exact in fp32, are accumulated in fp32 by the matrix core.  A stays fp32 in LDS and is split in registers after the
+// fragment read; B arrives as three bf16 planes a.w3 (split once from the weights), each [cout_pad][KK] bf16: per K-tile and
+// row 3 x 64 B instead of 128 B, staged by the same LDS-DMA into three [BN][32] bf16 images whose 16-B chunk index is
+// XOR-swizzled with (row >> 2) & 3.  Units, fix-up, epilogue and the C layout are those of the fp32 form (both MFMA shapes
+// have the same 32x32 accumulator layout).
+template <int BM, int BN, int WARPS_M, int WARPS_N, int PAD_MODE, bool SPLIT = false>
 __global__ __launch_bounds__(256) void k_igemm(const IgemmArgs a) {
     constexpr int WM = BM / WARPS_M, WN = BN / WARPS_N;
     constexpr int TM = WM / 32, TN = WN / 32;
-    constexpr int A_PT = BM / 32, B_PT = BN / 32;      // staging rows per thread
-    constexpr int STAGE_FLOATS = (BM + BN) * 32;
+    constexpr int A_PT = BM / 32;                      // A staging rows per thread = A pieces per K-tile
+    constexpr int B_PT = SPLIT ? 3 * (BN / 64) : BN / 32;      // B pieces per K-tile (split: 64 rows of one plane per piece)
+    constexpr int STAGE_FLOATS = SPLIT ? BM * 32 + BN * 48 : (BM + BN) * 32;
     static_assert(WARPS_M * WARPS_N == 4, "4 waves");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int MAIN_FLOATS = (2 * STAGE_FLOATS > BM * (BN + 4)) ? 2 * STAGE_FLOATS : BM * (BN + 4);
@@ -129,10 +150,17 @@ __global__ __launch_bounds__(256) void k_igemm(const IgemmArgs a) {
     // current source pointer of every staged row (advances 32 floats per K-tile; the
     // A pointers are re-derived when the tap changes)
     const float* a_ptr[A_PT];
-    const float* b_ptr[B_PT];
+    const float* b_ptr[B_PT];        // split form: pointers into the bf16 planes
 #pragma unroll
-    for (int i = 0; i < B_PT; ++i)
-        b_ptr[i] = wb + (size_t)(n0 + srow + 32 * i) * a.KK + kbase0 + lch * 4;
+    for (int i = 0; i < B_PT; ++i) {
+        if constexpr (SPLIT) {
+            const int brow = tid >> 2, bch = (tid & 3) ^ ((brow >> 2) & 3);
+            const int plane = i / (BN / 64), piece = i % (BN / 64);
+            b_ptr[i] = reinterpret_cast<const float*>(a.w3 + (size_t)plane * a.w3_pstride + (size_t)(n0 + brow + 64 * piece) * a.KK + kbase0 + bch * 8);
+        } else {
+            b_ptr[i] = wb + (size_t)(n0 + srow + 32 * i) * a.KK + kbase0 + lch * 4;
+        }
+    }
 
     auto set_tap = [&]() {
 #pragma unroll
@@ -159,8 +187,13 @@ __global__ __launch_bounds__(256) void k_igemm(const IgemmArgs a) {
             a_ptr[d] += 32;
         } else {
             const int i = d - A_PT;
-            __builtin_amdgcn_global_load_lds(GLB_PTR(b_ptr[i]), LDS_PTR(sA + (BM + 32 * i + 8 * wave) * 32), 16, 0, 0);
-            b_ptr[i] += 32;
+            if constexpr (SPLIT) {      // 16 rows x 64 B per wave; 32 bf16 = 16 floats per K-tile
+                __builtin_amdgcn_global_load_lds(GLB_PTR(b_ptr[i]), LDS_PTR(sA + BM * 32 + (i / (BN / 64)) * BN * 16 + (64 * (i % (BN / 64)) + 16 * wave) * 16), 16, 0, 0);
+                b_ptr[i] += 16;
+            } else {
+                __builtin_amdgcn_global_load_lds(GLB_PTR(b_ptr[i]), LDS_PTR(sA + (BM + 32 * i + 8 * wave) * 32), 16, 0, 0);
+                b_ptr[i] += 32;
+            }
         }
     };
     // after all pieces of a K-tile are issued: move to the next tap when the channel run ends
@@ -189,69 +222,181 @@ __global__ __launch_bounds__(256) void k_igemm(const IgemmArgs a) {
     for (int q = 0; q < 4; ++q) pc[q] = ((2 * q + fh) ^ fswz) * 4;
     const int fragA = (wm * WM + frow) * 32, fragB = (BM + wn * WN + frow) * 32;
 
-    constexpr int NQ = TM * TN * 4;          // MFMAs per 8-k chunk
-    constexpr int NR = TM + TN;              // fragment reads per chunk
     constexpr int ND = A_PT + B_PT;          // DMA pieces per K-tile
-    constexpr int NDH = (ND + 1) / 2;        // ... issued in the gaps of chunks 0 and 1
-    static_assert(NR + NDH <= NQ, "fillers must fit the MFMA gaps of a chunk");
-    f32x4 af[2][TM], bf[2][TN];
 #define FFR_PIN __builtin_amdgcn_sched_barrier(0)
-
-    // fragment read r of a chunk: rows of A then rows of B, 16 B per lane (4 k values)
-    auto read_piece = [&](int slot, const float* stage, int pcv, int r) {
-        if (r < TM) af[slot][r] = *reinterpret_cast<const f32x4*>(stage + fragA + r * 32 * 32 + pcv);
-        else bf[slot][r - TM] = *reinterpret_cast<const f32x4*>(stage + fragB + (r - TM) * 32 * 32 + pcv);
-    };
-
-    // One K-tile.  Every MFMA gap (64 cycles on the SIMD's matrix pipe) carries at most ONE
-    // filler -- a fragment ds_read_b128 for the next chunk or one LDS-DMA piece of the next
-    // K-tile -- and the order is pinned (sched_barrier): an LDS-DMA costs its wave ~60 issue
-    // cycles, so 4-8 of them back to back starve the matrix pipe (measured: -10 % at 8 blocks/CU,
-    // more in the 1-block/CU tail).  The barrier that publishes tile t+1 sits in front of the
-    // LAST chunk of tile t, so the first fragments of t+1 are read under that chunk's MFMAs.
-    auto tile_body = [&]<bool LAST>(int cur) {
-        const float* stage = smem + cur * STAGE_FLOATS;
-        const float* stage_n = smem + (cur ^ 1) * STAGE_FLOATS;
+    if constexpr (SPLIT) {
+        // K-tile = two K = 16 steps.  Per step and 32x32 tile six bf16 MFMAs (small products first); the fillers of a step, in
+        // this order, spread evenly over its MFMA gaps and pinned: the fragment reads of the NEXT step (A: two fp32
+        // ds_read_b128 per 32 rows, B: one per plane and 32 columns), in step 1 the LDS-DMA pieces of the K-tile after the
+        // next, then the split of the next step's A values in registers (per pair of values two units: 5 and 6 vector
+        // instructions).  A K-tile lasts ~1.5 k cycles here, a quarter of the fp32 form's: a DMA issued in step 0 for the
+        // barrier in front of step 1 (the fp32 form's distance) would have ~0.3 us to arrive.  The stage of tile t is free
+        // once that barrier has passed (step 1 reads tile t + 1), so tile t + 2 is requested right behind it and has a whole
+        // K-tile of time.
+        // Vector instructions do not overlap with MFMAs on this chip (profiles/r05_probe_mfma_valu_coissue.txt): the split
+        // is paid in full, which is why a wave takes ALL columns of its rows (WARPS_N = 1 where BN allows): no A value is
+        // split twice.
+        constexpr int NPROD = 6;
+        constexpr int PA[NPROD] = {2, 0, 1, 1, 0, 0}, PB[NPROD] = {0, 2, 1, 0, 1, 0};
+        constexpr int NQ = TM * TN * NPROD;      // MFMAs per step
+        constexpr int NR = 2 * TM + 3 * TN;      // fragment reads per step
+        constexpr int NU = TM * 8;               // split units per step
+        f32x4 araw[TM][2];
+        u32x4 pa[2][TM][3];
+        f32x4 pb[2][TN][3];
+        const int bswz = (lane >> 2) & 3;
+        int pcA[2][2], pcB[2];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            if (q == 3 && !LAST) {
+        for (int st = 0; st < 2; ++st) {
+            pcA[st][0] = ((4 * st + 2 * fh) ^ fswz) * 4;
+            pcA[st][1] = ((4 * st + 2 * fh + 1) ^ fswz) * 4;
+            pcB[st] = ((2 * st + fh) ^ bswz) * 4;
+        }
+        const int fragB3 = BM * 32 + (wn * WN + frow) * 16;
+        auto read_piece = [&](int slot, const float* stage, int st, int r) __attribute__((always_inline)) {
+            if (r < 2 * TM) araw[r / 2][r % 2] = *reinterpret_cast<const f32x4*>(stage + fragA + (r / 2) * 32 * 32 + pcA[st][r % 2]);
+            else {
+                const int j = (r - 2 * TM) / 3, p = (r - 2 * TM) % 3;
+                pb[slot][j][p] = *reinterpret_cast<const f32x4*>(stage + fragB3 + p * BN * 16 + j * 32 * 16 + pcB[st]);
+            }
+        };
+        // unit u of the split of araw into pa[slot]: row block u / 8, pair (u / 2) % 4, first / second half
+        auto split_unit = [&](int slot, int u) __attribute__((always_inline)) {
+            const int i = u / 8, e2 = (u / 2) % 4, v = e2 / 2, e = 2 * (e2 % 2);
+            float lo = araw[i][v][e], hi = araw[i][v][e + 1];
+            const unsigned w = cvt_pk_bf16(lo, hi);
+            pa[slot][i][u % 2][e2] = w;
+            lo -= __builtin_bit_cast(float, w << 16);          // exact: the residual of a rounding to 8 bits fits fp32
+            hi -= __builtin_bit_cast(float, w & 0xffff0000u);
+            if (u % 2) pa[slot][i][2][e2] = cvt_pk_bf16(lo, hi);
+            else { araw[i][v][e] = lo; araw[i][v][e + 1] = hi; }
+        };
+        // Step ST of a K-tile is spelled out at compile time, gap by gap (a `#pragma unroll` nest over steps, gaps and fillers
+        // exceeds the unroller's size limit for the 128x128 tile before it folds, and the fragment arrays then live in scratch).
+        // filler FI of the step: a fragment read, an LDS-DMA piece or a split unit
+        auto filler = [&]<int ST, bool LAST, int FI>(int cur, bool more) __attribute__((always_inline)) {
+            constexpr int NDS = (ST == 1 && !LAST) ? ND : 0;
+            if constexpr (FI < NR) read_piece(ST ^ 1, smem + (ST == 0 ? cur : cur ^ 1) * STAGE_FLOATS, ST ^ 1, FI);
+            else if constexpr (FI < NR + NDS) { if (more) dma_piece(cur, FI - NR); }
+            else split_unit(ST ^ 1, FI - NR - NDS);
+        };
+        // gap G: one MFMA and the fillers f with f * NQ / F == G
+        auto gap = [&]<int ST, bool LAST, int G>(int cur, bool more) __attribute__((always_inline)) {
+            constexpr int NDS = (ST == 1 && !LAST) ? ND : 0;
+            constexpr int F = (ST == 0 || !LAST) ? NR + NDS + NU : 0;       // LAST: step 1 has no next step to prepare
+            constexpr int q = G / (TM * TN), i = (G / TN) % TM, j = G % TN;
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, pa[ST][i][PA[q]]),
+                                                               __builtin_bit_cast(bf16x8, pb[ST][j][PB[q]]), acc[i][j], 0, 0, 0);
+            constexpr int F0 = (G * F + NQ - 1) / NQ, F1 = ((G + 1) * F + NQ - 1) / NQ;
+            [&]<int... K>(std::integer_sequence<int, K...>) __attribute__((always_inline)) {
+                (filler.template operator()<ST, LAST, F0 + K>(cur, more), ...);
+            }(std::make_integer_sequence<int, F1 - F0>{});
+            FFR_PIN;
+        };
+        auto step = [&]<int ST, bool LAST, int... G>(int cur, bool more, std::integer_sequence<int, G...>) __attribute__((always_inline)) {
+            if (ST == 1 && !LAST) {
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 __syncthreads();
                 FFR_PIN;
             }
+            (gap.template operator()<ST, LAST, G>(cur, more), ...);
+            if (ST == 1 && !LAST && more) { advance_tile(); FFR_PIN; }
+        };
+        // tile t in stage cur = t & 1; more: tile t + 2 exists
+        auto tile_body = [&]<bool LAST>(int cur, bool more) __attribute__((always_inline)) {
+            step.template operator()<0, LAST>(cur, more, std::make_integer_sequence<int, NQ>{});
+            step.template operator()<1, LAST>(cur, more, std::make_integer_sequence<int, NQ>{});
+        };
+        if (FFR_TRACE_ON(a.trace)) { const unsigned long long t = __builtin_amdgcn_s_memtime(); tr_acc[0] += t - tr_t; tr_t = t; }
+        // prologue: tiles 0 and 1 -> stages 0 and 1; wait for tile 0 only; its first fragments -> slot 0
 #pragma unroll
-            for (int g = 0; g < NQ; ++g) {
-                const int e = g / (TM * TN), i = (g / TN) % TM, j = g % TN;
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[q & 1][i][e], bf[q & 1][j][e], acc[i][j], 0, 0, 0);
-                if (g < NR) {
-                    if (q < 3) read_piece((q + 1) & 1, stage, pc[q + 1], g);
-                    else if (!LAST) read_piece(0, stage_n, pc[0], g);
-                } else if (!LAST && q < 2 && (g - NR) < NDH && q * NDH + (g - NR) < ND) {
-                    dma_piece(cur ^ 1, q * NDH + (g - NR));
-                }
-                FFR_PIN;
-            }
-            if (q == 1 && !LAST) { advance_tile(); FFR_PIN; }
+        for (int d = 0; d < ND; ++d) dma_piece(0, d);
+        advance_tile();
+        if (nk > 1) {
+#pragma unroll
+            for (int d = 0; d < ND; ++d) dma_piece(1, d);
+            advance_tile();
+            static_assert(ND < 16, "vmcnt immediate");
+            __builtin_amdgcn_s_waitcnt(0x0F70 | ND);        // vmcnt(ND): the ND pieces of tile 1 may still be in flight
+        } else {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
-    };
-
-    if (FFR_TRACE_ON(a.trace)) { const unsigned long long t = __builtin_amdgcn_s_memtime(); tr_acc[0] += t - tr_t; tr_t = t; }
-    // prologue: tile 0 -> stage 0, its first fragments -> slot 0
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 #pragma unroll
-    for (int d = 0; d < ND; ++d) dma_piece(0, d);
-    advance_tile();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
+        for (int r = 0; r < NR; ++r) read_piece(0, smem, 0, r);
 #pragma unroll
-    for (int r = 0; r < NR; ++r) read_piece(0, smem, pc[0], r);
-    FFR_PIN;
-    if (FFR_TRACE_ON(a.trace)) { const unsigned long long t = __builtin_amdgcn_s_memtime(); tr_acc[1] += t - tr_t; tr_t = t; }
-    __builtin_amdgcn_s_setprio(0);
+        for (int u = 0; u < NU; ++u) split_unit(0, u);
+        FFR_PIN;
+        if (FFR_TRACE_ON(a.trace)) { const unsigned long long t = __builtin_amdgcn_s_memtime(); tr_acc[1] += t - tr_t; tr_t = t; }
+        __builtin_amdgcn_s_setprio(0);
 #pragma unroll 1
-    for (int it = 0; it + 1 < nk; ++it) tile_body.template operator()<false>(it & 1);
-    tile_body.template operator()<true>((nk - 1) & 1);
-    __builtin_amdgcn_s_setprio(2);
-    if (FFR_TRACE_ON(a.trace)) { const unsigned long long t = __builtin_amdgcn_s_memtime(); tr_acc[2] += t - tr_t; tr_t = t; }
+        for (int it = 0; it + 1 < nk; ++it) tile_body.template operator()<false>(it & 1, it + 2 < nk);
+        tile_body.template operator()<true>((nk - 1) & 1, false);
+        __builtin_amdgcn_s_setprio(2);
+        if (FFR_TRACE_ON(a.trace)) { const unsigned long long t = __builtin_amdgcn_s_memtime(); tr_acc[2] += t - tr_t; tr_t = t; }
+    } else {
+        constexpr int NQ = TM * TN * 4;          // MFMAs per 8-k chunk
+        constexpr int NR = TM + TN;              // fragment reads per chunk
+        constexpr int NDH = (ND + 1) / 2;        // ... issued in the gaps of chunks 0 and 1
+        static_assert(NR + NDH <= NQ, "fillers must fit the MFMA gaps of a chunk");
+        f32x4 af[2][TM], bf[2][TN];
+
+        // fragment read r of a chunk: rows of A then rows of B, 16 B per lane (4 k values)
+        auto read_piece = [&](int slot, const float* stage, int pcv, int r) {
+            if (r < TM) af[slot][r] = *reinterpret_cast<const f32x4*>(stage + fragA + r * 32 * 32 + pcv);
+            else bf[slot][r - TM] = *reinterpret_cast<const f32x4*>(stage + fragB + (r - TM) * 32 * 32 + pcv);
+        };
+
+        // One K-tile.  Every MFMA gap (64 cycles on the SIMD's matrix pipe) carries at most ONE
+        // filler -- a fragment ds_read_b128 for the next chunk or one LDS-DMA piece of the next
+        // K-tile -- and the order is pinned (sched_barrier): an LDS-DMA costs its wave ~60 issue
+        // cycles, so 4-8 of them back to back starve the matrix pipe (measured: -10 % at 8 blocks/CU,
+        // more in the 1-block/CU tail).  The barrier that publishes tile t+1 sits in front of the
+        // LAST chunk of tile t, so the first fragments of t+1 are read under that chunk's MFMAs.
+        auto tile_body = [&]<bool LAST>(int cur) {
+            const float* stage = smem + cur * STAGE_FLOATS;
+            const float* stage_n = smem + (cur ^ 1) * STAGE_FLOATS;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                if (q == 3 && !LAST) {
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    __syncthreads();
+                    FFR_PIN;
+                }
+#pragma unroll
+                for (int g = 0; g < NQ; ++g) {
+                    const int e = g / (TM * TN), i = (g / TN) % TM, j = g % TN;
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[q & 1][i][e], bf[q & 1][j][e], acc[i][j], 0, 0, 0);
+                    if (g < NR) {
+                        if (q < 3) read_piece((q + 1) & 1, stage, pc[q + 1], g);
+                        else if (!LAST) read_piece(0, stage_n, pc[0], g);
+                    } else if (!LAST && q < 2 && (g - NR) < NDH && q * NDH + (g - NR) < ND) {
+                        dma_piece(cur ^ 1, q * NDH + (g - NR));
+                    }
+                    FFR_PIN;
+                }
+                if (q == 1 && !LAST) { advance_tile(); FFR_PIN; }
+            }
+        };
+
+        if (FFR_TRACE_ON(a.trace)) { const unsigned long long t = __builtin_amdgcn_s_memtime(); tr_acc[0] += t - tr_t; tr_t = t; }
+        // prologue: tile 0 -> stage 0, its first fragments -> slot 0
+#pragma unroll
+        for (int d = 0; d < ND; ++d) dma_piece(0, d);
+        advance_tile();
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < NR; ++r) read_piece(0, smem, pc[0], r);
+        FFR_PIN;
+        if (FFR_TRACE_ON(a.trace)) { const unsigned long long t = __builtin_amdgcn_s_memtime(); tr_acc[1] += t - tr_t; tr_t = t; }
+        __builtin_amdgcn_s_setprio(0);
+#pragma unroll 1
+        for (int it = 0; it + 1 < nk; ++it) tile_body.template operator()<false>(it & 1);
+        tile_body.template operator()<true>((nk - 1) & 1);
+        __builtin_amdgcn_s_setprio(2);
+        if (FFR_TRACE_ON(a.trace)) { const unsigned long long t = __builtin_amdgcn_s_memtime(); tr_acc[2] += t - tr_t; tr_t = t; }
+    }
 #undef FFR_PIN
 
     // ---- epilogue: accumulators -> LDS (C tile, row stride BN+4) -> whole rows, 16 B per lane ----
@@ -433,29 +578,43 @@ void igemm_tile_shape(int tile, int* bm, int* bn) {
     }
 }
 
-static size_t igemm_lds_bytes(int bm, int bn) {
-    size_t stages = (size_t)2 * (bm + bn) * 32, ctile = (size_t)bm * (bn + 4);
+static size_t igemm_lds_bytes(int bm, int bn, bool split) {
+    size_t stages = split ? (size_t)2 * (bm * 32 + bn * 48) : (size_t)2 * (bm + bn) * 32, ctile = (size_t)bm * (bn + 4);
     return (stages > ctile ? stages : ctile) * 4 + (size_t)(bm + 4) * 4 + (size_t)9 * bn * 4;
 }
 
 hipError_t igemm_init() {
     hipError_t e;
-#define FFR_SET_LDS(BM, BN, WMM, WNN)                                                                   \
-    e = hipFuncSetAttribute((const void*)k_igemm<BM, BN, WMM, WNN, 0>,                                  \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)igemm_lds_bytes(BM, BN));  \
-    if (e != hipSuccess) return e;                                                                      \
-    e = hipFuncSetAttribute((const void*)k_igemm<BM, BN, WMM, WNN, 1>,                                  \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)igemm_lds_bytes(BM, BN));  \
+#define FFR_SET_LDS(BM, BN, WMM, WNN, SPLIT)                                                                   \
+    e = hipFuncSetAttribute((const void*)k_igemm<BM, BN, WMM, WNN, 0, SPLIT>,                                  \
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)igemm_lds_bytes(BM, BN, SPLIT));  \
+    if (e != hipSuccess) return e;                                                                             \
+    e = hipFuncSetAttribute((const void*)k_igemm<BM, BN, WMM, WNN, 1, SPLIT>,                                  \
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)igemm_lds_bytes(BM, BN, SPLIT));  \
     if (e != hipSuccess) return e;
-    FFR_SET_LDS(128, 128, 2, 2)
-    FFR_SET_LDS(128, 64, 2, 2)
-    FFR_SET_LDS(64, 64, 2, 2)
-    FFR_SET_LDS(256, 64, 4, 1)
+    FFR_SET_LDS(128, 128, 2, 2, false)
+    FFR_SET_LDS(128, 64, 2, 2, false)
+    FFR_SET_LDS(64, 64, 2, 2, false)
+    FFR_SET_LDS(256, 64, 4, 1, false)
+    // split form: a wave owns all columns of its rows where the tile allows it (no A value is split twice)
+    FFR_SET_LDS(128, 128, 4, 1, true)
+    FFR_SET_LDS(128, 64, 4, 1, true)
+    FFR_SET_LDS(64, 64, 2, 2, true)
+    FFR_SET_LDS(256, 64, 4, 1, true)
 #undef FFR_SET_LDS
     return e;
 }
 
-int igemm_resident_blocks(int tile) {   // blocks of 256 threads one CU holds (LDS-limited)
+int igemm_resident_blocks(int tile, bool split) {   // blocks of 256 threads one CU holds (LDS-limited)
+    if (split) {     // a stage is (BM * 4 + BN * 6) * 32 B: 87 / 60 / 43 / 96 KB per block with the tables
+        switch (tile) {
+            case IGEMM_TILE_128x128: return 1;
+            case IGEMM_TILE_128x64: return 2;
+            case IGEMM_TILE_64x64: return 3;
+            case IGEMM_TILE_256x64: return 1;
+            default: return 0;
+        }
+    }
     switch (tile) {
         case IGEMM_TILE_128x128: return 2;
         case IGEMM_TILE_128x64: return 3;
@@ -469,18 +628,49 @@ hipError_t launch_igemm(const IgemmArgs& a, int tile, int nblocks, hipStream_t s
     int bm, bn;
     igemm_tile_shape(tile, &bm, &bn);
     if (!bm || nblocks <= 0) return hipErrorInvalidValue;
+    const bool split = a.w3 != nullptr;
+    if (split && a.nbatch != 1) return hipErrorInvalidValue;      // the planes have no batch stride
     dim3 grid((unsigned)nblocks, 1, 1);
-    const size_t lds = igemm_lds_bytes(bm, bn);
-#define FFR_LAUNCH(BM, BN, WMM, WNN)                                                                      \
-    if (a.pad_mode == 1) hipLaunchKernelGGL((k_igemm<BM, BN, WMM, WNN, 1>), grid, dim3(256), lds, stream, a); \
-    else hipLaunchKernelGGL((k_igemm<BM, BN, WMM, WNN, 0>), grid, dim3(256), lds, stream, a);
-    switch (tile) {
-        case IGEMM_TILE_128x128: FFR_LAUNCH(128, 128, 2, 2) break;
-        case IGEMM_TILE_128x64: FFR_LAUNCH(128, 64, 2, 2) break;
-        case IGEMM_TILE_64x64: FFR_LAUNCH(64, 64, 2, 2) break;
-        case IGEMM_TILE_256x64: FFR_LAUNCH(256, 64, 4, 1) break;
+    const size_t lds = igemm_lds_bytes(bm, bn, split);
+#define FFR_LAUNCH(BM, BN, WMM, WNN, SPLIT)                                                                          \
+    if (a.pad_mode == 1) hipLaunchKernelGGL((k_igemm<BM, BN, WMM, WNN, 1, SPLIT>), grid, dim3(256), lds, stream, a); \
+    else hipLaunchKernelGGL((k_igemm<BM, BN, WMM, WNN, 0, SPLIT>), grid, dim3(256), lds, stream, a);
+    if (split) {
+        switch (tile) {
+            case IGEMM_TILE_128x128: FFR_LAUNCH(128, 128, 4, 1, true) break;
+            case IGEMM_TILE_128x64: FFR_LAUNCH(128, 64, 4, 1, true) break;
+            case IGEMM_TILE_64x64: FFR_LAUNCH(64, 64, 2, 2, true) break;
+            case IGEMM_TILE_256x64: FFR_LAUNCH(256, 64, 4, 1, true) break;
+        }
+    } else {
+        switch (tile) {
+            case IGEMM_TILE_128x128: FFR_LAUNCH(128, 128, 2, 2, false) break;
+            case IGEMM_TILE_128x64: FFR_LAUNCH(128, 64, 2, 2, false) break;
+            case IGEMM_TILE_64x64: FFR_LAUNCH(64, 64, 2, 2, false) break;
+            case IGEMM_TILE_256x64: FFR_LAUNCH(256, 64, 4, 1, false) break;
+        }
     }
 #undef FFR_LAUNCH
+    return hipGetLastError();
+}
+
+// planes[p][i] = piece p of w[i] (bf16, round to nearest even), p = 0..2: the device-side split of raw fp32 weights
+// (ffr_op_conv's test flag; the loaders split on the host from the double-precision fold)
+__global__ void k_split_weights(const float* __restrict__ w, unsigned short* __restrict__ planes, size_t n) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        float r = w[i];
+#pragma unroll
+        for (int p = 0; p < 3; ++p) {
+            const unsigned short h = (unsigned short)(cvt_pk_bf16(r, 0.f) & 0xffffu);
+            planes[(size_t)p * n + i] = h;
+            r -= __builtin_bit_cast(float, (unsigned)h << 16);
+        }
+    }
+}
+
+hipError_t launch_split_weights(const float* w, unsigned short* planes, size_t n, hipStream_t stream) {
+    const size_t blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(k_split_weights, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, stream, w, planes, n);
     return hipGetLastError();
 }
 

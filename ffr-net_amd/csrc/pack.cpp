@@ -37,6 +37,63 @@ int upload(ffr_handle* h, std::vector<void*>& owner, const std::vector<float>& v
     return FFR_OK;
 }
 
+// bf16 (round to nearest even) of a double, as the value it represents; exact in float
+static double round_bf16(double d) {
+    if (d == 0.0 || !std::isfinite(d)) return d;
+    if (std::fabs(d) >= 1.2e-38) {                       // normal range: round the double's significand to 8 bits in place
+        unsigned long long u;
+        memcpy(&u, &d, 8);
+        u += 0x00000fffffffffffull + ((u >> 45) & 1);
+        u &= ~((1ull << 45) - 1);
+        memcpy(&d, &u, 8);
+        return d;
+    }
+    int e;
+    std::frexp(d, &e);                                   // |d| = m * 2^e, m in [0.5, 1)
+    int q = e - 8;                                       // 8 significand bits
+    if (q < -133) q = -133;                              // bf16 subnormals
+    return std::nearbyint(std::ldexp(d, -q)) * std::ldexp(1.0, q);     // default rounding mode: ties to even
+}
+
+// The three bf16 planes [3][n] of the double-precision weights wd[n] for k_igemm's split-operand form: p1 = bf16(w),
+// p2 = bf16(w - p1), p3 = bf16(w - p1 - p2) -- together they carry more of the fold than its fp32 rounding did.
+// An optimisation: when the device cannot hold them the layer keeps the fp32 form, logged once, not an error.
+int upload_split(ffr_handle* h, std::vector<void*>& owner, const std::vector<double>& wd, unsigned short** out) {
+    *out = nullptr;
+    const size_t n = wd.size();
+    std::vector<unsigned short> pl(3 * n);
+    for (size_t i = 0; i < n; ++i) {
+        double r = wd[i];
+        for (int p = 0; p < 3; ++p) {
+            const double b = round_bf16(r);
+            const float bf = (float)b;
+            unsigned u;
+            memcpy(&u, &bf, 4);
+            pl[(size_t)p * n + i] = (unsigned short)(u >> 16);
+            r -= b;
+        }
+    }
+    void* p = nullptr;
+    const size_t bytes = pl.size() * sizeof(unsigned short);
+    hipError_t e = hipMalloc(&p, bytes);
+    if (e == hipSuccess) e = hipMemcpy(p, pl.data(), bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        if (p) hipFree(p);
+        (void)hipGetLastError();
+        if (!h->split_gave_up_logged) {
+            h->split_gave_up_logged = true;
+            fprintf(stderr, "ffrnet: no room for the split-operand weight planes (%zu bytes: %s); the layers concerned keep the fp32 kernel\n",
+                    bytes, hipGetErrorString(e));
+        }
+        return FFR_OK;
+    }
+    owner.push_back(p);
+    if (&owner == &h->enc_allocs) { h->enc_weight_bytes += bytes; h->split_weight_bytes += bytes; }
+    if (&owner == &h->rec_allocs) h->rec_weight_bytes += bytes;
+    *out = (unsigned short*)p;
+    return FFR_OK;
+}
+
 // Pack one convolution: W[cout][cin][R][S] -> [cout_pad][(r*S+s)*cin_pad + ci], with an
 // optional per-input-channel affine folded in front (pre-conv BatchNorm: scale into the
 // weights, shift into one bias per zero-padding border class) and an optional
@@ -50,6 +107,10 @@ int pack_conv(ffr_handle* h, std::vector<void*>& owner, const float* W, int cout
     L->border = in_bn ? 1 : 0;
     const int KK = R * S * L->cin_pad;
     std::vector<float> wp((size_t)L->cout_pad * KK, 0.f);
+    const int wino_min_cin = h->opt.wino_mincin;
+    const bool wino = R == 3 && S == 3 && stride == 1 && pad == 1 && L->cin_pad >= wino_min_cin && wino_min_cin > 0;
+    std::vector<double> wd;                      // the fold in double, for the split planes of a layer that always runs direct
+    if (!wino) wd.assign(wp.size(), 0.0);
     const int ncls = L->border ? 9 : 1;
     std::vector<float> bias((size_t)ncls * L->cout_pad, 0.f);
     std::vector<double> tap(R * S);
@@ -63,6 +124,7 @@ int pack_conv(ffr_handle* h, std::vector<void*>& owner, const float* W, int cout
                     const double wv = W[(((size_t)co * cin + ci) * R + r) * S + s];
                     const double si = in_bn ? in_bn->s[ci] : 1.0;
                     wp[(size_t)co * KK + (size_t)(r * S + s) * L->cin_pad + ci] = (float)(wv * si * g);
+                    if (!wino) wd[(size_t)co * KK + (size_t)(r * S + s) * L->cin_pad + ci] = wv * si * g;
                     if (in_bn) tsum += wv * in_bn->t[ci];
                 }
                 tap[r * S + s] = tsum;
@@ -87,13 +149,14 @@ int pack_conv(ffr_handle* h, std::vector<void*>& owner, const float* W, int cout
     }
     RC(upload(h, owner, wp, &L->w));
     RC(upload(h, owner, bias, &L->bias));
+    L->w3 = nullptr;
+    if (!wino) RC(upload_split(h, owner, wd, &L->w3));
     L->wu = nullptr;
     L->wuc = nullptr;
     for (int tau = 0; tau < 4; ++tau) L->wum[tau] = nullptr;
     L->direct = false;          // new weights: the layer's plan returns to Winograd, its calibration is void
     L->sensitivity = -1.0;
-    const int wino_min_cin = h->opt.wino_mincin;
-    if (R == 3 && S == 3 && stride == 1 && pad == 1 && L->cin_pad >= wino_min_cin && wino_min_cin > 0) {
+    if (wino) {
         // U[xi = i*6+j][co][ci] = (G g G^T)[i][j], same BN folds as the direct weights
         static const double G[6][3] = {{0.25, 0, 0}, {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
                                        {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0, 0, 1}};
@@ -246,7 +309,7 @@ int ffr_load_encoder(ffr_handle* h, const ffr_tensor_desc* t, int n) {
     free_list(h->enc_allocs);
     ++h->generation;
     h->enc_loaded = false;
-    h->mixed_ready_n = 0; h->mixed_weight_bytes = 0; h->enc_weight_bytes = 0; h->mixed_pack_s = 0.0;
+    h->mixed_ready_n = 0; h->mixed_weight_bytes = 0; h->enc_weight_bytes = 0; h->mixed_pack_s = 0.0; h->split_weight_bytes = 0;
     const auto load_t0 = std::chrono::steady_clock::now();
     SD sd; sd.h = h;
     for (int i = 0; i < n; ++i) if (t[i].name) sd.m[t[i].name] = &t[i];
@@ -322,18 +385,21 @@ int ffr_load_encoder(ffr_handle* h, const ffr_tensor_desc* t, int n) {
         L = ConvW();
         L.cin = L.cin_pad = 25088; L.cout = L.cout_pad = 512; L.R = L.S = 1; L.stride = 1; L.pad = 0;
         std::vector<float> wp((size_t)512 * 25088), bb(512);
+        std::vector<double> wd(wp.size());
         for (int o = 0; o < 512; ++o) {
             double acc = bias[o];
             for (int c = 0; c < 512; ++c)
                 for (int p = 0; p < 49; ++p) {
                     const double wv = W[(size_t)o * 25088 + c * 49 + p];
                     wp[(size_t)o * 25088 + p * 512 + c] = (float)(wv * b0.s[c] * b4.s[o]);
+                    wd[(size_t)o * 25088 + p * 512 + c] = wv * b0.s[c] * b4.s[o];
                     acc += wv * b0.t[c];
                 }
             bb[o] = (float)(b4.s[o] * acc + b4.t[o]);
         }
         RC(upload(h, own, wp, &L.w));
         RC(upload(h, own, bb, &L.bias));
+        RC(upload_split(h, own, wd, &L.w3));
     }
     h->enc_loaded = true;
     h->enc_load_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - load_t0).count();

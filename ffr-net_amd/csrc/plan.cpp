@@ -122,17 +122,22 @@ ConvPlan plan_conv(const ffr_handle* h, const ConvW& L, const ConvCall& c) {
 //  * large problems (at least a quarter of a tile of K-tiles per persistent block at 128x128):
 //    persistent stream-K over 256 CUs x resident blocks, biggest tile that divides cout (tile
 //    efficiency measured on the MI355X: 128x128 > 128x64 > 64x64, profiles/r01_conv_sweep*);
+//  * split-operand form (split): the same rules with that form's resident blocks (its stages are larger: igemm.hip);
 //  * small problems: 64x64 tiles; whole tiles per block when they fill 160..1024 blocks
 //    (nothing is cut), else stream-K with at least `min_units` K-tiles per block.
-void plan_igemm(long long M, int cout_pad, int nkt, int nbatch, int force_tile, int min_units, int* tile, int* nblocks, int* granule) {
+void plan_igemm(long long M, int cout_pad, int nkt, int nbatch, int force_tile, int min_units, int* tile, int* nblocks, int* granule, bool split) {
     auto ntiles = [&](int t) {
         int bm, bn;
         igemm_tile_shape(t, &bm, &bn);
         return ((M + bm - 1) / bm) * (long long)(cout_pad / bn) * nbatch;
     };
     int best = (cout_pad % 128 == 0) ? IGEMM_TILE_128x128 : IGEMM_TILE_128x64;
+    // split form: one 128x128 block fills a CU's LDS, so nothing runs beside a block's prologue and epilogue; with fewer than 16
+    // K-tiles per tile (the 1x1 shortcuts: 2 / 4 / 8) those outweigh the loop and two 128x64 blocks per CU are faster
+    // (batch 256: 56 / 42 / 43 us against 65 / 49 / 49; the 3x3 stride-2 layers with 18-72 K-tiles: 365 / 345 / 345 against 335 / 326 / 310)
+    if (split && nkt < 16) best = IGEMM_TILE_128x64;
     const long long big_units = ntiles(best) * nkt;
-    const bool large = big_units / (256LL * igemm_resident_blocks(best)) >= (nkt + 3) / 4 && M * nbatch >= 1024;
+    const bool large = big_units / (256LL * igemm_resident_blocks(best, split)) >= (nkt + 3) / 4 && M * nbatch >= 1024;
     if (!large) best = IGEMM_TILE_64x64;
     bool exact = false;
     if (large) {
@@ -140,14 +145,14 @@ void plan_igemm(long long M, int cout_pad, int nkt, int nbatch, int force_tile, 
         for (int t = IGEMM_TILE_128x128; t <= IGEMM_TILE_128x64; ++t) {
             int bm, bn;
             igemm_tile_shape(t, &bm, &bn);
-            if (cout_pad % bn) continue;
-            if (ntiles(t) % (256LL * igemm_resident_blocks(t)) == 0) { best = t; exact = true; break; }
+            if (cout_pad % bn || (split && nkt < 16 && t == IGEMM_TILE_128x128)) continue;
+            if (ntiles(t) % (256LL * igemm_resident_blocks(t, split)) == 0) { best = t; exact = true; break; }
         }
     }
     if (force_tile >= 1 && force_tile <= IGEMM_NTILES) { best = force_tile; exact = false; }
     const long long tiles = ntiles(best);
     const long long units = tiles * (long long)nkt;
-    const long long pmax = 256LL * igemm_resident_blocks(best);
+    const long long pmax = 256LL * igemm_resident_blocks(best, split);
     long long p;
     *granule = 1;
     if (exact || (nkt < 16 && tiles >= pmax && (nkt <= 4 || tiles >= pmax * 8))) {   // whole tiles, nothing is cut

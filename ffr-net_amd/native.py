@@ -30,7 +30,7 @@ class TensorDesc(C.Structure):
 class MemStats(C.Structure):
     _fields_ = [('encoder_weight_bytes', C.c_size_t), ('recnet_weight_bytes', C.c_size_t), ('mixed_tile_weight_bytes', C.c_size_t),
                 ('workspace_bytes', C.c_size_t), ('encoder_load_seconds', C.c_double), ('recnet_load_seconds', C.c_double),
-                ('mixed_tile_pack_seconds', C.c_double)]
+                ('mixed_tile_pack_seconds', C.c_double), ('split_weight_bytes', C.c_size_t)]
 
 
 class KClassStat(C.Structure):

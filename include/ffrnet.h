@@ -269,6 +269,14 @@ int ffr_profile_enable(ffr_handle* h, int on);
  *   "combine_v" (1)       1: a bottleneck's combine (res * scale + shortcut) also writes the Winograd transform V of its
  *                         output when the next unit's conv1 runs k_wino_fused from V (stage 3 / 4): k_combine_in_c
  *                         replaces k_combine + k_wino_in_c
+ *   "igemm_split" (1)     1: the direct convolutions whose weights ffr_load_encoder split into three bf16 planes (the layers
+ *                         that never run Winograd: 3x3 stride 2, the 1x1 shortcuts, and the output_layer GEMM) run k_igemm's
+ *                         split-operand form: the same fp32 product as six exact bf16 x bf16 products per term on the bf16
+ *                         matrix cores, accumulated in fp32 (error of the order of one fp32 rounding per product, DESIGN.md
+ *                         3.2 / 4).  0: every launch is the fp32-MFMA kernel.  Callers that pass raw fp32 weights (ffr_op_conv
+ *                         without flags bit1, the training GEMMs, the batched Winograd GEMMs) always run the fp32 form.  The
+ *                         planes cost 1.5 x the fp32 weights of those layers (ffr_memory_stats: split_weight_bytes); a device
+ *                         that cannot hold them keeps the fp32 form for the layers concerned, logs once and does not fail.
  *   "gemm_stream" (1), "sk_minunits" (18)   round-1 path details (batched-GEMM Winograd, stream-K granule)
  *   "wf_trace", "igemm_trace" (0)   per-launch phase stamps on stderr; only in a -DFFR_TRACE build (tools/trace_build.py),
  *                                    the shipped library returns FFR_ERR_UNSUPPORTED
@@ -323,10 +331,12 @@ int ffr_calibrate(ffr_handle* h, const float* x_nchw, const float* featmap_nchw,
 /* Device memory and packing time of the handle (round 5; the reference's counterpart is `net.load_state_dict(...)` +
  * `.to(device)`, models/trainer.py:98-113, which has no packing step).  mixed_tile_* are the three extra Winograd weight
  * sets of the exact 14x14 tiling: derived on the device the first time a batch large enough to use them arrives
- * (ffr_reserve / the first forward of >= 256 images), 0 before.                                                     */
+ * (ffr_reserve / the first forward of >= 256 images), 0 before.  split_weight_bytes (part of encoder_weight_bytes) are
+ * the bf16 planes of the split-operand form of k_igemm (option "igemm_split"), made by ffr_load_encoder.            */
 typedef struct ffr_mem_stats {
     size_t encoder_weight_bytes, recnet_weight_bytes, mixed_tile_weight_bytes, workspace_bytes;
     double encoder_load_seconds, recnet_load_seconds, mixed_tile_pack_seconds;
+    size_t split_weight_bytes;
 } ffr_mem_stats;
 int ffr_memory_stats(const ffr_handle* h, ffr_mem_stats* out);
 /* fp32-MFMA rate this device delivers on a register-resident v_mfma_f32_32x32x2_f32 loop (iters x 16 MFMAs per
@@ -343,7 +353,8 @@ int ffr_profile_read(ffr_handle* h, ffr_kclass_stat* out /* [FFR_KC_COUNT] */);
  *   slope  [cout_pad] PReLU slopes or NULL
  *   resid  [N,Ho,Wo,res_pitch] added after the activation, or NULL
  *   out    [N,Ho,Wo,out_pitch], channels [out_coff, out_coff+cout_store) written
- *   pad_mode 0 = zero, 1 = reflect;  flags bit0 = sigmoid at the end
+ *   pad_mode 0 = zero, 1 = reflect;  flags bit0 = sigmoid at the end; bit1 = run the split-operand form of the kernel
+ *   (option "igemm_split") on a device-side split of w into three bf16 planes (tests; synchronises the stream)
  *   tile   0 = heuristic, else 1..4 = forced tile config (128x128, 128x64, 64x64, 256x64);
  *   splitk is ignored (the kernel is stream-K: K is balanced over the blocks by itself) */
 typedef struct {
