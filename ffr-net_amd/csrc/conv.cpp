@@ -135,7 +135,7 @@ static int trace_wino_fused(ffr_handle* h, WinoFusedArgs& f, const ConvW& L, con
         const int cpp = 4, nph = f.nkc / cpp;                      // K chunks per phase, phases
         fprintf(stderr, "[wf trace] %dx%d cin %d cout %d (input transform in the kernel, %d-channel blocks%s): %d live blocks of %d | per block (wave 0): "
                         "prologue %.0f loop %.0f = %d phases x (transform %.0f + barrier %.0f + %d K chunks of %.0f) epilogue %.0f cyc | "
-                        "block ends spread over %.1f us\n", c.H, c.W, L.cin_pad, L.cout_pad, p.half_n ? 32 : 64, "", cnt, nb,
+                        "block ends spread over %.1f us\n", c.H, c.W, L.cin_pad, L.cout_pad, p.half_n ? 32 : 64, p.split ? ", split-operand K loop" : "", cnt, nb,
                 pro / cnt, loop / cnt, nph, ep[0] / cnt, ep[1] / cnt, cpp, (loop / cnt / nph - ep[0] / cnt - ep[1] / cnt) / cpp, epi / cnt,
                 (double)(r1 - r0) / 100.0);
     }
@@ -223,6 +223,7 @@ static int conv_fused(ffr_handle* h, const ConvW& L, const ConvCall& c, const Co
     // batch 256); with the in-kernel transform an XCD owns a contiguous range of tile groups (halo rows shared in its L2).
     // The alternatives (one channel group per XCD; XCD quads splitting the channel groups) measured slower: EXPERIMENTS.md
     f.map_v = p.phased ? 2 : 1; f.half_n = p.half_n ? 1 : 0;
+    f.U3 = p.split ? L.wu3 : nullptr;
     f.Uc = L.wuc; f.bias = L.bias; f.slope = L.slope; f.resid = c.resid; f.out = c.out; f.tile_sums = c.tile_sums;
     f.N = c.N; f.H = c.H; f.W = c.W; f.nkc = L.cin_pad / 8;
     f.cout_pad = L.cout_pad; f.cout_store = c.cout_store; f.out_pitch = c.out_pitch; f.out_coff = c.out_coff;
@@ -231,8 +232,9 @@ static int conv_fused(ffr_handle* h, const ConvW& L, const ConvCall& c, const Co
 #ifdef FFR_TRACE
     if (h->opt.wf_trace) return trace_wino_fused(h, f, L, c, p, st);
 #endif
-    Scope s(h, st, FFR_KC_WINO_FUSED, flops, bytes, fexec, flops / 4.0);
+    Scope s(h, st, FFR_KC_WINO_FUSED, flops, bytes, fexec, flops / 4.0);      // flops_executed stays the fp32-equivalent count in the split form
     HIPCK(h, launch_wino_fused(f, st));
+    if (p.split) ++h->wf_split_launches;
     return FFR_OK;
 }
 
@@ -314,7 +316,7 @@ int run_conv(ffr_handle* h, const ConvW& L, const ConvCall& c, hipStream_t st) {
     if (p.path == ConvPlan::Fused) {
         // tail split: the first n_main images fused, the rest through the transform kernels + batched GEMM
         ConvCall c1 = c, c2 = c;
-        c1.N = p.n_main; c1.force = p.half_n ? ConvForce::FusedHalf : ConvForce::Fused;
+        c1.N = p.n_main; c1.force = p.half_n ? ConvForce::FusedHalf : p.split ? ConvForce::FusedSplit : ConvForce::Fused;
         c2.N = c.N - p.n_main; c2.force = ConvForce::Unfused;
         const size_t px = (size_t)p.n_main * c.H * c.W;
         c2.x = c.x + px * c.in_pitch;

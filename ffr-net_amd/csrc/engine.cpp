@@ -123,6 +123,18 @@ int ffr_memory_stats(const ffr_handle* h, ffr_mem_stats* out) {
     out->recnet_load_seconds = h->rec_load_s;
     out->mixed_tile_pack_seconds = h->mixed_pack_s;
     out->split_weight_bytes = h->split_weight_bytes;
+    out->wf_split_weight_bytes = h->wf_split_weight_bytes;
+    out->wf_split_launches = h->wf_split_launches;
+    return FFR_OK;
+}
+
+int ffr_split_planes_host(const double* w, long long n, unsigned short* planes) {
+    if (!w || !planes || n < 0) return FFR_ERR_ARG;
+    for (long long i = 0; i < n; ++i) {
+        unsigned short q[3];
+        split_bf16x3(w[i], q);
+        for (int p = 0; p < 3; ++p) planes[(size_t)p * n + i] = q[p];
+    }
     return FFR_OK;
 }
 
@@ -554,7 +566,7 @@ const OptEntry OPTIONS[] = {
     {"wf_phased_maxk", &Options::wf_phased_maxk, nullptr, 0, 1 << 20}, {"wf_minblocks", nullptr, &Options::wf_minblocks, 0, 1LL << 40},
     {"se_maxtiles", &Options::se_maxtiles, nullptr, 0, 1 << 20}, {"wf_tailsplit", &Options::wf_tailsplit, nullptr, 0, 1},
     {"gemm_stream", &Options::gemm_stream, nullptr, 0, 1}, {"sk_minunits", &Options::sk_minunits, nullptr, 1, 1 << 20},
-    {"combine_v", &Options::combine_v, nullptr, 0, 1}, {"wf_mixed", &Options::wf_mixed, nullptr, 0, 1},
+    {"combine_v", &Options::combine_v, nullptr, 0, 1}, {"wf_split", &Options::wf_split, nullptr, 0, 1}, {"wf_mixed", &Options::wf_mixed, nullptr, 0, 1},
     {"channel_rows", &Options::channel_rows, nullptr, 0, 4}, {"igemm_split", &Options::igemm_split, nullptr, 0, 1},
     {"wf_trace", &Options::wf_trace, nullptr, 0, 1}, {"igemm_trace", &Options::igemm_trace, nullptr, 0, 1},
 };
@@ -688,7 +700,7 @@ int ffr_op_conv3x3(ffr_handle* h, const float* x, int N, int H, int W, int cin, 
     FFR_DEVICE_SCOPE(h); RC(check_fwd(h, false, false, N));
     if (!x || !w_host || !bias_host || !out || cin % 32 || cout % 4 || cin <= 0 || cout <= 0)
         return fail(h, FFR_ERR_ARG, "ffr_op_conv3x3: bad arguments (cin %% 32, cout %% 4)");
-    if (use_wino < 0 || use_wino > 4) return fail(h, FFR_ERR_ARG, "ffr_op_conv3x3: use_wino must be 0..4");
+    if (use_wino < 0 || use_wino > 5) return fail(h, FFR_ERR_ARG, "ffr_op_conv3x3: use_wino must be 0..5");
     hipStream_t st = (hipStream_t)stream;
     Work w;
     RC(ensure_arena(h, N > 8 ? N : 8, 112, 112, &w));
@@ -699,6 +711,8 @@ int ffr_op_conv3x3(ffr_handle* h, const float* x, int N, int H, int W, int cin, 
     ConvW L;
     int rc = pack_conv(h, own, w_host, cout, cin, 3, 3, nullptr, &ob, slope_host, 1, 1, pad_mode, &L);
     if (rc == FFR_OK && use_wino && !L.wu) rc = fail(h, FFR_ERR_UNSUPPORTED, "layer not eligible for the Winograd path (cin < FFR_WINO_MINCIN)");
+    if (rc == FFR_OK && use_wino == 5 && !L.wu3)
+        rc = fail(h, FFR_ERR_UNSUPPORTED, "the split-operand fused form needs cin <= wf_phased_maxk (%d) and room for its weight planes", h->opt.wf_phased_maxk);
     if (rc == FFR_OK && use_wino == 4) {
         if (!wino_mixed_eligible(h, L, N, H, W, cin, w.wino_cap, ConvForce::Mixed)) rc = fail(h, FFR_ERR_UNSUPPORTED, "layer / map not eligible for the mixed-tile path");
         else rc = ensure_mixed_weights(h, L, own, true);

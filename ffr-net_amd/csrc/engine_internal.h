@@ -38,6 +38,8 @@ struct ConvW {
     bool wum_gave_up = false;   // the device could not hold this layer's extra sets: it stays on padded F(4x4) tiles (never retried)
     unsigned short* w3 = nullptr;   // `w` as three bf16 planes [3][cout_pad][KK] for k_igemm's split-operand form (layers that always run
                              // direct, and the FC; split from the double-precision fold at load time), or null: the fp32 form
+    unsigned short* wu3 = nullptr;  // G g G^T as three bf16 planes in the order of k_wino_fused's split-operand form (ffr_kernels.h: WinoFusedArgs::U3;
+                             // layers with cin_pad <= wf_phased_maxk, split from the double-precision fold at load time), or null
     float* wuc = nullptr;    // the same in the K-chunk order k_wino_fused streams ([cout_pad/64][cin_pad/8][36][128][4]) or null
     // per-layer arithmetic plan (ffr_layer_set_arith / ffr_calibrate): a layer with wu pinned to direct runs exactly
     // what it runs under option wino = 0.  ffr_load_* reset it (pack_conv).
@@ -68,6 +70,7 @@ struct Options {
     int wf_mixed = 1;             // 1: 14x14 maps are tiled 4+4+3+3 (k_wino_fused_mixed) when the launch gives every CU two blocks or more
     int channel_rows = 0;         // k_channel_path: blocks per image (1, 2, 4); 0 = from the batch and the CU count (round 5)
     int igemm_split = 1;          // 1: direct convolutions whose weights were split at load time run k_igemm's split-operand form (bf16 matrix cores)
+    int wf_split = 1;             // 1: fused Winograd launches that transform their own input run the split-operand K loop where the layer has the planes
     int combine_v = 1;            // 1: a bottleneck's combine also writes V for the next conv1 when that runs k_wino_fused from V
     int wf_trace = 0, igemm_trace = 0;   // -DFFR_TRACE builds only: per-launch phase stamps on stderr (synchronises)
     // Retired in round 6, their A/B settled (EXPERIMENTS.md): wino_112, wf_halfblocks, wf_mapv, wf_mapx, wf_maph, wm_xcdpairs,
@@ -96,7 +99,9 @@ struct ffr_handle {
     size_t enc_weight_bytes = 0, rec_weight_bytes = 0;      // device bytes of the packed weights (ffr_memory_stats)
     size_t mixed_weight_bytes = 0;                          // of them: the lazily derived weight sets of the exact 14x14 tiling
     double enc_load_s = 0.0, rec_load_s = 0.0, mixed_pack_s = 0.0;   // wall seconds of the last ffr_load_* / of all lazy packs
-    size_t split_weight_bytes = 0;                          // of enc_weight_bytes: the bf16 planes of the split-operand form
+    size_t split_weight_bytes = 0;                          // of enc_weight_bytes: the bf16 planes of k_igemm's split-operand form
+    size_t wf_split_weight_bytes = 0;                       // of enc_weight_bytes: the bf16 planes of k_wino_fused's split-operand form
+    long long wf_split_launches = 0;                        // k_wino_fused launches in the split-operand form since ffr_create
     bool mixed_gave_up_logged = false, split_gave_up_logged = false;
     int mixed_ready_n = 0, mixed_ready_h = 0, mixed_ready_w = 0;     // prepare_mixed_weights ran for batches up to n of h x w (a shortcut only:
                                                                      // readiness itself is per layer, ConvW::wum / wum_gave_up)
@@ -213,6 +218,8 @@ bool bn_fold(SD& sd, const std::string& p, int C, BNFold& o);
 int upload(ffr_handle* h, std::vector<void*>& owner, const std::vector<float>& v, float** out);
 int pack_conv(ffr_handle* h, std::vector<void*>& owner, const float* W, int cout, int cin, int R, int S,
               const BNFold* in_bn, const BNFold* out_bn, const float* slope, int stride, int pad, int pad_mode, ConvW* L);
+void split_bf16x3(double w, unsigned short out[3]);       // p1 = bf16(w), p2 = bf16(w - p1), p3 = bf16(w - p1 - p2), round to nearest even
+void pack_wino_split(const double* ud, int cout_pad, int cin_pad, unsigned short* pl);
 void free_list(std::vector<void*>& v);
 int ensure_mixed_weights(ffr_handle* h, ConvW& L, std::vector<void*>& owner, bool strict);
 int prepare_mixed_weights(ffr_handle* h, int N, int H, int W, size_t wino_cap);
@@ -223,7 +230,8 @@ inline ConvW& rec_conv(ffr_handle* h, int i) { return i < 9 ? h->sp[i] : i < 12 
 // What a caller asks of a convolution's arithmetic; the values are those of use_wino in ffr_op_conv3x3.  Auto: the planner
 // decides (option wino, the layer's plan, wino_fused_form, the tail split).  Fused / FusedHalf: k_wino_fused with 32 x 64 /
 // 32 x 32 blocks.  Unfused: transform kernels + batched GEMM.  Mixed: the exact 4+4+3+3 tiling of a 14x14 map.
-enum class ConvForce { Auto = -1, Direct = 0, Fused = 1, Unfused = 2, FusedHalf = 3, Mixed = 4 };
+// FusedSplit: Fused with the in-kernel transform and the split-operand K loop (refused where the layer or the launch cannot).
+enum class ConvForce { Auto = -1, Direct = 0, Fused = 1, Unfused = 2, FusedHalf = 3, Mixed = 4, FusedSplit = 5 };
 
 struct ConvCall {
     const float* x; int N, H, W, in_pitch;
@@ -245,6 +253,7 @@ struct ConvPlan {
     enum Path { Direct, Mixed, Fused, Unfused } path = Direct;
     bool half_n = false;            // Fused: blocks of 32 tiles x 32 channels (else 32 x 64)
     bool phased = false;            // Fused: the kernel transforms its own input, V never exists in memory
+    bool split = false;             // Fused + phased: the K loop runs on the bf16 matrix cores from the layer's three planes (ConvW::wu3)
     int n_main = 0;                 // Fused: the first n_main images run fused and the rest Unfused (0: no split)
     hipStream_t side = nullptr;     // ... the rest is enqueued first, on this stream (null: after the main part on the launch stream)
     bool takes_v = false;           // the whole conv runs fused from a V in k_wino_fused's order (a combine may write it)

@@ -15,6 +15,14 @@
 
 namespace ffr {
 
+// two bf16 (round to nearest even) of two floats in one register: lo in bits 0-15 (the split-operand forms of k_igemm and
+// k_wino_fused)
+__device__ __forceinline__ unsigned cvt_pk_bf16(float lo, float hi) {
+    unsigned r;
+    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
+    return r;
+}
+
 // ---- implicit-GEMM convolution (igemm.hip) -----------------------------------------
 // out[m][n] = epilogue( sum_k A[m][k] * Wp[n][k] ),  m = (img, ho, wo), k = (r, s, ci)
 struct IgemmArgs {
@@ -99,7 +107,11 @@ struct WinoFusedArgs {
     int th, tw, mbn, nbn;                   // filled by the launcher
     long long T;
     unsigned long long* trace;              // diagnostics (-DFFR_TRACE build, option "wf_trace"): 10 words per wave, or null
+    // split-operand form (wino_fused.hip): G g G^T as three bf16 planes in the order
+    // [cout_pad/64][cin_pad/16][36][2 halves][3 planes][64 lanes][8 bf16]; non-null selects the form (Vc null, half_n 0)
+    const unsigned short* U3;
 };
+inline size_t wino_split_u_elems(int cout_pad, int cin_pad) { return (size_t)(cout_pad / 64) * (cin_pad / 16) * 36 * 2 * 3 * 64 * 8; }
 bool combine_in_c_supported(int H, int W, int C);
 hipError_t launch_combine_in_c(const float* res, const float* scale, const float* sh, float* out, float* Vc, int N, int H,
                                int W, int C, hipStream_t stream);

@@ -36,13 +36,6 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 #define LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
 #define GLB_PTR(p) ((const __attribute__((address_space(1))) void*)(p))
 
-// two bf16 (round to nearest even) of two floats in one register: lo in bits 0-15
-__device__ __forceinline__ unsigned cvt_pk_bf16(float lo, float hi) {
-    unsigned r;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-    return r;
-}
-
 // SPLIT (split-operand form): the same fp32 product on v_mfma_f32_32x32x16_bf16.  Every fp32 value is the sum
 // of three bf16 pieces (a1 = bf16(a), a2 = bf16(a - a1), a3 = bf16(a - a1 - a2)); the six products ai*bj with i + j <= 4, each
 // exact in fp32, are accumulated in fp32 by the matrix core.  A stays fp32 in LDS and is split in registers after the

@@ -58,21 +58,52 @@ static double round_bf16(double d) {
 // The three bf16 planes [3][n] of the double-precision weights wd[n] for k_igemm's split-operand form: p1 = bf16(w),
 // p2 = bf16(w - p1), p3 = bf16(w - p1 - p2) -- together they carry more of the fold than its fp32 rounding did.
 // An optimisation: when the device cannot hold them the layer keeps the fp32 form, logged once, not an error.
+void split_bf16x3(double w, unsigned short out[3]) {
+    for (int p = 0; p < 3; ++p) {
+        const double b = round_bf16(w);
+        const float bf = (float)b;
+        unsigned u;
+        memcpy(&u, &bf, 4);
+        out[p] = (unsigned short)(u >> 16);
+        w -= b;
+    }
+}
+
+static int upload_planes(ffr_handle* h, std::vector<void*>& owner, const std::vector<unsigned short>& pl, size_t* counter, unsigned short** out);
+
 int upload_split(ffr_handle* h, std::vector<void*>& owner, const std::vector<double>& wd, unsigned short** out) {
-    *out = nullptr;
     const size_t n = wd.size();
     std::vector<unsigned short> pl(3 * n);
     for (size_t i = 0; i < n; ++i) {
-        double r = wd[i];
-        for (int p = 0; p < 3; ++p) {
-            const double b = round_bf16(r);
-            const float bf = (float)b;
-            unsigned u;
-            memcpy(&u, &bf, 4);
-            pl[(size_t)p * n + i] = (unsigned short)(u >> 16);
-            r -= b;
-        }
+        unsigned short q[3];
+        split_bf16x3(wd[i], q);
+        for (int p = 0; p < 3; ++p) pl[(size_t)p * n + i] = q[p];
     }
+    return upload_planes(h, owner, pl, &h->split_weight_bytes, out);
+}
+
+// The three bf16 planes of ud = G g G^T [36][cout_pad][cin_pad] (double, BN folded) in the order k_wino_fused's split-operand
+// form streams them: [cout_pad/64][16-channel K step][xi][2 halves][3 planes][64 lanes][8 bf16]; lane = 32 * (k half) + (output
+// channel & 31) carries the channels 16 step + 8 (k half) + 0..7, one 16-byte load per lane and plane.
+void pack_wino_split(const double* ud, int cout_pad, int cin_pad, unsigned short* pl) {
+    const int nst = cin_pad / 16;
+    for (int nb = 0; nb < cout_pad / 64; ++nb)
+        for (int s = 0; s < nst; ++s)
+            for (int xi = 0; xi < 36; ++xi)
+                for (int nt = 0; nt < 2; ++nt)
+                    for (int lane = 0; lane < 64; ++lane)
+                        for (int i = 0; i < 8; ++i) {
+                            const int co = nb * 64 + nt * 32 + (lane & 31), ci = 16 * s + 8 * (lane >> 5) + i;
+                            unsigned short q[3];
+                            split_bf16x3(ud[((size_t)xi * cout_pad + co) * cin_pad + ci], q);
+                            const size_t base = ((((size_t)nb * nst + s) * 36 + xi) * 2 + nt) * 3;
+                            for (int p = 0; p < 3; ++p) pl[((base + p) * 64 + lane) * 8 + i] = q[p];
+                        }
+}
+
+// Uploads bf16 planes; *counter (a field of h) takes their bytes when they belong to the encoder.
+static int upload_planes(ffr_handle* h, std::vector<void*>& owner, const std::vector<unsigned short>& pl, size_t* counter, unsigned short** out) {
+    *out = nullptr;
     void* p = nullptr;
     const size_t bytes = pl.size() * sizeof(unsigned short);
     hipError_t e = hipMalloc(&p, bytes);
@@ -88,7 +119,7 @@ int upload_split(ffr_handle* h, std::vector<void*>& owner, const std::vector<dou
         return FFR_OK;
     }
     owner.push_back(p);
-    if (&owner == &h->enc_allocs) { h->enc_weight_bytes += bytes; h->split_weight_bytes += bytes; }
+    if (&owner == &h->enc_allocs) { h->enc_weight_bytes += bytes; *counter += bytes; }
     if (&owner == &h->rec_allocs) h->rec_weight_bytes += bytes;
     *out = (unsigned short*)p;
     return FFR_OK;
@@ -153,6 +184,7 @@ int pack_conv(ffr_handle* h, std::vector<void*>& owner, const float* W, int cout
     if (!wino) RC(upload_split(h, owner, wd, &L->w3));
     L->wu = nullptr;
     L->wuc = nullptr;
+    L->wu3 = nullptr;
     for (int tau = 0; tau < 4; ++tau) L->wum[tau] = nullptr;
     L->direct = false;          // new weights: the layer's plan returns to Winograd, its calibration is void
     L->sensitivity = -1.0;
@@ -161,6 +193,10 @@ int pack_conv(ffr_handle* h, std::vector<void*>& owner, const float* W, int cout
         static const double G[6][3] = {{0.25, 0, 0}, {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
                                        {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0, 0, 1}};
         std::vector<float> wu((size_t)36 * L->cout_pad * L->cin_pad, 0.f);
+        // layers whose fused launches transform their own input: the fold in double, for the planes of the split-operand K loop
+        const bool split = L->cin_pad <= h->opt.wf_phased_maxk && L->cin_pad % 32 == 0;
+        std::vector<double> wud;
+        if (split) wud.assign(wu.size(), 0.0);
         for (int co = 0; co < cout; ++co) {
             const double g = out_bn ? out_bn->s[co] : 1.0;
             for (int ci = 0; ci < cin; ++ci) {
@@ -173,6 +209,7 @@ int pack_conv(ffr_handle* h, std::vector<void*>& owner, const float* W, int cout
                     for (int j = 0; j < 6; ++j) {
                         const double u = tmp[i][0] * G[j][0] + tmp[i][1] * G[j][1] + tmp[i][2] * G[j][2];
                         wu[((size_t)(i * 6 + j) * L->cout_pad + co) * L->cin_pad + ci] = (float)(u * sc);
+                        if (split) wud[((size_t)(i * 6 + j) * L->cout_pad + co) * L->cin_pad + ci] = u * sc;
                     }
             }
         }
@@ -192,6 +229,11 @@ int pack_conv(ffr_handle* h, std::vector<void*>& owner, const float* W, int cout
                             for (int e = 0; e < 4; ++e) dst[e] = src[e];
                         }
         RC(upload(h, owner, wuc, &L->wuc));
+        if (split) {
+            std::vector<unsigned short> pl(wino_split_u_elems(L->cout_pad, L->cin_pad));
+            pack_wino_split(wud.data(), L->cout_pad, L->cin_pad, pl.data());
+            RC(upload_planes(h, owner, pl, &h->wf_split_weight_bytes, &L->wu3));
+        }
     }
     L->slope = nullptr;
     if (slope) {
@@ -309,7 +351,7 @@ int ffr_load_encoder(ffr_handle* h, const ffr_tensor_desc* t, int n) {
     free_list(h->enc_allocs);
     ++h->generation;
     h->enc_loaded = false;
-    h->mixed_ready_n = 0; h->mixed_weight_bytes = 0; h->enc_weight_bytes = 0; h->mixed_pack_s = 0.0; h->split_weight_bytes = 0;
+    h->mixed_ready_n = 0; h->mixed_weight_bytes = 0; h->enc_weight_bytes = 0; h->mixed_pack_s = 0.0; h->split_weight_bytes = 0; h->wf_split_weight_bytes = 0;
     const auto load_t0 = std::chrono::steady_clock::now();
     SD sd; sd.h = h;
     for (int i = 0; i < n; ++i) if (t[i].name) sd.m[t[i].name] = &t[i];

@@ -26,6 +26,7 @@ static bool short_last_round(const ffr_handle* h, long long block_tiles) {
 // (32 x 32) or Unfused (transform kernels + batched GEMM).  A forced form is kept while option wino_fused is on.
 ConvForce wino_fused_form(const ffr_handle* h, int cin_pad, int cout_pad, long long T, double x_bytes, ConvForce ask) {
     if (!h->opt.wino_fused || ask == ConvForce::Direct || ask == ConvForce::Unfused) return ConvForce::Unfused;
+    if (ask == ConvForce::FusedSplit) return ConvForce::Fused;
     if (ask == ConvForce::Fused || ask == ConvForce::FusedHalf) return ask;
     // One block tile (all 36 xi) occupies a whole CU and cannot be cut: a launch with fewer block tiles than CUs leaves matrix
     // cores idle, where the batched-GEMM path balances K-tiles over every CU (Conv4Space at batch 256: 32..128 block tiles of
@@ -95,6 +96,10 @@ ConvPlan plan_conv(const ffr_handle* h, const ConvW& L, const ConvCall& c) {
         p.path = ConvPlan::Fused;
         p.phased = phased;
         p.half_n = form == ConvForce::FusedHalf;
+        // split-operand K loop: the layer has the planes, the launch is the in-kernel-transform form with 32 x 64 blocks, and option
+        // wf_split is on (Auto) or the caller asks for it by name.  A caller that forces Fused / FusedHalf gets the fp32 loop.
+        p.split = L.wu3 && phased && !p.half_n && (f == ConvForce::FusedSplit || (f == ConvForce::Auto && h->opt.wf_split != 0));
+        if (f == ConvForce::FusedSplit && !p.split) { p = ConvPlan{}; p.refused = "the split-operand fused form was asked for a layer or launch that cannot run it"; return p; }
         const int nbn = L.cout_pad / (p.half_n ? 32 : 64);
         const long long block_tiles = (T + 31) / 32 * nbn;
         if (f == ConvForce::Auto && short_last_round(h, block_tiles)) {
@@ -113,7 +118,8 @@ ConvPlan plan_conv(const ffr_handle* h, const ConvW& L, const ConvCall& c) {
         p.takes_v = !phased && p.n_main == 0 && L.pad_mode == 0 && c.in_pitch == L.cin_pad;
         return p;
     }
-    if (L.wu == L.wuc) p.refused = "Winograd weights exist in the fused kernel's order only, but this launch cannot run fused";
+    if (f == ConvForce::FusedSplit) p.refused = "the split-operand fused form was asked for a launch that cannot run fused";
+    else if (L.wu == L.wuc) p.refused = "Winograd weights exist in the fused kernel's order only, but this launch cannot run fused";
     else if ((size_t)36 * T * L.cin_pad <= c.wino_cap && (size_t)36 * T * L.cout_pad <= c.wino_cap && T < 0x7fffffffLL) p.path = ConvPlan::Unfused;
     return p;
 }

@@ -27,6 +27,9 @@
 
 namespace ffr {
 
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
 // ---- input transform into the chunked operand order ---------------------------------------------------------
 // grid (mbn, cin_pad / 32); wave w of a block = K chunk 4*blockIdx.y + w of tile group blockIdx.x; lane = piece
 template <int PAD_MODE>
@@ -205,6 +208,7 @@ __device__ __forceinline__ void wait_vmcnt(int n) {
 
 // ---- the fused GEMM + output transform ------------------------------------------------------------------------
 constexpr int WF_EPI_FLOATS = 36 * 32 * 32;  // the epilogue's E[xi][tile][32 channels] (147,456 B); the K loop uses no LDS
+constexpr int WF_U3_STEP = 2 * 3 * 64 * 16;   // split form: bytes of U per (channel group, 16-channel K step, xi): 2 halves x 3 planes x 64 lanes x 8 bf16
 constexpr int WF_LDS_BYTES = (WF_EPI_FLOATS + 9 * 64 + 32 * 8 + 32 * 12) * 4;   // + bias table + tile table + patch-offset table = 152,320 B
 
 // MODE 0 (PHASED = false): V comes pre-transformed from k_wino_in_c (global memory, fragment order).
@@ -216,9 +220,16 @@ constexpr int WF_LDS_BYTES = (WF_EPI_FLOATS + 9 * 64 + 32 * 8 + 32 * 12) * 4;   
 // NT = 32-channel halves per block: 2 = the 32-tile x 64-channel block tile; 1 = 32 tiles x 32 channels (half the
 // accumulators and half the work per block: twice as many blocks for launches that would leave CUs idle or run a
 // nearly empty last round -- small batches, stage 4 and RecNet at 128 images per GPU).
-template <int MODE, int NT>
+// SPLIT (MODE 1, NT 2; split-operand form): the K loop runs on v_mfma_f32_32x32x16_bf16 as k_igemm's split form
+//                 does.  V stays fp32 in LDS, in the same image: a lane reads the 8 channels of its half of a 16-channel K step
+//                 (two fragments of one K chunk) and splits them into three bf16 pieces in registers, once per value (wave
+//                 w alone reads its xi); U arrives as three bf16 planes a.U3 (pack.cpp, split from the double-precision
+//                 G g G^T).  Six products per term, small ones first; both MFMA shapes share the 32x32 accumulator layout,
+//                 so transform, epilogue and tables are those of the fp32 form.
+template <int MODE, int NT, bool SPLIT = false>
 __global__ __launch_bounds__(256, 1) void k_wino_fused(const WinoFusedArgs a) {
     constexpr bool PHASED = MODE != 0;
+    static_assert(!SPLIT || (MODE == 1 && NT == 2), "the split-operand form exists for the in-kernel transform with 32 x 64 blocks");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
@@ -312,11 +323,16 @@ __global__ __launch_bounds__(256, 1) void k_wino_fused(const WinoFusedArgs a) {
     // 36 KB per K chunk, at most 6.9 MB)
     const __amdgpu_buffer_rsrc_t vrs = __builtin_amdgcn_make_buffer_rsrc((void*)(PHASED ? a.Uc : a.Vc + (size_t)mb * nkc * 36 * 256), 0,
                                                                          PHASED ? 0u : (unsigned)nkc * 36u * 1024u, 0x00020000);
-    const __amdgpu_buffer_rsrc_t urs = __builtin_amdgcn_make_buffer_rsrc((void*)a.Uc, 0, (unsigned)((size_t)a.cout_pad * nkc * 8 * 36 * 4), 0x00020000);
+    // (split form: three bf16 planes, 6 KB per channel group, 16-channel K step and xi)
+    const __amdgpu_buffer_rsrc_t urs = SPLIT
+        ? __builtin_amdgcn_make_buffer_rsrc((void*)a.U3, 0, (unsigned)((size_t)(a.cout_pad >> 6) * (nkc >> 1) * 36 * WF_U3_STEP), 0x00020000)
+        : __builtin_amdgcn_make_buffer_rsrc((void*)a.Uc, 0, (unsigned)((size_t)a.cout_pad * nkc * 8 * 36 * 4), 0x00020000);
     const unsigned lane16 = (unsigned)lane * 16u;
     unsigned vp = (unsigned)(9 * wave) * 1024u;                                 // scalar byte offsets of this wave's xi 0 in the current K chunk
     // U is packed per 64-channel group: [cout_pad/64][K chunk][xi][2 halves][64 lanes][4]
-    unsigned up = NT == 2 ? (unsigned)(nb * nkc * 36 + 9 * wave) * 2048u
+    // split form: [cout_pad/64][16-channel K step][xi][2 halves][3 planes][64 lanes][8 bf16]
+    unsigned up = SPLIT ? (unsigned)(nb * (nkc >> 1) * 36 + 9 * wave) * (unsigned)WF_U3_STEP
+                : NT == 2 ? (unsigned)(nb * nkc * 36 + 9 * wave) * 2048u
                           : (unsigned)((nb >> 1) * nkc * 36 + 9 * wave) * 2048u + (unsigned)(nb & 1) * 1024u;
     auto ldfrag = [&](const __amdgpu_buffer_rsrc_t& rs, unsigned so) {
         return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, lane16, so, 0));
@@ -403,6 +419,49 @@ __global__ __launch_bounds__(256, 1) void k_wino_fused(const WinoFusedArgs a) {
     auto reada = [&](int buf, int c, int j) {
         af[buf] = *reinterpret_cast<const f32x4*>(smem + (c * 36 + 9 * wave + j) * 256 + aoff[c]);
     };
+    // split form.  A phase is 18 steps k = 9 s + j: 16-channel K step s, xi j.  The bf16 MFMA wants from lane (H = lane >> 5,
+    // t = lane & 31) the channels 8H .. 8H+7 of the K step: both fragments (h = 0, 1) of K chunk 2s + H in the image above, two
+    // conflict-free ds_read_b128.  U: NS slots of 2 halves x 3 planes, slot k % NS holds step k, reloaded one step after its
+    // use, NS - 1 steps ahead of the next.
+    constexpr int NS = 3;
+    constexpr int PU[6] = {2, 0, 1, 1, 0, 0}, PV[6] = {0, 2, 1, 0, 1, 0};      // the six products, small ones first
+    u32x4 fu3[SPLIT ? NS : 1][NT][3], pv[2][3];
+    f32x4 vraw[2];
+    int voff[2][2];
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int hh = 0; hh < 2; ++hh) {
+            const int c = 2 * s + (lane >> 5);
+            voff[s][hh] = c * 36 * 256 + (32 * hh + (lane & 24) + ((lane + 2 * c + hh) & 7)) * 4;
+        }
+    auto loadu3 = [&](int slot, int k, unsigned u) {
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+            for (int p = 0; p < 3; ++p)
+                fu3[slot][nt][p] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
+                    urs, lane16, u + (unsigned)((k / 9) * 36 + k % 9) * (unsigned)WF_U3_STEP + (unsigned)(nt * 3 + p) * 1024u, 0));
+    };
+    auto loadu3_one = [&](int slot, int k, int m, unsigned u) {       // load m of the six of a slot
+        fu3[slot][m / 3][m % 3] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
+            urs, lane16, u + (unsigned)((k / 9) * 36 + k % 9) * (unsigned)WF_U3_STEP + (unsigned)m * 1024u, 0));
+    };
+    auto readv = [&](int k) {
+#pragma unroll
+        for (int hh = 0; hh < 2; ++hh) vraw[hh] = *reinterpret_cast<const f32x4*>(smem + (9 * wave + k % 9) * 256 + voff[k / 9][hh]);
+    };
+    // unit u of the 3-way split of vraw into pv[slot] (k_igemm's split_unit): pair u / 2, first / second half
+    auto split_unit = [&](int slot, int u) __attribute__((always_inline)) {
+        const int e2 = u / 2, v = e2 / 2, e = 2 * (e2 % 2);
+        float lo = vraw[v][e], hi = vraw[v][e + 1];
+        const unsigned w = cvt_pk_bf16(lo, hi);
+        pv[slot][u % 2][e2] = w;
+        lo -= __builtin_bit_cast(float, w << 16);          // exact: the residual of a rounding to 8 bits fits fp32
+        hi -= __builtin_bit_cast(float, w & 0xffff0000u);
+        if (u % 2) pv[slot][2][e2] = cvt_pk_bf16(lo, hi);
+        else { vraw[v][e] = lo; vraw[v][e + 1] = hi; }
+    };
     __syncthreads();                                        // the tile table is visible
     // The input is read through a buffer resource: a tap outside the map (zero padding) or a tile beyond T gets an
     // offset past the end of the tensor, for which the hardware returns zeros -- no select, no branch.  (0x40000000 per
@@ -474,7 +533,9 @@ __global__ __launch_bounds__(256, 1) void k_wino_fused(const WinoFusedArgs a) {
 #pragma unroll
             for (int j = 0; j < 6; ++j) *reinterpret_cast<f32x4*>(vout + (i * 6 + j) * 256) = v[j];
             // the registers of the finished rows take this phase's first weight fragments
-            if (i >= 2) {
+            if constexpr (SPLIT) {
+                if (i >= 6 - NS) loadu3(i - (6 - NS), i - (6 - NS), up);
+            } else if (i >= 2) {
 #pragma unroll
                 for (int q = 0; q < 2; ++q)
 #pragma unroll
@@ -485,6 +546,40 @@ __global__ __launch_bounds__(256, 1) void k_wino_fused(const WinoFusedArgs a) {
         if (FFR_TRACE_ON(a.trace)) se[0] += __builtin_amdgcn_s_memtime() - tp0;       // diagnostics: transform (before the barrier)
         __syncthreads();
         if (FFR_TRACE_ON(a.trace)) se[1] += __builtin_amdgcn_s_memtime() - tp0;       // ... incl. the barrier
+        if constexpr (SPLIT) {
+        // -- 18 steps of 12 MFMAs; in their gaps, pinned: the V reads of the next step, the six weight loads of the slot the
+        // previous step consumed (one per gap), two patch values of the next phase (steps 10..17, in place of today's last K
+        // chunk), the split of the next step's V (one unit per gap)
+        readv(0);
+#pragma unroll
+        for (int u = 0; u < 8; ++u) split_unit(0, u);
+        FFR_PIN;
+#pragma unroll
+        for (int k = 0; k < 18; ++k) {
+            const int j = k % 9, cur = k & 1, slot = k % NS;
+#pragma unroll
+            for (int g = 0; g < 6 * NT; ++g) {
+                const int q = g / NT, nt = g % NT;
+                if (j < 8) acc[j][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fu3[slot][nt][PU[q]]),
+                                                                              __builtin_bit_cast(bf16x8, pv[cur][PV[q]]), acc[j][nt], 0, 0, 0);
+                // (s_nop: the operands may come from the vector instructions of the gap before, which the hazard recognizer
+                // cannot relate to an MFMA it does not see)
+                else asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(accv[nt]) : "v"(fu3[slot][nt][PU[q]]), "v"(pv[cur][PV[q]]));
+                if (g == 0) {
+                    if (k == 9) offsets();
+                    if (k < 17) readv(k + 1);
+                }
+                if (g >= 1 && g <= 3 * NT && k >= 1 && k - 1 + NS < 18) loadu3_one((k - 1) % NS, k - 1 + NS, g - 1, up);
+                if (k >= 10 && (g == 3 * NT + 1 || g == 3 * NT + 2)) {
+                    const int idx = 2 * (k - 10) + (g - 3 * NT - 1);
+                    pre[idx] = load_px(idx, soff_next);
+                }
+                if (k < 17 && g >= 4 && g < 12) split_unit(cur ^ 1, g - 4);
+                FFR_PIN;
+            }
+        }
+        up += 2u * 36u * (unsigned)WF_U3_STEP;
+        } else {
         reada(0, 0, 0);
         // -- 4 K chunks: 9 steps of 8 MFMAs; A fragment of the next step from LDS, weight fragments 8 steps ahead --
 #pragma unroll
@@ -517,6 +612,7 @@ __global__ __launch_bounds__(256, 1) void k_wino_fused(const WinoFusedArgs a) {
                 }
             }
             up += 36 * 2048u;
+        }
         }
         __syncthreads();                                    // everybody is done reading V before the next transform
     }
@@ -678,8 +774,8 @@ __global__ __launch_bounds__(256, 1) void k_wino_fused(const WinoFusedArgs a) {
 }
 
 hipError_t wino_fused_init() {
-    const void* fns[4] = {(const void*)k_wino_fused<0, 2>, (const void*)k_wino_fused<1, 2>,
-                          (const void*)k_wino_fused<0, 1>, (const void*)k_wino_fused<1, 1>};
+    const void* fns[5] = {(const void*)k_wino_fused<0, 2>, (const void*)k_wino_fused<1, 2>, (const void*)k_wino_fused<0, 1>,
+                          (const void*)k_wino_fused<1, 1>, (const void*)k_wino_fused<1, 2, true>};
     for (const void* f : fns) {
         hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, WF_LDS_BYTES);
         if (e != hipSuccess) return e;
@@ -708,11 +804,14 @@ hipError_t launch_wino_fused(WinoFusedArgs a, hipStream_t stream) {
     a.nbn = a.cout_pad / (a.half_n ? 32 : 64);
     const dim3 grid(wf_grid(a.mbn, a.nbn, a.map_v));
     if (a.Vc) {
+        if (a.U3) return hipErrorInvalidValue;                      // ... and only with the in-kernel transform
         if (a.half_n) hipLaunchKernelGGL((k_wino_fused<0, 1>), grid, dim3(256), WF_LDS_BYTES, stream, a);
         else hipLaunchKernelGGL((k_wino_fused<0, 2>), grid, dim3(256), WF_LDS_BYTES, stream, a);
     } else {
         if (!a.x || a.nkc % 4 || a.x_bytes == 0 || a.x_bytes > 0x40000000u) return hipErrorInvalidValue;
+        if (a.U3 && a.half_n) return hipErrorInvalidValue;         // the split-operand form has 32 x 64 blocks only
         if (a.half_n) hipLaunchKernelGGL((k_wino_fused<1, 1>), grid, dim3(256), WF_LDS_BYTES, stream, a);
+        else if (a.U3) hipLaunchKernelGGL((k_wino_fused<1, 2, true>), grid, dim3(256), WF_LDS_BYTES, stream, a);
         else hipLaunchKernelGGL((k_wino_fused<1, 2>), grid, dim3(256), WF_LDS_BYTES, stream, a);
     }
     return hipGetLastError();

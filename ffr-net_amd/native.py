@@ -30,7 +30,8 @@ class TensorDesc(C.Structure):
 class MemStats(C.Structure):
     _fields_ = [('encoder_weight_bytes', C.c_size_t), ('recnet_weight_bytes', C.c_size_t), ('mixed_tile_weight_bytes', C.c_size_t),
                 ('workspace_bytes', C.c_size_t), ('encoder_load_seconds', C.c_double), ('recnet_load_seconds', C.c_double),
-                ('mixed_tile_pack_seconds', C.c_double), ('split_weight_bytes', C.c_size_t)]
+                ('mixed_tile_pack_seconds', C.c_double), ('split_weight_bytes', C.c_size_t),
+                ('wf_split_weight_bytes', C.c_size_t), ('wf_split_launches', C.c_longlong)]
 
 
 class KClassStat(C.Structure):
@@ -112,6 +113,7 @@ SYMBOLS = [
     ('ffr_layer_set_arith', C.c_int, [_P, C.c_int, C.c_int]),
     ('ffr_calibrate', C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_double), _P]),
     ('ffr_memory_stats', C.c_int, [_P, _P]),
+    ('ffr_split_planes_host', C.c_int, [_P, C.c_longlong, _P]),
     ('ffr_set_option', C.c_int, [_P, C.c_char_p, C.c_longlong]),
     ('ffr_get_option', C.c_int, [_P, C.c_char_p, C.POINTER(C.c_longlong)]),
     ('ffr_probe_mfma_peak', C.c_int, [_P, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), _P]),

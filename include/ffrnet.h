@@ -269,6 +269,12 @@ int ffr_profile_enable(ffr_handle* h, int on);
  *   "combine_v" (1)       1: a bottleneck's combine (res * scale + shortcut) also writes the Winograd transform V of its
  *                         output when the next unit's conv1 runs k_wino_fused from V (stage 3 / 4): k_combine_in_c
  *                         replaces k_combine + k_wino_in_c
+ *   "wf_split" (1)        1: the k_wino_fused launches that transform their own input (cin <= wf_phased_maxk, 32 x 64 blocks: stages
+ *                         1-2) run their K loop in the split-operand form of "igemm_split" below: V is split into three bf16
+ *                         pieces in registers after the LDS read, G g G^T comes as three bf16 planes that ffr_load_* split from the
+ *                         double-precision fold (1.5 x the fp32 bytes of those layers, ffr_memory_stats: wf_split_weight_bytes; a
+ *                         device without room keeps the fp32 loop for the layer, logs once and does not fail).  0: every launch is
+ *                         the fp32-MFMA kernel, bit for bit.  The training path and raw-weight callers keep fp32.
  *   "igemm_split" (1)     1: the direct convolutions whose weights ffr_load_encoder split into three bf16 planes (the layers
  *                         that never run Winograd: 3x3 stride 2, the 1x1 shortcuts, and the output_layer GEMM) run k_igemm's
  *                         split-operand form: the same fp32 product as six exact bf16 x bf16 products per term on the bf16
@@ -332,13 +338,20 @@ int ffr_calibrate(ffr_handle* h, const float* x_nchw, const float* featmap_nchw,
  * `.to(device)`, models/trainer.py:98-113, which has no packing step).  mixed_tile_* are the three extra Winograd weight
  * sets of the exact 14x14 tiling: derived on the device the first time a batch large enough to use them arrives
  * (ffr_reserve / the first forward of >= 256 images), 0 before.  split_weight_bytes (part of encoder_weight_bytes) are
- * the bf16 planes of the split-operand form of k_igemm (option "igemm_split"), made by ffr_load_encoder.            */
+ * the bf16 planes of the split-operand form of k_igemm (option "igemm_split"), made by ffr_load_encoder;
+ * wf_split_weight_bytes (part of encoder_weight_bytes too) those of k_wino_fused's (option "wf_split"), and
+ * wf_split_launches counts the k_wino_fused launches that ran in that form since ffr_create (tests read the plan from it). */
 typedef struct ffr_mem_stats {
     size_t encoder_weight_bytes, recnet_weight_bytes, mixed_tile_weight_bytes, workspace_bytes;
     double encoder_load_seconds, recnet_load_seconds, mixed_tile_pack_seconds;
     size_t split_weight_bytes;
+    size_t wf_split_weight_bytes;
+    long long wf_split_launches;
 } ffr_mem_stats;
 int ffr_memory_stats(const ffr_handle* h, ffr_mem_stats* out);
+/* The packer's 3-way bf16 split of the split-operand forms, on the host (no device, no handle; tests): planes[p][i], p = 0..2,
+ * are the bf16 pieces (round to nearest even) of w[i]: p1 = bf16(w), p2 = bf16(w - p1), p3 = bf16(w - p1 - p2).       */
+int ffr_split_planes_host(const double* w, long long n, unsigned short* planes);
 /* fp32-MFMA rate this device delivers on a register-resident v_mfma_f32_32x32x2_f32 loop (iters x 16 MFMAs per
  * wave, 8 waves per CU) and the shader clock it holds meanwhile: the measured denominator of a roofline fraction. */
 int ffr_probe_mfma_peak(ffr_handle* h, int iters, double* tflops, double* clock_ghz, void* stream);
@@ -371,7 +384,8 @@ int ffr_op_conv(ffr_handle* h, const ffr_conv_desc* d, void* stream);
  * bias[cout], optional PReLU slope[cout]) on x[N,H,W,cin] NHWC (device, cin % 32 == 0), packed on
  * the fly.  use_wino: 0 = direct implicit GEMM, 1 = Winograd F(4x4,3x3) with GEMM and output transform in one kernel
  * (k_wino_fused; input transform inside it for cin <= 128), 2 = Winograd as transform kernels around a batched GEMM, 3 = k_wino_fused
- * with 32 x 32 blocks, 4 = the exact 4+4+3+3 tiling of a 14x14 map with 256 input channels (k_wino_fused_mixed).  Test hook
+ * with 32 x 32 blocks, 4 = the exact 4+4+3+3 tiling of a 14x14 map with 256 input channels (k_wino_fused_mixed), 5 = as 1 with the
+ * split-operand K loop (option "wf_split"; FFR_ERR_UNSUPPORTED for cin > wf_phased_maxk).  Test hook
  * that holds every path to torch's conv2d.  out[N,H,W,cout] NHWC device, cout % 4 == 0.         */
 int ffr_op_conv3x3(ffr_handle* h, const float* x_nhwc, int N, int H, int W, int cin,
                    const float* w_host, const float* bias_host, const float* slope_host, int cout,
