@@ -106,6 +106,7 @@ void ffr_destroy(ffr_handle* h) {
     if (h->arena) hipFree(h->arena);
     if (h->tickets) hipFree(h->tickets);
     if (h->search_buf) hipFree(h->search_buf);
+    if (h->cluster_buf) hipFree(h->cluster_buf);
     if (h->align_buf) hipFree(h->align_buf);
     if (h->zero) hipFree(h->zero);
     for (auto& r : h->prof_log) { hipEventDestroy(r.e0); hipEventDestroy(r.e1); }
@@ -305,6 +306,59 @@ int ffr_topk_merge(ffr_handle* h, const float* score, const int64_t* index, int 
     return FFR_OK;
 }
 
+// ---- clustering (cluster.hip) ----------------------------------------------------------------------------------------
+int ffr_cluster_threshold(ffr_handle* h, const float* emb, const float* norms, long long N, int dim, float threshold,
+                          int64_t* rep, void* stream) {
+    FFR_DEVICE_SCOPE(h); RC(check_fwd(h, false, false, 1));
+    if (dim != 512) return fail(h, FFR_ERR_UNSUPPORTED, "ffr_cluster_threshold: dim must be 512, got %d", dim);
+    if (N < 0 || N >= (1ll << 31)) return fail(h, FFR_ERR_ARG, "ffr_cluster_threshold: N must be in [0, 2^31), got %lld", N);
+    if (threshold != threshold) return fail(h, FFR_ERR_ARG, "ffr_cluster_threshold: the threshold is NaN");
+    if (N == 0) return FFR_OK;
+    if (!emb || !rep) return fail(h, FFR_ERR_ARG, "ffr_cluster_threshold: emb / rep is null");
+    if (misaligned16(emb) || ((uintptr_t)rep & 7) || ((uintptr_t)norms & 3))
+        return fail(h, FFR_ERR_ARG, "ffr_cluster_threshold: emb rows must be 16-byte aligned (rep 8, norms 4)");
+    int T = 0, S = 0;
+    long long chunk_rows = 0;
+    cluster_plan(N, h->num_cus, &T, &S, &chunk_rows);
+    if ((long long)T * S >= (1ll << 31))
+        return fail(h, FFR_ERR_UNSUPPORTED, "ffr_cluster_threshold: N = %lld needs %lld blocks, over the grid limit", N, (long long)T * S);
+    hipStream_t st = (hipStream_t)stream;
+    // scratch: row norms [N] (used when the caller passes none), then parent [N]
+    const size_t norm_bytes = ((size_t)N * 4 + 255) & ~(size_t)255;
+    const size_t need = norm_bytes + (size_t)N * 4;
+    if (need > h->cluster_bytes) {
+        if (h->cluster_buf) { hipDeviceSynchronize(); hipFree(h->cluster_buf); h->cluster_buf = nullptr; h->cluster_bytes = 0; }
+        void* p = nullptr;
+        if (hipMalloc(&p, need) != hipSuccess) return fail(h, FFR_ERR_NOMEM, "hipMalloc of %zu clustering bytes failed", need);
+        h->cluster_buf = (char*)p;
+        h->cluster_bytes = need;
+        ++h->generation;          // a graph captured around an earlier call points at the old scratch
+    }
+    float* own_norms = (float*)h->cluster_buf;
+    int* parent = (int*)(h->cluster_buf + norm_bytes);
+    Scope s(h, st, FFR_KC_SCORE, (double)N * (double)(N - 1) * dim, 2.0 * (double)N * (dim + 1) + 16.0 * N);
+    if (!norms) {
+        HIPCK(h, launch_row_norms(emb, N, own_norms, st));
+        norms = own_norms;
+    }
+    HIPCK(h, launch_cluster_threshold(emb, norms, N, threshold, T, S, chunk_rows, parent, rep, st));
+    return FFR_OK;
+}
+
+int ffr_cluster_templates(ffr_handle* h, const float* emb, const float* norms, const int64_t* order, const int64_t* offsets,
+                          long long C, int dim, float* templates, void* stream) {
+    FFR_DEVICE_SCOPE(h); RC(check_fwd(h, false, false, 1));
+    if (dim != 512) return fail(h, FFR_ERR_UNSUPPORTED, "ffr_cluster_templates: dim must be 512, got %d", dim);
+    if (C < 0 || C >= (1ll << 31)) return fail(h, FFR_ERR_ARG, "ffr_cluster_templates: C must be in [0, 2^31), got %lld", C);
+    if (C == 0) return FFR_OK;
+    if (!emb || !order || !offsets || !templates) return fail(h, FFR_ERR_ARG, "ffr_cluster_templates: a null pointer");
+    if (misaligned16(emb) || misaligned16(templates) || ((uintptr_t)order & 7) || ((uintptr_t)offsets & 7) || ((uintptr_t)norms & 3))
+        return fail(h, FFR_ERR_ARG, "ffr_cluster_templates: emb and templates rows must be 16-byte aligned (order, offsets 8, norms 4)");
+    hipStream_t st = (hipStream_t)stream;
+    Scope s(h, st, FFR_KC_SCORE, 0.0, 4.0 * (double)C * dim);
+    HIPCK(h, launch_cluster_templates(emb, norms, order, offsets, C, templates, st));
+    return FFR_OK;
+}
 
 // ---- face alignment (align.hip) --------------------------------------------------------------------------------------
 static int align_tfm_check(ffr_handle* h, const float* landmarks, const float* tmpl, int K) {

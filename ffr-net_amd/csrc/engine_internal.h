@@ -128,6 +128,9 @@ struct ffr_handle {
     // 1:N search scratch (ffr_search_topk): probe norms + per-chunk top-k lists; grows on demand
     char* search_buf = nullptr;
     size_t search_bytes = 0;
+    // clustering scratch (ffr_cluster_threshold): row norms [N] + union-find parent [N] int32; grows on demand
+    char* cluster_buf = nullptr;
+    size_t cluster_bytes = 0;
     // alignment scratch (ffr_embed_aligned): transforms [N][6] fp64, valid flags [N], crops [N][112][112][3]; grows on demand
     char* align_buf = nullptr;
     size_t align_bytes = 0;

@@ -215,6 +215,17 @@ hipError_t launch_search_topk(const float* query, const float* qnorm, int Q, con
 hipError_t launch_topk_merge(const float* score, const int64_t* index, int S, int Q, int k, float* out_s, int64_t* out_i,
                              hipStream_t stream);
 
+// ---- clustering (cluster.hip) ----------------------------------------------------------
+// chunking of the self-join: probe tiles x row chunks, sized for the blocks on and above the diagonal; N >= 1
+void cluster_plan(long long N, int num_cus, int* ntiles, int* nchunks, long long* chunk_rows);
+// rep[i] = smallest row of i's component under the edges s(i, j) > threshold, i < j (three launches: init, join, flatten);
+// parent: N ints of scratch; norms = launch_row_norms(emb); N < 2^31, nchunks * ntiles < 2^31, rows 16-byte aligned
+hipError_t launch_cluster_threshold(const float* emb, const float* norms, long long N, float threshold, int ntiles, int nchunks,
+                                    long long chunk_rows, int* parent, int64_t* rep, hipStream_t stream);
+// templates[c] = normalised sum of the normalised rows order[offsets[c] .. offsets[c+1]); norms may be null
+hipError_t launch_cluster_templates(const float* emb, const float* norms, const int64_t* order, const int64_t* offsets,
+                                    long long C, float* templates, hipStream_t stream);
+
 // ---- face alignment (align.hip) --------------------------------------------------------
 // landmarks[N][K][2], tmpl[K][2] fp32 -> A[N][6] fp64 (row-major 2x3, crop -> frame), valid[N]; 2 <= K <= 16; with a
 // frame_index[N] (may be null) a face whose frame is outside [0,F) is invalid too

@@ -101,6 +101,8 @@ SYMBOLS = [
     ('ffr_row_norms', C.c_int, [_P, _P, C.c_longlong, C.c_int, _P, _P]),
     ('ffr_search_topk', C.c_int, [_P, _P, C.c_int, _P, _P, C.c_longlong, C.c_int, C.c_int, C.c_longlong, _P, _P, _P]),
     ('ffr_topk_merge', C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    ('ffr_cluster_threshold', C.c_int, [_P, _P, _P, C.c_longlong, C.c_int, C.c_float, _P, _P]),
+    ('ffr_cluster_templates', C.c_int, [_P, _P, _P, _P, _P, C.c_longlong, C.c_int, _P, _P]),
     ('ffr_align_transforms', C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, _P]),
     ('ffr_align_warp', C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_longlong, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
     ('ffr_embed_aligned', C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_longlong, _P, _P, _P, C.c_int, _P, C.c_int, _P, _P, _P,
@@ -474,6 +476,61 @@ class Engine(object):
             self._ck(self.lib.ffr_topk_merge(self._h, _ptr(scores), _ptr(index), S, Q, k, _ptr(out_s), _ptr(out_i),
                                              self._stream()))
         return out_s, out_i
+
+    # -- clustering (include/ffrnet.h: ffr_cluster_threshold, ffr_cluster_templates) -----------------------------------
+    def _cluster_rows(self, emb, norms, who):
+        _check_dev(emb, 'emb', device=self.device)
+        if emb.dim() != 2:
+            raise RuntimeError('ffrnet_amd: %s expects emb [N,dim], got %s' % (who, list(emb.shape)))
+        emb = emb.contiguous()
+        if norms is not None:
+            _check_dev(norms, 'norms', device=self.device)
+            if tuple(norms.shape) != (emb.size(0),):
+                raise RuntimeError('ffrnet_amd: norms must be [%d], got %s' % (emb.size(0), list(norms.shape)))
+            norms = norms.contiguous()
+        return emb, norms
+
+    def _index_tensor(self, t, name):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device.index != self.device.index:
+            raise RuntimeError('ffrnet_amd: %s must be a tensor on %s' % (name, self.device))
+        if t.dtype != torch.int64 or t.dim() != 1:
+            raise RuntimeError('ffrnet_amd: %s must be a 1-d int64 tensor, got %s %s' % (name, t.dtype, list(t.shape)))
+        return t.contiguous()
+
+    def cluster(self, emb, threshold, norms=None):
+        """Single-link clustering of emb[N,512] (device fp32) at one cosine threshold: rows i < j are joined iff their
+        search score is > threshold -> rep[N] int64, rep[i] = the smallest row index of i's cluster.  norms[N]:
+        row_norms(emb), computed in the call when not given."""
+        emb, norms = self._cluster_rows(emb, norms, 'cluster')
+        N = emb.size(0)
+        rep = torch.empty((N,), device=emb.device, dtype=torch.int64)
+        with torch.cuda.device(self.device):
+            self._ck(self.lib.ffr_cluster_threshold(self._h, _ptr(emb if N else None), _ptr(norms), N, emb.size(1),
+                                                    float(threshold), _ptr(rep), self._stream()))
+        return rep
+
+    def cluster_templates(self, emb, order, offsets, norms=None, validate=True):
+        """One template per cluster: order (int64, rows of emb sorted by cluster then index) and offsets[C+1] (int64,
+        ascending) -> templates[C,512], row c = the normalised sum of the normalised rows order[offsets[c]:offsets[c+1]].
+        The kernel trusts both; `validate` range-checks them here first (one small sync)."""
+        emb, norms = self._cluster_rows(emb, norms, 'cluster_templates')
+        order, offsets = self._index_tensor(order, 'order'), self._index_tensor(offsets, 'offsets')
+        if offsets.numel() < 1:
+            raise RuntimeError('ffrnet_amd: offsets must hold C + 1 entries')
+        Cn = offsets.numel() - 1
+        if validate and Cn:
+            d = offsets[1:] - offsets[:-1]
+            bad = bool(((offsets[0] < 0) | (d.min() < 0) | (offsets[-1] > order.numel())).item())
+            if not bad and order.numel():
+                bad = bool(((order.min() < 0) | (order.max() >= emb.size(0))).item())
+            if bad:
+                raise RuntimeError('ffrnet_amd: cluster_templates needs 0 <= order < %d and ascending offsets within '
+                                   '[0, %d]' % (emb.size(0), order.numel()))
+        out = torch.empty((Cn, emb.size(1)), device=emb.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            self._ck(self.lib.ffr_cluster_templates(self._h, _ptr(emb if emb.size(0) else None), _ptr(norms), _ptr(order),
+                                                    _ptr(offsets), Cn, emb.size(1), _ptr(out), self._stream()))
+        return out
 
     # -- face alignment (include/ffrnet.h: ffr_align_transforms, ffr_align_warp, ffr_embed_aligned) -------------------
     def _align_points(self, landmarks, template):

@@ -140,6 +140,40 @@ int ffr_search_topk(ffr_handle* h, const float* query, int Q, const float* galle
 int ffr_topk_merge(ffr_handle* h, const float* score, const int64_t* index, int S, int Q, int k,
                    float* out_score, int64_t* out_index, void* stream);
 
+/* ---- clustering (unlabelled embeddings -> identities -> one template per identity) ----------------------------------
+ * The step in front of enrolment: N unlabelled faces are grouped by single-link clustering at one cosine threshold, and
+ * each group is fused into one template row.  The N x N scores never leave the chip; the output is one label per row.
+ *   edge   rows i < j are joined iff s(probe = i, gallery row = j) > threshold -- the strict > of the verification
+ *          protocol -- with s exactly the fp32 score ffr_search_topk gives for probe i and gallery row j (bit for bit).
+ *          The diagonal and i > j are never evaluated.  A zero row scores 0 against everything: it stays alone for any
+ *          threshold >= 0.  Clusters are the connected components of the edges (transitive closure).
+ *   result rep[N] int64: rep[i] = the SMALLEST row index of i's cluster (so rep[i] <= i, rep[rep[i]] == rep[i], and two rows
+ *          share a cluster iff their rep is equal).  The result does not depend on the order in which the device meets
+ *          the edges: repeated calls are bitwise equal.
+ *   how    a lock-free union-find over parent[N] in the handle's scratch: find walks parent[] to a root; two different
+ *          roots are united by atomicCAS(&parent[larger], larger, smaller); on failure the walk continues from the value
+ *          the CAS returned.  Termination: parent[x] <= x holds at every instant (a root is only ever re-pointed to a
+ *          smaller index), so every walk strictly descends and ends within N hops whatever other waves do, and the larger
+ *          root of a retried union strictly decreases: no lock, no spinning, no wait on another wave.  Only roots are
+ *          hooked, always under a smaller index, so each finished cluster has one root, its smallest row.
+ *   shapes dim = 512 only (FFR_ERR_UNSUPPORTED otherwise).  FFR_ERR_ARG: N < 0 or N >= 2^31, a NaN threshold, a null emb or
+ *          rep, emb not 16-byte aligned.  norms[N] = ffr_row_norms(emb), or NULL: computed into the scratch.  N = 0 (and
+ *          C = 0 below) succeeds and touches nothing.
+ *   memory no host synchronisation; the scratch (norms, parent) grows on demand -- hipMalloc on the first call at a larger
+ *          N, which bumps ffr_generation -- so a call can be captured into a hipGraph once it has run at that N.
+ *   NaN    rows holding NaN or inf give unspecified (in-bounds) labels.
+ * No weights need to be loaded.  Profiled under FFR_KC_SCORE; a clustering counts flops = N*(N-1)*512.               */
+int ffr_cluster_threshold(ffr_handle* h, const float* emb, const float* norms, long long N, int dim, float threshold,
+                          int64_t* rep, void* stream);
+/* One template per cluster: templates[c] = t / |t| with t = sum over r of emb[r] / |emb[r]|, r running through
+ * order[offsets[c]] .. order[offsets[c+1] - 1] in that sequence (sequential fp32 per component: deterministic, bitwise
+ * repeatable).  A zero row contributes zero; an all-zero sum gives a zero template.  order[] holds row indices of emb
+ * (int64; for a clustering: the rows sorted by cluster, then by index), offsets[C + 1] is ascending (int64); both are
+ * trusted, the caller keeps them in bounds.  norms: ffr_row_norms(emb) or NULL (computed per row, the same values).
+ * templates[C][dim] fp32, 16-byte aligned.  Errors as above (C in place of N).                                        */
+int ffr_cluster_templates(ffr_handle* h, const float* emb, const float* norms, const int64_t* order, const int64_t* offsets,
+                          long long C, int dim, float* templates, void* stream);
+
 /* ---- face alignment (landmarks -> similarity transform -> aligned uint8 crop) ---------------------------------------
  * Replaces the reference's host preprocessing, lfw/gen_lfw112x96.py:6-17 (align) with lfw/matlab_cp2tform.py
  * (get_similarity_transform_for_cv2) in front of cv2.warpAffine: frames and detector landmarks already on the device
