@@ -39,6 +39,7 @@
 
 #include <cmath>
 
+#include "device_util.h"
 #include "ffr_kernels.h"
 
 namespace ffr {

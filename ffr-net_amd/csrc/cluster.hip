@@ -8,9 +8,8 @@
 //
 // k_cluster_init     parent[x] = x.
 // k_cluster_join     the hot path: the self-join of the [N][512] array with itself.
-//  - K loop: the K loop of k_search_topk, copied unchanged (32 probes x 128 rows per block step, v_mfma_f32_32x32x2_f32,
-//    operands in the same lane permutation, 8 accumulator chains added in the same fixed tree, acc / (qn*gn + 1e-8f)).
-//    Keep the two loops textually identical: the tests compare the edge set with the scores of ffr_search_topk bitwise.
+//  - K loop: the 32 x 128 cosine tile of cosine_tile.h, the one k_search_topk instantiates: the bitwise identity of the edge
+//    scores with the scores of ffr_search_topk is structural.
 //  - Triangle: a block is (chunk of rows, tile of 32 probes), logical id as in the search.  A block whose chunk ends at
 //    or before its tile's first probe has no pair i < j and exits at once; the others start at the first 128-row step
 //    that can hold a row greater than the tile's smallest probe.  The grid is the chunks x tiles rectangle (cluster_plan
@@ -46,30 +45,13 @@
 
 #include <algorithm>
 
+#include "cosine_tile.h"
+#include "device_util.h"
 #include "ffr_kernels.h"
 
 namespace ffr {
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-// the tile constants of search.hip
-constexpr int CL_DIM = 512;
-constexpr int CL_QT = 32;                 // probes per block
-constexpr int CL_WAVES = 4;
-constexpr int CL_STEP = 32 * CL_WAVES;    // rows per block step
-constexpr int CL_NG = CL_DIM / 8;         // 16-byte groups per lane and row half: 64
-constexpr int CL_PF = 16;                 // groups of the row operand in flight
-constexpr int CL_NACC = 8;                // accumulators per tile: group j feeds chain j % 8
-constexpr long long CL_MAX_CHUNK = 1 << 20;   // rows: 2^29 floats, a 32-bit element offset
-
-__device__ __forceinline__ float wave_sum64(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 __device__ __forceinline__ int uf_load(const int* parent, int x) {
     return __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -113,96 +95,61 @@ struct JoinArgs {
     const float* norm;        // [N]
     int* parent;              // [N]
     long long N;
-    long long chunk_rows;     // rows per chunk (the last one may be shorter), a multiple of CL_STEP, <= CL_MAX_CHUNK
+    long long chunk_rows;     // rows per chunk (the last one may be shorter), a multiple of CT_STEP, <= CT_MAX_CHUNK
     float threshold;
     int nchunks, ntiles;
 };
 
 __global__ __launch_bounds__(256, 1) void k_cluster_join(const JoinArgs a) {
-    __shared__ __attribute__((aligned(16))) f32x4 qf[CL_NG * 64];    // probe fragments [64][64]
+    __shared__ __attribute__((aligned(16))) f32x4 qf[CT_NG * 64];    // probe fragments [64][64]
 
     const int tid = threadIdx.x, lane = tid & 63, n = lane & 31, h = lane >> 5;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-    // XCD-grouped logical block id (bijective for any grid), chunk-major: as k_search_topk
-    const int nb = gridDim.x, b = blockIdx.x, xcd = b & 7, loc = b >> 3, qq = nb >> 3, rr = nb & 7;
-    const int lid = xcd < rr ? xcd * (qq + 1) + loc : rr * (qq + 1) + (xcd - rr) * qq + loc;
-    const int chunk = lid / a.ntiles, tile = lid - chunk * a.ntiles;
+    int chunk, tile;
+    cosine_block(a.ntiles, chunk, tile);
     const long long c0 = (long long)chunk * a.chunk_rows;
     const long long rem = a.N - c0;
     const int rows = (int)(rem < a.chunk_rows ? rem : a.chunk_rows);    // >= 1
-    const int q0 = tile * CL_QT;
+    const int q0 = tile * CT_QT;
     if (c0 + rows <= (long long)q0 + 1) return;        // no row of this chunk is greater than the tile's smallest probe
-    const int nq = min(CL_QT, (int)(a.N - q0));
+    const int nq = min(CT_QT, (int)(a.N - q0));
     // the first step that can hold row q0 + 1
-    const int step0 = (long long)q0 + 1 > c0 ? (int)(((long long)q0 + 1 - c0) / CL_STEP) : 0;
+    const int step0 = (long long)q0 + 1 > c0 ? (int)(((long long)q0 + 1 - c0) / CT_STEP) : 0;
 
-    // probe tile in fragment order: qf[j*64 + l] = q[q0 + (l&31)][8j + 4(l>>5) .. +3]
-    for (int e = tid; e < CL_NG * 64; e += 256) {
-        const int j = e >> 6, l = e & 63, qn = l & 31;
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (qn < nq) v = *(const f32x4*)(a.emb + (size_t)(q0 + qn) * CL_DIM + 8 * j + 4 * (l >> 5));
-        qf[e] = v;
-    }
+    cosine_fill_probes(qf, a.emb, q0, nq, tid);
     const float qn_lane = n < nq ? a.norm[q0 + n] : 0.f;
     const int irow = q0 + n;                            // this lane's probe row (an edge needs n < nq)
 
-    // 64-bit chunk base, 32-bit element offsets inside it
-    const float* __restrict__ gch = a.emb + (size_t)c0 * CL_DIM;
     const float* __restrict__ nch = a.norm + c0;
-    const unsigned lane_off = 4u * h;
-    int row = min(step0 * CL_STEP + w * 32 + n, rows - 1);
-    f32x4 pf[CL_PF];
-#pragma unroll
-    for (int u = 0; u < CL_PF; ++u) pf[u] = *(const f32x4*)(gch + ((unsigned)row * CL_DIM + 8u * u + lane_off));
+    CosineStream gs(a.emb + (size_t)c0 * CT_DIM, lane);
+    gs.prime(min(step0 * CT_STEP + w * 32 + n, rows - 1));
     __syncthreads();
 
-    const int nsteps = (rows + CL_STEP - 1) / CL_STEP;
+    const int nsteps = (rows + CT_STEP - 1) / CT_STEP;
     for (int step = step0; step < nsteps; ++step) {
-        const int sbase = step * CL_STEP;
-        const int next = min(row + CL_STEP, rows - 1);
-        // norms of the 16 rows this lane scores, fetched ahead of the K loop
+        const int sbase = step * CT_STEP;
+        const int next = min(gs.row + CT_STEP, rows - 1);
+        // gallery norms of the 16 rows this lane scores, fetched ahead of the K loop
         float gn[16];
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int gr = min(sbase + w * 32 + (r & 3) + 8 * (r >> 2) + 4 * h, rows - 1);
-            gn[r] = nch[(unsigned)gr];
-        }
-        f32x16 acc8[CL_NACC];
-#pragma unroll
-        for (int u = 0; u < CL_NACC; ++u) acc8[u] = f32x16{};
-        f32x4 bq = qf[lane];
-#pragma unroll
-        for (int j = 0; j < CL_NG; ++j) {
-            const f32x4 av = pf[j % CL_PF];
-            const int jn = j + CL_PF;          // refill the slot: this tile's group jn, or the next tile's group jn - 64
-            if (jn < CL_NG) pf[j % CL_PF] = *(const f32x4*)(gch + ((unsigned)row * CL_DIM + 8u * jn + lane_off));
-            else pf[j % CL_PF] = *(const f32x4*)(gch + ((unsigned)next * CL_DIM + 8u * (jn - CL_NG) + lane_off));
-            const f32x4 bv = bq;
-            if (j + 1 < CL_NG) bq = qf[(j + 1) * 64 + lane];
-            f32x16& acc = acc8[j % CL_NACC];
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bv.x, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bv.y, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, bv.z, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bv.w, acc, 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);     // keep each refill CL_PF groups ahead of its use (hipcc sinks it otherwise)
-        }
-        row = next;
-        // the 8 partial chains in a fixed tree
-        const f32x16 acc = ((acc8[0] + acc8[1]) + (acc8[2] + acc8[3])) + ((acc8[4] + acc8[5]) + (acc8[6] + acc8[7]));
+        for (int r = 0; r < 16; ++r) gn[r] = nch[(unsigned)min(acc_row(sbase + w * 32, r) + 4 * h, rows - 1)];
+        f32x16 acc8[CT_NACC];
+        gs.tile(acc8, qf, next);
+        const f32x16 acc = COSINE_CHAIN_SUM(acc8);
 
         // epilogue: scores, edge test (i < j inside the chunk, score > threshold), union
         unsigned mask = 0;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int lr = w * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;        // row within the step
-            const float sc = acc[r] / (qn_lane * gn[r] + 1e-8f);
+            const int lr = cosine_lane_row(w, r, h);
+            const float sc = cosine_score(acc[r], qn_lane, gn[r]);
             if (n < nq && sbase + lr < rows && c0 + sbase + lr > (long long)irow && sc > a.threshold) mask |= 1u << r;
         }
         while (mask) {
             const int r = __builtin_ctz(mask);
             mask &= mask - 1;
-            const int jrow = (int)(c0 + sbase + w * 32 + (r & 3) + 8 * (r >> 2) + 4 * h);      // < N < 2^31
+            const int jrow = (int)(c0 + sbase + cosine_lane_row(w, r, h));      // < N < 2^31
             uf_unite(a.parent, irow, jrow);
         }
     }
@@ -224,17 +171,17 @@ __global__ __launch_bounds__(256) void k_cluster_templates(const TemplateArgs a)
     const long long lo = a.offsets[c], hi = a.offsets[c + 1];
     f32x4 t0 = {0.f, 0.f, 0.f, 0.f}, t1 = {0.f, 0.f, 0.f, 0.f};
     for (long long e = lo; e < hi; ++e) {
-        const float* p = a.emb + (size_t)a.order[e] * CL_DIM;
+        const float* p = a.emb + (size_t)a.order[e] * CT_DIM;
         float nr;
         if (a.norm) {
             nr = a.norm[a.order[e]];
         } else {                         // |x_r| in the summation order of k_row_norms
             float aa = 0.f;
-            for (int k = lane; k < CL_DIM; k += 64) {
+            for (int k = lane; k < CT_DIM; k += 64) {
                 const float v = p[k];
                 aa += v * v;
             }
-            nr = sqrtf(wave_sum64(aa));
+            nr = sqrtf(wave_sum(aa));
         }
         if (!(nr > 0.f)) continue;       // a zero row contributes zero
         const f32x4 x0 = *(const f32x4*)(p + 8 * lane), x1 = *(const f32x4*)(p + 8 * lane + 4);
@@ -246,12 +193,12 @@ __global__ __launch_bounds__(256) void k_cluster_templates(const TemplateArgs a)
     for (int k = 0; k < 4; ++k) ss += t0[k] * t0[k];
 #pragma unroll
     for (int k = 0; k < 4; ++k) ss += t1[k] * t1[k];
-    const float tn = sqrtf(wave_sum64(ss));
+    const float tn = sqrtf(wave_sum(ss));
     if (tn > 0.f) {
         t0 /= tn;
         t1 /= tn;
     }
-    float* o = a.out + (size_t)c * CL_DIM + 8 * lane;
+    float* o = a.out + (size_t)c * CT_DIM + 8 * lane;
     *(f32x4*)o = t0;
     *(f32x4*)(o + 4) = t1;
 }
@@ -261,15 +208,8 @@ __global__ __launch_bounds__(256) void k_cluster_templates(const TemplateArgs a)
 // The search balances a rectangle; here only the blocks on and above the diagonal work, about half of chunks x tiles, and
 // the ones on the diagonal less than the others: aim at 4 working blocks per CU so that the uneven ones even out.
 void cluster_plan(long long N, int num_cus, int* ntiles, int* nchunks, long long* chunk_rows) {
-    const long long T = (N + CL_QT - 1) / CL_QT;
-    long long S = (8LL * num_cus + T - 1) / T;
-    S = std::max(S, (N + CL_MAX_CHUNK - 1) / CL_MAX_CHUNK);
-    S = std::max(1LL, std::min(S, (N + CL_STEP - 1) / CL_STEP));       // at least one step of rows per chunk
-    long long cr = (N + S - 1) / S;
-    cr = std::min(CL_MAX_CHUNK, (cr + CL_STEP - 1) / CL_STEP * CL_STEP);
-    *ntiles = (int)T;
-    *nchunks = (int)((N + cr - 1) / cr);
-    *chunk_rows = cr;
+    *ntiles = (int)((N + CT_QT - 1) / CT_QT);
+    cosine_chunks(*ntiles, N, 8, num_cus, nchunks, chunk_rows);
 }
 
 hipError_t launch_cluster_threshold(const float* emb, const float* norms, long long N, float threshold, int ntiles, int nchunks,

@@ -1,18 +1,10 @@
 // Trunk kernels that are not GEMMs: stem conv, squeeze-excitation, residual combine,
 // head finish, layout changes, cosine score.  All HBM/latency bound; 64-wide waves,
 // 16-byte accesses, wave-level shuffles for the reductions.
+#include "device_util.h"
 #include "ffr_kernels.h"
 
 namespace ffr {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 // ---------------------------------------------------------------------------------------
 // Stem: Conv3x3(3->64, pad 1, no bias) + BN + PReLU   (pretrain/model_ir_se50.py:118-120)
@@ -150,7 +142,7 @@ __global__ __launch_bounds__(256) void k_stem(const float* __restrict__ x, const
         for (int r = 0; r < 16; ++r) {
             float v = acc[r] + b;
             v = v >= 0.f ? v : v * sl;
-            tw_[((r & 3) + 8 * (r >> 2) + 4 * half) * STEM_TLD + (lane & 31)] = v;
+            tw_[(acc_row(0, r) + 4 * half) * STEM_TLD + (lane & 31)] = v;
         }
         // same wave wrote and reads: no workgroup barrier, the LDS executes a wave's operations in order (the compiler is told not to
         // move the reads over the writes)

@@ -15,14 +15,6 @@
 
 namespace ffr {
 
-// two bf16 (round to nearest even) of two floats in one register: lo in bits 0-15 (the split-operand forms of k_igemm and
-// k_wino_fused)
-__device__ __forceinline__ unsigned cvt_pk_bf16(float lo, float hi) {
-    unsigned r;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-    return r;
-}
-
 // ---- implicit-GEMM convolution (igemm.hip) -----------------------------------------
 // out[m][n] = epilogue( sum_k A[m][k] * Wp[n][k] ),  m = (img, ho, wo), k = (r, s, ci)
 struct IgemmArgs {

@@ -10,15 +10,10 @@
 // fetched and its fragments are read under the last K-tile of the current one, and a finished
 // accumulator tile is copied out of the accumulation registers and stored straight from registers
 // (128-byte pieces) while the next tile multiplies.  No bias / activation: plain store.
+#include "device_util.h"
 #include "ffr_kernels.h"
 
 namespace ffr {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-#define LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
-#define GLB_PTR(p) ((const __attribute__((address_space(1))) void*)(p))
 
 template <int BM, int BN, int WARPS_M, int WARPS_N>
 __global__ __launch_bounds__(256, (BM * BN >= 128 * 128 ? 2 : 3)) void k_gemm_stream(const GemmStreamArgs a) {
@@ -94,7 +89,6 @@ __global__ __launch_bounds__(256, (BM * BN >= 128 * 128 ? 2 : 3)) void k_gemm_st
 
     f32x16 acc[TM][TN];
     f32x4 af[2][TM], bf[2][TN];
-#define FFR_PIN __builtin_amdgcn_sched_barrier(0)
     auto read_piece = [&](int slot, const float* stage, int pcv, int r) {
         if (r < TM) af[slot][r] = *reinterpret_cast<const f32x4*>(stage + fragA + r * 32 * 32 + pcv);
         else bf[slot][r - TM] = *reinterpret_cast<const f32x4*>(stage + fragB + (r - TM) * 32 * 32 + pcv);
@@ -162,7 +156,7 @@ __global__ __launch_bounds__(256, (BM * BN >= 128 * 128 ? 2 : 3)) void k_gemm_st
         for (int i = 0; i < TM; ++i)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int mlr = i * 32 + (r & 3) + 8 * (r >> 2);
+                const int mlr = acc_row(i * 32, r);
                 if (mrow_cur + mlr < a.M) {
 #pragma unroll
                     for (int j = 0; j < TN; ++j) {
@@ -171,7 +165,6 @@ __global__ __launch_bounds__(256, (BM * BN >= 128 * 128 ? 2 : 3)) void k_gemm_st
                 }
             }
     }
-#undef FFR_PIN
 }
 
 static size_t gs_lds_bytes(int bm, int bn) { return (size_t)2 * (bm + bn) * 32 * 4; }

@@ -22,19 +22,12 @@
 // * Epilogue in registers: bias (optionally one of 9 border classes, for the BN that
 //   precedes a zero-padded conv), PReLU, residual add, sigmoid; NHWC store with pitch /
 //   channel offset so concatenations are just addressing.
+#include "device_util.h"
 #include "ffr_kernels.h"
 
 #include <utility>
 
 namespace ffr {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-#define LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
-#define GLB_PTR(p) ((const __attribute__((address_space(1))) void*)(p))
 
 // SPLIT (split-operand form): the same fp32 product on v_mfma_f32_32x32x16_bf16.  Every fp32 value is the sum
 // of three bf16 pieces (a1 = bf16(a), a2 = bf16(a - a1), a3 = bf16(a - a1 - a2)); the six products ai*bj with i + j <= 4, each
@@ -216,7 +209,6 @@ __global__ __launch_bounds__(256) void k_igemm(const IgemmArgs a) {
     const int fragA = (wm * WM + frow) * 32, fragB = (BM + wn * WN + frow) * 32;
 
     constexpr int ND = A_PT + B_PT;          // DMA pieces per K-tile
-#define FFR_PIN __builtin_amdgcn_sched_barrier(0)
     if constexpr (SPLIT) {
         // K-tile = two K = 16 steps.  Per step and 32x32 tile six bf16 MFMAs (small products first); the fillers of a step, in
         // this order, spread evenly over its MFMA gaps and pinned: the fragment reads of the NEXT step (A: two fp32
@@ -257,12 +249,8 @@ __global__ __launch_bounds__(256) void k_igemm(const IgemmArgs a) {
         auto split_unit = [&](int slot, int u) __attribute__((always_inline)) {
             const int i = u / 8, e2 = (u / 2) % 4, v = e2 / 2, e = 2 * (e2 % 2);
             float lo = araw[i][v][e], hi = araw[i][v][e + 1];
-            const unsigned w = cvt_pk_bf16(lo, hi);
-            pa[slot][i][u % 2][e2] = w;
-            lo -= __builtin_bit_cast(float, w << 16);          // exact: the residual of a rounding to 8 bits fits fp32
-            hi -= __builtin_bit_cast(float, w & 0xffff0000u);
-            if (u % 2) pa[slot][i][2][e2] = cvt_pk_bf16(lo, hi);
-            else { araw[i][v][e] = lo; araw[i][v][e + 1] = hi; }
+            if (u % 2) { const u32x2 p = split_bf16_second(lo, hi); pa[slot][i][1][e2] = p.x; pa[slot][i][2][e2] = p.y; }
+            else { pa[slot][i][0][e2] = split_bf16_first(lo, hi); araw[i][v][e] = lo; araw[i][v][e + 1] = hi; }
         };
         // Step ST of a K-tile is spelled out at compile time, gap by gap (a `#pragma unroll` nest over steps, gaps and fillers
         // exceeds the unroller's size limit for the 128x128 tile before it folds, and the fragment arrays then live in scratch).
@@ -390,7 +378,6 @@ __global__ __launch_bounds__(256) void k_igemm(const IgemmArgs a) {
         __builtin_amdgcn_s_setprio(2);
         if (FFR_TRACE_ON(a.trace)) { const unsigned long long t = __builtin_amdgcn_s_memtime(); tr_acc[2] += t - tr_t; tr_t = t; }
     }
-#undef FFR_PIN
 
     // ---- epilogue: accumulators -> LDS (C tile, row stride BN+4) -> whole rows, 16 B per lane ----
     // (register-layout stores are 128-B pieces, one instruction per accumulator register: 64
@@ -405,7 +392,7 @@ __global__ __launch_bounds__(256) void k_igemm(const IgemmArgs a) {
     for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int ml = wm * WM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
+            const int ml = acc_row(wm * WM + i * 32, r) + 4 * fh;
 #pragma unroll
             for (int j = 0; j < TN; ++j) sC[ml * LDC + wn * WN + j * 32 + frow] = acc[i][j][r];
         }

@@ -1,6 +1,7 @@
 // libffrnet_hip.so: the weight packer -- ffr_load_encoder / ffr_load_recnet fold the BatchNorms (and the border-class biases)
 // into the convolution weights and lay them out for the kernels: direct, Winograd U, the K-chunk order of k_wino_fused; the
 // exact-tiling weight sets are derived on the device when a launch first needs them.  Host code only.
+#include "device_util.h"
 #include "engine_internal.h"
 
 using namespace ffr_eng;
@@ -531,7 +532,7 @@ int ffr_load_recnet(ffr_handle* h, const ffr_tensor_desc* t, int n) {
                 for (int ks = 0; ks < 16; ++ks)
                     w8a[((size_t)t * 64 + lane) * 16 + ks] = W8[(size_t)(32 * t + (lane & 31)) * 32 + 2 * ks + (lane >> 5)];
             for (int hh = 0; hh < 2; ++hh)
-                for (int r = 0; r < 16; ++r) b8a[((size_t)t * 2 + hh) * 16 + r] = b8[32 * t + (r & 3) + 8 * (r >> 2) + 4 * hh];
+                for (int r = 0; r < 16; ++r) b8a[((size_t)t * 2 + hh) * 16 + r] = b8[acc_row(32 * t, r) + 4 * hh];
         }
         RC(upload(h, own, w8a, &p)); cw.w8a = p;
         RC(upload(h, own, b8a, &p)); cw.b8a = p;

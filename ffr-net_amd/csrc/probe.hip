@@ -1,11 +1,10 @@
 // fp32-MFMA peak probe: the denominator of bench.py's roofline fraction, measured on the device it runs on.
 // MI355X holds its shader clock below the 2.4 GHz of the data sheet under matrix load (MI355X_MICROARCH.md, DVFS),
 // so the rate a perfect kernel could reach here is clock x 256 CUs x 256 FLOP/clk, not 157.3 TFLOP/s.
+#include "device_util.h"
 #include "ffr_kernels.h"
 
 namespace ffr {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 __global__ __launch_bounds__(256, 2) void k_mfma_probe(int iters, unsigned long long* stamps, float* sink) {
     // operands differ per lane and are not constants the compiler could fold

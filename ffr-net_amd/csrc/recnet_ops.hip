@@ -2,11 +2,10 @@
 // 372-386, 398-423): self-similarity, the channel-attention row-MLP fused with the
 // M_channel @ X product, the spatial rectification product, the 7x7 average pool.
 // One workgroup per image; X = featmap as [49 positions][512 channels] (NHWC).
+#include "device_util.h"
 #include "ffr_kernels.h"
 
 namespace ffr {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // ---------------------------------------------------------------------------------------
 // ss_space[i][j] = <X_i, X_j> / (max(|X_i|,1e-12) * max(|X_j|,1e-12))   (recnet.py:220-231)
@@ -139,7 +138,6 @@ __global__ __launch_bounds__(256, 1) void k_channel_path(const float* __restrict
     // through LDS, added in wave order.  (The scalar form -- 6 outputs per thread, 512 dependent-latency iterations of two LDS reads and
     // one L2 load each -- took ~90 of the kernel's 245 us.)
     {
-        typedef float f32x16 __attribute__((ext_vector_type(16)));
         const int pj = lane & 31, kh = lane >> 5;
         const int p_hi2 = (32 + pj) < 51 ? (32 + pj) : 51;         // XT[..][49..51] are zeros
         f32x16 g0, g1;
@@ -159,7 +157,7 @@ __global__ __launch_bounds__(256, 1) void k_channel_path(const float* __restrict
         float* Gp = G + 49 * 32 + wave * (64 * 32);                // [4 waves][64 positions][32]
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int j = (r & 3) + 8 * (r >> 2) + 4 * kh;
+            const int j = acc_row(0, r) + 4 * kh;
             Gp[pj * 32 + j] = g0[r];
             Gp[(32 + pj) * 32 + j] = g1[r];
         }
@@ -245,7 +243,6 @@ __global__ __launch_bounds__(256, 1) void k_channel_path(const float* __restrict
     //   fcT[p][c] += X[p][c'] * Mt[c'][c]                     2 x 16 MFMAs; the accumulator tile Mt IS the B operand:
     //       k-step r feeds register r (lanes 0-31 hold row (r&3)+8(r>>2), lanes 32-63 that row + 4), A = X^T from LDS
     // Wave w owns rows c in [row_base, row_base + 32 CT) = CT column tiles of the MFMA output.
-    typedef float f32x16 __attribute__((ext_vector_type(16)));
     const int mj = lane & 31, mh = lane >> 5;
     float HB[CT][16];
 #pragma unroll
@@ -285,7 +282,7 @@ __global__ __launch_bounds__(256, 1) void k_channel_path(const float* __restrict
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int cprow = cpt * 32 + (r & 3) + 8 * (r >> 2) + 4 * mh;
+            const int cprow = acc_row(cpt * 32, r) + 4 * mh;
             xa[0][r] = XT[cprow * XT_LD + p_lo];
             xa[1][r] = XT[cprow * XT_LD + p_hi];
         }
@@ -301,7 +298,7 @@ __global__ __launch_bounds__(256, 1) void k_channel_path(const float* __restrict
             if (dbg_M && n == 0) {      // parity tests only: M_channel[c][c'] of image 0, straight from the accumulator tile
 #pragma unroll
                 for (int r = 0; r < 16; ++r)
-                    dbg_M[(row_base + 32 * ct + mj) * 512 + cpt * 32 + (r & 3) + 8 * (r >> 2) + 4 * mh] = z[r];
+                    dbg_M[acc_row((row_base + 32 * ct + mj) * 512 + cpt * 32, r) + 4 * mh] = z[r];   // row0 = the flat offset of column cpt * 32
             }
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
@@ -320,7 +317,7 @@ __global__ __launch_bounds__(256, 1) void k_channel_path(const float* __restrict
         for (int pt = 0; pt < 2; ++pt)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int p = pt * 32 + (r & 3) + 8 * (r >> 2) + 4 * mh;
+                const int p = acc_row(pt * 32, r) + 4 * mh;
                 if (p < 49) {
                     const int pf = (p / 7) * 7 + (6 - p % 7);
                     Fn[p * pitchF + 512 + c] = fc[ct][pt][r];

@@ -3,11 +3,10 @@
 // the data-gradient convolution.  HBM-streaming kernels: lanes run along the channels (NHWC), 16-byte
 // accesses where the layout allows, per-channel sums in fp64 (slice partials, fixed combination order).
 // Reference: models/recnet.py:52-85 (ConvLayer), :119-147 (NormLayer = nn.BatchNorm2d), :87-117 (PReLU).
+#include "device_util.h"
 #include "train_kernels.h"
 
 namespace ffr {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // rows are cut into at most 32 slices per group (the *_final kernels walk the slices serially per channel)
 static int n_slices(int rows_g) {
@@ -862,12 +861,6 @@ hipError_t launch_mspace_grad_in(const float* dM, float* dms, int imgs, hipStrea
 
 // ---- CosFace head ------------------------------------------------------------------------------------
 // one wave per row of 512
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 __global__ __launch_bounds__(256) void k_row_normalize(const float* __restrict__ u, int u_pitch, float* __restrict__ v,
                                                       float* __restrict__ norm, int rows) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -1065,8 +1058,7 @@ hipError_t launch_loss_ch_prep(const float* feat, int pitch, int coff, float* Yh
 }
 
 __device__ __forceinline__ double block_sum_double(double v, double* sh) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    v = wave_sum(v);
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
     __syncthreads();
     double r = 0.0;
@@ -1160,8 +1152,7 @@ __global__ __launch_bounds__(256) void k_ss_space_loss(const float* __restrict__
         float s = 0.f;
 #pragma unroll
         for (int e = 0; e < 4; ++e) s += a[e] * a[e] + b[e] * b[e];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+        s = wave_sum(s);
         const float d = fmaxf(sqrtf(s), 1e-12f);
         *reinterpret_cast<f32x4*>(Zh + i * 516 + lane * 8) = a / d;
         *reinterpret_cast<f32x4*>(Zh + i * 516 + lane * 8 + 4) = b / d;
@@ -1194,8 +1185,7 @@ __global__ __launch_bounds__(256) void k_ss_space_loss(const float* __restrict__
         }
         const float z0 = Zh[i * 516 + tid], z1 = Zh[i * 516 + tid + 256];
         float dot = g0 * z0 + g1 * z1;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) dot += __shfl_xor(dot, o);
+        dot = wave_sum(dot);
         if (lane == 0) shf[wv] = dot;
         __syncthreads();
         dot = (shf[0] + shf[1]) + (shf[2] + shf[3]);

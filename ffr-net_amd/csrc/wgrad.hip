@@ -26,15 +26,10 @@
 //    resources: per-lane byte offset in one VGPR per DMA instruction, computed once; the K-tile advances the SCALAR offset
 //    (round 4 did the same for the operand streams of k_wino_fused; per-lane 64-bit pointers cost ~8 VALU instructions in
 //    front of every DMA, and every VALU instruction delays the wave's next MFMA by its issue time).
+#include "device_util.h"
 #include "train_kernels.h"
 
 namespace ffr {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-#define LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
-#define GLB_PTR(p) ((const __attribute__((address_space(1))) void*)(p))
 
 // BM x 128 output tile, BK = 32 rows per K-tile, 4 waves as 2 x 2
 // PLAIN: taps == 1 on plain rows (H = W = 1): the gather is a row pointer, no pixel arithmetic
@@ -225,7 +220,7 @@ __global__ __launch_bounds__(256, 2) void k_wgrad(const WgradArgs a) {
                 const int col = wn * WN + jj * 32 + (lane & 31);
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int row = wm * WM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * par;
+                    const int row = acc_row(wm * WM + i * 32, r) + 4 * par;
                     out[row * BN + col] = acc[i][jj][r];
                 }
             }
@@ -240,7 +235,7 @@ __global__ __launch_bounds__(256, 2) void k_wgrad(const WgradArgs a) {
             if (col < a.Ng) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int row = co0 + wm * WM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * par;
+                    const int row = acc_row(co0 + wm * WM + i * 32, r) + 4 * par;
                     out[(size_t)row * a.Ng + col] = acc[i][jj][r];
                 }
             }

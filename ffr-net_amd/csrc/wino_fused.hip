@@ -22,13 +22,11 @@
 // Epilogue: the 36 x 32 x 64 products of the block go through LDS in two passes of 32 channels (147 KB, which the K
 // loop does not use); a thread then owns (tile, 4 channels), applies A^T m A and the convolution epilogue and stores 16
 // bytes per pixel; a wave-store covers 8 tiles x 128 bytes.  DESIGN.md 3.1 states the design, EXPERIMENTS.md has the measurements behind each choice.
+#include "device_util.h"
 #include "ffr_kernels.h"
 #include "wino_math.h"
 
 namespace ffr {
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 // ---- input transform into the chunked operand order ---------------------------------------------------------
 // grid (mbn, cin_pad / 32); wave w of a block = K chunk 4*blockIdx.y + w of tile group blockIdx.x; lane = piece
@@ -353,7 +351,6 @@ __global__ __launch_bounds__(256, 1) void k_wino_fused(const WinoFusedArgs a) {
             for (int j = 0; j < 8; ++j) acc[j][nt][r] = 0.f;
         }
 
-#define FFR_PIN __builtin_amdgcn_sched_barrier(0)
     if constexpr (MODE == 0) {
     // fragment registers: slot j holds (V, U lo, U hi) of xi j for the K chunk that consumes it next
     f32x4 fv[9], fu[9][NT];
@@ -451,16 +448,12 @@ __global__ __launch_bounds__(256, 1) void k_wino_fused(const WinoFusedArgs a) {
 #pragma unroll
         for (int hh = 0; hh < 2; ++hh) vraw[hh] = *reinterpret_cast<const f32x4*>(smem + (9 * wave + k % 9) * 256 + voff[k / 9][hh]);
     };
-    // unit u of the 3-way split of vraw into pv[slot] (k_igemm's split_unit): pair u / 2, first / second half
+    // unit u of the 3-way split of vraw into pv[slot] (split_bf16_first / split_bf16_second of device_util.h): pair u / 2, first / second half
     auto split_unit = [&](int slot, int u) __attribute__((always_inline)) {
         const int e2 = u / 2, v = e2 / 2, e = 2 * (e2 % 2);
         float lo = vraw[v][e], hi = vraw[v][e + 1];
-        const unsigned w = cvt_pk_bf16(lo, hi);
-        pv[slot][u % 2][e2] = w;
-        lo -= __builtin_bit_cast(float, w << 16);          // exact: the residual of a rounding to 8 bits fits fp32
-        hi -= __builtin_bit_cast(float, w & 0xffff0000u);
-        if (u % 2) pv[slot][2][e2] = cvt_pk_bf16(lo, hi);
-        else { vraw[v][e] = lo; vraw[v][e + 1] = hi; }
+        if (u % 2) { const u32x2 p = split_bf16_second(lo, hi); pv[slot][1][e2] = p.x; pv[slot][2][e2] = p.y; }
+        else { pv[slot][0][e2] = split_bf16_first(lo, hi); vraw[v][e] = lo; vraw[v][e + 1] = hi; }
     };
     __syncthreads();                                        // the tile table is visible
     // The input is read through a buffer resource: a tap outside the map (zero padding) or a tile beyond T gets an
@@ -617,7 +610,6 @@ __global__ __launch_bounds__(256, 1) void k_wino_fused(const WinoFusedArgs a) {
         __syncthreads();                                    // everybody is done reading V before the next transform
     }
     }
-#undef FFR_PIN
     if (FFR_TRACE_ON(a.trace)) st2 = __builtin_amdgcn_s_memtime();
 
     // ---- epilogue ----------------------------------------------------------------------------------------
@@ -661,12 +653,12 @@ __global__ __launch_bounds__(256, 1) void k_wino_fused(const WinoFusedArgs a) {
                     f32x4 mc[6], yc[4];
 #pragma unroll
                     for (int i = 0; i < 6; ++i) mc[i] = e[(i * 6 + j) * 256];
-                    at6q(mc, yc);
+                    at6t(mc, yc);
 #pragma unroll
                     for (int i = 0; i < 4; ++i) tmp[i][j] = yc[i];
                 }
 #pragma unroll
-                for (int i = 0; i < 4; ++i) at6q(tmp[i], y[i]);
+                for (int i = 0; i < 4; ++i) at6t(tmp[i], y[i]);
             }
             const int cl = nt * 32 + 4 * cq;            // channel within the block's channel group
             const int cg = n0 + cl;

@@ -13,6 +13,7 @@
 //   k_wino_in_mixed    : X[N,H,W,pitch] --B_r^T d B_c--> V_type in the fragment order the GEMM streams, one region per type
 //   k_wino_fused_mixed : per block M[xi] = V[xi] U[xi]^T on the fp32 matrix cores, A_r^T M A_c + bias (border class) + PReLU
 //                        (+ residual, sigmoid, SE tile sums) -> out
+#include "device_util.h"
 #include "ffr_kernels.h"
 #include "wino_math.h"
 
@@ -34,7 +35,7 @@ __device__ __forceinline__ void at5q(const f32x4 m[5], f32x4 y[3]) {
     y[2] = s12 + 4.f * m[3] + m[4];
 }
 template <int A> __device__ __forceinline__ void btv(const f32x4* d, f32x4* v) { if constexpr (A == 6) bt6v(d, v); else bt5v(d, v); }
-template <int A> __device__ __forceinline__ void atq(const f32x4* m, f32x4* y) { if constexpr (A == 6) at6q(m, y); else at5q(m, y); }
+template <int A> __device__ __forceinline__ void atq(const f32x4* m, f32x4* y) { if constexpr (A == 6) at6t(m, y); else at5q(m, y); }
 
 // tile t of type (MR, MC) -> image, origin of its outputs
 template <int MR, int MC>
@@ -299,7 +300,6 @@ hipError_t launch_combine_in_mixed(const float* res, const float* scale, const f
 constexpr int WM_EPI_FLOATS = 36 * 32 * 32;
 constexpr int WM_LDS_BYTES = (WM_EPI_FLOATS + 9 * 64 + 32 * 8) * 4;
 
-#define FFR_PIN __builtin_amdgcn_sched_barrier(0)
 template <int MR, int MC>
 __device__ __forceinline__ void fused_mixed_body(const WinoMixedArgs& a, int tau, int mb, int nb, float* smem) {
     constexpr int AR = MR + 2, AC = MC + 2, X = AR * AC, S = (X + 3) / 4, XP = 4 * S, NT = 2;
@@ -478,7 +478,6 @@ __device__ __forceinline__ void fused_mixed_body(const WinoMixedArgs& a, int tau
         tr[8] = (unsigned long long)tau; tr[9] = 1;
     }
 }
-#undef FFR_PIN
 
 __global__ __launch_bounds__(256, 1) void k_wino_fused_mixed(const WinoMixedArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];

@@ -13,30 +13,11 @@
 //   (igemm)   :  M[xi][T][cout_pad] = V[xi][T][cin_pad] * U[xi][cout_pad][cin_pad]^T, xi = 0..35
 //   k_wino_out:  M -> out[N,H,W,out_pitch] with the conv epilogue (border-class bias, PReLU,
 //                residual, sigmoid)
+#include "device_util.h"
 #include "ffr_kernels.h"
+#include "wino_math.h"
 
 namespace ffr {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// v = B^T d
-__device__ __forceinline__ void bt6(const f32x4 d[6], f32x4 v[6]) {
-    v[0] = 4.f * d[0] - 5.f * d[2] + d[4];
-    v[1] = -4.f * (d[1] + d[2]) + d[3] + d[4];
-    v[2] = 4.f * (d[1] - d[2]) - d[3] + d[4];
-    v[3] = 2.f * (d[3] - d[1]) - d[2] + d[4];
-    v[4] = 2.f * (d[1] - d[3]) - d[2] + d[4];
-    v[5] = 4.f * d[1] - 5.f * d[3] + d[5];
-}
-
-// y = A^T m
-__device__ __forceinline__ void at6(const f32x4 m[6], f32x4 y[4]) {
-    const f32x4 s12 = m[1] + m[2], d12 = m[1] - m[2], s34 = m[3] + m[4], d34 = m[3] - m[4];
-    y[0] = m[0] + s12 + s34;
-    y[1] = d12 + 2.f * d34;
-    y[2] = s12 + 4.f * s34;
-    y[3] = d12 + 8.f * d34 + m[5];
-}
 
 // item idx = (tile t, channel quad): t = idx / cq, then t -> (image n, tile row ty, tile column tx).  The items of every launch
 // this library makes are fewer than 2^31, for which everything is 32-bit arithmetic (a 64-bit division is ~100 instructions, and
@@ -91,7 +72,7 @@ __global__ __launch_bounds__(256) void k_wino_in(const float* __restrict__ x, fl
             d[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
             if (ok) d[i] = *reinterpret_cast<const f32x4*>(xn + ((size_t)hi * W + wi) * pitch);
         }
-        bt6(d, v);
+        bt6v(d, v);
 #pragma unroll
         for (int i = 0; i < 6; ++i) tmp[i][j] = v[i];
     }
@@ -100,7 +81,7 @@ __global__ __launch_bounds__(256) void k_wino_in(const float* __restrict__ x, fl
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
         f32x4 v[6];
-        bt6(tmp[i], v);
+        bt6v(tmp[i], v);
 #pragma unroll
         for (int j = 0; j < 6; ++j) *reinterpret_cast<f32x4*>(vout + (size_t)(i * 6 + j) * plane) = v[j];
     }
@@ -127,7 +108,7 @@ __global__ __launch_bounds__(256) void k_wino_out(const WinoOutArgs a) {
         f32x4 m[6], y[4];
 #pragma unroll
         for (int i = 0; i < 6; ++i) m[i] = *reinterpret_cast<const f32x4*>(min + (size_t)(i * 6 + j) * plane);
-        at6(m, y);
+        at6t(m, y);
 #pragma unroll
         for (int i = 0; i < 4; ++i) tmp[i][j] = y[i];
     }
@@ -138,7 +119,7 @@ __global__ __launch_bounds__(256) void k_wino_out(const WinoOutArgs a) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         f32x4 y[4];
-        at6(tmp[i], y);
+        at6t(tmp[i], y);
         const int oh = ty * 4 + i;
         if (oh >= a.H) continue;
         const int rc = !a.border_bias ? 0 : (oh == 0 ? 0 : (oh == a.H - 1 ? 2 : 1));
@@ -360,7 +341,7 @@ __global__ __launch_bounds__(256) void k_wino_out_in(const WinoOutInArgs a) {
             f32x4 m[6], y[4];
 #pragma unroll
             for (int i = 0; i < 6; ++i) m[i] = *reinterpret_cast<const f32x4*>(min + (size_t)(i * 6 + j) * plane);
-            at6(m, y);
+            at6t(m, y);
 #pragma unroll
             for (int i = 0; i < 4; ++i) tmp[i][j] = y[i];
         }
@@ -369,7 +350,7 @@ __global__ __launch_bounds__(256) void k_wino_out_in(const WinoOutInArgs a) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             f32x4 y[4];
-            at6(tmp[i], y);
+            at6t(tmp[i], y);
             const int oh = ty * 4 + i;
             if (oh >= a.H) continue;
             const int rc = !a.border_bias ? 0 : (oh == 0 ? 0 : (oh == a.H - 1 ? 2 : 1));
@@ -400,7 +381,7 @@ __global__ __launch_bounds__(256) void k_wino_out_in(const WinoOutInArgs a) {
             d[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
             if (okw && (unsigned)hi < (unsigned)a.H) d[i] = *reinterpret_cast<const f32x4*>(act + ((size_t)hi * a.W + wi) * CB + q * 4);
         }
-        bt6(d, v);
+        bt6v(d, v);
 #pragma unroll
         for (int i = 0; i < 6; ++i) tmp[i][j] = v[i];
     }
@@ -408,7 +389,7 @@ __global__ __launch_bounds__(256) void k_wino_out_in(const WinoOutInArgs a) {
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
         f32x4 v[6];
-        bt6(tmp[i], v);
+        bt6v(tmp[i], v);
 #pragma unroll
         for (int j = 0; j < 6; ++j) *reinterpret_cast<f32x4*>(vout + (size_t)(i * 6 + j) * plane) = v[j];
     }

@@ -87,7 +87,9 @@ def test_planted_clusters_exact(eng):
     assert torch.equal(eng.cluster(dev(emb), THR, norms=eng.row_norms(dev(emb))), rep)
 
 
-@pytest.mark.parametrize('N', [1, 2, 31, 32, 33, 127, 128, 129, 257, 1000])
+# 4129 = 4096 + 33: up to 1000 rows a chunk is one 128-row step; at 4129 a chunk has several, so blocks start at a later
+# step of their chunk and the prefetch crosses a step boundary inside it; the last tile holds one probe
+@pytest.mark.parametrize('N', [1, 2, 31, 32, 33, 127, 128, 129, 257, 1000, 4129])
 def test_tile_and_step_boundaries(eng, N):
     emb, truth, info, want, S = planted(N)
     assert cluster_ref.margin(S, THR) > MARGIN

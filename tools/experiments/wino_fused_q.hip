@@ -101,7 +101,6 @@ __global__ __launch_bounds__(256, 1) void k_wino_fused_q(const WinoFusedArgs a) 
         for (int j = 0; j < 4; ++j) accv[j][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
     }
 
-#define FFR_PIN __builtin_amdgcn_sched_barrier(0)
     f32x4 fu[WQ_R];
     f32x4 fv[4][2];                                        // V fragments of the current pair of steps and of the next
     // step t of the phase: t & 3 goes into the instruction's immediate offset (12 bits), the rest into the scalar offset (one
@@ -236,7 +235,6 @@ __global__ __launch_bounds__(256, 1) void k_wino_fused_q(const WinoFusedArgs a) 
         up += 72 * 1024u;
         __syncthreads();                                    // everybody is done reading V before the next transform
     }
-#undef FFR_PIN
     if (FFR_TRACE_ON(a.trace)) st2 = __builtin_amdgcn_s_memtime();
 
     // ---- epilogue: A^T m A in registers, activation, one pass through LDS for whole-line stores ----------------------
@@ -251,7 +249,6 @@ __global__ __launch_bounds__(256, 1) void k_wino_fused_q(const WinoFusedArgs a) 
     const int my_pix0 = s_tile[(lane & 31) * 8 + 0], my_vrc = s_tile[(lane & 31) * 8 + 1];
     float* const ob = a.out + a.out_coff + n0 + jt * 4;    // copy role: channels 4 jt .. 4 jt + 3 of the block's 64
     const bool cok = n0 + jt * 4 + 3 < a.cout_store;
-#define FFR_PIN __builtin_amdgcn_sched_barrier(0)
     // copy of one tile: wave w stores pixel row w; 16 lanes = the 256-byte line of one pixel (64 channels); the geometry
     // of tile tl comes from lane tl's registers (v_readlane -> SGPR), not from LDS
     auto copy_issue = [&](int tl) {
@@ -303,7 +300,7 @@ __global__ __launch_bounds__(256, 1) void k_wino_fused_q(const WinoFusedArgs a) 
                     const f32x4 q = (i * 6 + j) < 32 ? acc[(i * 6 + j) & 31][nt] : accv[(i * 6 + j) & 3][nt];
                     mc[i] = hp ? (f32x2){q[2], q[3]} : (f32x2){q[0], q[1]};
                 }
-                at6p(mc, yc);
+                at6t(mc, yc);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) tmp[i][j] = yc[i];
                 if (nt == 1 && hp * 10 + j < 16) copy_store(hp * 10 + j, copy_issue(hp * 10 + j));     // slot hp * 10 + j of 20: one tile of the first half
@@ -313,7 +310,7 @@ __global__ __launch_bounds__(256, 1) void k_wino_fused_q(const WinoFusedArgs a) 
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 f32x2 yr[4];
-                at6p(tmp[i], yr);
+                at6t(tmp[i], yr);
 #pragma unroll
                 for (int jj = 0; jj < 4; ++jj) {
                     f32x2 v = yr[jj] + *reinterpret_cast<const f32x2*>(s_bias + rc[i] + cc[jj] + cl + 2 * hp);
@@ -353,7 +350,6 @@ __global__ __launch_bounds__(256, 1) void k_wino_fused_q(const WinoFusedArgs a) 
 #pragma unroll
         for (int k = 0; k < 16; ++k) copy_store(16 + k, v[k]);
     }
-#undef FFR_PIN
     if (FFR_TRACE_ON(a.trace) && lane == 0) {
         unsigned long long* tr = a.trace + ((size_t)blockIdx.x * 4 + wave) * 10;
         tr[0] = st0; tr[1] = st1; tr[2] = st2; tr[3] = __builtin_amdgcn_s_memtime();
