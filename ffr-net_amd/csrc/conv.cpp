@@ -39,7 +39,7 @@ static int trace_igemm(ffr_handle* h, IgemmArgs& a, int tile, int nblocks, long 
 
 // k_wino_fused_mixed: per-block phase stamps and which CU ran which tile types
 static int trace_wino_mixed(ffr_handle* h, WinoMixedArgs& f, const ConvW& L, const ConvCall& c, hipStream_t st) {
-    const int nbm = wino_mixed_blocks_launched(c.N, c.H, c.W, L.cout_pad, f.xcd_pairs);
+    const int nbm = wino_mixed_blocks_launched(c.N, c.H, c.W, L.cout_pad);
     unsigned long long* dbuf = nullptr;
     HIPCK(h, hipMalloc((void**)&dbuf, (size_t)nbm * 12 * sizeof(unsigned long long)));
     HIPCK(h, hipMemsetAsync(dbuf, 0, (size_t)nbm * 12 * sizeof(unsigned long long), st));
@@ -192,7 +192,6 @@ static int conv_mixed(ffr_handle* h, const ConvW& L, const ConvCall& c, double f
     f.N = c.N; f.H = c.H; f.W = c.W; f.nkc = L.cin_pad / 8;
     f.cout_pad = L.cout_pad; f.cout_store = c.cout_store; f.out_pitch = c.out_pitch; f.out_coff = c.out_coff;
     f.res_pitch = c.res_pitch; f.border_bias = L.border; f.flags = c.flags;
-    f.xcd_pairs = 1;       // XCDs specialise in pairs of tile types (round 5; the uniform map measured slower: EXPERIMENTS.md)
     double fexec = 0.0, fuse = 0.0;
     for (int tau = 0; tau < 4; ++tau) {
         const int nr = tau >= 2 ? g.n3 : g.n4, nc = (tau & 1) ? g.n3 : g.n4;
@@ -218,11 +217,7 @@ static int conv_fused(ffr_handle* h, const ConvW& L, const ConvCall& c, const Co
     WinoFusedArgs f{};
     f.Vc = p.phased ? nullptr : c.winoV; f.x = c.x; f.in_pitch = c.in_pitch; f.pad_mode = L.pad_mode;
     f.x_bytes = p.phased ? (unsigned)(4.0 * c.N * c.H * c.W * c.in_pitch) : 0u;
-    // block -> tile mapping: the channel groups of a tile group next to each other on ONE XCD (V is fetched into that
-    // L2 once instead of once per channel group: 59.5 -> 45.7 GB fetched + written per forward, 17.53 -> 17.32 ms at
-    // batch 256); with the in-kernel transform an XCD owns a contiguous range of tile groups (halo rows shared in its L2).
-    // The alternatives (one channel group per XCD; XCD quads splitting the channel groups) measured slower: EXPERIMENTS.md
-    f.map_v = p.phased ? 2 : 1; f.half_n = p.half_n ? 1 : 0;
+    f.half_n = p.half_n ? 1 : 0;
     f.U3 = p.split ? L.wu3 : nullptr;
     f.Uc = L.wuc; f.bias = L.bias; f.slope = L.slope; f.resid = c.resid; f.out = c.out; f.tile_sums = c.tile_sums;
     f.N = c.N; f.H = c.H; f.W = c.W; f.nkc = L.cin_pad / 8;

@@ -74,7 +74,8 @@ struct Options {
     int combine_v = 1;            // 1: a bottleneck's combine also writes V for the next conv1 when that runs k_wino_fused from V
     int wf_trace = 0, igemm_trace = 0;   // -DFFR_TRACE builds only: per-launch phase stamps on stderr (synchronises)
     // Retired in round 6, their A/B settled (EXPERIMENTS.md): wino_112, wf_halfblocks, wf_mapv, wf_mapx, wf_maph, wm_xcdpairs,
-    // wino_slice_mb, gs_tile, wino_oi, se_fuse, igemm_tile64 -- the code keeps the measured-best setting of each.
+    // wino_slice_mb, gs_tile, wino_oi, se_fuse, igemm_tile64 -- the code keeps the measured-best setting of each (of the block
+    // maps wf_mapv, wf_mapx, wf_maph and wm_xcdpairs only that one: the maps that lost are gone from the kernels).
 };
 
 struct ProfRec {

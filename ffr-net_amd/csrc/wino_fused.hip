@@ -22,8 +22,12 @@
 // Epilogue: the 36 x 32 x 64 products of the block go through LDS in two passes of 32 channels (147 KB, which the K
 // loop does not use); a thread then owns (tile, 4 channels), applies A^T m A and the convolution epilogue and stores 16
 // bytes per pixel; a wave-store covers 8 tiles x 128 bytes.  DESIGN.md 3.1 states the design, EXPERIMENTS.md has the measurements behind each choice.
+//
+// What this kernel has in common with k_wino_fused_mixed (wino_mixed.hip) -- the patch transform of the input side, the LDS
+// tables, the V-fed K loop, the accumulator staging and the pointwise epilogue -- is defined once, in wino_fused_core.h.
 #include "device_util.h"
 #include "ffr_kernels.h"
+#include "wino_fused_core.h"
 #include "wino_math.h"
 
 namespace ffr {
@@ -39,12 +43,8 @@ __global__ __launch_bounds__(256) void k_wino_in_c(const float* __restrict__ x, 
     const int hh = lane & 1;
     const long long t = (long long)mb * 32 + tl;
     const int c4 = kc * 8 + hh * 4;
-    float* vout = Vc + (((size_t)mb * nkc + kc) * 36) * 256 + (hh * 32 + tl) * 4;     // fragment order: lane of k_wino_fused
-    if (t >= T) {
-#pragma unroll
-        for (int xi = 0; xi < 36; ++xi) *reinterpret_cast<f32x4*>(vout + xi * 256) = (f32x4){0.f, 0.f, 0.f, 0.f};
-        return;
-    }
+    float* vout = wino_frag_ptr<36>(Vc, mb, nkc, kc, hh, tl);
+    if (t >= T) { wino_frag_zero<36>(vout); return; }
     const unsigned tu = (unsigned)t, tpi = (unsigned)(tw * th);       // T < 2^31: 32-bit divisions
     const int n = (int)(tu / tpi);
     const unsigned tr = tu - (unsigned)n * tpi;
@@ -109,39 +109,23 @@ __global__ __launch_bounds__(256) void k_combine_in_c(const float* __restrict__ 
                                                      const float* __restrict__ sh, float* __restrict__ out,
                                                      float* __restrict__ Vc, int N, int H, int W, int C, int nkc, int th, int tw) {
     __shared__ __attribute__((aligned(16))) float s_x[CIC_MAXPX * 32];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int mb = blockIdx.x;
     const int tiles_img = th * tw, ipg = 32 / tiles_img, HW = H * W;
     const int n_first = mb * ipg;
     const int n_imgs = N - n_first < ipg ? N - n_first : ipg;
     const int cb = blockIdx.y * 32;
-    // phase 1: x of the group's images, 8 lanes per pixel line
-    {
-        const int q4 = (tid & 7) * 4;
-        const int npx = n_imgs * HW;
-        for (int p = tid >> 3; p < npx; p += 32) {
-            const int il = p / HW;
-            const size_t off = ((size_t)n_first * HW + p) * C + cb + q4;
-            const f32x4 sv = scale ? *reinterpret_cast<const f32x4*>(scale + (size_t)(n_first + il) * C + cb + q4) : (f32x4){1.f, 1.f, 1.f, 1.f};
-            const f32x4 x = *reinterpret_cast<const f32x4*>(res + off) * sv + *reinterpret_cast<const f32x4*>(sh + off);
-            *reinterpret_cast<f32x4*>(out + off) = x;
-            *reinterpret_cast<f32x4*>(s_x + p * 32 + q4) = x;
-        }
-    }
+    combine_to_lds(res, scale, sh, out, s_x, n_first, n_imgs * HW, HW, C, cb);       // phase 1
     __syncthreads();
     // phase 2: tile 8 wave + (lane >> 3), channel quad lane & 7
     const int tl = 8 * wave + (lane >> 3), quad = lane & 7;
     const int kc = blockIdx.y * 4 + (quad >> 1), hf = quad & 1;
-    float* vout = Vc + (((size_t)mb * nkc + kc) * 36) * 256 + (hf * 32 + tl) * 4;
+    float* vout = wino_frag_ptr<36>(Vc, mb, nkc, kc, hf, tl);
     const int il = tl / tiles_img, tr = tl - il * tiles_img;
-    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-    if (il >= n_imgs) {
-#pragma unroll
-        for (int xi = 0; xi < 36; ++xi) *reinterpret_cast<f32x4*>(vout + xi * 256) = zero4;
-        return;
-    }
+    if (il >= n_imgs) { wino_frag_zero<36>(vout); return; }
     const int ty = tr / tw, tx = tr - ty * tw;
     const int h0 = ty * 4 - 1, w0 = tx * 4 - 1;
+    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
     const float* xi_base = s_x + il * HW * 32 + quad * 4;
     f32x4 d[6][6];
 #pragma unroll
@@ -155,22 +139,7 @@ __global__ __launch_bounds__(256) void k_combine_in_c(const float* __restrict__ 
             if (okh && (unsigned)wi < (unsigned)W) d[i][j] = *reinterpret_cast<const f32x4*>(xi_base + (hi * W + wi) * 32);
         }
     }
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        f32x4 col[6], v[6];
-#pragma unroll
-        for (int i = 0; i < 6; ++i) col[i] = d[i][j];
-        bt6v(col, v);
-#pragma unroll
-        for (int i = 0; i < 6; ++i) d[i][j] = v[i];
-    }
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        f32x4 v[6];
-        bt6v(d[i], v);
-#pragma unroll
-        for (int j = 0; j < 6; ++j) *reinterpret_cast<f32x4*>(vout + (i * 6 + j) * 256) = v[j];
-    }
+    wino_patch_to_frags<6, 6>(d, vout);
 }
 
 // tile groups must hold whole images: 32 % (tiles per image) == 0 and at most CIC_MAXPX pixels per group
@@ -189,23 +158,7 @@ hipError_t launch_combine_in_c(const float* res, const float* scale, const float
     return hipGetLastError();
 }
 
-// s_waitcnt vmcnt(n) for a value that is a constant only after unrolling
-__device__ __forceinline__ void wait_vmcnt(int n) {
-    switch (n) {
-        case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-        case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-        case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-        case 9: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
-        case 12: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;
-        case 15: asm volatile("s_waitcnt vmcnt(15)" ::: "memory"); break;
-        case 18: asm volatile("s_waitcnt vmcnt(18)" ::: "memory"); break;
-        case 21: asm volatile("s_waitcnt vmcnt(21)" ::: "memory"); break;
-        default: asm volatile("s_waitcnt vmcnt(24)" ::: "memory"); break;
-    }
-}
-
 // ---- the fused GEMM + output transform ------------------------------------------------------------------------
-constexpr int WF_EPI_FLOATS = 36 * 32 * 32;  // the epilogue's E[xi][tile][32 channels] (147,456 B); the K loop uses no LDS
 constexpr int WF_U3_STEP = 2 * 3 * 64 * 16;   // split form: bytes of U per (channel group, 16-channel K step, xi): 2 halves x 3 planes x 64 lanes x 8 bf16
 constexpr int WF_LDS_BYTES = (WF_EPI_FLOATS + 9 * 64 + 32 * 8 + 32 * 12) * 4;   // + bias table + tile table + patch-offset table = 152,320 B
 
@@ -232,33 +185,21 @@ __global__ __launch_bounds__(256, 1) void k_wino_fused(const WinoFusedArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     // block -> (tile group mb, channel group nb).  Blocks b and b + 8 share an XCD (round-robin dispatch) and with it
-    // a 4 MB L2.  map_v (default): the channel groups of one tile group are neighbours on ONE XCD and run at the same
-    // time, so V is fetched into that L2 once; the blocks of an XCD walk through K in step, so the chunk of U they all
-    // need (73.7 KB per channel group) is in the L2 as well.  Otherwise: as few channel groups per XCD as possible (its
-    // slice of U stays in the L2, V is re-read by the XCD of every channel group).  Speed only.
+    // a 4 MB L2.  The channel groups of one tile group are neighbours on ONE XCD and run at the same time, so V is fetched
+    // into that L2 once; the blocks of an XCD walk through K in step, so the chunk of U they all need (73.7 KB per channel
+    // group) is in the L2 as well (59.5 -> 45.7 GB fetched + written per forward, 17.53 -> 17.32 ms at batch 256).  Speed only;
+    // the maps that lost the comparison (one channel group per XCD; XCD quads splitting the channel groups) are in EXPERIMENTS.md.
     const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-    int nb, mb;
-    if (a.map_v == 2) {     // as map_v == 1, and an XCD owns a CONTIGUOUS range of tile groups (round 5, launches that transform their own
-        // input): tile groups mb and mb + 1 cover neighbouring tile rows of the same image, whose 6x6 patches share two pixel rows of
-        // every six -- on one XCD that halo is fetched into the L2 once, with the round-robin map below twice (two XCDs)
-        nb = idx % a.nbn; mb = xcd * ((a.mbn + 7) >> 3) + idx / a.nbn;
+    const int nb = idx % a.nbn;
+    int mb;
+    if constexpr (PHASED) {
+        // an XCD owns a CONTIGUOUS range of tile groups: tile groups mb and mb + 1 cover neighbouring tile rows of the same image,
+        // whose 6x6 patches share two pixel rows of every six -- on one XCD that halo is fetched into the L2 once, with the
+        // round-robin map below twice (two XCDs)
+        mb = xcd * ((a.mbn + 7) >> 3) + idx / a.nbn;
         if (idx / a.nbn >= ((a.mbn + 7) >> 3)) return;
-    } else if (a.map_v == 3) {
-        // round 5, V-fed launches with many channel groups (nbn even, >= 4): XCDs 0-3 take the lower half of the channel groups, XCDs 4-7
-        // the upper half; a tile group is processed by one XCD of each quad.  Every L2 then streams HALF of U per launch and V is
-        // read by two XCDs instead of one: for cin = cout = 512 on 7x7 maps 151 + 150 MB instead of 302 + 75 MB.
-        const int hn = a.nbn >> 1;
-        nb = (xcd >> 2) * hn + idx % hn; mb = (idx / hn) * 4 + (xcd & 3);
-    } else if (a.map_v) {   // all channel groups of a tile group on one XCD, next to each other in dispatch order
-        nb = idx % a.nbn; mb = (idx / a.nbn) * 8 + xcd;
-    } else if (a.nbn % 8 == 0) {
-        const int r = a.nbn >> 3;
-        nb = xcd * r + idx % r; mb = idx / r;
-    } else if (8 % a.nbn == 0) {
-        const int per = 8 / a.nbn;
-        nb = xcd % a.nbn; mb = xcd / a.nbn + per * idx;
     } else {
-        nb = idx % a.nbn; mb = (idx / a.nbn) * 8 + xcd;
+        mb = (idx / a.nbn) * 8 + xcd;
     }
     if (mb >= a.mbn) return;
     const int nkc = a.nkc;
@@ -267,27 +208,21 @@ __global__ __launch_bounds__(256, 1) void k_wino_fused(const WinoFusedArgs a) {
     // epilogue tables (their LDS is never aliased; the epilogue's first barrier publishes them)
     const int tid = threadIdx.x;
     const int n0 = nb * (32 * NT);
-    float* const s_bias = smem + WF_EPI_FLOATS;                       // [9][64] border-class biases of this channel group
-    int* const s_tile = reinterpret_cast<int*>(s_bias + 9 * 64);     // [32][8]: origin pixel, valid rows | cols << 8, border rows, border cols, image base pixel, 4ty-1, 4tx-1
-    for (int i = tid; i < (a.border_bias ? 9 : 1) * 64; i += 256)
-        if ((i & 63) < 32 * NT) s_bias[i] = a.bias[(size_t)(i >> 6) * a.cout_pad + n0 + (i & 63)];
+    float* const s_bias = smem + WF_EPI_FLOATS;
+    int* const s_tile = reinterpret_cast<int*>(s_bias + 9 * 64);     // [4..6]: image base pixel, 4ty-1, 4tx-1
+    wf_fill_bias<NT>(s_bias, a.bias, a.border_bias, a.cout_pad, n0);
     if (tid < 32) {
         const long long t = (long long)mb * 32 + tid;
-        int pix0 = 0, vrc = 0, br = 0, bc = 0, ibase = 0, h0 = 0, w0 = 0;
-        if (t < a.T) {
+        const bool valid = t < a.T;
+        int n = 0, ty = 0, tx = 0;
+        if (valid) {
             const unsigned tiles_img = (unsigned)(a.th * a.tw);        // T < 2^31 (run_conv): 32-bit divisions
-            const int n = (int)((unsigned)t / tiles_img);
+            n = (int)((unsigned)t / tiles_img);
             const int tr = (int)((unsigned)t - (unsigned)n * tiles_img);
-            const int ty = (int)((unsigned)tr / (unsigned)a.tw), tx = tr - ty * a.tw;
-            pix0 = (n * a.H + ty * 4) * a.W + tx * 4;
-            ibase = n * a.H * a.W; h0 = ty * 4 - 1; w0 = tx * 4 - 1;
-            const int vr = a.H - ty * 4 < 4 ? a.H - ty * 4 : 4, vc = a.W - tx * 4 < 4 ? a.W - tx * 4 : 4;
-            vrc = vr | (vc << 8);
-            // row i of the tile is the map's top row iff ty == 0 && i == 0; its bottom row iff i == H-1-4ty
-            br = (ty == 0 ? 1 : 0) | ((a.H - 1 - ty * 4) & 0xff) << 8;
-            bc = (tx == 0 ? 1 : 0) | ((a.W - 1 - tx * 4) & 0xff) << 8;
+            ty = (int)((unsigned)tr / (unsigned)a.tw); tx = tr - ty * a.tw;
         }
-        s_tile[tid * 8 + 0] = pix0; s_tile[tid * 8 + 1] = vrc; s_tile[tid * 8 + 2] = br; s_tile[tid * 8 + 3] = bc;
+        const int ibase = valid ? n * a.H * a.W : 0, h0 = valid ? ty * 4 - 1 : 0, w0 = valid ? tx * 4 - 1 : 0;
+        wf_tile_record(s_tile + tid * 8, valid, n, ty * 4, tx * 4, 4, 4, a.H, a.W);
         s_tile[tid * 8 + 4] = ibase; s_tile[tid * 8 + 5] = h0; s_tile[tid * 8 + 6] = w0;
         if constexpr (PHASED) {
             // byte offsets of the 6 patch rows / columns of this tile (without the lane's channel quad), or a value past the end
@@ -301,9 +236,9 @@ __global__ __launch_bounds__(256, 1) void k_wino_fused(const WinoFusedArgs a) {
                 if (a.pad_mode == 1) {
                     hi = hi < 0 ? -hi : (hi >= a.H ? 2 * a.H - 2 - hi : hi); if (hi < 0) hi = 0;
                     wi = wi < 0 ? -wi : (wi >= a.W ? 2 * a.W - 2 - wi : wi); if (wi < 0) wi = 0;
-                    rok = vrc != 0; cok = true;
+                    rok = valid; cok = true;
                 } else {
-                    rok = vrc != 0 && (unsigned)hi < (unsigned)a.H;
+                    rok = valid && (unsigned)hi < (unsigned)a.H;
                     cok = (unsigned)wi < (unsigned)a.W;
                 }
                 so[i] = rok ? (unsigned)((ibase + hi * a.W) * a.in_pitch) * 4u : 0x40000000u;
@@ -312,21 +247,18 @@ __global__ __launch_bounds__(256, 1) void k_wino_fused(const WinoFusedArgs a) {
         }
     }
 
-    // operand streams of this wave: one 16-byte fragment per lane, xi and K chunk (lane-linear in memory)
-    // Both streams are read through buffer resources: the per-lane part of the address (lane * 16 bytes) sits in one VGPR,
-    // everything else -- tile group, wave, xi, K chunk -- in the SCALAR offset, which SALU instructions and immediates
-    // advance.  (Per-lane 64-bit pointers cost 16 v_add_co / v_addc pairs per K chunk, and every VALU instruction delays
-    // the next MFMA by its issue time: round 4, measured on k_wino_fused_q first.)
-    // (V can exceed 4 GB -- 7.4 GB for the 112x112 layer at 1024 images -- so its resource starts at this block's tile group:
-    // 36 KB per K chunk, at most 6.9 MB)
-    const __amdgpu_buffer_rsrc_t vrs = __builtin_amdgcn_make_buffer_rsrc((void*)(PHASED ? a.Uc : a.Vc + (size_t)mb * nkc * 36 * 256), 0,
-                                                                         PHASED ? 0u : (unsigned)nkc * 36u * 1024u, 0x00020000);
+    f32x16 acc[8][NT], accv[NT];      // the wave's 9 xi x NT halves (wino_fused_core.h)
+    wf_zero_acc<NT>(acc, accv);
+
+    if constexpr (MODE == 0) {
+    wf_vfed_gemm<9, NT>(a.Vc, a.Uc, mb, nb, nkc, a.cout_pad, wave, lane, acc, accv, a.trace, st1);
+    } else if constexpr (MODE == 1) {
+    // the weight stream of this wave through a buffer resource, as in wf_vfed_gemm; V comes from LDS
     // (split form: three bf16 planes, 6 KB per channel group, 16-channel K step and xi)
     const __amdgpu_buffer_rsrc_t urs = SPLIT
         ? __builtin_amdgcn_make_buffer_rsrc((void*)a.U3, 0, (unsigned)((size_t)(a.cout_pad >> 6) * (nkc >> 1) * 36 * WF_U3_STEP), 0x00020000)
         : __builtin_amdgcn_make_buffer_rsrc((void*)a.Uc, 0, (unsigned)((size_t)a.cout_pad * nkc * 8 * 36 * 4), 0x00020000);
     const unsigned lane16 = (unsigned)lane * 16u;
-    unsigned vp = (unsigned)(9 * wave) * 1024u;                                 // scalar byte offsets of this wave's xi 0 in the current K chunk
     // U is packed per 64-channel group: [cout_pad/64][K chunk][xi][2 halves][64 lanes][4]
     // split form: [cout_pad/64][16-channel K step][xi][2 halves][3 planes][64 lanes][8 bf16]
     unsigned up = SPLIT ? (unsigned)(nb * (nkc >> 1) * 36 + 9 * wave) * (unsigned)WF_U3_STEP
@@ -335,72 +267,6 @@ __global__ __launch_bounds__(256, 1) void k_wino_fused(const WinoFusedArgs a) {
     auto ldfrag = [&](const __amdgpu_buffer_rsrc_t& rs, unsigned so) {
         return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, lane16, so, 0));
     };
-    const int rowl = lane & 31;
-
-    // 18 accumulator tiles = 288 registers, but a wave addresses 256 AGPRs + 256 VGPRs and hipcc keeps every builtin
-    // MFMA accumulator in AGPRs (a 17th tile is copied in and out around each of its MFMAs, with the full MFMA
-    // latency exposed): xi 0..7 of the wave use the builtin (16 tiles, all 256 AGPRs), xi 8 the VGPR form of the same
-    // instruction through inline asm (accv, 32 VGPRs)
-    f32x16 acc[8][NT], accv[NT];
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            accv[nt][r] = 0.f;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) acc[j][nt][r] = 0.f;
-        }
-
-    if constexpr (MODE == 0) {
-    // fragment registers: slot j holds (V, U lo, U hi) of xi j for the K chunk that consumes it next
-    f32x4 fv[9], fu[9][NT];
-    auto load = [&](int j, int part, unsigned v, unsigned u) {
-        if (part == 0) fv[j] = ldfrag(vrs, v + j * 1024u);
-        else fu[j][part - 1] = ldfrag(urs, u + j * 2048u + (part - 1) * 1024u);
-    };
-    // ---- prologue: xi 0..7 of K chunk 0 in flight (xi 8 follows in step 0) ----
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-#pragma unroll
-        for (int part = 0; part <= NT; ++part) load(j, part, vp, up);
-        FFR_PIN;            // in THIS order: vmcnt counts loads in issue order, and the loop's waits are derived from it
-    }
-    FFR_PIN;
-    if (FFR_TRACE_ON(a.trace)) st1 = __builtin_amdgcn_s_memtime();
-
-    // one K chunk: 9 steps (xi) of 8 MFMAs; every step reloads the slot the previous step consumed, 8 steps ahead of
-    // its next use.  vp/up point at the chunk being multiplied.  LAST: no chunk follows.
-    auto chunk = [&]<bool LAST>() {
-#pragma unroll
-        for (int j = 0; j < 9; ++j) {
-            const f32x4 av = fv[j], b0 = fu[j][0], b1 = fu[j][NT - 1];
-#pragma unroll
-            for (int g = 0; g < 4 * NT; ++g) {
-                const int e = g / NT, nt = g % NT;
-                if (j < 8) acc[j][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(nt ? b1[e] : b0[e], av[e], acc[j][nt], 0, 0, 0);
-                else asm volatile("v_mfma_f32_32x32x2_f32 %0, %1, %2, %0" : "+v"(accv[nt]) : "v"(nt ? b1[e] : b0[e]), "v"(av[e]));
-                // the step's three loads go out back to back in ONE MFMA gap: an MFMA whose gap carries vector-memory
-                // instructions issues ~8 cycles late plus ~14 per load (measured: 5.30k cycles per K chunk with one load in
-                // each of three gaps, 5.15k with three loads in one gap, 4.70k without loads)
-                if (g == 1) {
-#pragma unroll
-                    for (int part = 0; part <= NT; ++part) {
-                        if (j == 0) load(8, part, vp, up);                                     // xi 8 of this chunk
-                        else if (!LAST) load(j - 1, part, vp + 36 * 1024u, up + 36 * 2048u);       // xi j-1 of the next chunk
-                    }
-                }
-                FFR_PIN;
-            }
-        }
-    };
-#pragma unroll 1
-    for (int kc = 0; kc + 1 < nkc; ++kc) {
-        chunk.template operator()<false>();
-        vp += 36 * 1024u;
-        up += 36 * 2048u;
-    }
-    chunk.template operator()<true>();
-    } else if constexpr (MODE == 1) {
     // ---- PHASED: per 32 input channels: input transform -> LDS, then 4 K chunks with the A fragments from LDS ----
     f32x4 fu[9][NT];
     auto loadu = [&](int j, int part, unsigned u) {
@@ -619,23 +485,11 @@ __global__ __launch_bounds__(256, 1) void k_wino_fused(const WinoFusedArgs a) {
     // and lane, no branches.
     // the inline-asm MFMAs are invisible to hipcc's hazard recognizer: their results must not be read for 18 cycles
     asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
-    const int hsel = lane >> 5;
     const int cq = lane & 7;                        // channel quad of this lane within the 32-channel half
     const bool vec4 = ((a.out_pitch | a.out_coff | a.res_pitch) & 3) == 0;
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
-        // E[xi][tile][co]: the 32-channel half nt of all 32 tiles
-#pragma unroll
-        for (int j = 0; j < 9; ++j)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                // the MFMAs run with A = U, B = V: a lane holds tile rowl and, in registers 4q..4q+3, the FOUR CONSECUTIVE channels
-                // 8q + 4 hsel + 0..3 -> one 16-byte LDS write (36 per pass instead of 144 dword writes); the 16-byte chunk index is
-                // XOR-ed with the tile so that 8 lanes (8 tiles, one chunk) hit 8 different bank columns; the reader applies the same XOR
-                const f32x16& t16 = j < 8 ? acc[j < 8 ? j : 0][nt] : accv[nt];
-                *reinterpret_cast<f32x4*>(smem + ((9 * wave + j) * 32 + rowl) * 32 + (((2 * q + hsel) ^ (rowl & 7)) * 4)) =
-                    (f32x4){t16[4 * q], t16[4 * q + 1], t16[4 * q + 2], t16[4 * q + 3]};
-            }
+        wf_stage_acc<9, 36, NT>(smem, wave, lane, nt, acc, accv);      // E[xi][tile][co]: the 32-channel half nt of all 32 tiles
         __syncthreads();
         if (FFR_TRACE_ON(a.trace) && !PHASED) se[2 * nt] = __builtin_amdgcn_s_memtime();
         // one (tile, 4 channels) per thread: a wave-instruction reads / stores 8 tiles x 128 bytes
@@ -644,7 +498,7 @@ __global__ __launch_bounds__(256, 1) void k_wino_fused(const WinoFusedArgs a) {
         if (vrc != 0) {                                                 // else: tile beyond T
             const int pix0 = s_tile[tl * 8 + 0];
             const int vr = vrc & 0xff, vc = vrc >> 8;
-            const f32x4* e = reinterpret_cast<const f32x4*>(smem + tl * 32 + 4 * (cq ^ (tl & 7)));
+            const f32x4* e = wf_staged(smem, tl, cq);
             f32x4 y[4][4];
             {
                 f32x4 tmp[4][6];
@@ -662,8 +516,7 @@ __global__ __launch_bounds__(256, 1) void k_wino_fused(const WinoFusedArgs a) {
             }
             const int cl = nt * 32 + 4 * cq;            // channel within the block's channel group
             const int cg = n0 + cl;
-            f32x4 slope = {1.f, 1.f, 1.f, 1.f};
-            if (a.slope) slope = *reinterpret_cast<const f32x4*>(a.slope + cg);
+            const f32x4 slope = wf_slope(a.slope, cg);
             // bias per pixel: one value, or one of 9 border classes
             f32x4 bs[4][4];
             if (!a.border_bias) {
@@ -673,13 +526,9 @@ __global__ __launch_bounds__(256, 1) void k_wino_fused(const WinoFusedArgs a) {
 #pragma unroll
                     for (int jj = 0; jj < 4; ++jj) bs[i][jj] = b0;
             } else {
-                const int br = s_tile[tl * 8 + 2], bc = s_tile[tl * 8 + 3];
                 int rc[4], cc[4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    rc[i] = ((i == 0 && (br & 1)) ? 0 : (i == (br >> 8) ? 2 : 1)) * 3 * 64;
-                    cc[i] = ((i == 0 && (bc & 1)) ? 0 : (i == (bc >> 8) ? 2 : 1)) * 64;
-                }
+                wf_border_offsets(s_tile[tl * 8 + 2], 3 * 64, rc);
+                wf_border_offsets(s_tile[tl * 8 + 3], 64, cc);
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -712,14 +561,7 @@ __global__ __launch_bounds__(256, 1) void k_wino_fused(const WinoFusedArgs a) {
                 for (int i = 3; i >= 0; --i)
 #pragma unroll
                     for (int jj = 3; jj >= 0; --jj) {
-                        f32x4 v = y[i][jj] + bs[i][jj];
-#pragma unroll
-                        for (int c = 0; c < 4; ++c) v[c] = fmaxf(v[c], 0.f) + slope[c] * fminf(v[c], 0.f);     // PReLU without VCC
-                        if (rb) v += rs[i][jj];
-                        if (a.flags & 1) {
-#pragma unroll
-                            for (int c = 0; c < 4; ++c) v[c] = 1.0f / (1.0f + __expf(-v[c]));
-                        }
+                        const f32x4 v = wf_pointwise(y[i][jj], bs[i][jj], slope, rb != nullptr, [&] { return rs[i][jj]; }, a.flags);
                         *reinterpret_cast<f32x4*>(ob + (ro[i] + co[jj]) * a.out_pitch) = v;
                         if (a.tile_sums) psum += v * (mr[i] * mc[jj]);
                     }
@@ -742,10 +584,7 @@ __global__ __launch_bounds__(256, 1) void k_wino_fused(const WinoFusedArgs a) {
                         }
                     }
             }
-            if (a.tile_sums) {
-                const long long t = (long long)mb * 32 + tl;
-                *reinterpret_cast<f32x4*>(a.tile_sums + (size_t)t * a.cout_pad + cg) = psum;
-            }
+            if (a.tile_sums) wf_store_tile_sum(a.tile_sums, (long long)mb * 32 + tl, a.cout_pad, cg, psum);
         }
         if (FFR_TRACE_ON(a.trace) && !PHASED) se[2 * nt + 1] = __builtin_amdgcn_s_memtime();
         __syncthreads();
@@ -775,17 +614,11 @@ hipError_t wino_fused_init() {
     return hipSuccess;
 }
 
-static int wf_grid(int mbn, int nbn, int map_v) {      // inverse of the block decoding in k_wino_fused
-    if (map_v == 3) return (mbn + 3) / 4 * 8 * (nbn >> 1);
-    if (map_v) return (mbn + 7) / 8 * 8 * nbn;
-    if (nbn % 8 == 0) return mbn * nbn;
-    if (8 % nbn == 0) { const int per = 8 / nbn; return 8 * ((mbn + per - 1) / per); }
-    return (mbn + 7) / 8 * 8 * nbn;
-}
+static int wf_grid(int mbn, int nbn) { return (mbn + 7) / 8 * 8 * nbn; }      // inverse of the block decoding in k_wino_fused
 
 int wino_fused_blocks(const WinoFusedArgs& a) {
     const long long T = (long long)a.N * ((a.H + 3) / 4) * ((a.W + 3) / 4);
-    return wf_grid((int)((T + 31) / 32), a.cout_pad / (a.half_n ? 32 : 64), a.map_v);
+    return wf_grid((int)((T + 31) / 32), a.cout_pad / (a.half_n ? 32 : 64));
 }
 
 hipError_t launch_wino_fused(WinoFusedArgs a, hipStream_t stream) {
@@ -794,7 +627,7 @@ hipError_t launch_wino_fused(WinoFusedArgs a, hipStream_t stream) {
     a.T = (long long)a.N * a.th * a.tw;
     a.mbn = (int)((a.T + 31) / 32);
     a.nbn = a.cout_pad / (a.half_n ? 32 : 64);
-    const dim3 grid(wf_grid(a.mbn, a.nbn, a.map_v));
+    const dim3 grid(wf_grid(a.mbn, a.nbn));
     if (a.Vc) {
         if (a.U3) return hipErrorInvalidValue;                      // ... and only with the in-kernel transform
         if (a.half_n) hipLaunchKernelGGL((k_wino_fused<0, 1>), grid, dim3(256), WF_LDS_BYTES, stream, a);

@@ -13,29 +13,14 @@
 //   k_wino_in_mixed    : X[N,H,W,pitch] --B_r^T d B_c--> V_type in the fragment order the GEMM streams, one region per type
 //   k_wino_fused_mixed : per block M[xi] = V[xi] U[xi]^T on the fp32 matrix cores, A_r^T M A_c + bias (border class) + PReLU
 //                        (+ residual, sigmoid, SE tile sums) -> out
+// Both are the F(4x4) kernels of wino_fused.hip with other constants: the pieces they share are in wino_fused_core.h, the 5-point
+// transforms beside the 6-point ones in wino_math.h.  Here: tile -> origin, the type dispatch, A_r^T M A_c and the full-tile stores.
 #include "device_util.h"
 #include "ffr_kernels.h"
+#include "wino_fused_core.h"
 #include "wino_math.h"
 
 namespace ffr {
-
-// v = B^T d for F(3,3): 5 points {0, 1, -1, 2, inf}
-__device__ __forceinline__ void bt5v(const f32x4 d[5], f32x4 v[5]) {
-    v[0] = 2.f * d[0] - d[1] - 2.f * d[2] + d[3];
-    v[1] = -2.f * d[1] - d[2] + d[3];
-    v[2] = 2.f * d[1] - 3.f * d[2] + d[3];
-    v[3] = d[3] - d[1];
-    v[4] = 2.f * d[1] - d[2] - 2.f * d[3] + d[4];
-}
-// y = A^T m for F(3,3)
-__device__ __forceinline__ void at5q(const f32x4 m[5], f32x4 y[3]) {
-    const f32x4 s12 = m[1] + m[2], d12 = m[1] - m[2];
-    y[0] = m[0] + s12 + m[3];
-    y[1] = d12 + 2.f * m[3];
-    y[2] = s12 + 4.f * m[3] + m[4];
-}
-template <int A> __device__ __forceinline__ void btv(const f32x4* d, f32x4* v) { if constexpr (A == 6) bt6v(d, v); else bt5v(d, v); }
-template <int A> __device__ __forceinline__ void atq(const f32x4* m, f32x4* y) { if constexpr (A == 6) at6t(m, y); else at5q(m, y); }
 
 // tile t of type (MR, MC) -> image, origin of its outputs
 template <int MR, int MC>
@@ -58,16 +43,12 @@ __device__ __forceinline__ void in_mixed_body(const WinoInMixedArgs& a, int tau,
     const int kc = blockIdx.y * 4 + wave;
     const int tl = lane >> 1, hh = lane & 1;
     const long long t = (long long)mb * 32 + tl;
-    float* vout = a.V[tau] + (((size_t)mb * a.nkc + kc) * XP) * 256 + (hh * 32 + tl) * 4;
-    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-    if (t >= a.T[tau]) {
-#pragma unroll
-        for (int e = 0; e < XP; ++e) *reinterpret_cast<f32x4*>(vout + e * 256) = zero4;
-        return;
-    }
+    float* vout = wino_frag_ptr<XP>(a.V[tau], mb, a.nkc, kc, hh, tl);
+    if (t >= a.T[tau]) { wino_frag_zero<XP>(vout); return; }
     int n, q, r0, c0;
     mixed_tile<MR, MC>(a.g, t, &n, &q, &r0, &c0);
     const float* xn = a.x + (size_t)n * a.H * a.W * a.pitch + kc * 8 + hh * 4;
+    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
     f32x4 tmp[AR][AC];
 #pragma unroll
     for (int j = 0; j < AC; ++j) {
@@ -116,31 +97,22 @@ __global__ __launch_bounds__(256) void k_wino_in_mixed(const WinoInMixedArgs a) 
 constexpr int CIM_PX = 2 * 14 * 14;
 template <int MR, int MC>
 __device__ __forceinline__ void combine_mixed_tiles(const WinoInMixedArgs& a, const float* s_x, int n_first, int n_imgs) {
-    constexpr int AR = MR + 2, AC = MC + 2, X = AR * AC, XP = (X + 3) / 4 * 4, TAU = 2 * (MR == 3) + (MC == 3);
+    constexpr int AR = MR + 2, AC = MC + 2, XP = (AR * AC + 3) / 4 * 4, TAU = 2 * (MR == 3) + (MC == 3);
     const int lane = threadIdx.x & 63;
     const int tile = lane >> 3, quad = lane & 7;            // 8 tiles (2 images x 4 of this type), 4-channel quad of the block's 32
     const int il = tile >> 2, q = tile & 3;
     const int kc = blockIdx.y * 4 + (quad >> 1), hf = quad & 1;
     const int t = (n_first + il) * 4 + q;                   // tile index within the type: 4 tiles per image
-    float* vout = a.V[TAU] + (((size_t)(t >> 5) * a.nkc + kc) * XP) * 256 + (hf * 32 + (t & 31)) * 4;
-    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+    float* vout = wino_frag_ptr<XP>(a.V[TAU], t >> 5, a.nkc, kc, hf, t & 31);
     if (blockIdx.x == gridDim.x - 1) {
-        // the rows of the last 32-tile group behind this block's two images: zero, as k_wino_in_mixed leaves them (V rows >= T
-        // are defined for every producer; the GEMM computes them and drops the results)
+        // the rows of the last 32-tile group behind this block's two images: zero, as k_wino_in_mixed leaves them
         const int t_end = (int)((a.T[TAU] + 31) / 32) * 32;
-        for (int tz = (n_first + 2) * 4 + tile; tz < t_end; tz += 8) {
-            float* vz = a.V[TAU] + (((size_t)(tz >> 5) * a.nkc + kc) * XP) * 256 + (hf * 32 + (tz & 31)) * 4;
-#pragma unroll
-            for (int e = 0; e < XP; ++e) *reinterpret_cast<f32x4*>(vz + e * 256) = zero4;
-        }
+        for (int tz = (n_first + 2) * 4 + tile; tz < t_end; tz += 8) wino_frag_zero<XP>(wino_frag_ptr<XP>(a.V[TAU], tz >> 5, a.nkc, kc, hf, tz & 31));
     }
-    if (il >= n_imgs) {
-#pragma unroll
-        for (int e = 0; e < XP; ++e) *reinterpret_cast<f32x4*>(vout + e * 256) = zero4;
-        return;
-    }
+    if (il >= n_imgs) { wino_frag_zero<XP>(vout); return; }
     const int ai = q >> 1, bi = q & 1;
     const int r0 = MR == 4 ? a.g.o4[ai] : a.g.o3[ai], c0 = MC == 4 ? a.g.o4[bi] : a.g.o3[bi];
+    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
     const float* xb = s_x + il * (14 * 14) * 32 + quad * 4;
     f32x4 d[AR][AC];
 #pragma unroll
@@ -154,47 +126,17 @@ __device__ __forceinline__ void combine_mixed_tiles(const WinoInMixedArgs& a, co
             if (okh && (unsigned)wi < 14u) d[i][j] = *reinterpret_cast<const f32x4*>(xb + (hi * 14 + wi) * 32);
         }
     }
-#pragma unroll
-    for (int j = 0; j < AC; ++j) {
-        f32x4 col[AR], v[AR];
-#pragma unroll
-        for (int i = 0; i < AR; ++i) col[i] = d[i][j];
-        btv<AR>(col, v);
-#pragma unroll
-        for (int i = 0; i < AR; ++i) d[i][j] = v[i];
-    }
-#pragma unroll
-    for (int i = 0; i < AR; ++i) {
-        f32x4 v[AC];
-        btv<AC>(d[i], v);
-#pragma unroll
-        for (int j = 0; j < AC; ++j) *reinterpret_cast<f32x4*>(vout + (i * AC + j) * 256) = v[j];
-    }
-#pragma unroll
-    for (int e = X; e < XP; ++e) *reinterpret_cast<f32x4*>(vout + e * 256) = zero4;
+    wino_patch_to_frags<AR, AC>(d, vout);
 }
 
 __global__ __launch_bounds__(256) void k_combine_in_mixed(const float* __restrict__ res, const float* __restrict__ scale,
                                                          const float* __restrict__ sh, float* __restrict__ out,
                                                          const WinoInMixedArgs a, int C) {
     __shared__ __attribute__((aligned(16))) float s_x[CIM_PX * 32];
-    const int tid = threadIdx.x, wave = tid >> 6;
-    const int HW = 14 * 14;
+    const int wave = threadIdx.x >> 6;
     const int n_first = blockIdx.x * 2;
     const int n_imgs = a.N - n_first < 2 ? a.N - n_first : 2;
-    const int cb = blockIdx.y * 32;
-    {   // phase 1: x of the block's images, 8 lanes per pixel line
-        const int q4 = (tid & 7) * 4;
-        const int npx = n_imgs * HW;
-        for (int p = tid >> 3; p < npx; p += 32) {
-            const int il = p / HW;
-            const size_t off = ((size_t)n_first * HW + p) * C + cb + q4;
-            const f32x4 sv = scale ? *reinterpret_cast<const f32x4*>(scale + (size_t)(n_first + il) * C + cb + q4) : (f32x4){1.f, 1.f, 1.f, 1.f};
-            const f32x4 x = *reinterpret_cast<const f32x4*>(res + off) * sv + *reinterpret_cast<const f32x4*>(sh + off);
-            *reinterpret_cast<f32x4*>(out + off) = x;
-            *reinterpret_cast<f32x4*>(s_x + p * 32 + q4) = x;
-        }
-    }
+    combine_to_lds(res, scale, sh, out, s_x, n_first, n_imgs * 14 * 14, 14 * 14, C, blockIdx.y * 32);      // phase 1
     __syncthreads();
     switch (wave) {         // phase 2: one tile type per wave
         case 0: combine_mixed_tiles<4, 4>(a, s_x, n_first, n_imgs); break;
@@ -297,8 +239,7 @@ hipError_t launch_combine_in_mixed(const float* res, const float* scale, const f
 }
 
 // ---- the fused GEMM + output transform -----------------------------------------------------------------------------
-constexpr int WM_EPI_FLOATS = 36 * 32 * 32;
-constexpr int WM_LDS_BYTES = (WM_EPI_FLOATS + 9 * 64 + 32 * 8) * 4;
+constexpr int WM_LDS_BYTES = (WF_EPI_FLOATS + 9 * 64 + 32 * 8) * 4;      // E + bias table + tile table
 
 template <int MR, int MC>
 __device__ __forceinline__ void fused_mixed_body(const WinoMixedArgs& a, int tau, int mb, int nb, float* smem) {
@@ -310,108 +251,33 @@ __device__ __forceinline__ void fused_mixed_body(const WinoMixedArgs& a, int tau
     const int n0 = nb * 64;
     unsigned long long st0 = 0, st1 = 0, st2 = 0, st3 = 0, sr0 = 0;      // trace build (option wf_trace): shader-clock stamps of the phases
     if (FFR_TRACE_ON(a.trace)) { st0 = __builtin_amdgcn_s_memtime(); sr0 = __builtin_amdgcn_s_memrealtime(); }
-    float* const s_bias = smem + WM_EPI_FLOATS;                       // [9][64] border-class biases of this channel group
-    int* const s_tile = reinterpret_cast<int*>(s_bias + 9 * 64);     // [32][8]: origin pixel, valid, top/bottom row, left/right col, tile-sum slot
-    for (int i = tid; i < (a.border_bias ? 9 : 1) * 64; i += 256) s_bias[i] = a.bias[(size_t)(i >> 6) * a.cout_pad + n0 + (i & 63)];
+    float* const s_bias = smem + WF_EPI_FLOATS;
+    int* const s_tile = reinterpret_cast<int*>(s_bias + 9 * 64);     // [4]: tile-sum slot
+    wf_fill_bias<NT>(s_bias, a.bias, a.border_bias, a.cout_pad, n0);
     if (tid < 32) {
         const long long t = (long long)mb * 32 + tid;
-        int pix0 = 0, valid = 0, br = 0, bc = 0, tslot = 0;
-        if (t < a.T[tau]) {
-            int n, q, r0, c0;
-            mixed_tile<MR, MC>(a.g, t, &n, &q, &r0, &c0);
-            pix0 = (n * a.H + r0) * a.W + c0;
-            valid = 1;
-            // row i of the tile is the map's top row iff r0 == 0 && i == 0; its bottom row iff i == H - 1 - r0
-            br = (r0 == 0 ? 1 : 0) | ((a.H - 1 - r0) & 0xff) << 8;
-            bc = (c0 == 0 ? 1 : 0) | ((a.W - 1 - c0) & 0xff) << 8;
-            tslot = n * a.tpi_total + a.tpi_off[tau] + q;
-        }
-        s_tile[tid * 8 + 0] = pix0; s_tile[tid * 8 + 1] = valid; s_tile[tid * 8 + 2] = br; s_tile[tid * 8 + 3] = bc;
-        s_tile[tid * 8 + 4] = tslot;
+        const bool valid = t < a.T[tau];
+        int n = 0, q = 0, r0 = 0, c0 = 0;
+        if (valid) mixed_tile<MR, MC>(a.g, t, &n, &q, &r0, &c0);
+        wf_tile_record(s_tile + tid * 8, valid, n, r0, c0, MR, MC, a.H, a.W);
+        s_tile[tid * 8 + 4] = valid ? n * a.tpi_total + a.tpi_off[tau] + q : 0;
     }
-    // operand streams through buffer resources (see k_wino_fused): per-lane offset in one VGPR, the rest scalar
-    const __amdgpu_buffer_rsrc_t vrs = __builtin_amdgcn_make_buffer_rsrc((void*)(a.V[tau] + (size_t)mb * nkc * XP * 256), 0, (unsigned)nkc * XP * 1024u, 0x00020000);
-    const __amdgpu_buffer_rsrc_t urs = __builtin_amdgcn_make_buffer_rsrc((void*)a.U[tau], 0, (unsigned)((size_t)a.cout_pad * nkc * 8 * XP * 4), 0x00020000);
-    const unsigned lane16 = (unsigned)lane * 16u;
-    unsigned vp = (unsigned)(S * wave) * 1024u;
-    unsigned up = (unsigned)(nb * nkc * XP + S * wave) * 2048u;
-    auto ldfrag = [&](const __amdgpu_buffer_rsrc_t& rs, unsigned so) {
-        return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, lane16, so, 0));
-    };
-    const int rowl = lane & 31;
     f32x16 acc[8][NT], accv[NT];
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            accv[nt][r] = 0.f;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) acc[j][nt][r] = 0.f;
-        }
-    f32x4 fv[S], fu[S][NT];
-    auto load = [&](int j, int part, unsigned v, unsigned u) {
-        if (part == 0) fv[j] = ldfrag(vrs, v + j * 1024u);
-        else fu[j][part - 1] = ldfrag(urs, u + j * 2048u + (part - 1) * 1024u);
-    };
-#pragma unroll
-    for (int j = 0; j < S - 1; ++j) {
-#pragma unroll
-        for (int part = 0; part <= NT; ++part) load(j, part, vp, up);
-        FFR_PIN;
-    }
-    FFR_PIN;
-    if (FFR_TRACE_ON(a.trace)) st1 = __builtin_amdgcn_s_memtime();
-    auto chunk = [&]<bool LAST>() {
-#pragma unroll
-        for (int j = 0; j < S; ++j) {
-            const f32x4 av = fv[j], b0 = fu[j][0], b1 = fu[j][1];
-#pragma unroll
-            for (int g = 0; g < 4 * NT; ++g) {
-                const int e = g / NT, nt = g % NT;
-                if (j < 8) acc[j][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(nt ? b1[e] : b0[e], av[e], acc[j][nt], 0, 0, 0);
-                else asm volatile("v_mfma_f32_32x32x2_f32 %0, %1, %2, %0" : "+v"(accv[nt]) : "v"(nt ? b1[e] : b0[e]), "v"(av[e]));
-                if (g == 1) {
-#pragma unroll
-                    for (int part = 0; part <= NT; ++part) {
-                        if (j == 0) load(S - 1, part, vp, up);                                             // the last xi of this chunk
-                        else if (!LAST) load(j - 1, part, vp + XP * 1024u, up + XP * 2048u);              // xi j-1 of the next chunk
-                    }
-                }
-                FFR_PIN;
-            }
-        }
-    };
-#pragma unroll 1
-    for (int kc = 0; kc + 1 < nkc; ++kc) {
-        chunk.template operator()<false>();
-        vp += XP * 1024u;
-        up += XP * 2048u;
-    }
-    chunk.template operator()<true>();
+    wf_zero_acc<NT>(acc, accv);
+    wf_vfed_gemm<S, NT>(a.V[tau], a.U[tau], mb, nb, nkc, a.cout_pad, wave, lane, acc, accv, a.trace, st1);
     if (FFR_TRACE_ON(a.trace)) st2 = __builtin_amdgcn_s_memtime();
 
     // ---- epilogue: two passes of 32 channels through E[xi][tile][32] in LDS (as k_wino_fused), transforms per tile type ----
     if (S == 9) asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
-    const int hsel = lane >> 5;
     const int cq = lane & 7;
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
-#pragma unroll
-        for (int j = 0; j < S; ++j) {
-            const int e = S * wave + j;
-            if (e < X) {
-                const f32x16& t16 = j < 8 ? acc[j < 8 ? j : 0][nt] : accv[nt];
-#pragma unroll
-                for (int q = 0; q < 4; ++q)         // lane = tile rowl, registers 4q..4q+3 = channels 8q + 4 hsel + 0..3 (A = U, B = V): see k_wino_fused
-                    *reinterpret_cast<f32x4*>(smem + (e * 32 + rowl) * 32 + (((2 * q + hsel) ^ (rowl & 7)) * 4)) =
-                        (f32x4){t16[4 * q], t16[4 * q + 1], t16[4 * q + 2], t16[4 * q + 3]};
-            }
-        }
+        wf_stage_acc<S, X, NT>(smem, wave, lane, nt, acc, accv);
         __syncthreads();
         const int tl = (lane >> 3) + 8 * wave;
         if (s_tile[tl * 8 + 1] != 0) {                                  // else: tile beyond T
             const int pix0 = s_tile[tl * 8 + 0];
-            const f32x4* ev = reinterpret_cast<const f32x4*>(smem + tl * 32 + 4 * (cq ^ (tl & 7)));
+            const f32x4* ev = wf_staged(smem, tl, cq);
             f32x4 tmp[MR][AC];
 #pragma unroll
             for (int j = 0; j < AC; ++j) {
@@ -424,15 +290,11 @@ __device__ __forceinline__ void fused_mixed_body(const WinoMixedArgs& a, int tau
             }
             const int cl = nt * 32 + 4 * cq;
             const int cg = n0 + cl;
-            f32x4 slope = {1.f, 1.f, 1.f, 1.f};
-            if (a.slope) slope = *reinterpret_cast<const f32x4*>(a.slope + cg);
+            const f32x4 slope = wf_slope(a.slope, cg);
             int rc[MR], cc[MC];
             if (a.border_bias) {
-                const int br = s_tile[tl * 8 + 2], bc = s_tile[tl * 8 + 3];
-#pragma unroll
-                for (int i = 0; i < MR; ++i) rc[i] = ((i == 0 && (br & 1)) ? 0 : (i == (br >> 8) ? 2 : 1)) * 3 * 64;
-#pragma unroll
-                for (int i = 0; i < MC; ++i) cc[i] = ((i == 0 && (bc & 1)) ? 0 : (i == (bc >> 8) ? 2 : 1)) * 64;
+                wf_border_offsets(s_tile[tl * 8 + 2], 3 * 64, rc);
+                wf_border_offsets(s_tile[tl * 8 + 3], 64, cc);
             } else {
 #pragma unroll
                 for (int i = 0; i < MR; ++i) rc[i] = 0;
@@ -449,20 +311,14 @@ __device__ __forceinline__ void fused_mixed_body(const WinoMixedArgs& a, int tau
                     atq<AC>(tmp[i], yr);
 #pragma unroll
                     for (int jj = 0; jj < MC; ++jj) {
-                        f32x4 v = yr[jj] + *reinterpret_cast<const f32x4*>(s_bias + rc[i] + cc[jj] + cl);
-#pragma unroll
-                        for (int c = 0; c < 4; ++c) v[c] = fmaxf(v[c], 0.f) + slope[c] * fminf(v[c], 0.f);
-                        if (rb) v += *reinterpret_cast<const f32x4*>(rb + (size_t)(i * a.W + jj) * a.res_pitch);
-                        if (a.flags & 1) {
-#pragma unroll
-                            for (int c = 0; c < 4; ++c) v[c] = 1.0f / (1.0f + __expf(-v[c]));
-                        }
+                        const f32x4 v = wf_pointwise(yr[jj], *reinterpret_cast<const f32x4*>(s_bias + rc[i] + cc[jj] + cl), slope, rb != nullptr,
+                                                     [&] { return *reinterpret_cast<const f32x4*>(rb + (size_t)(i * a.W + jj) * a.res_pitch); }, a.flags);
                         *reinterpret_cast<f32x4*>(ob + (size_t)(i * a.W + jj) * a.out_pitch) = v;
                         psum += v;
                     }
                 }
             }
-            if (a.tile_sums) *reinterpret_cast<f32x4*>(a.tile_sums + (size_t)s_tile[tl * 8 + 4] * a.cout_pad + cg) = psum;
+            if (a.tile_sums) wf_store_tile_sum(a.tile_sums, s_tile[tl * 8 + 4], a.cout_pad, cg, psum);
         }
         __syncthreads();
         if (FFR_TRACE_ON(a.trace) && nt == 0) st3 = __builtin_amdgcn_s_memtime();
@@ -481,27 +337,17 @@ __device__ __forceinline__ void fused_mixed_body(const WinoMixedArgs& a, int tau
 
 __global__ __launch_bounds__(256, 1) void k_wino_fused_mixed(const WinoMixedArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    // blocks ordered by type: [ (4,4) | (4,3) | (3,4) | (3,3) ]; inside a type the map of k_wino_fused (the channel groups of a tile
-    // group next to each other on one XCD)
-    const int b = blockIdx.x;
-    int tau, nb, mb;
-    if (a.xcd_pairs) {
-        // Round 5: the XCDs specialise in PAIRS of tile types.  Blocks b and b + 8 share an XCD (round-robin dispatch); XCDs 0-3 run
-        // (4,4) in the first half of the grid and (3,3) in the second, XCDs 4-7 run (4,3) then (3,4): every CU still pairs a long block
-        // with a short one (9 + 7 = 8 + 8 slots), but an XCD's L2 streams TWO weight sets per launch instead of four (268 -> 134 MB of
-        // the 405 MB a 256 -> 256 launch fetched: every XCD read all four sets once).  Inside a type: tile groups round-robin over the
-        // four XCDs of its pair, the channel groups of a tile group next to each other on one XCD (V from that L2).
-        const int half = b >= a.boff[1];                    // boff[1] = blocks of the first half (a multiple of 8)
-        const int bl = b - (half ? a.boff[1] : 0);
-        const int xcd = bl & 7, idx = bl >> 3;
-        tau = xcd < 4 ? (half ? 3 : 0) : (half ? 2 : 1);
-        nb = idx % a.nbn; mb = (idx / a.nbn) * 4 + (xcd & 3);
-    } else {
-        tau = b >= a.boff[2] ? (b >= a.boff[3] ? 3 : 2) : (b >= a.boff[1] ? 1 : 0);
-        const int bl = b - a.boff[tau];
-        const int xcd = bl & 7, idx = bl >> 3;
-        nb = idx % a.nbn; mb = (idx / a.nbn) * 8 + xcd;
-    }
+    // The XCDs specialise in PAIRS of tile types.  Blocks b and b + 8 share an XCD (round-robin dispatch); XCDs 0-3 run
+    // (4,4) in the first half of the grid and (3,3) in the second, XCDs 4-7 run (4,3) then (3,4): every CU pairs a long block
+    // with a short one (9 + 7 = 8 + 8 slots), and an XCD's L2 streams TWO weight sets per launch instead of four (268 -> 134 MB of
+    // the 405 MB a 256 -> 256 launch fetched with the types in four consecutive ranges, where every XCD read all four sets once:
+    // EXPERIMENTS.md, round 5).  Inside a type: tile groups round-robin over the four XCDs of its pair, the channel groups of a
+    // tile group next to each other on one XCD (V from that L2).
+    const int half = blockIdx.x >= a.half_blocks;       // half_blocks is a multiple of 8
+    const int bl = blockIdx.x - (half ? a.half_blocks : 0);
+    const int xcd = bl & 7, idx = bl >> 3;
+    const int tau = xcd < 4 ? (half ? 3 : 0) : (half ? 2 : 1);
+    const int nb = idx % a.nbn, mb = (idx / a.nbn) * 4 + (xcd & 3);
     if (mb >= a.mbn[tau]) return;
     switch (tau) {
         case 0: fused_mixed_body<4, 4>(a, 0, mb, nb, smem); break;
@@ -524,38 +370,30 @@ hipError_t launch_wino_fused_mixed(WinoMixedArgs a, hipStream_t stream) {
     wino_mixed_counts(a.g, a.N, a.T, a.mbn);
     a.nbn = a.cout_pad / 64;
     const float* vbase = a.V[0];
-    int tot = 0, tpi = 0;
+    int tpi = 0;
     for (int tau = 0; tau < 4; ++tau) {
         a.V[tau] = vbase + off[tau];
-        a.boff[tau] = tot;
-        tot += (a.mbn[tau] + 7) / 8 * 8 * a.nbn;
         const int nr = MIXED_MR[tau] == 4 ? a.g.n4 : a.g.n3, nc = MIXED_MC[tau] == 4 ? a.g.n4 : a.g.n3;
         a.tpi_off[tau] = tpi;
         tpi += nr * nc;
     }
     a.tpi_total = tpi;
-    if (a.xcd_pairs) {
-        // every type has the same number of tile groups on a square map (n4 * n3 tiles per image each way): two halves of
-        // 8 * ceil(groups / 4) * nbn blocks
-        int gmax = 0;
-        for (int tau = 0; tau < 4; ++tau) gmax = a.mbn[tau] > gmax ? a.mbn[tau] : gmax;
-        const int half = (gmax + 3) / 4 * 8 * a.nbn;
-        a.boff[0] = 0; a.boff[1] = half; a.boff[2] = half; a.boff[3] = half;
-        tot = 2 * half;
-    }
+    const int tot = wino_mixed_blocks_launched(a.N, a.H, a.W, a.cout_pad);
+    a.half_blocks = tot / 2;
     hipLaunchKernelGGL(k_wino_fused_mixed, dim3(tot), dim3(256), WM_LDS_BYTES, stream, a);
     return hipGetLastError();
 }
 
-// grid size of launch_wino_fused_mixed (tile groups rounded up to 8 per type for the XCD-aware map)
-int wino_mixed_blocks_launched(int N, int H, int W, int cout_pad, int xcd_pairs) {
+// grid size of launch_wino_fused_mixed: two halves of 8 * ceil(groups / 4) * nbn blocks (every type has the same number of tile
+// groups on a square map, n4 * n3 tiles per image each way; a pair of types shares the four XCDs of its quad)
+int wino_mixed_blocks_launched(int N, int H, int W, int cout_pad) {
     WinoMixedGeom g;
     if (!wino_mixed_geom(H, W, &g)) return 0;
     long long T[4]; int groups[4];
     wino_mixed_counts(g, N, T, groups);
-    int tot = 0, gmax = 0;
-    for (int tau = 0; tau < 4; ++tau) { tot += (groups[tau] + 7) / 8 * 8 * (cout_pad / 64); gmax = groups[tau] > gmax ? groups[tau] : gmax; }
-    return xcd_pairs ? 2 * ((gmax + 3) / 4 * 8 * (cout_pad / 64)) : tot;
+    int gmax = 0;
+    for (int tau = 0; tau < 4; ++tau) gmax = groups[tau] > gmax ? groups[tau] : gmax;
+    return 2 * ((gmax + 3) / 4 * 8 * (cout_pad / 64));
 }
 
 size_t wino_mixed_u_floats(int tau, int cout_pad, int cin_pad) { return (size_t)(cout_pad / 64) * (cin_pad / 8) * wino_mixed_xp(tau) * 512; }

@@ -121,6 +121,7 @@ WINO_CASES = [
     (700, 28, 28, 128, 64, 0, False, False),  # 34300 tiles: GEMM rows beyond 2^15
     (40, 56, 56, 64, 128, 0, True, True),     # two channel groups, two phases, residual through the q-form epilogue
     (33, 30, 22, 96, 192, 1, True, False),    # reflect padding, ragged map, three phases, last tile group partly empty
+    (3, 9, 9, 256, 68, 0, True, True),        # V-fed, ragged 9x9 tiles over both edges, 4 of the second channel group's 64 channels stored
 ]
 
 
