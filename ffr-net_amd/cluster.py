@@ -9,6 +9,13 @@ grouped by person and every group fused into one template row:
 
 The clustering is single-link at one cosine threshold: rows i < j are joined iff their search score is > threshold, and
 a cluster is a connected component of those edges.  It runs on the device; only pairwise_scores() is host logic.
+
+A collection that keeps growing is extended instead of clustered again (include/ffrnet.h: ffr_cluster_extend): only the
+pairs that involve a new row are scored, and the result is the clustering of all rows at once, label for label:
+
+  store = cluster.Incremental(engine, threshold)
+  store.add(f_batch)                                 # as often as faces arrive; must_link= ties the frames of one track
+  t = store.templates()                              # when a gallery is wanted
 """
 import collections
 
@@ -29,6 +36,121 @@ def dense_ids(rep):
 def cluster(engine, emb, threshold, norms=None):
     """Single-link clustering of emb[N,512] (fp32, on the Engine's device) at `threshold` -> Clusters."""
     return dense_ids(engine.cluster(emb, threshold, norms=norms))
+
+
+def representatives(labels):
+    """Arbitrary integer labels[N] (track ids, person ids; any device) -> rep[N] int64: the first row index that carries
+    each row's label.  Plain torch.  This is the `prior` form of Engine.cluster_extend: rows with equal labels are tied."""
+    labels = torch.as_tensor(labels).reshape(-1)
+    n = labels.numel()
+    _, inv = torch.unique(labels, return_inverse=True)
+    row = torch.arange(n, device=labels.device, dtype=torch.int64)
+    first = torch.full((n,), n, device=labels.device, dtype=torch.int64).scatter_reduce_(0, inv, row, 'amin')
+    return first[inv]
+
+
+def changes(rep_before, rep_after):
+    """What an extension did to the clusters that existed: -> (stale, now), both int64.  stale holds the rows that were
+    representatives in rep_before and are none in rep_after (their cluster was absorbed by one with a smaller first row),
+    now[k] = rep_after[stale[k]], the cluster they went to.  A caller that keeps one template per cluster drops the
+    templates of `stale` and recomputes those of `now`; clusters that merely gained rows keep their representative and
+    show up in neither."""
+    rep_before, rep_after = torch.as_tensor(rep_before).reshape(-1), torch.as_tensor(rep_after).reshape(-1)
+    n = rep_before.numel()
+    if rep_after.numel() < n:
+        raise ValueError('changes: %d labels before, %d after' % (n, rep_after.numel()))
+    row = torch.arange(n, device=rep_before.device, dtype=torch.int64)
+    after = rep_after[:n].to(rep_before.device)
+    stale = row[(rep_before == row) & (after != row)]
+    return stale, after[stale]
+
+
+def _new_prior(n_old, n_new, must_link, device):
+    """prior of n_new rows appended at n_old: each row itself, or the first new row with its must_link label"""
+    if must_link is None:
+        return torch.arange(n_old, n_old + n_new, device=device, dtype=torch.int64)
+    must_link = torch.as_tensor(must_link).reshape(-1)
+    if must_link.numel() != n_new:
+        raise RuntimeError('ffrnet_amd: %d must_link labels for %d new rows' % (must_link.numel(), n_new))
+    return representatives(must_link).to(device) + n_old
+
+
+def extend(engine, emb, threshold, earlier, norms=None, must_link=None):
+    """Extend a clustering of the first rows of emb[N,512] to all N rows -> Clusters, equal to cluster(engine, emb,
+    threshold) when `earlier` is the clustering of emb[:n_old] at this threshold.  earlier: a Clusters or a rep[n_old]
+    (n_old = 0: a clustering from scratch).  must_link: integer labels of the N - n_old new rows (track ids); new rows
+    with equal labels are in one cluster whatever they score.  Only the pairs with a new row are scored."""
+    rep = earlier.rep if isinstance(earlier, Clusters) else torch.as_tensor(earlier)
+    rep = rep.reshape(-1).to(device=emb.device, dtype=torch.int64)
+    n_old, n = rep.numel(), emb.size(0)
+    if n_old > n:
+        raise RuntimeError('ffrnet_amd: %d earlier labels for %d embeddings' % (n_old, n))
+    prior = torch.cat((rep, _new_prior(n_old, n - n_old, must_link, emb.device)))
+    return dense_ids(engine.cluster_extend(emb, threshold, prior, n_old, norms=norms, out=prior))
+
+
+class Incremental(object):
+    """A clustering that keeps being added to: embeddings [n,512], their norms and rep[n] on the Engine's device, in
+    grow-only buffers (as search.Gallery).  add() scores the new rows against everything held and among themselves; after
+    every add the labels are those of one clustering of all rows held.  Rows keep their index for ever; rep of an old
+    row can only decrease (cluster.changes tells which clusters were absorbed)."""
+
+    def __init__(self, engine, threshold, capacity=0):
+        self.engine = engine
+        self.threshold = float(threshold)
+        self._n = 0
+        self._emb = torch.empty((int(capacity), 512), device=engine.device, dtype=torch.float32)
+        self._norms = torch.empty((int(capacity),), device=engine.device, dtype=torch.float32)
+        self._rep = torch.empty((int(capacity),), device=engine.device, dtype=torch.int64)
+
+    def __len__(self):
+        return self._n
+
+    @property
+    def embeddings(self):
+        return self._emb[:self._n]
+
+    @property
+    def norms(self):
+        return self._norms[:self._n]
+
+    @property
+    def rep(self):
+        return self._rep[:self._n]
+
+    @property
+    def clusters(self):
+        return dense_ids(self.rep)
+
+    def templates(self):
+        """One unit template per cluster of the rows held -> [C,512], row c for cluster id c."""
+        return templates(self.engine, self.embeddings, self.clusters, norms=self.norms)
+
+    def add(self, emb, must_link=None):
+        """Append emb[n,512] (fp32, on the Engine's device) and extend the clustering -> the index of its first row.
+        must_link: integer labels of these n rows; equal labels are tied (the frames of one track)."""
+        if not isinstance(emb, torch.Tensor) or emb.dim() != 2 or emb.size(1) != 512:
+            raise RuntimeError('ffrnet_amd: Incremental.add expects [n,512] embeddings, got %s'
+                               % (list(emb.shape) if isinstance(emb, torch.Tensor) else type(emb)))
+        n, first = emb.size(0), self._n
+        new_prior = _new_prior(first, n, must_link, self._rep.device)
+        if first + n > self._emb.size(0):
+            cap = max(first + n, 2 * self._emb.size(0), 1024)
+            grown = []
+            for buf in (self._emb, self._norms, self._rep):
+                new = torch.empty((cap,) + tuple(buf.shape[1:]), device=buf.device, dtype=buf.dtype)
+                new[:first] = buf[:first]
+                grown.append(new)
+            self._emb, self._norms, self._rep = grown
+        if n:
+            total = first + n
+            self._emb[first:total] = emb
+            self._norms[first:total] = self.engine.row_norms(self._emb[first:total])
+            self._rep[first:total] = new_prior
+            self.engine.cluster_extend(self._emb[:total], self.threshold, self._rep[:total], first,
+                                       norms=self._norms[:total], validate=False, out=self._rep[:total])
+            self._n = total
+        return first
 
 
 def member_order(clusters):

@@ -1,12 +1,15 @@
 // cluster.hip -- group N unlabelled 512-d embeddings into identities on the device (include/ffrnet.h:
-// ffr_cluster_threshold / ffr_cluster_templates): single-link clustering at one cosine threshold, then one template row
-// per cluster.  The N x N score matrix never leaves the chip; the output is one label per row.
+// ffr_cluster_threshold / ffr_cluster_extend / ffr_cluster_templates): single-link clustering at one cosine threshold,
+// extended batch by batch where the collection grows, then one template row per cluster.  The N x N score matrix never
+// leaves the chip; the output is one label per row.
 //
 // Edge rule: rows i < j are joined iff s(probe = i, gallery row = j) > threshold (strict, as eval_acc compares), with
 // s = dot / (|i| |j| + 1e-8) in exactly the fp32 arithmetic of k_search_topk (search.hip): the score of (i, j) is
 // bit-for-bit the score ffr_search_topk returns for probe i and gallery row j.  The diagonal and i > j are never evaluated.
 //
 // k_cluster_init     parent[x] = x.
+// k_cluster_seed     ffr_cluster_extend's start: parent[x] = prior[x] where 0 <= prior[x] <= x, else x.  The only place
+//                    where caller data reaches parent[]; see "Seeded start" below.
 // k_cluster_join     the hot path: the self-join of the [N][512] array with itself.
 //  - K loop: the 32 x 128 cosine tile of cosine_tile.h, the one k_search_topk instantiates: the bitwise identity of the edge
 //    scores with the scores of ffr_search_topk is structural.
@@ -16,6 +19,12 @@
 //    sizes the chunks so that the blocks with work, about half of it, fill the CUs several times over: their work is uneven
 //    along the diagonal); the idle half costs one early return each.  Known cost (EXPERIMENTS.md): an XCD takes a
 //    contiguous run of tiles, so the XCD with the long rows of the triangle finishes last.
+//  - Row range: k_cluster_join<true> (ffr_cluster_extend) lays the chunks over the rows [first, N) only and the tiles over
+//    all probes [0, N): the pairs i < j with j >= first, i.e. the first x (N - first) rectangle plus the triangle among
+//    the new rows.  Chunk bases, the early return, step0 and the edge test work on absolute row numbers; with first = 0
+//    they are those of k_cluster_join<false>, the instantiation ffr_cluster_threshold launches, which is compiled with the
+//    constant 0.  All tiles of one chunk of new rows are neighbours in the XCD-contiguous block map, and the old rows are
+//    read once per chunk into LDS as probes.  Over the old rows no block is idle and none sits on the diagonal.
 //  - Epilogue: no list, no LDS merge.  Lane (n, h) holds the 16 scores of probe q0 + n; every (i, j) with i < j, j inside
 //    the chunk and score > threshold is united in a lock-free union-find over parent[N] (int32, the handle's scratch):
 //      find   walk parent[] to a root r (parent[r] == r);
@@ -34,6 +43,14 @@
 //    L2 or this CU's L1; a stale value is still a valid (older) ancestor, but the loads that decide "already one root" and
 //    the CAS must see the memory the atomics of the other XCDs work on.  Vector atomics only.
 //    No path compression: a walk is bounded by the component's size, and the clusters of a face collection are small.
+//    Seeded start: properties (1) and (2) ask of the START only that parent[] is a forest with parent[x] <= x.  The seed
+//    writes prior[x] only where 0 <= prior[x] <= x and x otherwise, so (1) holds at the first instant whatever the caller
+//    passed (a cycle in parent[] would be a hang, an index outside [0, N) a fault), and afterwards by the same argument: a
+//    CAS replaces parent[x] only from x, by something smaller.  In such a forest every walk descends to a row that points
+//    to itself, so the root of a tree is its smallest member, as (2) needs; from there on only roots are hooked, under
+//    smaller members of other trees, and every tree keeps one root, its smallest row.  The components at the end are those
+//    of (links x - prior[x]) + (scored edges), and the flattened result is their smallest row whatever the order.  A deep
+//    prior (prior[x] = x - 1) is legal and walked hop by hop: callers pass flattened labels.
 // k_cluster_flatten  rep[i] = find(i) as int64, after the join in stream order.
 // k_cluster_templates  one template per cluster: t = sum_r x_r / |x_r| over the cluster's rows in ascending row index
 //                (order[] = rows sorted by cluster then index, offsets[C + 1]), then t / |t|.  One wave per cluster, lane
@@ -85,6 +102,14 @@ __global__ __launch_bounds__(256) void k_cluster_init(int* __restrict__ parent, 
     if (x < n) parent[x] = x;
 }
 
+// whatever prior[] holds, parent[x] <= x afterwards (the invariant every walk relies on) and no index leaves [0, n)
+__global__ __launch_bounds__(256) void k_cluster_seed(int* __restrict__ parent, const int64_t* __restrict__ prior, int n) {
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    if (x >= n) return;
+    const int64_t p = prior[x];
+    parent[x] = (0 <= p && p <= (int64_t)x) ? (int)p : x;
+}
+
 __global__ __launch_bounds__(256) void k_cluster_flatten(const int* __restrict__ parent, int n, int64_t* __restrict__ rep) {
     const int x = blockIdx.x * 256 + threadIdx.x;
     if (x < n) rep[x] = uf_find(parent, x);
@@ -98,8 +123,11 @@ struct JoinArgs {
     long long chunk_rows;     // rows per chunk (the last one may be shorter), a multiple of CT_STEP, <= CT_MAX_CHUNK
     float threshold;
     int nchunks, ntiles;
+    long long first;          // RANGE: the chunks cover the rows [first, N)
 };
 
+// RANGE = false: the chunks cover all rows (first is not read)
+template <bool RANGE>
 __global__ __launch_bounds__(256, 1) void k_cluster_join(const JoinArgs a) {
     __shared__ __attribute__((aligned(16))) f32x4 qf[CT_NG * 64];    // probe fragments [64][64]
 
@@ -108,7 +136,7 @@ __global__ __launch_bounds__(256, 1) void k_cluster_join(const JoinArgs a) {
 
     int chunk, tile;
     cosine_block(a.ntiles, chunk, tile);
-    const long long c0 = (long long)chunk * a.chunk_rows;
+    const long long c0 = (RANGE ? a.first : 0) + (long long)chunk * a.chunk_rows;
     const long long rem = a.N - c0;
     const int rows = (int)(rem < a.chunk_rows ? rem : a.chunk_rows);    // >= 1
     const int q0 = tile * CT_QT;
@@ -212,6 +240,34 @@ void cluster_plan(long long N, int num_cus, int* ntiles, int* nchunks, long long
     cosine_chunks(*ntiles, N, 8, num_cus, nchunks, chunk_rows);
 }
 
+// The chunks cover the N - N_old new rows only, the tiles every probe.  Of the chunks x tiles rectangle the share
+// 1 - N_new / 2N has work (all of it over the old rows, half of it over the new rows' own triangle): the same aim of 4
+// working blocks per CU gives 8 N / (2 N - N_new) blocks per CU, 8 at N_old = 0 (cluster_plan) and 4 for a small batch.
+void cluster_extend_plan(long long N_old, long long N, int num_cus, int* ntiles, int* nchunks, long long* chunk_rows) {
+    const long long n_new = N - N_old;
+    *ntiles = (int)((N + CT_QT - 1) / CT_QT);
+    const long long per_cu = N > 0 ? (8 * N + 2 * N - n_new - 1) / (2 * N - n_new) : 8;
+    cosine_chunks(*ntiles, n_new, per_cu, num_cus, nchunks, chunk_rows);
+}
+
+hipError_t launch_cluster_extend(const float* emb, const float* norms, long long N_old, long long N, float threshold, int ntiles,
+                                 int nchunks, long long chunk_rows, const int64_t* prior, int* parent, int64_t* rep,
+                                 hipStream_t stream) {
+    if (N <= 0) return hipSuccess;
+    const unsigned nb = (unsigned)((N + 255) / 256);
+    hipLaunchKernelGGL(k_cluster_seed, dim3(nb), dim3(256), 0, stream, parent, prior, (int)N);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    if (N > 1 && N_old < N) {
+        JoinArgs a{emb, norms, parent, N, chunk_rows, threshold, nchunks, ntiles, N_old};
+        hipLaunchKernelGGL(k_cluster_join<true>, dim3((unsigned)((long long)nchunks * ntiles)), dim3(256), 0, stream, a);
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k_cluster_flatten, dim3(nb), dim3(256), 0, stream, (const int*)parent, (int)N, rep);
+    return hipGetLastError();
+}
+
 hipError_t launch_cluster_threshold(const float* emb, const float* norms, long long N, float threshold, int ntiles, int nchunks,
                                     long long chunk_rows, int* parent, int64_t* rep, hipStream_t stream) {
     if (N <= 0) return hipSuccess;
@@ -220,8 +276,8 @@ hipError_t launch_cluster_threshold(const float* emb, const float* norms, long l
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     if (N > 1) {
-        JoinArgs a{emb, norms, parent, N, chunk_rows, threshold, nchunks, ntiles};
-        hipLaunchKernelGGL(k_cluster_join, dim3((unsigned)((long long)nchunks * ntiles)), dim3(256), 0, stream, a);
+        JoinArgs a{emb, norms, parent, N, chunk_rows, threshold, nchunks, ntiles, 0};
+        hipLaunchKernelGGL(k_cluster_join<false>, dim3((unsigned)((long long)nchunks * ntiles)), dim3(256), 0, stream, a);
         e = hipGetLastError();
         if (e != hipSuccess) return e;
     }

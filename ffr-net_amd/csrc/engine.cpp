@@ -307,6 +307,23 @@ int ffr_topk_merge(ffr_handle* h, const float* score, const int64_t* index, int 
 }
 
 // ---- clustering (cluster.hip) ----------------------------------------------------------------------------------------
+// scratch of ffr_cluster_threshold / ffr_cluster_extend: row norms [N] (used when the caller passes none), then parent [N]
+static int cluster_scratch(ffr_handle* h, long long N, float** own_norms, int** parent) {
+    const size_t norm_bytes = ((size_t)N * 4 + 255) & ~(size_t)255;
+    const size_t need = norm_bytes + (size_t)N * 4;
+    if (need > h->cluster_bytes) {
+        if (h->cluster_buf) { hipDeviceSynchronize(); hipFree(h->cluster_buf); h->cluster_buf = nullptr; h->cluster_bytes = 0; }
+        void* p = nullptr;
+        if (hipMalloc(&p, need) != hipSuccess) return fail(h, FFR_ERR_NOMEM, "hipMalloc of %zu clustering bytes failed", need);
+        h->cluster_buf = (char*)p;
+        h->cluster_bytes = need;
+        ++h->generation;          // a graph captured around an earlier call points at the old scratch
+    }
+    *own_norms = (float*)h->cluster_buf;
+    *parent = (int*)(h->cluster_buf + norm_bytes);
+    return FFR_OK;
+}
+
 int ffr_cluster_threshold(ffr_handle* h, const float* emb, const float* norms, long long N, int dim, float threshold,
                           int64_t* rep, void* stream) {
     FFR_DEVICE_SCOPE(h); RC(check_fwd(h, false, false, 1));
@@ -323,25 +340,48 @@ int ffr_cluster_threshold(ffr_handle* h, const float* emb, const float* norms, l
     if ((long long)T * S >= (1ll << 31))
         return fail(h, FFR_ERR_UNSUPPORTED, "ffr_cluster_threshold: N = %lld needs %lld blocks, over the grid limit", N, (long long)T * S);
     hipStream_t st = (hipStream_t)stream;
-    // scratch: row norms [N] (used when the caller passes none), then parent [N]
-    const size_t norm_bytes = ((size_t)N * 4 + 255) & ~(size_t)255;
-    const size_t need = norm_bytes + (size_t)N * 4;
-    if (need > h->cluster_bytes) {
-        if (h->cluster_buf) { hipDeviceSynchronize(); hipFree(h->cluster_buf); h->cluster_buf = nullptr; h->cluster_bytes = 0; }
-        void* p = nullptr;
-        if (hipMalloc(&p, need) != hipSuccess) return fail(h, FFR_ERR_NOMEM, "hipMalloc of %zu clustering bytes failed", need);
-        h->cluster_buf = (char*)p;
-        h->cluster_bytes = need;
-        ++h->generation;          // a graph captured around an earlier call points at the old scratch
-    }
-    float* own_norms = (float*)h->cluster_buf;
-    int* parent = (int*)(h->cluster_buf + norm_bytes);
+    float* own_norms = nullptr;
+    int* parent = nullptr;
+    RC(cluster_scratch(h, N, &own_norms, &parent));
     Scope s(h, st, FFR_KC_SCORE, (double)N * (double)(N - 1) * dim, 2.0 * (double)N * (dim + 1) + 16.0 * N);
     if (!norms) {
         HIPCK(h, launch_row_norms(emb, N, own_norms, st));
         norms = own_norms;
     }
     HIPCK(h, launch_cluster_threshold(emb, norms, N, threshold, T, S, chunk_rows, parent, rep, st));
+    return FFR_OK;
+}
+
+int ffr_cluster_extend(ffr_handle* h, const float* emb, const float* norms, long long N_old, long long N, int dim,
+                       float threshold, const int64_t* prior, int64_t* rep, void* stream) {
+    FFR_DEVICE_SCOPE(h); RC(check_fwd(h, false, false, 1));
+    if (dim != 512) return fail(h, FFR_ERR_UNSUPPORTED, "ffr_cluster_extend: dim must be 512, got %d", dim);
+    if (N < 0 || N >= (1ll << 31)) return fail(h, FFR_ERR_ARG, "ffr_cluster_extend: N must be in [0, 2^31), got %lld", N);
+    if (N_old < 0 || N_old > N) return fail(h, FFR_ERR_ARG, "ffr_cluster_extend: N_old must be in [0, N = %lld], got %lld", N, N_old);
+    if (threshold != threshold) return fail(h, FFR_ERR_ARG, "ffr_cluster_extend: the threshold is NaN");
+    if (N == 0) return FFR_OK;
+    if (!emb || !rep || !prior) return fail(h, FFR_ERR_ARG, "ffr_cluster_extend: emb / prior / rep is null");
+    if (misaligned16(emb) || ((uintptr_t)rep & 7) || ((uintptr_t)prior & 7) || ((uintptr_t)norms & 3))
+        return fail(h, FFR_ERR_ARG, "ffr_cluster_extend: emb rows must be 16-byte aligned (prior and rep 8, norms 4)");
+    const long long n_new = N - N_old;
+    const bool join = N > 1 && n_new > 0;
+    int T = 0, S = 0;
+    long long chunk_rows = 0;
+    if (join) cluster_extend_plan(N_old, N, h->num_cus, &T, &S, &chunk_rows);
+    if ((long long)T * S >= (1ll << 31))
+        return fail(h, FFR_ERR_UNSUPPORTED, "ffr_cluster_extend: N = %lld with %lld new rows needs %lld blocks, over the grid limit", N,
+                    n_new, (long long)T * S);
+    hipStream_t st = (hipStream_t)stream;
+    float* own_norms = nullptr;
+    int* parent = nullptr;
+    RC(cluster_scratch(h, N, &own_norms, &parent));
+    Scope s(h, st, FFR_KC_SCORE, (double)dim * (2.0 * (double)N_old * (double)n_new + (double)n_new * (double)(n_new - 1)),
+            2.0 * (double)N * (dim + 1) + 24.0 * N);
+    if (!norms && join) {
+        HIPCK(h, launch_row_norms(emb, N, own_norms, st));
+        norms = own_norms;
+    }
+    HIPCK(h, launch_cluster_extend(emb, norms, N_old, N, threshold, T, S, chunk_rows, prior, parent, rep, st));
     return FFR_OK;
 }
 

@@ -212,6 +212,13 @@ void cluster_plan(long long N, int num_cus, int* ntiles, int* nchunks, long long
 // parent: N ints of scratch; norms = launch_row_norms(emb); N < 2^31, nchunks * ntiles < 2^31, rows 16-byte aligned
 hipError_t launch_cluster_threshold(const float* emb, const float* norms, long long N, float threshold, int ntiles, int nchunks,
                                     long long chunk_rows, int* parent, int64_t* rep, hipStream_t stream);
+// chunking of the row-range join: the N - N_old new rows in chunks under ceil(N / 32) probe tiles; 0 <= N_old <= N, N >= 1
+void cluster_extend_plan(long long N_old, long long N, int num_cus, int* ntiles, int* nchunks, long long* chunk_rows);
+// rep[i] = smallest row of i's component under the links i - prior[i] and the edges s(i, j) > threshold, i < j, j >= N_old
+// (seed, row-range join, flatten); an entry of prior outside [0, i] counts as i; rep may be prior; otherwise as above
+hipError_t launch_cluster_extend(const float* emb, const float* norms, long long N_old, long long N, float threshold, int ntiles,
+                                 int nchunks, long long chunk_rows, const int64_t* prior, int* parent, int64_t* rep,
+                                 hipStream_t stream);
 // templates[c] = normalised sum of the normalised rows order[offsets[c] .. offsets[c+1]); norms may be null
 hipError_t launch_cluster_templates(const float* emb, const float* norms, const int64_t* order, const int64_t* offsets,
                                     long long C, float* templates, hipStream_t stream);

@@ -103,6 +103,7 @@ SYMBOLS = [
     ('ffr_topk_merge', C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     ('ffr_cluster_threshold', C.c_int, [_P, _P, _P, C.c_longlong, C.c_int, C.c_float, _P, _P]),
     ('ffr_cluster_templates', C.c_int, [_P, _P, _P, _P, _P, C.c_longlong, C.c_int, _P, _P]),
+    ('ffr_cluster_extend', C.c_int, [_P, _P, _P, C.c_longlong, C.c_longlong, C.c_int, C.c_float, _P, _P, _P]),
     ('ffr_align_transforms', C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, _P]),
     ('ffr_align_warp', C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_longlong, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
     ('ffr_embed_aligned', C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_longlong, _P, _P, _P, C.c_int, _P, C.c_int, _P, _P, _P,
@@ -507,6 +508,37 @@ class Engine(object):
         with torch.cuda.device(self.device):
             self._ck(self.lib.ffr_cluster_threshold(self._h, _ptr(emb if N else None), _ptr(norms), N, emb.size(1),
                                                     float(threshold), _ptr(rep), self._stream()))
+        return rep
+
+    def cluster_extend(self, emb, threshold, prior, n_old, norms=None, validate=True, out=None):
+        """Extend a clustering by new rows: emb[N,512] holds all rows, the first n_old of them clustered before.  prior[N]
+        (device int64) is a labelling in representative form, prior[i] <= i: the earlier rep for the old rows; for a new
+        row the row itself, or an earlier row it is known to belong with.  Only the pairs i < j with j >= n_old are scored
+        -> rep[N] int64, the smallest row of each component of (links i - prior[i]) + (scored edges): with prior[:n_old] =
+        cluster(emb[:n_old]) and prior[j] = j for the new rows, exactly cluster(emb).  Pass flattened labels (prior[prior[i]]
+        == prior[i]): deep chains are legal but walked hop by hop.  The kernel reads an entry outside [0, i] as i;
+        `validate` range-checks prior here first (one small sync) and raises.  out: the result tensor, prior itself allowed."""
+        emb, norms = self._cluster_rows(emb, norms, 'cluster_extend')
+        prior = self._index_tensor(prior, 'prior')
+        N, n_old = emb.size(0), int(n_old)
+        if prior.numel() != N:
+            raise RuntimeError('ffrnet_amd: prior must be [%d], got %s' % (N, list(prior.shape)))
+        if n_old < 0 or n_old > N:
+            raise RuntimeError('ffrnet_amd: cluster_extend needs 0 <= n_old <= %d, got %d' % (N, n_old))
+        if validate and N:
+            row = torch.arange(N, device=prior.device, dtype=torch.int64)
+            if bool(((prior < 0) | (prior > row)).any().item()):
+                raise RuntimeError('ffrnet_amd: cluster_extend needs 0 <= prior[i] <= i (and so < %d)' % N)
+        if out is None:
+            rep = torch.empty((N,), device=emb.device, dtype=torch.int64)
+        else:
+            rep = self._index_tensor(out, 'out')
+            if rep.numel() != N or rep.data_ptr() != out.data_ptr():
+                raise RuntimeError('ffrnet_amd: out must be a contiguous [%d] int64 tensor' % N)
+        with torch.cuda.device(self.device):
+            self._ck(self.lib.ffr_cluster_extend(self._h, _ptr(emb if N else None), _ptr(norms), n_old, N, emb.size(1),
+                                                 float(threshold), _ptr(prior if N else None), _ptr(rep if N else None),
+                                                 self._stream()))
         return rep
 
     def cluster_templates(self, emb, order, offsets, norms=None, validate=True):

@@ -173,6 +173,32 @@ int ffr_cluster_threshold(ffr_handle* h, const float* emb, const float* norms, l
  * templates[C][dim] fp32, 16-byte aligned.  Errors as above (C in place of N).                                        */
 int ffr_cluster_templates(ffr_handle* h, const float* emb, const float* norms, const int64_t* order, const int64_t* offsets,
                           long long C, int dim, float* templates, void* stream);
+/* Extend a clustering by new rows, equal to clustering everything.  emb[N][dim] holds ALL rows, the earlier ones first;
+ * the rows [N_old, N) are new.  norms[N] or NULL as above.
+ *   prior  prior[N] int64, a labelling in representative form: prior[i] <= i names a row already known to belong with i.
+ *          For a row clustered before it is the earlier rep; for a new row it is the row itself, or an earlier row it must
+ *          be linked to whatever it scores (a frame of the same track).
+ *   scored exactly the pairs i < j with j >= N_old: the N_old x (N - N_old) rectangle plus the triangle among the new
+ *          rows.  Roles, score bits and the strict > are those of ffr_cluster_threshold: the smaller index is the probe.
+ *   result rep[N] int64 (rep == prior, in place, is allowed): rep[i] = the smallest row of i's connected component under
+ *          (links i - prior[i]) + (scored edges).  So rep[i] <= the root of i in prior <= i, rep[rep[i]] == rep[i], and the
+ *          labels of OLD rows change where a new row bridges two old clusters.  The components of an edge set do not depend
+ *          on the order in which the edges are met: repeated calls are bitwise equal, and
+ *          (a) if prior[:N_old] is ffr_cluster_threshold of the first N_old rows at this threshold and prior[j] = j for the
+ *              new j, rep equals ffr_cluster_threshold over all N rows, bit for bit -- also batch after batch;
+ *          (b) N_old = N scores nothing and returns the flattened prior (rep[i] = the root of i);
+ *          (c) N_old = 0 is a full clustering under must-links.
+ *   guard  an entry of prior outside [0, i] is read as i: the row starts alone.  The termination argument above rests on
+ *          parent[x] <= x, and the seed is the only place where caller data reaches parent[], so it makes that true whatever
+ *          it is given.  Deep priors (a chain prior[i] = i - 1) are legal but walked hop by hop, without compression: pass
+ *          flattened labels (the rep of an earlier call is flat).
+ *   errors as ffr_cluster_threshold; FFR_ERR_ARG also for N_old < 0, N_old > N, and a null or not 8-byte-aligned prior when
+ *          N > 0.  N = 0 succeeds and touches nothing.
+ *   memory no host synchronisation; the scratch of ffr_cluster_threshold (norms, parent) is shared, grows and bumps
+ *          ffr_generation under the same rule; the two calls may alternate freely on one handle.
+ * Profiled as one launch under FFR_KC_SCORE with flops = 512 * (2 * N_old * N_new + N_new * (N_new - 1)), N_new = N - N_old. */
+int ffr_cluster_extend(ffr_handle* h, const float* emb, const float* norms, long long N_old, long long N, int dim,
+                       float threshold, const int64_t* prior, int64_t* rep, void* stream);
 
 /* ---- face alignment (landmarks -> similarity transform -> aligned uint8 crop) ---------------------------------------
  * Replaces the reference's host preprocessing, lfw/gen_lfw112x96.py:6-17 (align) with lfw/matlab_cp2tform.py
