@@ -1,6 +1,7 @@
 // Types and helpers shared by the host translation units of libffrnet_hip.so: plan.cpp (convolution planner), conv.cpp
 // (launchers), pack.cpp (weight packer, ffr_load_*), forward.cpp (workspace and forward pipelines), engine.cpp (the rest of
-// the C ABI) and train.cpp (the RecNet training step).  Not part of the public interface.
+// the C ABI) and train_layer.cpp / train_graph.cpp / train_params.cpp (the RecNet training step; their own types are in
+// train_internal.h).  Not part of the public interface.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -24,7 +25,7 @@ namespace ffr_eng {
 
 using namespace ffr;
 
-struct TrainState;   // train.cpp
+struct TrainState;   // train_internal.h
 
 struct ConvW {
     int cin = 0, cin_pad = 0, cout = 0, cout_pad = 0, R = 1, S = 1, stride = 1, pad = 0, pad_mode = 0, border = 0;
@@ -122,7 +123,7 @@ struct ffr_handle {
     bool prof = false;
     std::vector<ffr_eng::ProfRec> prof_log;
     std::vector<hipEvent_t> ev_pool;
-    // RecNet training state (train.cpp), or null
+    // RecNet training state (train_params.cpp), or null
     ffr_eng::TrainState* train = nullptr;
     // weight-gradient launch plans of the most recent backward (ffr_train_wgrad_plan)
     std::vector<ffr_wgrad_launch> wgrad_log;
@@ -327,7 +328,7 @@ int gemm_rows(ffr_handle* h, const Work& w, const float* A, int a_pitch, int K_p
 int gemm_batched(ffr_handle* h, const Work& w, const float* A, long long a_bstride, int K_pad, const float* W,
                  long long w_bstride, int N_pad, float* out, int out_pitch, long long out_bstride, int M, int nbatch,
                  hipStream_t st);
-// train.cpp
+// train_params.cpp
 void train_free(ffr_handle* h);
 
 }  // namespace ffr_eng

@@ -81,9 +81,6 @@ hipError_t launch_fold_reflect(const float* dxp, int p_pitch, int imgs, int C, c
                                int add_coff, float* out, int out_pitch, int out_coff, hipStream_t stream);
 
 // ---- small elementwise pieces ------------------------------------------------------------------
-// out[row][c] = a[row][a_coff+c] (+ b[row][b_coff+c])
-hipError_t launch_add_slices(const float* a, int a_pitch, int a_coff, const float* b, int b_pitch, int b_coff,
-                             float* out, int out_pitch, int out_coff, int rows, int C, hipStream_t stream);
 // g[row][c] *= s[row][c] * (1 - s[row][c])     (backward of a sigmoid whose OUTPUT is s)
 hipError_t launch_sigmoid_bwd(float* g, int g_pitch, const float* s, int s_pitch, int rows, int C, hipStream_t stream);
 // d feat[n][p][c] = df[n][c] / 49 (+ add[n][p][c])     (AvgPool2d(7) backward)

@@ -428,29 +428,6 @@ hipError_t launch_fold_reflect(const float* dxp, int p_pitch, int imgs, int C, c
 }
 
 // ---- small elementwise pieces --------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_add_slices(const float* __restrict__ a, int a_pitch, int a_coff,
-                                                   const float* __restrict__ b, int b_pitch, int b_coff,
-                                                   float* __restrict__ out, int out_pitch, int out_coff, long long total4,
-                                                   int C) {
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= total4) return;
-    const int cq = C >> 2;
-    const long long row = idx / cq;
-    const int c = (int)(idx - row * cq) * 4;
-    f32x4 v = *reinterpret_cast<const f32x4*>(a + row * a_pitch + a_coff + c);
-    if (b) v += *reinterpret_cast<const f32x4*>(b + row * b_pitch + b_coff + c);
-    *reinterpret_cast<f32x4*>(out + row * out_pitch + out_coff + c) = v;
-}
-
-hipError_t launch_add_slices(const float* a, int a_pitch, int a_coff, const float* b, int b_pitch, int b_coff,
-                             float* out, int out_pitch, int out_coff, int rows, int C, hipStream_t stream) {
-    if ((C | a_pitch | a_coff | b_pitch | b_coff | out_pitch | out_coff) & 3) return hipErrorInvalidValue;
-    const long long total4 = (long long)rows * (C >> 2);
-    hipLaunchKernelGGL(k_add_slices, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, stream, a, a_pitch, a_coff, b,
-                       b_pitch, b_coff, out, out_pitch, out_coff, total4, C);
-    return hipGetLastError();
-}
-
 __global__ __launch_bounds__(256) void k_sigmoid_bwd(float* __restrict__ g, int g_pitch, const float* __restrict__ s,
                                                     int s_pitch, long long total, int C) {
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;

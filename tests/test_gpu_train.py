@@ -792,6 +792,35 @@ def test_train_forward_small_and_odd_batches(engine, specs, n):
             assert rel(sd_after[k], v) < 2e-4, k
 
 
+def test_contexts_and_scratch_regrow_on_a_live_handle(specs):
+    """Contexts and backward scratch that grow and are carved again on a live handle: training iterations (without the
+    optimiser step: the parameters stay) at 1 pair, 3 pairs, then 1 pair again on ONE handle.  1 pair is the smallest batch
+    the BatchNorm statistics accept; 3 is odd and makes both the context and the scratch be reallocated; the last
+    iteration carves a smaller context beside a scratch that stays the larger one.  After each, the flat gradient buffer and
+    the five loss outputs equal, bit for bit, those of a fresh handle that only ever ran that size on the same inputs."""
+    sd_e = synth.synth_state_dict(specs['encoder'], seed=0)
+    sd_r = synth.synth_state_dict(specs['recnet'], seed=0)
+    batches = {n: tuple(t.cuda() for t in synth.synth_train_batch(n, seed=60 + n)) for n in (1, 3)}
+
+    def handle():
+        eng = ffrnet_amd.Engine(0)
+        eng.load_encoder(sd_e)
+        return ffrnet_amd.NativeTrainer(eng, sd_r)       # ffr_train_init + the view of the flat gradient buffer
+
+    def iteration(tr, n):
+        out5 = tr.engine.train_iteration(*batches[n])
+        torch.cuda.synchronize()
+        return out5.clone(), tr.flat_grads.clone()
+
+    want = {n: iteration(handle(), n) for n in (1, 3)}
+    live = handle()
+    for step, n in enumerate((1, 3, 1)):
+        out5, grads = iteration(live, n)
+        assert torch.isfinite(out5).all() and grads.abs().max() > 0, (step, n)
+        assert torch.equal(out5, want[n][0]), (step, n, out5, want[n][0])
+        assert torch.equal(grads, want[n][1]), (step, n, (grads - want[n][1]).abs().max().item())
+
+
 def test_trained_weights_feed_the_eval_path(specs):
     """After training iterations the exported state_dict (torch layouts, running statistics) must drive the
     verification path like any checkpoint: oracle eval forward == native eval forward on it, and the RecNet
