@@ -53,8 +53,8 @@ hipError_t launch_bn_apply(const float* y, int Cp, int G, int rows_g, BnBuffers 
 // backward of [BN(batch stats) -> PReLU]: da = gradient wrt the PReLU output ([rows][da_pitch] at da_coff).
 // reduce: per group sums -> b.c1, b.c2 and dgamma/dbeta/dslope (+= when accumulate); apply: dy[rows][Cp].
 hipError_t launch_bn_bwd(const float* da, int da_pitch, int da_coff, const float* y, int Cp, int G, int rows_g,
-                         BnBuffers b, const float* gamma, const float* slope, float* dgamma, float* dbeta,
-                         float* dslope, int accumulate, float* dy, double* part, hipStream_t stream);
+                         BnBuffers b, const float* slope, float* dgamma, float* dbeta, float* dslope, int accumulate,
+                         float* dy, double* part, hipStream_t stream);
 
 // ---- data-gradient helpers ---------------------------------------------------------------------
 // Wd[ci][8 - t][co] = W[co][t][ci]: the rotated / transposed 3x3 weights of the data-gradient convolution.

@@ -123,7 +123,7 @@ int layer_backward(ffr_handle* h, const Work& w, TScratch& s, int G, int N, cons
     const TLayer& L = b.L; const TSaved& sv = b.sv;
     const int imgs = G * N, rows = imgs * 49;
     RC(check_scratch(h, s, L, imgs));
-    TLAUNCH(FFR_KC_TRAIN_BN, launch_bn_bwd(b.da.p, b.da.pitch, b.da.coff, sv.y, L.cout_pad, G, N * 49, sv.bn, L.gamma, L.slope, L.ggamma, L.gbeta,
+    TLAUNCH(FFR_KC_TRAIN_BN, launch_bn_bwd(b.da.p, b.da.pitch, b.da.coff, sv.y, L.cout_pad, G, N * 49, sv.bn, L.slope, L.ggamma, L.gbeta,
                                            L.gslope, b.accumulate, s.dy, s.part, st));
     const long long T = (long long)imgs * 4;          // 2x2 tiles of 4x4 outputs per 7x7 map
     const double useful = 2.0 * rows * 9.0 * L.cout * L.cin;

@@ -1,20 +1,43 @@
-// Elementwise / reduction kernels of the RecNet training step: train-mode BatchNorm (batch statistics
-// per group) + PReLU forward and backward, the adjoint of the reflection padding, weight re-layout for
-// the data-gradient convolution.  HBM-streaming kernels: lanes run along the channels (NHWC), 16-byte
-// accesses where the layout allows, per-channel sums in fp64 (slice partials, fixed combination order).
-// Reference: models/recnet.py:52-85 (ConvLayer), :119-147 (NormLayer = nn.BatchNorm2d), :87-117 (PReLU).
+// Every kernel of the RecNet training step that is not a convolution or a GEMM:
+//   - train-mode BatchNorm (batch statistics per group) + PReLU, forward and backward; the data-gradient helpers (weight
+//     re-layout, 8x8 canvas, edge rows, adjoint of the reflection padding); small elementwise pieces
+//     (models/recnet.py:52-85 ConvLayer, :119-147 NormLayer = nn.BatchNorm2d, :87-117 PReLU);
+//   - the Conv4Channel / Conv4Space layout helpers, the CosFace head, Adam, torch <-> kernel parameter layouts;
+//   - the four loss items of Trainer.backward with their gradients.
+// HBM-streaming kernels: lanes run along the channels (NHWC), 16-byte accesses where the layout allows.  Every sum has
+// a fixed order: per-channel sums are fp64 slice partials that meet in lanes4_sum(), block sums in block_sum_double().
 #include "device_util.h"
 #include "train_kernels.h"
 
 namespace ffr {
 
-// rows are cut into at most 32 slices per group (the *_final kernels walk the slices serially per channel)
-static int n_slices(int rows_g) {
-    const int n = (rows_g + 97) / 98;
-    return n > 32 ? 32 : n;
+// The slice rule of the per-channel sums: 98 rows per slice until `cap` slices are reached, then `cap` even slices
+// (the *_final kernels walk the slices serially per channel).
+struct Slices { int n, rows; };
+static Slices slices(int rows, int cap) {
+    int n = (rows + 97) / 98;
+    if (n > cap) n = cap;
+    return {n, (rows + n - 1) / n};
 }
-static int slice_rows(int rows_g) { const int n = n_slices(rows_g); return (rows_g + n - 1) / n; }
-size_t bn_part_doubles(int G, int rows_g, int Cp) { return (size_t)G * n_slices(rows_g) * 3 * Cp; }
+static const int BN_SLICE_CAP = 32;
+size_t bn_part_doubles(int G, int rows_g, int Cp) { return (size_t)G * slices(rows_g, BN_SLICE_CAP).n * 3 * Cp; }
+
+// The one definition of a per-channel fp64 sum: a block is 64 channels x 4 lanes (of rows, slices or images) and every
+// thread brings the K running sums of its lane.  The lanes meet in LDS and are added as (0 + 1) + (2 + 3).  That order
+// is part of the contract (bitwise repeatable steps, exact resume, byte-identical dumps), so no kernel spells it out
+// again.  True for the first 64 threads, which now hold the totals in v.  A caller that uses sh again (a group loop)
+// puts a barrier in front of the call.
+template <int K>
+__device__ __forceinline__ bool lanes4_sum(double (&v)[K], double (*sh)[4][64]) {
+    const int t = threadIdx.x & 63, l = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < K; ++k) sh[k][l][t] = v[k];
+    __syncthreads();
+    if (threadIdx.x >= 64) return false;
+#pragma unroll
+    for (int k = 0; k < K; ++k) v[k] = (sh[k][0][t] + sh[k][1][t]) + (sh[k][2][t] + sh[k][3][t]);
+    return true;
+}
 
 // grid (Cp/64, nslices, G), block 256 = 64 channels x 4 row lanes
 __global__ __launch_bounds__(256) void k_bn_stats_partial(const float* __restrict__ y, int Cp, int rows_g, int SLICE_ROWS,
@@ -23,23 +46,17 @@ __global__ __launch_bounds__(256) void k_bn_stats_partial(const float* __restric
     const int s = blockIdx.y, g = blockIdx.z, nsl = gridDim.y;
     const int r0 = s * SLICE_ROWS;
     const int r1 = min(r0 + SLICE_ROWS, rows_g);
-    double a = 0.0, b = 0.0;
+    double a[2] = {0.0, 0.0};                 // sum y, sum y^2
     const float* yp = y + (size_t)g * rows_g * Cp + c;
     for (int r = r0 + rl; r < r1; r += 4) {
         const double v = (double)yp[(size_t)r * Cp];
-        a += v; b += v * v;
+        a[0] += v; a[1] += v * v;
     }
     __shared__ double sh[2][4][64];
-    sh[0][rl][threadIdx.x & 63] = a;
-    sh[1][rl][threadIdx.x & 63] = b;
-    __syncthreads();
-    if (threadIdx.x < 64) {
-        const int t = threadIdx.x;
-        a = (sh[0][0][t] + sh[0][1][t]) + (sh[0][2][t] + sh[0][3][t]);
-        b = (sh[1][0][t] + sh[1][1][t]) + (sh[1][2][t] + sh[1][3][t]);
+    if (lanes4_sum(a, sh)) {
         double* p = part + ((size_t)(g * nsl + s) * 3) * Cp + c;
-        p[0] = a;
-        p[Cp] = b;
+        p[0] = a[0];
+        p[Cp] = a[1];
     }
 }
 
@@ -57,19 +74,15 @@ __global__ __launch_bounds__(256) void k_bn_stats_final(const double* __restrict
         rv = running_var ? running_var[c] : 0.f;
     }
     for (int g = 0; g < G; ++g) {
-        double s1 = 0.0, s2 = 0.0;
+        double a[2] = {0.0, 0.0};
         for (int s = sl; s < nsl; s += 4) {
             const double* p = part + ((size_t)(g * nsl + s) * 3) * Cp + c;
-            s1 += p[0]; s2 += p[Cp];
+            a[0] += p[0]; a[1] += p[Cp];
         }
         __syncthreads();
-        sh[0][sl][t] = s1; sh[1][sl][t] = s2;
-        __syncthreads();
-        if (threadIdx.x < 64) {
-            s1 = (sh[0][0][t] + sh[0][1][t]) + (sh[0][2][t] + sh[0][3][t]);
-            s2 = (sh[1][0][t] + sh[1][1][t]) + (sh[1][2][t] + sh[1][3][t]);
-            const double mean = s1 / rows_g;
-            double var = s2 / rows_g - mean * mean;
+        if (lanes4_sum(a, sh)) {
+            const double mean = a[0] / rows_g;
+            double var = a[1] / rows_g - mean * mean;
             if (var < 0.0) var = 0.0;
             const float invstd = (float)(1.0 / sqrt(var + (double)eps));
             const float sc = gamma[c] * invstd;
@@ -92,9 +105,9 @@ hipError_t launch_bn_stats(const float* y, int Cp, int G, int rows_g, const floa
                            float* running_mean, float* running_var, float momentum, float eps, BnBuffers b,
                            double* part, hipStream_t stream) {
     if (Cp % 64 || G <= 0 || rows_g <= 0) return hipErrorInvalidValue;
-    const int nsl = n_slices(rows_g);
-    hipLaunchKernelGGL(k_bn_stats_partial, dim3(Cp / 64, nsl, G), dim3(256), 0, stream, y, Cp, rows_g, slice_rows(rows_g), part);
-    hipLaunchKernelGGL(k_bn_stats_final, dim3(Cp / 64), dim3(256), 0, stream, part, Cp, G, nsl, rows_g, gamma, beta,
+    const Slices sl = slices(rows_g, BN_SLICE_CAP);
+    hipLaunchKernelGGL(k_bn_stats_partial, dim3(Cp / 64, sl.n, G), dim3(256), 0, stream, y, Cp, rows_g, sl.rows, part);
+    hipLaunchKernelGGL(k_bn_stats_final, dim3(Cp / 64), dim3(256), 0, stream, part, Cp, G, sl.n, rows_g, gamma, beta,
                        running_mean, running_var, momentum, eps, b);
     return hipGetLastError();
 }
@@ -150,25 +163,22 @@ __global__ __launch_bounds__(256) void k_bn_bwd_partial(const float* __restrict_
     const int r1 = min(r0 + SLICE_ROWS, rows_g);
     const float sc = b.scale[g * Cp + c], sh = b.shift[g * Cp + c], mu = b.mean[g * Cp + c], is = b.invstd[g * Cp + c];
     const float sl = slope[c];
-    double s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    double a[3] = {0.0, 0.0, 0.0};            // S1, S2, S3
     for (int r = r0 + rl; r < r1; r += 4) {
         const size_t row = (size_t)g * rows_g + r;
         const float yv = y[row * Cp + c];
         const float d = da[row * da_pitch + da_coff + c];
         const float z = yv * sc + sh;
         const float dz = z > 0.f ? d : d * sl;
-        s1 += (double)dz;
-        s2 += (double)dz * (double)((yv - mu) * is);
-        if (!(z > 0.f)) s3 += (double)d * (double)z;
+        a[0] += (double)dz;
+        a[1] += (double)dz * (double)((yv - mu) * is);
+        if (!(z > 0.f)) a[2] += (double)d * (double)z;
     }
     __shared__ double sh3[3][4][64];
-    const int t = threadIdx.x & 63;
-    sh3[0][rl][t] = s1; sh3[1][rl][t] = s2; sh3[2][rl][t] = s3;
-    __syncthreads();
-    if (threadIdx.x < 64) {
+    if (lanes4_sum(a, sh3)) {
         double* p = part + ((size_t)(g * nsl + s) * 3) * Cp + c;
 #pragma unroll
-        for (int k = 0; k < 3; ++k) p[(size_t)k * Cp] = (sh3[k][0][t] + sh3[k][1][t]) + (sh3[k][2][t] + sh3[k][3][t]);
+        for (int k = 0; k < 3; ++k) p[(size_t)k * Cp] = a[k];
     }
 }
 
@@ -179,21 +189,16 @@ __global__ __launch_bounds__(256) void k_bn_bwd_final(const double* __restrict__
     const int c = blockIdx.x * 64 + t;
     double tg = 0.0, tb = 0.0, ts = 0.0;
     for (int g = 0; g < G; ++g) {
-        double s1 = 0.0, s2 = 0.0, s3 = 0.0;
+        double a[3] = {0.0, 0.0, 0.0};
         for (int s = sl; s < nsl; s += 4) {
             const double* p = part + ((size_t)(g * nsl + s) * 3) * Cp + c;
-            s1 += p[0]; s2 += p[Cp]; s3 += p[2 * (size_t)Cp];
+            a[0] += p[0]; a[1] += p[Cp]; a[2] += p[2 * (size_t)Cp];
         }
         __syncthreads();
-        sh[0][sl][t] = s1; sh[1][sl][t] = s2; sh[2][sl][t] = s3;
-        __syncthreads();
-        if (threadIdx.x < 64) {
-            s1 = (sh[0][0][t] + sh[0][1][t]) + (sh[0][2][t] + sh[0][3][t]);
-            s2 = (sh[1][0][t] + sh[1][1][t]) + (sh[1][2][t] + sh[1][3][t]);
-            s3 = (sh[2][0][t] + sh[2][1][t]) + (sh[2][2][t] + sh[2][3][t]);
-            b.c1[g * Cp + c] = (float)(s1 / rows_g);
-            b.c2[g * Cp + c] = (float)(s2 / rows_g);
-            tb += s1; tg += s2; ts += s3;
+        if (lanes4_sum(a, sh)) {
+            b.c1[g * Cp + c] = (float)(a[0] / rows_g);
+            b.c2[g * Cp + c] = (float)(a[1] / rows_g);
+            tb += a[0]; tg += a[1]; ts += a[2];
         }
     }
     if (threadIdx.x < 64) {
@@ -231,14 +236,13 @@ __global__ __launch_bounds__(256) void k_bn_bwd_apply(const float* __restrict__ 
 }
 
 hipError_t launch_bn_bwd(const float* da, int da_pitch, int da_coff, const float* y, int Cp, int G, int rows_g,
-                         BnBuffers b, const float* gamma, const float* slope, float* dgamma, float* dbeta,
-                         float* dslope, int accumulate, float* dy, double* part, hipStream_t stream) {
-    (void)gamma;
+                         BnBuffers b, const float* slope, float* dgamma, float* dbeta, float* dslope, int accumulate,
+                         float* dy, double* part, hipStream_t stream) {
     if (Cp % 64 || ((da_pitch | da_coff) & 3)) return hipErrorInvalidValue;
-    const int nsl = n_slices(rows_g);
-    hipLaunchKernelGGL(k_bn_bwd_partial, dim3(Cp / 64, nsl, G), dim3(256), 0, stream, da, da_pitch, da_coff, y, Cp, rows_g,
-                       slice_rows(rows_g), b, slope, part);
-    hipLaunchKernelGGL(k_bn_bwd_final, dim3(Cp / 64), dim3(256), 0, stream, part, Cp, G, nsl, rows_g, b, dgamma, dbeta,
+    const Slices sl = slices(rows_g, BN_SLICE_CAP);
+    hipLaunchKernelGGL(k_bn_bwd_partial, dim3(Cp / 64, sl.n, G), dim3(256), 0, stream, da, da_pitch, da_coff, y, Cp, rows_g,
+                       sl.rows, b, slope, part);
+    hipLaunchKernelGGL(k_bn_bwd_final, dim3(Cp / 64), dim3(256), 0, stream, part, Cp, G, sl.n, rows_g, b, dgamma, dbeta,
                        dslope, accumulate);
     const long long total4 = (long long)G * rows_g * (Cp >> 2);
     hipLaunchKernelGGL(k_bn_bwd_apply, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, stream, da, da_pitch, da_coff, y,
@@ -247,11 +251,11 @@ hipError_t launch_bn_bwd(const float* da, int da_pitch, int da_coff, const float
 }
 
 // ---- data-gradient helpers -------------------------------------------------------------------------
-// 32x32 (co, ci) tiles of one tap through LDS: reads coalesced along ci, writes coalesced along co
-__global__ __launch_bounds__(256) void k_pack_dgrad(const float* __restrict__ W, int cout_pad, int cin_pad,
-                                                   float* __restrict__ Wd, int cinD_pad) {
+// The 32x32 (co, ci) tile of block (x, y) of tap t of W[cout_pad][9][cin_pad] through LDS: reads coalesced along ci, writes
+// coalesced along co.  Row ci (< rows_out) lands in slot `slot` of dst[rows_out][nslots][cout_pad]; ci >= cin_pad reads 0.
+__device__ __forceinline__ void transpose_tap_tile(const float* __restrict__ W, int cout_pad, int cin_pad, int t,
+                                                   float* __restrict__ dst, int nslots, int slot, int rows_out) {
     __shared__ float tile[32][33];
-    const int t = blockIdx.z;
     const int ci0 = blockIdx.x * 32, co0 = blockIdx.y * 32;
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;    // 8 rows per pass
     for (int i = ty; i < 32; i += 8) {
@@ -261,8 +265,15 @@ __global__ __launch_bounds__(256) void k_pack_dgrad(const float* __restrict__ W,
     __syncthreads();
     for (int i = ty; i < 32; i += 8) {
         const int ci = ci0 + i;
-        if (ci < cinD_pad) Wd[((size_t)ci * 9 + (8 - t)) * cout_pad + co0 + tx] = tile[tx][i];
+        if (ci < rows_out) dst[((size_t)ci * nslots + slot) * cout_pad + co0 + tx] = tile[tx][i];
     }
+}
+
+// Wd[ci][8 - t][co] = W[co][t][ci]: blockIdx.z = tap
+__global__ __launch_bounds__(256) void k_pack_dgrad(const float* __restrict__ W, int cout_pad, int cin_pad,
+                                                   float* __restrict__ Wd, int cinD_pad) {
+    const int t = blockIdx.z;
+    transpose_tap_tile(W, cout_pad, cin_pad, t, Wd, 9, 8 - t, cinD_pad);
 }
 
 hipError_t launch_pack_dgrad(const float* W, int cout_pad, int cin_pad, float* Wd, int cinD_pad, hipStream_t stream) {
@@ -324,25 +335,13 @@ hipError_t launch_dgrad_edges(const float* dy, float* Eb, float* Er, int imgs, i
     return hipGetLastError();
 }
 
-// 32x32 (co, ci) tiles through LDS, as k_pack_dgrad; blockIdx.z = which of the 6 taps (3 bottom, 3 right)
+// blockIdx.z = which of the 6 taps (3 bottom, 3 right)
 __global__ __launch_bounds__(256) void k_pack_dgrad_edges(const float* __restrict__ W, int cout_pad, int cin_pad,
                                                          float* __restrict__ Wb, float* __restrict__ Wr, int rows_out) {
-    __shared__ float tile[32][33];
     const int z = blockIdx.z;
     const int k = z % 3;
     const int t = z < 3 ? 2 * 3 + k : k * 3 + 2;        // bottom: (r = 2, s = k); right: (r = k, s = 2)
-    float* dst = z < 3 ? Wb : Wr;
-    const int ci0 = blockIdx.x * 32, co0 = blockIdx.y * 32;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    for (int i = ty; i < 32; i += 8) {
-        const int ci = ci0 + tx;
-        tile[i][tx] = ci < cin_pad ? W[((size_t)(co0 + i) * 9 + t) * cin_pad + ci] : 0.f;
-    }
-    __syncthreads();
-    for (int i = ty; i < 32; i += 8) {
-        const int ci = ci0 + i;
-        if (ci < rows_out) dst[((size_t)ci * 3 + k) * cout_pad + co0 + tx] = tile[tx][i];
-    }
+    transpose_tap_tile(W, cout_pad, cin_pad, t, z < 3 ? Wb : Wr, 3, k, rows_out);
 }
 
 hipError_t launch_pack_dgrad_edges(const float* W, int cout_pad, int cin_pad, float* Wb, float* Wr, int rows_out,
@@ -353,10 +352,13 @@ hipError_t launch_pack_dgrad_edges(const float* W, int cout_pad, int cin_pad, fl
     return hipGetLastError();
 }
 
-__global__ __launch_bounds__(256) void k_fold_reflect3(const float* __restrict__ main8, const float* __restrict__ bottom,
-                                                      const float* __restrict__ right, int p_pitch, long long total4, int C,
-                                                      const float* __restrict__ add, int add_pitch, int add_coff,
-                                                      float* __restrict__ out, int out_pitch, int out_coff) {
+// Adjoint of the reflection padding: out[img][h][w] = the sum of the pixels (qh, qw) of the image's padded 9x9 gradient that
+// read (h, w) (+ add).  Padded coordinate q in [0,9) reads original refl(q - 1); (h) is read by q = h + 1 and, for h = 1,
+// q = 0, for h = 5, q = 8.  Src says where pixel (qh, qw) lives: Src::at(img, qh, qw) -> its row of p_pitch floats.
+template <class Src>
+__device__ __forceinline__ void fold_reflect(const Src src, int p_pitch, long long total4, int C,
+                                             const float* __restrict__ add, int add_pitch, int add_coff,
+                                             float* __restrict__ out, int out_pitch, int out_coff) {
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= total4) return;
     const int cq = C >> 2;
@@ -371,15 +373,37 @@ __global__ __launch_bounds__(256) void k_fold_reflect3(const float* __restrict__
         const int qh = a == 0 ? h + 1 : (h == 1 ? 0 : 8);
         for (int bq = 0; bq < nw; ++bq) {
             const int qw = bq == 0 ? w + 1 : (w == 1 ? 0 : 8);
-            const float* src;
-            if (qh == 8) src = bottom + ((size_t)img * 9 + qw) * p_pitch;
-            else if (qw == 8) src = right + ((size_t)img * 8 + qh) * p_pitch;
-            else src = main8 + ((size_t)img * 64 + qh * 8 + qw) * p_pitch;
-            s += *reinterpret_cast<const f32x4*>(src + c);
+            s += *reinterpret_cast<const f32x4*>(src.at(img, qh, qw, p_pitch) + c);
         }
     }
     if (add) s += *reinterpret_cast<const f32x4*>(add + row * add_pitch + add_coff + c);
     *reinterpret_cast<f32x4*>(out + row * out_pitch + out_coff + c) = s;
+}
+
+// the 9x9 gradient in three pieces: rows / columns 0..7 as an 8x8 map, the bottom row [9], the right column [8]
+struct FoldSrc3 {
+    const float* __restrict__ main8;
+    const float* __restrict__ bottom;
+    const float* __restrict__ right;
+    __device__ __forceinline__ const float* at(long long img, int qh, int qw, int p_pitch) const {
+        if (qh == 8) return bottom + ((size_t)img * 9 + qw) * p_pitch;
+        if (qw == 8) return right + ((size_t)img * 8 + qh) * p_pitch;
+        return main8 + ((size_t)img * 64 + qh * 8 + qw) * p_pitch;
+    }
+};
+// the 9x9 gradient as one map
+struct FoldSrc9 {
+    const float* __restrict__ dxp;
+    __device__ __forceinline__ const float* at(long long img, int qh, int qw, int p_pitch) const {
+        return dxp + ((size_t)img * 81 + qh * 9 + qw) * p_pitch;
+    }
+};
+
+__global__ __launch_bounds__(256) void k_fold_reflect3(const float* __restrict__ main8, const float* __restrict__ bottom,
+                                                      const float* __restrict__ right, int p_pitch, long long total4, int C,
+                                                      const float* __restrict__ add, int add_pitch, int add_coff,
+                                                      float* __restrict__ out, int out_pitch, int out_coff) {
+    fold_reflect(FoldSrc3{main8, bottom, right}, p_pitch, total4, C, add, add_pitch, add_coff, out, out_pitch, out_coff);
 }
 
 hipError_t launch_fold_reflect3(const float* main8, const float* bottom, const float* right, int p_pitch, int imgs, int C,
@@ -392,30 +416,10 @@ hipError_t launch_fold_reflect3(const float* main8, const float* bottom, const f
     return hipGetLastError();
 }
 
-// padded coordinate q in [0,9) reads original refl(q - 1); (h) is read by q = h + 1 and, for h = 1, q = 0,
-// for h = 5, q = 8
 __global__ __launch_bounds__(256) void k_fold_reflect(const float* __restrict__ dxp, int p_pitch, long long total4, int C,
                                                      const float* __restrict__ add, int add_pitch, int add_coff,
                                                      float* __restrict__ out, int out_pitch, int out_coff) {
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= total4) return;
-    const int cq = C >> 2;
-    const long long row = idx / cq;
-    const int c = (int)(idx - row * cq) * 4;
-    const long long img = row / 49;
-    const int p = (int)(row - img * 49);
-    const int h = p / 7, w = p - h * 7;
-    const int nh = (h == 1 || h == 5) ? 2 : 1, nw = (w == 1 || w == 5) ? 2 : 1;
-    f32x4 s = {0.f, 0.f, 0.f, 0.f};
-    for (int a = 0; a < nh; ++a) {
-        const int qh = a == 0 ? h + 1 : (h == 1 ? 0 : 8);
-        for (int bq = 0; bq < nw; ++bq) {
-            const int qw = bq == 0 ? w + 1 : (w == 1 ? 0 : 8);
-            s += *reinterpret_cast<const f32x4*>(dxp + ((size_t)img * 81 + qh * 9 + qw) * p_pitch + c);
-        }
-    }
-    if (add) s += *reinterpret_cast<const f32x4*>(add + row * add_pitch + add_coff + c);
-    *reinterpret_cast<f32x4*>(out + row * out_pitch + out_coff + c) = s;
+    fold_reflect(FoldSrc9{dxp}, p_pitch, total4, C, add, add_pitch, add_coff, out, out_pitch, out_coff);
 }
 
 hipError_t launch_fold_reflect(const float* dxp, int p_pitch, int imgs, int C, const float* add, int add_pitch,
@@ -476,12 +480,7 @@ hipError_t launch_fill(float* p, float v, size_t n, hipStream_t stream) {
     return hipGetLastError();
 }
 
-}  // namespace ffr
-
-// =====================================================================================================
-// second part: Conv4Channel layout helpers, CosFace head, optimiser
-namespace ffr {
-
+// ---- Conv4Channel / Conv4Space layout helpers ----------------------------------------------------------
 __global__ __launch_bounds__(256) void k_sigmoid_bwd_ext(float* __restrict__ g, const float* __restrict__ ext,
                                                         const float* __restrict__ s, size_t n4) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -506,15 +505,10 @@ __global__ __launch_bounds__(256) void k_colsum_partial(const float* __restrict_
     const int s = blockIdx.y;
     const int r0 = s * SLICE_ROWS;
     const int r1 = min(r0 + SLICE_ROWS, rows);
-    double a = 0.0;
-    for (int r = r0 + rl; r < r1; r += 4) a += (double)x[(size_t)r * pitch + c];
-    __shared__ double sh[4][64];
-    sh[rl][threadIdx.x & 63] = a;
-    __syncthreads();
-    if (threadIdx.x < 64) {
-        const int t = threadIdx.x;
-        part[(size_t)s * Cp + c] = (sh[0][t] + sh[1][t]) + (sh[2][t] + sh[3][t]);
-    }
+    double a[1] = {0.0};
+    for (int r = r0 + rl; r < r1; r += 4) a[0] += (double)x[(size_t)r * pitch + c];
+    __shared__ double sh[1][4][64];
+    if (lanes4_sum(a, sh)) part[(size_t)s * Cp + c] = a[0];
 }
 
 // 64 channels x 4 slice lanes per block
@@ -522,26 +516,21 @@ __global__ __launch_bounds__(256) void k_colsum_final(const double* __restrict__
                                                      int accumulate) {
     const int t = threadIdx.x & 63, sl = threadIdx.x >> 6;
     const int c = blockIdx.x * 64 + t;
-    double a = 0.0;
-    for (int s = sl; s < nsl; s += 4) a += part[(size_t)s * Cp + c];
-    __shared__ double sh[4][64];
-    sh[sl][t] = a;
-    __syncthreads();
-    if (threadIdx.x < 64) {
-        a = (sh[0][t] + sh[1][t]) + (sh[2][t] + sh[3][t]);
-        if (accumulate) a += out[c];
-        out[c] = (float)a;
+    double a[1] = {0.0};
+    for (int s = sl; s < nsl; s += 4) a[0] += part[(size_t)s * Cp + c];
+    __shared__ double sh[1][4][64];
+    if (lanes4_sum(a, sh)) {
+        if (accumulate) a[0] += out[c];
+        out[c] = (float)a[0];
     }
 }
 
 hipError_t launch_colsum(const float* x, int pitch, int rows, int Cp, float* out, int accumulate, double* part,
                          hipStream_t stream) {
     if (Cp % 64) return hipErrorInvalidValue;
-    int nsl = (rows + 97) / 98;            // up to 384 slices: tall, narrow inputs (131072 x 64) need the blocks
-    if (nsl > 384) nsl = 384;
-    const int sr = (rows + nsl - 1) / nsl;
-    hipLaunchKernelGGL(k_colsum_partial, dim3(Cp / 64, nsl), dim3(256), 0, stream, x, pitch, rows, Cp, sr, part);
-    hipLaunchKernelGGL(k_colsum_final, dim3(Cp / 64), dim3(256), 0, stream, part, Cp, nsl, out, accumulate);
+    const Slices sl = slices(rows, 384);   // up to 384 slices: tall, narrow inputs (131072 x 64) need the blocks
+    hipLaunchKernelGGL(k_colsum_partial, dim3(Cp / 64, sl.n), dim3(256), 0, stream, x, pitch, rows, Cp, sl.rows, part);
+    hipLaunchKernelGGL(k_colsum_final, dim3(Cp / 64), dim3(256), 0, stream, part, Cp, sl.n, out, accumulate);
     return hipGetLastError();
 }
 
@@ -567,21 +556,31 @@ hipError_t launch_transpose_pad(const float* W, int R, int C, int w_pitch, float
     return hipGetLastError();
 }
 
+// The 32 channel vectors of block (c0 / 32, n) over the 49 positions of a NHWC image: x points at (n, position 0, c0).
+// The tile [49][32] goes to t, d = max(|vector|, 1e-12) to norm[0..32) when that is not null, 1 / d to inv; t and inv are
+// readable on return.
+__device__ __forceinline__ void ch_tile_norms(const float* __restrict__ x, int pitch, float (*t)[33], float* inv,
+                                              float* __restrict__ norm) {
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    for (int p = ty; p < 49; p += 8) t[p][tx] = x[(size_t)p * pitch + tx];
+    __syncthreads();
+    if (threadIdx.x < 32) {
+        float s = 0.f;
+        for (int p = 0; p < 49; ++p) s += t[p][threadIdx.x] * t[p][threadIdx.x];
+        const float d = fmaxf(sqrtf(s), 1e-12f);
+        inv[threadIdx.x] = 1.0f / d;
+        if (norm) norm[threadIdx.x] = d;
+    }
+    __syncthreads();
+}
+
 // one block per (image, 32-channel group): tile X[49][32] through LDS
 __global__ __launch_bounds__(256) void k_ch_prep(const float* __restrict__ X, float* __restrict__ Xt,
                                                 float* __restrict__ Xht, float* __restrict__ cat) {
     __shared__ float t[49][33];
     __shared__ float inv[32];
     const int n = blockIdx.y, c0 = blockIdx.x * 32;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    for (int p = ty; p < 49; p += 8) t[p][tx] = X[((size_t)n * 49 + p) * 512 + c0 + tx];
-    __syncthreads();
-    if (threadIdx.x < 32) {
-        float s = 0.f;
-        for (int p = 0; p < 49; ++p) s += t[p][threadIdx.x] * t[p][threadIdx.x];
-        inv[threadIdx.x] = 1.0f / fmaxf(sqrtf(s), 1e-12f);
-    }
-    __syncthreads();
+    ch_tile_norms(X + (size_t)n * 49 * 512 + c0, 512, t, inv, nullptr);
     // 32 channels x 64 positions, lanes along the positions
     for (int i = threadIdx.x; i < 32 * 64; i += 256) {
         const int c = i >> 6, p = i & 63;
@@ -645,17 +644,14 @@ __global__ __launch_bounds__(256) void k_prelu_rows_bwd(float* __restrict__ dy, 
 // dslope[c] (+)= sum over the images of rowdot[n*512 + c]; 64 channels x 4 image lanes per block
 __global__ __launch_bounds__(256) void k_rowdot_to_slope(const float* __restrict__ rowdot, long long imgs, float* dslope,
                                                         int accumulate) {
-    __shared__ double sh[4][64];
+    __shared__ double sh[1][4][64];
     const int t = threadIdx.x & 63, il = threadIdx.x >> 6;
     const int c = blockIdx.x * 64 + t;
-    double a = 0.0;
-    for (long long n = il; n < imgs; n += 4) a += (double)rowdot[n * 512 + c];
-    sh[il][t] = a;
-    __syncthreads();
-    if (threadIdx.x < 64) {
-        a = (sh[0][t] + sh[1][t]) + (sh[2][t] + sh[3][t]);
-        if (accumulate) a += dslope[c];
-        dslope[c] = (float)a;
+    double a[1] = {0.0};
+    for (long long n = il; n < imgs; n += 4) a[0] += (double)rowdot[n * 512 + c];
+    if (lanes4_sum(a, sh)) {
+        if (accumulate) a[0] += dslope[c];
+        dslope[c] = (float)a[0];
     }
 }
 
@@ -837,20 +833,25 @@ hipError_t launch_mspace_grad_in(const float* dM, float* dms, int imgs, hipStrea
 }
 
 // ---- CosFace head ------------------------------------------------------------------------------------
-// one wave per row of 512
-__global__ __launch_bounds__(256) void k_row_normalize(const float* __restrict__ u, int u_pitch, float* __restrict__ v,
-                                                      float* __restrict__ norm, int rows) {
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (row >= rows) return;
-    const f32x4 a = *reinterpret_cast<const f32x4*>(u + (size_t)row * u_pitch + lane * 8);
-    const f32x4 b = *reinterpret_cast<const f32x4*>(u + (size_t)row * u_pitch + lane * 8 + 4);
+// one wave per row of 512, 8 floats per lane: v = u / d with d = max(|u|, 1e-12), which is returned
+__device__ __forceinline__ float row512_normalize(const float* __restrict__ u, float* __restrict__ v, int lane) {
+    const f32x4 a = *reinterpret_cast<const f32x4*>(u + lane * 8);
+    const f32x4 b = *reinterpret_cast<const f32x4*>(u + lane * 8 + 4);
     float s = 0.f;
 #pragma unroll
     for (int e = 0; e < 4; ++e) s += a[e] * a[e] + b[e] * b[e];
     s = wave_sum(s);
     const float d = fmaxf(sqrtf(s), 1e-12f);
-    *reinterpret_cast<f32x4*>(v + (size_t)row * 512 + lane * 8) = a / d;
-    *reinterpret_cast<f32x4*>(v + (size_t)row * 512 + lane * 8 + 4) = b / d;
+    *reinterpret_cast<f32x4*>(v + lane * 8) = a / d;
+    *reinterpret_cast<f32x4*>(v + lane * 8 + 4) = b / d;
+    return d;
+}
+
+__global__ __launch_bounds__(256) void k_row_normalize(const float* __restrict__ u, int u_pitch, float* __restrict__ v,
+                                                      float* __restrict__ norm, int rows) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= rows) return;
+    const float d = row512_normalize(u + (size_t)row * u_pitch, v + (size_t)row * 512, lane);
     if (lane == 0) norm[row] = d;
 }
 
@@ -1011,16 +1012,7 @@ __global__ __launch_bounds__(256) void k_loss_ch_prep(const float* __restrict__ 
     __shared__ float inv[32];
     const int n = blockIdx.y, c0 = blockIdx.x * 32;
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    for (int p = ty; p < 49; p += 8) t[p][tx] = feat[((size_t)n * 49 + p) * pitch + coff + c0 + tx];
-    __syncthreads();
-    if (threadIdx.x < 32) {
-        float s = 0.f;
-        for (int p = 0; p < 49; ++p) s += t[p][threadIdx.x] * t[p][threadIdx.x];
-        const float d = fmaxf(sqrtf(s), 1e-12f);
-        inv[threadIdx.x] = 1.0f / d;
-        ynorm[(size_t)n * 512 + c0 + threadIdx.x] = d;
-    }
-    __syncthreads();
+    ch_tile_norms(feat + (size_t)n * 49 * pitch + coff + c0, pitch, t, inv, ynorm + (size_t)n * 512 + c0);
     for (int i = threadIdx.x; i < 32 * 64; i += 256) {
         const int c = i >> 6, p = i & 63;
         Yht[((size_t)n * 512 + c0 + c) * 64 + p] = p < 49 ? t[p][c] * inv[c] : 0.f;
@@ -1123,16 +1115,7 @@ __global__ __launch_bounds__(256) void k_ss_space_loss(const float* __restrict__
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     // rows -> LDS, one wave per row in turn
     for (int i = wv; i < 49; i += 4) {
-        const float* z = feat + ((size_t)n * 49 + i) * pitch + coff;
-        const f32x4 a = *reinterpret_cast<const f32x4*>(z + lane * 8);
-        const f32x4 b = *reinterpret_cast<const f32x4*>(z + lane * 8 + 4);
-        float s = 0.f;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) s += a[e] * a[e] + b[e] * b[e];
-        s = wave_sum(s);
-        const float d = fmaxf(sqrtf(s), 1e-12f);
-        *reinterpret_cast<f32x4*>(Zh + i * 516 + lane * 8) = a / d;
-        *reinterpret_cast<f32x4*>(Zh + i * 516 + lane * 8 + 4) = b / d;
+        const float d = row512_normalize(feat + ((size_t)n * 49 + i) * pitch + coff, Zh + i * 516, lane);
         if (lane == 0) nrm[i] = d;
     }
     __syncthreads();

@@ -33,6 +33,8 @@ def engine():
 
 CONVLAYER_CASES = [   # (G, N, cin, cout)
     (1, 4, 64, 64), (2, 3, 128, 128), (1, 5, 49, 49), (2, 2, 561, 256), (1, 3, 128, 49), (1, 2, 1024, 512),
+    (2, 9, 64, 64),      # 441 rows per group: 5 slices of 89 rows, the last 85 -- a slice lane of the *_final kernels takes a second step, twice
+    (1, 66, 64, 64),     # 3234 rows: the first image count at which the cap of 32 slices binds (102 rows, the last 72)
 ]
 
 
