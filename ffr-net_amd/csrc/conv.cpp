@@ -258,24 +258,9 @@ static int conv_unfused(ffr_handle* h, const ConvW& L, const ConvCall& c, long l
     }
     // the roofline numerator of the GEMM stays the DIRECT convolution's algorithmic FLOPs
     if (h->opt.gemm_stream) {
-        // 36 GEMMs in one persistent launch with a continuous K-tile stream; tile shape: fewest rounds of whole tiles over
-        // the resident blocks, weighted by loop efficiency
-        int gtile = IGEMM_TILE_128x64, gblocks = 768;
-        double best = 1e300;
-        for (int tt = IGEMM_TILE_128x128; tt <= IGEMM_TILE_128x64; ++tt) {
-            int bm, bn;
-            igemm_tile_shape(tt, &bm, &bn);
-            if (L.cout_pad % bn) continue;
-            const long long tiles = 36LL * ((T + bm - 1) / bm) * (L.cout_pad / bn);
-            const long long pmax = 256LL * igemm_resident_blocks(tt);
-            const long long p = pmax > tiles ? tiles : pmax;
-            const double rounds = (double)((tiles + p - 1) / p);
-            // a block gets 1/R of its CU (R co-resident blocks), so a round of tiles costs bm*bn*R;
-            // the 128x64 loop runs at ~92% of the 128x128 loop's rate (measured per layer, r01 traces)
-            const double share = (double)((p + 255) / 256);
-            const double cost = rounds * bm * bn * share / (tt == IGEMM_TILE_128x128 ? 1.0 : 0.92);
-            if (cost < best) { best = cost; gtile = tt; gblocks = (int)p; }
-        }
+        // 36 GEMMs in one persistent launch with a continuous K-tile stream
+        int gtile, gblocks;
+        plan_gemm_stream(T, L.cout_pad, &gtile, &gblocks);
         GemmStreamArgs g{};
         g.A = c.winoV; g.W = L.wu; g.C = c.winoM; g.M = (int)T; g.K = L.cin_pad; g.Npad = L.cout_pad; g.nbatch = 36;
         int bm, bn;

@@ -273,6 +273,7 @@ bool wino_mixed_eligible(const ffr_handle* h, const ConvW& L, int N, int H, int 
 ConvPlan plan_conv(const ffr_handle* h, const ConvW& L, const ConvCall& c);
 void plan_igemm(long long M, int cout_pad, int nkt, int nbatch, int force_tile, int min_units, int* tile, int* nblocks, int* granule,
                 bool split = false);
+void plan_gemm_stream(long long T, int cout_pad, int* tile, int* nblocks);
 // conv.cpp
 int run_gemm(ffr_handle* h, IgemmArgs& a, const ConvCall& c, double flops, double bytes, hipStream_t st, double fuse = -1.0);
 int run_conv(ffr_handle* h, const ConvW& L, const ConvCall& c, hipStream_t st);

@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 // Diagnostics (per-block clock stamps) exist only in a -DFFR_TRACE build (tools/trace_build.py); the shipped library
 // compiles them out.
@@ -42,9 +43,46 @@ struct IgemmArgs {
 };
 enum { IGEMM_TILE_128x128 = 1, IGEMM_TILE_128x64 = 2, IGEMM_TILE_64x64 = 3, IGEMM_TILE_256x64 = 4,
        IGEMM_NTILES = 4 };
-void igemm_tile_shape(int tile, int* bm, int* bn);
+// The one table of tile facts: shape and the grid of the block's 4 waves (rows x columns) in the fp32 form and in the split
+// form, where a wave owns all columns of its rows when the tile allows it (no A value is split twice).  Entry 0: no tile.
+struct IgemmTile { int bm, bn, wm, wn, wm_split, wn_split; };
+constexpr IgemmTile IGEMM_TILES[IGEMM_NTILES + 1] = {
+    {0, 0, 0, 0, 0, 0}, {128, 128, 2, 2, 4, 1}, {128, 64, 2, 2, 4, 1}, {64, 64, 2, 2, 2, 2}, {256, 64, 4, 1, 4, 1}};
+// calls f with the tile index as a compile-time constant (IGEMM_TILES[t] picks the template arguments); no tile: a null result
+template <typename F>
+inline auto igemm_tile_dispatch(int tile, F&& f) -> decltype(f(std::integral_constant<int, IGEMM_TILE_128x128>{})) {
+    switch (tile) {
+        case IGEMM_TILE_128x128: return f(std::integral_constant<int, IGEMM_TILE_128x128>{});
+        case IGEMM_TILE_128x64: return f(std::integral_constant<int, IGEMM_TILE_128x64>{});
+        case IGEMM_TILE_64x64: return f(std::integral_constant<int, IGEMM_TILE_64x64>{});
+        case IGEMM_TILE_256x64: return f(std::integral_constant<int, IGEMM_TILE_256x64>{});
+        default: return {};
+    }
+}
+inline void igemm_tile_shape(int tile, int* bm, int* bn) {
+    const IgemmTile& t = IGEMM_TILES[tile >= 1 && tile <= IGEMM_NTILES ? tile : 0];
+    *bm = t.bm; *bn = t.bn;
+}
+// Dynamic LDS of a k_igemm block, in floats from its start.  One stage of the 2-stage ring: a K-tile of BM rows of A and BN of B,
+// 32 fp32 each; split form: B as three bf16 planes, 3 x 16 floats per row (k_gemm_stream's stage is the fp32 one).  The
+// epilogue's C tile [BM][BN + 4] lies over the ring; behind both s_cls, [BM] border class per row and [BM] = ticket (4 ints
+// keep the alignment), then s_bias [9][BN], the border-class biases of the tile.
+constexpr int igemm_stage_floats(int bm, int bn, bool split) { return split ? bm * 32 + bn * 48 : (bm + bn) * 32; }
+constexpr int igemm_cls_offset(int bm, int bn, bool split) {
+    return 2 * igemm_stage_floats(bm, bn, split) > bm * (bn + 4) ? 2 * igemm_stage_floats(bm, bn, split) : bm * (bn + 4);
+}
+constexpr int igemm_bias_offset(int bm, int bn, bool split) { return igemm_cls_offset(bm, bn, split) + bm + 4; }
+constexpr int igemm_lds_bytes(int bm, int bn, bool split) { return (igemm_bias_offset(bm, bn, split) + 9 * bn) * 4; }
+// blocks of 256 threads one CU holds: k_igemm is LDS-limited, 160 KiB per CU
+constexpr int igemm_resident_blocks(int tile, bool split = false) {
+    return tile >= 1 && tile <= IGEMM_NTILES ? 163840 / igemm_lds_bytes(IGEMM_TILES[tile].bm, IGEMM_TILES[tile].bn, split) : 0;
+}
+// the planners (plan.cpp) are tuned to these: a stage change that alters a residency has to be a decision, not a side effect
+static_assert(igemm_resident_blocks(IGEMM_TILE_128x128) == 2 && igemm_resident_blocks(IGEMM_TILE_128x128, true) == 1 &&
+              igemm_resident_blocks(IGEMM_TILE_128x64) == 3 && igemm_resident_blocks(IGEMM_TILE_128x64, true) == 2 &&
+              igemm_resident_blocks(IGEMM_TILE_64x64) == 4 && igemm_resident_blocks(IGEMM_TILE_64x64, true) == 3 &&
+              igemm_resident_blocks(IGEMM_TILE_256x64) == 1 && igemm_resident_blocks(IGEMM_TILE_256x64, true) == 1, "residency");
 hipError_t igemm_init();   // raises the dynamic-LDS limit of the instantiations
-int igemm_resident_blocks(int tile, bool split = false);
 // planes[p][i], p = 0..2: the bf16 pieces of w[i] (round to nearest even; w[i] = their sum up to 2^-26 |w[i]|)
 hipError_t launch_split_weights(const float* w, unsigned short* planes, size_t n, hipStream_t stream);
 // persistent stream-K launch over `nblocks` blocks; tiles that are cut are finished inside

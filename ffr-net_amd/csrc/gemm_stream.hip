@@ -1,49 +1,34 @@
 // Batched plain fp32-MFMA GEMM with a CONTINUOUS K-tile stream across output tiles:
 //     C[b][m][n] = sum_k A[b][m][k] * W[b][n][k]          (the 36 GEMMs of a Winograd F(4x4,3x3) conv)
 //
-// Same operand staging and MFMA schedule as k_igemm (igemm.hip): 16-byte LDS-DMA pieces into an
-// XOR-swizzled [row][32] LDS image, v_mfma_f32_32x32x2_f32, one filler per MFMA gap, pinned order,
-// 2-stage ring with the barrier in front of the last chunk of a K-tile.  What differs: these GEMMs have
-// short K (4..48 K-tiles), so a per-tile prologue (first DMA round trip) and an LDS-staged epilogue
-// cost as much as the multiply (measured: 2x the loop time at K = 256).  Here a persistent block owns
-// a contiguous range of whole tiles and never stops the stream: the first K-tile of the next tile is
-// fetched and its fragments are read under the last K-tile of the current one, and a finished
-// accumulator tile is copied out of the accumulation registers and stored straight from registers
-// (128-byte pieces) while the next tile multiplies.  No bias / activation: plain store.
-#include "device_util.h"
+// Same operand staging and MFMA schedule as the fp32 form of k_igemm, from the same definitions (igemm_core.h describes
+// them).  What differs: these GEMMs have short K (4..48 K-tiles), so a per-tile prologue (first DMA round trip) and an
+// LDS-staged epilogue cost as much as the multiply (measured: 2x the loop time at K = 256).  Here a persistent block owns
+// a contiguous range of whole tiles and never stops the stream: the first K-tile of the next tile is fetched and its
+// fragments are read under the last K-tile of the current one, and a finished accumulator tile is copied out of the
+// accumulation registers and stored straight from registers (128-byte pieces) while the next tile multiplies.  No bias /
+// activation: plain store.
 #include "ffr_kernels.h"
+#include "igemm_core.h"
 
 namespace ffr {
 
 template <int BM, int BN, int WARPS_M, int WARPS_N>
-__global__ __launch_bounds__(256, (BM * BN >= 128 * 128 ? 2 : 3)) void k_gemm_stream(const GemmStreamArgs a) {
+__global__ __launch_bounds__(256, 163840 / igemm_lds_bytes(BM, BN, false))      // the fp32 k_igemm's residency: what plan_gemm_stream counts on
+void k_gemm_stream(const GemmStreamArgs a) {
     constexpr int WM = BM / WARPS_M, WN = BN / WARPS_N;
     constexpr int TM = WM / 32, TN = WN / 32;
     constexpr int A_PT = BM / 32, B_PT = BN / 32;
-    constexpr int STAGE_FLOATS = (BM + BN) * 32;
-    constexpr int NQ = TM * TN * 4, NR = TM + TN, ND = A_PT + B_PT, NDH = (ND + 1) / 2;
-    static_assert(WARPS_M * WARPS_N == 4 && NR + NDH <= NQ, "layout");
+    constexpr int STAGE_FLOATS = igemm_stage_floats(BM, BN, false);
+    constexpr int NR = TM + TN, ND = A_PT + B_PT;
+    static_assert(WARPS_M * WARPS_N == 4, "layout");
     extern __shared__ __attribute__((aligned(16))) float smem[];
 
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int wm = wave / WARPS_N, wn = wave % WARPS_N;
-    // lane-derived values are re-derived per tile from an opaque copy of the thread id (see igemm.hip:
-    // otherwise hipcc hoists every per-lane address out of the tile loop and runs out of registers)
+    // lane-derived values are re-derived per tile from an opaque copy of the thread id
     int srow, lch, frow, fh, fragA, fragB, pc[4];
-    auto lane_values = [&]() {
-        int tid = threadIdx.x;
-        asm volatile("" : "+v"(tid));
-        const int lane = tid & 63;
-        srow = tid >> 3;
-        lch = (tid & 7) ^ ((srow >> 1) & 7);
-        frow = lane & 31;
-        fh = lane >> 5;
-        const int fswz = (lane >> 1) & 7;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) pc[q] = ((2 * q + fh) ^ fswz) * 4;
-        fragA = (wm * WM + frow) * 32;
-        fragB = (BM + wn * WN + frow) * 32;
-    };
+    auto lane_values = [&]() { igemm_lane_map<BM, WM, WN>(opaque_tid(), wm, wn, srow, lch, frow, fh, pc, fragA, fragB); };
     lane_values();
 
     const long long T = (long long)a.nbatch * a.mtiles * a.ntiles;
@@ -76,47 +61,15 @@ __global__ __launch_bounds__(256, (BM * BN >= 128 * 128 ? 2 : 3)) void k_gemm_st
         orow = a.C + (long long)batch * a.M * a.Npad + (size_t)mrow0 * a.Npad + n0 + wn * WN + frow;
     };
     auto dma_piece = [&](int buf, int d) {
-        float* sA = smem + buf * STAGE_FLOATS;
-        if (d < A_PT) {
-            __builtin_amdgcn_global_load_lds(GLB_PTR(a_ptr[d]), LDS_PTR(sA + (32 * d + 8 * wave) * 32), 16, 0, 0);
-            a_ptr[d] += 32;
-        } else {
-            const int i = d - A_PT;
-            __builtin_amdgcn_global_load_lds(GLB_PTR(b_ptr[i]), LDS_PTR(sA + (BM + 32 * i + 8 * wave) * 32), 16, 0, 0);
-            b_ptr[i] += 32;
-        }
+        igemm_dma_piece(smem + buf * STAGE_FLOATS, wave, d, d < A_PT ? a_ptr[d] : b_ptr[d - A_PT]);
     };
 
     f32x16 acc[TM][TN];
     f32x4 af[2][TM], bf[2][TN];
-    auto read_piece = [&](int slot, const float* stage, int pcv, int r) {
-        if (r < TM) af[slot][r] = *reinterpret_cast<const f32x4*>(stage + fragA + r * 32 * 32 + pcv);
-        else bf[slot][r - TM] = *reinterpret_cast<const f32x4*>(stage + fragB + (r - TM) * 32 * 32 + pcv);
-    };
-    // one K-tile (see igemm.hip tile_body); LAST = nothing follows in this block's stream
+    // one K-tile; LAST = nothing follows in this block's stream
     auto ktile = [&]<bool LAST>(int cur) {
-        const float* stage = smem + cur * STAGE_FLOATS;
-        const float* stage_n = smem + (cur ^ 1) * STAGE_FLOATS;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            if (q == 3 && !LAST) {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __syncthreads();
-                FFR_PIN;
-            }
-#pragma unroll
-            for (int g = 0; g < NQ; ++g) {
-                const int e = g / (TM * TN), i = (g / TN) % TM, j = g % TN;
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[q & 1][i][e], bf[q & 1][j][e], acc[i][j], 0, 0, 0);
-                if (g < NR) {
-                    if (q < 3) read_piece((q + 1) & 1, stage, pc[q + 1], g);
-                    else if (!LAST) read_piece(0, stage_n, pc[0], g);
-                } else if (!LAST && q < 2 && (g - NR) < NDH && q * NDH + (g - NR) < ND) {
-                    dma_piece(cur ^ 1, q * NDH + (g - NR));
-                }
-                FFR_PIN;
-            }
-        }
+        igemm_ktile<TM, TN, ND, LAST>(acc, af, bf, smem + cur * STAGE_FLOATS, smem + (cur ^ 1) * STAGE_FLOATS, fragA, fragB, pc,
+                                      [&](int d) { dma_piece(cur ^ 1, d); }, [] {});
     };
 
     // ---- start of the stream -----------------------------------------------------------
@@ -126,7 +79,7 @@ __global__ __launch_bounds__(256, (BM * BN >= 128 * 128 ? 2 : 3)) void k_gemm_st
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 #pragma unroll
-    for (int r = 0; r < NR; ++r) read_piece(0, smem, pc[0], r);
+    for (int r = 0; r < NR; ++r) igemm_read_piece(af[0], bf[0], smem, fragA, fragB, pc[0], r);
     FFR_PIN;
     int s = 0;                                    // K-tiles streamed so far (stage parity)
 #pragma unroll 1
@@ -167,30 +120,36 @@ __global__ __launch_bounds__(256, (BM * BN >= 128 * 128 ? 2 : 3)) void k_gemm_st
     }
 }
 
-static size_t gs_lds_bytes(int bm, int bn) { return (size_t)2 * (bm + bn) * 32 * 4; }
+static size_t gs_lds_bytes(int bm, int bn) { return (size_t)2 * igemm_stage_floats(bm, bn, false) * 4; }
+
+// tile index -> instantiation (the fp32 wave grid of the tile table); null: not a tile of this kernel
+static const void* gemm_stream_kernel(int tile) {
+    return igemm_tile_dispatch(tile, [](auto t) -> const void* {
+        constexpr IgemmTile T = IGEMM_TILES[t];
+        if constexpr (t == IGEMM_TILE_128x128 || t == IGEMM_TILE_128x64) return (const void*)k_gemm_stream<T.bm, T.bn, T.wm, T.wn>;
+        else return nullptr;
+    });
+}
 
 hipError_t gemm_stream_init() {
-    hipError_t e = hipFuncSetAttribute((const void*)k_gemm_stream<128, 128, 2, 2>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)gs_lds_bytes(128, 128));
-    if (e != hipSuccess) return e;
-    return hipFuncSetAttribute((const void*)k_gemm_stream<128, 64, 2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)gs_lds_bytes(128, 64));
+    for (int tile = IGEMM_TILE_128x128; tile <= IGEMM_TILE_128x64; ++tile) {
+        const hipError_t e = hipFuncSetAttribute(gemm_stream_kernel(tile), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 (int)gs_lds_bytes(IGEMM_TILES[tile].bm, IGEMM_TILES[tile].bn));
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 // tile: IGEMM_TILE_128x128 or IGEMM_TILE_128x64
 hipError_t launch_gemm_stream(GemmStreamArgs a, int tile, int nblocks, hipStream_t stream) {
     int bm, bn;
     igemm_tile_shape(tile, &bm, &bn);
-    if ((tile != IGEMM_TILE_128x128 && tile != IGEMM_TILE_128x64) || a.Npad % bn || a.K % 32 || nblocks <= 0)
-        return hipErrorInvalidValue;
+    const void* kernel = gemm_stream_kernel(tile);
+    if (!kernel || a.Npad % bn || a.K % 32 || nblocks <= 0) return hipErrorInvalidValue;
     a.mtiles = (a.M + bm - 1) / bm;
     a.ntiles = a.Npad / bn;
-    const size_t lds = gs_lds_bytes(bm, bn);
-    if (tile == IGEMM_TILE_128x128)
-        hipLaunchKernelGGL((k_gemm_stream<128, 128, 2, 2>), dim3(nblocks), dim3(256), lds, stream, a);
-    else
-        hipLaunchKernelGGL((k_gemm_stream<128, 64, 2, 2>), dim3(nblocks), dim3(256), lds, stream, a);
-    return hipGetLastError();
+    void* args[] = {&a};
+    return hipLaunchKernel(kernel, dim3(nblocks), dim3(256), args, gs_lds_bytes(bm, bn), stream);
 }
 
 }  // namespace ffr

@@ -10,11 +10,8 @@
 //   per-lane SOURCE address does the im2col gather; zero padding reads a zero page,
 //   reflect padding mirrors the index.  Weights are pre-packed [cout][r][s][ci], so
 //   A- and B-tile rows are both 128-byte runs of k and share one staging path.
-// * K-tile = 32 floats (one tap, 32 channels).  LDS image [row][32] is lane-linear for
-//   the DMA; the 16-B chunk index is XOR-swizzled with (row>>1)&7 on the SOURCE side
-//   and on the ds_read_b128 side, which makes the fragment reads bank-conflict free.
-// * v_mfma_f32_32x32x2_f32 (exact fp32, 256 FLOP/clk/CU).  One ds_read_b128 per
-//   operand row feeds 4 MFMAs (lanes 0-31 hold k..k+3, lanes 32-63 hold k+4..k+7).
+// * K-tile = 32 floats (one tap, 32 channels) on v_mfma_f32_32x32x2_f32 (exact fp32, 256 FLOP/clk/CU).  The swizzled
+//   LDS image, the fragment reads and the K-tile schedule are igemm_core.h's, shared with k_gemm_stream.
 // * 2-stage LDS ring, one barrier per K-tile: the DMA of tile t+1 is in flight while
 //   tile t is multiplied.
 // * Split-operand form (template parameter SPLIT, launches with IgemmArgs::w3): the same fp32 product
@@ -22,8 +19,8 @@
 // * Epilogue in registers: bias (optionally one of 9 border classes, for the BN that
 //   precedes a zero-padded conv), PReLU, residual add, sigmoid; NHWC store with pitch /
 //   channel offset so concatenations are just addressing.
-#include "device_util.h"
 #include "ffr_kernels.h"
+#include "igemm_core.h"
 
 #include <utility>
 
@@ -42,12 +39,11 @@ __global__ __launch_bounds__(256) void k_igemm(const IgemmArgs a) {
     constexpr int TM = WM / 32, TN = WN / 32;
     constexpr int A_PT = BM / 32;                      // A staging rows per thread = A pieces per K-tile
     constexpr int B_PT = SPLIT ? 3 * (BN / 64) : BN / 32;      // B pieces per K-tile (split: 64 rows of one plane per piece)
-    constexpr int STAGE_FLOATS = SPLIT ? BM * 32 + BN * 48 : (BM + BN) * 32;
+    constexpr int STAGE_FLOATS = igemm_stage_floats(BM, BN, SPLIT);
     static_assert(WARPS_M * WARPS_N == 4, "4 waves");
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    constexpr int MAIN_FLOATS = (2 * STAGE_FLOATS > BM * (BN + 4)) ? 2 * STAGE_FLOATS : BM * (BN + 4);
-    int* s_cls = reinterpret_cast<int*>(smem + MAIN_FLOATS);     // [BM] border class per row, [BM] = ticket
-    float* s_bias = smem + MAIN_FLOATS + BM + 4;                // [9][BN] border-class biases of this tile
+    int* s_cls = reinterpret_cast<int*>(smem + igemm_cls_offset(BM, BN, SPLIT));     // [BM] border class per row, [BM] = ticket
+    float* s_bias = smem + igemm_bias_offset(BM, BN, SPLIT);                        // [9][BN] border-class biases of this tile
 
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int wm = wave / WARPS_N, wn = wave % WARPS_N;
@@ -81,17 +77,14 @@ __global__ __launch_bounds__(256) void k_igemm(const IgemmArgs a) {
     // which is streaming MFMAs and wins the age-based arbitration: the setup / epilogue VALU and
     // memory instructions went out at ~1 per MFMA (64 cycles).  Priority 2 for these phases.
     __builtin_amdgcn_s_setprio(2);
-    // the thread id is re-read through an opaque asm every segment: otherwise hipcc hoists every
-    // lane-dependent address of the epilogue out of the segment loop and keeps ~100 extra
-    // VGPRs alive across the MFMA loop (128x64: 196 instead of ~100 registers -> 2 blocks/CU)
-    int tid = threadIdx.x;
-    asm volatile("" : "+v"(tid));
+    // every lane value of the segment, the epilogue's addresses included, derives from this opaque copy (igemm_core.h)
+    const int tid = opaque_tid();
     if (FFR_TRACE_ON(a.trace)) { tr_t = __builtin_amdgcn_s_memtime(); ++tr_seg; }
     const int lane = tid & 63;
+    int srow, lch, frow, fh, fragA, fragB, pc[4];
+    igemm_lane_map<BM, WM, WN>(tid, wm, wn, srow, lch, frow, fh, pc, fragA, fragB);
 
     // ---- per-thread staging rows -------------------------------------------------
-    const int srow = tid >> 3;                              // 0..31
-    const int lch = (tid & 7) ^ ((srow >> 1) & 7);          // logical 16-B chunk this lane fetches
     int a_pix[A_PT], a_h0[A_PT], a_w0[A_PT];                // pixel base of the image, top-left tap coordinates
 #pragma unroll
     for (int i = 0; i < A_PT; ++i) {
@@ -168,18 +161,12 @@ __global__ __launch_bounds__(256) void k_igemm(const IgemmArgs a) {
     // one 16-B-per-lane LDS-DMA piece (8 rows x 128 B per wave) of the next K-tile
     auto dma_piece = [&](int buf, int d) {
         float* sA = smem + buf * STAGE_FLOATS;
-        if (d < A_PT) {
-            __builtin_amdgcn_global_load_lds(GLB_PTR(a_ptr[d]), LDS_PTR(sA + (32 * d + 8 * wave) * 32), 16, 0, 0);
-            a_ptr[d] += 32;
-        } else {
+        if (d < A_PT) igemm_dma_piece(sA, wave, d, a_ptr[d]);
+        else if constexpr (!SPLIT) igemm_dma_piece(sA, wave, d, b_ptr[d - A_PT]);
+        else {                          // 16 rows x 64 B per wave; 32 bf16 = 16 floats per K-tile
             const int i = d - A_PT;
-            if constexpr (SPLIT) {      // 16 rows x 64 B per wave; 32 bf16 = 16 floats per K-tile
-                __builtin_amdgcn_global_load_lds(GLB_PTR(b_ptr[i]), LDS_PTR(sA + BM * 32 + (i / (BN / 64)) * BN * 16 + (64 * (i % (BN / 64)) + 16 * wave) * 16), 16, 0, 0);
-                b_ptr[i] += 16;
-            } else {
-                __builtin_amdgcn_global_load_lds(GLB_PTR(b_ptr[i]), LDS_PTR(sA + (BM + 32 * i + 8 * wave) * 32), 16, 0, 0);
-                b_ptr[i] += 32;
-            }
+            __builtin_amdgcn_global_load_lds(GLB_PTR(b_ptr[i]), LDS_PTR(sA + BM * 32 + (i / (BN / 64)) * BN * 16 + (64 * (i % (BN / 64)) + 16 * wave) * 16), 16, 0, 0);
+            b_ptr[i] += 16;
         }
     };
     // after all pieces of a K-tile are issued: move to the next tap when the channel run ends
@@ -199,14 +186,6 @@ __global__ __launch_bounds__(256) void k_igemm(const IgemmArgs a) {
         for (int j = 0; j < TN; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    const int frow = lane & 31;
-    const int fh = lane >> 5;
-    const int fswz = (lane >> 1) & 7;
-    int pc[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) pc[q] = ((2 * q + fh) ^ fswz) * 4;
-    const int fragA = (wm * WM + frow) * 32, fragB = (BM + wn * WN + frow) * 32;
 
     constexpr int ND = A_PT + B_PT;          // DMA pieces per K-tile
     if constexpr (SPLIT) {
@@ -229,7 +208,7 @@ __global__ __launch_bounds__(256) void k_igemm(const IgemmArgs a) {
         f32x4 araw[TM][2];
         u32x4 pa[2][TM][3];
         f32x4 pb[2][TN][3];
-        const int bswz = (lane >> 2) & 3;
+        const int fswz = (lane >> 1) & 7, bswz = (lane >> 2) & 3;     // chunk swizzle of the fp32 A rows, of the bf16 B rows
         int pcA[2][2], pcB[2];
 #pragma unroll
         for (int st = 0; st < 2; ++st) {
@@ -316,48 +295,12 @@ __global__ __launch_bounds__(256) void k_igemm(const IgemmArgs a) {
         __builtin_amdgcn_s_setprio(2);
         if (FFR_TRACE_ON(a.trace)) { const unsigned long long t = __builtin_amdgcn_s_memtime(); tr_acc[2] += t - tr_t; tr_t = t; }
     } else {
-        constexpr int NQ = TM * TN * 4;          // MFMAs per 8-k chunk
         constexpr int NR = TM + TN;              // fragment reads per chunk
-        constexpr int NDH = (ND + 1) / 2;        // ... issued in the gaps of chunks 0 and 1
-        static_assert(NR + NDH <= NQ, "fillers must fit the MFMA gaps of a chunk");
         f32x4 af[2][TM], bf[2][TN];
-
-        // fragment read r of a chunk: rows of A then rows of B, 16 B per lane (4 k values)
-        auto read_piece = [&](int slot, const float* stage, int pcv, int r) {
-            if (r < TM) af[slot][r] = *reinterpret_cast<const f32x4*>(stage + fragA + r * 32 * 32 + pcv);
-            else bf[slot][r - TM] = *reinterpret_cast<const f32x4*>(stage + fragB + (r - TM) * 32 * 32 + pcv);
-        };
-
-        // One K-tile.  Every MFMA gap (64 cycles on the SIMD's matrix pipe) carries at most ONE
-        // filler -- a fragment ds_read_b128 for the next chunk or one LDS-DMA piece of the next
-        // K-tile -- and the order is pinned (sched_barrier): an LDS-DMA costs its wave ~60 issue
-        // cycles, so 4-8 of them back to back starve the matrix pipe (measured: -10 % at 8 blocks/CU,
-        // more in the 1-block/CU tail).  The barrier that publishes tile t+1 sits in front of the
-        // LAST chunk of tile t, so the first fragments of t+1 are read under that chunk's MFMAs.
+        // one K-tile from stage cur (igemm_core.h); once the pieces of the next one are out, the sources move on
         auto tile_body = [&]<bool LAST>(int cur) {
-            const float* stage = smem + cur * STAGE_FLOATS;
-            const float* stage_n = smem + (cur ^ 1) * STAGE_FLOATS;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                if (q == 3 && !LAST) {
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    __syncthreads();
-                    FFR_PIN;
-                }
-#pragma unroll
-                for (int g = 0; g < NQ; ++g) {
-                    const int e = g / (TM * TN), i = (g / TN) % TM, j = g % TN;
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[q & 1][i][e], bf[q & 1][j][e], acc[i][j], 0, 0, 0);
-                    if (g < NR) {
-                        if (q < 3) read_piece((q + 1) & 1, stage, pc[q + 1], g);
-                        else if (!LAST) read_piece(0, stage_n, pc[0], g);
-                    } else if (!LAST && q < 2 && (g - NR) < NDH && q * NDH + (g - NR) < ND) {
-                        dma_piece(cur ^ 1, q * NDH + (g - NR));
-                    }
-                    FFR_PIN;
-                }
-                if (q == 1 && !LAST) { advance_tile(); FFR_PIN; }
-            }
+            igemm_ktile<TM, TN, ND, LAST>(acc, af, bf, smem + cur * STAGE_FLOATS, smem + (cur ^ 1) * STAGE_FLOATS, fragA, fragB, pc,
+                                          [&](int d) { dma_piece(cur ^ 1, d); }, [&] { advance_tile(); FFR_PIN; });
         };
 
         if (FFR_TRACE_ON(a.trace)) { const unsigned long long t = __builtin_amdgcn_s_memtime(); tr_acc[0] += t - tr_t; tr_t = t; }
@@ -368,7 +311,7 @@ __global__ __launch_bounds__(256) void k_igemm(const IgemmArgs a) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
 #pragma unroll
-        for (int r = 0; r < NR; ++r) read_piece(0, smem, pc[0], r);
+        for (int r = 0; r < NR; ++r) igemm_read_piece(af[0], bf[0], smem, fragA, fragB, pc[0], r);
         FFR_PIN;
         if (FFR_TRACE_ON(a.trace)) { const unsigned long long t = __builtin_amdgcn_s_memtime(); tr_acc[1] += t - tr_t; tr_t = t; }
         __builtin_amdgcn_s_setprio(0);
@@ -548,90 +491,33 @@ __global__ __launch_bounds__(256) void k_igemm(const IgemmArgs a) {
     }
 }
 
-void igemm_tile_shape(int tile, int* bm, int* bn) {
-    switch (tile) {
-        case IGEMM_TILE_128x128: *bm = 128; *bn = 128; break;
-        case IGEMM_TILE_128x64: *bm = 128; *bn = 64; break;
-        case IGEMM_TILE_64x64: *bm = 64; *bn = 64; break;
-        case IGEMM_TILE_256x64: *bm = 256; *bn = 64; break;
-        default: *bm = 0; *bn = 0;
-    }
-}
-
-static size_t igemm_lds_bytes(int bm, int bn, bool split) {
-    size_t stages = split ? (size_t)2 * (bm * 32 + bn * 48) : (size_t)2 * (bm + bn) * 32, ctile = (size_t)bm * (bn + 4);
-    return (stages > ctile ? stages : ctile) * 4 + (size_t)(bm + 4) * 4 + (size_t)9 * bn * 4;
+// tile index -> instantiation of (pad mode, form), with the form's wave grid of the tile table; null: no such tile
+static const void* igemm_kernel(int tile, int pad_mode, bool split) {
+    return igemm_tile_dispatch(tile, [&](auto t) -> const void* {
+        constexpr IgemmTile T = IGEMM_TILES[t];
+        if (split) return pad_mode == 1 ? (const void*)k_igemm<T.bm, T.bn, T.wm_split, T.wn_split, 1, true> : (const void*)k_igemm<T.bm, T.bn, T.wm_split, T.wn_split, 0, true>;
+        return pad_mode == 1 ? (const void*)k_igemm<T.bm, T.bn, T.wm, T.wn, 1, false> : (const void*)k_igemm<T.bm, T.bn, T.wm, T.wn, 0, false>;
+    });
 }
 
 hipError_t igemm_init() {
-    hipError_t e;
-#define FFR_SET_LDS(BM, BN, WMM, WNN, SPLIT)                                                                   \
-    e = hipFuncSetAttribute((const void*)k_igemm<BM, BN, WMM, WNN, 0, SPLIT>,                                  \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)igemm_lds_bytes(BM, BN, SPLIT));  \
-    if (e != hipSuccess) return e;                                                                             \
-    e = hipFuncSetAttribute((const void*)k_igemm<BM, BN, WMM, WNN, 1, SPLIT>,                                  \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)igemm_lds_bytes(BM, BN, SPLIT));  \
-    if (e != hipSuccess) return e;
-    FFR_SET_LDS(128, 128, 2, 2, false)
-    FFR_SET_LDS(128, 64, 2, 2, false)
-    FFR_SET_LDS(64, 64, 2, 2, false)
-    FFR_SET_LDS(256, 64, 4, 1, false)
-    // split form: a wave owns all columns of its rows where the tile allows it (no A value is split twice)
-    FFR_SET_LDS(128, 128, 4, 1, true)
-    FFR_SET_LDS(128, 64, 4, 1, true)
-    FFR_SET_LDS(64, 64, 2, 2, true)
-    FFR_SET_LDS(256, 64, 4, 1, true)
-#undef FFR_SET_LDS
-    return e;
-}
-
-int igemm_resident_blocks(int tile, bool split) {   // blocks of 256 threads one CU holds (LDS-limited)
-    if (split) {     // a stage is (BM * 4 + BN * 6) * 32 B: 87 / 60 / 43 / 96 KB per block with the tables
-        switch (tile) {
-            case IGEMM_TILE_128x128: return 1;
-            case IGEMM_TILE_128x64: return 2;
-            case IGEMM_TILE_64x64: return 3;
-            case IGEMM_TILE_256x64: return 1;
-            default: return 0;
-        }
+    for (int i = 0; i < IGEMM_NTILES * 4; ++i) {       // every tile x pad mode x form
+        const int tile = 1 + i / 4, split = i & 1;
+        const hipError_t e = hipFuncSetAttribute(igemm_kernel(tile, (i >> 1) & 1, split), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 igemm_lds_bytes(IGEMM_TILES[tile].bm, IGEMM_TILES[tile].bn, split));
+        if (e != hipSuccess) return e;
     }
-    switch (tile) {
-        case IGEMM_TILE_128x128: return 2;
-        case IGEMM_TILE_128x64: return 3;
-        case IGEMM_TILE_64x64: return 4;
-        case IGEMM_TILE_256x64: return 1;
-        default: return 0;
-    }
+    return hipSuccess;
 }
 
 hipError_t launch_igemm(const IgemmArgs& a, int tile, int nblocks, hipStream_t stream) {
-    int bm, bn;
-    igemm_tile_shape(tile, &bm, &bn);
-    if (!bm || nblocks <= 0) return hipErrorInvalidValue;
     const bool split = a.w3 != nullptr;
+    const void* kernel = igemm_kernel(tile, a.pad_mode, split);
+    if (!kernel || nblocks <= 0) return hipErrorInvalidValue;
     if (split && a.nbatch != 1) return hipErrorInvalidValue;      // the planes have no batch stride
-    dim3 grid((unsigned)nblocks, 1, 1);
-    const size_t lds = igemm_lds_bytes(bm, bn, split);
-#define FFR_LAUNCH(BM, BN, WMM, WNN, SPLIT)                                                                          \
-    if (a.pad_mode == 1) hipLaunchKernelGGL((k_igemm<BM, BN, WMM, WNN, 1, SPLIT>), grid, dim3(256), lds, stream, a); \
-    else hipLaunchKernelGGL((k_igemm<BM, BN, WMM, WNN, 0, SPLIT>), grid, dim3(256), lds, stream, a);
-    if (split) {
-        switch (tile) {
-            case IGEMM_TILE_128x128: FFR_LAUNCH(128, 128, 4, 1, true) break;
-            case IGEMM_TILE_128x64: FFR_LAUNCH(128, 64, 4, 1, true) break;
-            case IGEMM_TILE_64x64: FFR_LAUNCH(64, 64, 2, 2, true) break;
-            case IGEMM_TILE_256x64: FFR_LAUNCH(256, 64, 4, 1, true) break;
-        }
-    } else {
-        switch (tile) {
-            case IGEMM_TILE_128x128: FFR_LAUNCH(128, 128, 2, 2, false) break;
-            case IGEMM_TILE_128x64: FFR_LAUNCH(128, 64, 2, 2, false) break;
-            case IGEMM_TILE_64x64: FFR_LAUNCH(64, 64, 2, 2, false) break;
-            case IGEMM_TILE_256x64: FFR_LAUNCH(256, 64, 4, 1, false) break;
-        }
-    }
-#undef FFR_LAUNCH
-    return hipGetLastError();
+    void* args[] = {const_cast<IgemmArgs*>(&a)};
+    return hipLaunchKernel(kernel, dim3((unsigned)nblocks, 1, 1), dim3(256), args,
+                           igemm_lds_bytes(IGEMM_TILES[tile].bm, IGEMM_TILES[tile].bn, split), stream);
 }
 
 // planes[p][i] = piece p of w[i] (bf16, round to nearest even), p = 0..2: the device-side split of raw fp32 weights

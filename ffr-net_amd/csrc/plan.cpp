@@ -179,4 +179,25 @@ void plan_igemm(long long M, int cout_pad, int nkt, int nbatch, int force_tile, 
     *nblocks = (int)p;
 }
 
+// Tile shape and block count of k_gemm_stream for the 36 GEMMs [T x K] * [K x cout_pad] of a Winograd convolution: fewest
+// rounds of whole tiles over the resident blocks, weighted by loop efficiency.
+void plan_gemm_stream(long long T, int cout_pad, int* tile, int* nblocks) {
+    *tile = IGEMM_TILE_128x64; *nblocks = 768;
+    double best = 1e300;
+    for (int tt = IGEMM_TILE_128x128; tt <= IGEMM_TILE_128x64; ++tt) {
+        int bm, bn;
+        igemm_tile_shape(tt, &bm, &bn);
+        if (cout_pad % bn) continue;
+        const long long tiles = 36LL * ((T + bm - 1) / bm) * (cout_pad / bn);
+        const long long pmax = 256LL * igemm_resident_blocks(tt);
+        const long long p = pmax > tiles ? tiles : pmax;
+        const double rounds = (double)((tiles + p - 1) / p);
+        // a block gets 1/R of its CU (R co-resident blocks), so a round of tiles costs bm*bn*R;
+        // the 128x64 loop runs at ~92% of the 128x128 loop's rate (measured per layer, r01 traces)
+        const double share = (double)((p + 255) / 256);
+        const double cost = rounds * bm * bn * share / (tt == IGEMM_TILE_128x128 ? 1.0 : 0.92);
+        if (cost < best) { best = cost; *tile = tt; *nblocks = (int)p; }
+    }
+}
+
 }  // namespace ffr_eng

@@ -122,6 +122,7 @@ WINO_CASES = [
     (40, 56, 56, 64, 128, 0, True, True),     # two channel groups, two phases, residual through the q-form epilogue
     (33, 30, 22, 96, 192, 1, True, False),    # reflect padding, ragged map, three phases, last tile group partly empty
     (3, 9, 9, 256, 68, 0, True, True),        # V-fed, ragged 9x9 tiles over both edges, 4 of the second channel group's 64 channels stored
+    (200, 7, 7, 64, 512, 1, True, False),     # batched GEMM: 1008 tiles of 128x128 (the 7th row tile ragged) on 512 blocks, tile to tile across batches
 ]
 
 
