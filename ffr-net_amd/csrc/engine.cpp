@@ -47,6 +47,44 @@ std::vector<PlanLayer> plan_layers(const ffr_handle* hc) {
 void plan_changed(ffr_handle* h) { ++h->generation; h->mixed_ready_n = 0; }
 }  // namespace ffr_eng
 
+// ---- pieces the entry points share --------------------------------------------------------------------------------------
+static int check_hw(ffr_handle* h, int H, int W) {
+    if (H < 32 || W < 32 || (H & 15) || (W & 15)) return fail(h, FFR_ERR_ARG, "H and W must be multiples of 16, >= 32");
+    return FFR_OK;
+}
+
+static int check_dim(ffr_handle* h, const char* who, int dim) {
+    if (dim != 512) return fail(h, FFR_ERR_UNSUPPORTED, "%s: dim must be 512, got %d", who, dim);
+    return FFR_OK;
+}
+
+static bool misaligned16(const void* p) { return ((uintptr_t)p & 15) != 0; }
+
+// A scratch laid out the way layout() lays out the workspace: `lay` takes its pieces from a measuring Arena, the buffer grows
+// to that size, and `lay` runs again on the buffer
+template <class F> static int carve(ffr_handle* h, DevBuf& b, const char* what, F lay) {
+    Arena measure(nullptr);
+    lay(measure);
+    RC(grow(h, b, measure.off, what));
+    Arena a(b.p);
+    lay(a);
+    return FFR_OK;
+}
+
+// featmap [N,512,7,7] -> w.X, where run_recnet reads it
+static int featmap_to_x(ffr_handle* h, const Work& w, const float* featmap_nchw, int N, hipStream_t st) {
+    HIPCK(h, launch_nchw_to_nhwc(featmap_nchw, w.X, 512, N, 49, 512, st));
+    return FFR_OK;
+}
+
+// The tail of ffr_embed, ffr_embed_u8 and ffr_embed_aligned: workspace, encoder into w.X, RecNet
+static int embed_tail(ffr_handle* h, const float* x, const U8In* u8, int N, float* f_new, float* f, hipStream_t st) {
+    Work w;
+    RC(ensure_arena_encoder(h, N, 112, 112, &w));
+    RC(run_encoder(h, w, x, N, 112, 112, w.X, f, st, u8));
+    return run_recnet(h, w, N, f_new, nullptr, st);
+}
+
 // =========================================================================================
 extern "C" {
 
@@ -103,11 +141,7 @@ void ffr_destroy(ffr_handle* h) {
     if (h->ev_fork) hipEventDestroy(h->ev_fork);
     if (h->ev_join) hipEventDestroy(h->ev_join);
     if (h->side) hipStreamDestroy(h->side);
-    if (h->arena) hipFree(h->arena);
-    if (h->tickets) hipFree(h->tickets);
-    if (h->search_buf) hipFree(h->search_buf);
-    if (h->cluster_buf) hipFree(h->cluster_buf);
-    if (h->align_buf) hipFree(h->align_buf);
+    for (DevBuf* b : {&h->arena, &h->tickets, &h->search, &h->cluster, &h->align}) if (b->p) hipFree(b->p);
     if (h->zero) hipFree(h->zero);
     for (auto& r : h->prof_log) { hipEventDestroy(r.e0); hipEventDestroy(r.e1); }
     for (auto e : h->ev_pool) hipEventDestroy(e);
@@ -119,7 +153,7 @@ int ffr_memory_stats(const ffr_handle* h, ffr_mem_stats* out) {
     out->encoder_weight_bytes = h->enc_weight_bytes;
     out->recnet_weight_bytes = h->rec_weight_bytes;
     out->mixed_tile_weight_bytes = h->mixed_weight_bytes;
-    out->workspace_bytes = h->arena_bytes;
+    out->workspace_bytes = h->arena.bytes;
     out->encoder_load_seconds = h->enc_load_s;
     out->recnet_load_seconds = h->rec_load_s;
     out->mixed_tile_pack_seconds = h->mixed_pack_s;
@@ -155,7 +189,7 @@ static int encoder_forward(ffr_handle* h, const float* x, const U8In* u8, int N,
                            void* stream) {
     FFR_DEVICE_SCOPE(h); RC(check_fwd(h, true, false, N));
     if (u8 ? !u8->img : !x) return fail(h, FFR_ERR_ARG, u8 ? "img is null" : "x is null");
-    if (H < 32 || W < 32 || (H & 15) || (W & 15)) return fail(h, FFR_ERR_ARG, "H and W must be multiples of 16, >= 32");
+    RC(check_hw(h, H, W));
     if (f && (H != 112 || W != 112)) return fail(h, FFR_ERR_UNSUPPORTED, "f needs a 112x112 input (Linear(512*7*7,512))");
     hipStream_t st = (hipStream_t)stream;
     Work w;
@@ -186,7 +220,7 @@ int ffr_recnet_forward(ffr_handle* h, const float* featmap_nchw, int N, float* f
     RC(ensure_arena(h, N, 112, 112, &w));
     {
         Scope s(h, st, FFR_KC_LAYOUT, 0, 8.0 * N * 49 * 512);
-        HIPCK(h, launch_nchw_to_nhwc(featmap_nchw, w.X, 512, N, 49, 512, st));
+        RC(featmap_to_x(h, w, featmap_nchw, N, st));
     }
     RC(run_recnet(h, w, N, f_new, nullptr, st));
     if (feat_new_nchw) {
@@ -199,23 +233,15 @@ int ffr_recnet_forward(ffr_handle* h, const float* featmap_nchw, int N, float* f
 int ffr_embed(ffr_handle* h, const float* x, int N, float* f_new, float* f, void* stream) {
     FFR_DEVICE_SCOPE(h); RC(check_fwd(h, true, true, N));
     if (!x || !f_new) return fail(h, FFR_ERR_ARG, "x / f_new is null");
-    hipStream_t st = (hipStream_t)stream;
-    Work w;
-    RC(ensure_arena_encoder(h, N, 112, 112, &w));
-    RC(run_encoder(h, w, x, N, 112, 112, w.X, f, st));
-    return run_recnet(h, w, N, f_new, nullptr, st);
+    return embed_tail(h, x, nullptr, N, f_new, f, (hipStream_t)stream);
 }
 
 int ffr_embed_u8(ffr_handle* h, const uint8_t* img_hwc_rgb, const uint8_t* flip, int N, float* f_new, float* f,
                  void* stream) {
     FFR_DEVICE_SCOPE(h); RC(check_fwd(h, true, true, N));
     if (!img_hwc_rgb || !f_new) return fail(h, FFR_ERR_ARG, "img / f_new is null");
-    hipStream_t st = (hipStream_t)stream;
-    Work w;
-    RC(ensure_arena_encoder(h, N, 112, 112, &w));
-    U8In u8{img_hwc_rgb, flip};
-    RC(run_encoder(h, w, nullptr, N, 112, 112, w.X, f, st, &u8));
-    return run_recnet(h, w, N, f_new, nullptr, st);
+    const U8In u8{img_hwc_rgb, flip};
+    return embed_tail(h, nullptr, &u8, N, f_new, f, (hipStream_t)stream);
 }
 
 int ffr_cosine_scores(ffr_handle* h, const float* a, const float* b, int n, int dim, float* score, void* stream) {
@@ -243,11 +269,9 @@ int ffr_lfw_fold_accuracy(ffr_handle* h, const float* score, const int32_t* labe
 unsigned long long ffr_generation(const ffr_handle* h) { return h ? h->generation : 0; }
 
 // ---- 1:N identification (search.hip) ---------------------------------------------------------------------------------
-static bool misaligned16(const void* p) { return ((uintptr_t)p & 15) != 0; }
-
 int ffr_row_norms(ffr_handle* h, const float* x, long long n, int dim, float* norms, void* stream) {
     FFR_DEVICE_SCOPE(h); RC(check_fwd(h, false, false, 1));
-    if (dim != 512) return fail(h, FFR_ERR_UNSUPPORTED, "ffr_row_norms: dim must be 512, got %d", dim);
+    RC(check_dim(h, "ffr_row_norms", dim));
     if (!x || !norms || n < 1) return fail(h, FFR_ERR_ARG, "ffr_row_norms: bad arguments");
     hipStream_t st = (hipStream_t)stream;
     Scope s(h, st, FFR_KC_SCORE, 2.0 * n * dim, 4.0 * n * (dim + 1));
@@ -258,7 +282,7 @@ int ffr_row_norms(ffr_handle* h, const float* x, long long n, int dim, float* no
 int ffr_search_topk(ffr_handle* h, const float* query, int Q, const float* gallery, const float* gallery_norms, long long G,
                     int dim, int k, long long index_base, float* top_score, int64_t* top_index, void* stream) {
     FFR_DEVICE_SCOPE(h); RC(check_fwd(h, false, false, 1));
-    if (dim != 512) return fail(h, FFR_ERR_UNSUPPORTED, "ffr_search_topk: dim must be 512, got %d", dim);
+    RC(check_dim(h, "ffr_search_topk", dim));
     if (!query || !top_score || !top_index || Q < 1 || k < 1 || k > 128 || G < 0 || (G > 0 && (!gallery || !gallery_norms)))
         return fail(h, FFR_ERR_ARG, "ffr_search_topk: bad arguments (Q >= 1, 1 <= k <= 128, G >= 0, non-null pointers)");
     if (misaligned16(query) || (G > 0 && misaligned16(gallery)))
@@ -273,20 +297,13 @@ int ffr_search_topk(ffr_handle* h, const float* query, int Q, const float* galle
     long long chunk_rows = 0;
     search_plan(Q, G, h->num_cus, &T, &S, &chunk_rows);
     // scratch: probe norms [Q], then the chunk lists [S][Q][k] (scores, indices) when there is more than one chunk
-    const size_t norm_bytes = ((size_t)Q * 4 + 255) & ~(size_t)255;
-    const size_t list_s = S > 1 ? (((size_t)S * Q * k * 4 + 255) & ~(size_t)255) : 0;
-    const size_t need = norm_bytes + list_s + (S > 1 ? (size_t)S * Q * k * 8 : 0);
-    if (need > h->search_bytes) {
-        if (h->search_buf) { hipDeviceSynchronize(); hipFree(h->search_buf); h->search_buf = nullptr; h->search_bytes = 0; }
-        void* p = nullptr;
-        if (hipMalloc(&p, need) != hipSuccess) return fail(h, FFR_ERR_NOMEM, "hipMalloc of %zu search bytes failed", need);
-        h->search_buf = (char*)p;
-        h->search_bytes = need;
-        ++h->generation;          // a graph captured around an earlier call points at the old scratch
-    }
-    float* qnorm = (float*)h->search_buf;
-    float* part_s = S > 1 ? (float*)(h->search_buf + norm_bytes) : top_score;
-    int64_t* part_i = S > 1 ? (int64_t*)(h->search_buf + norm_bytes + list_s) : top_index;
+    float* qnorm = nullptr;
+    float* part_s = top_score;
+    int64_t* part_i = top_index;
+    RC(carve(h, h->search, "search", [&](Arena& a) {
+        qnorm = a.take(Q);
+        if (S > 1) { part_s = a.take((size_t)S * Q * k); part_i = a.take<int64_t>((size_t)S * Q * k); }
+    }));
     Scope s(h, st, FFR_KC_SCORE, 2.0 * Q * (double)G * dim, 4.0 * (double)G * (dim + 1) + 4.0 * Q * dim + 12.0 * Q * k);
     HIPCK(h, launch_row_norms(query, Q, qnorm, st));
     HIPCK(h, launch_search_topk(query, qnorm, Q, gallery, gallery_norms, G, k, index_base, T, S, chunk_rows, part_s, part_i,
@@ -307,88 +324,58 @@ int ffr_topk_merge(ffr_handle* h, const float* score, const int64_t* index, int 
 }
 
 // ---- clustering (cluster.hip) ----------------------------------------------------------------------------------------
-// scratch of ffr_cluster_threshold / ffr_cluster_extend: row norms [N] (used when the caller passes none), then parent [N]
-static int cluster_scratch(ffr_handle* h, long long N, float** own_norms, int** parent) {
-    const size_t norm_bytes = ((size_t)N * 4 + 255) & ~(size_t)255;
-    const size_t need = norm_bytes + (size_t)N * 4;
-    if (need > h->cluster_bytes) {
-        if (h->cluster_buf) { hipDeviceSynchronize(); hipFree(h->cluster_buf); h->cluster_buf = nullptr; h->cluster_bytes = 0; }
-        void* p = nullptr;
-        if (hipMalloc(&p, need) != hipSuccess) return fail(h, FFR_ERR_NOMEM, "hipMalloc of %zu clustering bytes failed", need);
-        h->cluster_buf = (char*)p;
-        h->cluster_bytes = need;
-        ++h->generation;          // a graph captured around an earlier call points at the old scratch
+// The body of ffr_cluster_threshold (ext = false: no prior, N_old = 0) and of ffr_cluster_extend; `who` names the entry in messages
+static int cluster_rows(ffr_handle* h, const char* who, bool ext, const float* emb, const float* norms, long long N_old,
+                        long long N, int dim, float threshold, const int64_t* prior, int64_t* rep, void* stream) {
+    FFR_DEVICE_SCOPE(h); RC(check_fwd(h, false, false, 1));
+    RC(check_dim(h, who, dim));
+    if (N < 0 || N >= (1ll << 31)) return fail(h, FFR_ERR_ARG, "%s: N must be in [0, 2^31), got %lld", who, N);
+    if (N_old < 0 || N_old > N) return fail(h, FFR_ERR_ARG, "%s: N_old must be in [0, N = %lld], got %lld", who, N, N_old);
+    if (threshold != threshold) return fail(h, FFR_ERR_ARG, "%s: the threshold is NaN", who);
+    if (N == 0) return FFR_OK;
+    if (!emb || !rep || (ext && !prior)) return fail(h, FFR_ERR_ARG, "%s: emb / %srep is null", who, ext ? "prior / " : "");
+    if (misaligned16(emb) || ((uintptr_t)rep & 7) || ((uintptr_t)prior & 7) || ((uintptr_t)norms & 3))
+        return fail(h, FFR_ERR_ARG, "%s: emb rows must be 16-byte aligned (%srep 8, norms 4)", who, ext ? "prior and " : "");
+    const long long n_new = N - N_old;
+    const bool join = !ext || (N > 1 && n_new > 0);       // are there pairs to score?
+    int T = 0, S = 0;
+    long long chunk_rows = 0;
+    if (!ext) cluster_plan(N, h->num_cus, &T, &S, &chunk_rows);
+    else if (join) cluster_extend_plan(N_old, N, h->num_cus, &T, &S, &chunk_rows);
+    if ((long long)T * S >= (1ll << 31)) {
+        if (ext) return fail(h, FFR_ERR_UNSUPPORTED, "%s: N = %lld with %lld new rows needs %lld blocks, over the grid limit", who, N, n_new, (long long)T * S);
+        return fail(h, FFR_ERR_UNSUPPORTED, "%s: N = %lld needs %lld blocks, over the grid limit", who, N, (long long)T * S);
     }
-    *own_norms = (float*)h->cluster_buf;
-    *parent = (int*)(h->cluster_buf + norm_bytes);
+    hipStream_t st = (hipStream_t)stream;
+    // scratch: row norms [N] (used when the caller passes none), then parent [N]
+    float* own_norms = nullptr;
+    int* parent = nullptr;
+    RC(carve(h, h->cluster, "clustering", [&](Arena& a) { own_norms = a.take(N); parent = a.take<int>(N); }));
+    const double pairs = ext ? 2.0 * (double)N_old * (double)n_new + (double)n_new * (double)(n_new - 1) : (double)N * (double)(N - 1);
+    Scope s(h, st, FFR_KC_SCORE, dim * pairs, 2.0 * (double)N * (dim + 1) + (ext ? 24.0 : 16.0) * N);
+    if (!norms && join) {
+        HIPCK(h, launch_row_norms(emb, N, own_norms, st));
+        norms = own_norms;
+    }
+    if (ext) HIPCK(h, launch_cluster_extend(emb, norms, N_old, N, threshold, T, S, chunk_rows, prior, parent, rep, st));
+    else HIPCK(h, launch_cluster_threshold(emb, norms, N, threshold, T, S, chunk_rows, parent, rep, st));
     return FFR_OK;
 }
 
 int ffr_cluster_threshold(ffr_handle* h, const float* emb, const float* norms, long long N, int dim, float threshold,
                           int64_t* rep, void* stream) {
-    FFR_DEVICE_SCOPE(h); RC(check_fwd(h, false, false, 1));
-    if (dim != 512) return fail(h, FFR_ERR_UNSUPPORTED, "ffr_cluster_threshold: dim must be 512, got %d", dim);
-    if (N < 0 || N >= (1ll << 31)) return fail(h, FFR_ERR_ARG, "ffr_cluster_threshold: N must be in [0, 2^31), got %lld", N);
-    if (threshold != threshold) return fail(h, FFR_ERR_ARG, "ffr_cluster_threshold: the threshold is NaN");
-    if (N == 0) return FFR_OK;
-    if (!emb || !rep) return fail(h, FFR_ERR_ARG, "ffr_cluster_threshold: emb / rep is null");
-    if (misaligned16(emb) || ((uintptr_t)rep & 7) || ((uintptr_t)norms & 3))
-        return fail(h, FFR_ERR_ARG, "ffr_cluster_threshold: emb rows must be 16-byte aligned (rep 8, norms 4)");
-    int T = 0, S = 0;
-    long long chunk_rows = 0;
-    cluster_plan(N, h->num_cus, &T, &S, &chunk_rows);
-    if ((long long)T * S >= (1ll << 31))
-        return fail(h, FFR_ERR_UNSUPPORTED, "ffr_cluster_threshold: N = %lld needs %lld blocks, over the grid limit", N, (long long)T * S);
-    hipStream_t st = (hipStream_t)stream;
-    float* own_norms = nullptr;
-    int* parent = nullptr;
-    RC(cluster_scratch(h, N, &own_norms, &parent));
-    Scope s(h, st, FFR_KC_SCORE, (double)N * (double)(N - 1) * dim, 2.0 * (double)N * (dim + 1) + 16.0 * N);
-    if (!norms) {
-        HIPCK(h, launch_row_norms(emb, N, own_norms, st));
-        norms = own_norms;
-    }
-    HIPCK(h, launch_cluster_threshold(emb, norms, N, threshold, T, S, chunk_rows, parent, rep, st));
-    return FFR_OK;
+    return cluster_rows(h, "ffr_cluster_threshold", false, emb, norms, 0, N, dim, threshold, nullptr, rep, stream);
 }
 
 int ffr_cluster_extend(ffr_handle* h, const float* emb, const float* norms, long long N_old, long long N, int dim,
                        float threshold, const int64_t* prior, int64_t* rep, void* stream) {
-    FFR_DEVICE_SCOPE(h); RC(check_fwd(h, false, false, 1));
-    if (dim != 512) return fail(h, FFR_ERR_UNSUPPORTED, "ffr_cluster_extend: dim must be 512, got %d", dim);
-    if (N < 0 || N >= (1ll << 31)) return fail(h, FFR_ERR_ARG, "ffr_cluster_extend: N must be in [0, 2^31), got %lld", N);
-    if (N_old < 0 || N_old > N) return fail(h, FFR_ERR_ARG, "ffr_cluster_extend: N_old must be in [0, N = %lld], got %lld", N, N_old);
-    if (threshold != threshold) return fail(h, FFR_ERR_ARG, "ffr_cluster_extend: the threshold is NaN");
-    if (N == 0) return FFR_OK;
-    if (!emb || !rep || !prior) return fail(h, FFR_ERR_ARG, "ffr_cluster_extend: emb / prior / rep is null");
-    if (misaligned16(emb) || ((uintptr_t)rep & 7) || ((uintptr_t)prior & 7) || ((uintptr_t)norms & 3))
-        return fail(h, FFR_ERR_ARG, "ffr_cluster_extend: emb rows must be 16-byte aligned (prior and rep 8, norms 4)");
-    const long long n_new = N - N_old;
-    const bool join = N > 1 && n_new > 0;
-    int T = 0, S = 0;
-    long long chunk_rows = 0;
-    if (join) cluster_extend_plan(N_old, N, h->num_cus, &T, &S, &chunk_rows);
-    if ((long long)T * S >= (1ll << 31))
-        return fail(h, FFR_ERR_UNSUPPORTED, "ffr_cluster_extend: N = %lld with %lld new rows needs %lld blocks, over the grid limit", N,
-                    n_new, (long long)T * S);
-    hipStream_t st = (hipStream_t)stream;
-    float* own_norms = nullptr;
-    int* parent = nullptr;
-    RC(cluster_scratch(h, N, &own_norms, &parent));
-    Scope s(h, st, FFR_KC_SCORE, (double)dim * (2.0 * (double)N_old * (double)n_new + (double)n_new * (double)(n_new - 1)),
-            2.0 * (double)N * (dim + 1) + 24.0 * N);
-    if (!norms && join) {
-        HIPCK(h, launch_row_norms(emb, N, own_norms, st));
-        norms = own_norms;
-    }
-    HIPCK(h, launch_cluster_extend(emb, norms, N_old, N, threshold, T, S, chunk_rows, prior, parent, rep, st));
-    return FFR_OK;
+    return cluster_rows(h, "ffr_cluster_extend", true, emb, norms, N_old, N, dim, threshold, prior, rep, stream);
 }
 
 int ffr_cluster_templates(ffr_handle* h, const float* emb, const float* norms, const int64_t* order, const int64_t* offsets,
                           long long C, int dim, float* templates, void* stream) {
     FFR_DEVICE_SCOPE(h); RC(check_fwd(h, false, false, 1));
-    if (dim != 512) return fail(h, FFR_ERR_UNSUPPORTED, "ffr_cluster_templates: dim must be 512, got %d", dim);
+    RC(check_dim(h, "ffr_cluster_templates", dim));
     if (C < 0 || C >= (1ll << 31)) return fail(h, FFR_ERR_ARG, "ffr_cluster_templates: C must be in [0, 2^31), got %lld", C);
     if (C == 0) return FFR_OK;
     if (!emb || !order || !offsets || !templates) return fail(h, FFR_ERR_ARG, "ffr_cluster_templates: a null pointer");
@@ -459,27 +446,18 @@ int ffr_embed_aligned(ffr_handle* h, const uint8_t* frames, int F, int H, int W,
     RC(align_warp_check(h, frames, F, H, W, pitch_bytes, frame_index, 112, 112));
     hipStream_t st = (hipStream_t)stream;
     // scratch: transforms [N][6] fp64, valid [N], crops [N][112][112][3]
-    const size_t a_bytes = ((size_t)N * 48 + 255) & ~(size_t)255, v_bytes = ((size_t)N + 255) & ~(size_t)255;
-    const size_t need = a_bytes + v_bytes + (size_t)N * 112 * 112 * 3;
-    if (need > h->align_bytes) {
-        if (h->align_buf) { hipDeviceSynchronize(); hipFree(h->align_buf); h->align_buf = nullptr; h->align_bytes = 0; }
-        void* p = nullptr;
-        if (hipMalloc(&p, need) != hipSuccess) return fail(h, FFR_ERR_NOMEM, "hipMalloc of %zu alignment bytes failed", need);
-        h->align_buf = (char*)p;
-        h->align_bytes = need;
-        ++h->generation;          // a graph captured around an earlier call points at the old scratch
-    }
-    double* A = (double*)h->align_buf;
-    uint8_t* v = (uint8_t*)(h->align_buf + a_bytes);
-    uint8_t* crop = (uint8_t*)(h->align_buf + a_bytes + v_bytes);
-    Work w;
-    RC(ensure_arena_encoder(h, N, 112, 112, &w));
+    double* A = nullptr;
+    uint8_t *v = nullptr, *crop = nullptr;
+    RC(carve(h, h->align, "alignment", [&](Arena& a) {
+        A = a.take<double>((size_t)N * 6);
+        v = a.take<uint8_t>(N);
+        crop = a.take<uint8_t>((size_t)N * 112 * 112 * 3);
+    }));
     RC(align_tfm(h, landmarks, tmpl, N, K, frame_index, F, A, v, st));
     RC(align_warp(h, frames, F, H, W, pitch_bytes, frame_index, A, v, N, 112, 112, crop, st));
     if (valid) HIPCK(h, hipMemcpyAsync(valid, v, (size_t)N, hipMemcpyDeviceToDevice, st));
-    U8In u8{crop, flip};
-    RC(run_encoder(h, w, nullptr, N, 112, 112, w.X, f, st, &u8));
-    return run_recnet(h, w, N, f_new, nullptr, st);
+    const U8In u8{crop, flip};
+    return embed_tail(h, nullptr, &u8, N, f_new, f, st);
 }
 
 // ---- per-layer arithmetic plan --------------------------------------------------------------------------------------
@@ -525,7 +503,7 @@ int ffr_calibrate(ffr_handle* h, const float* x, const float* featmap, int N, in
     if ((x != nullptr) == (featmap != nullptr)) return fail(h, FFR_ERR_ARG, "ffr_calibrate: pass images (x) or a featmap, exactly one of them");
     const bool enc = x != nullptr;
     FFR_DEVICE_SCOPE(h); RC(check_fwd(h, enc, !enc, N));
-    if (enc && (H < 32 || W < 32 || (H & 15) || (W & 15))) return fail(h, FFR_ERR_ARG, "H and W must be multiples of 16, >= 32");
+    if (enc) RC(check_hw(h, H, W));
     if (!enc && (H != 7 || W != 7)) return fail(h, FFR_ERR_ARG, "ffr_calibrate: a featmap is [N,512,7,7] (H = W = 7)");
     const bool is112 = enc && H == 112 && W == 112;
     const bool rec = !enc || (h->rec_loaded && is112);
@@ -576,11 +554,8 @@ int ffr_calibrate(ffr_handle* h, const float* x, const float* featmap, int N, in
     HIPCK(h, hipMemsetAsync(table, 0, (size_t)max_trials * 8 * sizeof(float), st));
 
     auto forward = [&]() -> int {
-        if (enc) {
-            RC(run_encoder(h, w, x, N, H, W, featmap_nhwc, is112 ? f_cur : nullptr, st));
-        } else {
-            HIPCK(h, launch_nchw_to_nhwc(featmap, w.X, 512, N, 49, 512, st));
-        }
+        if (enc) RC(run_encoder(h, w, x, N, H, W, featmap_nhwc, is112 ? f_cur : nullptr, st));
+        else RC(featmap_to_x(h, w, featmap, N, st));
         if (rec) RC(run_recnet(h, w, N, fnew_cur, nullptr, st));
         return FFR_OK;
     };
@@ -664,6 +639,7 @@ const OptEntry OPTIONS[] = {
     {"channel_rows", &Options::channel_rows, nullptr, 0, 4}, {"igemm_split", &Options::igemm_split, nullptr, 0, 1},
     {"wf_trace", &Options::wf_trace, nullptr, 0, 1}, {"igemm_trace", &Options::igemm_trace, nullptr, 0, 1},
 };
+long long option_value(const Options& o, const OptEntry& e) { return e.i ? (long long)(o.*(e.i)) : o.*(e.l); }
 const OptEntry* find_option(const char* name) {
     if (name) for (const OptEntry& e : OPTIONS) if (!strcmp(e.name, name)) return &e;
     return nullptr;
@@ -683,8 +659,7 @@ int ffr_set_option(ffr_handle* h, const char* name, long long value) {
     // every knob changes which kernels a forward launches or which scratch buffers they use: a hipGraph captured
     // before the change replays the OLD sequence, so a changed value invalidates captures (GraphedEmbed re-captures
     // when ffr_generation moves)
-    const long long old = e->i ? (long long)(h->opt.*(e->i)) : h->opt.*(e->l);
-    if (old != value) ++h->generation;
+    if (option_value(h->opt, *e) != value) ++h->generation;
     if (e->i) h->opt.*(e->i) = (int)value; else h->opt.*(e->l) = value;
     return FFR_OK;
 }
@@ -693,7 +668,7 @@ int ffr_get_option(const ffr_handle* h, const char* name, long long* value) {
     if (!h || !value) return fail(nullptr, FFR_ERR_ARG, "ffr_get_option: bad arguments");
     const OptEntry* e = find_option(name);
     if (!e) return fail(const_cast<ffr_handle*>(h), FFR_ERR_ARG, "ffr_get_option: unknown option '%s'", name ? name : "(null)");
-    *value = e->i ? (long long)(h->opt.*(e->i)) : h->opt.*(e->l);
+    *value = option_value(h->opt, *e);
     return FFR_OK;
 }
 
@@ -827,7 +802,7 @@ int ffr_op_conv3x3(ffr_handle* h, const float* x, int N, int H, int W, int cin, 
 int ffr_encoder_trunk_nhwc(ffr_handle* h, const float* x, int N, int H, int W, int n_blocks, float* out, void* stream) {
     FFR_DEVICE_SCOPE(h); RC(check_fwd(h, true, false, N));
     if (!x || !out || n_blocks < 0 || n_blocks > (int)h->blocks.size()) return fail(h, FFR_ERR_ARG, "ffr_encoder_trunk_nhwc: bad arguments");
-    if (H < 32 || W < 32 || (H & 15) || (W & 15)) return fail(h, FFR_ERR_ARG, "H and W must be multiples of 16, >= 32");
+    RC(check_hw(h, H, W));
     hipStream_t st = (hipStream_t)stream;
     Work w;
     RC(ensure_arena_encoder(h, N, H, W, &w));
@@ -844,7 +819,7 @@ int ffr_recnet_debug(ffr_handle* h, const float* featmap_nchw, int N, float* ss_
     hipStream_t st = (hipStream_t)stream;
     Work w;
     RC(ensure_arena(h, N, 112, 112, &w));
-    HIPCK(h, launch_nchw_to_nhwc(featmap_nchw, w.X, 512, N, 49, 512, st));
+    RC(featmap_to_x(h, w, featmap_nchw, N, st));
     RecDebug d{ss_space, M_space, feat_space, feat_channel_raw, feat_channel, ss_channel0, M_channel0};
     return run_recnet(h, w, N, nullptr, &d, st);
 }

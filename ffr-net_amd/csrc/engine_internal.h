@@ -79,6 +79,8 @@ struct Options {
     // maps wf_mapv, wf_mapx, wf_maph and wm_xcdpairs only that one: the maps that lost are gone from the kernels).
 };
 
+struct DevBuf { char* p = nullptr; size_t bytes = 0; };
+
 struct ProfRec {
     hipEvent_t e0, e1;
     int kc;
@@ -113,11 +115,10 @@ struct ffr_handle {
     ffr_eng::ConvW fc;
     ffr_eng::ConvW sp[9], fm[3], mg[3];
     ffr::ChannelPathWeights cw{};
-    // workspace arena
-    char* arena = nullptr;
-    size_t arena_bytes = 0;
-    int* tickets = nullptr;      // stream-K arrival counters (zero between launches)
-    size_t tickets_cap = 0;
+    // grow-only device buffers (grow(), forward.cpp): the workspace arena, the stream-K arrival counters (int, zero between
+    // launches), and the scratch of ffr_search_topk (probe norms + per-chunk top-k lists), of ffr_cluster_threshold /
+    // ffr_cluster_extend (row norms [N] + union-find parent [N]) and of ffr_embed_aligned (transforms, valid flags, crops)
+    ffr_eng::DevBuf arena, tickets, search, cluster, align;
     ffr_eng::Options opt;
     // profiling
     bool prof = false;
@@ -127,16 +128,7 @@ struct ffr_handle {
     ffr_eng::TrainState* train = nullptr;
     // weight-gradient launch plans of the most recent backward (ffr_train_wgrad_plan)
     std::vector<ffr_wgrad_launch> wgrad_log;
-    // 1:N search scratch (ffr_search_topk): probe norms + per-chunk top-k lists; grows on demand
-    char* search_buf = nullptr;
-    size_t search_bytes = 0;
-    // clustering scratch (ffr_cluster_threshold): row norms [N] + union-find parent [N] int32; grows on demand
-    char* cluster_buf = nullptr;
-    size_t cluster_bytes = 0;
-    // alignment scratch (ffr_embed_aligned): transforms [N][6] fp64, valid flags [N], crops [N][112][112][3]; grows on demand
-    char* align_buf = nullptr;
-    size_t align_bytes = 0;
-    // bumped whenever device memory a caller may have captured (hipGraph) is released: workspace regrowth, weight
+    // bumped whenever device memory a caller may have captured (hipGraph) moves: every allocation of grow(), weight
     // reload, ffr_train_init
     unsigned long long generation = 1;
 };
@@ -278,13 +270,13 @@ void plan_gemm_stream(long long T, int cout_pad, int* tile, int* nblocks);
 int run_gemm(ffr_handle* h, IgemmArgs& a, const ConvCall& c, double flops, double bytes, hipStream_t st, double fuse = -1.0);
 int run_conv(ffr_handle* h, const ConvW& L, const ConvCall& c, hipStream_t st);
 
+// Hands out 256-byte aligned pieces of one buffer; on a null base it only measures (off = the bytes the pieces need)
 struct Arena {
-    char* base; size_t off = 0, cap;
-    Arena(char* b, size_t c) : base(b), cap(c) {}
-    float* take(size_t floats) {
-        size_t bytes = (floats * 4 + 255) & ~(size_t)255;
-        float* p = base ? (float*)(base + off) : nullptr;
-        off += bytes;
+    char* base; size_t off = 0;
+    explicit Arena(char* b) : base(b) {}
+    template <class T = float> T* take(size_t count) {
+        T* p = base ? (T*)(base + off) : nullptr;
+        off += (count * sizeof(T) + 255) & ~(size_t)255;
         return p;
     }
 };
@@ -309,6 +301,9 @@ inline ConvCall conv_call(const Work& w, ConvForce force = ConvForce::Auto) {   
     c.winoV = w.winoV; c.winoM = w.winoM; c.wino_cap = w.wino_cap; c.force = force;
     return c;
 }
+// The one place a DevBuf is allocated: enough already -> nothing; else synchronise, free, hipMalloc (and zero fill), and
+// ++generation -- a graph captured around an earlier call points at the old buffer.  FFR_ERR_NOMEM names `what`.
+int grow(ffr_handle* h, DevBuf& b, size_t need_bytes, const char* what, bool zeroed = false);
 int ensure_arena(ffr_handle* h, int N, int H, int W, Work* w);
 int ensure_arena_encoder(ffr_handle* h, int N, int H, int W, Work* w);     // + the exact-tiling weight sets an encoder forward of this size uses
 // uint8 HWC RGB input of the stem; with img2, images [n_split, N) come from img2 and flip[] has one flag per pair

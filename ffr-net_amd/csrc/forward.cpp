@@ -12,7 +12,7 @@ namespace ffr_eng {
 // ---- workspace ---------------------------------------------------------------------------
 
 Work layout(const Options& opt, char* base, int N, int H, int W) {
-    Arena a(base, 0);
+    Arena a(base);
     Work w{};
     const size_t S0 = (size_t)N * H * W * 64;
     const size_t hw16 = (size_t)(H / 16) * (W / 16);
@@ -57,29 +57,24 @@ Work layout(const Options& opt, char* base, int N, int H, int W) {
     return w;
 }
 
-int ensure_arena(ffr_handle* h, int N, int H, int W, Work* w) {
-    const size_t need = layout(h->opt, nullptr, N, H, W).total;
-    if (need > h->arena_bytes) {
-        if (h->arena) { hipDeviceSynchronize(); hipFree(h->arena); h->arena = nullptr; h->arena_bytes = 0; ++h->generation; }
-        void* p = nullptr;
-        if (hipMalloc(&p, need) != hipSuccess)
-            return fail(h, FFR_ERR_NOMEM, "hipMalloc of %zu workspace bytes failed", need);
-        h->arena = (char*)p;
-        h->arena_bytes = need;
+int grow(ffr_handle* h, DevBuf& b, size_t need_bytes, const char* what, bool zeroed) {
+    if (need_bytes <= b.bytes) return FFR_OK;
+    ++h->generation;          // also when the allocation below fails: the old buffer is gone by then
+    if (b.p) { hipDeviceSynchronize(); hipFree(b.p); b = DevBuf(); }
+    void* p = nullptr;
+    if (hipMalloc(&p, need_bytes) != hipSuccess) return fail(h, FFR_ERR_NOMEM, "hipMalloc of %zu %s bytes failed", need_bytes, what);
+    if (zeroed && hipMemset(p, 0, need_bytes) != hipSuccess) { hipFree(p); return fail(h, FFR_ERR_HIP, "hipMemset failed"); }
+    b.p = (char*)p;
+    b.bytes = need_bytes;
+    return FFR_OK;
+}
 
-    }
-    const size_t need_t = (size_t)N * H * W / 64 + 4096;
-    if (need_t > h->tickets_cap) {
-        if (h->tickets) { hipDeviceSynchronize(); hipFree(h->tickets); h->tickets = nullptr; h->tickets_cap = 0; ++h->generation; }
-        void* p = nullptr;
-        if (hipMalloc(&p, need_t * sizeof(int)) != hipSuccess) return fail(h, FFR_ERR_NOMEM, "hipMalloc of the ticket array failed");
-        if (hipMemset(p, 0, need_t * sizeof(int)) != hipSuccess) return fail(h, FFR_ERR_HIP, "hipMemset failed");
-        h->tickets = (int*)p;
-        h->tickets_cap = need_t;
-    }
-    *w = layout(h->opt, h->arena, N, H, W);
-    w->tickets = h->tickets;
-    w->tickets_cap = h->tickets_cap;
+int ensure_arena(ffr_handle* h, int N, int H, int W, Work* w) {
+    RC(grow(h, h->arena, layout(h->opt, nullptr, N, H, W).total, "workspace"));
+    RC(grow(h, h->tickets, ((size_t)N * H * W / 64 + 4096) * sizeof(int), "ticket", true));
+    *w = layout(h->opt, h->arena.p, N, H, W);
+    w->tickets = (int*)h->tickets.p;
+    w->tickets_cap = h->tickets.bytes / sizeof(int);
     return FFR_OK;
 }
 

@@ -18,7 +18,7 @@ int ensure_ctx(ffr_handle* h, TrainState* t, Ctx& c, int G, int N) {
     free_ctx(c);
     const size_t imgs = (size_t)G * N, rows = imgs * 49, crow = imgs * 512;
     auto carve = [&](char* base) -> size_t {
-        Arena a(base, 0);
+        Arena a(base);
         c.X = a.take(rows * 512 + 64 * 512);
         c.bufS = a.take(rows * 576); c.bufF = a.take(rows * 1024); c.bufM = a.take(rows * 1536);
         c.ms = a.take(rows * 64); c.featnew = a.take(rows * 512);
@@ -55,7 +55,7 @@ int ensure_scratch(ffr_handle* h, TrainState* t, int imgs_i) {
     cap.part = (size_t)512 * 512;
     for (int i = 0; i < 15; ++i) { const TLayer& L = train_layer(t, i); grow_to(cap, layer_scratch(L.cin_pad, L.cout_pad, L.dgrad_width, imgs_i)); }
     auto carve = [&](char* base) -> size_t {
-        Arena a(base, 0);
+        Arena a(base);
         carve_scratch(a, cap, NET_SLAB_FLOATS, t->sc);
         t->dFeatNew = a.take(rows * 512); t->d512a = a.take(rows * 512); t->d512b = a.take(rows * 512);
         t->dBufM = a.take(rows * 1024); t->extM = a.take(rows * 1024); t->dF = a.take(rows * 1024);

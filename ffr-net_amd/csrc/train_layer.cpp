@@ -228,7 +228,7 @@ extern "C" int ffr_op_convlayer_train(ffr_handle* h, const float* x_nhwc, int G,
     if (h->train) { s.wino = h->train->sc.wino; s.fused = h->train->sc.fused; }     // ffr_train_option, when a training state exists
     const LayerScratch cap = layer_scratch(L.cin_pad, L.cout_pad, L.dgrad_width, G * N);
     auto carve = [&](char* base) -> size_t {
-        Arena a(base, 0);
+        Arena a(base);
         L.gw = a.take(wp.size()); gv = a.take((size_t)5 * L.cout_pad); sv.y = a.take((size_t)rows * L.cout_pad);
         carve_bn(a, G, L.cout_pad, sv.bn);
         carve_scratch(a, cap, op_slab_floats(L), s);

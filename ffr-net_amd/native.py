@@ -174,11 +174,11 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
-def _check_dev(t, name, shape_tail=None, device=None):
-    """Boundary check of a tensor handed to the library as a raw pointer.  `device`: the handle's device -- a tensor
-    on ANOTHER GPU is rejected (its pointer would be dereferenced by kernels running on the handle's GPU: peer reads
-    over xGMI at best, a fault at worst; one process per GPU must `torch.cuda.set_device(local_rank)` or pass explicit
-    devices)."""
+def _check(t, name, device, dtype=torch.float32, shape=None, hint=''):
+    """Boundary check of a tensor handed to the library as a raw pointer: a torch.Tensor on `device` (the handle's; None
+    skips that one question) of `dtype`, and of `shape` when given -- one entry per dimension, a string standing for any
+    size.  A tensor on ANOTHER GPU is rejected: its pointer would be dereferenced by kernels running on the handle's GPU
+    (peer reads over xGMI at best, a fault at worst)."""
     if not isinstance(t, torch.Tensor):
         raise TypeError('%s must be a torch.Tensor' % name)
     if not t.is_cuda:
@@ -188,41 +188,30 @@ def _check_dev(t, name, shape_tail=None, device=None):
         raise RuntimeError('ffrnet_amd: %s is on %s but this Engine lives on %s; move the tensor there (or create the '
                            'Engine on the tensor\'s device: one process per GPU calls torch.cuda.set_device(local_rank) '
                            'before anything else)' % (name, t.device, device))
-    if t.dtype != torch.float32:
-        raise RuntimeError('ffrnet_amd: %s must be float32, got %s' % (name, t.dtype))
-    if shape_tail is not None and tuple(t.shape[1:]) != tuple(shape_tail):
-        raise RuntimeError('ffrnet_amd: %s expected shape [N,%s], got %s'
-                           % (name, ','.join(map(str, shape_tail)), list(t.shape)))
+    if t.dtype != dtype:
+        raise RuntimeError('ffrnet_amd: %s must be %s, got %s' % (name, str(dtype).replace('torch.', ''), t.dtype))
+    if shape is not None and (len(t.shape) != len(shape) or
+                              any(not isinstance(want, str) and got != want for got, want in zip(t.shape, shape))):
+        raise RuntimeError('ffrnet_amd: %s expected shape [%s]%s, got %s'
+                           % (name, ','.join(map(str, shape)), hint, list(t.shape)))
 
 
-def _check_u8(t, name, device, hw=None):
-    """Boundary check of a decoded-image tensor: uint8 [N,H,W,3] (HWC, RGB) on the handle's device."""
-    if not isinstance(t, torch.Tensor):
-        raise TypeError('%s must be a torch.Tensor' % name)
-    if not t.is_cuda:
-        raise RuntimeError('ffrnet_amd: %s is on %s; the native HIP path needs a ROCm device tensor (there is no CPU '
-                           'fallback)' % (name, t.device))
-    if t.device.index != device.index:
-        raise RuntimeError('ffrnet_amd: %s is on %s but this Engine lives on %s' % (name, t.device, device))
-    if t.dtype != torch.uint8:
-        raise RuntimeError('ffrnet_amd: %s must be uint8 images [N,H,W,3], got %s' % (name, t.dtype))
-    if t.dim() != 4 or t.size(3) != 3 or (hw is not None and tuple(t.shape[1:3]) != tuple(hw)):
-        raise RuntimeError('ffrnet_amd: %s expected shape [N,%s,3] (HWC, RGB), got %s'
-                           % (name, '%d,%d' % tuple(hw) if hw is not None else 'H,W', list(t.shape)))
+def _check_dev(t, name, shape_tail=None, device=None):
+    """_check of a float32 tensor [N, *shape_tail]."""
+    _check(t, name, device, shape=None if shape_tail is None else ('N',) + tuple(shape_tail))
 
 
-def _flip_flags(flip, n, device, name='flip'):
-    """uint8 [n] device copy of per-image / per-pair flip flags (bool or uint8; nonzero = mirror), or None."""
-    if flip is None:
-        return None
-    if not isinstance(flip, torch.Tensor) or flip.dtype not in (torch.bool, torch.uint8):
-        raise RuntimeError('ffrnet_amd: %s must be a bool or uint8 tensor, got %s'
-                           % (name, flip.dtype if isinstance(flip, torch.Tensor) else type(flip)))
-    if flip.numel() != n:
-        raise RuntimeError('ffrnet_amd: %s must hold %d flags, got %d' % (name, n, flip.numel()))
-    if flip.is_cuda and flip.device.index != device.index:
-        raise RuntimeError('ffrnet_amd: %s is on %s but this Engine lives on %s' % (name, flip.device, device))
-    return flip.reshape(-1).to(device, torch.uint8).contiguous()
+_U8_HINT = ' (HWC, RGB)'
+
+
+def _loss_weights(loss_weight):
+    return (C.c_double * 4)(*[float(x) for x in loss_weight])
+
+
+def _arith_code(arith):
+    if arith not in ARITH:
+        raise ValueError("ffrnet_amd: arith must be 'direct' or 'winograd', got %r" % (arith,))
+    return ARITH[arith]
 
 
 class Engine(object):
@@ -257,6 +246,43 @@ class Engine(object):
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _call(self, fn, *args, stream=True):
+        """One native call on this handle under its device context: fn(handle, *args[, torch's current stream]), status
+        checked."""
+        with torch.cuda.device(self.device):
+            self._ck(fn(self._h, *args, self._stream()) if stream else fn(self._h, *args))
+
+    def _tensor(self, t, name, dtype=torch.float32, shape=None, hint=''):
+        """_check against this Engine's device: every tensor check of the class goes through here."""
+        _check(t, name, self.device, dtype, shape, hint)
+
+    def _flags(self, flip, n, name='flip'):
+        """uint8 [n] device copy of per-image / per-pair flip flags (bool or uint8; nonzero = mirror), or None."""
+        if flip is None:
+            return None
+        if not isinstance(flip, torch.Tensor) or flip.dtype not in (torch.bool, torch.uint8):
+            raise RuntimeError('ffrnet_amd: %s must be a bool or uint8 tensor, got %s'
+                               % (name, flip.dtype if isinstance(flip, torch.Tensor) else type(flip)))
+        if flip.numel() != n:
+            raise RuntimeError('ffrnet_amd: %s must hold %d flags, got %d' % (name, n, flip.numel()))
+        if flip.is_cuda and flip.device.index != self.device.index:
+            raise RuntimeError('ffrnet_amd: %s is on %s but this Engine lives on %s' % (name, flip.device, self.device))
+        return flip.reshape(-1).to(self.device, torch.uint8).contiguous()
+
+    def _empty(self, *shape, dtype=torch.float32):
+        return torch.empty(shape, device=self.device, dtype=dtype)
+
+    def _embed_outputs(self, n, want_f, out=None):
+        """(f_new[n,512], f[n,512] or None): new tensors, or the caller's preallocated pair `out` after its checks."""
+        if out is None:
+            return self._empty(n, 512), self._empty(n, 512) if want_f else None
+        for o, nm in zip(out, ('out[0]', 'out[1]')):
+            if o is not None:
+                self._tensor(o, nm)
+                if tuple(o.shape) != (n, 512) or not o.is_contiguous():
+                    raise RuntimeError('ffrnet_amd: %s must be a contiguous [%d,512] tensor, got %s' % (nm, n, list(o.shape)))
+        return out
 
     @staticmethod
     def _descs(sd):
@@ -295,49 +321,37 @@ class Engine(object):
         self._recnet_sig = None      # whoever loaded through a shell records its signature after this call
 
     # -- forward --------------------------------------------------------------
-    def encoder_forward(self, x, want_f=True, want_featmap=True):
-        _check_dev(x, 'x', device=self.device)
-        if x.dim() != 4 or x.size(1) != 3:
-            raise RuntimeError('ffrnet_amd: encoder input must be [N,3,H,W], got %s' % list(x.shape))
-        x = x.contiguous()
-        n, _, h, w = x.shape
+    def _encoder_forward(self, fn, inputs, n, h, w, want_f, want_featmap):
+        """encoder_forward and encoder_forward_u8 after their input checks"""
         if h % 16 or w % 16:
             raise RuntimeError('ffrnet_amd: H and W must be multiples of 16, got %dx%d' % (h, w))
         if want_f and (h, w) != (112, 112):
             # same failure as the reference: Linear(512*7*7, 512), model_ir_se50.py:124
             raise RuntimeError('mat1 and mat2 shapes cannot be multiplied (%dx%d and 25088x512)'
                                % (n, 512 * (h // 16) * (w // 16)))
-        fm = torch.empty((n, 512, h // 16, w // 16), device=x.device, dtype=torch.float32) \
-            if want_featmap else None
-        f = torch.empty((n, 512), device=x.device, dtype=torch.float32) if want_f else None
-        with torch.cuda.device(self.device):
-            self._ck(self.lib.ffr_encoder_forward(self._h, _ptr(x), n, h, w, _ptr(fm), _ptr(f),
-                                                  self._stream()))
+        fm = self._empty(n, 512, h // 16, w // 16) if want_featmap else None
+        f = self._empty(n, 512) if want_f else None
+        self._call(fn, *[_ptr(t) for t in inputs], n, h, w, _ptr(fm), _ptr(f))
         return fm, f
+
+    def encoder_forward(self, x, want_f=True, want_featmap=True):
+        self._tensor(x, 'x')
+        if x.dim() != 4 or x.size(1) != 3:
+            raise RuntimeError('ffrnet_amd: encoder input must be [N,3,H,W], got %s' % list(x.shape))
+        n, _, h, w = x.shape
+        return self._encoder_forward(self.lib.ffr_encoder_forward, (x.contiguous(),), n, h, w, want_f, want_featmap)
 
     def encoder_forward_u8(self, img, flip=None, want_f=True, want_featmap=True):
         """encoder_forward from decoded images: img[N,H,W,3] uint8 HWC RGB (device), flip: optional bool / uint8 [N]
         per-image h-flip flags.  The input step (BGR swap, flip, ToTensor, Normalize(0.5, 0.5)) runs in the stem
         -> (featmap[N,512,H/16,W/16], f[N,512]), bit-identical to encoder_forward(O.preprocess_u8(img, flip))."""
-        _check_u8(img, 'img', self.device)
-        img = img.contiguous()
+        self._tensor(img, 'img', torch.uint8, ('N', 'H', 'W', 3), _U8_HINT)
         n, h, w, _ = img.shape
-        if h % 16 or w % 16:
-            raise RuntimeError('ffrnet_amd: H and W must be multiples of 16, got %dx%d' % (h, w))
-        if want_f and (h, w) != (112, 112):
-            raise RuntimeError('mat1 and mat2 shapes cannot be multiplied (%dx%d and 25088x512)'
-                               % (n, 512 * (h // 16) * (w // 16)))
-        fl = _flip_flags(flip, n, self.device)
-        fm = torch.empty((n, 512, h // 16, w // 16), device=img.device, dtype=torch.float32) \
-            if want_featmap else None
-        f = torch.empty((n, 512), device=img.device, dtype=torch.float32) if want_f else None
-        with torch.cuda.device(self.device):
-            self._ck(self.lib.ffr_encoder_forward_u8(self._h, _ptr(img), _ptr(fl), n, h, w, _ptr(fm), _ptr(f),
-                                                     self._stream()))
-        return fm, f
+        return self._encoder_forward(self.lib.ffr_encoder_forward_u8, (img.contiguous(), self._flags(flip, n)), n, h, w,
+                                     want_f, want_featmap)
 
     def recnet_forward(self, featmap, want_feat_new=True):
-        _check_dev(featmap, 'input', device=self.device)
+        self._tensor(featmap, 'input')
         if featmap.dim() != 4 or tuple(featmap.shape[1:]) != (512, 7, 7):
             c = featmap.size(1) + featmap.size(2) * featmap.size(3) if featmap.dim() == 4 else -1
             # the reference fails in Conv4Space's first conv (models/recnet.py:363)
@@ -346,97 +360,72 @@ class Engine(object):
                                % (list(featmap.shape), c))
         featmap = featmap.contiguous()
         n = featmap.size(0)
-        f_new = torch.empty((n, 512), device=featmap.device, dtype=torch.float32)
-        feat_new = torch.empty((n, 512, 7, 7), device=featmap.device, dtype=torch.float32) \
-            if want_feat_new else None
-        with torch.cuda.device(self.device):
-            self._ck(self.lib.ffr_recnet_forward(self._h, _ptr(featmap), n, _ptr(f_new),
-                                                 _ptr(feat_new), self._stream()))
+        f_new = self._empty(n, 512)
+        feat_new = self._empty(n, 512, 7, 7) if want_feat_new else None
+        self._call(self.lib.ffr_recnet_forward, _ptr(featmap), n, _ptr(f_new), _ptr(feat_new))
         return f_new, feat_new
 
     def embed(self, x, want_f=True, out=None):
         """x[N,3,112,112] -> (f_new[N,512], f[N,512]); `out` = preallocated (f_new, f)."""
-        _check_dev(x, 'x', (3, 112, 112), device=self.device)
+        self._tensor(x, 'x', shape=('N', 3, 112, 112))
         x = x.contiguous()
         n = x.size(0)
-        if out is not None:
-            f_new, f = out
-            for o, nm in ((f_new, 'out[0]'), (f, 'out[1]')):
-                if o is None:
-                    continue
-                _check_dev(o, nm, device=self.device)
-                if tuple(o.shape) != (n, 512) or not o.is_contiguous():
-                    raise RuntimeError('ffrnet_amd: %s must be a contiguous [%d,512] tensor, got %s' % (nm, n, list(o.shape)))
-        else:
-            f_new = torch.empty((n, 512), device=x.device, dtype=torch.float32)
-            f = torch.empty((n, 512), device=x.device, dtype=torch.float32) if want_f else None
-        with torch.cuda.device(self.device):
-            self._ck(self.lib.ffr_embed(self._h, _ptr(x), n, _ptr(f_new), _ptr(f), self._stream()))
+        f_new, f = self._embed_outputs(n, want_f, out)
+        self._call(self.lib.ffr_embed, _ptr(x), n, _ptr(f_new), _ptr(f))
         return f_new, f
 
     def embed_u8(self, img, flip=None, want_f=True):
-        """img[N,112,112,3] uint8 RGB (device) -> (f_new, f); flip: optional uint8[N] h-flip flags."""
-        if not (torch.is_tensor(img) and img.is_cuda and img.dtype == torch.uint8):
-            raise RuntimeError('ffrnet_amd: embed_u8 needs a uint8 ROCm device tensor [N,112,112,3]')
-        if img.device.index != self.device.index:
-            raise RuntimeError('ffrnet_amd: img is on %s but this Engine lives on %s' % (img.device, self.device))
-        if img.dim() != 4 or tuple(img.shape[1:]) != (112, 112, 3):
-            raise RuntimeError('ffrnet_amd: embed_u8 expects [N,112,112,3] (HWC, RGB), got %s' % list(img.shape))
+        """img[N,112,112,3] uint8 RGB (device) -> (f_new, f); flip: optional bool / uint8 [N] h-flip flags."""
+        self._tensor(img, 'img', torch.uint8, ('N', 112, 112, 3), _U8_HINT)
         img = img.contiguous()
         n = img.size(0)
-        fl = flip.to(device=img.device, dtype=torch.uint8).contiguous() if flip is not None else None
-        f_new = torch.empty((n, 512), device=img.device, dtype=torch.float32)
-        f = torch.empty((n, 512), device=img.device, dtype=torch.float32) if want_f else None
-        with torch.cuda.device(self.device):
-            self._ck(self.lib.ffr_embed_u8(self._h, _ptr(img), _ptr(fl), n, _ptr(f_new), _ptr(f), self._stream()))
+        fl = self._flags(flip, n)
+        f_new, f = self._embed_outputs(n, want_f)
+        self._call(self.lib.ffr_embed_u8, _ptr(img), _ptr(fl), n, _ptr(f_new), _ptr(f))
         return f_new, f
 
     def cosine_scores(self, a, b):
-        _check_dev(a, 'a', device=self.device)
-        _check_dev(b, 'b', device=self.device)
+        self._tensor(a, 'a')
+        self._tensor(b, 'b')
         if a.shape != b.shape or a.dim() != 2:
             raise RuntimeError('cosine_scores: a and b must both be [n,dim]')
         a, b = a.contiguous(), b.contiguous()
-        s = torch.empty((a.size(0),), device=a.device, dtype=torch.float32)
-        with torch.cuda.device(self.device):
-            self._ck(self.lib.ffr_cosine_scores(self._h, _ptr(a), _ptr(b), a.size(0), a.size(1),
-                                                _ptr(s), self._stream()))
+        s = self._empty(a.size(0))
+        self._call(self.lib.ffr_cosine_scores, _ptr(a), _ptr(b), a.size(0), a.size(1), _ptr(s))
         return s
 
     def lfw_fold_accuracy(self, scores, labels, n_folds=10):
         """Device fold protocol: scores[n] fp32, labels[n] -> (mean accuracy, [(best_thr, acc)] per fold).
         The mean divides by n_folds (the reference hard-codes 10 = its n_folds)."""
-        _check_dev(scores, 'scores', device=self.device)
+        self._tensor(scores, 'scores')
         scores = scores.contiguous()
-        lab = labels.to(device=scores.device, dtype=torch.int32).contiguous()
-        thr = torch.empty(n_folds, device=scores.device, dtype=torch.float64)
-        acc = torch.empty(n_folds, device=scores.device, dtype=torch.float64)
-        with torch.cuda.device(self.device):
-            self._ck(self.lib.ffr_lfw_fold_accuracy(self._h, _ptr(scores), _ptr(lab), scores.numel(), n_folds,
-                                                    _ptr(thr), _ptr(acc), self._stream()))
+        if not torch.is_tensor(labels) or labels.numel() != scores.numel():      # the native call takes one n for both
+            raise RuntimeError('ffrnet_amd: lfw_fold_accuracy needs one label per score: %d scores, %s labels'
+                               % (scores.numel(), labels.numel() if torch.is_tensor(labels) else type(labels)))
+        lab = labels.reshape(-1).to(device=self.device, dtype=torch.int32).contiguous()
+        thr, acc = self._empty(n_folds, dtype=torch.float64), self._empty(n_folds, dtype=torch.float64)
+        self._call(self.lib.ffr_lfw_fold_accuracy, _ptr(scores), _ptr(lab), scores.numel(), n_folds, _ptr(thr), _ptr(acc))
         thr, acc = thr.cpu().tolist(), acc.cpu().tolist()
         return sum(acc) / n_folds, list(zip(thr, acc))
 
     # -- 1:N identification (include/ffrnet.h: ffr_row_norms, ffr_search_topk, ffr_topk_merge) -------------------------
     def row_norms(self, x):
         """|x[r]| of x[n,512] rows (device fp32), the norms the search divides by -> norms[n]."""
-        _check_dev(x, 'x', device=self.device)
+        self._tensor(x, 'x')
         if x.dim() != 2:
             raise RuntimeError('ffrnet_amd: row_norms expects [n,dim], got %s' % list(x.shape))
         x = x.contiguous()
-        out = torch.empty((x.size(0),), device=x.device, dtype=torch.float32)
-        if x.size(0) == 0:
-            return out
-        with torch.cuda.device(self.device):
-            self._ck(self.lib.ffr_row_norms(self._h, _ptr(x), x.size(0), x.size(1), _ptr(out), self._stream()))
+        out = self._empty(x.size(0))
+        if x.size(0):
+            self._call(self.lib.ffr_row_norms, _ptr(x), x.size(0), x.size(1), _ptr(out))
         return out
 
     def search(self, query, gallery, k, gallery_norms=None, index_base=0):
         """Exact cosine top-k: query[Q,512], gallery[G,512] (device fp32) -> (scores[Q,k] fp32, index[Q,k] int64), per
         probe by descending score, ties by ascending index; index = index_base + gallery row; (-inf, -1) pads G < k.
         gallery_norms[G]: row_norms(gallery), computed here when not given (pass them when the gallery is reused)."""
-        _check_dev(query, 'query', device=self.device)
-        _check_dev(gallery, 'gallery', device=self.device)
+        self._tensor(query, 'query')
+        self._tensor(gallery, 'gallery')
         if query.dim() != 2 or gallery.dim() != 2 or query.size(1) != gallery.size(1):
             raise RuntimeError('ffrnet_amd: search expects query [Q,dim] and gallery [G,dim], got %s and %s'
                                % (list(query.shape), list(gallery.shape)))
@@ -445,57 +434,45 @@ class Engine(object):
         if gallery_norms is None:
             gallery_norms = self.row_norms(gallery) if G else None
         else:
-            _check_dev(gallery_norms, 'gallery_norms', device=self.device)
+            self._tensor(gallery_norms, 'gallery_norms')
             if tuple(gallery_norms.shape) != (G,):
                 raise RuntimeError('ffrnet_amd: gallery_norms must be [%d], got %s' % (G, list(gallery_norms.shape)))
             gallery_norms = gallery_norms.contiguous()
         Q, k = query.size(0), int(k)
-        scores = torch.empty((Q, max(k, 0)), device=query.device, dtype=torch.float32)
-        index = torch.empty((Q, max(k, 0)), device=query.device, dtype=torch.int64)
-        with torch.cuda.device(self.device):
-            self._ck(self.lib.ffr_search_topk(self._h, _ptr(query), Q, _ptr(gallery if G else None), _ptr(gallery_norms),
-                                              G, query.size(1), k, int(index_base), _ptr(scores), _ptr(index),
-                                              self._stream()))
+        scores, index = self._empty(Q, max(k, 0)), self._empty(Q, max(k, 0), dtype=torch.int64)
+        self._call(self.lib.ffr_search_topk, _ptr(query), Q, _ptr(gallery if G else None), _ptr(gallery_norms), G,
+                   query.size(1), k, int(index_base), _ptr(scores), _ptr(index))
         return scores, index
 
     def topk_merge(self, scores, index):
         """Merge S sorted lists per probe, scores[S,Q,k] fp32 and index[S,Q,k] int64 (device; index < 0 = padding), in
         the order of search() -> (scores[Q,k], index[Q,k])."""
-        _check_dev(scores, 'scores', device=self.device)
-        if not isinstance(index, torch.Tensor) or not index.is_cuda or index.device.index != self.device.index:
-            raise RuntimeError('ffrnet_amd: index must be a tensor on %s' % self.device)
-        if index.dtype != torch.int64:
-            raise RuntimeError('ffrnet_amd: index must be int64, got %s' % index.dtype)
+        self._tensor(scores, 'scores')
+        self._tensor(index, 'index', torch.int64)
         if scores.dim() != 3 or tuple(index.shape) != tuple(scores.shape):
             raise RuntimeError('ffrnet_amd: topk_merge expects scores and index [S,Q,k], got %s and %s'
                                % (list(scores.shape), list(index.shape)))
         S, Q, k = scores.shape
         scores, index = scores.contiguous(), index.contiguous()
-        out_s = torch.empty((Q, k), device=scores.device, dtype=torch.float32)
-        out_i = torch.empty((Q, k), device=scores.device, dtype=torch.int64)
-        with torch.cuda.device(self.device):
-            self._ck(self.lib.ffr_topk_merge(self._h, _ptr(scores), _ptr(index), S, Q, k, _ptr(out_s), _ptr(out_i),
-                                             self._stream()))
+        out_s, out_i = self._empty(Q, k), self._empty(Q, k, dtype=torch.int64)
+        self._call(self.lib.ffr_topk_merge, _ptr(scores), _ptr(index), S, Q, k, _ptr(out_s), _ptr(out_i))
         return out_s, out_i
 
     # -- clustering (include/ffrnet.h: ffr_cluster_threshold, ffr_cluster_templates) -----------------------------------
     def _cluster_rows(self, emb, norms, who):
-        _check_dev(emb, 'emb', device=self.device)
+        self._tensor(emb, 'emb')
         if emb.dim() != 2:
             raise RuntimeError('ffrnet_amd: %s expects emb [N,dim], got %s' % (who, list(emb.shape)))
         emb = emb.contiguous()
         if norms is not None:
-            _check_dev(norms, 'norms', device=self.device)
+            self._tensor(norms, 'norms')
             if tuple(norms.shape) != (emb.size(0),):
                 raise RuntimeError('ffrnet_amd: norms must be [%d], got %s' % (emb.size(0), list(norms.shape)))
             norms = norms.contiguous()
         return emb, norms
 
     def _index_tensor(self, t, name):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device.index != self.device.index:
-            raise RuntimeError('ffrnet_amd: %s must be a tensor on %s' % (name, self.device))
-        if t.dtype != torch.int64 or t.dim() != 1:
-            raise RuntimeError('ffrnet_amd: %s must be a 1-d int64 tensor, got %s %s' % (name, t.dtype, list(t.shape)))
+        self._tensor(t, name, torch.int64, ('N',))
         return t.contiguous()
 
     def cluster(self, emb, threshold, norms=None):
@@ -504,10 +481,9 @@ class Engine(object):
         row_norms(emb), computed in the call when not given."""
         emb, norms = self._cluster_rows(emb, norms, 'cluster')
         N = emb.size(0)
-        rep = torch.empty((N,), device=emb.device, dtype=torch.int64)
-        with torch.cuda.device(self.device):
-            self._ck(self.lib.ffr_cluster_threshold(self._h, _ptr(emb if N else None), _ptr(norms), N, emb.size(1),
-                                                    float(threshold), _ptr(rep), self._stream()))
+        rep = self._empty(N, dtype=torch.int64)
+        self._call(self.lib.ffr_cluster_threshold, _ptr(emb if N else None), _ptr(norms), N, emb.size(1), float(threshold),
+                   _ptr(rep))
         return rep
 
     def cluster_extend(self, emb, threshold, prior, n_old, norms=None, validate=True, out=None):
@@ -530,15 +506,13 @@ class Engine(object):
             if bool(((prior < 0) | (prior > row)).any().item()):
                 raise RuntimeError('ffrnet_amd: cluster_extend needs 0 <= prior[i] <= i (and so < %d)' % N)
         if out is None:
-            rep = torch.empty((N,), device=emb.device, dtype=torch.int64)
+            rep = self._empty(N, dtype=torch.int64)
         else:
             rep = self._index_tensor(out, 'out')
             if rep.numel() != N or rep.data_ptr() != out.data_ptr():
                 raise RuntimeError('ffrnet_amd: out must be a contiguous [%d] int64 tensor' % N)
-        with torch.cuda.device(self.device):
-            self._ck(self.lib.ffr_cluster_extend(self._h, _ptr(emb if N else None), _ptr(norms), n_old, N, emb.size(1),
-                                                 float(threshold), _ptr(prior if N else None), _ptr(rep if N else None),
-                                                 self._stream()))
+        self._call(self.lib.ffr_cluster_extend, _ptr(emb if N else None), _ptr(norms), n_old, N, emb.size(1),
+                   float(threshold), _ptr(prior if N else None), _ptr(rep if N else None))
         return rep
 
     def cluster_templates(self, emb, order, offsets, norms=None, validate=True):
@@ -558,10 +532,9 @@ class Engine(object):
             if bad:
                 raise RuntimeError('ffrnet_amd: cluster_templates needs 0 <= order < %d and ascending offsets within '
                                    '[0, %d]' % (emb.size(0), order.numel()))
-        out = torch.empty((Cn, emb.size(1)), device=emb.device, dtype=torch.float32)
-        with torch.cuda.device(self.device):
-            self._ck(self.lib.ffr_cluster_templates(self._h, _ptr(emb if emb.size(0) else None), _ptr(norms), _ptr(order),
-                                                    _ptr(offsets), Cn, emb.size(1), _ptr(out), self._stream()))
+        out = self._empty(Cn, emb.size(1))
+        self._call(self.lib.ffr_cluster_templates, _ptr(emb if emb.size(0) else None), _ptr(norms), _ptr(order),
+                   _ptr(offsets), Cn, emb.size(1), _ptr(out))
         return out
 
     # -- face alignment (include/ffrnet.h: ffr_align_transforms, ffr_align_warp, ffr_embed_aligned) -------------------
@@ -570,12 +543,12 @@ class Engine(object):
         tmpl = _align.as_template(template)
         K = tmpl.size(0)
         N = _align.check_landmarks(landmarks, K)
-        _check_dev(landmarks, 'landmarks', device=self.device)
+        self._tensor(landmarks, 'landmarks')
         return landmarks.contiguous(), tmpl.to(self.device), N, K
 
     def _align_frames(self, frames, frame_index, N):
         """frames [F,H,W,3] uint8 (rows may be padded) and frame_index [N] -> (frames, pitch_bytes, int32 frame_index)"""
-        _check_u8(frames, 'frames', self.device)
+        self._tensor(frames, 'frames', torch.uint8, ('F', 'H', 'W', 3), _U8_HINT)
         if frames.size(0) < 1 or frames.size(1) < 1 or frames.size(2) < 1:
             raise RuntimeError('ffrnet_amd: frames must not be empty, got %s' % list(frames.shape))
         pitch = _align.frame_pitch(frames)
@@ -596,11 +569,8 @@ class Engine(object):
         (A float64 [N,6], valid uint8 [N]): the row-major 2x3 similarity crop -> frame of the reference's cp2tform fit,
         valid = 0 (and A = 0) for degenerate or non-finite landmarks."""
         landmarks, tmpl, N, K = self._align_points(landmarks, template)
-        A = torch.empty((N, 6), device=self.device, dtype=torch.float64)
-        valid = torch.empty((N,), device=self.device, dtype=torch.uint8)
-        with torch.cuda.device(self.device):
-            self._ck(self.lib.ffr_align_transforms(self._h, _ptr(landmarks), _ptr(tmpl), N, K, _ptr(A), _ptr(valid),
-                                                   self._stream()))
+        A, valid = self._empty(N, 6, dtype=torch.float64), self._empty(N, dtype=torch.uint8)
+        self._call(self.lib.ffr_align_transforms, _ptr(landmarks), _ptr(tmpl), N, K, _ptr(A), _ptr(valid))
         return A, valid
 
     def align_warp(self, frames, frame_index, A, valid=None, out_hw=(112, 112)):
@@ -608,18 +578,15 @@ class Engine(object):
         float64 -> crops uint8 [N,h,w,3] by the exact 1/32-pixel bilinear rule of include/ffrnet.h; zeros where
         valid[n] == 0 or frame_index[n] is outside [0,F)."""
         oh, ow = _align.check_out_hw(out_hw)
-        if not isinstance(A, torch.Tensor) or not A.is_cuda or A.device.index != self.device.index:
-            raise RuntimeError('ffrnet_amd: A must be a tensor on %s' % self.device)
-        if A.dtype != torch.float64 or A.dim() != 2 or A.size(1) != 6 or A.size(0) < 1:
-            raise RuntimeError('ffrnet_amd: A must be float64 [N,6] with N >= 1, got %s %s' % (A.dtype, list(A.shape)))
+        self._tensor(A, 'A', torch.float64, ('N', 6))
         N = A.size(0)
+        if N < 1:
+            raise RuntimeError('ffrnet_amd: A must be float64 [N,6] with N >= 1, got %s' % list(A.shape))
         frames, pitch, fidx = self._align_frames(frames, frame_index, N)
-        v = _flip_flags(valid, N, self.device, 'valid')
-        crop = torch.empty((N, oh, ow, 3), device=self.device, dtype=torch.uint8)
-        with torch.cuda.device(self.device):
-            self._ck(self.lib.ffr_align_warp(self._h, _ptr(frames), frames.size(0), frames.size(1), frames.size(2), pitch,
-                                             _ptr(fidx), _ptr(A.contiguous()), _ptr(v), N, oh, ow, _ptr(crop),
-                                             self._stream()))
+        v = self._flags(valid, N, 'valid')
+        crop = self._empty(N, oh, ow, 3, dtype=torch.uint8)
+        self._call(self.lib.ffr_align_warp, _ptr(frames), frames.size(0), frames.size(1), frames.size(2), pitch, _ptr(fidx),
+                   _ptr(A.contiguous()), _ptr(v), N, oh, ow, _ptr(crop))
         return crop
 
     def align_crops(self, frames, frame_index, landmarks, template=_align.TEMPLATE_112x112, out_hw=(112, 112)):
@@ -634,14 +601,11 @@ class Engine(object):
         the embedding of a zero crop, to be dropped."""
         landmarks, tmpl, N, K = self._align_points(landmarks, template)
         frames, pitch, fidx = self._align_frames(frames, frame_index, N)
-        fl = _flip_flags(flip, N, self.device)
-        f_new = torch.empty((N, 512), device=self.device, dtype=torch.float32)
-        f = torch.empty((N, 512), device=self.device, dtype=torch.float32) if want_f else None
-        valid = torch.empty((N,), device=self.device, dtype=torch.uint8)
-        with torch.cuda.device(self.device):
-            self._ck(self.lib.ffr_embed_aligned(self._h, _ptr(frames), frames.size(0), frames.size(1), frames.size(2), pitch,
-                                                _ptr(fidx), _ptr(landmarks), _ptr(tmpl), K, _ptr(fl), N, _ptr(f_new),
-                                                _ptr(f), _ptr(valid), self._stream()))
+        fl = self._flags(flip, N)
+        f_new, f = self._embed_outputs(N, want_f)
+        valid = self._empty(N, dtype=torch.uint8)
+        self._call(self.lib.ffr_embed_aligned, _ptr(frames), frames.size(0), frames.size(1), frames.size(2), pitch, _ptr(fidx),
+                   _ptr(landmarks), _ptr(tmpl), K, _ptr(fl), N, _ptr(f_new), _ptr(f), _ptr(valid))
         return f_new, f, valid
 
     # -- arena / measurement --------------------------------------------------
@@ -649,13 +613,11 @@ class Engine(object):
         return int(self.lib.ffr_workspace_bytes(self._h, n, h, w))
 
     def reserve(self, n, h=112, w=112):
-        with torch.cuda.device(self.device):
-            self._ck(self.lib.ffr_reserve(self._h, n, h, w))
+        self._call(self.lib.ffr_reserve, n, h, w, stream=False)
 
     def set_option(self, name, value):
         """Experiment knob of this handle (include/ffrnet.h: ffr_set_option); the library reads no environment."""
-        with torch.cuda.device(self.device):
-            self._ck(self.lib.ffr_set_option(self._h, name.encode(), int(value)))
+        self._call(self.lib.ffr_set_option, name.encode(), int(value), stream=False)
 
     def get_option(self, name):
         v = C.c_longlong(0)
@@ -702,9 +664,8 @@ class Engine(object):
 
     def set_layer_arith(self, name_or_index, arith):
         """Pin one layer to 'direct' or return it to 'winograd'.  Changes generation() (captured graphs re-capture)."""
-        if arith not in ARITH:
-            raise ValueError("ffrnet_amd: arith must be 'direct' or 'winograd', got %r" % (arith,))
-        self._ck(self.lib.ffr_layer_set_arith(self._h, self._layer_index(name_or_index), ARITH[arith]))
+        code = _arith_code(arith)
+        self._ck(self.lib.ffr_layer_set_arith(self._h, self._layer_index(name_or_index), code))
 
     def arithmetic_plan(self, net=None):
         """{layer name: 'direct' | 'winograd'} of the loaded nets (or of one net: 'encoder' | 'recnet')."""
@@ -717,8 +678,7 @@ class Engine(object):
         for name, arith in plan.items():
             if name not in known:
                 raise KeyError('ffrnet_amd: no Winograd-eligible layer named %r' % (name,))
-            if arith not in ARITH:
-                raise ValueError("ffrnet_amd: arith must be 'direct' or 'winograd', got %r" % (arith,))
+            _arith_code(arith)
         for name, l in known.items():
             if net is None or l['net'] == net:
                 want = plan.get(name, 'winograd')
@@ -732,10 +692,9 @@ class Engine(object):
         {f, featmap, f_new, feat_new: value or None where the forward has no such output}}.  Calibrate at the batch size
         you will run: the Winograd kernels depend on it."""
         if (x is None) == (featmap is None):
-            with torch.cuda.device(self.device):
-                self._ck(self.lib.ffr_calibrate(self._h, _ptr(x), _ptr(featmap), 1, 112, 112, float(tol), None, self._stream()))
+            self._call(self.lib.ffr_calibrate, _ptr(x), _ptr(featmap), 1, 112, 112, float(tol), None)      # raises
         t = x if x is not None else featmap
-        _check_dev(t, 'x' if x is not None else 'featmap', device=self.device)
+        self._tensor(t, 'x' if x is not None else 'featmap')
         t = t.contiguous()
         if x is not None and (t.dim() != 4 or t.size(1) != 3):
             raise RuntimeError('ffrnet_amd: calibration images must be [N,3,H,W], got %s' % list(t.shape))
@@ -743,9 +702,8 @@ class Engine(object):
             raise RuntimeError('ffrnet_amd: a calibration featmap must be [N,512,7,7], got %s' % list(t.shape))
         n, _, h, w = t.shape
         ach = (C.c_double * 4)()
-        with torch.cuda.device(self.device):
-            self._ck(self.lib.ffr_calibrate(self._h, _ptr(x if x is None else t), _ptr(featmap if featmap is None else t),
-                                            n, h, w, float(tol), ach, self._stream()))
+        self._call(self.lib.ffr_calibrate, _ptr(x if x is None else t), _ptr(featmap if featmap is None else t), n, h, w,
+                   float(tol), ach)
         return dict(tol=float(tol), n=int(n),
                     layers=[dict(name=l['name'], net=l['net'], sensitivity=l['sensitivity'], arith=l['arith']) for l in self.layers()],
                     achieved={k: (ach[i] if ach[i] >= 0 else None) for i, k in enumerate(CALIB_TENSORS)})
@@ -759,8 +717,7 @@ class Engine(object):
     def probe_mfma_peak(self, iters=20000):
         """(TFLOP/s, shader clock in GHz) of a register-resident fp32-MFMA loop on this device."""
         tf, ghz = C.c_double(0), C.c_double(0)
-        with torch.cuda.device(self.device):
-            self._ck(self.lib.ffr_probe_mfma_peak(self._h, iters, C.byref(tf), C.byref(ghz), self._stream()))
+        self._call(self.lib.ffr_probe_mfma_peak, iters, C.byref(tf), C.byref(ghz))
         return tf.value, ghz.value
 
     def profile_enable(self, on=True):
@@ -783,25 +740,19 @@ class Engine(object):
             elif v is None:
                 v = 0 if k not in ('x', 'w', 'bias', 'slope', 'resid', 'out') else None
             setattr(d, k, v)
-        with torch.cuda.device(self.device):
-            self._ck(self.lib.ffr_op_conv(self._h, C.byref(d), self._stream()))
+        self._call(self.lib.ffr_op_conv, C.byref(d))
 
     def op_conv3x3(self, x_nhwc, w, bias, slope=None, pad_mode=0, use_wino=True, resid=None):
         """x[N,H,W,cin] device NHWC, w[cout,cin,3,3] / bias / slope host tensors -> out[N,H,W,cout]."""
-        _check_dev(x_nhwc, 'x', device=self.device)
+        self._tensor(x_nhwc, 'x')
         x_nhwc = x_nhwc.contiguous()
         n, hh, ww, cin = x_nhwc.shape
         wh = w.detach().float().cpu().contiguous()
         bh = bias.detach().float().cpu().contiguous()
         sh = slope.detach().float().cpu().contiguous() if slope is not None else None
-        out = torch.empty((n, hh, ww, wh.size(0)), device=x_nhwc.device, dtype=torch.float32)
-        with torch.cuda.device(self.device):
-            self._ck(self.lib.ffr_op_conv3x3(self._h, _ptr(x_nhwc), n, hh, ww, cin, C.c_void_p(wh.data_ptr()),
-                                             C.c_void_p(bh.data_ptr()),
-                                             C.c_void_p(sh.data_ptr()) if sh is not None else C.c_void_p(0),
-                                             wh.size(0), pad_mode, int(use_wino),
-                                             _ptr(resid.contiguous()) if resid is not None else C.c_void_p(0),
-                                             _ptr(out), self._stream()))
+        out = self._empty(n, hh, ww, wh.size(0))
+        self._call(self.lib.ffr_op_conv3x3, _ptr(x_nhwc), n, hh, ww, cin, _ptr(wh), _ptr(bh), _ptr(sh), wh.size(0), pad_mode,
+                   int(use_wino), _ptr(resid.contiguous() if resid is not None else None), _ptr(out))
         return out
 
     def op_convlayer_train(self, x_nhwc, G, w, gamma, beta, slope, da_nhwc, need_dx=True):
@@ -809,7 +760,7 @@ class Engine(object):
         x_nhwc [G*N,7,7,cin] and da_nhwc [G*N,7,7,cout] device tensors (logical channel counts);
         w [cout,cin,3,3], gamma/beta/slope [cout] host tensors.
         Returns dict(out, dx, dw[cout,cin,3,3], dgamma, dbeta, dslope, running_mean, running_var, mean, invstd)."""
-        _check_dev(x_nhwc, 'x', device=self.device)
+        self._tensor(x_nhwc, 'x')
         gn, hh, ww, cin = x_nhwc.shape
         assert hh == 7 and ww == 7 and gn % G == 0
         cout = w.size(0)
@@ -826,10 +777,8 @@ class Engine(object):
         dw = torch.empty((cout_pad, 9, cin_pad), device=dev)
         dvec = torch.empty((5, cout_pad), device=dev)
         stats = torch.empty((2, G, cout_pad), device=dev)
-        with torch.cuda.device(self.device):
-            self._ck(self.lib.ffr_op_convlayer_train(self._h, _ptr(xp), G, gn // G, cin, cout,
-                                                     *[C.c_void_p(t.data_ptr()) for t in host], _ptr(dap), _ptr(out),
-                                                     _ptr(dx), _ptr(dw), _ptr(dvec), _ptr(stats), self._stream()))
+        self._call(self.lib.ffr_op_convlayer_train, _ptr(xp), G, gn // G, cin, cout, *[_ptr(t) for t in host], _ptr(dap),
+                   _ptr(out), _ptr(dx), _ptr(dw), _ptr(dvec), _ptr(stats))
         dwt = dw[:cout, :, :cin].reshape(cout, 3, 3, cin).permute(0, 3, 1, 2).contiguous()
         return dict(out=out[:, :cout].reshape(gn, 7, 7, cout), dx=dx[:, :cin].reshape(gn, 7, 7, cin) if need_dx else None,
                     dw=dwt, dgamma=dvec[0, :cout], dbeta=dvec[1, :cout], dslope=dvec[2, :cout],
@@ -838,6 +787,7 @@ class Engine(object):
 
     # -- RecNet training step (include/ffrnet_train.h) --------------------------------------------
     N_CLASSES = 10575
+    _WHICH = {'param': 0, 'grad': 1, 'exp_avg': 2, 'exp_avg_sq': 3, 'running': 4}
     validate_labels = True     # range check of class ids (the reference fails loudly in scatter_ / CrossEntropyLoss)
 
     def _labels(self, label, n, device):
@@ -868,15 +818,13 @@ class Engine(object):
 
     def train_get(self, key, which='param'):
         """One tensor in torch layout on the host; which: param | grad | exp_avg | exp_avg_sq | running."""
-        code = {'param': 0, 'grad': 1, 'exp_avg': 2, 'exp_avg_sq': 3, 'running': 4}[which]
         out = torch.empty(self._train_spec[key], dtype=torch.float32)
-        self._ck(self.lib.ffr_train_get(self._h, code, key.encode(), C.c_void_p(out.data_ptr()), out.numel()))
+        self._ck(self.lib.ffr_train_get(self._h, self._WHICH[which], key.encode(), C.c_void_p(out.data_ptr()), out.numel()))
         return out
 
     def train_set(self, key, value, which='param'):
-        code = {'param': 0, 'grad': 1, 'exp_avg': 2, 'exp_avg_sq': 3}[which]
         v = value.detach().to('cpu', torch.float32).contiguous()
-        self._ck(self.lib.ffr_train_set(self._h, code, key.encode(), C.c_void_p(v.data_ptr()), v.numel()))
+        self._ck(self.lib.ffr_train_set(self._h, self._WHICH[which], key.encode(), C.c_void_p(v.data_ptr()), v.numel()))
 
     def train_state_dict(self):
         """The RecNet state_dict as the reference would save it (models/trainer.py:216-224)."""
@@ -892,27 +840,23 @@ class Engine(object):
         return sd
 
     def train_zero_grad(self):
-        with torch.cuda.device(self.device):
-            self._ck(self.lib.ffr_train_zero_grad(self._h, self._stream()))
+        self._call(self.lib.ffr_train_zero_grad)
 
     def train_forward(self, featmap, label, groups=1, slot=0, want=('f_new', 'pred_loss', 'pred_label', 'M_space',
                                                                       'M_channel', 'feat_space', 'feat_channel')):
         """RecNet.forward(input, label) in train() mode on `groups` BatchNorm batches stacked along dim 0.
         Returns the reference's 7-tuple (entries not in `want` are None)."""
-        _check_dev(featmap, 'featmap', device=self.device)
+        self._tensor(featmap, 'featmap')
         featmap = featmap.contiguous()
         n = featmap.size(0)
         if featmap.dim() != 4 or tuple(featmap.shape[1:]) != (512, 7, 7) or n % groups:
             raise RuntimeError('ffrnet_amd: RecNet input must be [G*N,512,7,7], got %s' % list(featmap.shape))
         lab = self._labels(label, n, featmap.device)
-        dev = featmap.device
         shapes = dict(f_new=(n, 512), pred_loss=(n, self.N_CLASSES), pred_label=(n, self.N_CLASSES), M_space=(n, 49, 49),
                       M_channel=(n, 512, 512), feat_space=(n, 512, 7, 7), feat_channel=(n, 512, 7, 7))
         names = ('f_new', 'pred_loss', 'pred_label', 'M_space', 'M_channel', 'feat_space', 'feat_channel')
-        outs = [torch.empty(shapes[k], device=dev, dtype=torch.float32) if k in want else None for k in names]
-        with torch.cuda.device(self.device):
-            self._ck(self.lib.ffr_train_forward(self._h, slot, _ptr(featmap), _ptr(lab), groups, n // groups,
-                                                *[_ptr(o) for o in outs], self._stream()))
+        outs = [self._empty(*shapes[k]) if k in want else None for k in names]
+        self._call(self.lib.ffr_train_forward, slot, _ptr(featmap), _ptr(lab), groups, n // groups, *[_ptr(o) for o in outs])
         return tuple(outs)
 
     def train_backward(self, grads, slot=0):
@@ -920,70 +864,58 @@ class Engine(object):
         gs = [g.contiguous().float() if g is not None else None for g in grads]
         for g in gs:
             if g is not None:
-                _check_dev(g, 'grad', device=self.device)
-        with torch.cuda.device(self.device):
-            self._ck(self.lib.ffr_train_backward(self._h, slot, *[_ptr(g) for g in gs], self._stream()))
-
-    _WHICH = {'param': 0, 'grad': 1, 'exp_avg': 2, 'exp_avg_sq': 3, 'running': 4}
+                self._tensor(g, 'grad')
+        self._call(self.lib.ffr_train_backward, slot, *[_ptr(g) for g in gs])
 
     def train_export(self, key, out, which='grad'):
         """One entry in torch layout into the device tensor `out` (no host round trip)."""
-        _check_dev(out, 'out', device=self.device)
-        assert out.is_contiguous() and out.dtype == torch.float32
-        with torch.cuda.device(self.device):
-            self._ck(self.lib.ffr_train_export(self._h, self._WHICH[which], key.encode(), _ptr(out), self._stream()))
+        self._tensor(out, 'out')
+        assert out.is_contiguous()
+        self._call(self.lib.ffr_train_export, self._WHICH[which], key.encode(), _ptr(out))
         return out
 
     def train_import(self, key, value, which='param'):
-        _check_dev(value, 'value', device=self.device)
-        v = value.detach().contiguous().float()
-        with torch.cuda.device(self.device):
-            self._ck(self.lib.ffr_train_import(self._h, self._WHICH[which], key.encode(), _ptr(v), self._stream()))
+        self._tensor(value, 'value')
+        v = value.detach().contiguous()
+        self._call(self.lib.ffr_train_import, self._WHICH[which], key.encode(), _ptr(v))
 
     def train_losses(self, f_enc, loss_weight=(1, 1, 1, 1), slot=0):
         """The four weighted loss items + accuracy (device tensor [5]) of the forward in `slot` (G = 2)."""
-        _check_dev(f_enc, 'f_enc', device=self.device)
-        out = torch.empty(5, device=f_enc.device, dtype=torch.float32)
-        lw = (C.c_double * 4)(*[float(x) for x in loss_weight])
-        with torch.cuda.device(self.device):
-            self._ck(self.lib.ffr_train_losses(self._h, slot, _ptr(f_enc.contiguous()), lw, _ptr(out), self._stream()))
+        self._tensor(f_enc, 'f_enc')
+        out = self._empty(5)
+        self._call(self.lib.ffr_train_losses, slot, _ptr(f_enc.contiguous()), _loss_weights(loss_weight), _ptr(out))
         return out
 
     def train_backward_losses(self, slot=0):
-        with torch.cuda.device(self.device):
-            self._ck(self.lib.ffr_train_backward_losses(self._h, slot, self._stream()))
+        self._call(self.lib.ffr_train_backward_losses, slot)
 
     def train_iteration(self, img_non, img_ocl, label, loss_weight=(1, 1, 1, 1)):
         """Encoder + RecNet train forward + losses + zero_grad + backward in one native call -> device tensor [5]."""
-        _check_dev(img_non, 'img_non', device=self.device)
-        _check_dev(img_ocl, 'img_ocl', device=self.device)
+        self._tensor(img_non, 'img_non')
+        self._tensor(img_ocl, 'img_ocl')
         n = img_non.size(0)
         if tuple(img_non.shape[1:]) != (3, 112, 112) or img_ocl.shape != img_non.shape:
             raise RuntimeError('ffrnet_amd: training images must be [N,3,112,112] pairs')
         lab = self._labels(label, n, img_non.device)
-        out = torch.empty(5, device=img_non.device, dtype=torch.float32)
-        lw = (C.c_double * 4)(*[float(x) for x in loss_weight])
-        with torch.cuda.device(self.device):
-            self._ck(self.lib.ffr_train_iteration(self._h, _ptr(img_non.contiguous()), _ptr(img_ocl.contiguous()), _ptr(lab), n,
-                                                  lw, _ptr(out), self._stream()))
+        out = self._empty(5)
+        self._call(self.lib.ffr_train_iteration, _ptr(img_non.contiguous()), _ptr(img_ocl.contiguous()), _ptr(lab), n,
+                   _loss_weights(loss_weight), _ptr(out))
         return out
 
     def train_iteration_u8(self, img_non, img_ocl, label, flip=None, loss_weight=(1, 1, 1, 1)):
         """train_iteration from decoded images: img_non / img_ocl [N,112,112,3] uint8 HWC RGB (device); flip: optional
         bool / uint8 [N], one h-flip flag per PAIR (the clean and the occluded image are mirrored together)."""
-        _check_u8(img_non, 'img_non', self.device, (112, 112))
-        _check_u8(img_ocl, 'img_ocl', self.device, (112, 112))
+        self._tensor(img_non, 'img_non', torch.uint8, ('N', 112, 112, 3), _U8_HINT)
+        self._tensor(img_ocl, 'img_ocl', torch.uint8, ('N', 112, 112, 3), _U8_HINT)
         n = img_non.size(0)
         if img_ocl.shape != img_non.shape:
             raise RuntimeError('ffrnet_amd: training images must be [N,112,112,3] pairs, got %s and %s'
                                % (list(img_non.shape), list(img_ocl.shape)))
-        fl = _flip_flags(flip, n, self.device)
+        fl = self._flags(flip, n)
         lab = self._labels(label, n, img_non.device)
-        out = torch.empty(5, device=img_non.device, dtype=torch.float32)
-        lw = (C.c_double * 4)(*[float(x) for x in loss_weight])
-        with torch.cuda.device(self.device):
-            self._ck(self.lib.ffr_train_iteration_u8(self._h, _ptr(img_non.contiguous()), _ptr(img_ocl.contiguous()),
-                                                     _ptr(fl), _ptr(lab), n, lw, _ptr(out), self._stream()))
+        out = self._empty(5)
+        self._call(self.lib.ffr_train_iteration_u8, _ptr(img_non.contiguous()), _ptr(img_ocl.contiguous()), _ptr(fl), _ptr(lab),
+                   n, _loss_weights(loss_weight), _ptr(out))
         return out
 
     def train_buckets(self):
@@ -1023,39 +955,28 @@ class Engine(object):
         return out
 
     def train_adam_step(self, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, clip_value=1.0):
-        with torch.cuda.device(self.device):
-            self._ck(self.lib.ffr_train_adam_step(self._h, lr, betas[0], betas[1], eps, weight_decay, clip_value,
-                                                  self._stream()))
+        self._call(self.lib.ffr_train_adam_step, lr, betas[0], betas[1], eps, weight_decay, clip_value)
 
     def encoder_trunk_nhwc(self, x, n_blocks):
-        _check_dev(x, 'x', device=self.device)
+        self._tensor(x, 'x')
         x = x.contiguous()
         n, _, h, w = x.shape
         chans, div = 64, 1
         from .synth import ir_blocks
         for cin, depth, stride in ir_blocks(getattr(self, 'num_layers', 50))[:n_blocks]:
             chans, div = depth, div * stride
-        out = torch.empty((n, h // div, w // div, chans), device=x.device, dtype=torch.float32)
-        with torch.cuda.device(self.device):
-            self._ck(self.lib.ffr_encoder_trunk_nhwc(self._h, _ptr(x), n, h, w, n_blocks,
-                                                     _ptr(out), self._stream()))
+        out = self._empty(n, h // div, w // div, chans)
+        self._call(self.lib.ffr_encoder_trunk_nhwc, _ptr(x), n, h, w, n_blocks, _ptr(out))
         return out
 
     def recnet_debug(self, featmap):
-        _check_dev(featmap, 'input', (512, 7, 7), device=self.device)
+        self._tensor(featmap, 'input', shape=('N', 512, 7, 7))
         featmap = featmap.contiguous()
-        n, dev = featmap.size(0), featmap.device
-        o = dict(ss_space=torch.empty((n, 49, 49), device=dev),
-                 M_space=torch.empty((n, 49, 49), device=dev),
-                 feat_space=torch.empty((n, 512, 7, 7), device=dev),
-                 feat_channel_raw=torch.empty((n, 512, 7, 7), device=dev),
-                 feat_channel=torch.empty((n, 512, 7, 7), device=dev),
-                 ss_channel0=torch.empty((512, 512), device=dev), M_channel0=torch.empty((512, 512), device=dev))
-        with torch.cuda.device(self.device):
-            self._ck(self.lib.ffr_recnet_debug(
-                self._h, _ptr(featmap), n, _ptr(o['ss_space']), _ptr(o['M_space']),
-                _ptr(o['feat_space']), _ptr(o['feat_channel_raw']), _ptr(o['feat_channel']),
-                _ptr(o['ss_channel0']), _ptr(o['M_channel0']), self._stream()))
+        n = featmap.size(0)
+        o = dict(ss_space=self._empty(n, 49, 49), M_space=self._empty(n, 49, 49), feat_space=self._empty(n, 512, 7, 7),
+                 feat_channel_raw=self._empty(n, 512, 7, 7), feat_channel=self._empty(n, 512, 7, 7),
+                 ss_channel0=self._empty(512, 512), M_channel0=self._empty(512, 512))
+        self._call(self.lib.ffr_recnet_debug, _ptr(featmap), n, *[_ptr(t) for t in o.values()])
         return o
 
 

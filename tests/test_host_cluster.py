@@ -1,18 +1,11 @@
 """CPU checks of the clustering's host side: the oracle of tests/cluster_ref.py against brute-force transitive closure,
-ffrnet_amd.cluster.pairwise_scores against hand-computed values, the dense-id helper, and the two new C symbols (declared,
-exported, bound with the header's argument counts)."""
-import ctypes
-import os
-import re
-
+ffrnet_amd.cluster.pairwise_scores against hand-computed values, and the dense-id helper.  (The C symbols are held to the
+header with every other row of native.SYMBOLS: test_host_logic.py.)"""
 import numpy as np
 import torch
 
 import cluster_ref
 from ffrnet_amd import cluster as fc
-from ffrnet_amd import native
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_oracle_union_find_matches_bruteforce_closure():
@@ -76,30 +69,3 @@ def test_dense_ids_on_cpu_tensors():
     assert empty.n_clusters == 0 and fc.member_order(empty)[1].tolist() == [0]
     import ffrnet_amd
     assert ffrnet_amd.cluster is fc and ffrnet_amd.Clusters is fc.Clusters
-
-
-def _header_args(name):
-    hdr = open(os.path.join(ROOT, 'include', 'ffrnet.h')).read()
-    m = re.search(r'^int\s+%s\s*\(([^;]*)\)\s*;' % name, hdr, re.M | re.S)
-    assert m, '%s is not declared in include/ffrnet.h' % name
-    return [a.strip() for a in m.group(1).split(',')]
-
-
-def test_cluster_symbols_are_declared_exported_and_bound():
-    lib = ctypes.CDLL(native.lib_path())
-    bound = {n: (res, args) for n, res, args in native.SYMBOLS}
-    for name, nargs in (('ffr_cluster_threshold', 8), ('ffr_cluster_templates', 9)):
-        args = _header_args(name)
-        assert len(args) == nargs, args
-        getattr(lib, name)
-        res, argtypes = bound[name]
-        assert res is ctypes.c_int and len(argtypes) == len(args)
-        for decl, ct in zip(args, argtypes):          # pointers as void*, long long / int / float by value
-            if '*' in decl:
-                assert ct is ctypes.c_void_p, decl
-            elif decl.startswith('long long'):
-                assert ct is ctypes.c_longlong, decl
-            elif decl.startswith('float'):
-                assert ct is ctypes.c_float, decl
-            else:
-                assert decl.startswith('int') and ct is ctypes.c_int, decl

@@ -1,11 +1,7 @@
 """CPU checks of the incremental clustering's host side: the oracle of tests/cluster_extend_ref.py against brute-force
 transitive closure, ffrnet_amd.cluster.representatives / changes against hand-written cases, the bookkeeping of
-cluster.Incremental and cluster.extend over a stub engine that answers from the oracle, and the new C symbol (declared,
-exported, bound with the header's arguments)."""
-import ctypes
-import os
-import re
-
+cluster.Incremental and cluster.extend over a stub engine that answers from the oracle.  (The C symbol is held to the header
+with every other row of native.SYMBOLS: test_host_logic.py.)"""
 import numpy as np
 import pytest
 import torch
@@ -13,32 +9,8 @@ import torch
 import cluster_extend_ref as xref
 import cluster_ref
 from ffrnet_amd import cluster as fc
-from ffrnet_amd import native
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 THR = 0.5
-
-
-def test_extend_symbol_is_declared_exported_and_bound():
-    hdr = open(os.path.join(ROOT, 'include', 'ffrnet.h')).read()
-    m = re.search(r'^int\s+ffr_cluster_extend\s*\(([^;]*)\)\s*;', hdr, re.M | re.S)
-    assert m, 'ffr_cluster_extend is not declared in include/ffrnet.h'
-    args = [a.strip() for a in m.group(1).split(',')]
-    assert len(args) == 10, args
-    getattr(ctypes.CDLL(native.lib_path()), 'ffr_cluster_extend')
-    res, argtypes = {n: (r, a) for n, r, a in native.SYMBOLS}['ffr_cluster_extend']
-    assert res is ctypes.c_int and len(argtypes) == 10
-    for decl, ct in zip(args, argtypes):          # pointers as void*, long long / int / float by value
-        if '*' in decl:
-            assert ct is ctypes.c_void_p, decl
-        elif decl.startswith('long long'):
-            assert ct is ctypes.c_longlong, decl
-        elif decl.startswith('float'):
-            assert ct is ctypes.c_float, decl
-        else:
-            assert decl.startswith('int') and ct is ctypes.c_int, decl
-    assert [a.split()[-1].lstrip('*') for a in args] == ['h', 'emb', 'norms', 'N_old', 'N', 'dim', 'threshold', 'prior', 'rep',
-                                                         'stream']
 
 
 def test_oracle_with_prior_matches_bruteforce_closure():

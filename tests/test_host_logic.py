@@ -95,6 +95,58 @@ def test_c_abi_exports_every_declared_symbol():
         assert rc != 0 and not h.value          # no device -> error code, never a CPU path
 
 
+def _header_prototypes():
+    """{name: (return type, [parameter declarations])} of every function include/*.h declares, comments stripped."""
+    import glob
+    hdr = ''.join(open(f).read() for f in sorted(glob.glob(os.path.join(ROOT, 'include', '*.h'))))
+    hdr = re.sub(r'//[^\n]*', '', re.sub(r'/\*.*?\*/', '', hdr, flags=re.S))
+    protos = {}
+    for ret, name, params in re.findall(r'^([A-Za-z_][\w \t\*]*?)\b(ffr_[a-z_0-9]+)\s*\(([^;{}]*)\)\s*;', hdr, re.M):
+        assert name not in protos, name
+        params = [' '.join(a.split()) for a in params.split(',')]
+        protos[name] = (' '.join(ret.split()), [] if params == ['void'] else params)
+    return protos
+
+
+_C_SCALARS = {'int': ctypes.c_int, 'long long': ctypes.c_longlong, 'float': ctypes.c_float, 'double': ctypes.c_double,
+              'size_t': ctypes.c_size_t, 'unsigned long long': ctypes.c_ulonglong}
+
+
+def _bound_as(decl, ct):
+    """Is the ctypes type `ct` a binding of the C type of `decl` (a parameter with its name, or a bare return type)?"""
+    if '*' in decl or '[' in decl:
+        return ct in (ctypes.c_void_p, ctypes.c_char_p) or (isinstance(ct, type) and issubclass(ct, ctypes._Pointer))
+    ctype = decl if decl in _C_SCALARS or decl == 'void' else decl.rsplit(' ', 1)[0]
+    return ct is (None if ctype == 'void' else _C_SCALARS[ctype])
+
+
+def test_symbol_table_matches_the_header_prototypes():
+    """Every row of native.SYMBOLS against its prototype in include/*.h: the argument count, pointers and arrays bound as a
+    pointer type, scalars as the ctypes type of the same C type, the return type likewise -- a wrong argtypes row corrupts
+    a call silently.  The counts of the clustering entry points and the argument order of ffr_cluster_extend are spelled out."""
+    protos = _header_prototypes()
+    rows = {name: (res, args) for name, res, args in native.SYMBOLS}
+    assert len(rows) == len(native.SYMBOLS) and set(rows) == set(protos) and len(protos) >= 60
+    bad = []
+    for name, (ret, params) in sorted(protos.items()):
+        res, argtypes = rows[name]
+        if not _bound_as(ret, res):
+            bad.append('%s returns %s, bound as %s' % (name, ret, res))
+        if len(argtypes) != len(params):
+            bad.append('%s takes %d arguments, bound with %d' % (name, len(params), len(argtypes)))
+        bad += ['%s: %s bound as %s' % (name, decl, ct) for decl, ct in zip(params, argtypes) if not _bound_as(decl, ct)]
+    assert not bad, bad
+    # the check itself tells the types apart
+    assert _bound_as('long long G', ctypes.c_longlong) and not _bound_as('long long G', ctypes.c_int)
+    assert _bound_as('const float* x', ctypes.c_void_p) and not _bound_as('const float* x', ctypes.c_longlong)
+    assert _bound_as('double* v', ctypes.POINTER(ctypes.c_double)) and not _bound_as('float t', ctypes.c_double)
+    assert _bound_as('const char*', ctypes.c_char_p) and _bound_as('void', None) and not _bound_as('int', None)
+    for name, nargs in (('ffr_cluster_threshold', 8), ('ffr_cluster_templates', 9), ('ffr_cluster_extend', 10)):
+        assert len(protos[name][1]) == nargs and protos[name][0] == 'int', protos[name]
+    assert [a.split()[-1].lstrip('*') for a in protos['ffr_cluster_extend'][1]] == [
+        'h', 'emb', 'norms', 'N_old', 'N', 'dim', 'threshold', 'prior', 'rep', 'stream']
+
+
 def test_integration_lists_the_sources():
     """INTEGRATION.md section 5 names the translation units of the library; held to SOURCES of
     __graft_entry__.py (the experiment kernel k_wino_fused_q left the product in round 5 and must not come back unnoticed),
@@ -334,11 +386,19 @@ def test_gradient_averaging_two_ranks():
 class _FakeDeviceTensor(object):
     """Stands in for a tensor on a GPU this container does not have: _check_dev only looks at type, device, dtype, shape."""
 
-    def __new__(cls, index, shape=(2, 3, 112, 112)):
+    def __new__(cls, index, shape=(2, 3, 112, 112), dtype=torch.float32):
         from unittest import mock
         t = mock.Mock(spec=torch.Tensor)
-        t.is_cuda, t.device, t.dtype, t.shape = True, torch.device('cuda', index), torch.float32, torch.Size(shape)
+        t.is_cuda, t.device, t.dtype, t.shape = True, torch.device('cuda', index), dtype, torch.Size(shape)
+        t.contiguous.return_value, t.size.return_value, t.numel.return_value = t, shape[0], int(np.prod(shape))
         return t
+
+
+def _stub_engine(index):
+    """An Engine without a handle or a library (no GPU here): a method that reaches the library raises AttributeError."""
+    eng = native.Engine.__new__(native.Engine)
+    eng.device, eng._h = torch.device('cuda', index), None       # __del__ -> close() finds nothing to destroy
+    return eng
 
 
 def test_boundary_rejects_tensors_of_another_device():
@@ -347,19 +407,42 @@ def test_boundary_rejects_tensors_of_another_device():
     native._check_dev(here, 'x', (3, 112, 112), device=torch.device('cuda', 3))
     with pytest.raises(RuntimeError, match=r'cuda:0 but this Engine lives on cuda:3'):
         native._check_dev(there, 'x', (3, 112, 112), device=torch.device('cuda', 3))
-    # every Engine method that takes a device tensor passes its own device to the check
+    # no Engine method calls a module-level tensor check, where the device is an argument to forget: every check goes
+    # through the method that binds self.device
     src = open(os.path.join(ROOT, 'ffr-net_amd', 'native.py')).read()
-    body = src.split('class Engine(object):', 1)[1]
-    calls = re.findall(r'_check_dev\((.*)\)', body)
-    assert len(calls) >= 18 and all('device=self.device' in c or 'device=self.engine.device' in c for c in calls), calls
+    body = src.split('class Engine(object):', 1)[1].split('\nclass ', 1)[0]
+    method = body[body.index('    def _tensor(self'):]
+    method = method[:method.index('\n    def ', 1)]
+    assert '_check(t, name, self.device,' in method
+    assert not re.findall(r'(?<![\w.])_check\w*\(', body.replace(method, '')), 'a tensor check that bypasses Engine._tensor'
+    assert len(re.findall(r'self\._tensor\(', body)) >= 18
     # out= buffers of Engine.embed get the same check (no GPU: run the method body against a stub handle)
-    eng = native.Engine.__new__(native.Engine)
-    eng.device = torch.device('cuda', 3)
+    eng = _stub_engine(3)
     x = _FakeDeviceTensor(3)
     x.contiguous.return_value, x.size.return_value = x, 2
     with pytest.raises(RuntimeError, match=r'out\[0\] is on cuda:0'):
         eng.embed(x, out=(_FakeDeviceTensor(0, (2, 512)), _FakeDeviceTensor(3, (2, 512))))
-    eng._h = None       # __del__ -> close() finds nothing to destroy
+
+
+def test_embed_u8_and_fold_accuracy_count_their_second_argument():
+    """k_stem reads one flip flag per image and ffr_lfw_fold_accuracy one label per score: a shorter tensor is refused
+    before any native call (the stub engine has no library to reach), as is a flip tensor of another device."""
+    eng = _stub_engine(3)
+    img = _FakeDeviceTensor(3, (4, 112, 112, 3), torch.uint8)
+    with pytest.raises(RuntimeError, match='4 flags'):
+        eng.embed_u8(img, torch.zeros(3, dtype=torch.uint8))
+    with pytest.raises(RuntimeError, match='bool or uint8'):
+        eng.embed_u8(img, torch.zeros(4, dtype=torch.int64))
+    far = _FakeDeviceTensor(0, (4,), torch.uint8)
+    with pytest.raises(RuntimeError, match='flip is on cuda:0 but this Engine lives on cuda:3'):
+        eng.embed_u8(img, far)
+    with pytest.raises(RuntimeError, match=r'img is on cuda:0 but this Engine lives on cuda:3'):
+        eng.embed_u8(_FakeDeviceTensor(0, (4, 112, 112, 3), torch.uint8))
+    with pytest.raises(RuntimeError, match=r'\[N,112,112,3\]'):
+        eng.embed_u8(_FakeDeviceTensor(3, (4, 112, 96, 3), torch.uint8))
+    scores = _FakeDeviceTensor(3, (5,))
+    with pytest.raises(RuntimeError, match='one label per score: 5 scores, 4 labels'):
+        eng.lfw_fold_accuracy(scores, torch.zeros(4, dtype=torch.int64))
 
 
 def test_shells_refuse_data_parallel_replicas():
