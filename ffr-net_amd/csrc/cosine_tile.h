@@ -60,26 +60,45 @@ __device__ __forceinline__ void cosine_fill_probes(f32x4* qf, const float* q, in
 // row within a block step of accumulator element r of wave w, lane half h
 __device__ __forceinline__ int cosine_lane_row(int w, int r, int h) { return acc_row(w * 32, r) + 4 * h; }
 
-__device__ __forceinline__ float cosine_score(float acc, float qn, float gn) { return acc / (qn * gn + 1e-8f); }
+// The denominator is one fused multiply-add, spelled out: left to the compiler's contraction, k_search_topk fused it for 14 of
+// a lane's 16 scores and not for the other 2, so a pair's last bit depended on where its row sat in a tile (and a kernel that
+// places rows elsewhere, k_search_rescore, could not reproduce it).
+__device__ __forceinline__ float cosine_score(float acc, float qn, float gn) { return acc / __builtin_fmaf(qn, gn, 1e-8f); }
 
 // The 8 partial chains of a tile, added in a fixed tree.  A macro, expanded in kernel scope: as a function (even a forced
 // inline one) the sum is vectorised differently and the register allocation of both kernels moves.
 #define COSINE_CHAIN_SUM(a) ((((a)[0] + (a)[1]) + ((a)[2] + (a)[3])) + (((a)[4] + (a)[5]) + ((a)[6] + (a)[7])))
 
-// A lane's stream through one chunk of the gallery: a 64-bit chunk base plus 32-bit element offsets inside it (<= 2^20 rows =
-// 2^29 floats per chunk), CT_PF groups in flight.
-struct CosineStream {
+// Where the 16-byte group j of a lane's row lies.  ChunkRows: a row of one chunk of the gallery, a 64-bit chunk base plus
+// 32-bit element offsets inside it (<= 2^20 rows = 2^29 floats per chunk).  GatherRows: any row of the gallery, named by its
+// 64-bit index (the shortlist of search_coarse.hip spans the whole gallery).
+struct ChunkRows {
+    typedef int Row;
     const float* __restrict__ base;
     unsigned lane_off;
-    int lane, row;
+    __device__ __forceinline__ f32x4 group(int r, int j) const { return *(const f32x4*)(base + ((unsigned)r * CT_DIM + 8u * j + lane_off)); }
+};
+struct GatherRows {
+    typedef long long Row;
+    const float* __restrict__ base;
+    unsigned lane_off;
+    __device__ __forceinline__ f32x4 group(long long r, int j) const { return *(const f32x4*)(base + (size_t)r * CT_DIM + (8u * j + lane_off)); }
+};
+
+// A lane's stream through the rows its address rule names, CT_PF groups in flight.
+template <class Addr>
+struct CosineStreamT {
+    Addr addr;
+    int lane;
+    typename Addr::Row row;
     f32x4 pf[CT_PF];
 
-    __device__ __forceinline__ CosineStream(const float* chunk_base, int lane_) : base(chunk_base), lane_off(4u * (lane_ >> 5)), lane(lane_) {}
+    __device__ __forceinline__ CosineStreamT(const float* base, int lane_) : addr{base, 4u * (lane_ >> 5)}, lane(lane_) {}
 
-    __device__ __forceinline__ f32x4 group(int r, int j) const { return *(const f32x4*)(base + ((unsigned)r * CT_DIM + 8u * j + lane_off)); }
+    __device__ __forceinline__ f32x4 group(typename Addr::Row r, int j) const { return addr.group(r, j); }
 
-    // the first CT_PF groups of row r (in bounds of the chunk)
-    __device__ __forceinline__ void prime(int r) {
+    // the first CT_PF groups of row r (in bounds)
+    __device__ __forceinline__ void prime(typename Addr::Row r) {
         row = r;
 #pragma unroll
         for (int u = 0; u < CT_PF; ++u) pf[u] = group(row, u);
@@ -88,7 +107,7 @@ struct CosineStream {
     // acc8 = the 8 chains of the 32 x 32 dots of the current row against the probe fragments qf (their sum:
     // COSINE_CHAIN_SUM); the ring refills with the rest of this row, then with the first groups of row `next`, which becomes
     // the current row
-    __device__ __forceinline__ void tile(f32x16 (&acc8)[CT_NACC], const f32x4* qf, int next) {
+    __device__ __forceinline__ void tile(f32x16 (&acc8)[CT_NACC], const f32x4* qf, typename Addr::Row next) {
 #pragma unroll
         for (int u = 0; u < CT_NACC; ++u) acc8[u] = f32x16{};
         f32x4 bq = qf[lane];
@@ -109,5 +128,6 @@ struct CosineStream {
         row = next;
     }
 };
+typedef CosineStreamT<ChunkRows> CosineStream;
 
 }  // namespace ffr

@@ -323,6 +323,70 @@ int ffr_topk_merge(ffr_handle* h, const float* score, const int64_t* index, int 
     return FFR_OK;
 }
 
+// ---- certified bf16 shortlist search (search_coarse.hip) -----------------------------------------------------------------
+int ffr_coarse_pack(ffr_handle* h, const float* rows, const float* norms, long long n, int dim, uint16_t* plane, int* plane_flag,
+                    void* stream) {
+    FFR_DEVICE_SCOPE(h); RC(check_fwd(h, false, false, 1));
+    RC(check_dim(h, "ffr_coarse_pack", dim));
+    if (!rows || !norms || !plane || !plane_flag || n < 1) return fail(h, FFR_ERR_ARG, "ffr_coarse_pack: bad arguments (n >= 1, non-null pointers)");
+    if (misaligned16(rows) || misaligned16(plane)) return fail(h, FFR_ERR_ARG, "ffr_coarse_pack: rows and plane must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    Scope s(h, st, FFR_KC_SCORE, 1.0 * n * dim, 6.0 * n * dim + 4.0 * n);
+    HIPCK(h, launch_coarse_pack(rows, norms, n, plane, plane_flag, st));
+    return FFR_OK;
+}
+
+int ffr_search_topk_coarse(ffr_handle* h, const float* query, int Q, const float* gallery, const float* gallery_norms,
+                           const uint16_t* gallery_plane, const int* plane_flag, long long G, int dim, int k, long long index_base,
+                           float* top_score, int64_t* top_index, int* certified, void* stream) {
+    FFR_DEVICE_SCOPE(h); RC(check_fwd(h, false, false, 1));
+    RC(check_dim(h, "ffr_search_topk_coarse", dim));
+    if (!query || !top_score || !top_index || Q < 1 || k < 1 || k > 128 || G < 0 ||
+        (G > 0 && (!gallery || !gallery_norms || !gallery_plane || !plane_flag)))
+        return fail(h, FFR_ERR_ARG, "ffr_search_topk_coarse: bad arguments (Q >= 1, 1 <= k <= 128, G >= 0, non-null pointers)");
+    if (misaligned16(query) || (G > 0 && (misaligned16(gallery) || misaligned16(gallery_plane))))
+        return fail(h, FFR_ERR_ARG, "ffr_search_topk_coarse: query, gallery and plane rows must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    if (G == 0 || k > coarse_max_k()) {          // nothing to shortlist, or a k the pass does not serve: the exact search alone
+        if (certified) HIPCK(h, hipMemsetAsync(certified, 0, sizeof(int) * (size_t)Q, st));
+        return ffr_search_topk(h, query, Q, gallery, gallery_norms, G, dim, k, index_base, top_score, top_index, stream);
+    }
+    const int kp = coarse_shortlist_size(k);
+    int T = 0, S = 0, Tf = 0, Sf = 0;
+    long long chunk_rows = 0, chunk_f = 0;
+    search_plan(Q, G, h->num_cus, &T, &S, &chunk_rows);
+    coarse_fallback_plan(Q, G, h->num_cus, &Tf, &Sf, &chunk_f);
+    // scratch: probe norms [Q]; shortlists [Q][kp]; the uncertified probes' ids [Q], count, rows [Q][512], norms [Q] and exact
+    // lists [Q][k]; the chunk lists of the coarse pass [S][Q][kp] and then of the exact pass [Sf][Q][k], in the same space
+    const size_t part_n = std::max(S > 1 ? (size_t)S * Q * kp : 0, Sf > 1 ? (size_t)Sf * Q * k : 0);
+    float *qnorm = nullptr, *sl_s = nullptr, *uq = nullptr, *uqn = nullptr, *fb_s = nullptr, *part_s = nullptr;
+    int64_t *sl_i = nullptr, *fb_i = nullptr, *part_i = nullptr;
+    int *ulist = nullptr, *ucount = nullptr;
+    RC(carve(h, h->search, "search", [&](Arena& a) {
+        qnorm = a.take(Q);
+        sl_s = a.take((size_t)Q * kp); sl_i = a.take<int64_t>((size_t)Q * kp);
+        ulist = a.take<int>(Q); ucount = a.take<int>(1);
+        uq = a.take((size_t)Q * dim); uqn = a.take(Q);
+        fb_s = a.take((size_t)Q * k); fb_i = a.take<int64_t>((size_t)Q * k);
+        if (part_n) { part_s = a.take(part_n); part_i = a.take<int64_t>(part_n); }
+    }));
+    Scope s(h, st, FFR_KC_SCORE, 2.0 * Q * (double)G * dim, 2.0 * (double)G * (dim + 2) + 4.0 * Q * dim + 12.0 * Q * (k + kp));
+    HIPCK(h, launch_row_norms(query, Q, qnorm, st));
+    HIPCK(h, hipMemsetAsync(ucount, 0, sizeof(int), st));
+    HIPCK(h, launch_search_coarse(query, qnorm, Q, gallery_plane, gallery_norms, G, kp, T, S, chunk_rows, S > 1 ? part_s : sl_s,
+                                  S > 1 ? part_i : sl_i, st));
+    if (S > 1) HIPCK(h, launch_topk_merge(part_s, part_i, S, Q, kp, sl_s, sl_i, st));
+    HIPCK(h, launch_search_rescore(query, qnorm, Q, gallery, gallery_norms, sl_s, sl_i, plane_flag, G, k, kp, index_base, top_score,
+                                   top_index, certified, ulist, ucount, st));
+    // the exact search of the probes that were not certified, sized for Q: tiles past the device count leave at once
+    HIPCK(h, launch_probe_gather(query, qnorm, ulist, ucount, Q, uq, uqn, st));
+    HIPCK(h, launch_search_topk(uq, uqn, Q, gallery, gallery_norms, G, k, index_base, Tf, Sf, chunk_f, Sf > 1 ? part_s : fb_s,
+                                Sf > 1 ? part_i : fb_i, st, ucount));
+    if (Sf > 1) HIPCK(h, launch_topk_merge(part_s, part_i, Sf, Q, k, fb_s, fb_i, st, ucount));
+    HIPCK(h, launch_topk_scatter(fb_s, fb_i, ulist, ucount, Q, k, top_score, top_index, st));
+    return FFR_OK;
+}
+
 // ---- clustering (cluster.hip) ----------------------------------------------------------------------------------------
 // The body of ffr_cluster_threshold (ext = false: no prior, N_old = 0) and of ffr_cluster_extend; `who` names the entry in messages
 static int cluster_rows(ffr_handle* h, const char* who, bool ext, const float* emb, const float* norms, long long N_old,

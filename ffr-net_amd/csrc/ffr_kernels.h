@@ -235,13 +235,40 @@ hipError_t launch_row_norms(const float* x, long long n, float* norms, hipStream
 // chunking of a search: probe tiles x gallery chunks (chunk_rows <= search_max_chunk_rows()); G >= 1
 long long search_max_chunk_rows();
 void search_plan(int Q, long long G, int num_cus, int* ntiles, int* nchunks, long long* chunk_rows);
-// top-k lists [nchunks][Q][k] of every gallery chunk (one launch); k <= 128, dim 512, rows 16-byte aligned
+// top-k lists [nchunks][Q][k] of every gallery chunk (one launch); k <= 128, dim 512, rows 16-byte aligned.  live (device, or
+// null): only the probes [0, *live) are searched, the lists of the others are left as they are
 hipError_t launch_search_topk(const float* query, const float* qnorm, int Q, const float* gallery, const float* gnorm,
                               long long G, int k, long long index_base, int ntiles, int nchunks, long long chunk_rows,
-                              float* out_s, int64_t* out_i, hipStream_t stream);
-// S sorted lists [S][Q][k] -> [Q][k] (descending score, ties by ascending index; index < 0 = padding); S <= 4096
+                              float* out_s, int64_t* out_i, hipStream_t stream, const int* live = nullptr);
+// S sorted lists [S][Q][k] -> [Q][k] (descending score, ties by ascending index; index < 0 = padding); S <= 4096; live as above
 hipError_t launch_topk_merge(const float* score, const int64_t* index, int S, int Q, int k, float* out_s, int64_t* out_i,
-                             hipStream_t stream);
+                             hipStream_t stream, const int* live = nullptr);
+
+// ---- certified bf16 shortlist search (search_coarse.hip) ------------------------------
+// rows the coarse pass lists per probe for a top-k (k <= coarse_max_k()), and the largest k it serves
+int coarse_shortlist_size(int k);
+int coarse_max_k();
+// chunking of the exact pass over the probes that were not certified: as search_plan, with chunks fine enough that a few live
+// probes still reach every CU
+void coarse_fallback_plan(int Q, long long G, int num_cus, int* ntiles, int* nchunks, long long* chunk_rows);
+// plane[r] = bf16(rows[r] / norms[r]) of [n][512] rows; *flag |= 1 when a norm is unsafe (not zero and outside [2^-60, 2^60])
+hipError_t launch_coarse_pack(const float* rows, const float* norms, long long n, uint16_t* plane, int* flag, hipStream_t stream);
+// shortlists [nchunks][Q][kp] of every plane chunk by coarse score, index = gallery row (one launch); merged by launch_topk_merge
+hipError_t launch_search_coarse(const float* query, const float* qnorm, int Q, const uint16_t* plane, const float* gnorm,
+                                long long G, int kp, int ntiles, int nchunks, long long chunk_rows, float* out_s, int64_t* out_i,
+                                hipStream_t stream);
+// exact scores of the shortlists sl[Q][kp], the certificate, the certified probes' top-k -> top[Q][k]; the others' ids ->
+// ulist[0 .. *ucount) (ucount zero before the launch); certified[Q] (0 / 1) may be null
+hipError_t launch_search_rescore(const float* query, const float* qnorm, int Q, const float* gallery, const float* gnorm,
+                                 const float* sl_s, const int64_t* sl_i, const int* plane_flag, long long G, int k, int kp,
+                                 long long index_base, float* top_s, int64_t* top_i, int* certified, int* ulist, int* ucount,
+                                 hipStream_t stream);
+// uq[i] = query[ulist[i]], uqn[i] = qnorm[ulist[i]] for i < *ucount (grid sized for Q)
+hipError_t launch_probe_gather(const float* query, const float* qnorm, const int* ulist, const int* ucount, int Q, float* uq,
+                               float* uqn, hipStream_t stream);
+// top[ulist[i]] = fb[i] for i < *ucount: the lists [k] of the exact pass back to their probes
+hipError_t launch_topk_scatter(const float* fb_s, const int64_t* fb_i, const int* ulist, const int* ucount, int Q, int k,
+                               float* top_s, int64_t* top_i, hipStream_t stream);
 
 // ---- clustering (cluster.hip) ----------------------------------------------------------
 // chunking of the self-join: probe tiles x row chunks, sized for the blocks on and above the diagonal; N >= 1

@@ -101,6 +101,8 @@ SYMBOLS = [
     ('ffr_row_norms', C.c_int, [_P, _P, C.c_longlong, C.c_int, _P, _P]),
     ('ffr_search_topk', C.c_int, [_P, _P, C.c_int, _P, _P, C.c_longlong, C.c_int, C.c_int, C.c_longlong, _P, _P, _P]),
     ('ffr_topk_merge', C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    ('ffr_coarse_pack', C.c_int, [_P, _P, _P, C.c_longlong, C.c_int, _P, _P, _P]),
+    ('ffr_search_topk_coarse', C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, C.c_longlong, C.c_int, C.c_int, C.c_longlong, _P, _P, _P, _P]),
     ('ffr_cluster_threshold', C.c_int, [_P, _P, _P, C.c_longlong, C.c_int, C.c_float, _P, _P]),
     ('ffr_cluster_templates', C.c_int, [_P, _P, _P, _P, _P, C.c_longlong, C.c_int, _P, _P]),
     ('ffr_cluster_extend', C.c_int, [_P, _P, _P, C.c_longlong, C.c_longlong, C.c_int, C.c_float, _P, _P, _P]),
@@ -443,6 +445,50 @@ class Engine(object):
         self._call(self.lib.ffr_search_topk, _ptr(query), Q, _ptr(gallery if G else None), _ptr(gallery_norms), G,
                    query.size(1), k, int(index_base), _ptr(scores), _ptr(index))
         return scores, index
+
+    def coarse_pack(self, rows, norms, plane_out, flag):
+        """plane_out[n,512] (int16: bf16 bits) = bf16(rows[r] / norms[r]) of rows[n,512]; flag (int32 [1], zero when its
+        gallery was created) gets 1 ORed in when a row's norm is unsafe (include/ffrnet.h: ffr_coarse_pack)."""
+        self._tensor(rows, 'rows', shape=('n', 512))
+        n = rows.size(0)
+        self._tensor(norms, 'norms', shape=(n,))
+        self._tensor(plane_out, 'plane_out', torch.int16, shape=(n, 512))
+        self._tensor(flag, 'flag', torch.int32, shape=(1,))
+        if not (rows.is_contiguous() and norms.is_contiguous() and plane_out.is_contiguous()):
+            raise RuntimeError('ffrnet_amd: coarse_pack expects contiguous rows, norms and plane_out')
+        if n:
+            self._call(self.lib.ffr_coarse_pack, _ptr(rows), _ptr(norms), n, 512, _ptr(plane_out), _ptr(flag))
+        return plane_out
+
+    def search_coarse(self, query, gallery, plane, flag, k, gallery_norms=None, index_base=0, return_certified=False):
+        """search() through the certified bf16 shortlist (include/ffrnet.h: ffr_search_topk_coarse): the same
+        (scores[Q,k], index[Q,k]) bit for bit.  plane[G,512] int16 and flag int32 [1] come from coarse_pack over the same
+        rows and norms.  return_certified: also certified[Q] int32, 1 where the shortlist was proven to hold the top-k,
+        0 where the probe went through the exact search."""
+        self._tensor(query, 'query')
+        self._tensor(gallery, 'gallery')
+        if query.dim() != 2 or gallery.dim() != 2 or query.size(1) != gallery.size(1):
+            raise RuntimeError('ffrnet_amd: search_coarse expects query [Q,dim] and gallery [G,dim], got %s and %s'
+                               % (list(query.shape), list(gallery.shape)))
+        query, gallery = query.contiguous(), gallery.contiguous()
+        G = gallery.size(0)
+        self._tensor(plane, 'plane', torch.int16, shape=(G, gallery.size(1)))
+        self._tensor(flag, 'flag', torch.int32, shape=(1,))
+        plane = plane.contiguous()
+        if gallery_norms is None:
+            gallery_norms = self.row_norms(gallery) if G else None
+        else:
+            self._tensor(gallery_norms, 'gallery_norms')
+            if tuple(gallery_norms.shape) != (G,):
+                raise RuntimeError('ffrnet_amd: gallery_norms must be [%d], got %s' % (G, list(gallery_norms.shape)))
+            gallery_norms = gallery_norms.contiguous()
+        Q, k = query.size(0), int(k)
+        scores, index = self._empty(Q, max(k, 0)), self._empty(Q, max(k, 0), dtype=torch.int64)
+        cert = self._empty(Q, dtype=torch.int32)
+        self._call(self.lib.ffr_search_topk_coarse, _ptr(query), Q, _ptr(gallery if G else None), _ptr(gallery_norms),
+                   _ptr(plane if G else None), _ptr(flag), G, query.size(1), k, int(index_base), _ptr(scores), _ptr(index),
+                   _ptr(cert))
+        return (scores, index, cert) if return_certified else (scores, index)
 
     def topk_merge(self, scores, index):
         """Merge S sorted lists per probe, scores[S,Q,k] fp32 and index[S,Q,k] int64 (device; index < 0 = padding), in

@@ -8,6 +8,10 @@ aligned pairs (lfw/lfw_eval.py).  This module answers "which of my G enrolled pe
   rates = identification_rates(index, probe_labels, gallery_labels)   # CMC rank-1 / 5 / 10
 
 A gallery spread over several processes (one per GPU) searches its shards with search_sharded().
+
+Gallery(engine, coarse=True) keeps a bf16 plane beside the rows (1 KB per row more) and searches through the certified bf16
+shortlist (include/ffrnet.h: ffr_search_topk_coarse): the same results bit for bit, the pass over the gallery on the bf16
+matrix cores.  Gallery.last_certified says which probes of the last search the shortlist was proven for.
 """
 import torch
 
@@ -17,17 +21,35 @@ except ImportError:            # pragma: no cover
     dist = None
 
 DIM = 512
+COARSE_EPS = 2.0 ** -8 + 2.0 ** -12      # bound on |coarse score - exact score| (FFR_COARSE_EPS of include/ffrnet.h)
+COARSE_MAX_K = 64                        # the coarse pass serves k <= 64
+
+
+def shortlist_size(k):
+    """Rows the coarse pass lists per probe for a top-k: min(128, max(2k, 32)); None for k > 64, where the exact search
+    runs alone."""
+    k = int(k)
+    if k > COARSE_MAX_K:
+        return None
+    return min(128, max(2 * k, 32))
 
 
 class Gallery(object):
     """Enrolled embeddings [n,512] and their norms on the Engine's device, in a grow-only buffer: add() appends, rows
-    keep their index for ever (the index search() returns)."""
+    keep their index for ever (the index search() returns).  coarse=True: a bf16 plane of the normalised rows and its
+    unsafe-norm flag grow beside them, add() packs the rows it appends, and search() goes through the certified shortlist
+    (the same results; last_certified[Q] int32 tells which probes were certified)."""
 
-    def __init__(self, engine, capacity=0):
+    def __init__(self, engine, capacity=0, coarse=False):
         self.engine = engine
         self._n = 0
         self._emb = torch.empty((int(capacity), DIM), device=engine.device, dtype=torch.float32)
         self._norms = torch.empty((int(capacity),), device=engine.device, dtype=torch.float32)
+        self.coarse = bool(coarse)
+        self.last_certified = None
+        if self.coarse:
+            self._plane = torch.empty((int(capacity), DIM), device=engine.device, dtype=torch.int16)
+            self._flag = torch.zeros((1,), device=engine.device, dtype=torch.int32)
 
     def __len__(self):
         return self._n
@@ -39,6 +61,16 @@ class Gallery(object):
     @property
     def norms(self):
         return self._norms[:self._n]
+
+    @property
+    def plane(self):
+        """bf16 bits [n,512] (int16) of the normalised rows; coarse galleries only."""
+        return self._plane[:self._n]
+
+    @property
+    def flag(self):
+        """int32 [1]: non-zero once a row with an unsafe norm was added; coarse galleries only."""
+        return self._flag
 
     def add(self, emb):
         """Append emb[n,512] (fp32, on the Engine's device) -> the index of its first row."""
@@ -54,9 +86,16 @@ class Gallery(object):
             emb_new[:first] = self._emb[:first]
             norms_new[:first] = self._norms[:first]
             self._emb, self._norms = emb_new, norms_new
+            if self.coarse:
+                plane_new = torch.empty((cap, DIM), device=self._emb.device, dtype=torch.int16)
+                plane_new[:first] = self._plane[:first]
+                self._plane = plane_new
         if n:
             self._emb[first:first + n] = emb
             self._norms[first:first + n] = self.engine.row_norms(self._emb[first:first + n])
+            if self.coarse:
+                self.engine.coarse_pack(self._emb[first:first + n], self._norms[first:first + n],
+                                        self._plane[first:first + n], self._flag)
         self._n = first + n
         return first
 
@@ -64,9 +103,17 @@ class Gallery(object):
         """Top-k enrolled rows of every probe query[Q,512] -> (scores[Q,k], index[Q,k]).  self_index[Q] (gallery
         indices of the probes themselves): leave-one-out search, the probe's own row is never returned."""
         if self_index is None:
-            return self.engine.search(query, self.embeddings, k, gallery_norms=self.norms, index_base=index_base)
-        s, i = self.engine.search(query, self.embeddings, int(k) + 1, gallery_norms=self.norms, index_base=index_base)
+            return self._search(query, k, index_base)
+        s, i = self._search(query, int(k) + 1, index_base)
         return drop_self(s, i, torch.as_tensor(self_index, device=i.device) + int(index_base))
+
+    def _search(self, query, k, index_base):
+        if not self.coarse:
+            return self.engine.search(query, self.embeddings, k, gallery_norms=self.norms, index_base=index_base)
+        s, i, self.last_certified = self.engine.search_coarse(query, self.embeddings, self.plane, self._flag, k,
+                                                              gallery_norms=self.norms, index_base=index_base,
+                                                              return_certified=True)
+        return s, i
 
 
 def drop_self(scores, index, self_index):

@@ -140,6 +140,42 @@ int ffr_search_topk(ffr_handle* h, const float* query, int Q, const float* galle
 int ffr_topk_merge(ffr_handle* h, const float* score, const int64_t* index, int S, int Q, int k,
                    float* out_score, int64_t* out_index, void* stream);
 
+/* ---- certified bf16 shortlist search -------------------------------------------------------------------------------------
+ * ffr_search_topk_coarse gives the outputs of ffr_search_topk, bit for bit, for every input without NaN/inf; only the way
+ * there differs.  The pass over the whole gallery runs on the bf16 matrix cores over a plane of half the bytes and picks a
+ * shortlist; the fp32 arithmetic of ffr_search_topk scores the shortlist; a proven bound certifies, per probe, that the
+ * shortlist holds the true top-k, and a probe without that certificate is searched exactly.  No approximate mode.
+ *   plane  gallery_plane[G][512] holds bf16(g / |g|) (round to nearest even, uint16_t at this boundary), |g| the norm of
+ *          ffr_row_norms: 1 KB per enrolled row beside the 2 KB fp32 row, which stays.  ffr_coarse_pack writes it for the
+ *          rows it is given (the rows an enrolment appends; a plane is the same however it was pieced together).
+ *   bound  the probe is split into two bf16 planes q / |q| = hi + lo.  With u = 2^-8 (bf16 unit round-off) Cauchy-Schwarz
+ *          gives |sum (hi + lo) g^ - cos(q, g)| <= u + u^2 + u^3; 2^-13 is allowed for accumulating the 1024 exact products
+ *          in the matrix core (assumed, 8 x a plain fp32 chain: the core's rounding is undocumented and no test can observe
+ *          c); the coarse score c = (sum (hi + lo) g^) |q||g| / (|q||g| + 1e-8) uses the norms of the exact
+ *          score s, itself within 1e-6 of the cosine.  |c - s| <= 0.00405 < FFR_COARSE_EPS = 2^-8 + 2^-12.
+ *   certificate  the pass keeps the k' = min(128, max(2k, 32)) best rows of a probe by (descending c, ascending index),
+ *          c_1 >= ... >= c_k', and they are scored exactly; s_k is the k-th best of them in the order of ffr_search_topk.
+ *          The probe is certified iff G <= k' or c_k' + FFR_COARSE_EPS < s_k (strictly: no row left out can even tie the
+ *          k-th); its answer is the top k of the re-scored shortlist.  Otherwise its answer comes from the exact search.
+ *   unsafe a norm that is not zero and outside [2^-60, 2^60], or not finite, is unsafe (its sum of squares under- or
+ *          overflowed), and so is a zero norm over a row that is not all zeros (every square underflowed).  ffr_coarse_pack
+ *          ORs 1 into *plane_flag (device int, zeroed by the caller at creation, sticky) when it meets such a row; while
+ *          the flag is set no probe is certified.  A probe with an unsafe norm is not certified.
+ *          A zero row packs to zeros and is safe.
+ *   k      the pass serves k <= 64; for 64 < k <= 128 (and for G = 0) the exact search runs alone and every probe is reported
+ *          uncertified.
+ * Arguments and error codes are those of ffr_search_topk; the plane must be 16-byte aligned and, like the gallery, may be
+ * NULL only when G = 0 (plane_flag likewise).  certified[Q] (device, 1 = the certificate held, 0 = searched exactly) may be
+ * NULL.  No host synchronisation: the exact pass over the uncertified probes is always launched and leaves at once where a
+ * device count says there is nothing to do, so a call can be captured into a hipGraph once it has run at that shape.
+ * Profiled under FFR_KC_SCORE; a coarse search counts flops = 2*Q*G*512, the scores it ranks.                          */
+#define FFR_COARSE_EPS (0.00390625f + 0.000244140625f)
+int ffr_coarse_pack(ffr_handle* h, const float* rows, const float* norms, long long n, int dim,
+                    uint16_t* plane, int* plane_flag, void* stream);
+int ffr_search_topk_coarse(ffr_handle* h, const float* query, int Q, const float* gallery, const float* gallery_norms,
+                           const uint16_t* gallery_plane, const int* plane_flag, long long G, int dim, int k,
+                           long long index_base, float* top_score, int64_t* top_index, int* certified, void* stream);
+
 /* ---- clustering (unlabelled embeddings -> identities -> one template per identity) ----------------------------------
  * The step in front of enrolment: N unlabelled faces are grouped by single-link clustering at one cosine threshold, and
  * each group is fused into one template row.  The N x N scores never leave the chip; the output is one label per row.
