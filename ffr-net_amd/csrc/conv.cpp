@@ -150,24 +150,29 @@ static int trace_wino_fused(ffr_handle* h, WinoFusedArgs& f, const ConvW& L, con
 
 // plan + launch one (possibly batched) implicit-GEMM described by `a` (M, nkt, cout_pad, nbatch set)
 int run_gemm(ffr_handle* h, IgemmArgs& a, const ConvCall& c, double flops, double bytes, hipStream_t st, double fuse) {
-    int tile, nblocks;
     int force = c.tile;
     if (force) {      // a forced tile whose width does not divide cout_pad would launch zero column tiles and leave `out` unwritten
         int fbm, fbn;
         igemm_tile_shape(force, &fbm, &fbn);
         if (a.cout_pad % fbn) return fail(h, FFR_ERR_ARG, "conv: forced tile %d (%d x %d) does not divide cout_pad %d", force, fbm, fbn, a.cout_pad);
     }
-    plan_igemm(a.M, a.cout_pad, a.nkt, a.nbatch, force, h->opt.sk_minunits, &tile, &nblocks, &a.granule, a.w3 != nullptr);
+    const GemmPlan g = plan_gemm_launch(a.M, a.cout_pad, a.nkt, a.nbatch, force, h->opt.sk_minunits, a.w3 != nullptr, c.partial_cap, c.tickets_cap);
+    if (g.nomem) return fail(h, FFR_ERR_NOMEM, "%s", g.nomem);
+    const int tile = g.tile, nblocks = g.nblocks;
+    const long long units = g.units;
+    const bool cut = g.cut;
     int bm, bn;
     igemm_tile_shape(tile, &bm, &bn);
-    a.mtiles = (a.M + bm - 1) / bm;
-    a.ntiles = a.cout_pad / bn;
-    const long long units = (long long)a.nbatch * a.mtiles * a.ntiles * a.nkt;
-    const bool cut = a.granule == 1 && ((units % nblocks) != 0 || ((units / nblocks) % a.nkt) != 0);
-    if (cut && (size_t)nblocks * 2 * bm * bn > c.partial_cap) return fail(h, FFR_ERR_NOMEM, "stream-K workspace too small");
+    a.granule = g.granule; a.mtiles = g.mtiles; a.ntiles = g.ntiles;
     a.partial = c.partial;
     a.tickets = c.tickets;
-    if ((size_t)a.nbatch * a.mtiles * a.ntiles > c.tickets_cap) return fail(h, FFR_ERR_NOMEM, "stream-K ticket array too small");
+    if (h->conv_rec) {      // the plan record: what this launch runs with, from the values above
+        ffr_conv_launch r{};
+        r.path = FFR_CP_DIRECT; r.images = a.N; r.rows = a.M;
+        r.tile = tile; r.nblocks = nblocks; r.granule = a.granule; r.nkt = a.nkt; r.tiles = a.nbatch * a.mtiles * a.ntiles;
+        r.cut = cut ? 1 : 0; r.split = a.w3 ? 1 : 0;
+        h->conv_log.push_back(r);
+    }
 #ifdef FFR_TRACE
     if (h->opt.igemm_trace) return trace_igemm(h, a, tile, nblocks, units, st);
 #endif
@@ -199,6 +204,12 @@ static int conv_mixed(ffr_handle* h, const ConvW& L, const ConvCall& c, double f
         fexec += 2.0 * wino_mixed_xp(tau) * std::ceil(Tt / 32.0) * 32.0 * L.cout_pad * L.cin_pad;
         fuse += 2.0 * wino_mixed_x(tau) * Tt * L.cout * L.cin;
     }
+    if (h->conv_rec) {
+        ffr_conv_launch r{};
+        r.path = FFR_CP_MIXED; r.images = c.N; r.rows = c.N * (g.n4 + g.n3) * (g.n4 + g.n3);
+        r.block_tiles = wino_mixed_blocks(c.N, c.H, c.W, L.cout_pad);
+        h->conv_log.push_back(r);
+    }
 #ifdef FFR_TRACE
     if (h->opt.wf_trace) return trace_wino_mixed(h, f, L, c, st);
 #endif
@@ -224,6 +235,12 @@ static int conv_fused(ffr_handle* h, const ConvW& L, const ConvCall& c, const Co
     f.cout_pad = L.cout_pad; f.cout_store = c.cout_store; f.out_pitch = c.out_pitch; f.out_coff = c.out_coff;
     f.res_pitch = c.res_pitch; f.border_bias = L.border; f.flags = c.flags;
     const double fexec = 2.0 * 36.0 * (double)((T + 31) / 32 * 32) * (double)L.cout_pad * L.cin_pad;
+    if (h->conv_rec) {
+        ffr_conv_launch r{};
+        r.path = FFR_CP_FUSED; r.images = c.N; r.rows = (int)T;
+        r.phased = p.phased ? 1 : 0; r.half_n = f.half_n; r.split = f.U3 ? 1 : 0; r.block_tiles = (int)((T + 31) / 32) * (L.cout_pad / (p.half_n ? 32 : 64));
+        h->conv_log.push_back(r);
+    }
 #ifdef FFR_TRACE
     if (h->opt.wf_trace) return trace_wino_fused(h, f, L, c, p, st);
 #endif
@@ -266,17 +283,38 @@ static int conv_unfused(ffr_handle* h, const ConvW& L, const ConvCall& c, long l
         int bm, bn;
         igemm_tile_shape(gtile, &bm, &bn);
         const double fexec = 2.0 * 36.0 * (double)((T + bm - 1) / bm) * bm * (double)L.cout_pad * L.cin_pad;
+        if (h->conv_rec) {
+            ffr_conv_launch r{};
+            r.path = FFR_CP_UNFUSED_STREAM; r.images = c.N; r.rows = (int)T;
+            r.tile = gtile; r.nblocks = gblocks; r.nkt = L.cin_pad / 32; r.granule = r.nkt;       // whole tiles only: nothing is cut
+            r.tiles = (int)(36 * ((T + bm - 1) / bm) * (L.cout_pad / bn));
+            h->conv_log.push_back(r);
+        }
         Scope s(h, st, FFR_KC_CONV_IGEMM, flops, bytes, fexec, flops / 4.0);
         HIPCK(h, launch_gemm_stream(g, gtile, gblocks, st));
     } else {
         RC(igemm_batched(h, c, c.winoV, T * L.cin_pad, L.cin_pad, L.wu, (long long)L.cout_pad * L.cin_pad, L.cout_pad, c.winoM, L.cout_pad,
                          T * L.cout_pad, (int)T, 36, flops, bytes, flops / 4.0, st));
+        if (h->conv_rec && !h->conv_log.empty()) { h->conv_log.back().path = FFR_CP_UNFUSED_IGEMM; h->conv_log.back().images = c.N; }
     }
     if (c.wino_stage == 1) return FFR_OK;        // the caller transforms M itself (k_wino_out_in)
     Scope s(h, st, FFR_KC_WINO, 0, 4.0 * (36.0 * T * L.cout_pad + (double)M * L.cout));
     HIPCK(h, launch_wino_out(c.winoM, L.bias, L.slope, c.resid, c.res_pitch, c.out, c.out_pitch, c.out_coff,
                              c.cout_store, L.cout_pad, c.N, c.H, c.W, L.border, c.flags, st, c.tile_sums));
     return FFR_OK;
+}
+
+// The two calls of a tail split (plan p of call c, p.n_main > 0): c1 = the first n_main images in the fused form of p, c2 = the
+// rest through the transform kernels + batched GEMM, every tensor of c moved on by those images
+void tail_split_calls(const ConvW& L, const ConvCall& c, const ConvPlan& p, ConvCall* c1, ConvCall* c2) {
+    *c1 = c; *c2 = c;
+    c1->N = p.n_main; c1->force = p.half_n ? ConvForce::FusedHalf : p.split ? ConvForce::FusedSplit : ConvForce::Fused;
+    c2->N = c.N - p.n_main; c2->force = ConvForce::Unfused;
+    const size_t px = (size_t)p.n_main * c.H * c.W;
+    if (c.x) c2->x = c.x + px * c.in_pitch;
+    if (c.out) c2->out = c.out + px * c.out_pitch;
+    if (c.resid) c2->resid = c.resid + px * c.res_pitch;
+    if (c.tile_sums) c2->tile_sums = c.tile_sums + (size_t)p.n_main * ((c.H + 3) / 4) * ((c.W + 3) / 4) * L.cout_pad;
 }
 
 // Runs the convolution L on call c as plan_conv plans it
@@ -288,6 +326,11 @@ int run_conv(ffr_handle* h, const ConvW& L, const ConvCall& c, hipStream_t st) {
     if (L.border && (c.H < 2 || c.W < 2)) return fail(h, FFR_ERR_UNSUPPORTED, "border-class bias needs H,W >= 2");
     const double flops = 2.0 * M * L.cout * (double)L.R * L.S * L.cin;
     const double bytes = 4.0 * ((double)c.N * c.H * c.W * L.cin + (double)M * L.cout + (double)L.cout * L.R * L.S * L.cin);
+    if (h->conv_rec) {      // a replayed capture would launch without recording
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        HIPCK(h, hipStreamIsCapturing(st, &cs));
+        if (cs != hipStreamCaptureStatusNone) return fail(h, FFR_ERR_STATE, "conv: the plan record is on and the stream is capturing");
+    }
     const ConvPlan p = plan_conv(h, L, c);
     if (p.refused) return fail(h, FFR_ERR_STATE, "%s", p.refused);
     if (p.path == ConvPlan::Mixed) return conv_mixed(h, L, c, flops, bytes, st);
@@ -295,14 +338,14 @@ int run_conv(ffr_handle* h, const ConvW& L, const ConvCall& c, hipStream_t st) {
     if (p.path == ConvPlan::Fused && !p.n_main) return conv_fused(h, L, c, p, flops, bytes, st);
     if (p.path == ConvPlan::Fused) {
         // tail split: the first n_main images fused, the rest through the transform kernels + batched GEMM
-        ConvCall c1 = c, c2 = c;
-        c1.N = p.n_main; c1.force = p.half_n ? ConvForce::FusedHalf : p.split ? ConvForce::FusedSplit : ConvForce::Fused;
-        c2.N = c.N - p.n_main; c2.force = ConvForce::Unfused;
-        const size_t px = (size_t)p.n_main * c.H * c.W;
-        c2.x = c.x + px * c.in_pitch;
-        c2.out = c.out + px * c.out_pitch;
-        if (c.resid) c2.resid = c.resid + px * c.res_pitch;
-        if (c.tile_sums) c2.tile_sums = c.tile_sums + (size_t)p.n_main * ((c.H + 3) / 4) * ((c.W + 3) / 4) * L.cout_pad;
+        ConvCall c1, c2;
+        tail_split_calls(L, c, p, &c1, &c2);
+        if (h->conv_rec) {
+            ffr_conv_launch r{};
+            r.path = FFR_CP_TAIL_SPLIT; r.images = c.N; r.rows = c.N * ((c.H + 3) / 4) * ((c.W + 3) / 4);
+            r.n_main = p.n_main; r.side = p.side ? 1 : 0; r.half_n = p.half_n ? 1 : 0; r.phased = p.phased ? 1 : 0; r.split = p.split ? 1 : 0;
+            h->conv_log.push_back(r);
+        }
         if (p.side) {
             HIPCK(h, hipEventRecord(h->ev_fork, st));
             HIPCK(h, hipStreamWaitEvent(p.side, h->ev_fork, 0));

@@ -863,6 +863,150 @@ int ffr_op_conv3x3(ffr_handle* h, const float* x, int N, int H, int W, int cin, 
     return rc;
 }
 
+int ffr_op_conv3x3_ex(ffr_handle* h, const ffr_conv3x3_desc* d, void* stream) {
+    if (!d) return fail(h, FFR_ERR_ARG, "ffr_op_conv3x3_ex: desc is null");
+    FFR_DEVICE_SCOPE(h); RC(check_fwd(h, false, false, d->N));
+    const int cin = d->cin, cout = d->cout;
+    if (!d->x || !d->w_host || !d->bias_host || !d->out || cin <= 0 || cin % 32 || cout <= 0 || d->H <= 0 || d->W <= 0 || d->N > 700)
+        return fail(h, FFR_ERR_ARG, "ffr_op_conv3x3_ex: bad arguments (null tensor, cin %% 32, N <= 700)");
+    if (d->use_wino < -1 || d->use_wino > 5) return fail(h, FFR_ERR_ARG, "ffr_op_conv3x3_ex: use_wino must be -1..5");
+    if (!d->in_scale_host != !d->in_shift_host || (d->in_scale_host && d->pad_mode != 0))
+        return fail(h, FFR_ERR_ARG, "ffr_op_conv3x3_ex: in_scale and in_shift come together, with zero padding");
+    const int in_pitch = d->in_pitch ? d->in_pitch : cin, out_pitch = d->out_pitch ? d->out_pitch : cout;
+    const int res_pitch = d->res_pitch ? d->res_pitch : cout, cout_store = d->cout_store ? d->cout_store : cout;
+    if (in_pitch < cin || in_pitch % 4 || cout_store < 1 || cout_store > cout || d->out_coff < 0 || d->out_coff + cout_store > out_pitch ||
+        (d->resid && res_pitch < cout_store) || (d->pad_mode != 0 && d->pad_mode != 1))
+        return fail(h, FFR_ERR_ARG, "ffr_op_conv3x3_ex: bad pitches (in_pitch >= cin and %% 4, out_coff + cout_store <= out_pitch, res_pitch >= cout_store)");
+    hipStream_t st = (hipStream_t)stream;
+    Work w;
+    RC(ensure_arena(h, d->N > 8 ? d->N : 8, 112, 112, &w));
+    std::vector<void*> own;
+    BNFold ob, ib;
+    ob.s.assign(cout, 1.0);
+    ob.t.assign(d->bias_host, d->bias_host + cout);
+    if (d->in_scale_host) { ib.s.assign(d->in_scale_host, d->in_scale_host + cin); ib.t.assign(d->in_shift_host, d->in_shift_host + cin); }
+    ConvW L;
+    const ConvForce force = (ConvForce)d->use_wino;
+    int rc = pack_conv(h, own, d->w_host, cout, cin, 3, 3, d->in_scale_host ? &ib : nullptr, &ob, d->slope_host, 1, 1, d->pad_mode, &L);
+    if (rc == FFR_OK && force != ConvForce::Direct && !L.wu) rc = fail(h, FFR_ERR_UNSUPPORTED, "layer not eligible for the Winograd path (cin < FFR_WINO_MINCIN)");
+    if (rc == FFR_OK && force == ConvForce::FusedSplit && !L.wu3)
+        rc = fail(h, FFR_ERR_UNSUPPORTED, "the split-operand fused form needs cin <= wf_phased_maxk (%d) and room for its weight planes", h->opt.wf_phased_maxk);
+    if (rc == FFR_OK && force == ConvForce::Mixed) {
+        if (((out_pitch | d->out_coff | res_pitch | cout_store) & 3) != 0) rc = fail(h, FFR_ERR_UNSUPPORTED, "the mixed-tile path stores whole channel quads: out_pitch, out_coff, res_pitch and cout_store must be multiples of 4");
+        else if (!wino_mixed_eligible(h, L, d->N, d->H, d->W, in_pitch, w.wino_cap, ConvForce::Mixed)) rc = fail(h, FFR_ERR_UNSUPPORTED, "layer / map not eligible for the mixed-tile path");
+        else rc = ensure_mixed_weights(h, L, own, true);
+    }
+    if (rc == FFR_OK) {
+        ConvCall c = conv_call(w, force);
+        c.x = d->x; c.N = d->N; c.H = d->H; c.W = d->W; c.in_pitch = in_pitch; c.resid = d->resid; c.res_pitch = res_pitch;
+        c.out = d->out; c.out_pitch = out_pitch; c.out_coff = d->out_coff; c.cout_store = cout_store; c.flags = d->flags & 1;
+        c.tile_sums = d->tile_sums;
+        // the form that was asked for runs, or the call fails: the planner's fall-backs (a scratch that is too small sends a
+        // Winograd convolution to the direct kernel) are the product's, not this hook's
+        const ConvPlan p = plan_conv(h, L, c);
+        const ConvPlan::Path want = force == ConvForce::Direct ? ConvPlan::Direct : force == ConvForce::Mixed ? ConvPlan::Mixed
+                                  : force == ConvForce::Unfused ? ConvPlan::Unfused : ConvPlan::Fused;
+        if (p.refused) rc = fail(h, FFR_ERR_STATE, "%s", p.refused);
+        else if (force == ConvForce::Auto ? p.path == ConvPlan::Direct : p.path != want)
+            rc = fail(h, FFR_ERR_UNSUPPORTED, "ffr_op_conv3x3_ex: the planner cannot run this descriptor in the form asked for (Winograd scratch too small for the shape?)");
+        else if (c.tile_sums && p.path == ConvPlan::Direct) rc = fail(h, FFR_ERR_UNSUPPORTED, "tile_sums come from the Winograd paths only");
+        else rc = run_conv(h, L, c, st);
+    }
+    hipStreamSynchronize(st);      // the packed weights die with this call
+    if (h->side) hipStreamSynchronize(h->side);
+    free_list(own);
+    return rc;
+}
+
+int ffr_conv_plan_record(ffr_handle* h, int on) {
+    if (!h) return fail(nullptr, FFR_ERR_ARG, "null handle");
+    h->conv_rec = on != 0;
+    if (on) h->conv_log.clear();
+    return FFR_OK;
+}
+
+int ffr_conv_plan_read(ffr_handle* h, ffr_conv_launch* out, int cap, int* n) {
+    if (!h || !n || cap < 0 || (cap > 0 && !out)) return fail(h, FFR_ERR_ARG, "ffr_conv_plan_read: bad arguments");
+    *n = (int)h->conv_log.size();
+    for (int i = 0; i < *n && i < cap; ++i) out[i] = h->conv_log[i];
+    return FFR_OK;
+}
+
+int ffr_plan_igemm_host(long long M, int cout_pad, int nkt, int nbatch, int force_tile, int min_units, int split, int count,
+                        int* tile, int* nblocks, int* granule) {
+    if (M < 1 || cout_pad < 64 || cout_pad % 64 || nkt < 1 || nbatch < 1 || min_units < 1 || count < 1 || !tile || !nblocks || !granule ||
+        force_tile < 0 || force_tile > IGEMM_NTILES)
+        return FFR_ERR_ARG;
+    if (force_tile) {
+        int bm, bn;
+        igemm_tile_shape(force_tile, &bm, &bn);
+        if (cout_pad % bn) return FFR_ERR_ARG;
+    }
+    for (int i = 0; i < count; ++i) plan_igemm(M + i, cout_pad, nkt, nbatch, force_tile, min_units, &tile[i], &nblocks[i], &granule[i], split != 0);
+    return FFR_OK;
+}
+
+int ffr_plan_conv_host(int cin, int cout, int R, int stride, int pad, int pad_mode, int has_wino, int has_wu3, int has_w3,
+                       int has_mixed, int N, int H, int W, int in_pitch, int out_pitch, int out_coff, int cout_store,
+                       int res_pitch, int num_cus, int force, long long* out) {
+    if (cin < 1 || cout < 1 || R < 1 || stride < 1 || pad < 0 || N < 1 || H < 1 || W < 1 || num_cus < 1 || force < -1 || force > 5 || !out)
+        return FFR_ERR_ARG;
+    static float mark[16];          // presence flags: the planner compares and tests the weight pointers, it never reads through them
+    ffr_handle fh;
+    fh.num_cus = num_cus;
+    fh.side = (hipStream_t)(void*)&mark[15];
+    ConvW L;
+    L.cin = cin; L.cin_pad = round_up(cin, 32); L.cout = cout; L.cout_pad = round_up(cout, 64);
+    L.R = R; L.S = R; L.stride = stride; L.pad = pad; L.pad_mode = pad_mode;
+    L.w = &mark[0];
+    if (has_wino) { L.wu = &mark[1]; L.wuc = &mark[2]; }
+    if (has_wu3) L.wu3 = (unsigned short*)&mark[3];
+    if (has_w3) L.w3 = (unsigned short*)&mark[4];
+    if (has_mixed) { L.wum[0] = L.wuc; L.wum[1] = &mark[5]; L.wum[2] = &mark[6]; L.wum[3] = &mark[7]; }
+    const int Na = N > 8 ? N : 8;
+    Work w = layout(fh.opt, nullptr, Na, 112, 112);
+    w.tickets_cap = (size_t)Na * 112 * 112 / 64 + 4096;
+    w.winoV = &mark[8]; w.winoM = &mark[9];
+    ConvCall c = conv_call(w, (ConvForce)force);
+    c.N = N; c.H = H; c.W = W; c.in_pitch = in_pitch ? in_pitch : L.cin_pad; c.out_pitch = out_pitch ? out_pitch : L.cout_pad;
+    c.out_coff = out_coff; c.cout_store = cout_store ? cout_store : cout; c.res_pitch = res_pitch ? res_pitch : L.cout_pad;
+    for (int i = 0; i < 24; ++i) out[i] = 0;
+    // one launch of the plan of call cc: kind, fits, tile, nblocks, granule, cut
+    auto describe = [&](const ConvCall& cc, const ConvPlan& p, long long* o) {
+        const long long T = (long long)cc.N * ((cc.H + 3) / 4) * ((cc.W + 3) / 4);
+        if (p.refused) { o[0] = 0; o[1] = 0; return; }
+        if (p.path == ConvPlan::Direct) {
+            const long long Ho = (cc.H + 2 * L.pad - L.R) / L.stride + 1, Wo = (cc.W + 2 * L.pad - L.S) / L.stride + 1;
+            const GemmPlan g = plan_gemm_launch(cc.N * Ho * Wo, L.cout_pad, L.R * L.S * L.cin_pad / 32, 1, cc.tile, fh.opt.sk_minunits,
+                                                L.w3 && fh.opt.igemm_split, cc.partial_cap, cc.tickets_cap);
+            o[0] = 1; o[1] = g.nomem ? 0 : 1; o[2] = g.tile; o[3] = g.nblocks; o[4] = g.granule; o[5] = g.cut;
+        } else if (p.path == ConvPlan::Fused) {
+            o[0] = 2; o[1] = p.phased || wino_chunked_floats(T, L.cin_pad) <= cc.wino_cap;
+        } else if (p.path == ConvPlan::Unfused) {
+            int gt, gb;
+            plan_gemm_stream(T, L.cout_pad, &gt, &gb);
+            o[0] = 3; o[1] = (size_t)36 * T * L.cin_pad <= cc.wino_cap && (size_t)36 * T * L.cout_pad <= cc.wino_cap; o[2] = gt; o[3] = gb;
+        } else {
+            WinoMixedGeom g;
+            o[0] = 4; o[1] = wino_mixed_geom(cc.H, cc.W, &g) && wino_mixed_v_floats(g, cc.N, L.cin_pad, nullptr) <= cc.wino_cap;
+        }
+    };
+    const ConvPlan p = plan_conv(&fh, L, c);
+    out[0] = p.path == ConvPlan::Direct ? 0 : p.path == ConvPlan::Mixed ? 1 : p.path == ConvPlan::Fused ? 2 : 3;
+    out[1] = p.half_n; out[2] = p.phased; out[3] = p.split; out[4] = p.n_main; out[5] = p.side != nullptr; out[6] = p.takes_v;
+    out[7] = p.refused != nullptr;
+    out[8] = ((H + 3) / 4) * ((W + 3) / 4);
+    if (p.path == ConvPlan::Fused && p.n_main) {     // the two calls of run_conv's tail-split arm
+        ConvCall c1, c2;
+        tail_split_calls(L, c, p, &c1, &c2);
+        describe(c1, plan_conv(&fh, L, c1), out + 9);
+        describe(c2, plan_conv(&fh, L, c2), out + 15);
+    } else {
+        describe(c, p, out + 9);
+    }
+    return FFR_OK;
+}
+
 int ffr_encoder_trunk_nhwc(ffr_handle* h, const float* x, int N, int H, int W, int n_blocks, float* out, void* stream) {
     FFR_DEVICE_SCOPE(h); RC(check_fwd(h, true, false, N));
     if (!x || !out || n_blocks < 0 || n_blocks > (int)h->blocks.size()) return fail(h, FFR_ERR_ARG, "ffr_encoder_trunk_nhwc: bad arguments");

@@ -128,6 +128,9 @@ struct ffr_handle {
     ffr_eng::TrainState* train = nullptr;
     // weight-gradient launch plans of the most recent backward (ffr_train_wgrad_plan)
     std::vector<ffr_wgrad_launch> wgrad_log;
+    // plan record of the convolution launchers (ffr_conv_plan_record / ffr_conv_plan_read): filled by run_conv's launchers while on
+    bool conv_rec = false;
+    std::vector<ffr_conv_launch> conv_log;
     // bumped whenever device memory a caller may have captured (hipGraph) moves: every allocation of grow(), weight
     // reload, ffr_train_init
     unsigned long long generation = 1;
@@ -242,7 +245,10 @@ struct ConvCall {
     int wino_stage = 0;                            // 0 whole conv; 1 stop after the GEMM (M stays in winoM); 2 V is ready in winoV
     bool v_mixed = false;                          // with wino_stage 2: V is in the four-region layout of wino_mixed.hip (k_combine_in_mixed wrote it)
     bool v_chunked = false;                        // with wino_stage 2: V is in the K-chunked fragment order of k_wino_fused (ConvPlan::takes_v)
-    float* tile_sums = nullptr;                    // Winograd paths only: per-tile sums of the stored outputs [T][cout_pad]
+    // Winograd paths only: per-tile sums of the stored outputs [T][cout_pad].  One rule for every kernel and every store path
+    // (vector or scalar stores, any pitch, cout_store < cout_pad): entry (tile, channel) is the sum of exactly the values this
+    // call stored to `out` for that channel over the tile's pixels inside the map; a channel that is not stored gets 0.
+    float* tile_sums = nullptr;
 };
 
 // Which kernels one convolution launches and how (plan_conv; run_conv's conv_* launch each path)
@@ -266,9 +272,13 @@ ConvPlan plan_conv(const ffr_handle* h, const ConvW& L, const ConvCall& c);
 void plan_igemm(long long M, int cout_pad, int nkt, int nbatch, int force_tile, int min_units, int* tile, int* nblocks, int* granule,
                 bool split = false);
 void plan_gemm_stream(long long T, int cout_pad, int* tile, int* nblocks);
+struct GemmPlan { int tile, nblocks, granule, mtiles, ntiles; long long units; bool cut; const char* nomem; };
+GemmPlan plan_gemm_launch(long long M, int cout_pad, int nkt, int nbatch, int force_tile, int min_units, bool split, size_t partial_cap,
+                          size_t tickets_cap);
 // conv.cpp
 int run_gemm(ffr_handle* h, IgemmArgs& a, const ConvCall& c, double flops, double bytes, hipStream_t st, double fuse = -1.0);
 int run_conv(ffr_handle* h, const ConvW& L, const ConvCall& c, hipStream_t st);
+void tail_split_calls(const ConvW& L, const ConvCall& c, const ConvPlan& p, ConvCall* c1, ConvCall* c2);
 
 // Hands out 256-byte aligned pieces of one buffer; on a null base it only measures (off = the bytes the pieces need)
 struct Arena {

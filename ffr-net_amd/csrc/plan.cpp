@@ -179,6 +179,23 @@ void plan_igemm(long long M, int cout_pad, int nkt, int nbatch, int force_tile, 
     *nblocks = (int)p;
 }
 
+// plan_igemm for one launch, with what follows from it: the tile grid, whether any tile is cut (the in-launch fix-up runs) and
+// whether the stream-K scratch of the call holds it (nomem: which piece does not).  run_gemm launches exactly this.
+GemmPlan plan_gemm_launch(long long M, int cout_pad, int nkt, int nbatch, int force_tile, int min_units, bool split, size_t partial_cap,
+                          size_t tickets_cap) {
+    GemmPlan g{};
+    plan_igemm(M, cout_pad, nkt, nbatch, force_tile, min_units, &g.tile, &g.nblocks, &g.granule, split);
+    int bm, bn;
+    igemm_tile_shape(g.tile, &bm, &bn);
+    g.mtiles = (int)((M + bm - 1) / bm);
+    g.ntiles = cout_pad / bn;
+    g.units = (long long)nbatch * g.mtiles * g.ntiles * nkt;
+    g.cut = g.granule == 1 && ((g.units % g.nblocks) != 0 || ((g.units / g.nblocks) % nkt) != 0);
+    if (g.cut && (size_t)g.nblocks * 2 * bm * bn > partial_cap) g.nomem = "stream-K workspace too small";
+    else if ((size_t)nbatch * g.mtiles * g.ntiles > tickets_cap) g.nomem = "stream-K ticket array too small";
+    return g;
+}
+
 // Tile shape and block count of k_gemm_stream for the 36 GEMMs [T x K] * [K x cout_pad] of a Winograd convolution: fewest
 // rounds of whole tiles over the resident blocks, weighted by loop efficiency.
 void plan_gemm_stream(long long T, int cout_pad, int* tile, int* nblocks) {

@@ -260,6 +260,9 @@ __device__ __forceinline__ void fused_mixed_body(const WinoMixedArgs& a, int tau
         int n = 0, q = 0, r0 = 0, c0 = 0;
         if (valid) mixed_tile<MR, MC>(a.g, t, &n, &q, &r0, &c0);
         wf_tile_record(s_tile + tid * 8, valid, n, r0, c0, MR, MC, a.H, a.W);
+        // tile-sum slot: image n owns tpi_total consecutive slots, the tile types in the order (4,4), (4,3), (3,4), (3,3) (tpi_off),
+        // the tiles of a type in raster order of that type's own grid (q).  plan_conv sends only whole channel quads here
+        // (cout_store % 4 == 0), so a quad is stored and summed entirely or not at all (its sums are 0): ConvCall::tile_sums
         s_tile[tid * 8 + 4] = valid ? n * a.tpi_total + a.tpi_off[tau] + q : 0;
     }
     f32x16 acc[8][NT], accv[NT];

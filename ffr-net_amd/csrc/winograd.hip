@@ -148,6 +148,7 @@ __global__ __launch_bounds__(256) void k_wino_out(const WinoOutArgs a) {
                         if (a.resid) s += a.resid[m * a.res_pitch + c4 + e];
                         if (a.flags & 1) s = 1.0f / (1.0f + __expf(-s));
                         a.out[m * a.out_pitch + a.out_coff + c4 + e] = s;
+                        psum[e] += s;         // tile sums are the sums of what was stored, on this path too (ConvCall::tile_sums)
                     }
                 }
             }

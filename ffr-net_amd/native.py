@@ -61,6 +61,22 @@ class WgradLaunch(C.Structure):
         'accumulate')]
 
 
+class Conv3x3Desc(C.Structure):
+    _fields_ = [('x', C.c_void_p), ('N', C.c_int), ('H', C.c_int), ('W', C.c_int), ('cin', C.c_int), ('in_pitch', C.c_int),
+                ('w_host', C.c_void_p), ('bias_host', C.c_void_p), ('slope_host', C.c_void_p), ('cout', C.c_int),
+                ('in_scale_host', C.c_void_p), ('in_shift_host', C.c_void_p),
+                ('resid', C.c_void_p), ('res_pitch', C.c_int),
+                ('out', C.c_void_p), ('out_pitch', C.c_int), ('out_coff', C.c_int), ('cout_store', C.c_int),
+                ('pad_mode', C.c_int), ('use_wino', C.c_int), ('flags', C.c_int),
+                ('tile_sums', C.c_void_p)]
+
+
+class ConvLaunch(C.Structure):
+    _fields_ = [(f, C.c_int) for f in ('path', 'images', 'rows', 'tile', 'nblocks', 'granule', 'nkt', 'tiles', 'cut', 'split',
+                                       'phased', 'half_n', 'block_tiles', 'n_main', 'side')]
+
+
+CONV_PATHS = ('direct', 'fused', 'unfused-gemm-stream', 'unfused-igemm', 'mixed', 'tail-split')
 WGRAD_PATHS = ('plain-taps9', 'plain-taps1', 'batched')
 ARITH = {'direct': 0, 'winograd': 1}
 CALIB_TENSORS = ('f', 'featmap', 'f_new', 'feat_new')
@@ -126,6 +142,11 @@ SYMBOLS = [
     ('ffr_profile_read', C.c_int, [_P, C.POINTER(KClassStat)]),
     ('ffr_op_conv', C.c_int, [_P, C.POINTER(ConvDesc), _P]),
     ('ffr_op_conv3x3', C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    ('ffr_op_conv3x3_ex', C.c_int, [_P, C.POINTER(Conv3x3Desc), _P]),
+    ('ffr_conv_plan_record', C.c_int, [_P, C.c_int]),
+    ('ffr_conv_plan_read', C.c_int, [_P, C.POINTER(ConvLaunch), C.c_int, C.POINTER(C.c_int)]),
+    ('ffr_plan_igemm_host', C.c_int, [C.c_longlong] + [C.c_int] * 7 + [_P, _P, _P]),
+    ('ffr_plan_conv_host', C.c_int, [C.c_int] * 20 + [_P]),
     ('ffr_encoder_trunk_nhwc', C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     ('ffr_recnet_debug', C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     # include/ffrnet_train.h
@@ -799,6 +820,48 @@ class Engine(object):
         out = self._empty(n, hh, ww, wh.size(0))
         self._call(self.lib.ffr_op_conv3x3, _ptr(x_nhwc), n, hh, ww, cin, _ptr(wh), _ptr(bh), _ptr(sh), wh.size(0), pad_mode,
                    int(use_wino), _ptr(resid.contiguous() if resid is not None else None), _ptr(out))
+        return out
+
+    def op_conv3x3_ex(self, x, w, bias, out, cin=None, slope=None, in_scale=None, in_shift=None, resid=None, out_coff=0,
+                      cout_store=0, pad_mode=0, use_wino=-1, sigmoid=False, tile_sums=None):
+        """The 3x3 / stride 1 / pad 1 convolution with the whole epilogue contract (test hook).  x [N,H,W,in_pitch], out
+        [N,H,W,out_pitch], resid [N,H,W,res_pitch] and tile_sums [T,cout_pad] are device tensors, written / read in place at
+        their own pitches; w [cout,cin,3,3], bias, slope, in_scale, in_shift host tensors.  use_wino -1: the planner's choice."""
+        for t, name in ((x, 'x'), (out, 'out')) + (((resid, 'resid'),) if resid is not None else ()) + \
+                (((tile_sums, 'tile_sums'),) if tile_sums is not None else ()):
+            self._tensor(t, name)
+            if not t.is_contiguous():
+                raise RuntimeError('ffrnet_amd: %s must be contiguous' % name)
+        host = [None if t is None else t.detach().float().cpu().contiguous() for t in (w, bias, slope, in_scale, in_shift)]
+        d = Conv3x3Desc()
+        d.x = x.data_ptr(); d.N, d.H, d.W, d.in_pitch = x.shape
+        d.cin = host[0].size(1) if cin is None else cin
+        d.w_host, d.bias_host, d.slope_host, d.in_scale_host, d.in_shift_host = [None if t is None else t.data_ptr() for t in host]
+        d.cout = host[0].size(0)
+        d.resid = resid.data_ptr() if resid is not None else None
+        d.res_pitch = resid.size(3) if resid is not None else 0
+        d.out = out.data_ptr(); d.out_pitch = out.size(3); d.out_coff = out_coff; d.cout_store = cout_store
+        d.pad_mode = pad_mode; d.use_wino = int(use_wino); d.flags = 1 if sigmoid else 0
+        d.tile_sums = tile_sums.data_ptr() if tile_sums is not None else None
+        self._call(self.lib.ffr_op_conv3x3_ex, C.byref(d))
+
+    def conv_plan_record(self, on=True):
+        """Switches the plan record of the convolution launchers on (clearing it) or off (test hook)."""
+        self._ck(self.lib.ffr_conv_plan_record(self._h, 1 if on else 0))
+
+    def conv_plan(self):
+        """The convolution launches since conv_plan_record(True), in launch order: [{path ('direct' | 'fused' |
+        'unfused-gemm-stream' | 'unfused-igemm' | 'mixed' | 'tail-split'), images, rows, tile, nblocks, granule, nkt, tiles, cut,
+        split, phased, half_n, block_tiles, n_main, side}] (include/ffrnet.h: ffr_conv_launch)."""
+        n = C.c_int(0)
+        self._ck(self.lib.ffr_conv_plan_read(self._h, None, 0, C.byref(n)))
+        arr = (ConvLaunch * max(n.value, 1))()
+        self._ck(self.lib.ffr_conv_plan_read(self._h, arr, n.value, C.byref(n)))
+        out = []
+        for i in range(n.value):
+            d = {f: getattr(arr[i], f) for f, _ in ConvLaunch._fields_}
+            d['path'] = CONV_PATHS[d['path']]
+            out.append(d)
         return out
 
     def op_convlayer_train(self, x_nhwc, G, w, gamma, beta, slope, da_nhwc, need_dx=True):

@@ -487,6 +487,65 @@ int ffr_op_conv3x3(ffr_handle* h, const float* x_nhwc, int N, int H, int W, int 
                    const float* w_host, const float* bias_host, const float* slope_host, int cout,
                    int pad_mode, int use_wino, const float* resid_nhwc, float* out_nhwc, void* stream);
 
+/* The same convolution with the whole epilogue contract of the Winograd kernels (test hook; the hook above stays as it is).
+ *   x [N,H,W,in_pitch] (in_pitch >= cin, cin % 32 == 0), out [N,H,W,out_pitch] with channels [out_coff, out_coff + cout_store)
+ *   written (cout_store <= cout; 0 = cout), resid [N,H,W,res_pitch] or NULL (res_pitch 0 = cout), flags bit0 = sigmoid.
+ *   use_wino -1 leaves the form to the planner (tail split included), 0..5 as above.
+ *   in_scale / in_shift [cin] (host, both or neither): a per-input-channel affine in front of the zero padding, folded by the
+ *   packer into the weights and the 9 border-class biases (pad_mode 0 only).
+ *   tile_sums [T][cout_pad] (device, optional; Winograd forms only): per-tile sums of the stored outputs, T = N * tiles per image
+ *   in raster order (the exact 14x14 tiling: slot n * tiles + offset of the tile type + index within the type, wino_mixed.hip).
+ * N <= 700.  A form that cannot honour the descriptor fails with the planner's reason (FFR_ERR_STATE / FFR_ERR_UNSUPPORTED);
+ * nothing else runs in its place. */
+typedef struct {
+    const float* x; int N, H, W, cin, in_pitch;
+    const float* w_host; const float* bias_host; const float* slope_host; int cout;
+    const float* in_scale_host; const float* in_shift_host;
+    const float* resid; int res_pitch;
+    float* out; int out_pitch, out_coff, cout_store;
+    int pad_mode, use_wino, flags;
+    float* tile_sums;
+} ffr_conv3x3_desc;
+int ffr_op_conv3x3_ex(ffr_handle* h, const ffr_conv3x3_desc* d, void* stream);
+
+/* ---- plan record of the convolution launchers (tests) ----------------------------
+ * While recording is on, every launch a convolution makes appends one entry, in launch order, as the launcher ran it: the
+ * values are taken where they are computed, not from a second copy of the rules.  Off by default (one branch on a bool per
+ * launch); switching it on clears the record; a convolution on a capturing stream is refused while it is on (FFR_ERR_STATE).
+ *   path    FFR_CP_DIRECT k_igemm | FFR_CP_FUSED k_wino_fused | FFR_CP_UNFUSED_STREAM k_gemm_stream between the transform kernels |
+ *           FFR_CP_UNFUSED_IGEMM batched k_igemm between them | FFR_CP_MIXED k_wino_fused_mixed | FFR_CP_TAIL_SPLIT: no launch, the
+ *           two entries that follow are the parts of one tail split (the part enqueued first comes first)
+ *   images, rows   images of this launch; GEMM rows M of a direct launch, Winograd tiles T otherwise
+ *   tile, nblocks, granule, nkt, tiles, cut, split   k_igemm / k_gemm_stream: tile config 1..4, persistent blocks, K-tiles a block
+ *           owns at least (1 or nkt), K-tiles per tile, tiles, 1 when a tile is cut (in-launch fix-up), split-operand form
+ *   phased, half_n, split, block_tiles   k_wino_fused: in-kernel input transform, 32 x 32 blocks, split-operand K loop, block tiles
+ *   n_main, side   FFR_CP_TAIL_SPLIT: images that run fused; 1 when the remainder went to the second stream */
+enum { FFR_CP_DIRECT = 0, FFR_CP_FUSED = 1, FFR_CP_UNFUSED_STREAM = 2, FFR_CP_UNFUSED_IGEMM = 3, FFR_CP_MIXED = 4, FFR_CP_TAIL_SPLIT = 5 };
+typedef struct ffr_conv_launch {
+    int path, images, rows;
+    int tile, nblocks, granule, nkt, tiles, cut, split;
+    int phased, half_n, block_tiles;
+    int n_main, side;
+} ffr_conv_launch;
+int ffr_conv_plan_record(ffr_handle* h, int on);
+int ffr_conv_plan_read(ffr_handle* h, ffr_conv_launch* out, int cap, int* n);
+
+/* ---- the planners on the host (no device, no handle; tests) ------------------------
+ * plan_igemm for `count` consecutive row counts M, M + 1, ...: tile[i], nblocks[i], granule[i] of k_igemm for [M + i rows] x
+ * [cout_pad] with nkt K-tiles per tile and nbatch GEMMs (force_tile 0 = the planner's choice, split != 0 = split-operand form). */
+int ffr_plan_igemm_host(long long M, int cout_pad, int nkt, int nbatch, int force_tile, int min_units, int split, int count,
+                        int* tile, int* nblocks, int* granule);
+/* plan_conv for one layer and one call under default options, with the scratch capacities of the workspace of N images of
+ * 112x112 (N >= 8).  Weight sets are presence flags: has_wino (Winograd weights, both orders), has_wu3 (planes of the fused
+ * split-operand loop), has_w3 (planes of the direct split-operand form), has_mixed (the exact-tiling sets).  force: -1..5.
+ * out[0..23]: [0..8] path (0 direct, 1 mixed, 2 fused, 3 unfused), half_n, phased, split, n_main, side, takes_v, refused,
+ *   tiles_img; [9..14] the launch, or the main part of a tail split, and [15..20] the remainder of a tail split (all 0 without
+ *   one), 6 values each: kind (0 none, 1 k_igemm, 2 k_wino_fused, 3 k_gemm_stream, 4 mixed), fits (every scratch the launch needs
+ *   is large enough), tile, nblocks, granule, cut; [21..23] spare. */
+int ffr_plan_conv_host(int cin, int cout, int R, int stride, int pad, int pad_mode, int has_wino, int has_wu3, int has_w3,
+                       int has_mixed, int N, int H, int W, int in_pitch, int out_pitch, int out_coff, int cout_store,
+                       int res_pitch, int num_cus, int force, long long* out);
+
 /* Encoder trunk only, stopping after `n_blocks` bottlenecks (0 = stem only,
  * 24 = whole body, before Backbone.bn); writes the NHWC activation.  Test hook for
  * the per-stage goldens.                                                            */
