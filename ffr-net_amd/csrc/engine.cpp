@@ -323,6 +323,67 @@ int ffr_topk_merge(ffr_handle* h, const float* score, const int64_t* index, int 
     return FFR_OK;
 }
 
+// ---- subject-labelled search (search.hip) ----------------------------------------------------------------------------------
+static bool misaligned4(const void* p) { return ((uintptr_t)p & 3) != 0; }
+
+int ffr_search_topk_subjects(ffr_handle* h, const float* query, int Q, const float* gallery, const float* gallery_norms,
+                             const int32_t* gallery_subject, long long G, int dim, int k, long long index_base, int distinct,
+                             float* top_score, int64_t* top_index, int32_t* top_subject, void* stream) {
+    FFR_DEVICE_SCOPE(h); RC(check_fwd(h, false, false, 1));
+    RC(check_dim(h, "ffr_search_topk_subjects", dim));
+    if (!query || !top_score || !top_index || !top_subject || Q < 1 || k < 1 || k > 128 || G < 0 ||
+        (G > 0 && (!gallery || !gallery_norms || !gallery_subject)))
+        return fail(h, FFR_ERR_ARG, "ffr_search_topk_subjects: bad arguments (Q >= 1, 1 <= k <= 128, G >= 0, non-null pointers)");
+    if (distinct != 0 && distinct != 1) return fail(h, FFR_ERR_ARG, "ffr_search_topk_subjects: distinct must be 0 or 1, got %d", distinct);
+    if (distinct && k > search_max_k_distinct())
+        return fail(h, FFR_ERR_ARG, "ffr_search_topk_subjects: identity mode serves k <= %d, got %d", search_max_k_distinct(), k);
+    if (misaligned16(query) || (G > 0 && misaligned16(gallery)))
+        return fail(h, FFR_ERR_ARG, "ffr_search_topk_subjects: query and gallery rows must be 16-byte aligned");
+    if (G > 0 && misaligned4(gallery_subject))
+        return fail(h, FFR_ERR_ARG, "ffr_search_topk_subjects: gallery_subject must be 4-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    if (G == 0) {                 // k slots of padding per probe: the merge of no list
+        Scope s(h, st, FFR_KC_SCORE, 0.0, 16.0 * Q * k);
+        HIPCK(h, launch_topk_merge_subjects(nullptr, nullptr, nullptr, 0, Q, k, distinct, top_score, top_index, top_subject, st));
+        return FFR_OK;
+    }
+    int T = 0, S = 0;
+    long long chunk_rows = 0;
+    search_plan(Q, G, h->num_cus, &T, &S, &chunk_rows);
+    // scratch: as ffr_search_topk, the chunk lists with a third plane [S][Q][k] of subjects
+    float* qnorm = nullptr;
+    float* part_s = top_score;
+    int64_t* part_i = top_index;
+    int32_t* part_u = top_subject;
+    RC(carve(h, h->search, "search", [&](Arena& a) {
+        qnorm = a.take(Q);
+        if (S > 1) {
+            part_s = a.take((size_t)S * Q * k); part_i = a.take<int64_t>((size_t)S * Q * k); part_u = a.take<int32_t>((size_t)S * Q * k);
+        }
+    }));
+    Scope s(h, st, FFR_KC_SCORE, 2.0 * Q * (double)G * dim, 4.0 * (double)G * (dim + 2) + 4.0 * Q * dim + 16.0 * Q * k);
+    HIPCK(h, launch_row_norms(query, Q, qnorm, st));
+    HIPCK(h, launch_search_subjects(query, qnorm, Q, gallery, gallery_norms, gallery_subject, G, k, index_base, distinct, T, S,
+                                    chunk_rows, part_s, part_i, part_u, st));
+    if (S > 1) HIPCK(h, launch_topk_merge_subjects(part_s, part_i, part_u, S, Q, k, distinct, top_score, top_index, top_subject, st));
+    return FFR_OK;
+}
+
+int ffr_topk_merge_subjects(ffr_handle* h, const float* score, const int64_t* index, const int32_t* subject, int S, int Q,
+                            int k, int distinct, float* out_score, int64_t* out_index, int32_t* out_subject, void* stream) {
+    FFR_DEVICE_SCOPE(h); RC(check_fwd(h, false, false, 1));
+    if (!score || !index || !subject || !out_score || !out_index || !out_subject || S < 1 || S > 4096 || Q < 1 || k < 1 || k > 128)
+        return fail(h, FFR_ERR_ARG,
+                    "ffr_topk_merge_subjects: bad arguments (1 <= S <= 4096, Q >= 1, 1 <= k <= 128, non-null pointers)");
+    if (distinct != 0 && distinct != 1) return fail(h, FFR_ERR_ARG, "ffr_topk_merge_subjects: distinct must be 0 or 1, got %d", distinct);
+    if (distinct && k > search_max_k_distinct())
+        return fail(h, FFR_ERR_ARG, "ffr_topk_merge_subjects: identity mode serves k <= %d, got %d", search_max_k_distinct(), k);
+    hipStream_t st = (hipStream_t)stream;
+    Scope s(h, st, FFR_KC_SCORE, 0.0, 16.0 * (double)S * Q * k + 16.0 * Q * k);
+    HIPCK(h, launch_topk_merge_subjects(score, index, subject, S, Q, k, distinct, out_score, out_index, out_subject, st));
+    return FFR_OK;
+}
+
 // ---- certified bf16 shortlist search (search_coarse.hip) -----------------------------------------------------------------
 int ffr_coarse_pack(ffr_handle* h, const float* rows, const float* norms, long long n, int dim, uint16_t* plane, int* plane_flag,
                     void* stream) {

@@ -243,6 +243,15 @@ hipError_t launch_search_topk(const float* query, const float* qnorm, int Q, con
 // S sorted lists [S][Q][k] -> [Q][k] (descending score, ties by ascending index; index < 0 = padding); S <= 4096; live as above
 hipError_t launch_topk_merge(const float* score, const int64_t* index, int S, int Q, int k, float* out_s, int64_t* out_i,
                              hipStream_t stream, const int* live = nullptr);
+// the same with subject[G] (< 0 = a removed row, never listed) and a third plane out_u of subjects; distinct: the lists hold
+// subjects, each by its best row, k <= search_max_k_distinct()
+int search_max_k_distinct();
+hipError_t launch_search_subjects(const float* query, const float* qnorm, int Q, const float* gallery, const float* gnorm,
+                                  const int32_t* subject, long long G, int k, long long index_base, int distinct, int ntiles,
+                                  int nchunks, long long chunk_rows, float* out_s, int64_t* out_i, int32_t* out_u,
+                                  hipStream_t stream);
+hipError_t launch_topk_merge_subjects(const float* score, const int64_t* index, const int32_t* subject, int S, int Q, int k,
+                                      int distinct, float* out_s, int64_t* out_i, int32_t* out_u, hipStream_t stream);
 
 // ---- certified bf16 shortlist search (search_coarse.hip) ------------------------------
 // rows the coarse pass lists per probe for a top-k (k <= coarse_max_k()), and the largest k it serves

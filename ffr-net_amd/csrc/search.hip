@@ -5,9 +5,13 @@
 // k_row_norms    |x| of [n][512] rows, one wave per row, the lane-strided sum of squares of k_cosine.
 // k_search_topk  the hot path: the exact instantiation of the search block of search_core.h, which describes it (the
 //                bf16 instantiation is k_search_coarse, search_coarse.hip).
+// k_search_subjects  the same block with a subject policy (ffr_search_topk_subjects): SR_LIVE ranks the rows that were not
+//                removed, SR_DISTINCT ranks subjects, each by its best row.
 // k_topk_merge   S sorted lists per probe -> one: one wave per probe, a k-step tournament over the list heads (wave
 //                argmax with the total order, lane as the last tie-break); the lists are staged in LDS when they fit.
 //                Slots with index < 0 are padding (-inf, -1) and sort after every real entry.
+// k_topk_merge_subjects  the same tournament with a subject per entry; in identity mode a winner whose subject was emitted
+//                before is dropped (lane p keeps the p-th emitted subject: one wave-wide compare), until k subjects are out.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -40,6 +44,7 @@ __global__ __launch_bounds__(256) void k_row_norms(const float* __restrict__ x, 
 }
 
 __global__ __launch_bounds__(256, 1) void k_search_topk(const SearchArgs a) { search_block<false>(a); }
+template <int SUBJ> __global__ __launch_bounds__(256, 1) void k_search_subjects(const SearchArgs a) { search_block<false, SUBJ>(a); }
 
 // (score, index) keys of the merge: padding (index < 0) sorts after everything
 __device__ __forceinline__ bool mg_beats(float s1, long long i1, int l1, float s2, long long i2, int l2) {
@@ -48,28 +53,37 @@ __device__ __forceinline__ bool mg_beats(float s1, long long i1, int l1, float s
     return l1 < l2;
 }
 
-__global__ __launch_bounds__(64) void k_topk_merge(const float* __restrict__ score, const int64_t* __restrict__ index, int S,
-                                                   int Q, int k, int staged, float* __restrict__ out_s,
-                                                   int64_t* __restrict__ out_i, const int* __restrict__ live) {
+// The merge of one probe's lists by one wave.  SUBJ: entries carry a subject (staged entries are 16 bytes, not 12), and with
+// `distinct` a popped winner is dropped when its subject is out already (k <= 64: lane p holds the p-th emitted subject).
+template <bool SUBJ>
+__device__ __forceinline__ void topk_merge_wave(const float* __restrict__ score, const int64_t* __restrict__ index,
+                                                const int32_t* __restrict__ subject, int S, int Q, int k, int staged, int distinct,
+                                                float* __restrict__ out_s, int64_t* __restrict__ out_i,
+                                                int32_t* __restrict__ out_u, const int* __restrict__ live) {
     extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
     const int q = blockIdx.x, lane = threadIdx.x;
     if (live && q >= *live) return;                       // a probe that was not searched: no lists, nothing to write
     int* hp = (int*)sm;                                   // head position of each list
     const float* ps;
     const int64_t* pi;
+    const int32_t* pu = nullptr;
     long long stride;                                     // elements between two lists
     if (staged) {
         int64_t* si = (int64_t*)(sm + (((size_t)S * 4 + 15) & ~(size_t)15));
         float* ss = (float*)(si + (size_t)S * k);
+        int32_t* su = (int32_t*)(ss + (size_t)S * k);
         for (int e = lane; e < S * k; e += 64) {
             const int l = e / k, p = e - l * k;
             const size_t o = ((size_t)l * Q + q) * k + p;
             ss[e] = score[o];
             si[e] = index[o];
+            if constexpr (SUBJ) su[e] = subject[o];
         }
         ps = ss; pi = si; stride = k;
+        if constexpr (SUBJ) pu = su;
     } else {
         ps = score + (size_t)q * k; pi = index + (size_t)q * k; stride = (long long)Q * k;
+        if constexpr (SUBJ) pu = subject + (size_t)q * k;
     }
     for (int l = lane; l < S; l += 64) hp[l] = 0;
     __syncthreads();
@@ -90,7 +104,8 @@ __global__ __launch_bounds__(64) void k_topk_merge(const float* __restrict__ sco
     };
     float bs; long long bi; int bl;
     lane_best(bs, bi, bl);
-    for (int p = 0; p < k; ++p) {
+    int p = 0, mine = -1;                                 // p entries are out; mine: the subject entry `lane` went out with
+    while (p < k) {
         float ws = bs; long long wi = bi; int wl = bl;
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
@@ -99,25 +114,51 @@ __global__ __launch_bounds__(64) void k_topk_merge(const float* __restrict__ sco
             const int l2 = __shfl_xor(wl, o);
             if (mg_beats(s2, i2, l2, ws, wi, wl)) { ws = s2; wi = i2; wl = l2; }
         }
-        const bool pad = wi == LLONG_MAX;
-        if (lane == 0) {
-            out_s[(size_t)q * k + p] = pad ? -INFINITY : ws;
-            out_i[(size_t)q * k + p] = pad ? (int64_t)-1 : (int64_t)wi;
+        if (wi == LLONG_MAX) break;                       // every list is exhausted: the rest is padding
+        bool out = true;
+        int wu = 0;
+        if constexpr (SUBJ) {
+            wu = pu[wl * stride + hp[wl]];
+            if (distinct) out = !__any(lane < p && mine == wu);
         }
-        if (pad) {                                        // every list is exhausted: the rest is padding
-            for (int r = p + 1 + lane; r < k; r += 64) { out_s[(size_t)q * k + r] = -INFINITY; out_i[(size_t)q * k + r] = -1; }
-            break;
+        if (out) {
+            if (lane == 0) {
+                out_s[(size_t)q * k + p] = ws;
+                out_i[(size_t)q * k + p] = (int64_t)wi;
+                if constexpr (SUBJ) out_u[(size_t)q * k + p] = wu;
+            }
+            if (lane == p) mine = wu;
+            ++p;
         }
-        if (wl < S && (wl & 63) == lane) {                // the lane that owns the winning list advances it
+        if ((wl & 63) == lane) {                          // the lane that owns the winning list advances it
             hp[wl] += 1;
             lane_best(bs, bi, bl);
         }
     }
+    for (int r = p + lane; r < k; r += 64) {
+        out_s[(size_t)q * k + r] = -INFINITY;
+        out_i[(size_t)q * k + r] = -1;
+        if constexpr (SUBJ) out_u[(size_t)q * k + r] = -1;
+    }
+}
+
+__global__ __launch_bounds__(64) void k_topk_merge(const float* __restrict__ score, const int64_t* __restrict__ index, int S,
+                                                   int Q, int k, int staged, float* __restrict__ out_s,
+                                                   int64_t* __restrict__ out_i, const int* __restrict__ live) {
+    topk_merge_wave<false>(score, index, nullptr, S, Q, k, staged, 0, out_s, out_i, nullptr, live);
+}
+
+__global__ __launch_bounds__(64) void k_topk_merge_subjects(const float* __restrict__ score, const int64_t* __restrict__ index,
+                                                            const int32_t* __restrict__ subject, int S, int Q, int k, int staged,
+                                                            int distinct, float* __restrict__ out_s, int64_t* __restrict__ out_i,
+                                                            int32_t* __restrict__ out_u) {
+    topk_merge_wave<true>(score, index, subject, S, Q, k, staged, distinct, out_s, out_i, out_u, nullptr);
 }
 
 }  // namespace
 
 long long search_max_chunk_rows() { return CT_MAX_CHUNK; }
+int search_max_k_distinct() { return SR_MAX_K_DISTINCT; }
 
 hipError_t launch_row_norms(const float* x, long long n, float* norms, hipStream_t stream) {
     if (n <= 0) return hipSuccess;
@@ -141,15 +182,47 @@ hipError_t launch_search_topk(const float* query, const float* qnorm, int Q, con
     return hipGetLastError();
 }
 
+hipError_t launch_search_subjects(const float* query, const float* qnorm, int Q, const float* gallery, const float* gnorm,
+                                  const int32_t* subject, long long G, int k, long long index_base, int distinct, int ntiles,
+                                  int nchunks, long long chunk_rows, float* out_s, int64_t* out_i, int32_t* out_u,
+                                  hipStream_t stream) {
+    SearchArgs a{query, qnorm, gallery, nullptr, gnorm, G, chunk_rows, index_base, out_s, out_i, nullptr, Q, k, nchunks, ntiles,
+                 subject, out_u};
+    const size_t lds = sr_lds_bytes(k, distinct != 0);
+    const void* fn = distinct ? (const void*)k_search_subjects<SR_DISTINCT> : (const void*)k_search_subjects<SR_LIVE>;
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    if (distinct) hipLaunchKernelGGL(k_search_subjects<SR_DISTINCT>, dim3((unsigned)(nchunks * ntiles)), dim3(256), lds, stream, a);
+    else hipLaunchKernelGGL(k_search_subjects<SR_LIVE>, dim3((unsigned)(nchunks * ntiles)), dim3(256), lds, stream, a);
+    return hipGetLastError();
+}
+
+// LDS of a merge: head positions [S], then the staged entries (`entry` bytes each) when they fit under MG_LDS_CAP
+static size_t merge_lds(int S, int k, int entry, int* staged) {
+    const size_t head = ((size_t)S * 4 + 15) & ~(size_t)15;
+    const size_t full = head + (size_t)S * k * entry;
+    *staged = S > 0 && full <= (size_t)MG_LDS_CAP;
+    return *staged ? full : head;
+}
+
 hipError_t launch_topk_merge(const float* score, const int64_t* index, int S, int Q, int k, float* out_s, int64_t* out_i,
                              hipStream_t stream, const int* live) {
-    const size_t head = ((size_t)S * 4 + 15) & ~(size_t)15;
-    const size_t full = head + (size_t)S * k * 12;
-    const int staged = S > 0 && full <= (size_t)MG_LDS_CAP;
-    const size_t lds = staged ? full : head;
+    int staged = 0;
+    const size_t lds = merge_lds(S, k, 12, &staged);
     hipError_t e = hipFuncSetAttribute((const void*)k_topk_merge, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MG_LDS_CAP);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_topk_merge, dim3((unsigned)Q), dim3(64), lds, stream, score, index, S, Q, k, staged, out_s, out_i, live);
+    return hipGetLastError();
+}
+
+hipError_t launch_topk_merge_subjects(const float* score, const int64_t* index, const int32_t* subject, int S, int Q, int k,
+                                      int distinct, float* out_s, int64_t* out_i, int32_t* out_u, hipStream_t stream) {
+    int staged = 0;
+    const size_t lds = merge_lds(S, k, 16, &staged);
+    hipError_t e = hipFuncSetAttribute((const void*)k_topk_merge_subjects, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MG_LDS_CAP);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_topk_merge_subjects, dim3((unsigned)Q), dim3(64), lds, stream, score, index, subject, S, Q, k, staged,
+                       distinct, out_s, out_i, out_u);
     return hipGetLastError();
 }
 

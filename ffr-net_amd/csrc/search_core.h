@@ -20,6 +20,13 @@
 //    of one chunk share that XCD's L2 and the chunk comes from HBM about once.
 //  - Live count: with a device pointer in SearchArgs::live, the probes [*live, Q) are not searched; blocks whose probe
 //    tile lies past the count leave at once.  A null pointer searches all Q.
+//  - Subjects (k_search_subjects, search.hip; include/ffrnet.h, ffr_search_topk_subjects): a compile-time policy.  SR_ROWS is
+//    the block above.  SR_LIVE reads subject[G] beside the norms and adds `subject >= 0` to the candidate test: removed rows
+//    never enter, the merge is the same, and the subject of a listed row is read again at write-out.  SR_DISTINCT lists
+//    subjects, not rows: candidates and list entries carry their subject in LDS, and the merge is the rank scatter over the
+//    elements that no other element of their own subject beats, so the list stays subject-unique and still does not depend
+//    on the order of arrival (no atomics here either).  The threshold argument holds: with k subjects listed, a row at or below the k-th score loses
+//    to k listed entries on score or index, or to its own subject's entry.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -31,6 +38,11 @@
 namespace ffr {
 
 constexpr int SR_CAND = 32;               // candidate slots per (probe, wave) and step
+constexpr int SR_MAX_K = 128;             // rows listed per probe (SR_ROWS, SR_LIVE)
+constexpr int SR_MAX_K_DISTINCT = 64;     // subjects listed per probe (SR_DISTINCT): see sr_lds_bytes
+constexpr int SR_NO_VICTIM = 255;         // SR_DISTINCT: a candidate that replaces no listed row (list positions are < 64)
+
+enum { SR_ROWS = 0, SR_LIVE = 1, SR_DISTINCT = 2 };     // the subject policy of a search block
 
 struct SearchArgs {
     const float* query;       // [Q][512]
@@ -45,6 +57,8 @@ struct SearchArgs {
     int64_t* out_i;
     const int* live;          // device, or null: the probes [*live, Q) are not searched (their tiles leave at once)
     int Q, k, nchunks, ntiles;
+    const int32_t* subject;   // [G], < 0 = a removed row (SR_LIVE, SR_DISTINCT)
+    int32_t* out_u;           // [S][Q][k] (SR_LIVE, SR_DISTINCT)
 };
 
 // The tile a search block scores with: the exact fp32 one of cosine_tile.h, or the bf16 one of coarse_tile.h
@@ -66,11 +80,21 @@ constexpr size_t SR_OFF_CN = SR_OFF_CR + CT_QT * CT_WAVES * SR_CAND;
 constexpr size_t SR_OFF_THR = SR_OFF_CN + CT_QT * CT_WAVES * 4;
 constexpr size_t SR_OFF_NL = SR_OFF_THR + CT_QT * 4;
 constexpr size_t SR_OFF_LIST = SR_OFF_NL + CT_QT * 4;
-__host__ __device__ constexpr size_t sr_lds_bytes(int k) { return SR_OFF_LIST + 2 * (size_t)CT_QT * k * 8; }
+// SR_DISTINCT adds, behind the lists: candidate subjects cu[32][4][32] i32 | two lists [32][k] of subjects | the candidates'
+// victims cv[32][4][32] u8.  One block per CU has 160 KiB: 71 424 + 512 k without subjects (136 960 at k = 128),
+// 91 904 + 768 k with them -- 141 056 at k = 64, and 190 208 at k = 128, which does not fit: SR_DISTINCT serves
+// k <= SR_MAX_K_DISTINCT.
+__host__ __device__ constexpr size_t sr_lds_bytes(int k, bool distinct = false) {
+    return SR_OFF_LIST + 2 * (size_t)CT_QT * k * 8 +
+           (distinct ? (size_t)CT_QT * CT_WAVES * SR_CAND * 5 + 2 * (size_t)CT_QT * k * 4 : 0);
+}
+static_assert(sr_lds_bytes(SR_MAX_K) <= 160 * 1024 && sr_lds_bytes(SR_MAX_K_DISTINCT, true) <= 160 * 1024 &&
+              sr_lds_bytes(SR_MAX_K, true) > 160 * 1024, "LDS of one search block");
 
 // One block of a search: k_search_topk (search.hip) is the exact instantiation, k_search_coarse (search_coarse.hip) the
-// bf16 one.  They differ in the tile alone; the threshold test, the survivor slots and the rank-scatter merge are this text.
-template <bool COARSE>
+// bf16 one, k_search_subjects (search.hip) the exact one with a subject policy.  They differ in the tile and in what the
+// policy adds; the threshold test, the survivor slots and the rank-scatter merge are this text.
+template <bool COARSE, int SUBJ = SR_ROWS>
 __device__ __forceinline__ void search_block(const SearchArgs& a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
     f32x4* qf = (f32x4*)sm;
@@ -81,6 +105,13 @@ __device__ __forceinline__ void search_block(const SearchArgs& a) {
     int* nl = (int*)(sm + SR_OFF_NL);
     float* ls0 = (float*)(sm + SR_OFF_LIST);              // list buffer b: scores at ls0 + b*QT*k, rows at li0 + b*QT*k
     int* li0 = (int*)(ls0 + 2 * CT_QT * a.k);
+    int *cu = nullptr, *lu0 = nullptr;                    // SR_DISTINCT: candidate subjects, the lists' subjects, victims
+    unsigned char* cv = nullptr;
+    if constexpr (SUBJ == SR_DISTINCT) {
+        cu = (int*)(sm + sr_lds_bytes(a.k));
+        lu0 = cu + CT_QT * CT_WAVES * SR_CAND;
+        cv = (unsigned char*)(lu0 + 2 * CT_QT * a.k);
+    }
 
     const int tid = threadIdx.x, lane = tid & 63, n = lane & 31, h = lane >> 5;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -105,6 +136,7 @@ __device__ __forceinline__ void search_block(const SearchArgs& a) {
     const float qn_lane = n < nq ? a.qnorm[q0 + n] : 0.f;
 
     const float* __restrict__ nch = a.gnorm + c0;
+    const int32_t* __restrict__ sch = SUBJ != SR_ROWS ? a.subject + c0 : nullptr;
     typename SearchTile<COARSE>::Stream gs(SearchTile<COARSE>::chunk(a, c0), lane);
     gs.prime(min(w * 32 + n, rows - 1));
     __syncthreads();
@@ -118,6 +150,11 @@ __device__ __forceinline__ void search_block(const SearchArgs& a) {
         float gn[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) gn[r] = nch[(unsigned)min(acc_row(sbase + w * 32, r) + 4 * h, rows - 1)];
+        int gu[SUBJ != SR_ROWS ? 16 : 1];        // and their subjects
+        if constexpr (SUBJ != SR_ROWS) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) gu[r] = sch[(unsigned)min(acc_row(sbase + w * 32, r) + 4 * h, rows - 1)];
+        }
         f32x16 acc;
         if constexpr (COARSE) {
             acc = gs.tile((const u32x4*)sm, next);
@@ -134,7 +171,9 @@ __device__ __forceinline__ void search_block(const SearchArgs& a) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             sc[r] = COARSE ? coarse_score(acc[r], qn_lane, gn[r]) : cosine_score(acc[r], qn_lane, gn[r]);
-            if (sbase + cosine_lane_row(w, r, h) < rows && sc[r] > t) mask |= 1u << r;
+            bool in = sbase + cosine_lane_row(w, r, h) < rows;
+            if constexpr (SUBJ != SR_ROWS) in = in && gu[r] >= 0;
+            if (in && sc[r] > t) mask |= 1u << r;
         }
         const int cnt = __builtin_popcount(mask);
         const int cnt0 = __shfl(cnt, n);         // the h = 0 lane of probe n goes first
@@ -146,13 +185,125 @@ __device__ __forceinline__ void search_block(const SearchArgs& a) {
             if (mask & (1u << r)) {
                 csq[slot] = sc[r];
                 crq[slot] = (unsigned char)cosine_lane_row(w, r, h);
+                if constexpr (SUBJ == SR_DISTINCT) cu[(n * CT_WAVES + w) * SR_CAND + slot] = gu[r];
                 ++slot;
             }
         if (h) cn[n * CT_WAVES + w] = cnt0 + cnt;
         if (!__syncthreads_or(cnt)) continue;
 
         // merge: rank scatter of list (cur) + candidates into list (cur ^ 1); 8 threads per probe
-        {
+        if constexpr (SUBJ == SR_DISTINCT) {
+            // The list holds a subject once, and its rows have smaller indices than every candidate.  A candidate is dead when a
+            // listed row of its subject scores as much, or another candidate of its subject beats it; the best candidate of a
+            // listed subject that scores more than the listed row kills that row (its victim).  The new list is the rank scatter
+            // of what is alive: rank = the rank of the row-mode merge less the dead rows in front.
+            const int q = tid >> 3, sub = tid & 7;
+            const int nL = nl[q];
+            int cw[CT_WAVES], m = 0;
+#pragma unroll
+            for (int v = 0; v < CT_WAVES; ++v) { cw[v] = cn[q * CT_WAVES + v]; m += cw[v]; }
+            const float* Ls = ls0 + (size_t)(cur * CT_QT + q) * k;
+            const int* Li = li0 + (size_t)(cur * CT_QT + q) * k;
+            int* Lu = lu0 + (size_t)(cur * CT_QT + q) * k;
+            float* Ns = ls0 + (size_t)((cur ^ 1) * CT_QT + q) * k;
+            int* Ni = li0 + (size_t)((cur ^ 1) * CT_QT + q) * k;
+            int* Nu = lu0 + (size_t)((cur ^ 1) * CT_QT + q) * k;
+            const float* csb = cs + q * CT_WAVES * SR_CAND;
+            const unsigned char* crb = cr + q * CT_WAVES * SR_CAND;
+            int* cub = cu + q * CT_WAVES * SR_CAND;
+            unsigned char* cvb = cv + q * CT_WAVES * SR_CAND;
+            // pass 1, candidates (x = sub + 8 i, i < 16): dead or alive, and the victim; written once every thread has looked
+            unsigned dead = 0;
+            int alive = 0, nvic = 0;
+            for (int x = sub, i = 0; x < m; x += 8, ++i) {
+                int c = x, v = 0;
+                while (c >= cw[v]) { c -= cw[v]; ++v; }
+                const float s = csb[v * SR_CAND + c];
+                const int lr = crb[v * SR_CAND + c], u = cub[v * SR_CAND + c];
+                bool d = false;
+                int victim = SR_NO_VICTIM;
+                // without a branch in the body, so that the reads of several rounds are in flight together: one wave per SIMD
+                // hides no LDS latency, and a merge costs what its dependent reads cost
+#pragma unroll 8
+                for (int j = 0; j < nL; ++j) {
+                    const bool mine = Lu[j] == u, ge = Ls[j] >= s;
+                    d |= mine & ge;
+                    victim = (mine & !ge) ? j : victim;
+                }
+                for (int v2 = 0; v2 < CT_WAVES; ++v2)
+#pragma unroll 4
+                    for (int c2 = 0; c2 < cw[v2]; ++c2) {
+                        const float s2 = csb[v2 * SR_CAND + c2];
+                        const bool mine = cub[v2 * SR_CAND + c2] == u;
+                        d |= mine & ((s2 > s) | ((s2 == s) & ((int)crb[v2 * SR_CAND + c2] < lr)));
+                    }
+                dead |= (unsigned)d << i;
+                cvb[v * SR_CAND + c] = (unsigned char)(d ? SR_NO_VICTIM : victim);     // nobody reads cv in this pass
+                alive += !d && victim == SR_NO_VICTIM;                                  // alive with a victim: one in, one out
+                nvic += !d && victim != SR_NO_VICTIM;
+            }
+            nvic += __shfl_xor(nvic, 1);                  // victims of this probe: none, most of the time
+            nvic += __shfl_xor(nvic, 2);
+            nvic += __shfl_xor(nvic, 4);
+            __syncthreads();
+            for (int x = sub, i = 0; x < m; x += 8, ++i) {
+                int c = x, v = 0;
+                while (c >= cw[v]) { c -= cw[v]; ++v; }
+                if (dead & (1u << i)) {                   // a dead candidate beats nothing from here on
+                    cub[v * SR_CAND + c] = -1;
+                    cs[q * CT_WAVES * SR_CAND + v * SR_CAND + c] = -INFINITY;
+                } else if (cvb[v * SR_CAND + c] != SR_NO_VICTIM) Lu[cvb[v * SR_CAND + c]] = -1;
+            }
+            __syncthreads();
+            // pass 2: the rank scatter of what is alive
+            for (int e = sub; e < nL + m; e += 8) {
+                float s;
+                int ri, u, rank, lr = 0;
+                if (e < nL) {
+                    u = Lu[e];
+                    if (u < 0) continue;
+                    s = Ls[e]; ri = Li[e];
+                    rank = e;
+                } else {
+                    int c = e - nL, v = 0;
+                    while (c >= cw[v]) { c -= cw[v]; ++v; }
+                    u = cub[v * SR_CAND + c];
+                    if (u < 0) continue;
+                    s = csb[v * SR_CAND + c];
+                    lr = crb[v * SR_CAND + c];
+                    ri = sbase + lr;
+                    int lo = 0, hi = nL;    // listed rows with a score >= s beat it (smaller index): binary search
+                    while (lo < hi) {
+                        const int mid = (lo + hi) >> 1;
+                        if (Ls[mid] >= s) lo = mid + 1; else hi = mid;
+                    }
+                    rank = lo;
+                }
+                const int before = rank;    // the listed rows in front, dead ones included
+                if (e < nL) lr = -1;        // a listed row loses no tie to a candidate
+                for (int v2 = 0; v2 < CT_WAVES; ++v2)
+#pragma unroll 4
+                    for (int c2 = 0; c2 < cw[v2]; ++c2) {
+                        const float s2 = csb[v2 * SR_CAND + c2];
+                        rank += (s2 > s) | ((s2 == s) & ((int)crb[v2 * SR_CAND + c2] < lr));
+                    }
+                if (nvic)
+                    for (int v2 = 0; v2 < CT_WAVES; ++v2)
+                        for (int c2 = 0; c2 < cw[v2]; ++c2) rank -= (int)cvb[v2 * SR_CAND + c2] < before;
+                if (rank < k) { Ns[rank] = s; Ni[rank] = ri; Nu[rank] = u; }
+            }
+            alive += __shfl_xor(alive, 1);
+            alive += __shfl_xor(alive, 2);
+            alive += __shfl_xor(alive, 4);
+            __syncthreads();
+            if (sub == 0) {
+                const int nn = min(k, nL + alive);
+                nl[q] = nn;
+                if (q < nq && nn == k) thr[q] = Ns[k - 1];
+            }
+            cur ^= 1;
+            __syncthreads();
+        } else {
             const int q = tid >> 3, sub = tid & 7;
             const int nL = nl[q];
             int cw[CT_WAVES], m = 0;
@@ -204,7 +355,7 @@ __device__ __forceinline__ void search_block(const SearchArgs& a) {
         }
     }
 
-    // one sorted list per (chunk, probe); empty slots are (-inf, -1)
+    // one sorted list per (chunk, probe); empty slots are (-inf, -1), and -1 for the subject
     const float* Ls = ls0 + (size_t)cur * CT_QT * k;
     const int* Li = li0 + (size_t)cur * CT_QT * k;
     const long long ib = a.index_base + c0;
@@ -214,6 +365,8 @@ __device__ __forceinline__ void search_block(const SearchArgs& a) {
         const size_t o = ((size_t)chunk * a.Q + q0 + q) * k + p;
         a.out_s[o] = ok ? Ls[q * k + p] : -INFINITY;
         a.out_i[o] = ok ? ib + Li[q * k + p] : (int64_t)-1;
+        if constexpr (SUBJ == SR_LIVE) a.out_u[o] = ok ? sch[(unsigned)Li[q * k + p]] : -1;
+        if constexpr (SUBJ == SR_DISTINCT) a.out_u[o] = ok ? lu0[(size_t)cur * CT_QT * k + q * k + p] : -1;
     }
 }
 

@@ -117,6 +117,9 @@ SYMBOLS = [
     ('ffr_row_norms', C.c_int, [_P, _P, C.c_longlong, C.c_int, _P, _P]),
     ('ffr_search_topk', C.c_int, [_P, _P, C.c_int, _P, _P, C.c_longlong, C.c_int, C.c_int, C.c_longlong, _P, _P, _P]),
     ('ffr_topk_merge', C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    ('ffr_search_topk_subjects', C.c_int, [_P, _P, C.c_int, _P, _P, _P, C.c_longlong, C.c_int, C.c_int, C.c_longlong, C.c_int, _P, _P, _P,
+                                           _P]),
+    ('ffr_topk_merge_subjects', C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     ('ffr_coarse_pack', C.c_int, [_P, _P, _P, C.c_longlong, C.c_int, _P, _P, _P]),
     ('ffr_search_topk_coarse', C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, C.c_longlong, C.c_int, C.c_int, C.c_longlong, _P, _P, _P, _P]),
     ('ffr_cluster_threshold', C.c_int, [_P, _P, _P, C.c_longlong, C.c_int, C.c_float, _P, _P]),
@@ -524,6 +527,59 @@ class Engine(object):
         out_s, out_i = self._empty(Q, k), self._empty(Q, k, dtype=torch.int64)
         self._call(self.lib.ffr_topk_merge, _ptr(scores), _ptr(index), S, Q, k, _ptr(out_s), _ptr(out_i))
         return out_s, out_i
+
+    # -- subject-labelled search (include/ffrnet.h: ffr_search_topk_subjects, ffr_topk_merge_subjects) -----------------
+    def _subjects(self, t, name, shape):
+        """int32 contiguous view or copy of subject ids (int32 or int64 on this Engine's device) of `shape`."""
+        if isinstance(t, torch.Tensor) and t.dtype == torch.int64:
+            self._tensor(t, name, torch.int64, shape)
+            return t.to(torch.int32).contiguous()
+        self._tensor(t, name, torch.int32, shape)
+        return t.contiguous()
+
+    def search_subjects(self, query, gallery, subjects, k, gallery_norms=None, index_base=0, distinct=True):
+        """search() over a gallery whose rows carry a subject id: subjects[G] int32 or int64, >= 0 = the row's subject,
+        < 0 = a removed row, which is never returned.  distinct=True (k <= 64): the top-k SUBJECTS, each once, by its best
+        row (maximum score, then smallest index); distinct=False (k <= 128): the top-k live rows
+        -> (scores[Q,k] fp32, index[Q,k] int64, subjects[Q,k] int32); (-inf, -1, -1) pads."""
+        self._tensor(query, 'query')
+        self._tensor(gallery, 'gallery')
+        if query.dim() != 2 or gallery.dim() != 2 or query.size(1) != gallery.size(1):
+            raise RuntimeError('ffrnet_amd: search_subjects expects query [Q,dim] and gallery [G,dim], got %s and %s'
+                               % (list(query.shape), list(gallery.shape)))
+        query, gallery = query.contiguous(), gallery.contiguous()
+        G = gallery.size(0)
+        subjects = self._subjects(subjects, 'subjects', (G,))
+        if gallery_norms is None:
+            gallery_norms = self.row_norms(gallery) if G else None
+        else:
+            self._tensor(gallery_norms, 'gallery_norms')
+            if tuple(gallery_norms.shape) != (G,):
+                raise RuntimeError('ffrnet_amd: gallery_norms must be [%d], got %s' % (G, list(gallery_norms.shape)))
+            gallery_norms = gallery_norms.contiguous()
+        Q, k = query.size(0), int(k)
+        scores, index = self._empty(Q, max(k, 0)), self._empty(Q, max(k, 0), dtype=torch.int64)
+        subj = self._empty(Q, max(k, 0), dtype=torch.int32)
+        self._call(self.lib.ffr_search_topk_subjects, _ptr(query), Q, _ptr(gallery if G else None), _ptr(gallery_norms),
+                   _ptr(subjects if G else None), G, query.size(1), k, int(index_base), int(bool(distinct)), _ptr(scores),
+                   _ptr(index), _ptr(subj))
+        return scores, index, subj
+
+    def topk_merge_subjects(self, scores, index, subjects, distinct=True):
+        """topk_merge() of lists that carry subjects: scores[S,Q,k] fp32, index[S,Q,k] int64, subjects[S,Q,k] int32 or
+        int64; distinct=True keeps the first entry of every subject -> (scores[Q,k], index[Q,k], subjects[Q,k])."""
+        self._tensor(scores, 'scores')
+        self._tensor(index, 'index', torch.int64)
+        if scores.dim() != 3 or tuple(index.shape) != tuple(scores.shape):
+            raise RuntimeError('ffrnet_amd: topk_merge_subjects expects scores, index and subjects [S,Q,k], got %s and %s'
+                               % (list(scores.shape), list(index.shape)))
+        S, Q, k = scores.shape
+        subjects = self._subjects(subjects, 'subjects', (S, Q, k))
+        scores, index = scores.contiguous(), index.contiguous()
+        out_s, out_i, out_u = self._empty(Q, k), self._empty(Q, k, dtype=torch.int64), self._empty(Q, k, dtype=torch.int32)
+        self._call(self.lib.ffr_topk_merge_subjects, _ptr(scores), _ptr(index), _ptr(subjects), S, Q, k, int(bool(distinct)),
+                   _ptr(out_s), _ptr(out_i), _ptr(out_u))
+        return out_s, out_i, out_u
 
     # -- clustering (include/ffrnet.h: ffr_cluster_threshold, ffr_cluster_templates) -----------------------------------
     def _cluster_rows(self, emb, norms, who):

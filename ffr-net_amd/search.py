@@ -12,6 +12,15 @@ A gallery spread over several processes (one per GPU) searches its shards with s
 Gallery(engine, coarse=True) keeps a bf16 plane beside the rows (1 KB per row more) and searches through the certified bf16
 shortlist (include/ffrnet.h: ffr_search_topk_coarse): the same results bit for bit, the pass over the gallery on the bf16
 matrix cores.  Gallery.last_certified says which probes of the last search the shortlist was proven for.
+
+Gallery(engine, subjects=True) keeps a subject id beside every row (include/ffrnet.h: ffr_search_topk_subjects): an enrolled
+person is several rows, and search_subjects() answers with the top-k PEOPLE, each once, by their best row:
+
+  gallery = Gallery(engine, subjects=True); gallery.add(f_enrol, subject_ids)
+  scores, subjects, index = gallery.search_subjects(f_probe, k=10)
+  rates = subject_rates(subjects, probe_labels)
+  gallery.remove([7, 12])                  # those people never come back, from search() either; rows keep their index
+  old_to_new = gallery.compact()           # drop the removed rows physically
 """
 import torch
 
@@ -38,15 +47,23 @@ class Gallery(object):
     """Enrolled embeddings [n,512] and their norms on the Engine's device, in a grow-only buffer: add() appends, rows
     keep their index for ever (the index search() returns).  coarse=True: a bf16 plane of the normalised rows and its
     unsafe-norm flag grow beside them, add() packs the rows it appends, and search() goes through the certified shortlist
-    (the same results; last_certified[Q] int32 tells which probes were certified)."""
+    (the same results; last_certified[Q] int32 tells which probes were certified).  subjects=True: a subject id (int32)
+    grows beside every row, add() takes the ids, search_subjects() ranks subjects, remove() withdraws subjects (their rows
+    stay in place, marked -1, and search() skips them) and compact() drops the removed rows."""
 
-    def __init__(self, engine, capacity=0, coarse=False):
+    def __init__(self, engine, capacity=0, coarse=False, subjects=False):
+        if coarse and subjects:
+            raise RuntimeError('ffrnet_amd: Gallery(coarse=True, subjects=True): the certified shortlist does not know '
+                               'subjects yet')
         self.engine = engine
         self._n = 0
         self._emb = torch.empty((int(capacity), DIM), device=engine.device, dtype=torch.float32)
         self._norms = torch.empty((int(capacity),), device=engine.device, dtype=torch.float32)
         self.coarse = bool(coarse)
         self.last_certified = None
+        self.has_subjects = bool(subjects)
+        if self.has_subjects:
+            self._subj = torch.empty((int(capacity),), device=engine.device, dtype=torch.int32)
         if self.coarse:
             self._plane = torch.empty((int(capacity), DIM), device=engine.device, dtype=torch.int16)
             self._flag = torch.zeros((1,), device=engine.device, dtype=torch.int32)
@@ -72,12 +89,41 @@ class Gallery(object):
         """int32 [1]: non-zero once a row with an unsafe norm was added; coarse galleries only."""
         return self._flag
 
-    def add(self, emb):
-        """Append emb[n,512] (fp32, on the Engine's device) -> the index of its first row."""
+    @property
+    def subjects(self):
+        """int32 [n]: the subject id of every row, -1 where the row was removed; galleries with subjects only."""
+        self._need_subjects('subjects')
+        return self._subj[:self._n]
+
+    def _need_subjects(self, what):
+        if not self.has_subjects:
+            raise RuntimeError('ffrnet_amd: Gallery.%s needs a gallery created with subjects=True' % what)
+
+    def _subject_ids(self, ids, what):
+        """int32 device tensor of subject ids, each in [0, 2^31)."""
+        ids = torch.as_tensor(ids)
+        if ids.dtype not in (torch.int32, torch.int64):
+            raise RuntimeError('ffrnet_amd: Gallery.%s expects int32 or int64 subject ids, got %s' % (what, ids.dtype))
+        ids = ids.reshape(-1).to(self._emb.device)
+        if ids.numel() and (int(ids.min().item()) < 0 or int(ids.max().item()) >= 2 ** 31):
+            raise RuntimeError('ffrnet_amd: Gallery.%s: subject ids must lie in [0, 2^31)' % what)
+        return ids.to(torch.int32)
+
+    def add(self, emb, subjects=None):
+        """Append emb[n,512] (fp32, on the Engine's device) -> the index of its first row.  A gallery with subjects
+        takes subjects[n] (int32 or int64, each in [0, 2^31)) as well."""
         if not isinstance(emb, torch.Tensor) or emb.dim() != 2 or emb.size(1) != DIM:
             raise RuntimeError('ffrnet_amd: Gallery.add expects [n,%d] embeddings, got %s'
                                % (DIM, list(emb.shape) if isinstance(emb, torch.Tensor) else type(emb)))
         n = emb.size(0)
+        if self.has_subjects:
+            if subjects is None:
+                raise RuntimeError('ffrnet_amd: Gallery.add: this gallery keeps subjects; pass subjects[n]')
+            subjects = self._subject_ids(subjects, 'add')
+            if subjects.numel() != n:
+                raise RuntimeError('ffrnet_amd: Gallery.add: %d rows but %d subject ids' % (n, subjects.numel()))
+        elif subjects is not None:
+            raise RuntimeError('ffrnet_amd: Gallery.add: subjects given to a gallery created without subjects=True')
         first = self._n
         if first + n > self._emb.size(0):
             cap = max(first + n, 2 * self._emb.size(0), 1024)
@@ -90,12 +136,18 @@ class Gallery(object):
                 plane_new = torch.empty((cap, DIM), device=self._emb.device, dtype=torch.int16)
                 plane_new[:first] = self._plane[:first]
                 self._plane = plane_new
+            if self.has_subjects:
+                subj_new = torch.empty((cap,), device=self._emb.device, dtype=torch.int32)
+                subj_new[:first] = self._subj[:first]
+                self._subj = subj_new
         if n:
             self._emb[first:first + n] = emb
             self._norms[first:first + n] = self.engine.row_norms(self._emb[first:first + n])
             if self.coarse:
                 self.engine.coarse_pack(self._emb[first:first + n], self._norms[first:first + n],
                                         self._plane[first:first + n], self._flag)
+            if self.has_subjects:
+                self._subj[first:first + n] = subjects
         self._n = first + n
         return first
 
@@ -107,7 +159,43 @@ class Gallery(object):
         s, i = self._search(query, int(k) + 1, index_base)
         return drop_self(s, i, torch.as_tensor(self_index, device=i.device) + int(index_base))
 
+    def search_subjects(self, query, k, index_base=0):
+        """Top-k enrolled SUBJECTS of every probe query[Q,512], each once, by its best row -> (scores[Q,k],
+        subjects[Q,k] int32, index[Q,k]); k <= 64; (-inf, -1, -1) pads when fewer than k subjects are enrolled."""
+        self._need_subjects('search_subjects')
+        s, i, u = self.engine.search_subjects(query, self.embeddings, self.subjects, k, gallery_norms=self.norms,
+                                              index_base=index_base, distinct=True)
+        return s, u, i
+
+    def remove(self, subject_ids):
+        """Withdraw subjects: every row of theirs is marked removed (-1) on the device and never returned again; rows keep
+        their index and len() does not change -> the number of rows removed."""
+        self._need_subjects('remove')
+        ids = self._subject_ids(subject_ids, 'remove')
+        live = self.subjects
+        hit = torch.isin(live, ids)
+        live[hit] = -1
+        return int(hit.sum().item())
+
+    def compact(self):
+        """Drop the removed rows physically: the live rows, their norms and ids move up unchanged (no norm is computed
+        again, so scores keep their bits) -> int64 [old len]: old index -> new index, -1 for a removed row."""
+        self._need_subjects('compact')
+        keep = self.subjects >= 0
+        new_index = torch.cumsum(keep.to(torch.int64), 0) - 1
+        new_index[~keep] = -1
+        n = int(keep.sum().item())
+        self._emb[:n] = self.embeddings[keep]
+        self._norms[:n] = self.norms[keep]
+        self._subj[:n] = self.subjects[keep]
+        self._n = n
+        return new_index
+
     def _search(self, query, k, index_base):
+        if self.has_subjects:           # row mode under the mask: removed rows never come back
+            s, i, _ = self.engine.search_subjects(query, self.embeddings, self.subjects, k, gallery_norms=self.norms,
+                                                  index_base=index_base, distinct=False)
+            return s, i
         if not self.coarse:
             return self.engine.search(query, self.embeddings, k, gallery_norms=self.norms, index_base=index_base)
         s, i, self.last_certified = self.engine.search_coarse(query, self.embeddings, self.plane, self._flag, k,
@@ -126,12 +214,17 @@ def drop_self(scores, index, self_index):
     return scores[keep].view(Q, k1 - 1), index[keep].view(Q, k1 - 1)
 
 
-def search_sharded(gallery_shard, query, k, group=None):
+def search_sharded(gallery_shard, query, k, group=None, distinct=None):
     """Search a gallery split in contiguous shards over the ranks of `group` (rank r holds rows that follow those of
     ranks < r): every rank passes its own Gallery and the SAME probes query[Q,512] and gets the global top-k.
     Index bases come from the gathered shard sizes; the per-rank [Q,k] lists travel in one all_gather_into_tensor and
-    every rank merges them (ffr_topk_merge).  Bitwise equal to one search over the concatenated gallery."""
+    every rank merges them (ffr_topk_merge).  Bitwise equal to one search over the concatenated gallery.
+    distinct=True, for shards with subjects: the top-k subjects, (scores, subjects, index) as Gallery.search_subjects
+    gives them; the exchange carries the subject as a fourth word and the merge is ffr_topk_merge_subjects.  The default
+    (None) and False give the row search of the shard: plain, or under the removal mask of a gallery with subjects."""
     eng = gallery_shard.engine
+    if distinct:
+        return _search_sharded_subjects(gallery_shard, query, k, group)
     if dist is None or not dist.is_available() or not dist.is_initialized() or dist.get_world_size(group) == 1:
         return gallery_shard.search(query, k)
     world, rank = dist.get_world_size(group), dist.get_rank(group)
@@ -149,6 +242,41 @@ def search_sharded(gallery_shard, query, k, group=None):
     all_s = allw[..., 0].contiguous().view(torch.float32)
     all_i = allw[..., 1:].contiguous().view(torch.int64).view(world, Q, kk)
     return eng.topk_merge(all_s, all_i)
+
+
+def _search_sharded_subjects(gallery_shard, query, k, group):
+    eng = gallery_shard.engine
+    if dist is None or not dist.is_available() or not dist.is_initialized() or dist.get_world_size(group) == 1:
+        return gallery_shard.search_subjects(query, k)
+    world, rank = dist.get_world_size(group), dist.get_rank(group)
+    sizes = torch.empty((world,), device=query.device, dtype=torch.int64)
+    dist.all_gather_into_tensor(sizes, torch.tensor([len(gallery_shard)], device=query.device, dtype=torch.int64),
+                                group=group)
+    base = int(sizes[:rank].sum().item())
+    s, u, i = gallery_shard.search_subjects(query, k, index_base=base)
+    Q, kk = s.shape
+    # one exchange: per slot the score's bits, the two halves of the index and the subject, as int32 words
+    mine = torch.cat((s.contiguous().view(torch.int32).view(Q, kk, 1), i.contiguous().view(torch.int32).view(Q, kk, 2),
+                      u.view(Q, kk, 1)), 2)
+    allw = torch.empty((world * Q, kk, 4), device=query.device, dtype=torch.int32)      # rank-major along dim 0
+    dist.all_gather_into_tensor(allw, mine.contiguous(), group=group)
+    allw = allw.view(world, Q, kk, 4)
+    all_s = allw[..., 0].contiguous().view(torch.float32)
+    all_i = allw[..., 1:3].contiguous().view(torch.int64).view(world, Q, kk)
+    out_s, out_i, out_u = eng.topk_merge_subjects(all_s, all_i, allw[..., 3].contiguous(), distinct=True)
+    return out_s, out_u, out_i
+
+
+def subject_rates(subjects, probe_labels, ranks=(1, 5, 10)):
+    """CMC over identity lists: the fraction of probes whose label is among their first r listed subjects, for every r in
+    ranks.  subjects[Q,k] (Gallery.search_subjects; -1 = padding, which never hits), probe_labels[Q] -> {r: rate}."""
+    subjects = torch.as_tensor(subjects)
+    pl = torch.as_tensor(probe_labels).to(subjects.device)
+    hit = (subjects == pl.reshape(-1, 1).to(subjects.dtype)) & (subjects >= 0)
+    out = {}
+    for r in ranks:
+        out[r] = float(hit[:, :r].any(1).double().mean().item()) if subjects.size(0) else 0.0
+    return out
 
 
 def identification_rates(index, probe_labels, gallery_labels, ranks=(1, 5, 10)):

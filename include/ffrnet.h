@@ -140,6 +140,41 @@ int ffr_search_topk(ffr_handle* h, const float* query, int Q, const float* galle
 int ffr_topk_merge(ffr_handle* h, const float* score, const int64_t* index, int S, int Q, int k,
                    float* out_score, int64_t* out_index, void* stream);
 
+/* ---- subject-labelled search (top-k identities in one pass, and removal) ----------------------------------------------
+ * An enrolled person is several gallery rows (images, a template, re-enrolments).  gallery_subject[G] (int32, device, 4-byte
+ * aligned) names the subject of every row: a value >= 0 is the subject the row belongs to; a value < 0 marks a REMOVED row,
+ * which is still read but is never a candidate and never appears in a result.
+ *   order  fix a probe q; s(q, g) is the score of ffr_search_topk, bit for bit.  Row g comes before row g' iff
+ *          s(q, g) > s(q, g'), or the scores are equal and g < g'.
+ *   rows   distinct = 0: the first k live rows in that order, 1 <= k <= 128.  With no removed row top_score and top_index
+ *          are those of ffr_search_topk, bit for bit.
+ *   identities  distinct = 1: best(u) is the first row of subject u in that order; the result is the first k of {best(u)},
+ *          1 <= k <= 64.  Every listed subject appears once, with its maximum score and the smallest index among the rows
+ *          that reach it.  The cap is the search block's LDS (160 KiB per CU, one block per CU): the block needs
+ *          71 424 + 512 k bytes to list rows and 20 480 + 256 k more to carry subjects -- 141 056 at k = 64, 190 208 at
+ *          k = 128.
+ *   result top_score[Q][k] fp32, top_index[Q][k] int64 (= index_base + gallery row), top_subject[Q][k] int32.  Slots beyond
+ *          the live rows (or subjects) hold (-inf, -1, -1).  G = 0 gives all padding.
+ *   shards searching contiguous shards (each with its index_base) and merging with ffr_topk_merge_subjects equals one
+ *          search, in both modes.  Identity mode: let u be in the global top k with best(u) in shard c.  Every subject that
+ *          beats u inside c does so with a row of c, so it beats u globally too; fewer than k do, and u is on c's list with
+ *          its global score and index.  Other shards may list u with a worse row; the merge keeps the first entry of a
+ *          subject and drops the later ones.  A subject outside the global top k is beaten by k subjects whose best rows
+ *          are all listed, so it cannot be emitted among the first k.
+ *   bitwise, memory, graphs: every guarantee of ffr_search_topk carries over -- results do not depend on Q, on the chunking
+ *          or on the sharding; no host synchronisation; the search scratch (probe norms, per-chunk lists with a subject
+ *          plane) grows on demand and is reused, so a call can be captured into a hipGraph once it has run at that shape.
+ * Errors are those of ffr_search_topk, and FFR_ERR_ARG for a NULL gallery_subject when G > 0, a gallery_subject that is not
+ * 4-byte aligned, a NULL top_subject, distinct outside {0, 1}, and k > 64 with distinct = 1.
+ * Profiled as one launch under FFR_KC_SCORE with flops = 2*Q*G*512.                                                      */
+int ffr_search_topk_subjects(ffr_handle* h, const float* query, int Q, const float* gallery, const float* gallery_norms,
+                             const int32_t* gallery_subject, long long G, int dim, int k, long long index_base,
+                             int distinct, float* top_score, int64_t* top_index, int32_t* top_subject, void* stream);
+/* ffr_topk_merge with a subject per entry (subject[S][Q][k]); distinct = 1 keeps the first entry of every subject and
+ * needs k <= 64.  Slots with index < 0 are padding.                                                                       */
+int ffr_topk_merge_subjects(ffr_handle* h, const float* score, const int64_t* index, const int32_t* subject, int S, int Q,
+                            int k, int distinct, float* out_score, int64_t* out_index, int32_t* out_subject, void* stream);
+
 /* ---- certified bf16 shortlist search -------------------------------------------------------------------------------------
  * ffr_search_topk_coarse gives the outputs of ffr_search_topk, bit for bit, for every input without NaN/inf; only the way
  * there differs.  The pass over the whole gallery runs on the bf16 matrix cores over a plane of half the bytes and picks a
