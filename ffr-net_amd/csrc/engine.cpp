@@ -1068,6 +1068,14 @@ int ffr_plan_conv_host(int cin, int cout, int R, int stride, int pad, int pad_mo
     return FFR_OK;
 }
 
+int ffr_plan_channel_rows_host(int N, int num_cus, int forced, int* row_blocks) {
+    if (N < 1 || num_cus < 1 || !row_blocks) return FFR_ERR_ARG;
+    const int rb = plan_channel_rows(N, num_cus, forced);
+    if (!rb) return FFR_ERR_ARG;
+    *row_blocks = rb;
+    return FFR_OK;
+}
+
 int ffr_encoder_trunk_nhwc(ffr_handle* h, const float* x, int N, int H, int W, int n_blocks, float* out, void* stream) {
     FFR_DEVICE_SCOPE(h); RC(check_fwd(h, true, false, N));
     if (!x || !out || n_blocks < 0 || n_blocks > (int)h->blocks.size()) return fail(h, FFR_ERR_ARG, "ffr_encoder_trunk_nhwc: bad arguments");
@@ -1082,14 +1090,15 @@ int ffr_encoder_trunk_nhwc(ffr_handle* h, const float* x, int N, int H, int W, i
 }
 
 int ffr_recnet_debug(ffr_handle* h, const float* featmap_nchw, int N, float* ss_space, float* M_space, float* feat_space,
-                     float* feat_channel_raw, float* feat_channel, float* ss_channel0, float* M_channel0, void* stream) {
+                     float* feat_channel_raw, float* feat_channel, float* ss_channel0, float* M_channel0, int image, void* stream) {
     FFR_DEVICE_SCOPE(h); RC(check_fwd(h, false, true, N));
     if (!featmap_nchw) return fail(h, FFR_ERR_ARG, "featmap is null");
+    if (image < 0 || image >= N) return fail(h, FFR_ERR_ARG, "ffr_recnet_debug: image %d is outside [0, %d)", image, N);
     hipStream_t st = (hipStream_t)stream;
     Work w;
     RC(ensure_arena(h, N, 112, 112, &w));
     RC(featmap_to_x(h, w, featmap_nchw, N, st));
-    RecDebug d{ss_space, M_space, feat_space, feat_channel_raw, feat_channel, ss_channel0, M_channel0};
+    RecDebug d{ss_space, M_space, feat_space, feat_channel_raw, feat_channel, ss_channel0, M_channel0, image};
     return run_recnet(h, w, N, nullptr, &d, st);
 }
 

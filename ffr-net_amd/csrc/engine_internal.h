@@ -272,6 +272,7 @@ ConvPlan plan_conv(const ffr_handle* h, const ConvW& L, const ConvCall& c);
 void plan_igemm(long long M, int cout_pad, int nkt, int nbatch, int force_tile, int min_units, int* tile, int* nblocks, int* granule,
                 bool split = false);
 void plan_gemm_stream(long long T, int cout_pad, int* tile, int* nblocks);
+int plan_channel_rows(int N, int num_cus, int forced);
 struct GemmPlan { int tile, nblocks, granule, mtiles, ntiles; long long units; bool cut; const char* nomem; };
 GemmPlan plan_gemm_launch(long long M, int cout_pad, int nkt, int nbatch, int force_tile, int min_units, bool split, size_t partial_cap,
                           size_t tickets_cap);
@@ -322,7 +323,7 @@ int run_trunk(ffr_handle* h, const Work& w, const float* x_nchw, int N, int H, i
               float** out_ptr, int* oh, int* ow, int* oc, const U8In* u8 = nullptr, const float* x2 = nullptr, int n_split = 0);
 int run_encoder(ffr_handle* h, const Work& w, const float* x, int N, int H, int W, float* featmap_nhwc, float* f,
                 hipStream_t st, const U8In* u8 = nullptr, const float* x2 = nullptr, int n_split = 0);
-struct RecDebug { float *ss_space, *M_space, *feat_space, *feat_channel_raw, *feat_channel, *ss_channel0, *M_channel0; };
+struct RecDebug { float *ss_space, *M_space, *feat_space, *feat_channel_raw, *feat_channel, *ss_channel0, *M_channel0; int image = 0; };   // ss_channel0 / M_channel0: of image `image`
 int conv_rec(ffr_handle* h, const Work& w, const ConvW& L, const float* x, int in_pitch, const float* resid,
              int res_pitch, float* out, int out_pitch, int out_coff, int flags, int N, hipStream_t st);
 int run_recnet(ffr_handle* h, const Work& w, int N, float* f_new, const RecDebug* dbg, hipStream_t st);

@@ -209,12 +209,11 @@ int conv_rec(ffr_handle* h, const Work& w, const ConvW& L, const float* x, int i
 
 #ifdef FFR_TRACE
 // k_channel_path with per-block phase stamps (option wf_trace): the launch, a stream sync, a summary on stderr
-static int trace_channel_path(ffr_handle* h, const Work& w, int N, hipStream_t st) {
+static int trace_channel_path(ffr_handle* h, const Work& w, int N, int rb, hipStream_t st) {
     unsigned long long* dbuf = nullptr;
     HIPCK(h, hipMalloc((void**)&dbuf, (size_t)N * 4 * 8 * sizeof(unsigned long long)));
     HIPCK(h, hipMemsetAsync(dbuf, 0, (size_t)N * 4 * 8 * sizeof(unsigned long long), st));
-    int rb = 0;
-    HIPCK(h, launch_channel_path(w.X, h->cw, w.bufF, 1024, N, st, nullptr, nullptr, h->num_cus, h->opt.channel_rows, dbuf, &rb));
+    HIPCK(h, launch_channel_path(w.X, h->cw, w.bufF, 1024, N, st, nullptr, nullptr, 0, rb, dbuf));
     HIPCK(h, hipStreamSynchronize(st));
     std::vector<unsigned long long> tr((size_t)N * 4 * 8);
     HIPCK(h, hipMemcpy(tr.data(), dbuf, tr.size() * 8, hipMemcpyDeviceToHost));
@@ -249,12 +248,19 @@ int run_recnet(ffr_handle* h, const Work& w, int N, float* f_new, const RecDebug
         // ss_channel Gram + Conv4Channel (6 linears) + M_channel @ X, algorithmic (unfused) count
         const double fl = 2.0 * N * (512.0 * 512 * 49 + 512.0 * (561 * 32 + 5 * 32 * 512) + 512.0 * 512 * 49);
         Scope s(h, st, FFR_KC_CHANNEL, fl, 4.0 * N * (49 * 512 * 3));
+        const int rb = plan_channel_rows(N, h->num_cus, h->opt.channel_rows);
+        if (!rb) return fail(h, FFR_ERR_ARG, "channel_rows is 0 (auto), 1, 2 or 4");
+        if (h->conv_rec) {      // the plan record: which instantiation of k_channel_path this launch is
+            ffr_conv_launch r{};
+            r.path = FFR_CP_CHANNEL; r.images = N; r.rows = 512 / rb; r.nblocks = N * rb;
+            h->conv_log.push_back(r);
+        }
 #ifdef FFR_TRACE
-        if (h->opt.wf_trace) RC(trace_channel_path(h, w, N, st));
+        if (h->opt.wf_trace) RC(trace_channel_path(h, w, N, rb, st));
         else
 #endif
-        HIPCK(h, launch_channel_path(w.X, h->cw, w.bufF, 1024, N, st, dbg ? dbg->ss_channel0 : nullptr, dbg ? dbg->M_channel0 : nullptr, h->num_cus,
-                                     h->opt.channel_rows));
+        HIPCK(h, launch_channel_path(w.X, h->cw, w.bufF, 1024, N, st, dbg ? dbg->ss_channel0 : nullptr, dbg ? dbg->M_channel0 : nullptr,
+                                     dbg ? dbg->image : 0, rb));
     }
     // Conv4Space (recnet.py:362-371)
     RC(conv_rec(h, w, h->sp[0], w.bufS, 576, nullptr, 0, w.s256a, 256, 0, 0, N, st));

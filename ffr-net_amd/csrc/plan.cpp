@@ -217,4 +217,22 @@ void plan_gemm_stream(long long T, int cout_pad, int* tile, int* nblocks) {
     }
 }
 
+// Row blocks per image of k_channel_path (1, 2 or 4; forced = option channel_rows, 0 leaves the choice here; 0 is returned for
+// a forced value that is none of them).  One block per CU (147.6 of the CU's 160 KB of LDS): rounds x block time, the fewest
+// row blocks among equals.  The block times (us: whole image / half / quarter of M_channel's rows) are MEASURED ON THE MI355X
+// (profiles/r05_channel_path_phase_trace.txt) and only their ratios matter; this library runs on gfx950 only (ffr_create
+// refuses other devices).
+int plan_channel_rows(int N, int num_cus, int forced) {
+    if (forced) return forced == 1 || forced == 2 || forced == 4 ? forced : 0;
+    const double t_block[3] = {181.0, 140.0, 101.0};
+    double best = 1e30;
+    int row_blocks = 1;
+    for (int k = 0; k < 3; ++k) {
+        const int rb = 1 << k;
+        const double t = (double)(((long long)N * rb + num_cus - 1) / num_cus) * t_block[k];
+        if (t < best - 1e-9) { best = t; row_blocks = rb; }
+    }
+    return row_blocks;
+}
+
 }  // namespace ffr_eng

@@ -95,7 +95,7 @@ template <int CT>
 __global__ __launch_bounds__(256, 1) void k_channel_path(const float* __restrict__ X, const ChannelPathWeights w,
                                                      const float* __restrict__ w1bT, float* __restrict__ bufF,
                                                      int pitchF, float* __restrict__ dbg_ss, float* __restrict__ dbg_M,
-                                                     unsigned long long* __restrict__ trace) {
+                                                     int dbg_n, unsigned long long* __restrict__ trace) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float* XT = sm;                       // [512][52]  X transposed: channel-major
     float* inv = XT + 512 * XT_LD;        // [512] 1/max(|X_c|,eps)
@@ -125,7 +125,7 @@ __global__ __launch_bounds__(256, 1) void k_channel_path(const float* __restrict
     }
     __syncthreads();
     if (FFR_TRACE_ON(trace)) ts[1] = __builtin_amdgcn_s_memtime();
-    if (dbg_ss && n == 0 && blockIdx.y == 0) {     // parity tests only: ss_channel of image 0 from the normalised vectors the path uses
+    if (dbg_ss && n == dbg_n && blockIdx.y == 0) {     // parity tests only: ss_channel of image dbg_n from the normalised vectors the path uses
         for (int o = tid; o < 512 * 512; o += 256) {
             const int c = o >> 9, cp = o & 511;
             float s = 0.f;
@@ -295,7 +295,7 @@ __global__ __launch_bounds__(256, 1) void k_channel_path(const float* __restrict
             for (int ks = 0; ks < 16; ++ks) z = __builtin_amdgcn_mfma_f32_32x32x2f32(wa[ks], HB[ct][ks], z, 0, 0, 0);
 #pragma unroll
             for (int r = 0; r < 16; ++r) z[r] = __builtin_amdgcn_rcpf(1.0f + __expf(-z[r]));      // v_rcp_f32 (1 ulp): an IEEE division is 10 instructions, 16 x 64 of them per image and wave sit between the MFMAs
-            if (dbg_M && n == 0) {      // parity tests only: M_channel[c][c'] of image 0, straight from the accumulator tile
+            if (dbg_M && n == dbg_n) {      // parity tests only: M_channel[c][c'] of image dbg_n, straight from the accumulator tile
 #pragma unroll
                 for (int r = 0; r < 16; ++r)
                     dbg_M[acc_row((row_base + 32 * ct + mj) * 512 + cpt * 32, r) + 4 * mh] = z[r];   // row0 = the flat offset of column cpt * 32
@@ -335,11 +335,9 @@ __global__ __launch_bounds__(256, 1) void k_channel_path(const float* __restrict
 }
 
 // w.w1b is passed TRANSPOSED ([512][32]) by the engine
-// row_blocks = 1, 2 or 4 blocks per image (0: chosen here from N and the CU count: the fewest rounds of one block per CU, weighted
-// with the measured time of a block of each shape)
+// row_blocks = 1, 2 or 4 blocks per image (plan.cpp: plan_channel_rows); dbg_ss / dbg_M receive ss_channel / M_channel of image dbg_n
 hipError_t launch_channel_path(const float* X, const ChannelPathWeights& w, float* bufF, int pitchF, int N,
-                               hipStream_t stream, float* dbg_ss, float* dbg_M, int num_cus, int row_blocks, unsigned long long* trace,
-                               int* row_blocks_used) {
+                               hipStream_t stream, float* dbg_ss, float* dbg_M, int dbg_n, int row_blocks, unsigned long long* trace) {
     static bool attr_done = false;
     const size_t lds = (size_t)(512 * XT_LD + 512 + 49 * 32 + 4 * 64 * 32) * 4;      // X^T, 1/norm, G, the four waves' partial G tiles
     if (!attr_done) {
@@ -350,23 +348,10 @@ hipError_t launch_channel_path(const float* X, const ChannelPathWeights& w, floa
         }
         attr_done = true;
     }
-    if (row_blocks == 0) {
-        // one block per CU (147.6 of the CU's 160 KB of LDS): rounds x block time.  The block times (us: whole image / half / quarter of
-        // M_channel's rows) are MEASURED ON THE MI355X (profiles/r05_channel_path_phase_trace.txt) and only their ratios matter; this
-        // library runs on gfx950 only (ffr_create refuses other devices)
-        const double t_block[3] = {181.0, 140.0, 101.0};
-        double best = 1e30;
-        for (int k = 0; k < 3; ++k) {
-            const int rb = 1 << k;
-            const double t = (double)(((long long)N * rb + num_cus - 1) / num_cus) * t_block[k];
-            if (t < best - 1e-9) { best = t; row_blocks = rb; }
-        }
-    }
-    if (row_blocks == 4) hipLaunchKernelGGL(k_channel_path<1>, dim3(N, 4), dim3(256), lds, stream, X, w, w.w1b, bufF, pitchF, dbg_ss, dbg_M, trace);
-    else if (row_blocks == 2) hipLaunchKernelGGL(k_channel_path<2>, dim3(N, 2), dim3(256), lds, stream, X, w, w.w1b, bufF, pitchF, dbg_ss, dbg_M, trace);
-    else if (row_blocks == 1) hipLaunchKernelGGL(k_channel_path<4>, dim3(N, 1), dim3(256), lds, stream, X, w, w.w1b, bufF, pitchF, dbg_ss, dbg_M, trace);
+    if (row_blocks == 4) hipLaunchKernelGGL(k_channel_path<1>, dim3(N, 4), dim3(256), lds, stream, X, w, w.w1b, bufF, pitchF, dbg_ss, dbg_M, dbg_n, trace);
+    else if (row_blocks == 2) hipLaunchKernelGGL(k_channel_path<2>, dim3(N, 2), dim3(256), lds, stream, X, w, w.w1b, bufF, pitchF, dbg_ss, dbg_M, dbg_n, trace);
+    else if (row_blocks == 1) hipLaunchKernelGGL(k_channel_path<4>, dim3(N, 1), dim3(256), lds, stream, X, w, w.w1b, bufF, pitchF, dbg_ss, dbg_M, dbg_n, trace);
     else return hipErrorInvalidValue;
-    if (row_blocks_used) *row_blocks_used = row_blocks;
     return hipGetLastError();
 }
 

@@ -76,7 +76,7 @@ class ConvLaunch(C.Structure):
                                        'phased', 'half_n', 'block_tiles', 'n_main', 'side')]
 
 
-CONV_PATHS = ('direct', 'fused', 'unfused-gemm-stream', 'unfused-igemm', 'mixed', 'tail-split')
+CONV_PATHS = ('direct', 'fused', 'unfused-gemm-stream', 'unfused-igemm', 'mixed', 'tail-split', 'channel')
 WGRAD_PATHS = ('plain-taps9', 'plain-taps1', 'batched')
 ARITH = {'direct': 0, 'winograd': 1}
 CALIB_TENSORS = ('f', 'featmap', 'f_new', 'feat_new')
@@ -151,7 +151,8 @@ SYMBOLS = [
     ('ffr_plan_igemm_host', C.c_int, [C.c_longlong] + [C.c_int] * 7 + [_P, _P, _P]),
     ('ffr_plan_conv_host', C.c_int, [C.c_int] * 20 + [_P]),
     ('ffr_encoder_trunk_nhwc', C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
-    ('ffr_recnet_debug', C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ('ffr_plan_channel_rows_host', C.c_int, [C.c_int, C.c_int, C.c_int, _P]),
+    ('ffr_recnet_debug', C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_int, _P]),
     # include/ffrnet_train.h
     ('ffr_op_convlayer_train', C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ('ffr_train_init', C.c_int, [_P, C.POINTER(TensorDesc), C.c_int]),
@@ -907,7 +908,7 @@ class Engine(object):
 
     def conv_plan(self):
         """The convolution launches since conv_plan_record(True), in launch order: [{path ('direct' | 'fused' |
-        'unfused-gemm-stream' | 'unfused-igemm' | 'mixed' | 'tail-split'), images, rows, tile, nblocks, granule, nkt, tiles, cut,
+        'unfused-gemm-stream' | 'unfused-igemm' | 'mixed' | 'tail-split' | 'channel' = RecNet's k_channel_path), images, rows, tile, nblocks, granule, nkt, tiles, cut,
         split, phased, half_n, block_tiles, n_main, side}] (include/ffrnet.h: ffr_conv_launch)."""
         n = C.c_int(0)
         self._ck(self.lib.ffr_conv_plan_read(self._h, None, 0, C.byref(n)))
@@ -1134,14 +1135,15 @@ class Engine(object):
         self._call(self.lib.ffr_encoder_trunk_nhwc, _ptr(x), n, h, w, n_blocks, _ptr(out))
         return out
 
-    def recnet_debug(self, featmap):
+    def recnet_debug(self, featmap, image=0):
+        """RecNet's internals (test hook); ss_channel0 / M_channel0 are those of image `image`."""
         self._tensor(featmap, 'input', shape=('N', 512, 7, 7))
         featmap = featmap.contiguous()
         n = featmap.size(0)
         o = dict(ss_space=self._empty(n, 49, 49), M_space=self._empty(n, 49, 49), feat_space=self._empty(n, 512, 7, 7),
                  feat_channel_raw=self._empty(n, 512, 7, 7), feat_channel=self._empty(n, 512, 7, 7),
                  ss_channel0=self._empty(512, 512), M_channel0=self._empty(512, 512))
-        self._call(self.lib.ffr_recnet_debug, _ptr(featmap), n, *[_ptr(t) for t in o.values()])
+        self._call(self.lib.ffr_recnet_debug, _ptr(featmap), n, *[_ptr(t) for t in o.values()], int(image))
         return o
 
 

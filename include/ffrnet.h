@@ -554,8 +554,11 @@ int ffr_op_conv3x3_ex(ffr_handle* h, const ffr_conv3x3_desc* d, void* stream);
  *   tile, nblocks, granule, nkt, tiles, cut, split   k_igemm / k_gemm_stream: tile config 1..4, persistent blocks, K-tiles a block
  *           owns at least (1 or nkt), K-tiles per tile, tiles, 1 when a tile is cut (in-launch fix-up), split-operand form
  *   phased, half_n, split, block_tiles   k_wino_fused: in-kernel input transform, 32 x 32 blocks, split-operand K loop, block tiles
- *   n_main, side   FFR_CP_TAIL_SPLIT: images that run fused; 1 when the remainder went to the second stream */
-enum { FFR_CP_DIRECT = 0, FFR_CP_FUSED = 1, FFR_CP_UNFUSED_STREAM = 2, FFR_CP_UNFUSED_IGEMM = 3, FFR_CP_MIXED = 4, FFR_CP_TAIL_SPLIT = 5 };
+ *   n_main, side   FFR_CP_TAIL_SPLIT: images that run fused; 1 when the remainder went to the second stream
+ * RecNet's channel launch is recorded too, as FFR_CP_CHANNEL (k_channel_path): images = N, nblocks = N x row blocks per image
+ * (1 / 2 / 4 = k_channel_path<4 / 2 / 1>), rows = the rows of M_channel one block evaluates (512 / row blocks). */
+enum { FFR_CP_DIRECT = 0, FFR_CP_FUSED = 1, FFR_CP_UNFUSED_STREAM = 2, FFR_CP_UNFUSED_IGEMM = 3, FFR_CP_MIXED = 4, FFR_CP_TAIL_SPLIT = 5,
+       FFR_CP_CHANNEL = 6 };
 typedef struct ffr_conv_launch {
     int path, images, rows;
     int tile, nblocks, granule, nkt, tiles, cut, split;
@@ -581,6 +584,10 @@ int ffr_plan_conv_host(int cin, int cout, int R, int stride, int pad, int pad_mo
                        int has_mixed, int N, int H, int W, int in_pitch, int out_pitch, int out_coff, int cout_store,
                        int res_pitch, int num_cus, int force, long long* out);
 
+/* The row blocks per image of k_channel_path for N images on num_cus CUs: forced = option "channel_rows" (0 = the automatic
+ * choice, 1 / 2 / 4 come back as they are, anything else is FFR_ERR_ARG). */
+int ffr_plan_channel_rows_host(int N, int num_cus, int forced, int* row_blocks);
+
 /* Encoder trunk only, stopping after `n_blocks` bottlenecks (0 = stem only,
  * 24 = whole body, before Backbone.bn); writes the NHWC activation.  Test hook for
  * the per-stage goldens.                                                            */
@@ -589,13 +596,13 @@ int ffr_encoder_trunk_nhwc(ffr_handle* h, const float* x_nchw, int N, int H, int
 
 /* RecNet internals for image-level goldens: any pointer may be NULL.
  *   ss_space[N,49,49] M_space[N,49,49]; ss_channel and M_channel are never stored by the fused channel path:
- *   ss_channel0[512,512] / M_channel0[512,512] receive them for IMAGE 0 only (debug stores inside the kernel);
+ *   ss_channel0[512,512] / M_channel0[512,512] receive them for ONE image, `image` in [0, N) (debug stores inside the kernel);
  *   feat_space[N,512,7,7] feat_channel_raw[N,512,7,7] (before ChannelFlipMerge)
  *   feat_channel[N,512,7,7] (after ChannelFlipMerge), all NCHW.                     */
 int ffr_recnet_debug(ffr_handle* h, const float* featmap_nchw, int N,
                      float* ss_space, float* M_space, float* feat_space,
                      float* feat_channel_raw, float* feat_channel, float* ss_channel0, float* M_channel0,
-                     void* stream);
+                     int image, void* stream);
 
 #ifdef __cplusplus
 }
