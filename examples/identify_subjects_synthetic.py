@@ -2,9 +2,11 @@
 """Identification over a subject-labelled gallery on synthetic images (needs an MI355X): several images per identity ->
 Gallery(subjects=True).add -> search_subjects -> remove one identity -> search again -> compact.
 
-    python examples/identify_subjects_synthetic.py [--identities 24] [--views 4]
+    python examples/identify_subjects_synthetic.py [--identities 24] [--views 4] [--coarse]
 
 An "identity" is a random image, a "view" of it the same image under pixel noise; the probes are further views.
+--coarse: after the first enrolment session the gallery gets its bf16 plane (build_plane()), and every search goes through
+the certified shortlist -- the same results bit for bit, which the example checks against the exact subject search.
 """
 import argparse, json, os, sys
 import torch
@@ -19,6 +21,7 @@ def main():
     ap.add_argument('--identities', type=int, default=24)
     ap.add_argument('--views', type=int, default=4)
     ap.add_argument('--noise', type=float, default=0.25)
+    ap.add_argument('--coarse', action='store_true', help='search through the certified bf16 shortlist')
     a = ap.parse_args()
     specs = json.load(open(os.path.join(ROOT, 'tests', 'golden', 'g0_state_dict_keys.json')))
     eng = ffrnet_amd.Engine(0)
@@ -36,11 +39,18 @@ def main():
     gallery = ffrnet_amd.Gallery(eng, subjects=True)
     half = n // 2
     gallery.add(f_enrol[:half], who[:half].cuda())                       # enrolment in two sessions
+    if a.coarse:
+        gallery.build_plane()                                            # packs the rows held; add() packs from here on
     gallery.add(f_enrol[half:], who[half:].cuda())
     k = min(5, a.identities)
     scores, subjects, index = gallery.search_subjects(f_probe, k)         # k people per probe, each once
     rows_s, rows_i = gallery.search(f_probe, k)                           # k rows: mostly views of one person
     print('%d rows of %d identities enrolled' % (len(gallery), a.identities))
+    if a.coarse:
+        es, ei, eu = eng.search_subjects(f_probe, gallery.embeddings, gallery.subjects, k, gallery_norms=gallery.norms)
+        assert torch.equal(scores, es) and torch.equal(index, ei) and torch.equal(subjects, eu)
+        print('shortlist: the bits of the exact search; last search certified for %d of %d probes'
+              % (int(gallery.last_certified.sum()), a.identities))
     print('probe 0: people %s, rows %s of people %s' % (subjects[0].tolist(), rows_i[0].tolist(),
                                                          who[rows_i[0].cpu()].tolist()))
     print('identity CMC  ', ffrnet_amd.subject_rates(subjects, labels, ranks=(1, k)))

@@ -25,6 +25,10 @@ constexpr int COARSE_MAX_K = 64;                             // the pass serves 
 constexpr int COARSE_MAX_SHORT = 128;
 // rows the pass lists per probe for a top-k
 __host__ __device__ constexpr int coarse_shortlist(int k) { return 2 * k > COARSE_MAX_SHORT ? COARSE_MAX_SHORT : 2 * k < 32 ? 32 : 2 * k; }
+// Identities (ffr_search_topk_coarse_subjects, distinct = 1): a person's rows crowd the head of a shortlist of rows, so the
+// list is min(128, max(4k, 64)) rows long and the pass serves k <= 32
+constexpr int COARSE_MAX_K_DISTINCT = 32;
+__host__ __device__ constexpr int coarse_shortlist_distinct(int k) { return 4 * k > COARSE_MAX_SHORT ? COARSE_MAX_SHORT : 4 * k < 64 ? 64 : 4 * k; }
 // a norm the bound holds for: zero (over a row of zeros: coarse_any_nonzero8), or within [2^-60, 2^60] (outside, the sum of
 // squares under- or overflows)
 __host__ __device__ __forceinline__ bool coarse_safe_norm(float nrm) { return nrm == 0.f || (nrm >= 0x1p-60f && nrm <= 0x1p60f); }

@@ -397,6 +397,62 @@ int ffr_coarse_pack(ffr_handle* h, const float* rows, const float* norms, long l
     return FFR_OK;
 }
 
+// The shortlist search of checked arguments, G >= 1 and a k the pass serves: ffr_search_topk_coarse (subject = null), and
+// ffr_search_topk_coarse_subjects, whose pass skips the removed rows, whose lists carry a subject plane and whose exact pass
+// is the subject search
+static int coarse_search(ffr_handle* h, const float* query, int Q, const float* gallery, const float* gallery_norms,
+                         const uint16_t* gallery_plane, const int* plane_flag, const int32_t* subject, long long G, int dim, int k,
+                         long long index_base, int distinct, float* top_score, int64_t* top_index, int32_t* top_subject, int* certified,
+                         hipStream_t st) {
+    const int kp = coarse_shortlist_size(k, distinct);
+    int T = 0, S = 0, Tf = 0, Sf = 0;
+    long long chunk_rows = 0, chunk_f = 0;
+    search_plan(Q, G, h->num_cus, &T, &S, &chunk_rows);
+    coarse_fallback_plan(Q, G, h->num_cus, &Tf, &Sf, &chunk_f);
+    // scratch: probe norms [Q]; shortlists [Q][kp]; the uncertified probes' ids [Q], count, rows [Q][512], norms [Q] and exact
+    // lists [Q][k]; the chunk lists of the coarse pass [S][Q][kp] and then of the exact pass [Sf][Q][k], in the same space;
+    // with subjects, a third plane for the exact lists and their chunk lists
+    const size_t part_n = std::max(S > 1 ? (size_t)S * Q * kp : 0, Sf > 1 ? (size_t)Sf * Q * k : 0);
+    float *qnorm = nullptr, *sl_s = nullptr, *uq = nullptr, *uqn = nullptr, *fb_s = nullptr, *part_s = nullptr;
+    int64_t *sl_i = nullptr, *fb_i = nullptr, *part_i = nullptr;
+    int32_t *fb_u = nullptr, *part_u = nullptr;
+    int *ulist = nullptr, *ucount = nullptr;
+    RC(carve(h, h->search, "search", [&](Arena& a) {
+        qnorm = a.take(Q);
+        sl_s = a.take((size_t)Q * kp); sl_i = a.take<int64_t>((size_t)Q * kp);
+        ulist = a.take<int>(Q); ucount = a.take<int>(1);
+        uq = a.take((size_t)Q * dim); uqn = a.take(Q);
+        fb_s = a.take((size_t)Q * k); fb_i = a.take<int64_t>((size_t)Q * k);
+        if (part_n) { part_s = a.take(part_n); part_i = a.take<int64_t>(part_n); }
+        if (subject) {
+            fb_u = a.take<int32_t>((size_t)Q * k);
+            if (Sf > 1) part_u = a.take<int32_t>((size_t)Sf * Q * k);
+        }
+    }));
+    Scope s(h, st, FFR_KC_SCORE, 2.0 * Q * (double)G * dim,
+            2.0 * (double)G * (dim + 2) + 4.0 * Q * dim + 12.0 * Q * (k + kp) + (subject ? 4.0 * (double)G + 4.0 * Q * k : 0.0));
+    HIPCK(h, launch_row_norms(query, Q, qnorm, st));
+    HIPCK(h, hipMemsetAsync(ucount, 0, sizeof(int), st));
+    HIPCK(h, launch_search_coarse(query, qnorm, Q, gallery_plane, gallery_norms, G, kp, T, S, chunk_rows, S > 1 ? part_s : sl_s,
+                                  S > 1 ? part_i : sl_i, st, subject));
+    if (S > 1) HIPCK(h, launch_topk_merge(part_s, part_i, S, Q, kp, sl_s, sl_i, st));
+    HIPCK(h, launch_search_rescore(query, qnorm, Q, gallery, gallery_norms, sl_s, sl_i, plane_flag, G, k, kp, index_base, top_score,
+                                   top_index, certified, ulist, ucount, st, subject, distinct, top_subject));
+    // the exact search of the probes that were not certified, sized for Q: tiles past the device count leave at once
+    HIPCK(h, launch_probe_gather(query, qnorm, ulist, ucount, Q, uq, uqn, st));
+    if (subject) {
+        HIPCK(h, launch_search_subjects(uq, uqn, Q, gallery, gallery_norms, subject, G, k, index_base, distinct, Tf, Sf, chunk_f,
+                                        Sf > 1 ? part_s : fb_s, Sf > 1 ? part_i : fb_i, Sf > 1 ? part_u : fb_u, st, ucount));
+        if (Sf > 1) HIPCK(h, launch_topk_merge_subjects(part_s, part_i, part_u, Sf, Q, k, distinct, fb_s, fb_i, fb_u, st, ucount));
+    } else {
+        HIPCK(h, launch_search_topk(uq, uqn, Q, gallery, gallery_norms, G, k, index_base, Tf, Sf, chunk_f, Sf > 1 ? part_s : fb_s,
+                                    Sf > 1 ? part_i : fb_i, st, ucount));
+        if (Sf > 1) HIPCK(h, launch_topk_merge(part_s, part_i, Sf, Q, k, fb_s, fb_i, st, ucount));
+    }
+    HIPCK(h, launch_topk_scatter(fb_s, fb_i, ulist, ucount, Q, k, top_score, top_index, st, fb_u, top_subject));
+    return FFR_OK;
+}
+
 int ffr_search_topk_coarse(ffr_handle* h, const float* query, int Q, const float* gallery, const float* gallery_norms,
                            const uint16_t* gallery_plane, const int* plane_flag, long long G, int dim, int k, long long index_base,
                            float* top_score, int64_t* top_index, int* certified, void* stream) {
@@ -407,45 +463,38 @@ int ffr_search_topk_coarse(ffr_handle* h, const float* query, int Q, const float
         return fail(h, FFR_ERR_ARG, "ffr_search_topk_coarse: bad arguments (Q >= 1, 1 <= k <= 128, G >= 0, non-null pointers)");
     if (misaligned16(query) || (G > 0 && (misaligned16(gallery) || misaligned16(gallery_plane))))
         return fail(h, FFR_ERR_ARG, "ffr_search_topk_coarse: query, gallery and plane rows must be 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
     if (G == 0 || k > coarse_max_k()) {          // nothing to shortlist, or a k the pass does not serve: the exact search alone
-        if (certified) HIPCK(h, hipMemsetAsync(certified, 0, sizeof(int) * (size_t)Q, st));
+        if (certified) HIPCK(h, hipMemsetAsync(certified, 0, sizeof(int) * (size_t)Q, (hipStream_t)stream));
         return ffr_search_topk(h, query, Q, gallery, gallery_norms, G, dim, k, index_base, top_score, top_index, stream);
     }
-    const int kp = coarse_shortlist_size(k);
-    int T = 0, S = 0, Tf = 0, Sf = 0;
-    long long chunk_rows = 0, chunk_f = 0;
-    search_plan(Q, G, h->num_cus, &T, &S, &chunk_rows);
-    coarse_fallback_plan(Q, G, h->num_cus, &Tf, &Sf, &chunk_f);
-    // scratch: probe norms [Q]; shortlists [Q][kp]; the uncertified probes' ids [Q], count, rows [Q][512], norms [Q] and exact
-    // lists [Q][k]; the chunk lists of the coarse pass [S][Q][kp] and then of the exact pass [Sf][Q][k], in the same space
-    const size_t part_n = std::max(S > 1 ? (size_t)S * Q * kp : 0, Sf > 1 ? (size_t)Sf * Q * k : 0);
-    float *qnorm = nullptr, *sl_s = nullptr, *uq = nullptr, *uqn = nullptr, *fb_s = nullptr, *part_s = nullptr;
-    int64_t *sl_i = nullptr, *fb_i = nullptr, *part_i = nullptr;
-    int *ulist = nullptr, *ucount = nullptr;
-    RC(carve(h, h->search, "search", [&](Arena& a) {
-        qnorm = a.take(Q);
-        sl_s = a.take((size_t)Q * kp); sl_i = a.take<int64_t>((size_t)Q * kp);
-        ulist = a.take<int>(Q); ucount = a.take<int>(1);
-        uq = a.take((size_t)Q * dim); uqn = a.take(Q);
-        fb_s = a.take((size_t)Q * k); fb_i = a.take<int64_t>((size_t)Q * k);
-        if (part_n) { part_s = a.take(part_n); part_i = a.take<int64_t>(part_n); }
-    }));
-    Scope s(h, st, FFR_KC_SCORE, 2.0 * Q * (double)G * dim, 2.0 * (double)G * (dim + 2) + 4.0 * Q * dim + 12.0 * Q * (k + kp));
-    HIPCK(h, launch_row_norms(query, Q, qnorm, st));
-    HIPCK(h, hipMemsetAsync(ucount, 0, sizeof(int), st));
-    HIPCK(h, launch_search_coarse(query, qnorm, Q, gallery_plane, gallery_norms, G, kp, T, S, chunk_rows, S > 1 ? part_s : sl_s,
-                                  S > 1 ? part_i : sl_i, st));
-    if (S > 1) HIPCK(h, launch_topk_merge(part_s, part_i, S, Q, kp, sl_s, sl_i, st));
-    HIPCK(h, launch_search_rescore(query, qnorm, Q, gallery, gallery_norms, sl_s, sl_i, plane_flag, G, k, kp, index_base, top_score,
-                                   top_index, certified, ulist, ucount, st));
-    // the exact search of the probes that were not certified, sized for Q: tiles past the device count leave at once
-    HIPCK(h, launch_probe_gather(query, qnorm, ulist, ucount, Q, uq, uqn, st));
-    HIPCK(h, launch_search_topk(uq, uqn, Q, gallery, gallery_norms, G, k, index_base, Tf, Sf, chunk_f, Sf > 1 ? part_s : fb_s,
-                                Sf > 1 ? part_i : fb_i, st, ucount));
-    if (Sf > 1) HIPCK(h, launch_topk_merge(part_s, part_i, Sf, Q, k, fb_s, fb_i, st, ucount));
-    HIPCK(h, launch_topk_scatter(fb_s, fb_i, ulist, ucount, Q, k, top_score, top_index, st));
-    return FFR_OK;
+    return coarse_search(h, query, Q, gallery, gallery_norms, gallery_plane, plane_flag, nullptr, G, dim, k, index_base, 0, top_score,
+                         top_index, nullptr, certified, (hipStream_t)stream);
+}
+
+int ffr_search_topk_coarse_subjects(ffr_handle* h, const float* query, int Q, const float* gallery, const float* gallery_norms,
+                                    const uint16_t* gallery_plane, const int* plane_flag, const int32_t* gallery_subject, long long G,
+                                    int dim, int k, long long index_base, int distinct, float* top_score, int64_t* top_index,
+                                    int32_t* top_subject, int* certified, void* stream) {
+    FFR_DEVICE_SCOPE(h); RC(check_fwd(h, false, false, 1));
+    RC(check_dim(h, "ffr_search_topk_coarse_subjects", dim));
+    if (!query || !top_score || !top_index || !top_subject || Q < 1 || k < 1 || k > 128 || G < 0 ||
+        (G > 0 && (!gallery || !gallery_norms || !gallery_plane || !plane_flag || !gallery_subject)))
+        return fail(h, FFR_ERR_ARG, "ffr_search_topk_coarse_subjects: bad arguments (Q >= 1, 1 <= k <= 128, G >= 0, non-null pointers)");
+    if (distinct != 0 && distinct != 1)
+        return fail(h, FFR_ERR_ARG, "ffr_search_topk_coarse_subjects: distinct must be 0 or 1, got %d", distinct);
+    if (distinct && k > search_max_k_distinct())
+        return fail(h, FFR_ERR_ARG, "ffr_search_topk_coarse_subjects: identity mode serves k <= %d, got %d", search_max_k_distinct(), k);
+    if (misaligned16(query) || (G > 0 && (misaligned16(gallery) || misaligned16(gallery_plane))))
+        return fail(h, FFR_ERR_ARG, "ffr_search_topk_coarse_subjects: query, gallery and plane rows must be 16-byte aligned");
+    if (G > 0 && misaligned4(gallery_subject))
+        return fail(h, FFR_ERR_ARG, "ffr_search_topk_coarse_subjects: gallery_subject must be 4-byte aligned");
+    if (G == 0 || k > coarse_max_k(distinct)) {  // as above; the pass lists identities for k <= 32
+        if (certified) HIPCK(h, hipMemsetAsync(certified, 0, sizeof(int) * (size_t)Q, (hipStream_t)stream));
+        return ffr_search_topk_subjects(h, query, Q, gallery, gallery_norms, gallery_subject, G, dim, k, index_base, distinct, top_score,
+                                        top_index, top_subject, stream);
+    }
+    return coarse_search(h, query, Q, gallery, gallery_norms, gallery_plane, plane_flag, gallery_subject, G, dim, k, index_base, distinct,
+                         top_score, top_index, top_subject, certified, (hipStream_t)stream);
 }
 
 // ---- clustering (cluster.hip) ----------------------------------------------------------------------------------------

@@ -244,40 +244,46 @@ hipError_t launch_search_topk(const float* query, const float* qnorm, int Q, con
 hipError_t launch_topk_merge(const float* score, const int64_t* index, int S, int Q, int k, float* out_s, int64_t* out_i,
                              hipStream_t stream, const int* live = nullptr);
 // the same with subject[G] (< 0 = a removed row, never listed) and a third plane out_u of subjects; distinct: the lists hold
-// subjects, each by its best row, k <= search_max_k_distinct()
+// subjects, each by its best row, k <= search_max_k_distinct(); live as above
 int search_max_k_distinct();
 hipError_t launch_search_subjects(const float* query, const float* qnorm, int Q, const float* gallery, const float* gnorm,
                                   const int32_t* subject, long long G, int k, long long index_base, int distinct, int ntiles,
                                   int nchunks, long long chunk_rows, float* out_s, int64_t* out_i, int32_t* out_u,
-                                  hipStream_t stream);
+                                  hipStream_t stream, const int* live = nullptr);
 hipError_t launch_topk_merge_subjects(const float* score, const int64_t* index, const int32_t* subject, int S, int Q, int k,
-                                      int distinct, float* out_s, int64_t* out_i, int32_t* out_u, hipStream_t stream);
+                                      int distinct, float* out_s, int64_t* out_i, int32_t* out_u, hipStream_t stream,
+                                      const int* live = nullptr);
 
 // ---- certified bf16 shortlist search (search_coarse.hip) ------------------------------
-// rows the coarse pass lists per probe for a top-k (k <= coarse_max_k()), and the largest k it serves
-int coarse_shortlist_size(int k);
-int coarse_max_k();
+// rows the coarse pass lists per probe for a top-k (k <= coarse_max_k()), and the largest k it serves; distinct: for a list
+// of subjects (ffr_search_topk_coarse_subjects)
+int coarse_shortlist_size(int k, int distinct = 0);
+int coarse_max_k(int distinct = 0);
 // chunking of the exact pass over the probes that were not certified: as search_plan, with chunks fine enough that a few live
 // probes still reach every CU
 void coarse_fallback_plan(int Q, long long G, int num_cus, int* ntiles, int* nchunks, long long* chunk_rows);
 // plane[r] = bf16(rows[r] / norms[r]) of [n][512] rows; *flag |= 1 when a norm is unsafe (not zero and outside [2^-60, 2^60])
 hipError_t launch_coarse_pack(const float* rows, const float* norms, long long n, uint16_t* plane, int* flag, hipStream_t stream);
-// shortlists [nchunks][Q][kp] of every plane chunk by coarse score, index = gallery row (one launch); merged by launch_topk_merge
+// shortlists [nchunks][Q][kp] of every plane chunk by coarse score, index = gallery row (one launch); merged by launch_topk_merge.
+// subject[G] (or null): the rows with subject < 0 are removed and never listed
 hipError_t launch_search_coarse(const float* query, const float* qnorm, int Q, const uint16_t* plane, const float* gnorm,
                                 long long G, int kp, int ntiles, int nchunks, long long chunk_rows, float* out_s, int64_t* out_i,
-                                hipStream_t stream);
+                                hipStream_t stream, const int32_t* subject = nullptr);
 // exact scores of the shortlists sl[Q][kp], the certificate, the certified probes' top-k -> top[Q][k]; the others' ids ->
-// ulist[0 .. *ucount) (ucount zero before the launch); certified[Q] (0 / 1) may be null
+// ulist[0 .. *ucount) (ucount zero before the launch); certified[Q] (0 / 1) may be null.  subject[G] (or null): shortlists of
+// live rows; top_u[Q][k] gets the subjects, and with distinct the lists hold subjects, each by its best row
 hipError_t launch_search_rescore(const float* query, const float* qnorm, int Q, const float* gallery, const float* gnorm,
                                  const float* sl_s, const int64_t* sl_i, const int* plane_flag, long long G, int k, int kp,
                                  long long index_base, float* top_s, int64_t* top_i, int* certified, int* ulist, int* ucount,
-                                 hipStream_t stream);
+                                 hipStream_t stream, const int32_t* subject = nullptr, int distinct = 0, int32_t* top_u = nullptr);
 // uq[i] = query[ulist[i]], uqn[i] = qnorm[ulist[i]] for i < *ucount (grid sized for Q)
 hipError_t launch_probe_gather(const float* query, const float* qnorm, const int* ulist, const int* ucount, int Q, float* uq,
                                float* uqn, hipStream_t stream);
-// top[ulist[i]] = fb[i] for i < *ucount: the lists [k] of the exact pass back to their probes
+// top[ulist[i]] = fb[i] for i < *ucount: the lists [k] of the exact pass back to their probes (fb_u -> top_u: their subject
+// plane, or null)
 hipError_t launch_topk_scatter(const float* fb_s, const int64_t* fb_i, const int* ulist, const int* ucount, int Q, int k,
-                               float* top_s, int64_t* top_i, hipStream_t stream);
+                               float* top_s, int64_t* top_i, hipStream_t stream, const int32_t* fb_u = nullptr,
+                               int32_t* top_u = nullptr);
 
 // ---- clustering (cluster.hip) ----------------------------------------------------------
 // chunking of the self-join: probe tiles x row chunks, sized for the blocks on and above the diagonal; N >= 1

@@ -151,8 +151,8 @@ __global__ __launch_bounds__(64) void k_topk_merge(const float* __restrict__ sco
 __global__ __launch_bounds__(64) void k_topk_merge_subjects(const float* __restrict__ score, const int64_t* __restrict__ index,
                                                             const int32_t* __restrict__ subject, int S, int Q, int k, int staged,
                                                             int distinct, float* __restrict__ out_s, int64_t* __restrict__ out_i,
-                                                            int32_t* __restrict__ out_u) {
-    topk_merge_wave<true>(score, index, subject, S, Q, k, staged, distinct, out_s, out_i, out_u, nullptr);
+                                                            int32_t* __restrict__ out_u, const int* __restrict__ live) {
+    topk_merge_wave<true>(score, index, subject, S, Q, k, staged, distinct, out_s, out_i, out_u, live);
 }
 
 }  // namespace
@@ -185,8 +185,8 @@ hipError_t launch_search_topk(const float* query, const float* qnorm, int Q, con
 hipError_t launch_search_subjects(const float* query, const float* qnorm, int Q, const float* gallery, const float* gnorm,
                                   const int32_t* subject, long long G, int k, long long index_base, int distinct, int ntiles,
                                   int nchunks, long long chunk_rows, float* out_s, int64_t* out_i, int32_t* out_u,
-                                  hipStream_t stream) {
-    SearchArgs a{query, qnorm, gallery, nullptr, gnorm, G, chunk_rows, index_base, out_s, out_i, nullptr, Q, k, nchunks, ntiles,
+                                  hipStream_t stream, const int* live) {
+    SearchArgs a{query, qnorm, gallery, nullptr, gnorm, G, chunk_rows, index_base, out_s, out_i, live, Q, k, nchunks, ntiles,
                  subject, out_u};
     const size_t lds = sr_lds_bytes(k, distinct != 0);
     const void* fn = distinct ? (const void*)k_search_subjects<SR_DISTINCT> : (const void*)k_search_subjects<SR_LIVE>;
@@ -216,13 +216,14 @@ hipError_t launch_topk_merge(const float* score, const int64_t* index, int S, in
 }
 
 hipError_t launch_topk_merge_subjects(const float* score, const int64_t* index, const int32_t* subject, int S, int Q, int k,
-                                      int distinct, float* out_s, int64_t* out_i, int32_t* out_u, hipStream_t stream) {
+                                      int distinct, float* out_s, int64_t* out_i, int32_t* out_u, hipStream_t stream,
+                                      const int* live) {
     int staged = 0;
     const size_t lds = merge_lds(S, k, 16, &staged);
     hipError_t e = hipFuncSetAttribute((const void*)k_topk_merge_subjects, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MG_LDS_CAP);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_topk_merge_subjects, dim3((unsigned)Q), dim3(64), lds, stream, score, index, subject, S, Q, k, staged,
-                       distinct, out_s, out_i, out_u);
+                       distinct, out_s, out_i, out_u, live);
     return hipGetLastError();
 }
 

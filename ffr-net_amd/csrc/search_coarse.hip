@@ -41,6 +41,25 @@
 // k_probe_gather / k_topk_scatter   the exact pass over the probes that were not certified runs without a host
 //                   synchronisation: it is always launched, sized for Q, on the gathered probes, and k_search_topk /
 //                   k_topk_merge take the device count -- tiles (probes) past it leave at once.
+//
+// Subjects (ffr_search_topk_coarse_subjects).  A gallery whose rows carry subject[G] (< 0 = removed) takes the same pass in
+// ROW mode under the removal mask -- k_search_coarse_live, the <true, SR_LIVE> instantiation of search_core.h -- so the
+// subject merge never runs over the gallery; identities are formed once per probe, on the <= 128 re-scored entries.
+// L is the shortlist of the k' best LIVE rows, c_1 >= ... >= c_k'; every live row outside L has c <= c_k', hence exact
+// s <= c_k' + eps, eps unchanged.  k' = min(128, max(2k, 32)) for rows (k <= 64) and min(128, max(4k, 64)) for identities
+// (k <= 32): a person's rows crowd the head of the list.  The probe is certified iff the plane flag is clear, its norm is
+// safe, and either L holds fewer than k' rows or G <= k' (L is then every live row: with removals, G > k' no longer means a
+// full list), or -- identities -- at least k entries are alive, and c_k' + eps < s_k, strictly.  An entry is alive iff no
+// other entry of its subject comes before it in the total order (descending exact score, ascending index); s_k is the score
+// of the k-th alive entry (rows: of the k-th entry).
+// Proof for identities.  Let u be one of the first k alive entries.  Its alive entry scores >= s_k > every row outside L, so
+// no row of u outside L beats or ties it: it is best(u) over the whole gallery.  Let v be a subject not among them: either
+// its best row in L ranks after the k-th alive entry, or v has no row in L and its best row scores below s_k.  Hence the
+// first k of {best(u)} over the gallery are the first k alive entries of L, with their scores and indices.  Fewer than k
+// alive entries in a full shortlist is not certified: more subjects may lie outside (one person enrolled with more rows than
+// the list holds).  The probes that are not certified go through k_search_subjects / k_topk_merge_subjects with the device
+// count, and their lists come back with the subject plane.
+//
 // Flops: a coarse search counts 2*Q*G*512, the scores it ranks (the second probe plane, the re-score and the exact pass over
 // uncertified probes are not counted).
 #include <hip/hip_runtime.h>
@@ -73,6 +92,8 @@ __global__ __launch_bounds__(256) void k_coarse_pack(const float* __restrict__ x
 }
 
 __global__ __launch_bounds__(256, 1) void k_search_coarse(const SearchArgs a) { search_block<true>(a); }
+// under the removal mask: rows with subject < 0 never enter; the shortlist goes out as rows, without a subject plane
+__global__ __launch_bounds__(256, 1) void k_search_coarse_live(const SearchArgs a) { search_block<true, SR_LIVE, false>(a); }
 
 struct RescoreArgs {
     const float* query;       // [Q][512]
@@ -89,20 +110,33 @@ struct RescoreArgs {
     int* ulist;               // [Q]
     int* ucount;
     int Q, k, kp;
+    const int32_t* subject;   // [G] (SUBJ): every listed row is live, subject >= 0
+    int32_t* top_u;           // [Q][k] (SUBJ)
+    int distinct;             // (SUBJ) 1: the lists hold subjects, each by its best row
 };
 
-// LDS: probe fragments [64][64] f32x4 | exact scores rs[128] | gallery rows ri[128] i64 | sk
+// LDS: probe fragments [64][64] f32x4 | exact scores rs[128] | gallery rows ri[128] i64 | sk | (SUBJ) subjects ru[128] i32,
+// alive flags ra[128] i32
 constexpr size_t RS_OFF_S = (size_t)CT_NG * 64 * 16;
 constexpr size_t RS_OFF_I = RS_OFF_S + (size_t)COARSE_MAX_SHORT * 4;
 constexpr size_t RS_OFF_K = RS_OFF_I + (size_t)COARSE_MAX_SHORT * 8;
-constexpr size_t RS_LDS = RS_OFF_K + 16;
+constexpr size_t RS_OFF_U = RS_OFF_K + 16;
+constexpr size_t RS_OFF_A = RS_OFF_U + (size_t)COARSE_MAX_SHORT * 4;
+constexpr size_t rs_lds_bytes(bool subj) { return subj ? RS_OFF_A + (size_t)COARSE_MAX_SHORT * 4 : RS_OFF_U; }
 
+// SUBJ = false: k_search_rescore of ffr_search_topk_coarse.  SUBJ = true: the shortlist came from k_search_coarse_live; every
+// entry carries subject[row], top_u is written beside the list, and with a.distinct the list holds subjects: an entry is
+// ALIVE iff no other entry of its subject comes before it in the total order, its place is the number of alive entries
+// before it, and s_k is the score of the k-th alive entry (two passes over the <= 128 entries, one barrier between them).
+template <bool SUBJ>
 __global__ __launch_bounds__(256, 1) void k_search_rescore(const RescoreArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
     f32x4* qf = (f32x4*)sm;
     float* rs = (float*)(sm + RS_OFF_S);
     long long* ri = (long long*)(sm + RS_OFF_I);
     float* sk = (float*)(sm + RS_OFF_K);
+    int* ru = (int*)(sm + RS_OFF_U);
+    int* ra = (int*)(sm + RS_OFF_A);
 
     const int tid = threadIdx.x, lane = tid & 63, n = lane & 31, h = lane >> 5;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -113,6 +147,7 @@ __global__ __launch_bounds__(256, 1) void k_search_rescore(const RescoreArgs a) 
     if (tid < COARSE_MAX_SHORT) {
         ri[tid] = tid < kp ? (long long)a.sl_i[(size_t)qi * kp + tid] : -1;
         rs[tid] = -INFINITY;
+        if constexpr (SUBJ) ru[tid] = ri[tid] >= 0 ? a.subject[ri[tid]] : -1;
     }
     const float qn = a.qnorm[qi];
     __syncthreads();
@@ -141,17 +176,44 @@ __global__ __launch_bounds__(256, 1) void k_search_rescore(const RescoreArgs a) 
 
     // rank of entry tid under the total order
     const bool live = tid < kp && ri[tid] >= 0;
+    const bool distinct = SUBJ && a.distinct;
     int rank = INT_MAX;
+    bool out = live;                                      // an entry that the list can hold: a row, or its subject's best row
     if (live) {
         const float s = rs[tid];
         const long long i = ri[tid];
         rank = 0;
-        for (int e = 0; e < kp; ++e) rank += ri[e] >= 0 && (rs[e] > s || (rs[e] == s && ri[e] < i));
-        if (rank == k - 1) sk[0] = s;
+        if constexpr (SUBJ) {
+            const int u = ru[tid];
+            bool behind = false;                          // behind another row of its own subject
+            for (int e = 0; e < kp; ++e) {
+                const bool first = ri[e] >= 0 && (rs[e] > s || (rs[e] == s && ri[e] < i));
+                rank += first;
+                behind |= first && ru[e] == u;
+            }
+            if (distinct) out = !behind;
+        } else {
+            for (int e = 0; e < kp; ++e) rank += ri[e] >= 0 && (rs[e] > s || (rs[e] == s && ri[e] < i));
+        }
     }
+    if constexpr (SUBJ) {
+        if (distinct) {                                   // place among the alive entries (uniform branch: barriers inside)
+            if (tid < COARSE_MAX_SHORT) ra[tid] = out;
+            __syncthreads();
+            if (out) {
+                const float s = rs[tid];
+                const long long i = ri[tid];
+                rank = 0;
+                for (int e = 0; e < kp; ++e) rank += ra[e] && (rs[e] > s || (rs[e] == s && ri[e] < i));
+            }
+        }
+    }
+    if (out && rank == k - 1) sk[0] = rs[tid];
     const int nv = __syncthreads_count(live);            // listed rows (padding is at the end)
+    const int no = SUBJ ? __syncthreads_count(out) : nv; // entries the list can hold
+    const bool whole = a.G <= kp || (SUBJ && nv < kp);    // the shortlist is every (live) row: under a mask, G > k' need not fill it
     bool ok = *a.plane_flag == 0 && coarse_safe_norm(qn) && !qbad;
-    if (ok && a.G > kp) ok = nv == kp && a.sl_s[(size_t)qi * kp + kp - 1] + COARSE_EPS < sk[0];
+    if (ok && !whole) ok = nv == kp && no >= k && a.sl_s[(size_t)qi * kp + kp - 1] + COARSE_EPS < sk[0];
     if (tid == 0) {
         if (a.certified) a.certified[qi] = ok;
         if (!ok) a.ulist[atomicAdd(a.ucount, 1)] = qi;
@@ -159,11 +221,15 @@ __global__ __launch_bounds__(256, 1) void k_search_rescore(const RescoreArgs a) 
     if (!ok) return;
     float* os = a.top_s + (size_t)qi * k;
     int64_t* oi = a.top_i + (size_t)qi * k;
-    if (rank < k) {
+    if (out && rank < k) {
         os[rank] = rs[tid];
         oi[rank] = a.index_base + ri[tid];
+        if constexpr (SUBJ) a.top_u[(size_t)qi * k + rank] = ru[tid];
     }
-    for (int p = nv + tid; p < k; p += 256) { os[p] = -INFINITY; oi[p] = -1; }
+    for (int p = no + tid; p < k; p += 256) {
+        os[p] = -INFINITY; oi[p] = -1;
+        if constexpr (SUBJ) a.top_u[(size_t)qi * k + p] = -1;
+    }
 }
 
 __global__ __launch_bounds__(128) void k_probe_gather(const float* __restrict__ query, const float* __restrict__ qnorm,
@@ -177,21 +243,23 @@ __global__ __launch_bounds__(128) void k_probe_gather(const float* __restrict__ 
 }
 
 __global__ __launch_bounds__(64) void k_topk_scatter(const float* __restrict__ fb_s, const int64_t* __restrict__ fb_i,
-                                                     const int* __restrict__ ulist, const int* __restrict__ ucount, int k,
-                                                     float* __restrict__ top_s, int64_t* __restrict__ top_i) {
+                                                     const int32_t* __restrict__ fb_u, const int* __restrict__ ulist,
+                                                     const int* __restrict__ ucount, int k, float* __restrict__ top_s,
+                                                     int64_t* __restrict__ top_i, int32_t* __restrict__ top_u) {
     const int i = blockIdx.x;
     if (i >= *ucount) return;
     const int dst = ulist[i];
     for (int p = threadIdx.x; p < k; p += 64) {
         top_s[(size_t)dst * k + p] = fb_s[(size_t)i * k + p];
         top_i[(size_t)dst * k + p] = fb_i[(size_t)i * k + p];
+        if (fb_u) top_u[(size_t)dst * k + p] = fb_u[(size_t)i * k + p];      // the subject plane, where the lists have one
     }
 }
 
 }  // namespace
 
-int coarse_shortlist_size(int k) { return coarse_shortlist(k); }
-int coarse_max_k() { return COARSE_MAX_K; }
+int coarse_shortlist_size(int k, int distinct) { return distinct ? coarse_shortlist_distinct(k) : coarse_shortlist(k); }
+int coarse_max_k(int distinct) { return distinct ? COARSE_MAX_K_DISTINCT : COARSE_MAX_K; }
 
 void coarse_fallback_plan(int Q, long long G, int num_cus, int* ntiles, int* nchunks, long long* chunk_rows) {
     *ntiles = (Q + CT_QT - 1) / CT_QT;
@@ -206,23 +274,30 @@ hipError_t launch_coarse_pack(const float* rows, const float* norms, long long n
 
 hipError_t launch_search_coarse(const float* query, const float* qnorm, int Q, const uint16_t* plane, const float* gnorm,
                                 long long G, int kp, int ntiles, int nchunks, long long chunk_rows, float* out_s, int64_t* out_i,
-                                hipStream_t stream) {
-    SearchArgs a{query, qnorm, nullptr, plane, gnorm, G, chunk_rows, 0, out_s, out_i, nullptr, Q, kp, nchunks, ntiles};
+                                hipStream_t stream, const int32_t* subject) {
+    SearchArgs a{query, qnorm, nullptr, plane, gnorm, G, chunk_rows, 0, out_s, out_i, nullptr, Q, kp, nchunks, ntiles,
+                 subject, nullptr};
     const size_t lds = sr_lds_bytes(kp);
-    hipError_t e = hipFuncSetAttribute((const void*)k_search_coarse, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const void* fn = subject ? (const void*)k_search_coarse_live : (const void*)k_search_coarse;
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_search_coarse, dim3((unsigned)(nchunks * ntiles)), dim3(256), lds, stream, a);
+    if (subject) hipLaunchKernelGGL(k_search_coarse_live, dim3((unsigned)(nchunks * ntiles)), dim3(256), lds, stream, a);
+    else hipLaunchKernelGGL(k_search_coarse, dim3((unsigned)(nchunks * ntiles)), dim3(256), lds, stream, a);
     return hipGetLastError();
 }
 
 hipError_t launch_search_rescore(const float* query, const float* qnorm, int Q, const float* gallery, const float* gnorm,
                                  const float* sl_s, const int64_t* sl_i, const int* plane_flag, long long G, int k, int kp,
                                  long long index_base, float* top_s, int64_t* top_i, int* certified, int* ulist, int* ucount,
-                                 hipStream_t stream) {
-    RescoreArgs a{query, qnorm, gallery, gnorm, sl_s, sl_i, plane_flag, G, index_base, top_s, top_i, certified, ulist, ucount, Q, k, kp};
-    hipError_t e = hipFuncSetAttribute((const void*)k_search_rescore, hipFuncAttributeMaxDynamicSharedMemorySize, (int)RS_LDS);
+                                 hipStream_t stream, const int32_t* subject, int distinct, int32_t* top_u) {
+    RescoreArgs a{query, qnorm, gallery, gnorm, sl_s, sl_i, plane_flag, G, index_base, top_s, top_i, certified, ulist, ucount, Q, k, kp,
+                  subject, top_u, distinct};
+    const size_t lds = rs_lds_bytes(subject != nullptr);
+    const void* fn = subject ? (const void*)k_search_rescore<true> : (const void*)k_search_rescore<false>;
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_search_rescore, dim3((unsigned)Q), dim3(256), RS_LDS, stream, a);
+    if (subject) hipLaunchKernelGGL(k_search_rescore<true>, dim3((unsigned)Q), dim3(256), lds, stream, a);
+    else hipLaunchKernelGGL(k_search_rescore<false>, dim3((unsigned)Q), dim3(256), lds, stream, a);
     return hipGetLastError();
 }
 
@@ -233,8 +308,8 @@ hipError_t launch_probe_gather(const float* query, const float* qnorm, const int
 }
 
 hipError_t launch_topk_scatter(const float* fb_s, const int64_t* fb_i, const int* ulist, const int* ucount, int Q, int k,
-                               float* top_s, int64_t* top_i, hipStream_t stream) {
-    hipLaunchKernelGGL(k_topk_scatter, dim3((unsigned)Q), dim3(64), 0, stream, fb_s, fb_i, ulist, ucount, k, top_s, top_i);
+                               float* top_s, int64_t* top_i, hipStream_t stream, const int32_t* fb_u, int32_t* top_u) {
+    hipLaunchKernelGGL(k_topk_scatter, dim3((unsigned)Q), dim3(64), 0, stream, fb_s, fb_i, fb_u, ulist, ucount, k, top_s, top_i, top_u);
     return hipGetLastError();
 }
 

@@ -25,7 +25,8 @@
 //    never enter, the merge is the same, and the subject of a listed row is read again at write-out.  SR_DISTINCT lists
 //    subjects, not rows: candidates and list entries carry their subject in LDS, and the merge is the rank scatter over the
 //    elements that no other element of their own subject beats, so the list stays subject-unique and still does not depend
-//    on the order of arrival (no atomics here either).  The threshold argument holds: with k subjects listed, a row at or below the k-th score loses
+//    on the order of arrival (no atomics here either).  The policy goes with either tile, and the chunk's subjects, like its
+//    norms, are a 64-bit base (subject + c0) plus 32-bit offsets.  The threshold argument holds: with k subjects listed, a row at or below the k-th score loses
 //    to k listed entries on score or index, or to its own subject's entry.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -58,7 +59,7 @@ struct SearchArgs {
     const int* live;          // device, or null: the probes [*live, Q) are not searched (their tiles leave at once)
     int Q, k, nchunks, ntiles;
     const int32_t* subject;   // [G], < 0 = a removed row (SR_LIVE, SR_DISTINCT)
-    int32_t* out_u;           // [S][Q][k] (SR_LIVE, SR_DISTINCT)
+    int32_t* out_u;           // [S][Q][k] (SR_LIVE, SR_DISTINCT; not touched, may be null, where OUT_U is false)
 };
 
 // The tile a search block scores with: the exact fp32 one of cosine_tile.h, or the bf16 one of coarse_tile.h
@@ -92,9 +93,11 @@ static_assert(sr_lds_bytes(SR_MAX_K) <= 160 * 1024 && sr_lds_bytes(SR_MAX_K_DIST
               sr_lds_bytes(SR_MAX_K, true) > 160 * 1024, "LDS of one search block");
 
 // One block of a search: k_search_topk (search.hip) is the exact instantiation, k_search_coarse (search_coarse.hip) the
-// bf16 one, k_search_subjects (search.hip) the exact one with a subject policy.  They differ in the tile and in what the
-// policy adds; the threshold test, the survivor slots and the rank-scatter merge are this text.
-template <bool COARSE, int SUBJ = SR_ROWS>
+// bf16 one, k_search_subjects (search.hip) the exact one with a subject policy, k_search_coarse_live (search_coarse.hip) the
+// bf16 one under the removal mask.  They differ in the tile and in what the policy adds; the threshold test, the survivor
+// slots and the rank-scatter merge are this text.  OUT_U = false: the lists go out without their subject plane (out_u is not
+// touched and may be null) -- a shortlist of rows, whose reader looks subject[row] up again.
+template <bool COARSE, int SUBJ = SR_ROWS, bool OUT_U = SUBJ != SR_ROWS>
 __device__ __forceinline__ void search_block(const SearchArgs& a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
     f32x4* qf = (f32x4*)sm;
@@ -365,8 +368,8 @@ __device__ __forceinline__ void search_block(const SearchArgs& a) {
         const size_t o = ((size_t)chunk * a.Q + q0 + q) * k + p;
         a.out_s[o] = ok ? Ls[q * k + p] : -INFINITY;
         a.out_i[o] = ok ? ib + Li[q * k + p] : (int64_t)-1;
-        if constexpr (SUBJ == SR_LIVE) a.out_u[o] = ok ? sch[(unsigned)Li[q * k + p]] : -1;
-        if constexpr (SUBJ == SR_DISTINCT) a.out_u[o] = ok ? lu0[(size_t)cur * CT_QT * k + q * k + p] : -1;
+        if constexpr (OUT_U && SUBJ == SR_LIVE) a.out_u[o] = ok ? sch[(unsigned)Li[q * k + p]] : -1;
+        if constexpr (OUT_U && SUBJ == SR_DISTINCT) a.out_u[o] = ok ? lu0[(size_t)cur * CT_QT * k + q * k + p] : -1;
     }
 }
 

@@ -122,6 +122,8 @@ SYMBOLS = [
     ('ffr_topk_merge_subjects', C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     ('ffr_coarse_pack', C.c_int, [_P, _P, _P, C.c_longlong, C.c_int, _P, _P, _P]),
     ('ffr_search_topk_coarse', C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, C.c_longlong, C.c_int, C.c_int, C.c_longlong, _P, _P, _P, _P]),
+    ('ffr_search_topk_coarse_subjects', C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, _P, C.c_longlong, C.c_int, C.c_int, C.c_longlong, C.c_int,
+                                                  _P, _P, _P, _P, _P]),
     ('ffr_cluster_threshold', C.c_int, [_P, _P, _P, C.c_longlong, C.c_int, C.c_float, _P, _P]),
     ('ffr_cluster_templates', C.c_int, [_P, _P, _P, _P, _P, C.c_longlong, C.c_int, _P, _P]),
     ('ffr_cluster_extend', C.c_int, [_P, _P, _P, C.c_longlong, C.c_longlong, C.c_int, C.c_float, _P, _P, _P]),
@@ -447,15 +449,13 @@ class Engine(object):
             self._call(self.lib.ffr_row_norms, _ptr(x), x.size(0), x.size(1), _ptr(out))
         return out
 
-    def search(self, query, gallery, k, gallery_norms=None, index_base=0):
-        """Exact cosine top-k: query[Q,512], gallery[G,512] (device fp32) -> (scores[Q,k] fp32, index[Q,k] int64), per
-        probe by descending score, ties by ascending index; index = index_base + gallery row; (-inf, -1) pads G < k.
-        gallery_norms[G]: row_norms(gallery), computed here when not given (pass them when the gallery is reused)."""
+    def _search_inputs(self, query, gallery, gallery_norms, who):
+        """The checks every search shares -> (query, gallery, gallery_norms, G), contiguous; the norms computed when not given"""
         self._tensor(query, 'query')
         self._tensor(gallery, 'gallery')
         if query.dim() != 2 or gallery.dim() != 2 or query.size(1) != gallery.size(1):
-            raise RuntimeError('ffrnet_amd: search expects query [Q,dim] and gallery [G,dim], got %s and %s'
-                               % (list(query.shape), list(gallery.shape)))
+            raise RuntimeError('ffrnet_amd: %s expects query [Q,dim] and gallery [G,dim], got %s and %s'
+                               % (who, list(query.shape), list(gallery.shape)))
         query, gallery = query.contiguous(), gallery.contiguous()
         G = gallery.size(0)
         if gallery_norms is None:
@@ -465,6 +465,13 @@ class Engine(object):
             if tuple(gallery_norms.shape) != (G,):
                 raise RuntimeError('ffrnet_amd: gallery_norms must be [%d], got %s' % (G, list(gallery_norms.shape)))
             gallery_norms = gallery_norms.contiguous()
+        return query, gallery, gallery_norms, G
+
+    def search(self, query, gallery, k, gallery_norms=None, index_base=0):
+        """Exact cosine top-k: query[Q,512], gallery[G,512] (device fp32) -> (scores[Q,k] fp32, index[Q,k] int64), per
+        probe by descending score, ties by ascending index; index = index_base + gallery row; (-inf, -1) pads G < k.
+        gallery_norms[G]: row_norms(gallery), computed here when not given (pass them when the gallery is reused)."""
+        query, gallery, gallery_norms, G = self._search_inputs(query, gallery, gallery_norms, 'search')
         Q, k = query.size(0), int(k)
         scores, index = self._empty(Q, max(k, 0)), self._empty(Q, max(k, 0), dtype=torch.int64)
         self._call(self.lib.ffr_search_topk, _ptr(query), Q, _ptr(gallery if G else None), _ptr(gallery_norms), G,
@@ -490,23 +497,10 @@ class Engine(object):
         (scores[Q,k], index[Q,k]) bit for bit.  plane[G,512] int16 and flag int32 [1] come from coarse_pack over the same
         rows and norms.  return_certified: also certified[Q] int32, 1 where the shortlist was proven to hold the top-k,
         0 where the probe went through the exact search."""
-        self._tensor(query, 'query')
-        self._tensor(gallery, 'gallery')
-        if query.dim() != 2 or gallery.dim() != 2 or query.size(1) != gallery.size(1):
-            raise RuntimeError('ffrnet_amd: search_coarse expects query [Q,dim] and gallery [G,dim], got %s and %s'
-                               % (list(query.shape), list(gallery.shape)))
-        query, gallery = query.contiguous(), gallery.contiguous()
-        G = gallery.size(0)
+        query, gallery, gallery_norms, G = self._search_inputs(query, gallery, gallery_norms, 'search_coarse')
         self._tensor(plane, 'plane', torch.int16, shape=(G, gallery.size(1)))
         self._tensor(flag, 'flag', torch.int32, shape=(1,))
         plane = plane.contiguous()
-        if gallery_norms is None:
-            gallery_norms = self.row_norms(gallery) if G else None
-        else:
-            self._tensor(gallery_norms, 'gallery_norms')
-            if tuple(gallery_norms.shape) != (G,):
-                raise RuntimeError('ffrnet_amd: gallery_norms must be [%d], got %s' % (G, list(gallery_norms.shape)))
-            gallery_norms = gallery_norms.contiguous()
         Q, k = query.size(0), int(k)
         scores, index = self._empty(Q, max(k, 0)), self._empty(Q, max(k, 0), dtype=torch.int64)
         cert = self._empty(Q, dtype=torch.int32)
@@ -543,21 +537,8 @@ class Engine(object):
         < 0 = a removed row, which is never returned.  distinct=True (k <= 64): the top-k SUBJECTS, each once, by its best
         row (maximum score, then smallest index); distinct=False (k <= 128): the top-k live rows
         -> (scores[Q,k] fp32, index[Q,k] int64, subjects[Q,k] int32); (-inf, -1, -1) pads."""
-        self._tensor(query, 'query')
-        self._tensor(gallery, 'gallery')
-        if query.dim() != 2 or gallery.dim() != 2 or query.size(1) != gallery.size(1):
-            raise RuntimeError('ffrnet_amd: search_subjects expects query [Q,dim] and gallery [G,dim], got %s and %s'
-                               % (list(query.shape), list(gallery.shape)))
-        query, gallery = query.contiguous(), gallery.contiguous()
-        G = gallery.size(0)
+        query, gallery, gallery_norms, G = self._search_inputs(query, gallery, gallery_norms, 'search_subjects')
         subjects = self._subjects(subjects, 'subjects', (G,))
-        if gallery_norms is None:
-            gallery_norms = self.row_norms(gallery) if G else None
-        else:
-            self._tensor(gallery_norms, 'gallery_norms')
-            if tuple(gallery_norms.shape) != (G,):
-                raise RuntimeError('ffrnet_amd: gallery_norms must be [%d], got %s' % (G, list(gallery_norms.shape)))
-            gallery_norms = gallery_norms.contiguous()
         Q, k = query.size(0), int(k)
         scores, index = self._empty(Q, max(k, 0)), self._empty(Q, max(k, 0), dtype=torch.int64)
         subj = self._empty(Q, max(k, 0), dtype=torch.int32)
@@ -565,6 +546,26 @@ class Engine(object):
                    _ptr(subjects if G else None), G, query.size(1), k, int(index_base), int(bool(distinct)), _ptr(scores),
                    _ptr(index), _ptr(subj))
         return scores, index, subj
+
+    def search_coarse_subjects(self, query, gallery, plane, flag, subjects, k, gallery_norms=None, index_base=0, distinct=True,
+                               return_certified=False):
+        """search_subjects() through the certified bf16 shortlist (include/ffrnet.h: ffr_search_topk_coarse_subjects): the
+        same (scores[Q,k], index[Q,k], subjects[Q,k]) bit for bit, in both modes and under every removal pattern.  plane and
+        flag as search_coarse() takes them, subjects[G] as search_subjects() does.  The pass serves k <= 32 identities
+        (distinct=True) and k <= 64 rows; above, the exact search runs alone.  return_certified: also certified[Q] int32."""
+        query, gallery, gallery_norms, G = self._search_inputs(query, gallery, gallery_norms, 'search_coarse_subjects')
+        self._tensor(plane, 'plane', torch.int16, shape=(G, gallery.size(1)))
+        self._tensor(flag, 'flag', torch.int32, shape=(1,))
+        plane = plane.contiguous()
+        subjects = self._subjects(subjects, 'subjects', (G,))
+        Q, k = query.size(0), int(k)
+        scores, index = self._empty(Q, max(k, 0)), self._empty(Q, max(k, 0), dtype=torch.int64)
+        subj = self._empty(Q, max(k, 0), dtype=torch.int32)
+        cert = self._empty(Q, dtype=torch.int32)
+        self._call(self.lib.ffr_search_topk_coarse_subjects, _ptr(query), Q, _ptr(gallery if G else None), _ptr(gallery_norms),
+                   _ptr(plane if G else None), _ptr(flag), _ptr(subjects if G else None), G, query.size(1), k, int(index_base),
+                   int(bool(distinct)), _ptr(scores), _ptr(index), _ptr(subj), _ptr(cert))
+        return (scores, index, subj, cert) if return_certified else (scores, index, subj)
 
     def topk_merge_subjects(self, scores, index, subjects, distinct=True):
         """topk_merge() of lists that carry subjects: scores[S,Q,k] fp32, index[S,Q,k] int64, subjects[S,Q,k] int32 or

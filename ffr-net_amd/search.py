@@ -13,6 +13,9 @@ Gallery(engine, coarse=True) keeps a bf16 plane beside the rows (1 KB per row mo
 shortlist (include/ffrnet.h: ffr_search_topk_coarse): the same results bit for bit, the pass over the gallery on the bf16
 matrix cores.  Gallery.last_certified says which probes of the last search the shortlist was proven for.
 
+A gallery with subjects gets the shortlist through build_plane() (include/ffrnet.h: ffr_search_topk_coarse_subjects): from
+then on search_subjects() and search() rank through the bf16 pass, bit for bit as before, and set last_certified.
+
 Gallery(engine, subjects=True) keeps a subject id beside every row (include/ffrnet.h: ffr_search_topk_subjects): an enrolled
 person is several rows, and search_subjects() answers with the top-k PEOPLE, each once, by their best row:
 
@@ -31,13 +34,17 @@ except ImportError:            # pragma: no cover
 
 DIM = 512
 COARSE_EPS = 2.0 ** -8 + 2.0 ** -12      # bound on |coarse score - exact score| (FFR_COARSE_EPS of include/ffrnet.h)
-COARSE_MAX_K = 64                        # the coarse pass serves k <= 64
+COARSE_MAX_K = 64                        # the coarse pass serves k <= 64 rows
+COARSE_MAX_K_DISTINCT = 32               # and k <= 32 identities
 
 
-def shortlist_size(k):
+def shortlist_size(k, distinct=False):
     """Rows the coarse pass lists per probe for a top-k: min(128, max(2k, 32)); None for k > 64, where the exact search
-    runs alone."""
+    runs alone.  distinct=True, for a top-k of identities: min(128, max(4k, 64)) -- a person's rows crowd the head of the
+    list -- and None for k > 32."""
     k = int(k)
+    if distinct:
+        return None if k > COARSE_MAX_K_DISTINCT else min(128, max(4 * k, 64))
     if k > COARSE_MAX_K:
         return None
     return min(128, max(2 * k, 32))
@@ -49,12 +56,13 @@ class Gallery(object):
     unsafe-norm flag grow beside them, add() packs the rows it appends, and search() goes through the certified shortlist
     (the same results; last_certified[Q] int32 tells which probes were certified).  subjects=True: a subject id (int32)
     grows beside every row, add() takes the ids, search_subjects() ranks subjects, remove() withdraws subjects (their rows
-    stay in place, marked -1, and search() skips them) and compact() drops the removed rows."""
+    stay in place, marked -1, and search() skips them) and compact() drops the removed rows.  build_plane() switches the
+    shortlist on for the rows a gallery holds already, with or without subjects."""
 
     def __init__(self, engine, capacity=0, coarse=False, subjects=False):
         if coarse and subjects:
             raise RuntimeError('ffrnet_amd: Gallery(coarse=True, subjects=True): the certified shortlist does not know '
-                               'subjects yet')
+                               'subjects yet at construction; create Gallery(subjects=True) and call build_plane()')
         self.engine = engine
         self._n = 0
         self._emb = torch.empty((int(capacity), DIM), device=engine.device, dtype=torch.float32)
@@ -151,6 +159,19 @@ class Gallery(object):
         self._n = first + n
         return first
 
+    def build_plane(self):
+        """Switch the certified shortlist on for this gallery: pack the bf16 plane and the unsafe-norm flag of the rows held
+        (one coarse_pack over all of them), set coarse = True; from then on add() packs what it appends.  The way a gallery
+        with subjects gets the pass; any gallery can switch it on without enrolling again.  Does nothing on a gallery that
+        has a plane."""
+        if self.coarse:
+            return
+        self._plane = torch.empty((self._emb.size(0), DIM), device=self._emb.device, dtype=torch.int16)
+        self._flag = torch.zeros((1,), device=self._emb.device, dtype=torch.int32)
+        if self._n:
+            self.engine.coarse_pack(self.embeddings, self.norms, self._plane[:self._n], self._flag)
+        self.coarse = True
+
     def search(self, query, k, self_index=None, index_base=0):
         """Top-k enrolled rows of every probe query[Q,512] -> (scores[Q,k], index[Q,k]).  self_index[Q] (gallery
         indices of the probes themselves): leave-one-out search, the probe's own row is never returned."""
@@ -163,9 +184,18 @@ class Gallery(object):
         """Top-k enrolled SUBJECTS of every probe query[Q,512], each once, by its best row -> (scores[Q,k],
         subjects[Q,k] int32, index[Q,k]); k <= 64; (-inf, -1, -1) pads when fewer than k subjects are enrolled."""
         self._need_subjects('search_subjects')
-        s, i, u = self.engine.search_subjects(query, self.embeddings, self.subjects, k, gallery_norms=self.norms,
-                                              index_base=index_base, distinct=True)
+        s, i, u = self._search_subjects(query, k, index_base, True)
         return s, u, i
+
+    def _search_subjects(self, query, k, index_base, distinct):
+        """(scores, index, subjects) of a gallery with subjects, through the shortlist when it has a plane"""
+        if not self.coarse:
+            return self.engine.search_subjects(query, self.embeddings, self.subjects, k, gallery_norms=self.norms,
+                                               index_base=index_base, distinct=distinct)
+        s, i, u, self.last_certified = self.engine.search_coarse_subjects(
+            query, self.embeddings, self.plane, self._flag, self.subjects, k, gallery_norms=self.norms, index_base=index_base,
+            distinct=distinct, return_certified=True)
+        return s, i, u
 
     def remove(self, subject_ids):
         """Withdraw subjects: every row of theirs is marked removed (-1) on the device and never returned again; rows keep
@@ -178,8 +208,9 @@ class Gallery(object):
         return int(hit.sum().item())
 
     def compact(self):
-        """Drop the removed rows physically: the live rows, their norms and ids move up unchanged (no norm is computed
-        again, so scores keep their bits) -> int64 [old len]: old index -> new index, -1 for a removed row."""
+        """Drop the removed rows physically: the live rows, their norms, ids and plane rows move up unchanged (no norm is
+        computed again, so scores keep their bits; the unsafe-norm flag stays as it is, set or not: conservative)
+        -> int64 [old len]: old index -> new index, -1 for a removed row."""
         self._need_subjects('compact')
         keep = self.subjects >= 0
         new_index = torch.cumsum(keep.to(torch.int64), 0) - 1
@@ -188,13 +219,14 @@ class Gallery(object):
         self._emb[:n] = self.embeddings[keep]
         self._norms[:n] = self.norms[keep]
         self._subj[:n] = self.subjects[keep]
+        if self.coarse:
+            self._plane[:n] = self.plane[keep]
         self._n = n
         return new_index
 
     def _search(self, query, k, index_base):
         if self.has_subjects:           # row mode under the mask: removed rows never come back
-            s, i, _ = self.engine.search_subjects(query, self.embeddings, self.subjects, k, gallery_norms=self.norms,
-                                                  index_base=index_base, distinct=False)
+            s, i, _ = self._search_subjects(query, k, index_base, False)
             return s, i
         if not self.coarse:
             return self.engine.search(query, self.embeddings, k, gallery_norms=self.norms, index_base=index_base)

@@ -210,6 +210,40 @@ int ffr_coarse_pack(ffr_handle* h, const float* rows, const float* norms, long l
 int ffr_search_topk_coarse(ffr_handle* h, const float* query, int Q, const float* gallery, const float* gallery_norms,
                            const uint16_t* gallery_plane, const int* plane_flag, long long G, int dim, int k,
                            long long index_base, float* top_score, int64_t* top_index, int* certified, void* stream);
+/* The shortlist search of a subject-labelled gallery: the outputs of ffr_search_topk_subjects with the same arguments, bit
+ * for bit, for every input without NaN/inf, every removal pattern and both modes.
+ *   method the pass over the plane ranks ROWS in both modes and skips the removed ones (gallery_subject < 0): per probe the
+ *          k' best live rows by (descending c, ascending index).  It never merges subjects.  The k' rows are scored exactly,
+ *          subject[row] is read again, and identities are formed on those <= 128 entries: in the order of
+ *          ffr_search_topk_subjects an entry is ALIVE iff no other entry of its subject comes before it; the answer of
+ *          distinct = 1 is the first k alive entries, s_k the score of the k-th.  distinct = 0 lists the first k entries.
+ *   k'     distinct = 0: min(128, max(2k, 32)), k <= 64, as ffr_search_topk_coarse.  distinct = 1: min(128, max(4k, 64)),
+ *          k <= 32 -- the rows of one person crowd the head of the list (about 8 of them where a person has 8), and at 2k
+ *          the k-th identity falls off the list too often to be worth the pass.  For larger k (distinct = 0: 64 < k <= 128,
+ *          distinct = 1: 32 < k <= 64) and for G = 0 ffr_search_topk_subjects runs alone and every probe is reported
+ *          uncertified.
+ *   certificate  L is the shortlist, c_1 >= ... >= c_k' its coarse scores.  Every live row outside L has c <= c_k', hence
+ *          s <= c_k' + FFR_COARSE_EPS.  The probe is certified iff the plane flag is clear, its norm is safe, and either L
+ *          holds fewer than k' rows or G <= k' (then L is every live row: with removals G > k' no longer means a full list), or
+ *          (distinct = 1) at least k entries are alive, and c_k' + FFR_COARSE_EPS < s_k, strictly; distinct = 0 takes the
+ *          k-th entry for the k-th alive one.
+ *          Identities: let u be one of the first k alive entries.  Its alive entry scores >= s_k > every row outside L, so no
+ *          row of u outside L beats or ties it: it is best(u) over the whole gallery.  A subject v that is not among them
+ *          has its best row in L behind the k-th alive entry, or no row in L, and then best(v) < s_k.  So the first k of
+ *          {best(u)} over the gallery are the first k alive entries of L, scores and indices included.  A full shortlist
+ *          with fewer than k alive entries is NOT certified -- more subjects may lie outside (one person enrolled with more
+ *          rows than the list holds).
+ *   exact  the probes without a certificate are gathered and searched by the kernels of ffr_search_topk_subjects, which take
+ *          the device count of such probes; always launched, sized for Q, no host synchronisation: the call can be captured
+ *          into a hipGraph once it has run at that shape.  Scratch comes from the handle's search arena.
+ * Arguments and error codes are the union of ffr_search_topk_coarse and ffr_search_topk_subjects: FFR_ERR_ARG for k > 64
+ * with distinct = 1, distinct outside {0, 1}, rows or plane not 16-byte aligned, subjects not 4-byte aligned, a NULL output,
+ * and a NULL gallery pointer (rows, norms, plane, flag, subjects) unless G = 0; FFR_ERR_UNSUPPORTED for dim != 512.
+ * certified[Q] may be NULL.  Profiled as one launch under FFR_KC_SCORE with flops = 2*Q*G*512.                          */
+int ffr_search_topk_coarse_subjects(ffr_handle* h, const float* query, int Q, const float* gallery, const float* gallery_norms,
+                                    const uint16_t* gallery_plane, const int* plane_flag, const int32_t* gallery_subject,
+                                    long long G, int dim, int k, long long index_base, int distinct, float* top_score,
+                                    int64_t* top_index, int32_t* top_subject, int* certified, void* stream);
 
 /* ---- clustering (unlabelled embeddings -> identities -> one template per identity) ----------------------------------
  * The step in front of enrolment: N unlabelled faces are grouped by single-link clustering at one cosine threshold, and
