@@ -1,4 +1,5 @@
-"""Grouping unlabelled embeddings into identities (include/ffrnet.h: ffr_cluster_threshold, ffr_cluster_templates).
+"""Grouping unlabelled embeddings into identities (include/ffrnet.h: ffr_cluster_threshold, ffr_cluster_density,
+ffr_cluster_templates).
 
 A photo collection or a dump of video tracks arrives as N unlabelled faces; before the first Gallery.add they have to be
 grouped by person and every group fused into one template row:
@@ -9,6 +10,15 @@ grouped by person and every group fused into one template row:
 
 The clustering is single-link at one cosine threshold: rows i < j are joined iff their search score is > threshold, and
 a cluster is a connected component of those edges.  It runs on the device; only pairwise_scores() is host logic.
+
+Single link lets a few in-between rows (a blurred frame, a half-occluded face, a look-alike) join two people into one
+cluster, whose template is then a mixture.  density() gates the same edges by density (DBSCAN): a row with fewer than
+min_rows rows within the threshold of it (itself counted) may attach to a cluster but never connects two, and a row with
+no dense neighbour is reported as noise instead of being enrolled as a one-row identity:
+
+  c = cluster.density(engine, f, threshold, min_rows=4)
+  t = cluster.templates(engine, f, c)[c.has_core]    # the clusters with a core; gallery row r is the r-th of them
+  gallery.add(t)
 
 A collection that keeps growing is extended instead of clustered again (include/ffrnet.h: ffr_cluster_extend): only the
 pairs that involve a new row are scored, and the result is the clustering of all rows at once, label for label:
@@ -26,6 +36,11 @@ Clusters.__doc__ = """rep[N] int64: the smallest row index of each row's cluster
 order of representative; n_clusters: C (int); sizes[C] int64: rows per cluster."""
 
 
+DensityClusters = collections.namedtuple('DensityClusters', ['rep', 'cluster_id', 'n_clusters', 'sizes', 'kind', 'has_core'])
+DensityClusters.__doc__ = """rep, cluster_id, n_clusters, sizes: as Clusters (member_order and templates accept either); kind[N]
+uint8: 2 core, 1 border, 0 noise; has_core[C] bool: False exactly for the noise singletons."""
+
+
 def dense_ids(rep):
     """rep[N] (any device) -> Clusters: ids 0 .. C-1 by ascending representative."""
     rep = torch.as_tensor(rep)
@@ -36,6 +51,23 @@ def dense_ids(rep):
 def cluster(engine, emb, threshold, norms=None):
     """Single-link clustering of emb[N,512] (fp32, on the Engine's device) at `threshold` -> Clusters."""
     return dense_ids(engine.cluster(emb, threshold, norms=norms))
+
+
+def density_ids(rep, kind):
+    """rep[N], kind[N] (any device) -> DensityClusters.  A noise row is alone in its cluster and every other cluster holds
+    a core row, so has_core is False exactly where the cluster's rows are noise."""
+    c = dense_ids(rep)
+    kind = torch.as_tensor(kind)
+    has_core = torch.zeros((c.n_clusters,), device=c.cluster_id.device, dtype=torch.bool)
+    has_core[c.cluster_id[kind.to(c.cluster_id.device) == 2]] = True
+    return DensityClusters(c.rep, c.cluster_id, c.n_clusters, c.sizes, kind, has_core)
+
+
+def density(engine, emb, threshold, min_rows, norms=None):
+    """Density-gated clustering of emb[N,512] (fp32, on the Engine's device) over the edges of cluster() -> DensityClusters:
+    rows with at least min_rows rows within `threshold` (themselves counted) are core and link; the others attach to their
+    best-scoring core neighbour or are noise.  templates(engine, emb, c)[c.has_core] is what gets enrolled."""
+    return density_ids(*engine.cluster_density(emb, threshold, min_rows, norms=norms))
 
 
 def representatives(labels):

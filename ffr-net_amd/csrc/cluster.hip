@@ -1,7 +1,8 @@
 // cluster.hip -- group N unlabelled 512-d embeddings into identities on the device (include/ffrnet.h:
-// ffr_cluster_threshold / ffr_cluster_extend / ffr_cluster_templates): single-link clustering at one cosine threshold,
-// extended batch by batch where the collection grows, then one template row per cluster.  The N x N score matrix never
-// leaves the chip; the output is one label per row.
+// ffr_cluster_threshold / ffr_cluster_extend / ffr_cluster_density / ffr_cluster_templates): single-link clustering at one
+// cosine threshold, extended batch by batch where the collection grows, or gated by density over the same edges (core rows
+// link, border rows attach, noise stays alone), then one template row per cluster.  The N x N score matrix never leaves the
+// chip; the output is one label per row.
 //
 // Edge rule: rows i < j are joined iff s(probe = i, gallery row = j) > threshold (strict, as eval_acc compares), with
 // s = dot / (|i| |j| + 1e-8) in exactly the fp32 arithmetic of k_search_topk (search.hip): the score of (i, j) is
@@ -10,7 +11,10 @@
 // k_cluster_init     parent[x] = x.
 // k_cluster_seed     ffr_cluster_extend's start: parent[x] = prior[x] where 0 <= prior[x] <= x, else x.  The only place
 //                    where caller data reaches parent[]; see "Seeded start" below.
-// k_cluster_join     the hot path: the self-join of the [N][512] array with itself.
+// k_cluster_walk     the hot path: the self-join of the [N][512] array with itself, one body (block map, early return,
+//                    step0, probe fill, norm prefetch, K loop, scores, edge mask) with the epilogue as a parameter.
+//                    <RANGE, EdgesUnite> is the join of single link, described first; EdgesDegree and EdgesGated are the
+//                    two passes of ffr_cluster_density, see "Density" below.
 //  - K loop: the 32 x 128 cosine tile of cosine_tile.h, the one k_search_topk instantiates: the bitwise identity of the edge
 //    scores with the scores of ffr_search_topk is structural.
 //  - Triangle: a block is (chunk of rows, tile of 32 probes), logical id as in the search.  A block whose chunk ends at
@@ -19,14 +23,15 @@
 //    sizes the chunks so that the blocks with work, about half of it, fill the CUs several times over: their work is uneven
 //    along the diagonal); the idle half costs one early return each.  Known cost (EXPERIMENTS.md): an XCD takes a
 //    contiguous run of tiles, so the XCD with the long rows of the triangle finishes last.
-//  - Row range: k_cluster_join<true> (ffr_cluster_extend) lays the chunks over the rows [first, N) only and the tiles over
+//  - Row range: k_cluster_walk<true, .> (ffr_cluster_extend) lays the chunks over the rows [first, N) only and the tiles over
 //    all probes [0, N): the pairs i < j with j >= first, i.e. the first x (N - first) rectangle plus the triangle among
 //    the new rows.  Chunk bases, the early return, step0 and the edge test work on absolute row numbers; with first = 0
-//    they are those of k_cluster_join<false>, the instantiation ffr_cluster_threshold launches, which is compiled with the
+//    they are those of k_cluster_walk<false, .>, the instantiation ffr_cluster_threshold launches, which is compiled with the
 //    constant 0.  All tiles of one chunk of new rows are neighbours in the XCD-contiguous block map, and the old rows are
 //    read once per chunk into LDS as probes.  Over the old rows no block is idle and none sits on the diagonal.
-//  - Epilogue: no list, no LDS merge.  Lane (n, h) holds the 16 scores of probe q0 + n; every (i, j) with i < j, j inside
-//    the chunk and score > threshold is united in a lock-free union-find over parent[N] (int32, the handle's scratch):
+//  - Epilogue (EdgesUnite): no list, no LDS merge.  Lane (n, h) holds the 16 scores of probe q0 + n; every (i, j) with
+//    i < j, j inside the chunk and score > threshold is united in a lock-free union-find over parent[N] (int32, the
+//    handle's scratch):
 //      find   walk parent[] to a root r (parent[r] == r);
 //      unite  roots equal -> done (tested with loads only: inside a formed cluster almost every edge is redundant, and
 //             loads are cheap where atomics are not); else atomicCAS(&parent[big], big, small), agent scope, which hooks
@@ -51,6 +56,24 @@
 //    smaller members of other trees, and every tree keeps one root, its smallest row.  The components at the end are those
 //    of (links x - prior[x]) + (scored edges), and the flattened result is their smallest row whatever the order.  A deep
 //    prior (prior[x] = x - 1) is legal and walked hop by hop: callers pass flattened labels.
+//  - Density (ffr_cluster_density): k_density_init (parent[x] = x, degree[x] = 0, best[x] = 0), then two walks of the
+//    triangle with the same body, so both see the edge mask single link sees, then three N-sized kernels.
+//      EdgesDegree  degree[x] += edges at x.  The probe side is summed in a register and added once per block; the row side
+//                   per step: a wave ballot of bit r of the mask, the popcount of each 32-lane half (the 32 probes against
+//                   one row), one vector atomic of up to 32 counts per wave.  Integer adds commute.
+//      EdgesGated   core(x) = degree[x] + 1 >= min_rows, read once per block for the probe and ahead of the K loop for the
+//                   lane's 16 rows.  Both ends core: uf_unite, as above.  One end core: a 64-bit atomic max of
+//                   (ordered score bits << 32 | 0xFFFFFFFF - core row) into best[non-core row]: the highest score wins,
+//                   then the smallest core row, whatever the order.  Neither: nothing.
+//      k_density_root / k_density_min / k_density_label: root[i] = find(i) for a core row, find(the core row of best[i]) for
+//                   a border row, i for noise; minrow[root[i]] = min over the members (atomicMin; only a border row can be
+//                   smaller than the root, the smallest core row); rep[i] = minrow[root[i]], kind[i], degree[i].
+//    The safety argument carries over unchanged: nothing here waits on another wave.  Only core rows enter the
+//    union-find, through the same uf_unite, so every parent[] walk (also the finds of k_density_root, which run after the
+//    join in stream order) keeps parent[x] <= x and descends.  The degree adds, the 64-bit max and the min are single
+//    no-return vector atomics at agent scope without a retry loop; there is no scalar memory write anywhere.  Every index
+//    is a row the edge mask admitted (< N) or a prefetch clamped to the chunk's last row; the core row read back from
+//    best[] was written as a row < N, and best[] is zeroed first (a real key is never 0: its low word is >= 2^31).
 // k_cluster_flatten  rep[i] = find(i) as int64, after the join in stream order.
 // k_cluster_templates  one template per cluster: t = sum_r x_r / |x_r| over the cluster's rows in ascending row index
 //                (order[] = rows sorted by cluster then index, offsets[C + 1]), then t / |t|.  One wave per cluster, lane
@@ -124,11 +147,124 @@ struct JoinArgs {
     float threshold;
     int nchunks, ntiles;
     long long first;          // RANGE: the chunks cover the rows [first, N)
+    // ffr_cluster_density only
+    int* degree;              // [N]
+    unsigned long long* best; // [N]
+    int min_rows;
 };
 
-// RANGE = false: the chunks cover all rows (first is not read)
-template <bool RANGE>
-__global__ __launch_bounds__(256, 1) void k_cluster_join(const JoinArgs a) {
+// What a lane does with the edges of one step (EdgesUnite, EdgesDegree, EdgesGated below):
+//   E(a, irow, live)   once per block; irow = the lane's probe row, live = it exists
+//   rows_ahead(...)    ahead of the K loop, where gn[] is fetched: per-row data of the 16 rows the lane scores
+//   step(...)          after the scores: mask has bit r set iff (irow, row of accumulator element r) is an edge.  Called by
+//                      all 64 lanes of every wave in every step (the step loop is uniform in a block): wave ballots are legal
+//   done(irow)         after the last step
+// Single link: every edge is united.
+struct EdgesUnite {
+    int* parent;
+    __device__ __forceinline__ EdgesUnite(const JoinArgs& a, int, bool) : parent(a.parent) {}
+    __device__ __forceinline__ void rows_ahead(long long, int, int, int, int) {}
+    __device__ __forceinline__ void step(unsigned mask, const f32x16&, float, const float (&)[16], int irow, long long j0, int w,
+                                         int h, int) {
+        while (mask) {
+            const int r = __builtin_ctz(mask);
+            mask &= mask - 1;
+            const int jrow = (int)(j0 + cosine_lane_row(w, r, h));      // < N < 2^31
+            uf_unite(parent, irow, jrow);
+        }
+    }
+    __device__ __forceinline__ void done(int) {}
+};
+
+__device__ __forceinline__ void degree_add(int* p, int v) {
+    __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// Degree pass: degree[x] += the edges at x.  Integer adds commute: any grouping gives the same sums.  Probe side: the
+// lane's edges of all steps are counted in a register and added once per block.  Row side: the 32 lanes of half h hold the
+// 32 probes against the same row of accumulator element r, so the popcount of that half of a wave ballot of bit r is the
+// row's count in this step; lane (n = r, h) keeps it, and one vector atomic per wave and step adds the up to 32 counts.
+struct EdgesDegree {
+    int* degree;
+    int mine;
+    __device__ __forceinline__ EdgesDegree(const JoinArgs& a, int, bool) : degree(a.degree), mine(0) {}
+    __device__ __forceinline__ void rows_ahead(long long, int, int, int, int) {}
+    __device__ __forceinline__ void step(unsigned mask, const f32x16&, float, const float (&)[16], int, long long j0, int w, int h,
+                                         int n) {
+        mine += __builtin_popcount(mask);
+        int cnt = 0;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const unsigned long long b = __ballot((mask >> r) & 1u);
+            const int c = __builtin_popcount(h ? (unsigned)(b >> 32) : (unsigned)b);
+            if (n == r) cnt = c;
+        }
+        // cnt > 0 only for n < 16 and a row inside the chunk (the edge mask tests it)
+        if (cnt) degree_add(degree + (j0 + cosine_lane_row(w, n & 15, h)), cnt);
+    }
+    __device__ __forceinline__ void done(int irow) {
+        if (mine) degree_add(degree + irow, mine);          // mine > 0 needs an edge, and an edge a live probe
+    }
+};
+
+// fp32 bits -> uint32 in the order of the values (-0 below +0; no NaN arrives: an edge has score > threshold)
+__device__ __forceinline__ unsigned ordered_bits(float f) {
+    const unsigned u = __float_as_uint(f);
+    return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
+}
+
+// Gated join, after the degree pass in stream order.  core(x) = degree[x] + 1 >= min_rows.  An edge between two core rows
+// is united as in single link (only core rows ever enter the union-find); an edge between a core row c and a non-core row
+// x offers c to x: best[x] = max(best[x], (ordered score << 32) | (0xFFFFFFFF - c)), one 64-bit vector atomic max at agent
+// scope, no loop.  The maximum of a set does not depend on the order of its elements: the winner is the highest score,
+// among equal scores the smallest core row.  best[] starts at 0, and a real key is never 0 (its low word is >= 2^31).
+struct EdgesGated {
+    int* parent;
+    const int* degree;
+    unsigned long long* best;
+    int need;                 // min_rows - 1 >= 0
+    bool pcore;               // the lane's probe row is core
+    unsigned cmask;           // bit r: the row of accumulator element r is core
+    __device__ __forceinline__ EdgesGated(const JoinArgs& a, int irow, bool live)
+        : parent(a.parent), degree(a.degree), best(a.best), need(a.min_rows - 1), cmask(0) {
+        pcore = live && degree[irow] >= need;
+    }
+    __device__ __forceinline__ void rows_ahead(long long c0, int sbase, int w, int h, int rows) {
+        const int* __restrict__ dch = degree + c0;
+        cmask = 0;
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+            if (dch[(unsigned)min(acc_row(sbase + w * 32, r) + 4 * h, rows - 1)] >= need) cmask |= 1u << r;
+    }
+    __device__ __forceinline__ void step(unsigned mask, const f32x16& acc, float qn, const float (&gn)[16], int irow, long long j0,
+                                         int w, int h, int) {
+        unsigned both = pcore ? mask & cmask : 0u;
+        const unsigned one = mask & (pcore ? ~cmask : cmask);
+        if (one) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                if (!((one >> r) & 1u)) continue;
+                const int jrow = (int)(j0 + cosine_lane_row(w, r, h));
+                const int core = pcore ? irow : jrow, other = pcore ? jrow : irow;
+                const unsigned long long key =
+                    ((unsigned long long)ordered_bits(cosine_score(acc[r], qn, gn[r])) << 32) | (0xFFFFFFFFu - (unsigned)core);
+                __hip_atomic_fetch_max(best + other, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+        while (both) {
+            const int r = __builtin_ctz(both);
+            both &= both - 1;
+            uf_unite(parent, irow, (int)(j0 + cosine_lane_row(w, r, h)));
+        }
+    }
+    __device__ __forceinline__ void done(int) {}
+};
+
+// The walk over the pairs i < j, one body for every pass: RANGE = false: the chunks cover all rows (first is not read);
+// E: what happens to the edges.  The scores and the edge mask are the same code for every E, so the passes of
+// ffr_cluster_density see exactly the edge set of ffr_cluster_threshold.
+template <bool RANGE, class E>
+__global__ __launch_bounds__(256, 1) void k_cluster_walk(const JoinArgs a) {
     __shared__ __attribute__((aligned(16))) f32x4 qf[CT_NG * 64];    // probe fragments [64][64]
 
     const int tid = threadIdx.x, lane = tid & 63, n = lane & 31, h = lane >> 5;
@@ -148,6 +284,7 @@ __global__ __launch_bounds__(256, 1) void k_cluster_join(const JoinArgs a) {
     cosine_fill_probes(qf, a.emb, q0, nq, tid);
     const float qn_lane = n < nq ? a.norm[q0 + n] : 0.f;
     const int irow = q0 + n;                            // this lane's probe row (an edge needs n < nq)
+    E edges(a, irow, n < nq);
 
     const float* __restrict__ nch = a.norm + c0;
     CosineStream gs(a.emb + (size_t)c0 * CT_DIM, lane);
@@ -162,11 +299,12 @@ __global__ __launch_bounds__(256, 1) void k_cluster_join(const JoinArgs a) {
         float gn[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) gn[r] = nch[(unsigned)min(acc_row(sbase + w * 32, r) + 4 * h, rows - 1)];
+        edges.rows_ahead(c0, sbase, w, h, rows);
         f32x16 acc8[CT_NACC];
         gs.tile(acc8, qf, next);
         const f32x16 acc = COSINE_CHAIN_SUM(acc8);
 
-        // epilogue: scores, edge test (i < j inside the chunk, score > threshold), union
+        // scores, edge test (i < j inside the chunk, score > threshold); the epilogue gets the edges
         unsigned mask = 0;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -174,13 +312,52 @@ __global__ __launch_bounds__(256, 1) void k_cluster_join(const JoinArgs a) {
             const float sc = cosine_score(acc[r], qn_lane, gn[r]);
             if (n < nq && sbase + lr < rows && c0 + sbase + lr > (long long)irow && sc > a.threshold) mask |= 1u << r;
         }
-        while (mask) {
-            const int r = __builtin_ctz(mask);
-            mask &= mask - 1;
-            const int jrow = (int)(c0 + sbase + cosine_lane_row(w, r, h));      // < N < 2^31
-            uf_unite(a.parent, irow, jrow);
-        }
+        edges.step(mask, acc, qn_lane, gn, irow, c0 + sbase, w, h, n);
     }
+    edges.done(irow);
+}
+
+// root[i]: the union-find root of the cluster i belongs to.  A core row: its own; a border row (best[i] != 0): that of the
+// core row its key names; a noise row: itself (it never entered the union-find, and no row points at it).  minrow starts
+// at the row itself: a root is a member of its cluster.
+__global__ __launch_bounds__(256) void k_density_root(const int* __restrict__ parent, const int* __restrict__ degree,
+                                                      const unsigned long long* __restrict__ best, int min_rows, int n,
+                                                      int* __restrict__ root, int* __restrict__ minrow) {
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    if (x >= n) return;
+    int r = x;
+    if (degree[x] >= min_rows - 1) r = uf_find(parent, x);
+    else if (best[x]) r = uf_find(parent, (int)(0xFFFFFFFFu - (unsigned)best[x]));     // a core row of [0, n)
+    root[x] = r;
+    minrow[x] = x;
+}
+
+// the smallest member per cluster; a root is the smallest CORE row, so only a border row can lower it
+__global__ __launch_bounds__(256) void k_density_min(const int* __restrict__ root, int n, int* __restrict__ minrow) {
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    if (x < n && x < root[x]) __hip_atomic_fetch_min(minrow + root[x], x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__global__ __launch_bounds__(256) void k_density_label(const int* __restrict__ root, const int* __restrict__ minrow,
+                                                       const int* __restrict__ degree, const unsigned long long* __restrict__ best,
+                                                       int min_rows, int n, int64_t* __restrict__ rep, uint8_t* __restrict__ kind,
+                                                       int32_t* __restrict__ degree_out) {
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    if (x >= n) return;
+    const int d = degree[x];
+    rep[x] = minrow[root[x]];
+    kind[x] = d >= min_rows - 1 ? 2 : best[x] ? 1 : 0;
+    if (degree_out) degree_out[x] = d;
+}
+
+// parent[x] = x, degree[x] = 0, best[x] = 0
+__global__ __launch_bounds__(256) void k_density_init(int* __restrict__ parent, int* __restrict__ degree,
+                                                      unsigned long long* __restrict__ best, int n) {
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    if (x >= n) return;
+    parent[x] = x;
+    degree[x] = 0;
+    best[x] = 0;
 }
 
 struct TemplateArgs {
@@ -259,8 +436,8 @@ hipError_t launch_cluster_extend(const float* emb, const float* norms, long long
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     if (N > 1 && N_old < N) {
-        JoinArgs a{emb, norms, parent, N, chunk_rows, threshold, nchunks, ntiles, N_old};
-        hipLaunchKernelGGL(k_cluster_join<true>, dim3((unsigned)((long long)nchunks * ntiles)), dim3(256), 0, stream, a);
+        JoinArgs a{emb, norms, parent, N, chunk_rows, threshold, nchunks, ntiles, N_old, nullptr, nullptr, 0};
+        hipLaunchKernelGGL((k_cluster_walk<true, EdgesUnite>), dim3((unsigned)((long long)nchunks * ntiles)), dim3(256), 0, stream, a);
         e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
@@ -276,12 +453,42 @@ hipError_t launch_cluster_threshold(const float* emb, const float* norms, long l
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     if (N > 1) {
-        JoinArgs a{emb, norms, parent, N, chunk_rows, threshold, nchunks, ntiles, 0};
-        hipLaunchKernelGGL(k_cluster_join<false>, dim3((unsigned)((long long)nchunks * ntiles)), dim3(256), 0, stream, a);
+        JoinArgs a{emb, norms, parent, N, chunk_rows, threshold, nchunks, ntiles, 0, nullptr, nullptr, 0};
+        hipLaunchKernelGGL((k_cluster_walk<false, EdgesUnite>), dim3((unsigned)((long long)nchunks * ntiles)), dim3(256), 0, stream, a);
         e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(k_cluster_flatten, dim3(nb), dim3(256), 0, stream, (const int*)parent, (int)N, rep);
+    return hipGetLastError();
+}
+
+hipError_t launch_cluster_density(const float* emb, const float* norms, long long N, float threshold, int min_rows, int ntiles,
+                                  int nchunks, long long chunk_rows, int* parent, int* degree, int* root, int* minrow,
+                                  unsigned long long* best, int64_t* rep, uint8_t* kind, int32_t* degree_out, hipStream_t stream) {
+    if (N <= 0) return hipSuccess;
+    const unsigned nb = (unsigned)((N + 255) / 256);
+    hipLaunchKernelGGL(k_density_init, dim3(nb), dim3(256), 0, stream, parent, degree, best, (int)N);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    if (N > 1) {
+        JoinArgs a{emb, norms, parent, N, chunk_rows, threshold, nchunks, ntiles, 0, degree, best, min_rows};
+        const dim3 grid((unsigned)((long long)nchunks * ntiles));
+        hipLaunchKernelGGL((k_cluster_walk<false, EdgesDegree>), grid, dim3(256), 0, stream, a);
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL((k_cluster_walk<false, EdgesGated>), grid, dim3(256), 0, stream, a);
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k_density_root, dim3(nb), dim3(256), 0, stream, (const int*)parent, (const int*)degree,
+                       (const unsigned long long*)best, min_rows, (int)N, root, minrow);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_density_min, dim3(nb), dim3(256), 0, stream, (const int*)root, (int)N, minrow);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_density_label, dim3(nb), dim3(256), 0, stream, (const int*)root, (const int*)minrow, (const int*)degree,
+                       (const unsigned long long*)best, min_rows, (int)N, rep, kind, degree_out);
     return hipGetLastError();
 }
 

@@ -1,4 +1,4 @@
-// cosine_tile.h -- the 32 probes x 128 rows cosine tile of k_search_topk (search.hip) and k_cluster_join (cluster.hip): the
+// cosine_tile.h -- the 32 probes x 128 rows cosine tile of k_search_topk (search.hip) and k_cluster_walk (cluster.hip): the
 // block map, the probe fragments, the per-lane gallery stream with its K loop, the accumulator row map and the score
 // formula.  Both kernels instantiate this one definition, so the score of a (probe, row) pair is the same fp32 arithmetic in
 // either of them by construction.

@@ -546,6 +546,44 @@ int ffr_cluster_extend(ffr_handle* h, const float* emb, const float* norms, long
     return cluster_rows(h, "ffr_cluster_extend", true, emb, norms, N_old, N, dim, threshold, prior, rep, stream);
 }
 
+int ffr_cluster_density(ffr_handle* h, const float* emb, const float* norms, long long N, int dim, float threshold, int min_rows,
+                        int64_t* rep, uint8_t* kind, int32_t* degree, void* stream) {
+    const char* who = "ffr_cluster_density";
+    FFR_DEVICE_SCOPE(h); RC(check_fwd(h, false, false, 1));
+    RC(check_dim(h, who, dim));
+    if (N < 0 || N >= (1ll << 31)) return fail(h, FFR_ERR_ARG, "%s: N must be in [0, 2^31), got %lld", who, N);
+    if (threshold != threshold) return fail(h, FFR_ERR_ARG, "%s: the threshold is NaN", who);
+    if (min_rows < 1) return fail(h, FFR_ERR_ARG, "%s: min_rows must be >= 1, got %d", who, min_rows);
+    if (N == 0) return FFR_OK;
+    if (!emb || !rep || !kind) return fail(h, FFR_ERR_ARG, "%s: emb / rep / kind is null", who);
+    if (misaligned16(emb) || ((uintptr_t)rep & 7) || ((uintptr_t)degree & 3) || ((uintptr_t)norms & 3))
+        return fail(h, FFR_ERR_ARG, "%s: emb rows must be 16-byte aligned (rep 8, degree and norms 4)", who);
+    int T = 0, S = 0;
+    long long chunk_rows = 0;
+    cluster_plan(N, h->num_cus, &T, &S, &chunk_rows);
+    if ((long long)T * S >= (1ll << 31))
+        return fail(h, FFR_ERR_UNSUPPORTED, "%s: N = %lld needs %lld blocks, over the grid limit", who, N, (long long)T * S);
+    hipStream_t st = (hipStream_t)stream;
+    // scratch: row norms [N] (used when the caller passes none), parent, degree, root, minrow [N] ints, best [N] 8-byte words
+    float* own_norms = nullptr;
+    int *parent = nullptr, *deg = nullptr, *root = nullptr, *minrow = nullptr;
+    unsigned long long* best = nullptr;
+    RC(carve(h, h->cluster, "clustering", [&](Arena& a) {
+        own_norms = a.take(N); parent = a.take<int>(N); deg = a.take<int>(N); root = a.take<int>(N); minrow = a.take<int>(N);
+        best = a.take<unsigned long long>(N);
+    }));
+    // the triangle is walked twice: degrees, then the gated join; bytes: the rows twice, 24 of scratch per row written and
+    // read, rep, kind and degree
+    Scope s(h, st, FFR_KC_SCORE, 2.0 * dim * (double)N * (double)(N - 1), 4.0 * (double)N * (dim + 1) + (degree ? 61.0 : 57.0) * N);
+    if (!norms) {
+        HIPCK(h, launch_row_norms(emb, N, own_norms, st));
+        norms = own_norms;
+    }
+    HIPCK(h, launch_cluster_density(emb, norms, N, threshold, min_rows, T, S, chunk_rows, parent, deg, root, minrow, best, rep, kind,
+                                    degree, st));
+    return FFR_OK;
+}
+
 int ffr_cluster_templates(ffr_handle* h, const float* emb, const float* norms, const int64_t* order, const int64_t* offsets,
                           long long C, int dim, float* templates, void* stream) {
     FFR_DEVICE_SCOPE(h); RC(check_fwd(h, false, false, 1));

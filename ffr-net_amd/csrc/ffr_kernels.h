@@ -299,6 +299,13 @@ void cluster_extend_plan(long long N_old, long long N, int num_cus, int* ntiles,
 hipError_t launch_cluster_extend(const float* emb, const float* norms, long long N_old, long long N, float threshold, int ntiles,
                                  int nchunks, long long chunk_rows, const int64_t* prior, int* parent, int64_t* rep,
                                  hipStream_t stream);
+// density-gated clustering over the edges of launch_cluster_threshold (init, degree walk, gated walk, root, min, label):
+// degree[i] = edges at i; core iff degree + 1 >= min_rows; rep[i] = smallest row of i's cluster (core components + the
+// border rows attached by best score, then smallest core row); kind 2 / 1 / 0 = core / border / noise.  Scratch: parent,
+// degree, root, minrow N ints each, best N 8-byte words; degree_out may be null; the plan is cluster_plan's
+hipError_t launch_cluster_density(const float* emb, const float* norms, long long N, float threshold, int min_rows, int ntiles,
+                                  int nchunks, long long chunk_rows, int* parent, int* degree, int* root, int* minrow,
+                                  unsigned long long* best, int64_t* rep, uint8_t* kind, int32_t* degree_out, hipStream_t stream);
 // templates[c] = normalised sum of the normalised rows order[offsets[c] .. offsets[c+1]); norms may be null
 hipError_t launch_cluster_templates(const float* emb, const float* norms, const int64_t* order, const int64_t* offsets,
                                     long long C, float* templates, hipStream_t stream);

@@ -127,6 +127,7 @@ SYMBOLS = [
     ('ffr_cluster_threshold', C.c_int, [_P, _P, _P, C.c_longlong, C.c_int, C.c_float, _P, _P]),
     ('ffr_cluster_templates', C.c_int, [_P, _P, _P, _P, _P, C.c_longlong, C.c_int, _P, _P]),
     ('ffr_cluster_extend', C.c_int, [_P, _P, _P, C.c_longlong, C.c_longlong, C.c_int, C.c_float, _P, _P, _P]),
+    ('ffr_cluster_density', C.c_int, [_P, _P, _P, C.c_longlong, C.c_int, C.c_float, C.c_int, _P, _P, _P, _P]),
     ('ffr_align_transforms', C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, _P]),
     ('ffr_align_warp', C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_longlong, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
     ('ffr_embed_aligned', C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_longlong, _P, _P, _P, C.c_int, _P, C.c_int, _P, _P, _P,
@@ -639,6 +640,22 @@ class Engine(object):
         self._call(self.lib.ffr_cluster_extend, _ptr(emb if N else None), _ptr(norms), n_old, N, emb.size(1),
                    float(threshold), _ptr(prior if N else None), _ptr(rep if N else None))
         return rep
+
+    def cluster_density(self, emb, threshold, min_rows, norms=None, return_degree=False):
+        """Density-gated clustering of emb[N,512] (device fp32) over the edges of cluster(): degree[i] = the rows scoring
+        > threshold with i; a row is core iff degree[i] + 1 >= min_rows; clusters are the components of the core-core edges;
+        a non-core row joins the cluster of its best-scoring core neighbour (ties: the smallest row) or stays alone
+        -> (rep[N] int64, the smallest row index of each row's cluster; kind[N] uint8: 2 core, 1 border, 0 noise), and
+        degree[N] int32 as a third entry with return_degree.  min_rows 1 and 2 give the rep of cluster()."""
+        emb, norms = self._cluster_rows(emb, norms, 'cluster_density')
+        if int(min_rows) != min_rows or min_rows < 1:
+            raise RuntimeError('ffrnet_amd: cluster_density needs an integer min_rows >= 1, got %r' % (min_rows,))
+        N = emb.size(0)
+        rep, kind = self._empty(N, dtype=torch.int64), self._empty(N, dtype=torch.uint8)
+        degree = self._empty(N, dtype=torch.int32) if return_degree else None
+        self._call(self.lib.ffr_cluster_density, _ptr(emb if N else None), _ptr(norms), N, emb.size(1), float(threshold),
+                   int(min_rows), _ptr(rep if N else None), _ptr(kind if N else None), _ptr(degree if N else None))
+        return (rep, kind, degree) if return_degree else (rep, kind)
 
     def cluster_templates(self, emb, order, offsets, norms=None, validate=True):
         """One template per cluster: order (int64, rows of emb sorted by cluster then index) and offsets[C+1] (int64,

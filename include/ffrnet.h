@@ -304,6 +304,38 @@ int ffr_cluster_templates(ffr_handle* h, const float* emb, const float* norms, c
  * Profiled as one launch under FFR_KC_SCORE with flops = 512 * (2 * N_old * N_new + N_new * (N_new - 1)), N_new = N - N_old. */
 int ffr_cluster_extend(ffr_handle* h, const float* emb, const float* norms, long long N_old, long long N, int dim,
                        float threshold, const int64_t* prior, int64_t* rep, void* stream);
+/* Density-gated clustering (DBSCAN over the edge set of ffr_cluster_threshold): a row links clusters only if enough rows
+ * lie within the threshold of it.  Single link lets a few in-between rows (a blurred frame, a look-alike) join two people
+ * into one cluster; here such sparse rows may attach to a cluster but never connect two, and isolated rows are reported.
+ *   edges  exactly those of ffr_cluster_threshold: rows i < j are adjacent iff s(probe = i, gallery row = j) > threshold
+ *          (strict), s with the fp32 bits ffr_search_topk returns for that pair; each pair is scored once, in that
+ *          orientation, the diagonal never.
+ *   degree degree[i] = the number of edges touching i.  Row i is CORE iff degree[i] + 1 >= min_rows (the row counts itself).
+ *   core   clusters are the connected components of the edges whose two end points are both core.
+ *   border a non-core row with at least one core neighbour joins the cluster of the core neighbour with the highest score
+ *          (scores compared as fp32 values; equal scores: the smallest row index).  It never links two clusters.
+ *   noise  a non-core row with no core neighbour is a cluster of its own.
+ *   result rep[N] int64: rep[i] = the smallest row index among ALL members of i's cluster, core and border together (a
+ *          border row can carry a smaller index than every core row of its cluster).  As for ffr_cluster_threshold,
+ *          rep[rep[i]] == rep[i] and two rows share a cluster iff their rep is equal.  kind[N] uint8: 2 core, 1 border,
+ *          0 noise.  degree[N] int32, or NULL when not wanted.  Every rule above is independent of the order in which the
+ *          device meets the edges: repeated calls are bitwise equal.
+ *   1, 2   at min_rows = 1 every row is core, at min_rows = 2 exactly the rows with a neighbour: in both cases rep equals
+ *          ffr_cluster_threshold's rep bit for bit (computed by the passes below, not by the other call).
+ *   how    the triangle of pairs is walked twice by the tile of ffr_cluster_threshold.  Pass 1 adds up degree[] with
+ *          integer atomic adds (they commute).  Pass 2 unites core-core edges in the lock-free union-find described above,
+ *          under the same termination argument, and for an edge between a core row c and a non-core row x raises best[x]
+ *          to (order-preserving bits of s) << 32 | (0xFFFFFFFF - c) with one 64-bit atomic max.  Three N-sized kernels
+ *          then take each row's root, the smallest member per root and the labels.  No step waits on another wave.
+ *   errors dim = 512 only (FFR_ERR_UNSUPPORTED otherwise).  FFR_ERR_ARG: N < 0 or N >= 2^31, a NaN threshold, min_rows < 1,
+ *          a null emb, rep or kind, emb not 16-byte aligned (rep 8, degree and norms 4).  norms as above.  N = 0 succeeds
+ *          and touches nothing.
+ *   memory no host synchronisation; the scratch is the one of ffr_cluster_threshold (norms, parent) plus degree, root,
+ *          minrow and best, 24 bytes per row, and grows and bumps ffr_generation under the same rule.
+ * Profiled as one launch under FFR_KC_SCORE with flops = 2*N*(N-1)*512: the triangle is walked twice.  Extending a density
+ * clustering by new rows is not offered: a new row can turn old rows into cores.                                      */
+int ffr_cluster_density(ffr_handle* h, const float* emb, const float* norms, long long N, int dim, float threshold, int min_rows,
+                        int64_t* rep, uint8_t* kind, int32_t* degree, void* stream);
 
 /* ---- face alignment (landmarks -> similarity transform -> aligned uint8 crop) ---------------------------------------
  * Replaces the reference's host preprocessing, lfw/gen_lfw112x96.py:6-17 (align) with lfw/matlab_cp2tform.py

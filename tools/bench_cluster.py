@@ -1,4 +1,4 @@
-"""Time the on-device clustering (Engine.cluster: k_row_norms + k_cluster_init + k_cluster_join + k_cluster_flatten) on
+"""Time the on-device clustering (Engine.cluster: k_row_norms + k_cluster_init + k_cluster_walk + k_cluster_flatten) on
 planted identities of about 8 rows each, with device events after a warm-up, against
 
   (b) Engine.search(emb, emb, k=1) at the same N: the same K loop over the full N x N rectangle, the yardstick;

@@ -1,4 +1,4 @@
-"""Time the incremental clustering (Engine.cluster_extend: k_cluster_seed + k_cluster_join over the new rows +
+"""Time the incremental clustering (Engine.cluster_extend: k_cluster_seed + k_cluster_walk over the new rows +
 k_cluster_flatten) against clustering everything again (Engine.cluster over all N rows), on the planted identities of
 tools/bench_cluster.py, with device events after a warm-up, the two calls interleaved in one process.
 
