@@ -17,9 +17,9 @@ from .search import Gallery, search_sharded, identification_rates, subject_rates
 from . import align  # noqa: F401
 from .align import TEMPLATE_96x112, TEMPLATE_112x112  # noqa: F401
 from . import cluster  # noqa: F401
-from .cluster import Clusters, DensityClusters, Incremental  # noqa: F401
+from .cluster import Clusters, DensityClusters, DensityState, Incremental, IncrementalDensity  # noqa: F401
 
 __all__ = ['Backbone', 'RecNet', 'ir_se_50_512', 'l2_norm', 'Engine', 'GraphedEmbed',
            'NativeLibraryMissing', 'lib_path', 'synth', 'lfw', 'checkpoint', 'train', 'NativeTrainer',
            'search', 'Gallery', 'search_sharded', 'identification_rates', 'subject_rates', 'align', 'TEMPLATE_96x112', 'TEMPLATE_112x112',
-           'cluster', 'Clusters', 'DensityClusters', 'Incremental']
+           'cluster', 'Clusters', 'DensityClusters', 'DensityState', 'Incremental', 'IncrementalDensity']

@@ -26,6 +26,13 @@ pairs that involve a new row are scored, and the result is the clustering of all
   store = cluster.Incremental(engine, threshold)
   store.add(f_batch)                                 # as often as faces arrive; must_link= ties the frames of one track
   t = store.templates()                              # when a gallery is wanted
+
+The density-gated clustering is extended in the same way (ffr_cluster_density_extend), with the per-row state the
+extension needs kept beside the labels; after every add the result is density() over all rows held:
+
+  store = cluster.IncrementalDensity(engine, threshold, min_rows=4)
+  store.add(f_batch)
+  t = store.templates()                              # one row per cluster with a core: what gets enrolled
 """
 import collections
 
@@ -86,7 +93,9 @@ def changes(rep_before, rep_after):
     representatives in rep_before and are none in rep_after (their cluster was absorbed by one with a smaller first row),
     now[k] = rep_after[stale[k]], the cluster they went to.  A caller that keeps one template per cluster drops the
     templates of `stale` and recomputes those of `now`; clusters that merely gained rows keep their representative and
-    show up in neither."""
+    show up in neither.  This is for single link (extend, Incremental) only: it relies on an old row's rep never rising
+    and on clusters changing by absorption alone.  A density-gated clustering keeps neither promise (a border row may
+    change sides); use density_changes there."""
     rep_before, rep_after = torch.as_tensor(rep_before).reshape(-1), torch.as_tensor(rep_after).reshape(-1)
     n = rep_before.numel()
     if rep_after.numel() < n:
@@ -181,6 +190,149 @@ class Incremental(object):
             self._rep[first:total] = new_prior
             self.engine.cluster_extend(self._emb[:total], self.threshold, self._rep[:total], first,
                                        norms=self._norms[:total], validate=False, out=self._rep[:total])
+            self._n = total
+        return first
+
+
+DensityState = collections.namedtuple('DensityState', ['rep', 'kind', 'degree', 'best', 'threshold', 'min_rows'])
+DensityState.__doc__ = """What Engine.cluster_density_extend needs of the rows clustered so far: rep[n] int64, kind[n] uint8,
+degree[n] int32, best[n] int64 (the key by which a border row chose its core row; 0 for core and noise rows), and the
+threshold and min_rows they were made with: a state is valid for no other."""
+
+
+def density_extend(engine, emb, threshold, min_rows, earlier=None, norms=None):
+    """Extend a density-gated clustering of the first rows of emb[N,512] to all N rows -> (DensityClusters, DensityState),
+    the clusters equal to density(engine, emb, threshold, min_rows).  earlier: the DensityState an earlier call returned for
+    emb[:n_old] (None: a clustering from scratch); it is left as it is.  Only the pairs with a new row, and the pairs of old
+    rows of which one was made core by the new rows, are scored.  A state made with another threshold or min_rows is refused."""
+    threshold, min_rows = float(threshold), int(min_rows)
+    if earlier is None:
+        rep = degree = best = None
+        n_old = 0
+    else:
+        if float(earlier.threshold) != threshold or int(earlier.min_rows) != min_rows:
+            raise RuntimeError('ffrnet_amd: the state was made with threshold %r and min_rows %d; it cannot be extended with %r '
+                               'and %d' % (earlier.threshold, earlier.min_rows, threshold, min_rows))
+        n_old = earlier.rep.numel()
+        if n_old > emb.size(0):
+            raise RuntimeError('ffrnet_amd: a state of %d rows for %d embeddings' % (n_old, emb.size(0)))
+        rep, degree, best = earlier.rep, earlier.degree, earlier.best
+        if n_old == emb.size(0):                               # [N] tensors are updated in place: work on copies
+            rep, degree, best = rep.clone(), degree.clone(), best.clone()
+    rep, kind, degree, best = engine.cluster_density_extend(emb, threshold, min_rows, rep, degree, best, n_old, norms=norms)
+    return density_ids(rep, kind), DensityState(rep, kind, degree, best, threshold, min_rows)
+
+
+def density_changes(before, after):
+    """What an extension did to the clusters of a density-gated clustering: -> (gone, recompute), both int64 and ascending.
+    before, after: rep tensors, or anything with a .rep (DensityClusters, DensityState), of n and N >= n rows.
+    gone: the representatives of `before` that are none in `after`.  recompute: the representatives of `after` whose
+    members among the first n rows are not exactly the members of one cluster of `before`, or that hold a new row.  A
+    caller that keeps one template per cluster drops those of `gone` and computes those of `recompute`.
+
+    changes() is not enough here.  Under single link an old row's rep can only decrease, and a cluster changes only by
+    being absorbed or by gaining rows.  Under density gating a border row may move to a better-scoring core row of ANOTHER
+    cluster once new rows made that one core: both clusters change though neither was absorbed, and if the row was the
+    smallest member of the cluster it left, that cluster's representative RISES to a row that was none before."""
+    before = torch.as_tensor(getattr(before, 'rep', before)).reshape(-1)
+    after = torch.as_tensor(getattr(after, 'rep', after)).reshape(-1).to(before.device)
+    n, total = before.numel(), after.numel()
+    if total < n:
+        raise ValueError('density_changes: %d labels before, %d after' % (n, total))
+    row = torch.arange(n, device=before.device, dtype=torch.int64)
+    old = after[:n]
+    gone = row[(before == row) & (old != row)]
+
+    def spread(key, value):
+        """per row: do all rows with this row's key carry one value?"""
+        lo = torch.full((total,), total, device=key.device, dtype=torch.int64).scatter_reduce_(0, key, value, 'amin')
+        hi = torch.full((total,), -1, device=key.device, dtype=torch.int64).scatter_reduce_(0, key, value, 'amax')
+        return lo[key] == hi[key]
+
+    # a cluster of `after` kept its old members iff they come from one cluster of `before` and that one went nowhere else
+    same = spread(old, before) & spread(before, old)
+    return gone, torch.unique(torch.cat((old[~same], after[n:])))
+
+
+class IncrementalDensity(object):
+    """A density-gated clustering that keeps being added to: embeddings [n,512], their norms and the state (rep, kind,
+    degree, best) on the Engine's device, in grow-only buffers (as Incremental).  After every add() the labels are those of
+    density() over all rows held.  Rows keep their index for ever; unlike Incremental, the rep of an old row can also rise
+    (density_changes tells which templates to drop and which to compute)."""
+
+    def __init__(self, engine, threshold, min_rows, capacity=0):
+        if int(min_rows) != min_rows or min_rows < 1:
+            raise RuntimeError('ffrnet_amd: IncrementalDensity needs an integer min_rows >= 1, got %r' % (min_rows,))
+        self.engine = engine
+        self.threshold = float(threshold)
+        self.min_rows = int(min_rows)
+        self._n = 0
+        cap, dev = int(capacity), engine.device
+        self._emb = torch.empty((cap, 512), device=dev, dtype=torch.float32)
+        self._norms = torch.empty((cap,), device=dev, dtype=torch.float32)
+        self._rep = torch.empty((cap,), device=dev, dtype=torch.int64)
+        self._kind = torch.empty((cap,), device=dev, dtype=torch.uint8)
+        self._degree = torch.empty((cap,), device=dev, dtype=torch.int32)
+        self._best = torch.empty((cap,), device=dev, dtype=torch.int64)
+
+    def __len__(self):
+        return self._n
+
+    @property
+    def embeddings(self):
+        return self._emb[:self._n]
+
+    @property
+    def norms(self):
+        return self._norms[:self._n]
+
+    @property
+    def rep(self):
+        return self._rep[:self._n]
+
+    @property
+    def kind(self):
+        return self._kind[:self._n]
+
+    @property
+    def degree(self):
+        return self._degree[:self._n]
+
+    @property
+    def state(self):
+        return DensityState(self.rep, self.kind, self.degree, self._best[:self._n], self.threshold, self.min_rows)
+
+    @property
+    def clusters(self):
+        return density_ids(self.rep, self.kind)
+
+    def templates(self):
+        """One unit template per cluster that has a core, in order of representative -> [C',512]: what gets enrolled."""
+        c = self.clusters
+        return templates(self.engine, self.embeddings, c, norms=self.norms)[c.has_core]
+
+    def add(self, emb):
+        """Append emb[n,512] (fp32, on the Engine's device) and extend the clustering -> the index of its first row."""
+        if not isinstance(emb, torch.Tensor) or emb.dim() != 2 or emb.size(1) != 512:
+            raise RuntimeError('ffrnet_amd: IncrementalDensity.add expects [n,512] embeddings, got %s'
+                               % (list(emb.shape) if isinstance(emb, torch.Tensor) else type(emb)))
+        n, first = emb.size(0), self._n
+        if first + n > self._emb.size(0):
+            cap = max(first + n, 2 * self._emb.size(0), 1024)
+            grown = []
+            for buf in (self._emb, self._norms, self._rep, self._kind, self._degree, self._best):
+                new = torch.empty((cap,) + tuple(buf.shape[1:]), device=buf.device, dtype=buf.dtype)
+                new[:first] = buf[:first]
+                grown.append(new)
+            self._emb, self._norms, self._rep, self._kind, self._degree, self._best = grown
+        if n:
+            total = first + n
+            self._emb[first:total] = emb
+            self._norms[first:total] = self.engine.row_norms(self._emb[first:total])
+            _, kind, _, _ = self.engine.cluster_density_extend(
+                self._emb[:total], self.threshold, self.min_rows, self._rep[:total], self._degree[:total], self._best[:total],
+                first, norms=self._norms[:total], validate=False)
+            self._kind[:total] = kind
             self._n = total
         return first
 

@@ -1,7 +1,8 @@
 // cluster.hip -- group N unlabelled 512-d embeddings into identities on the device (include/ffrnet.h:
-// ffr_cluster_threshold / ffr_cluster_extend / ffr_cluster_density / ffr_cluster_templates): single-link clustering at one
-// cosine threshold, extended batch by batch where the collection grows, or gated by density over the same edges (core rows
-// link, border rows attach, noise stays alone), then one template row per cluster.  The N x N score matrix never leaves the
+// ffr_cluster_threshold / ffr_cluster_extend / ffr_cluster_density / ffr_cluster_density_extend / ffr_cluster_templates):
+// single-link clustering at one cosine threshold, or gated by density over the same edges (core rows link, border rows
+// attach, noise stays alone), either of them extended batch by batch where the collection grows, then one template row per
+// cluster.  The N x N score matrix never leaves the
 // chip; the output is one label per row.
 //
 // Edge rule: rows i < j are joined iff s(probe = i, gallery row = j) > threshold (strict, as eval_acc compares), with
@@ -74,6 +75,37 @@
 //    no-return vector atomics at agent scope without a retry loop; there is no scalar memory write anywhere.  Every index
 //    is a row the edge mask admitted (< N) or a prefetch clamped to the chunk's last row; the core row read back from
 //    best[] was written as a row < N, and best[] is zeroed first (a real key is never 0: its low word is >= 2^31).
+//  - Density, extended (ffr_cluster_density_extend): the rows [0, n_old) carry the state (rep, degree, best) of an earlier
+//    call at the same threshold and min_rows; the result and the state left behind are those of ffr_cluster_density over
+//    all N rows.  need = min_rows - 1.  Degrees only grow, so a core row stays core and the old core components persist;
+//    among the old rows only the PROMOTED ones (degree_old < need <= degree) change status; and an old non-core row's key is
+//    a maximum over its core neighbours, a set that only grows: new key = max(old key, offers of the newly core neighbours).
+//      k_dext_init / k_dext_coremin / k_dext_parent   the seed: parent[x] = the smallest old core row with x's rep for an
+//                   old core row, x for every other row; degree and best of the new rows 0; deg0[] = the old degrees.
+//      k_cluster_walk<true, EdgesDegree>   adds the edges with a new end into degree[]: the instantiation is new, the body not.
+//      k_dext_promoted_list   P[0 .. m) = the promoted rows, m in device memory; any order: what follows is unions and maxima.
+//      k_cluster_walk<true, EdgesGated>    the gated join over the pairs with a new end, on the final core flags.
+//      k_dext_promoted   the old-old edges with an end in P: both ends are now core -> uf_unite; the other end y is not ->
+//                   p is offered to best[y].  Old-old edges with no end in P need nothing: core-core ones are in the seed,
+//                   core - non-core ones in the persisted key.  An edge between two promoted rows is met twice; a union and
+//                   a maximum are idempotent.
+//      k_density_root / k_density_min / k_density_label   as above.  best[] of core rows was zeroed on the way (old core
+//                   rows in the seed, promoted rows where they are listed, new rows start at 0 and a core row gets no
+//                   offer), so the state after an extension is bit for bit the state a call from scratch leaves.
+//    Transposed pairs: k_dext_promoted scores (y, p), y > p, as probe y against row p, where ffr_cluster_density scores
+//    probe p against row y.  The bits are the same: a dot is the same 8 chains over the same k in the same order, each term
+//    the product of the two rows' k-th components (an fp32 product commutes, and the MFMA adds its two products of a step in
+//    k order whichever operand they came in); the chain sum is a fixed tree; the denominator fmaf(qn, gn, 1e-8) commutes in
+//    qn, gn.  tests/test_gpu_cluster_density_extend.py holds this on the device (the score matrix equals its transpose).
+//    Seeded start (extends the paragraph above): caller data reaches parent[] only in the seed.  rep[x] is used only where
+//    0 <= rep[x] <= x, as an index into coremin[N]; coremin[r] is DX_NONE or the minimum of rows x < n_old that took part
+//    with rep[x] = r, and an old core row reads the cell it took part in itself: 0 <= parent[x] <= x, and parent[parent[x]]
+//    = parent[x] (the minimum is a core row of the same rep): a forest of depth 1 whatever was passed.  A rep outside [0, x]
+//    leaves x alone; a negative degree is read as 0; a key whose decoded row is >= n_old, or is no old core row, is read as 0,
+//    so k_density_root only ever follows a key to a core row of [0, N), a row of the union-find.  P holds rows < n_old
+//    written by k_dext_promoted_list, at most n_old of them (a row is listed once), and slots past m are never an edge.
+//    The safety argument carries over once more: k_dext_promoted adds edges through uf_unite between core rows and through
+//    the same single 64-bit max; its loop over work items is bounded by a count read once; no wave waits on another.
 // k_cluster_flatten  rep[i] = find(i) as int64, after the join in stream order.
 // k_cluster_templates  one template per cluster: t = sum_r x_r / |x_r| over the cluster's rows in ascending row index
 //                (order[] = rows sorted by cluster then index, offsets[C + 1]), then t / |t|.  One wave per cluster, lane
@@ -147,7 +179,7 @@ struct JoinArgs {
     float threshold;
     int nchunks, ntiles;
     long long first;          // RANGE: the chunks cover the rows [first, N)
-    // ffr_cluster_density only
+    // ffr_cluster_density and ffr_cluster_density_extend only
     int* degree;              // [N]
     unsigned long long* best; // [N]
     int min_rows;
@@ -350,6 +382,143 @@ __global__ __launch_bounds__(256) void k_density_label(const int* __restrict__ r
     if (degree_out) degree_out[x] = d;
 }
 
+// ---- ffr_cluster_density_extend: see "Density, extended" in the header ----
+
+constexpr int DX_NONE = 0x7FFFFFFF;       // coremin[]: no core row carries this rep
+
+__device__ __forceinline__ bool dx_rep_ok(int64_t r, int x) { return 0 <= r && r <= (int64_t)x; }
+
+// Seed 1 of 3.  New rows: alone, degree and best 0.  Old rows: the degree read as >= 0, written back and kept in deg0[]
+// (the promoted list needs the old value after the walk has added to degree[]).  coremin[] and the counter of P start empty.
+__global__ __launch_bounds__(256) void k_dext_init(int* __restrict__ parent, int* __restrict__ degree,
+                                                   unsigned long long* __restrict__ best, int* __restrict__ deg0,
+                                                   int* __restrict__ coremin, int* __restrict__ pcount, int n_old, int n) {
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    if (x == 0) *pcount = 0;
+    if (x >= n) return;
+    coremin[x] = DX_NONE;
+    if (x >= n_old) {
+        parent[x] = x;
+        degree[x] = 0;
+        best[x] = 0;
+        return;
+    }
+    const int d = max(degree[x], 0);
+    degree[x] = d;
+    deg0[x] = d;
+}
+
+// Seed 2 of 3, old rows.  A core row: best read as 0, and coremin[rep[x]] = min over the core rows x that carry this rep
+// (a rep outside [0, x] names nothing).  A non-core row: a key whose core row is not an old core row is read as 0.
+__global__ __launch_bounds__(256) void k_dext_coremin(const int64_t* __restrict__ rep, const int* __restrict__ deg0,
+                                                      unsigned long long* __restrict__ best, int* __restrict__ coremin, int need,
+                                                      int n_old) {
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    if (x >= n_old) return;
+    if (deg0[x] >= need) {
+        best[x] = 0;
+        const int64_t r = rep[x];
+        if (dx_rep_ok(r, x)) __hip_atomic_fetch_min(coremin + r, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    } else {
+        const unsigned long long key = best[x];
+        const unsigned c = 0xFFFFFFFFu - (unsigned)key;
+        if (key && (c >= (unsigned)n_old || deg0[c] < need)) best[x] = 0;
+    }
+}
+
+// Seed 3 of 3, old rows: an old core row hangs under the smallest old core row of its rep (itself at the least: it took
+// part in the minimum, so 0 <= coremin[rep[x]] <= x); every other row starts alone.
+__global__ __launch_bounds__(256) void k_dext_parent(const int64_t* __restrict__ rep, const int* __restrict__ deg0,
+                                                     const int* __restrict__ coremin, int* __restrict__ parent, int need, int n_old) {
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    if (x >= n_old) return;
+    const int64_t r = rep[x];
+    parent[x] = (deg0[x] >= need && dx_rep_ok(r, x)) ? coremin[r] : x;
+}
+
+// P[0 .. m) = the old rows the new rows made core, in any order; their keys are void from here on.  m <= n_old: a row
+// enters once.
+__global__ __launch_bounds__(256) void k_dext_promoted_list(const int* __restrict__ deg0, const int* __restrict__ degree,
+                                                            unsigned long long* __restrict__ best, int* __restrict__ plist,
+                                                            int* __restrict__ pcount, int need, int n_old) {
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    if (x >= n_old || deg0[x] >= need || degree[x] < need) return;
+    best[x] = 0;
+    plist[__hip_atomic_fetch_add(pcount, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)] = x;
+}
+
+struct PromotedArgs {
+    const float* emb;         // [N][512]
+    const float* norm;        // [N]
+    int* parent;              // [N]
+    const int* degree;        // [N], final
+    unsigned long long* best; // [N]
+    const int* plist;         // [n_old], the first *pcount entries are set
+    const int* pcount;
+    int n_old, ntiles;        // tiles of 32 probes over [0, n_old)
+    float threshold;
+    int need;
+};
+
+// The old-old edges with an end in P.  A work item is (tile of 32 old probes, slice of 128 rows of P); a fixed grid loops
+// over the ntiles * ceil(m / 128) items, m read from device memory (uniform in the block: the barriers are legal), so
+// m = 0 is one early return per block.  Wave w streams the rows P[128 s + 32 w ..] through CosineStreamT<GatherRows> (slots
+// past m repeat the slice's first row, in bounds, and are masked out); the tile, the chain sum and cosine_score are those
+// of k_cluster_walk.  The gallery side is always core, so an edge (y, p) is a unite when y is core and an offer of p to
+// best[y] when it is not.
+__global__ __launch_bounds__(256, 1) void k_dext_promoted(const PromotedArgs a) {
+    __shared__ __attribute__((aligned(16))) f32x4 qf[CT_NG * 64];
+    __shared__ int prow[CT_STEP];
+    __shared__ float pnorm[CT_STEP];
+
+    const int m = *a.pcount;
+    if (m <= 0) return;
+    const int tid = threadIdx.x, lane = tid & 63, n = lane & 31, h = lane >> 5;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int nslices = (m + CT_STEP - 1) / CT_STEP;
+    const long long items = (long long)a.ntiles * nslices;
+
+    for (long long it = blockIdx.x; it < items; it += gridDim.x) {
+        const int tile = (int)(it / nslices), slice = (int)(it - (long long)tile * nslices);
+        const int q0 = tile * CT_QT, nq = min(CT_QT, a.n_old - q0);
+        const int s0 = slice * CT_STEP, ns = min(CT_STEP, m - s0);         // >= 1
+        __syncthreads();                                    // the previous item's reads of qf, prow, pnorm are over
+        cosine_fill_probes(qf, a.emb, q0, nq, tid);
+        if (tid < CT_STEP) {
+            const int p = a.plist[s0 + (tid < ns ? tid : 0)];
+            prow[tid] = p;
+            pnorm[tid] = a.norm[p];
+        }
+        __syncthreads();
+
+        const int irow = q0 + n;                            // the lane's probe, an old row when n < nq
+        const bool live = n < nq;
+        const float qn = live ? a.norm[irow] : 0.f;
+        const bool pcore = live && a.degree[irow] >= a.need;
+
+        if (w * 32 >= ns) continue;                         // wave-uniform: none of this wave's 32 slots is set
+        const long long grow = prow[w * 32 + n];
+        CosineStreamT<GatherRows> gs(a.emb, lane);
+        gs.prime(grow);
+        f32x16 acc8[CT_NACC];
+        gs.tile(acc8, qf, grow);
+        const f32x16 acc = COSINE_CHAIN_SUM(acc8);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int slot = cosine_lane_row(w, r, h);
+            const int p = prow[slot];
+            const float sc = cosine_score(acc[r], qn, pnorm[slot]);
+            if (!(live && slot < ns && p != irow && sc > a.threshold)) continue;
+            if (pcore) {
+                uf_unite(a.parent, irow, p);
+            } else {
+                const unsigned long long key = ((unsigned long long)ordered_bits(sc) << 32) | (0xFFFFFFFFu - (unsigned)p);
+                __hip_atomic_fetch_max(a.best + irow, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+    }
+}
+
 // parent[x] = x, degree[x] = 0, best[x] = 0
 __global__ __launch_bounds__(256) void k_density_init(int* __restrict__ parent, int* __restrict__ degree,
                                                       unsigned long long* __restrict__ best, int n) {
@@ -489,6 +658,57 @@ hipError_t launch_cluster_density(const float* emb, const float* norms, long lon
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_density_label, dim3(nb), dim3(256), 0, stream, (const int*)root, (const int*)minrow, (const int*)degree,
                        (const unsigned long long*)best, min_rows, (int)N, rep, kind, degree_out);
+    return hipGetLastError();
+}
+
+int cluster_promoted_grid(long long N_old, int num_cus) {
+    const long long tiles = (N_old + CT_QT - 1) / CT_QT, most = tiles * ((N_old + CT_STEP - 1) / CT_STEP);
+    return (int)std::max(1LL, std::min(most, 2LL * num_cus));      // two blocks of 64 KiB LDS fit a CU
+}
+
+hipError_t launch_cluster_density_extend(const float* emb, const float* norms, long long N_old, long long N, float threshold,
+                                         int min_rows, int ntiles, int nchunks, long long chunk_rows, int promoted_grid, int* parent,
+                                         int* deg0, int* coremin, int* root, int* minrow, int* plist, int* pcount, int64_t* rep,
+                                         uint8_t* kind, int32_t* degree, unsigned long long* best, hipStream_t stream) {
+    if (N <= 0) return hipSuccess;
+    const unsigned nb = (unsigned)((N + 255) / 256), nbo = (unsigned)((N_old + 255) / 256);
+    const int need = min_rows - 1;
+    hipError_t e;
+    hipLaunchKernelGGL(k_dext_init, dim3(nb), dim3(256), 0, stream, parent, degree, best, deg0, coremin, pcount, (int)N_old, (int)N);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (N_old > 0) {
+        hipLaunchKernelGGL(k_dext_coremin, dim3(nbo), dim3(256), 0, stream, (const int64_t*)rep, (const int*)deg0, best, coremin, need,
+                           (int)N_old);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        hipLaunchKernelGGL(k_dext_parent, dim3(nbo), dim3(256), 0, stream, (const int64_t*)rep, (const int*)deg0, (const int*)coremin,
+                           parent, need, (int)N_old);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    if (N > 1 && N_old < N) {
+        JoinArgs a{emb, norms, parent, N, chunk_rows, threshold, nchunks, ntiles, N_old, degree, best, min_rows};
+        const dim3 grid((unsigned)((long long)nchunks * ntiles));
+        hipLaunchKernelGGL((k_cluster_walk<true, EdgesDegree>), grid, dim3(256), 0, stream, a);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if (N_old > 0) {
+            hipLaunchKernelGGL(k_dext_promoted_list, dim3(nbo), dim3(256), 0, stream, (const int*)deg0, (const int*)degree, best, plist,
+                               pcount, need, (int)N_old);
+            if ((e = hipGetLastError()) != hipSuccess) return e;
+        }
+        hipLaunchKernelGGL((k_cluster_walk<true, EdgesGated>), grid, dim3(256), 0, stream, a);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if (N_old > 1) {
+            PromotedArgs p{emb, norms, parent, degree, best, plist, pcount, (int)N_old, (int)((N_old + CT_QT - 1) / CT_QT), threshold, need};
+            hipLaunchKernelGGL(k_dext_promoted, dim3((unsigned)promoted_grid), dim3(256), 0, stream, p);
+            if ((e = hipGetLastError()) != hipSuccess) return e;
+        }
+    }
+    hipLaunchKernelGGL(k_density_root, dim3(nb), dim3(256), 0, stream, (const int*)parent, (const int*)degree,
+                       (const unsigned long long*)best, min_rows, (int)N, root, minrow);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_density_min, dim3(nb), dim3(256), 0, stream, (const int*)root, (int)N, minrow);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_density_label, dim3(nb), dim3(256), 0, stream, (const int*)root, (const int*)minrow, (const int*)degree,
+                       (const unsigned long long*)best, min_rows, (int)N, rep, kind, (int32_t*)nullptr);
     return hipGetLastError();
 }
 

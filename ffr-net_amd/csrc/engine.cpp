@@ -584,6 +584,50 @@ int ffr_cluster_density(ffr_handle* h, const float* emb, const float* norms, lon
     return FFR_OK;
 }
 
+int ffr_cluster_density_extend(ffr_handle* h, const float* emb, const float* norms, long long N_old, long long N, int dim,
+                               float threshold, int min_rows, int64_t* rep, uint8_t* kind, int32_t* degree,
+                               unsigned long long* best, void* stream) {
+    const char* who = "ffr_cluster_density_extend";
+    FFR_DEVICE_SCOPE(h); RC(check_fwd(h, false, false, 1));
+    RC(check_dim(h, who, dim));
+    if (N < 0 || N >= (1ll << 31)) return fail(h, FFR_ERR_ARG, "%s: N must be in [0, 2^31), got %lld", who, N);
+    if (N_old < 0 || N_old > N) return fail(h, FFR_ERR_ARG, "%s: N_old must be in [0, N = %lld], got %lld", who, N, N_old);
+    if (threshold != threshold) return fail(h, FFR_ERR_ARG, "%s: the threshold is NaN", who);
+    if (min_rows < 1) return fail(h, FFR_ERR_ARG, "%s: min_rows must be >= 1, got %d", who, min_rows);
+    if (N == 0) return FFR_OK;
+    if (!emb || !rep || !kind || !degree || !best) return fail(h, FFR_ERR_ARG, "%s: emb / rep / kind / degree / best is null", who);
+    if (misaligned16(emb) || ((uintptr_t)rep & 7) || ((uintptr_t)best & 7) || ((uintptr_t)degree & 3) || ((uintptr_t)norms & 3))
+        return fail(h, FFR_ERR_ARG, "%s: emb rows must be 16-byte aligned (rep and best 8, degree and norms 4)", who);
+    const long long n_new = N - N_old;
+    const bool join = N > 1 && n_new > 0;                 // are there pairs to score?
+    int T = 0, S = 0;
+    long long chunk_rows = 0;
+    if (join) cluster_extend_plan(N_old, N, h->num_cus, &T, &S, &chunk_rows);
+    if ((long long)T * S >= (1ll << 31))
+        return fail(h, FFR_ERR_UNSUPPORTED, "%s: N = %lld with %lld new rows needs %lld blocks, over the grid limit", who, N, n_new, (long long)T * S);
+    hipStream_t st = (hipStream_t)stream;
+    // scratch: row norms [N] (used when the caller passes none), parent, the old degrees, the per-rep core minimum, root,
+    // minrow [N] ints, the promoted rows [N_old] and their count; degree and best are the caller's state
+    float* own_norms = nullptr;
+    int *parent = nullptr, *deg0 = nullptr, *coremin = nullptr, *root = nullptr, *minrow = nullptr, *plist = nullptr, *pcount = nullptr;
+    RC(carve(h, h->cluster, "clustering", [&](Arena& a) {
+        own_norms = a.take(N); parent = a.take<int>(N); deg0 = a.take<int>(N); coremin = a.take<int>(N); root = a.take<int>(N);
+        minrow = a.take<int>(N); plist = a.take<int>(N_old + 1); pcount = a.take<int>(1);
+    }));
+    // both range walks, plus the promoted pass at its upper bound m = N_old (m is known on the device only)
+    const double pairs = join ? 2.0 * (2.0 * (double)N_old * (double)n_new + (double)n_new * (double)(n_new - 1)) +
+                                    2.0 * (double)N_old * (double)N_old : 0.0;
+    Scope s(h, st, FFR_KC_SCORE, dim * pairs, 4.0 * (double)N * (dim + 1) + 64.0 * N);
+    if (!norms && join) {
+        HIPCK(h, launch_row_norms(emb, N, own_norms, st));
+        norms = own_norms;
+    }
+    HIPCK(h, launch_cluster_density_extend(emb, norms, N_old, N, threshold, min_rows, T, S, chunk_rows,
+                                           cluster_promoted_grid(N_old, h->num_cus), parent, deg0, coremin, root, minrow, plist, pcount,
+                                           rep, kind, degree, best, st));
+    return FFR_OK;
+}
+
 int ffr_cluster_templates(ffr_handle* h, const float* emb, const float* norms, const int64_t* order, const int64_t* offsets,
                           long long C, int dim, float* templates, void* stream) {
     FFR_DEVICE_SCOPE(h); RC(check_fwd(h, false, false, 1));

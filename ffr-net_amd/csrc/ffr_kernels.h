@@ -306,6 +306,16 @@ hipError_t launch_cluster_extend(const float* emb, const float* norms, long long
 hipError_t launch_cluster_density(const float* emb, const float* norms, long long N, float threshold, int min_rows, int ntiles,
                                   int nchunks, long long chunk_rows, int* parent, int* degree, int* root, int* minrow,
                                   unsigned long long* best, int64_t* rep, uint8_t* kind, int32_t* degree_out, hipStream_t stream);
+// blocks of the promoted pass of launch_cluster_density_extend: a fixed grid, the work is counted on the device
+int cluster_promoted_grid(long long N_old, int num_cus);
+// launch_cluster_density over all N rows, from the state (rep, degree, best) of the first N_old: seed, degree walk and gated
+// walk over the pairs with a new row (the plan is cluster_extend_plan's), the old rows they made core listed in plist[*pcount],
+// the old-old edges at those, then root, min, label.  rep, degree, best [N] in and out (the caller's), kind [N] out.
+// Scratch: parent, deg0, coremin, root, minrow N ints each, plist N_old ints, pcount one int
+hipError_t launch_cluster_density_extend(const float* emb, const float* norms, long long N_old, long long N, float threshold,
+                                         int min_rows, int ntiles, int nchunks, long long chunk_rows, int promoted_grid, int* parent,
+                                         int* deg0, int* coremin, int* root, int* minrow, int* plist, int* pcount, int64_t* rep,
+                                         uint8_t* kind, int32_t* degree, unsigned long long* best, hipStream_t stream);
 // templates[c] = normalised sum of the normalised rows order[offsets[c] .. offsets[c+1]); norms may be null
 hipError_t launch_cluster_templates(const float* emb, const float* norms, const int64_t* order, const int64_t* offsets,
                                     long long C, float* templates, hipStream_t stream);

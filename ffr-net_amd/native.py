@@ -128,6 +128,7 @@ SYMBOLS = [
     ('ffr_cluster_templates', C.c_int, [_P, _P, _P, _P, _P, C.c_longlong, C.c_int, _P, _P]),
     ('ffr_cluster_extend', C.c_int, [_P, _P, _P, C.c_longlong, C.c_longlong, C.c_int, C.c_float, _P, _P, _P]),
     ('ffr_cluster_density', C.c_int, [_P, _P, _P, C.c_longlong, C.c_int, C.c_float, C.c_int, _P, _P, _P, _P]),
+    ('ffr_cluster_density_extend', C.c_int, [_P, _P, _P, C.c_longlong, C.c_longlong, C.c_int, C.c_float, C.c_int, _P, _P, _P, _P, _P]),
     ('ffr_align_transforms', C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, _P]),
     ('ffr_align_warp', C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_longlong, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
     ('ffr_embed_aligned', C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_longlong, _P, _P, _P, C.c_int, _P, C.c_int, _P, _P, _P,
@@ -229,6 +230,26 @@ def _check(t, name, device, dtype=torch.float32, shape=None, hint=''):
 def _check_dev(t, name, shape_tail=None, device=None):
     """_check of a float32 tensor [N, *shape_tail]."""
     _check(t, name, device, shape=None if shape_tail is None else ('N',) + tuple(shape_tail))
+
+
+def check_density_state(rep, degree, best):
+    """Range check of the state Engine.cluster_density_extend reads for its n_old old rows (tensors of [n_old] entries, any
+    device): 0 <= rep[i] <= i, degree[i] >= 0, and every key best[i] is 0 or names a row < n_old (the row is 0xFFFFFFFF minus
+    the key's low word).  Raises RuntimeError; plain torch, so it runs without a GPU."""
+    n_old = rep.numel()
+    if degree.numel() != n_old or best.numel() != n_old:
+        raise RuntimeError('ffrnet_amd: density state of %d / %d / %d rows' % (n_old, degree.numel(), best.numel()))
+    if n_old == 0:
+        return
+    rep, best = rep.reshape(-1).to(torch.int64), best.reshape(-1).to(torch.int64)
+    row = torch.arange(n_old, device=rep.device, dtype=torch.int64)
+    if bool(((rep < 0) | (rep > row)).any().item()):
+        raise RuntimeError('ffrnet_amd: density state needs 0 <= rep[i] <= i (and so < %d)' % n_old)
+    if bool((degree.reshape(-1) < 0).any().item()):
+        raise RuntimeError('ffrnet_amd: density state needs degree >= 0')
+    named = 0xFFFFFFFF - (best & 0xFFFFFFFF)
+    if bool(((best != 0) & (named >= n_old)).any().item()):
+        raise RuntimeError('ffrnet_amd: density state needs every key of best to be 0 or to name a row < %d' % n_old)
 
 
 _U8_HINT = ' (HWC, RGB)'
@@ -656,6 +677,41 @@ class Engine(object):
         self._call(self.lib.ffr_cluster_density, _ptr(emb if N else None), _ptr(norms), N, emb.size(1), float(threshold),
                    int(min_rows), _ptr(rep if N else None), _ptr(kind if N else None), _ptr(degree if N else None))
         return (rep, kind, degree) if return_degree else (rep, kind)
+
+    def cluster_density_extend(self, emb, threshold, min_rows, rep, degree, best, n_old, norms=None, validate=True):
+        """Extend a density-gated clustering by new rows: emb[N,512] holds all rows, the first n_old of them clustered
+        before at this threshold and min_rows.  The state of those rows is rep (int64), degree (int32) and best (int64: the
+        64 bits of the key by which a border row chose its core row, 0 for core and noise rows), each [n_old] or [N]; a
+        tensor of [N] entries is updated in place, and with n_old = 0 each may be None.  -> (rep, kind, degree, best), all
+        [N]: rep, kind and degree equal cluster_density(emb, ..., return_degree=True) when the state is the one an earlier
+        call left for emb[:n_old], and best is the state for the next call.  n_old = 0 clusters from scratch.  The kernels
+        read out-of-range state as "none"; `validate` range-checks it here first (check_density_state, one small sync)."""
+        emb, norms = self._cluster_rows(emb, norms, 'cluster_density_extend')
+        if int(min_rows) != min_rows or min_rows < 1:
+            raise RuntimeError('ffrnet_amd: cluster_density_extend needs an integer min_rows >= 1, got %r' % (min_rows,))
+        N, n_old = emb.size(0), int(n_old)
+        if n_old < 0 or n_old > N:
+            raise RuntimeError('ffrnet_amd: cluster_density_extend needs 0 <= n_old <= %d, got %d' % (N, n_old))
+        state = []
+        for t, name, dtype in ((rep, 'rep', torch.int64), (degree, 'degree', torch.int32), (best, 'best', torch.int64)):
+            if t is None and n_old == 0:
+                t = self._empty(N, dtype=dtype)
+            self._tensor(t, name, dtype, ('N',))
+            if t.numel() not in (n_old, N):
+                raise RuntimeError('ffrnet_amd: %s must be [%d] or [%d], got %s' % (name, n_old, N, list(t.shape)))
+            if t.numel() != N or not t.is_contiguous():
+                full = self._empty(N, dtype=dtype)
+                full[:n_old] = t[:n_old]
+                t = full
+            state.append(t)
+        rep, degree, best = state
+        if validate:
+            check_density_state(rep[:n_old], degree[:n_old], best[:n_old])
+        kind = self._empty(N, dtype=torch.uint8)
+        self._call(self.lib.ffr_cluster_density_extend, _ptr(emb if N else None), _ptr(norms), n_old, N, emb.size(1),
+                   float(threshold), int(min_rows), _ptr(rep if N else None), _ptr(kind if N else None),
+                   _ptr(degree if N else None), _ptr(best if N else None))
+        return rep, kind, degree, best
 
     def cluster_templates(self, emb, order, offsets, norms=None, validate=True):
         """One template per cluster: order (int64, rows of emb sorted by cluster then index) and offsets[C+1] (int64,

@@ -332,10 +332,40 @@ int ffr_cluster_extend(ffr_handle* h, const float* emb, const float* norms, long
  *          and touches nothing.
  *   memory no host synchronisation; the scratch is the one of ffr_cluster_threshold (norms, parent) plus degree, root,
  *          minrow and best, 24 bytes per row, and grows and bumps ffr_generation under the same rule.
- * Profiled as one launch under FFR_KC_SCORE with flops = 2*N*(N-1)*512: the triangle is walked twice.  Extending a density
- * clustering by new rows is not offered: a new row can turn old rows into cores.                                      */
+ * Profiled as one launch under FFR_KC_SCORE with flops = 2*N*(N-1)*512: the triangle is walked twice.  A collection that
+ * grows is extended with ffr_cluster_density_extend below.                                                            */
 int ffr_cluster_density(ffr_handle* h, const float* emb, const float* norms, long long N, int dim, float threshold, int min_rows,
                         int64_t* rep, uint8_t* kind, int32_t* degree, void* stream);
+/* Extend a density-gated clustering by new rows, equal to ffr_cluster_density over all rows.  emb[N][dim] holds ALL rows,
+ * the earlier ones first; the rows [N_old, N) are new.  norms[N] or NULL as above.
+ *   state  kept by the caller between calls, per row: rep[N] int64, degree[N] int32 and best[N] uint64, all three in and
+ *          out: the first N_old entries are read, all N are written.  best[i] is the key by which a border row chose its
+ *          cluster, (order-preserving bits of the score) << 32 | (0xFFFFFFFF - core row), and 0 for a core or a noise row.
+ *          kind[N] uint8 is out only.  The state is valid ONLY for the threshold and the min_rows it was made with.
+ *   equal  if (rep, degree, best)[:N_old] is the state this call left for the first N_old rows at this threshold and
+ *          min_rows, then rep, kind and degree equal ffr_cluster_density over all N rows bit for bit, and best is bit for
+ *          bit the state a call from scratch (N_old = 0) over the N rows leaves -- so it holds batch after batch.
+ *          N_old = 0 is the clustering from scratch and produces the state.  N_old = N scores nothing and returns the same
+ *          labels.  Unlike ffr_cluster_extend, the rep of an OLD row may also rise: a border row may move to a better core
+ *          row of another cluster, and if it was the smallest member, the cluster it left is named by a larger row.
+ *   scored the pairs i < j with j >= N_old, twice (degrees, then the gated join, as ffr_cluster_density walks the triangle),
+ *          then the pairs of old rows of which one was made core by the new rows: new rows can turn old rows into cores,
+ *          and the old edges at those must be treated again.  Their number m is found on the device; nothing is read back.
+ *   guard  the kernels read a rep[i] outside [0, i] as "row i starts alone", a negative degree as 0, and a key that names
+ *          a row >= N_old, or a row that is not core by the degrees passed, as 0: whatever is passed, every index stays
+ *          in [0, N) and every walk ends.  A state that is in range but wrong gives labels with rep[rep[i]] == rep[i] and
+ *          nothing more.
+ *   errors as ffr_cluster_density and ffr_cluster_extend: FFR_ERR_ARG for N outside [0, 2^31), N_old outside [0, N], a NaN
+ *          threshold, min_rows < 1, a null emb, rep, kind, degree or best when N > 0, emb not 16-byte aligned (rep and best
+ *          8, degree and norms 4); FFR_ERR_UNSUPPORTED for dim != 512 or a grid over the limit.  N = 0 succeeds and touches
+ *          nothing.
+ *   memory no host synchronisation; the scratch is shared with the other clustering calls (norms, parent, root, minrow, the
+ *          old degrees, one minimum per rep, the list of promoted rows and its count) and grows under the same rule.
+ * Profiled as one launch under FFR_KC_SCORE with flops = 512 * (2 * (2 * N_old * N_new + N_new * (N_new - 1)) + 2 * N_old^2),
+ * an upper bound: the last term stands for 2 * m * N_old with m <= N_old.                                              */
+int ffr_cluster_density_extend(ffr_handle* h, const float* emb, const float* norms, long long N_old, long long N, int dim,
+                               float threshold, int min_rows, int64_t* rep, uint8_t* kind, int32_t* degree,
+                               unsigned long long* best, void* stream);
 
 /* ---- face alignment (landmarks -> similarity transform -> aligned uint8 crop) ---------------------------------------
  * Replaces the reference's host preprocessing, lfw/gen_lfw112x96.py:6-17 (align) with lfw/matlab_cp2tform.py
