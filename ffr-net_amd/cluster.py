@@ -1,5 +1,5 @@
-"""Grouping unlabelled embeddings into identities (include/ffrnet.h: ffr_cluster_threshold, ffr_cluster_density,
-ffr_cluster_templates).
+"""Grouping unlabelled embeddings into identities (include/ffrnet.h: ffr_cluster_threshold, ffr_cluster_extend,
+ffr_cluster_remove, ffr_cluster_density, ffr_cluster_templates).
 
 A photo collection or a dump of video tracks arrives as N unlabelled faces; before the first Gallery.add they have to be
 grouped by person and every group fused into one template row:
@@ -26,6 +26,14 @@ pairs that involve a new row are scored, and the result is the clustering of all
   store = cluster.Incremental(engine, threshold)
   store.add(f_batch)                                 # as often as faces arrive; must_link= ties the frames of one track
   t = store.templates()                              # when a gallery is wanted
+
+Rows are taken out again the same way (ffr_cluster_remove): a deleted photo, an expired track, a withdrawn enrolment.  A
+cluster that loses no row keeps its label; the survivors of a cluster that loses one are joined again among themselves
+(it may fall apart when the row that bridged two people goes), and only their pairs are scored.  The result is the
+clustering of the remaining rows, label for label.  Single link only: there is no removal from a density-gated clustering.
+
+  old_to_new = store.remove(rows)                    # compacts; renumber side tables through the map
+  c, old_to_new, kept = cluster.remove(engine, f, threshold, c, rows=rows)      # the functional form; f is not touched
 
 The density-gated clustering is extended in the same way (ffr_cluster_density_extend), with the per-row state the
 extension needs kept beside the labels; after every add the result is density() over all rows held:
@@ -95,7 +103,8 @@ def changes(rep_before, rep_after):
     templates of `stale` and recomputes those of `now`; clusters that merely gained rows keep their representative and
     show up in neither.  This is for single link (extend, Incremental) only: it relies on an old row's rep never rising
     and on clusters changing by absorption alone.  A density-gated clustering keeps neither promise (a border row may
-    change sides); use density_changes there."""
+    change sides); use density_changes there.  A removal (remove, Incremental.remove) breaks both as well: clusters
+    split and representatives rise; use removal_changes there."""
     rep_before, rep_after = torch.as_tensor(rep_before).reshape(-1), torch.as_tensor(rep_after).reshape(-1)
     n = rep_before.numel()
     if rep_after.numel() < n:
@@ -130,11 +139,92 @@ def extend(engine, emb, threshold, earlier, norms=None, must_link=None):
     return dense_ids(engine.cluster_extend(emb, threshold, prior, n_old, norms=norms, out=prior))
 
 
+def _keep_mask(n, rows, keep, device):
+    """exactly one of rows (indices to remove; duplicates allowed) and keep (mask of the rows that stay) -> bool[n]"""
+    if (rows is None) == (keep is None):
+        raise ValueError('ffrnet_amd: give exactly one of rows (the indices to remove) and keep (the mask of rows that stay)')
+    if keep is not None:
+        keep = torch.as_tensor(keep).reshape(-1).to(device)
+        if keep.numel() != n or keep.dtype not in (torch.bool, torch.uint8):
+            raise RuntimeError('ffrnet_amd: keep must be a bool or uint8 mask of %d entries' % n)
+        return keep != 0
+    rows = torch.as_tensor(rows, dtype=torch.int64).reshape(-1).to(device)
+    if rows.numel() and (int(rows.min()) < 0 or int(rows.max()) >= n):
+        raise RuntimeError('ffrnet_amd: rows to remove must be in [0, %d)' % n)
+    mask = torch.ones((n,), device=device, dtype=torch.bool)
+    mask[rows] = False
+    return mask
+
+
+def _index_maps(keep):
+    """keep bool[n] -> (old_to_new int64[n], -1 for a removed row; kept int64[n_s], new-to-old, ascending)"""
+    kept = torch.nonzero(keep).reshape(-1)
+    old_to_new = torch.full((keep.numel(),), -1, device=keep.device, dtype=torch.int64)
+    old_to_new[kept] = torch.arange(kept.numel(), device=keep.device, dtype=torch.int64)
+    return old_to_new, kept
+
+
+def _surviving_prior(tie, kept):
+    """tie[n]: integer labels of the tie groups (must-links); kept: the surviving rows, ascending -> prior[n] int64: for a
+    surviving row the first surviving row of its group, for a removed row the row itself"""
+    prior = torch.arange(tie.numel(), device=tie.device, dtype=torch.int64)
+    prior[kept] = kept[representatives(tie[kept])]
+    return prior
+
+
+def remove(engine, emb, threshold, earlier, rows=None, keep=None, must_link=None, norms=None):
+    """Take rows out of a single-link clustering of emb[N,512] -> (Clusters of the survivors in compact numbering,
+    old_to_new int64[N] with -1 for a removed row, kept int64[N_s]: the surviving rows, new-to-old).  The Clusters equal
+    cluster(engine, emb[kept], threshold) when `earlier` (a Clusters or a rep[N]) is the clustering of emb at this threshold;
+    only the pairs among the survivors of the clusters that lost a row are scored.  Give exactly one of rows (indices to
+    remove, duplicates allowed) and keep (mask of the rows that stay).  must_link: integer labels of all N rows (track ids)
+    the clustering was made with; surviving rows with equal labels stay in one cluster whatever they score.  emb is not
+    touched: compact it with emb[kept].  Single link only; there is no removal from a density-gated clustering."""
+    rep = earlier.rep if isinstance(earlier, Clusters) else torch.as_tensor(earlier)
+    rep = rep.reshape(-1).to(device=emb.device, dtype=torch.int64)
+    n = emb.size(0)
+    if rep.numel() != n:
+        raise RuntimeError('ffrnet_amd: %d earlier labels for %d embeddings' % (rep.numel(), n))
+    mask = _keep_mask(n, rows, keep, emb.device)
+    old_to_new, kept = _index_maps(mask)
+    prior = None
+    if must_link is not None:
+        must_link = torch.as_tensor(must_link).reshape(-1).to(emb.device)
+        if must_link.numel() != n:
+            raise RuntimeError('ffrnet_amd: %d must_link labels for %d rows' % (must_link.numel(), n))
+        prior = _surviving_prior(must_link, kept)
+    after = engine.cluster_remove(emb, threshold, rep, mask, prior=prior, norms=norms)
+    return dense_ids(old_to_new[after[kept]]), old_to_new, kept
+
+
+def removal_changes(rep_before, rep_after):
+    """What a removal did to the clusters: -> (touched, now), both int64, ascending, in the numbering BEFORE the removal
+    (rep_after as Engine.cluster_remove returns it: same numbering, -1 for a removed row).  touched: the old representatives
+    of the clusters that lost a row; now: the representatives of the clusters their survivors form (none where a cluster
+    was removed whole; two or more where one fell apart; a row that was no representative before where the old one was
+    removed).  A caller that keeps one template per cluster drops those of `touched` and recomputes those of `now`; every
+    other cluster kept its rows and its label."""
+    before = torch.as_tensor(rep_before).reshape(-1).to(torch.int64)
+    after = torch.as_tensor(rep_after).reshape(-1).to(device=before.device, dtype=torch.int64)
+    if after.numel() != before.numel():
+        raise ValueError('removal_changes: %d labels before, %d after' % (before.numel(), after.numel()))
+    gone = after < 0
+    touched = torch.unique(before[gone])
+    hit = torch.zeros((before.numel(),), device=before.device, dtype=torch.bool)
+    hit[touched] = True
+    return touched, torch.unique(after[~gone & hit[before]])
+
+
 class Incremental(object):
     """A clustering that keeps being added to: embeddings [n,512], their norms and rep[n] on the Engine's device, in
     grow-only buffers (as search.Gallery).  add() scores the new rows against everything held and among themselves; after
-    every add the labels are those of one clustering of all rows held.  Rows keep their index for ever; rep of an old
-    row can only decrease (cluster.changes tells which clusters were absorbed)."""
+    every add the labels are those of one clustering of all rows held.  Between removals rows keep their index and the rep
+    of an old row can only decrease (cluster.changes tells which clusters were absorbed).  remove() takes rows out, compacts
+    the buffers and returns the old-to-new index map: the rows behind a removed one move down, and a rep may rise
+    (cluster.removal_changes, on the labels before compaction, tells which clusters to recompute).  The tie groups of
+    must_link are remembered per row, so that tied rows stay together when the row that connected them leaves.  remove()
+    always calls the removal: measured up to half of the rows leaving at once, it was never slower than compacting and
+    clustering again (EXPERIMENTS.md, tools/bench_cluster_remove.py), so there is no second route."""
 
     def __init__(self, engine, threshold, capacity=0):
         self.engine = engine
@@ -143,6 +233,7 @@ class Incremental(object):
         self._emb = torch.empty((int(capacity), 512), device=engine.device, dtype=torch.float32)
         self._norms = torch.empty((int(capacity),), device=engine.device, dtype=torch.float32)
         self._rep = torch.empty((int(capacity),), device=engine.device, dtype=torch.int64)
+        self._tie = torch.empty((int(capacity),), device=engine.device, dtype=torch.int64)     # first row of the tie group
 
     def __len__(self):
         return self._n
@@ -178,20 +269,45 @@ class Incremental(object):
         if first + n > self._emb.size(0):
             cap = max(first + n, 2 * self._emb.size(0), 1024)
             grown = []
-            for buf in (self._emb, self._norms, self._rep):
+            for buf in (self._emb, self._norms, self._rep, self._tie):
                 new = torch.empty((cap,) + tuple(buf.shape[1:]), device=buf.device, dtype=buf.dtype)
                 new[:first] = buf[:first]
                 grown.append(new)
-            self._emb, self._norms, self._rep = grown
+            self._emb, self._norms, self._rep, self._tie = grown
         if n:
             total = first + n
             self._emb[first:total] = emb
             self._norms[first:total] = self.engine.row_norms(self._emb[first:total])
             self._rep[first:total] = new_prior
+            self._tie[first:total] = new_prior
             self.engine.cluster_extend(self._emb[:total], self.threshold, self._rep[:total], first,
                                        norms=self._norms[:total], validate=False, out=self._rep[:total])
             self._n = total
         return first
+
+    def remove(self, rows):
+        """Take the rows with these indices out (any integer sequence or tensor; duplicates allowed) and compact the
+        buffers in order -> old_to_new int64[n]: the new index of every row held before, -1 for a removed one, so that
+        callers can renumber their side tables.  Afterwards the labels are those of one clustering of the rows still held
+        (with their must-links), and add() works as before.  Only the pairs among the survivors of the clusters that lost a
+        row are scored."""
+        n = self._n
+        keep = _keep_mask(n, rows, None, self._rep.device)
+        old_to_new, kept = _index_maps(keep)
+        ns = kept.numel()
+        if ns == n:
+            return old_to_new
+        tie = representatives(self._tie[:n][kept])                 # the first surviving row of each group, new numbering
+        prior = torch.arange(n, device=kept.device, dtype=torch.int64)
+        prior[kept] = kept[tie]
+        rep = self.engine.cluster_remove(self._emb[:n], self.threshold, self._rep[:n], keep, prior=prior,
+                                         norms=self._norms[:n], validate=False, out=self._rep[:n])
+        self._emb[:ns] = self._emb[:n][kept]
+        self._norms[:ns] = self._norms[:n][kept]
+        self._rep[:ns] = old_to_new[rep[kept]]
+        self._tie[:ns] = tie
+        self._n = ns
+        return old_to_new
 
 
 DensityState = collections.namedtuple('DensityState', ['rep', 'kind', 'degree', 'best', 'threshold', 'min_rows'])

@@ -1,8 +1,8 @@
 // cluster.hip -- group N unlabelled 512-d embeddings into identities on the device (include/ffrnet.h:
-// ffr_cluster_threshold / ffr_cluster_extend / ffr_cluster_density / ffr_cluster_density_extend / ffr_cluster_templates):
-// single-link clustering at one cosine threshold, or gated by density over the same edges (core rows link, border rows
-// attach, noise stays alone), either of them extended batch by batch where the collection grows, then one template row per
-// cluster.  The N x N score matrix never leaves the
+// ffr_cluster_threshold / ffr_cluster_extend / ffr_cluster_remove / ffr_cluster_density / ffr_cluster_density_extend /
+// ffr_cluster_templates): single-link clustering at one cosine threshold, or gated by density over the same edges (core rows
+// link, border rows attach, noise stays alone), either of them extended batch by batch where the collection grows, single
+// link also with rows taken out again, then one template row per cluster.  The N x N score matrix never leaves the
 // chip; the output is one label per row.
 //
 // Edge rule: rows i < j are joined iff s(probe = i, gallery row = j) > threshold (strict, as eval_acc compares), with
@@ -106,6 +106,32 @@
 //    written by k_dext_promoted_list, at most n_old of them (a row is listed once), and slots past m are never an edge.
 //    The safety argument carries over once more: k_dext_promoted adds edges through uf_unite between core rows and through
 //    the same single 64-bit max; its loop over work items is bounded by a count read once; no wave waits on another.
+//  - Removal (ffr_cluster_remove; single link only): keep[x] = 0 takes row x out; nothing moves, labels stay in the caller's
+//    numbering.  g(x) = rep_in[x] where 0 <= rep_in[x] <= x, else x.  A cluster that loses no row had no edge to any other
+//    cluster and removing rows adds none: it keeps its label.  A cluster that loses a row (its label is HIT) may fall apart:
+//    its survivors, the AFFECTED rows, are joined again among themselves, and only their pairs are scored.
+//      k_remove_init / k_remove_mark   hit[] = 0, m = 0; glabel[x] = g(x), hit[g(d)] = 1 for every removed d.
+//      k_remove_list   rep[x] = -1 for a removed row, g(x) for an unaffected survivor; the affected survivors go into
+//                   list[0 .. m), m in device memory, in any order, with parent[x] = prior[x] where prior is given,
+//                   0 <= prior[x] <= x and prior[x] is an affected survivor too (a must-link that outlives the removal), else x.
+//      k_remove_walk   the self-join of the listed rows, pairs taken by list position a < b; probes and rows are both
+//                   gathered through the list (cosine_fill_probes_gather, CosineStreamT<GatherRows>); uf_unite on row numbers.
+//      k_remove_flatten   rep[x] = find(x) for the listed rows.
+//    Equality with ffr_cluster_threshold over the survivors: compacting the survivors is a monotone renumbering, so "the
+//    smallest row" and "the smaller index is the probe" carry over.  The union-find works on row numbers, so its root is the
+//    component's smallest row whatever the list's order.  The list is NOT ascending, so a pair (x, y), x < y, may be scored
+//    as probe y against row x: the transposed score has the same bits, by the argument of "Transposed pairs" above, which
+//    tests/test_gpu_cluster_density_extend.py holds on the device; the edge set is therefore that of the ascending order, and
+//    the components of an edge set do not depend on the order the edges are met in.
+//    Safety: caller data (rep_in, prior, keep) reaches an index only through g(x) and the prior guard, both in [0, x], so
+//    hit[], glabel[] and keep[] are read inside [0, N).  parent[x] <= x after the seed whatever was passed: it is x, or a
+//    prior[x] in [0, x] that is itself listed, and so has its own parent set in the same launch; rows off the list never
+//    enter the union-find.  From there (1) and (2) hold as before: a CAS replaces parent[x] only from x by something smaller.
+//    A row is listed once (by its own thread), so m <= N and every slot written is < m; the walk and the flatten read m
+//    once, clamp it to N, and bound every loop by it; a list slot past m is never read (positions past a span's end repeat
+//    the span's last listed row).  Every row index the walk uses was written to list[] by k_remove_list, a row < N.  No
+//    wave waits on another: the slot reservation is one fetch-add per wave without a retry loop, the
+//    unions are uf_unite; vector atomics only.  m = 0 (nothing removed, or only whole clusters) scores nothing.
 // k_cluster_flatten  rep[i] = find(i) as int64, after the join in stream order.
 // k_cluster_templates  one template per cluster: t = sum_r x_r / |x_r| over the cluster's rows in ascending row index
 //                (order[] = rows sorted by cluster then index, offsets[C + 1]), then t / |t|.  One wave per cluster, lane
@@ -519,6 +545,149 @@ __global__ __launch_bounds__(256, 1) void k_dext_promoted(const PromotedArgs a) 
     }
 }
 
+// ---- ffr_cluster_remove: see "Removal" in the header ----
+
+// g(x): the label row x came with, under the guard of the seed (an entry outside [0, x] is read as x)
+__device__ __forceinline__ int rm_label(const int64_t* rep_in, int x) {
+    const int64_t r = rep_in[x];
+    return dx_rep_ok(r, x) ? (int)r : x;
+}
+
+__global__ __launch_bounds__(256) void k_remove_init(int* __restrict__ hit, int* __restrict__ mcount, int n) {
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    if (x == 0) *mcount = 0;
+    if (x < n) hit[x] = 0;
+}
+
+// glabel[x] = g(x), kept so that nothing reads rep_in after this kernel (rep may be rep_in); hit[g(d)] = 1 for a removed d:
+// every writer of a cell stores the same 1
+__global__ __launch_bounds__(256) void k_remove_mark(const int64_t* __restrict__ rep_in, const uint8_t* __restrict__ keep,
+                                                     int* __restrict__ glabel, int* __restrict__ hit, int n) {
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    if (x >= n) return;
+    const int g = rm_label(rep_in, x);
+    glabel[x] = g;
+    if (!keep[x]) hit[g] = 1;
+}
+
+// Removed rows and unaffected survivors get their label here.  An affected survivor is listed and seeded: parent[x] =
+// prior[x] where that is a row of [0, x] that is itself an affected survivor (it is then listed by its own thread), else x.
+// One atomic per wave reserves the wave's slots; the order of the list is whatever the waves' atomics make it.
+__global__ __launch_bounds__(256) void k_remove_list(const int* __restrict__ glabel, const int* __restrict__ hit,
+                                                     const uint8_t* __restrict__ keep, const int64_t* __restrict__ prior,
+                                                     int* __restrict__ parent, int* __restrict__ list, int* __restrict__ mcount,
+                                                     int64_t* __restrict__ rep, int n) {
+    const int x = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63;
+    bool listed = false;
+    int p = x;
+    if (x < n) {
+        if (!keep[x]) {
+            rep[x] = -1;
+        } else if (!hit[glabel[x]]) {
+            rep[x] = glabel[x];
+        } else {
+            listed = true;
+            if (prior) {
+                const int64_t q = prior[x];
+                if (dx_rep_ok(q, x) && keep[q] && hit[glabel[q]]) p = (int)q;
+            }
+        }
+    }
+    const unsigned long long b = __ballot(listed);
+    if (!b) return;
+    const int leader = __builtin_ctzll(b);
+    int base = 0;
+    if (lane == leader) base = __hip_atomic_fetch_add(mcount, __builtin_popcountll(b), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    base = __shfl(base, leader);
+    if (listed) {
+        parent[x] = p;
+        list[base + __builtin_popcountll(b & ((1ull << lane) - 1))] = x;         // < m <= n: a row is listed once
+    }
+}
+
+constexpr int RM_SPAN_STEPS = 8;                      // 128-slot steps an item streams per probe fill, at most
+constexpr int RM_SPAN = RM_SPAN_STEPS * CT_STEP;
+
+struct RemoveArgs {
+    const float* emb;         // [N][512]
+    const float* norm;        // [N]
+    int* parent;              // [N]
+    const int* list;          // [N], the first *mcount entries are set
+    const int* mcount;
+    int n;
+    float threshold;
+};
+
+// The self-join of the listed rows: the pairs of list positions a < b, probe list[a] against row list[b].  A work item is
+// (tile of 32 positions as probes, span of `spi` steps of 128 positions as rows); a fixed grid loops over the
+// ceil(m / 32) * ceil(steps / spi) items, m read once from device memory (uniform in the block: the barriers and the
+// `continue` are legal), so m < 2 is one early return per block.  An item whose span ends at or before its tile's first
+// position has no pair and is skipped; the others start at the first step that can hold a position above it, as
+// k_cluster_walk does on rows.  spi is sized from m so that there are about 4 items per block, up to RM_SPAN_STEPS: a
+// probe fill (64 KiB into LDS) is then shared by up to 1024 rows and the prefetch ring runs across the steps.  The span's
+// rows and norms are staged in LDS once per item; positions past m repeat the span's last row, in bounds, and are masked.
+// The tile, the chain sum and cosine_score are those of k_cluster_walk; the epilogue is uf_unite on the rows' own numbers.
+__global__ __launch_bounds__(256, 1) void k_remove_walk(const RemoveArgs a) {
+    __shared__ __attribute__((aligned(16))) f32x4 qf[CT_NG * 64];
+    __shared__ int prow[RM_SPAN];
+    __shared__ float pnorm[RM_SPAN];
+
+    const int m = min(*a.mcount, a.n);
+    if (m < 2) return;
+    const int tid = threadIdx.x, lane = tid & 63, n = lane & 31, h = lane >> 5;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int ntiles = (m + CT_QT - 1) / CT_QT, nst = (m + CT_STEP - 1) / CT_STEP;
+    const long long fit = (long long)ntiles * nst / (4LL * gridDim.x);
+    const int spi = (int)max(1LL, min((long long)RM_SPAN_STEPS, fit));
+    const int ngroups = (nst + spi - 1) / spi, span = spi * CT_STEP;
+    const long long items = (long long)ntiles * ngroups;
+
+    for (long long it = blockIdx.x; it < items; it += gridDim.x) {
+        const int tile = (int)(it / ngroups), group = (int)(it - (long long)tile * ngroups);
+        const int q0 = tile * CT_QT, nq = min(CT_QT, m - q0);              // >= 1
+        const int s0 = group * span, ns = min(span, m - s0);               // >= 1
+        if (s0 + ns <= q0 + 1) continue;                    // no position of this span is above the tile's first
+        const int step0 = q0 + 1 > s0 ? (q0 + 1 - s0) / CT_STEP : 0;
+        __syncthreads();                                    // the previous item's reads of qf, prow, pnorm are over
+        cosine_fill_probes_gather(qf, a.emb, a.list + q0, nq, tid);
+        for (int e = tid; e < span; e += 256) {
+            const int p = a.list[s0 + min(e, ns - 1)];
+            prow[e] = p;
+            pnorm[e] = a.norm[p];
+        }
+        __syncthreads();
+
+        const bool live = n < nq;
+        const int apos = q0 + n;                            // the lane's probe position
+        const int irow = live ? a.list[apos] : 0;
+        const float qn = live ? a.norm[irow] : 0.f;
+
+        CosineStreamT<GatherRows> gs(a.emb, lane);
+        gs.prime(prow[min(step0 * CT_STEP + w * 32 + n, ns - 1)]);
+        const int nsteps = (ns + CT_STEP - 1) / CT_STEP;    // nsteps * CT_STEP <= span
+        for (int step = step0; step < nsteps; ++step) {
+            const int sbase = step * CT_STEP;
+            f32x16 acc8[CT_NACC];
+            gs.tile(acc8, qf, prow[min(sbase + CT_STEP + w * 32 + n, ns - 1)]);
+            const f32x16 acc = COSINE_CHAIN_SUM(acc8);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int lr = sbase + cosine_lane_row(w, r, h);           // < span
+                const float sc = cosine_score(acc[r], qn, pnorm[lr]);
+                if (live && lr < ns && s0 + lr > apos && sc > a.threshold) uf_unite(a.parent, irow, prow[lr]);
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_remove_flatten(const int* __restrict__ parent, const int* __restrict__ list,
+                                                        const int* __restrict__ mcount, int n, int64_t* __restrict__ rep) {
+    const int s = blockIdx.x * 256 + threadIdx.x;
+    if (s >= min(*mcount, n)) return;
+    const int x = list[s];
+    rep[x] = uf_find(parent, x);
+}
+
 // parent[x] = x, degree[x] = 0, best[x] = 0
 __global__ __launch_bounds__(256) void k_density_init(int* __restrict__ parent, int* __restrict__ degree,
                                                       unsigned long long* __restrict__ best, int n) {
@@ -709,6 +878,34 @@ hipError_t launch_cluster_density_extend(const float* emb, const float* norms, l
     if ((e = hipGetLastError()) != hipSuccess) return e;
     hipLaunchKernelGGL(k_density_label, dim3(nb), dim3(256), 0, stream, (const int*)root, (const int*)minrow, (const int*)degree,
                        (const unsigned long long*)best, min_rows, (int)N, rep, kind, (int32_t*)nullptr);
+    return hipGetLastError();
+}
+
+int cluster_remove_grid(long long N, int num_cus) {
+    const long long tiles = (N + CT_QT - 1) / CT_QT, most = tiles * ((N + CT_STEP - 1) / CT_STEP);
+    return (int)std::max(1LL, std::min(most, 2LL * num_cus));      // the blocks loop over the items; as cluster_promoted_grid
+}
+
+hipError_t launch_cluster_remove(const float* emb, const float* norms, long long N, float threshold, int walk_grid,
+                                 const int64_t* rep_in, const int64_t* prior, const uint8_t* keep, int* parent, int* glabel, int* hit,
+                                 int* list, int* mcount, int64_t* rep, hipStream_t stream) {
+    if (N <= 0) return hipSuccess;
+    const unsigned nb = (unsigned)((N + 255) / 256);
+    hipError_t e;
+    hipLaunchKernelGGL(k_remove_init, dim3(nb), dim3(256), 0, stream, hit, mcount, (int)N);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_remove_mark, dim3(nb), dim3(256), 0, stream, rep_in, keep, glabel, hit, (int)N);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_remove_list, dim3(nb), dim3(256), 0, stream, (const int*)glabel, (const int*)hit, keep, prior, parent, list,
+                       mcount, rep, (int)N);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (N > 1) {
+        RemoveArgs a{emb, norms, parent, list, mcount, (int)N, threshold};
+        hipLaunchKernelGGL(k_remove_walk, dim3((unsigned)walk_grid), dim3(256), 0, stream, a);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k_remove_flatten, dim3(nb), dim3(256), 0, stream, (const int*)parent, (const int*)list, (const int*)mcount,
+                       (int)N, rep);
     return hipGetLastError();
 }
 

@@ -57,6 +57,16 @@ __device__ __forceinline__ void cosine_fill_probes(f32x4* qf, const float* q, in
     }
 }
 
+// the gathered form: probe qn is the row rows[qn] of q (the caller keeps rows[0 .. nq) inside q); the same fragment order
+__device__ __forceinline__ void cosine_fill_probes_gather(f32x4* qf, const float* q, const int* rows, int nq, int tid) {
+    for (int e = tid; e < CT_NG * 64; e += 256) {
+        const int j = e >> 6, l = e & 63, qn = l & 31;
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        if (qn < nq) v = *(const f32x4*)(q + (size_t)rows[qn] * CT_DIM + 8 * j + 4 * (l >> 5));
+        qf[e] = v;
+    }
+}
+
 // row within a block step of accumulator element r of wave w, lane half h
 __device__ __forceinline__ int cosine_lane_row(int w, int r, int h) { return acc_row(w * 32, r) + 4 * h; }
 

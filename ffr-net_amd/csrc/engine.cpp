@@ -546,6 +546,38 @@ int ffr_cluster_extend(ffr_handle* h, const float* emb, const float* norms, long
     return cluster_rows(h, "ffr_cluster_extend", true, emb, norms, N_old, N, dim, threshold, prior, rep, stream);
 }
 
+int ffr_cluster_remove(ffr_handle* h, const float* emb, const float* norms, long long N, int dim, float threshold,
+                       const int64_t* rep_in, const int64_t* prior, const uint8_t* keep, int64_t* rep, void* stream) {
+    const char* who = "ffr_cluster_remove";
+    FFR_DEVICE_SCOPE(h); RC(check_fwd(h, false, false, 1));
+    RC(check_dim(h, who, dim));
+    if (N < 0 || N >= (1ll << 31)) return fail(h, FFR_ERR_ARG, "%s: N must be in [0, 2^31), got %lld", who, N);
+    if (threshold != threshold) return fail(h, FFR_ERR_ARG, "%s: the threshold is NaN", who);
+    if (N == 0) return FFR_OK;
+    if (!emb || !rep || !rep_in || !keep) return fail(h, FFR_ERR_ARG, "%s: emb / rep_in / keep / rep is null", who);
+    if (misaligned16(emb) || ((uintptr_t)rep & 7) || ((uintptr_t)rep_in & 7) || ((uintptr_t)prior & 7) || ((uintptr_t)norms & 3))
+        return fail(h, FFR_ERR_ARG, "%s: emb rows must be 16-byte aligned (rep_in, prior and rep 8, norms 4)", who);
+    hipStream_t st = (hipStream_t)stream;
+    // scratch: row norms [N] (used when the caller passes none), parent, the guarded labels, the hit flags and the list of
+    // affected survivors [N] ints each, and the list's count
+    float* own_norms = nullptr;
+    int *parent = nullptr, *glabel = nullptr, *hit = nullptr, *list = nullptr, *mcount = nullptr;
+    RC(carve(h, h->cluster, "clustering", [&](Arena& a) {
+        own_norms = a.take(N); parent = a.take<int>(N); glabel = a.take<int>(N); hit = a.take<int>(N); list = a.take<int>(N);
+        mcount = a.take<int>(1);
+    }));
+    // the pairs scored, m (m - 1) for m affected survivors, are counted on the device only: 0 flops are recorded; bytes: the
+    // labels in and out, keep, and the N-sized scratch written and read
+    Scope s(h, st, FFR_KC_SCORE, 0.0, (prior ? 57.0 : 49.0) * (double)N);
+    if (!norms && N > 1) {
+        HIPCK(h, launch_row_norms(emb, N, own_norms, st));
+        norms = own_norms;
+    }
+    HIPCK(h, launch_cluster_remove(emb, norms, N, threshold, cluster_remove_grid(N, h->num_cus), rep_in, prior, keep, parent, glabel,
+                                   hit, list, mcount, rep, st));
+    return FFR_OK;
+}
+
 int ffr_cluster_density(ffr_handle* h, const float* emb, const float* norms, long long N, int dim, float threshold, int min_rows,
                         int64_t* rep, uint8_t* kind, int32_t* degree, void* stream) {
     const char* who = "ffr_cluster_density";

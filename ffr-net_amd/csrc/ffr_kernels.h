@@ -316,6 +316,15 @@ hipError_t launch_cluster_density_extend(const float* emb, const float* norms, l
                                          int min_rows, int ntiles, int nchunks, long long chunk_rows, int promoted_grid, int* parent,
                                          int* deg0, int* coremin, int* root, int* minrow, int* plist, int* pcount, int64_t* rep,
                                          uint8_t* kind, int32_t* degree, unsigned long long* best, hipStream_t stream);
+// blocks of the pair walk of launch_cluster_remove: a fixed grid, the work is counted on the device
+int cluster_remove_grid(long long N, int num_cus);
+// rows with keep[x] = 0 leave a single-link clustering rep_in (mark, list, walk over the pairs of the listed rows, flatten):
+// rep[x] = -1 for a removed row, the guarded rep_in[x] where x's cluster lost no row, else the smallest row of x's component
+// among the survivors of the clusters that lost one, under the edges s > threshold and the links x - prior[x] between two
+// such rows; prior may be null, rep may be rep_in.  Scratch: parent, glabel, hit, list N ints each, mcount one int
+hipError_t launch_cluster_remove(const float* emb, const float* norms, long long N, float threshold, int walk_grid,
+                                 const int64_t* rep_in, const int64_t* prior, const uint8_t* keep, int* parent, int* glabel, int* hit,
+                                 int* list, int* mcount, int64_t* rep, hipStream_t stream);
 // templates[c] = normalised sum of the normalised rows order[offsets[c] .. offsets[c+1]); norms may be null
 hipError_t launch_cluster_templates(const float* emb, const float* norms, const int64_t* order, const int64_t* offsets,
                                     long long C, float* templates, hipStream_t stream);

@@ -127,6 +127,7 @@ SYMBOLS = [
     ('ffr_cluster_threshold', C.c_int, [_P, _P, _P, C.c_longlong, C.c_int, C.c_float, _P, _P]),
     ('ffr_cluster_templates', C.c_int, [_P, _P, _P, _P, _P, C.c_longlong, C.c_int, _P, _P]),
     ('ffr_cluster_extend', C.c_int, [_P, _P, _P, C.c_longlong, C.c_longlong, C.c_int, C.c_float, _P, _P, _P]),
+    ('ffr_cluster_remove', C.c_int, [_P, _P, _P, C.c_longlong, C.c_int, C.c_float, _P, _P, _P, _P, _P]),
     ('ffr_cluster_density', C.c_int, [_P, _P, _P, C.c_longlong, C.c_int, C.c_float, C.c_int, _P, _P, _P, _P]),
     ('ffr_cluster_density_extend', C.c_int, [_P, _P, _P, C.c_longlong, C.c_longlong, C.c_int, C.c_float, C.c_int, _P, _P, _P, _P, _P]),
     ('ffr_align_transforms', C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, _P]),
@@ -661,6 +662,46 @@ class Engine(object):
         self._call(self.lib.ffr_cluster_extend, _ptr(emb if N else None), _ptr(norms), n_old, N, emb.size(1),
                    float(threshold), _ptr(prior if N else None), _ptr(rep if N else None))
         return rep
+
+    def cluster_remove(self, emb, threshold, rep, keep, prior=None, norms=None, validate=True, out=None):
+        """Take rows out of a single-link clustering: emb[N,512] holds all rows, rep[N] (device int64) their labels from
+        cluster() or cluster_extend() at this threshold, keep[N] (device bool or uint8) is nonzero for the rows that stay.
+        Nothing is moved -> rep[N] int64 in the same numbering: -1 for a removed row; the old label for every row of a
+        cluster that lost no row; for the survivors of the clusters that lost one, the smallest row of their component when
+        only they are joined again -- the labels of cluster() over the surviving rows, once compacted.  Only the pairs of
+        those survivors are scored.  A label may rise (the representative was removed, or the cluster split).  prior[N]
+        (device int64): must-links, prior[i] <= i the first SURVIVING row of i's tie group.  The kernels read an entry of rep
+        or prior outside [0, i] as i; `validate` range-checks both here first (one small sync) and raises.  out: the result
+        tensor, rep itself allowed.  Single link only: there is no removal from a density-gated clustering."""
+        emb, norms = self._cluster_rows(emb, norms, 'cluster_remove')
+        rep_in = self._index_tensor(rep, 'rep')
+        N = emb.size(0)
+        if rep_in.numel() != N:
+            raise RuntimeError('ffrnet_amd: rep must be [%d], got %s' % (N, list(rep_in.shape)))
+        if not isinstance(keep, torch.Tensor) or keep.dtype not in (torch.bool, torch.uint8):
+            raise RuntimeError('ffrnet_amd: keep must be a bool or uint8 tensor')
+        self._tensor(keep, 'keep', keep.dtype, (N,))
+        keep = keep.contiguous()
+        if prior is not None:
+            prior = self._index_tensor(prior, 'prior')
+            if prior.numel() != N:
+                raise RuntimeError('ffrnet_amd: prior must be [%d], got %s' % (N, list(prior.shape)))
+        if validate and N:
+            row = torch.arange(N, device=rep_in.device, dtype=torch.int64)
+            bad = (rep_in < 0) | (rep_in > row)
+            if prior is not None:
+                bad |= (prior < 0) | (prior > row)
+            if bool(bad.any().item()):
+                raise RuntimeError('ffrnet_amd: cluster_remove needs 0 <= rep[i] <= i and 0 <= prior[i] <= i (and so < %d)' % N)
+        if out is None:
+            res = self._empty(N, dtype=torch.int64)
+        else:
+            res = self._index_tensor(out, 'out')
+            if res.numel() != N or res.data_ptr() != out.data_ptr():
+                raise RuntimeError('ffrnet_amd: out must be a contiguous [%d] int64 tensor' % N)
+        self._call(self.lib.ffr_cluster_remove, _ptr(emb if N else None), _ptr(norms), N, emb.size(1), float(threshold),
+                   _ptr(rep_in if N else None), _ptr(prior if N else None), _ptr(keep if N else None), _ptr(res if N else None))
+        return res
 
     def cluster_density(self, emb, threshold, min_rows, norms=None, return_degree=False):
         """Density-gated clustering of emb[N,512] (device fp32) over the edges of cluster(): degree[i] = the rows scoring

@@ -304,6 +304,45 @@ int ffr_cluster_templates(ffr_handle* h, const float* emb, const float* norms, c
  * Profiled as one launch under FFR_KC_SCORE with flops = 512 * (2 * N_old * N_new + N_new * (N_new - 1)), N_new = N - N_old. */
 int ffr_cluster_extend(ffr_handle* h, const float* emb, const float* norms, long long N_old, long long N, int dim,
                        float threshold, const int64_t* prior, int64_t* rep, void* stream);
+/* Remove rows from a single-link clustering, equal to clustering the rest.  emb[N][dim], norms[N] or NULL: as in
+ * ffr_cluster_threshold.  All labels use the caller's row numbering: nothing is moved, the caller compacts afterwards if it
+ * wants to.  keep[N] uint8: keep[x] != 0 means row x survives.  (Removal from a density-gated clustering is a different
+ * problem -- degrees fall, core rows are demoted, border rows choose again -- and is not offered.)
+ *   labels g(x) = rep_in[x] if 0 <= rep_in[x] <= x, else x: the guard of ffr_cluster_extend.  A label r is HIT iff some
+ *          removed row d has g(d) == r; a surviving row x is AFFECTED iff g(x) is hit.
+ *   result rep[N] int64.  A removed row: -1.  An unaffected survivor: g(x) -- a cluster that loses no row keeps its label; it
+ *          had no edge to any other cluster, and removing rows adds none.  An affected survivor: the smallest row of x's
+ *          connected component, among the affected survivors only, under
+ *            the scored edges: a < b, both affected survivors, s(probe = a, gallery row = b) > threshold; score bits, roles
+ *              and the strict > are those of ffr_cluster_threshold;
+ *            the links x - prior[x], where prior is not NULL, 0 <= prior[x] <= x, and both ends are affected survivors:
+ *              the must-links that outlive the removal.
+ *   scored exactly the pairs of affected survivors, m (m - 1) / 2 of them; no pair with an unaffected or a removed row.
+ *          With identities of a few rows that is a few thousand rows where a handful is removed, not N.
+ *          (a) If rep_in is ffr_cluster_threshold of all N rows at this threshold, or the result of ffr_cluster_extend batch
+ *              after batch, and prior is NULL, then rep on the survivors is ffr_cluster_threshold over the survivors alone,
+ *              bit for bit once both are put in the same numbering: dropping the removed rows renumbers monotonically, so
+ *              "the smallest row" and "the smaller index is the probe" carry over.  With must-links, prior must name for each
+ *              row the first SURVIVING row of its tie group; the result then equals ffr_cluster_extend(N_old = 0) over the
+ *              survivors with that prior.
+ *          (b) Nothing removed: rep[x] = g(x), and no pair is scored.
+ *          (c) Everything removed: all labels are -1.
+ *          (d) rep == rep_in, in place, is allowed.
+ *          (e) Repeated calls are bitwise equal: the result does not depend on the order in which the device lists the rows
+ *              or meets the edges.  (The device may score a pair with the roles exchanged; the bits are the same.)
+ *          (f) A surviving row's rep may RISE here, the one place in single link where it can: when the representative
+ *              itself is removed, or the cluster splits.
+ *   guard  whatever rep_in, prior and keep hold, every index stays in [0, N) and every walk ends: the union-find is seeded
+ *          with parent[x] = x, or a prior[x] in [0, x] that is itself an affected survivor.
+ *   errors as ffr_cluster_threshold; FFR_ERR_ARG also for a null rep_in or keep when N > 0 and for rep_in or prior not 8-byte
+ *          aligned.  N = 0 succeeds and touches nothing.
+ *   memory no host synchronisation (m stays on the device); the scratch is carved from the clustering arena (norms, parent,
+ *          the guarded labels, the hit flags, the list and its count: 20 bytes per row), grows on demand and bumps
+ *          ffr_generation under the same rule; the call may alternate freely with the other clustering calls on one handle.
+ * Profiled as one launch under FFR_KC_SCORE with flops = 0: the pair count is known on the device only.  A caller that wants
+ * a rate computes m from rep_in and keep (the survivors whose label is hit) and uses 512 * m * (m - 1).               */
+int ffr_cluster_remove(ffr_handle* h, const float* emb, const float* norms, long long N, int dim, float threshold,
+                       const int64_t* rep_in, const int64_t* prior, const uint8_t* keep, int64_t* rep, void* stream);
 /* Density-gated clustering (DBSCAN over the edge set of ffr_cluster_threshold): a row links clusters only if enough rows
  * lie within the threshold of it.  Single link lets a few in-between rows (a blurred frame, a look-alike) join two people
  * into one cluster; here such sparse rows may attach to a cluster but never connect two, and isolated rows are reported.
