@@ -215,6 +215,28 @@ def removal_changes(rep_before, rep_after):
     return touched, torch.unique(after[~gone & hit[before]])
 
 
+def _batch_rows(who, emb):
+    """add()'s batch must be emb[n,512] -> n; `who` names the class in the message"""
+    if not isinstance(emb, torch.Tensor) or emb.dim() != 2 or emb.size(1) != 512:
+        raise RuntimeError('ffrnet_amd: %s.add expects [n,512] embeddings, got %s'
+                           % (who, list(emb.shape) if isinstance(emb, torch.Tensor) else type(emb)))
+    return emb.size(0)
+
+
+def _grown(bufs, held, need):
+    """The grow-only rule of the stores: bufs, a tuple of buffers that hold `held` rows each -> the same tuple while `need`
+    rows fit, else new buffers of at least twice the capacity with the rows held copied over."""
+    if need <= bufs[0].size(0):
+        return bufs
+    cap = max(need, 2 * bufs[0].size(0), 1024)
+    grown = []
+    for buf in bufs:
+        new = torch.empty((cap,) + tuple(buf.shape[1:]), device=buf.device, dtype=buf.dtype)
+        new[:held] = buf[:held]
+        grown.append(new)
+    return tuple(grown)
+
+
 class Incremental(object):
     """A clustering that keeps being added to: embeddings [n,512], their norms and rep[n] on the Engine's device, in
     grow-only buffers (as search.Gallery).  add() scores the new rows against everything held and among themselves; after
@@ -261,19 +283,9 @@ class Incremental(object):
     def add(self, emb, must_link=None):
         """Append emb[n,512] (fp32, on the Engine's device) and extend the clustering -> the index of its first row.
         must_link: integer labels of these n rows; equal labels are tied (the frames of one track)."""
-        if not isinstance(emb, torch.Tensor) or emb.dim() != 2 or emb.size(1) != 512:
-            raise RuntimeError('ffrnet_amd: Incremental.add expects [n,512] embeddings, got %s'
-                               % (list(emb.shape) if isinstance(emb, torch.Tensor) else type(emb)))
-        n, first = emb.size(0), self._n
+        n, first = _batch_rows('Incremental', emb), self._n
         new_prior = _new_prior(first, n, must_link, self._rep.device)
-        if first + n > self._emb.size(0):
-            cap = max(first + n, 2 * self._emb.size(0), 1024)
-            grown = []
-            for buf in (self._emb, self._norms, self._rep, self._tie):
-                new = torch.empty((cap,) + tuple(buf.shape[1:]), device=buf.device, dtype=buf.dtype)
-                new[:first] = buf[:first]
-                grown.append(new)
-            self._emb, self._norms, self._rep, self._tie = grown
+        self._emb, self._norms, self._rep, self._tie = _grown((self._emb, self._norms, self._rep, self._tie), first, first + n)
         if n:
             total = first + n
             self._emb[first:total] = emb
@@ -377,8 +389,7 @@ class IncrementalDensity(object):
     (density_changes tells which templates to drop and which to compute)."""
 
     def __init__(self, engine, threshold, min_rows, capacity=0):
-        if int(min_rows) != min_rows or min_rows < 1:
-            raise RuntimeError('ffrnet_amd: IncrementalDensity needs an integer min_rows >= 1, got %r' % (min_rows,))
+        engine._min_rows(min_rows, 'IncrementalDensity')
         self.engine = engine
         self.threshold = float(threshold)
         self.min_rows = int(min_rows)
@@ -429,18 +440,9 @@ class IncrementalDensity(object):
 
     def add(self, emb):
         """Append emb[n,512] (fp32, on the Engine's device) and extend the clustering -> the index of its first row."""
-        if not isinstance(emb, torch.Tensor) or emb.dim() != 2 or emb.size(1) != 512:
-            raise RuntimeError('ffrnet_amd: IncrementalDensity.add expects [n,512] embeddings, got %s'
-                               % (list(emb.shape) if isinstance(emb, torch.Tensor) else type(emb)))
-        n, first = emb.size(0), self._n
-        if first + n > self._emb.size(0):
-            cap = max(first + n, 2 * self._emb.size(0), 1024)
-            grown = []
-            for buf in (self._emb, self._norms, self._rep, self._kind, self._degree, self._best):
-                new = torch.empty((cap,) + tuple(buf.shape[1:]), device=buf.device, dtype=buf.dtype)
-                new[:first] = buf[:first]
-                grown.append(new)
-            self._emb, self._norms, self._rep, self._kind, self._degree, self._best = grown
+        n, first = _batch_rows('IncrementalDensity', emb), self._n
+        self._emb, self._norms, self._rep, self._kind, self._degree, self._best = _grown(
+            (self._emb, self._norms, self._rep, self._kind, self._degree, self._best), first, first + n)
         if n:
             total = first + n
             self._emb[first:total] = emb

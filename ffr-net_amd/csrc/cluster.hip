@@ -85,14 +85,14 @@
 //      k_cluster_walk<true, EdgesDegree>   adds the edges with a new end into degree[]: the instantiation is new, the body not.
 //      k_dext_promoted_list   P[0 .. m) = the promoted rows, m in device memory; any order: what follows is unions and maxima.
 //      k_cluster_walk<true, EdgesGated>    the gated join over the pairs with a new end, on the final core flags.
-//      k_dext_promoted   the old-old edges with an end in P: both ends are now core -> uf_unite; the other end y is not ->
+//      k_list_walk<WalkPromoted>   the old-old edges with an end in P: both ends are now core -> uf_unite; the other end y is not ->
 //                   p is offered to best[y].  Old-old edges with no end in P need nothing: core-core ones are in the seed,
 //                   core - non-core ones in the persisted key.  An edge between two promoted rows is met twice; a union and
 //                   a maximum are idempotent.
 //      k_density_root / k_density_min / k_density_label   as above.  best[] of core rows was zeroed on the way (old core
 //                   rows in the seed, promoted rows where they are listed, new rows start at 0 and a core row gets no
 //                   offer), so the state after an extension is bit for bit the state a call from scratch leaves.
-//    Transposed pairs: k_dext_promoted scores (y, p), y > p, as probe y against row p, where ffr_cluster_density scores
+//    Transposed pairs: k_list_walk<WalkPromoted> scores (y, p), y > p, as probe y against row p, where ffr_cluster_density scores
 //    probe p against row y.  The bits are the same: a dot is the same 8 chains over the same k in the same order, each term
 //    the product of the two rows' k-th components (an fp32 product commutes, and the MFMA adds its two products of a step in
 //    k order whichever operand they came in); the chain sum is a fixed tree; the denominator fmaf(qn, gn, 1e-8) commutes in
@@ -102,10 +102,10 @@
 //    with rep[x] = r, and an old core row reads the cell it took part in itself: 0 <= parent[x] <= x, and parent[parent[x]]
 //    = parent[x] (the minimum is a core row of the same rep): a forest of depth 1 whatever was passed.  A rep outside [0, x]
 //    leaves x alone; a negative degree is read as 0; a key whose decoded row is >= n_old, or is no old core row, is read as 0,
-//    so k_density_root only ever follows a key to a core row of [0, N), a row of the union-find.  P holds rows < n_old
-//    written by k_dext_promoted_list, at most n_old of them (a row is listed once), and slots past m are never an edge.
-//    The safety argument carries over once more: k_dext_promoted adds edges through uf_unite between core rows and through
-//    the same single 64-bit max; its loop over work items is bounded by a count read once; no wave waits on another.
+//    so k_density_root only ever follows a key to a core row of [0, N), a row of the union-find.  The walk over P is
+//    "List walk" below; its own part: an edge is a uf_unite between two core rows, or the same single 64-bit max into
+//    best[y] of an old non-core row y < n_old, with a promoted row p < n_old in the key: a core row of [0, N), as
+//    k_density_root needs.
 //  - Removal (ffr_cluster_remove; single link only): keep[x] = 0 takes row x out; nothing moves, labels stay in the caller's
 //    numbering.  g(x) = rep_in[x] where 0 <= rep_in[x] <= x, else x.  A cluster that loses no row had no edge to any other
 //    cluster and removing rows adds none: it keeps its label.  A cluster that loses a row (its label is HIT) may fall apart:
@@ -114,8 +114,8 @@
 //      k_remove_list   rep[x] = -1 for a removed row, g(x) for an unaffected survivor; the affected survivors go into
 //                   list[0 .. m), m in device memory, in any order, with parent[x] = prior[x] where prior is given,
 //                   0 <= prior[x] <= x and prior[x] is an affected survivor too (a must-link that outlives the removal), else x.
-//      k_remove_walk   the self-join of the listed rows, pairs taken by list position a < b; probes and rows are both
-//                   gathered through the list (cosine_fill_probes_gather, CosineStreamT<GatherRows>); uf_unite on row numbers.
+//      k_list_walk<WalkRemove>   the self-join of the listed rows, pairs taken by list position a < b; probes and rows are
+//                   both gathered through the list; uf_unite on row numbers.
 //      k_remove_flatten   rep[x] = find(x) for the listed rows.
 //    Equality with ffr_cluster_threshold over the survivors: compacting the survivors is a monotone renumbering, so "the
 //    smallest row" and "the smaller index is the probe" carry over.  The union-find works on row numbers, so its root is the
@@ -127,11 +127,23 @@
 //    hit[], glabel[] and keep[] are read inside [0, N).  parent[x] <= x after the seed whatever was passed: it is x, or a
 //    prior[x] in [0, x] that is itself listed, and so has its own parent set in the same launch; rows off the list never
 //    enter the union-find.  From there (1) and (2) hold as before: a CAS replaces parent[x] only from x by something smaller.
-//    A row is listed once (by its own thread), so m <= N and every slot written is < m; the walk and the flatten read m
-//    once, clamp it to N, and bound every loop by it; a list slot past m is never read (positions past a span's end repeat
-//    the span's last listed row).  Every row index the walk uses was written to list[] by k_remove_list, a row < N.  No
-//    wave waits on another: the slot reservation is one fetch-add per wave without a retry loop, the
-//    unions are uf_unite; vector atomics only.  m = 0 (nothing removed, or only whole clusters) scores nothing.
+//    The slot reservation of k_remove_list is one fetch-add per wave without a retry loop; the flatten reads m once and
+//    clamps it to N as the walk does ("List walk" below).  m = 0 (nothing removed, or only whole clusters) scores nothing.
+//  - List walk (k_list_walk<P>; P = WalkPromoted: the old rows [0, n_old) as probes against the promoted rows P, every pair
+//    but (p, p); P = WalkRemove: the listed rows against themselves, the pairs of list positions a < b).  One body: work
+//    items of (tile of 32 probes, span of 128-row steps of the list) under a fixed grid, the listed rows gathered through
+//    CosineStreamT<GatherRows> (and, as probes, cosine_fill_probes_gather), the tile, chain sum and score of k_cluster_walk.
+//    m: the list's length lives in device memory (the host never learns it); every block reads it once and reads it as at
+//    most `bound`, the number of rows that can be listed (n_old, N), so every loop is bounded by a value fixed at entry,
+//    whatever the cell holds.  Slots: list[] is written only by the kernel that builds it (k_dext_promoted_list,
+//    k_remove_list), earlier in stream order; a row is listed once, by its own thread, so m <= bound, the slots [0, m) are
+//    all written and none past them is.  Rows: every slot holds the listing thread's own row, < bound <= N, and a probe is
+//    either such a row or a position below n_old <= N: every index into emb, norm, degree, best and parent is < N.  Pads:
+//    the walk reads list[] only at positions below m; the probes of a tile past its end are zeros, the slots of a span
+//    past its end repeat its last listed row, in bounds, and the edge test masks both (n < nq, slot < ns): never an edge.
+//    No wave waits on another: the barriers sit in the item loop, whose trip count and first `continue` depend on m, the
+//    grid and the block index alone (uniform in a block); a wave with no live slot in a span skips the K loop after the
+//    barriers; the edges are uf_unite or one no-return 64-bit max; vector atomics only.
 // k_cluster_flatten  rep[i] = find(i) as int64, after the join in stream order.
 // k_cluster_templates  one template per cluster: t = sum_r x_r / |x_r| over the cluster's rows in ascending row index
 //                (order[] = rows sorted by cluster then index, offsets[C + 1]), then t / |t|.  One wave per cluster, lane
@@ -271,6 +283,13 @@ __device__ __forceinline__ unsigned ordered_bits(float f) {
     return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
 }
 
+// The key by which a non-core row chooses among the core rows offered to it: the highest score wins a 64-bit maximum, among
+// equal scores the smallest core row.  A real key is never 0: its low word is >= 2^31.
+__device__ __forceinline__ unsigned long long best_key(float score, int core) {
+    return ((unsigned long long)ordered_bits(score) << 32) | (0xFFFFFFFFu - (unsigned)core);
+}
+__device__ __forceinline__ unsigned best_core(unsigned long long key) { return 0xFFFFFFFFu - (unsigned)key; }
+
 // Gated join, after the degree pass in stream order.  core(x) = degree[x] + 1 >= min_rows.  An edge between two core rows
 // is united as in single link (only core rows ever enter the union-find); an edge between a core row c and a non-core row
 // x offers c to x: best[x] = max(best[x], (ordered score << 32) | (0xFFFFFFFF - c)), one 64-bit vector atomic max at agent
@@ -304,6 +323,7 @@ struct EdgesGated {
                 if (!((one >> r) & 1u)) continue;
                 const int jrow = (int)(j0 + cosine_lane_row(w, r, h));
                 const int core = pcore ? irow : jrow, other = pcore ? jrow : irow;
+                // best_key(score, core), spelled out: through the helper the register allocation of the walk moves
                 const unsigned long long key =
                     ((unsigned long long)ordered_bits(cosine_score(acc[r], qn, gn[r])) << 32) | (0xFFFFFFFFu - (unsigned)core);
                 __hip_atomic_fetch_max(best + other, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -385,7 +405,7 @@ __global__ __launch_bounds__(256) void k_density_root(const int* __restrict__ pa
     if (x >= n) return;
     int r = x;
     if (degree[x] >= min_rows - 1) r = uf_find(parent, x);
-    else if (best[x]) r = uf_find(parent, (int)(0xFFFFFFFFu - (unsigned)best[x]));     // a core row of [0, n)
+    else if (best[x]) r = uf_find(parent, (int)best_core(best[x]));     // a core row of [0, n)
     root[x] = r;
     minrow[x] = x;
 }
@@ -447,7 +467,7 @@ __global__ __launch_bounds__(256) void k_dext_coremin(const int64_t* __restrict_
         if (dx_rep_ok(r, x)) __hip_atomic_fetch_min(coremin + r, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     } else {
         const unsigned long long key = best[x];
-        const unsigned c = 0xFFFFFFFFu - (unsigned)key;
+        const unsigned c = best_core(key);
         if (key && (c >= (unsigned)n_old || deg0[c] < need)) best[x] = 0;
     }
 }
@@ -471,78 +491,6 @@ __global__ __launch_bounds__(256) void k_dext_promoted_list(const int* __restric
     if (x >= n_old || deg0[x] >= need || degree[x] < need) return;
     best[x] = 0;
     plist[__hip_atomic_fetch_add(pcount, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)] = x;
-}
-
-struct PromotedArgs {
-    const float* emb;         // [N][512]
-    const float* norm;        // [N]
-    int* parent;              // [N]
-    const int* degree;        // [N], final
-    unsigned long long* best; // [N]
-    const int* plist;         // [n_old], the first *pcount entries are set
-    const int* pcount;
-    int n_old, ntiles;        // tiles of 32 probes over [0, n_old)
-    float threshold;
-    int need;
-};
-
-// The old-old edges with an end in P.  A work item is (tile of 32 old probes, slice of 128 rows of P); a fixed grid loops
-// over the ntiles * ceil(m / 128) items, m read from device memory (uniform in the block: the barriers are legal), so
-// m = 0 is one early return per block.  Wave w streams the rows P[128 s + 32 w ..] through CosineStreamT<GatherRows> (slots
-// past m repeat the slice's first row, in bounds, and are masked out); the tile, the chain sum and cosine_score are those
-// of k_cluster_walk.  The gallery side is always core, so an edge (y, p) is a unite when y is core and an offer of p to
-// best[y] when it is not.
-__global__ __launch_bounds__(256, 1) void k_dext_promoted(const PromotedArgs a) {
-    __shared__ __attribute__((aligned(16))) f32x4 qf[CT_NG * 64];
-    __shared__ int prow[CT_STEP];
-    __shared__ float pnorm[CT_STEP];
-
-    const int m = *a.pcount;
-    if (m <= 0) return;
-    const int tid = threadIdx.x, lane = tid & 63, n = lane & 31, h = lane >> 5;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int nslices = (m + CT_STEP - 1) / CT_STEP;
-    const long long items = (long long)a.ntiles * nslices;
-
-    for (long long it = blockIdx.x; it < items; it += gridDim.x) {
-        const int tile = (int)(it / nslices), slice = (int)(it - (long long)tile * nslices);
-        const int q0 = tile * CT_QT, nq = min(CT_QT, a.n_old - q0);
-        const int s0 = slice * CT_STEP, ns = min(CT_STEP, m - s0);         // >= 1
-        __syncthreads();                                    // the previous item's reads of qf, prow, pnorm are over
-        cosine_fill_probes(qf, a.emb, q0, nq, tid);
-        if (tid < CT_STEP) {
-            const int p = a.plist[s0 + (tid < ns ? tid : 0)];
-            prow[tid] = p;
-            pnorm[tid] = a.norm[p];
-        }
-        __syncthreads();
-
-        const int irow = q0 + n;                            // the lane's probe, an old row when n < nq
-        const bool live = n < nq;
-        const float qn = live ? a.norm[irow] : 0.f;
-        const bool pcore = live && a.degree[irow] >= a.need;
-
-        if (w * 32 >= ns) continue;                         // wave-uniform: none of this wave's 32 slots is set
-        const long long grow = prow[w * 32 + n];
-        CosineStreamT<GatherRows> gs(a.emb, lane);
-        gs.prime(grow);
-        f32x16 acc8[CT_NACC];
-        gs.tile(acc8, qf, grow);
-        const f32x16 acc = COSINE_CHAIN_SUM(acc8);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int slot = cosine_lane_row(w, r, h);
-            const int p = prow[slot];
-            const float sc = cosine_score(acc[r], qn, pnorm[slot]);
-            if (!(live && slot < ns && p != irow && sc > a.threshold)) continue;
-            if (pcore) {
-                uf_unite(a.parent, irow, p);
-            } else {
-                const unsigned long long key = ((unsigned long long)ordered_bits(sc) << 32) | (0xFFFFFFFFu - (unsigned)p);
-                __hip_atomic_fetch_max(a.best + irow, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-    }
 }
 
 // ---- ffr_cluster_remove: see "Removal" in the header ----
@@ -605,51 +553,101 @@ __global__ __launch_bounds__(256) void k_remove_list(const int* __restrict__ gla
     }
 }
 
-constexpr int RM_SPAN_STEPS = 8;                      // 128-slot steps an item streams per probe fill, at most
-constexpr int RM_SPAN = RM_SPAN_STEPS * CT_STEP;
+// ---- k_list_walk: see "List walk" in the header ----
 
-struct RemoveArgs {
+constexpr int RM_SPAN_STEPS = 8;          // 128-slot steps an item of the removal streams per probe fill, at most
+
+struct ListArgs {
     const float* emb;         // [N][512]
     const float* norm;        // [N]
     int* parent;              // [N]
-    const int* list;          // [N], the first *mcount entries are set
-    const int* mcount;
-    int n;
+    const int* list;          // the first *count entries are set, each a row < bound
+    const int* count;
+    int bound;                // *count is read as at most this: N (removal), n_old (promoted pass)
     float threshold;
+    // the promoted pass only
+    const int* degree;        // [N], final
+    unsigned long long* best; // [N]
+    int need;
 };
 
-// The self-join of the listed rows: the pairs of list positions a < b, probe list[a] against row list[b].  A work item is
-// (tile of 32 positions as probes, span of `spi` steps of 128 positions as rows); a fixed grid loops over the
-// ceil(m / 32) * ceil(steps / spi) items, m read once from device memory (uniform in the block: the barriers and the
-// `continue` are legal), so m < 2 is one early return per block.  An item whose span ends at or before its tile's first
-// position has no pair and is skipped; the others start at the first step that can hold a position above it, as
-// k_cluster_walk does on rows.  spi is sized from m so that there are about 4 items per block, up to RM_SPAN_STEPS: a
-// probe fill (64 KiB into LDS) is then shared by up to 1024 rows and the prefetch ring runs across the steps.  The span's
-// rows and norms are staged in LDS once per item; positions past m repeat the span's last row, in bounds, and are masked.
-// The tile, the chain sum and cosine_score are those of k_cluster_walk; the epilogue is uf_unite on the rows' own numbers.
-__global__ __launch_bounds__(256, 1) void k_remove_walk(const RemoveArgs a) {
-    __shared__ __attribute__((aligned(16))) f32x4 qf[CT_NG * 64];
-    __shared__ int prow[RM_SPAN];
-    __shared__ float pnorm[RM_SPAN];
+// What differs between the two walks over a list; the item loop is k_list_walk's.
+//   SPAN_STEPS     the most 128-slot steps an item spans: prow / pnorm hold that many
+//   BLOCKS_PER_CU  the kernel's launch bound
+//   TRIANGLE       pairs go by list position a < b: items below the diagonal are skipped, the others start at step0
+//   probes(a, m)   how many probe positions there are; probe_row(a, pos) the row at one (pos below that count);
+//                  fill(qf, a, q0, nq, tid) the fragments of the probes at the positions q0 .. q0 + nq
+//   pair(...)      does (probe at position apos, listed row at position bpos) count?
+//   P(a, irow, live) per-probe state, once per item; edge(a, irow, jrow, sc) what an edge does
+// Promoted pass (ffr_cluster_density_extend): the probes are the old rows [0, n_old) themselves and every pair but (p, p)
+// counts.  The listed row is always core, so an edge is a unite when the probe is core and an offer of the listed row to
+// best[probe] when it is not.  One step per item: two blocks share a CU.
+struct WalkPromoted {
+    static constexpr int SPAN_STEPS = 1, BLOCKS_PER_CU = 2;
+    static constexpr bool TRIANGLE = false;
+    bool pcore;
+    __device__ __forceinline__ WalkPromoted(const ListArgs& a, int irow, bool live) : pcore(live && a.degree[irow] >= a.need) {}
+    static __device__ __forceinline__ int probes(const ListArgs& a, int) { return a.bound; }
+    static __device__ __forceinline__ int probe_row(const ListArgs&, int pos) { return pos; }
+    static __device__ __forceinline__ void fill(f32x4* qf, const ListArgs& a, int q0, int nq, int tid) {
+        cosine_fill_probes(qf, a.emb, q0, nq, tid);
+    }
+    static __device__ __forceinline__ bool pair(int, int, int irow, int jrow) { return jrow != irow; }
+    __device__ __forceinline__ void edge(const ListArgs& a, int irow, int jrow, float sc) const {
+        if (pcore) uf_unite(a.parent, irow, jrow);
+        else __hip_atomic_fetch_max(a.best + irow, best_key(sc, jrow), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+};
 
-    const int m = min(*a.mcount, a.n);
-    if (m < 2) return;
+// Removal (ffr_cluster_remove): the self-join of the listed rows, probe list[a] against row list[b] for the positions
+// a < b; every edge is a unite on the rows' own numbers.  A probe fill (64 KiB into LDS) is shared by up to 1024 rows and the
+// prefetch ring runs across the steps.
+struct WalkRemove {
+    static constexpr int SPAN_STEPS = RM_SPAN_STEPS, BLOCKS_PER_CU = 1;
+    static constexpr bool TRIANGLE = true;
+    __device__ __forceinline__ WalkRemove(const ListArgs&, int, bool) {}
+    static __device__ __forceinline__ int probes(const ListArgs&, int m) { return m; }
+    static __device__ __forceinline__ int probe_row(const ListArgs& a, int pos) { return a.list[pos]; }
+    static __device__ __forceinline__ void fill(f32x4* qf, const ListArgs& a, int q0, int nq, int tid) {
+        cosine_fill_probes_gather(qf, a.emb, a.list + q0, nq, tid);
+    }
+    static __device__ __forceinline__ bool pair(int apos, int bpos, int, int) { return bpos > apos; }
+    __device__ __forceinline__ void edge(const ListArgs& a, int irow, int jrow, float) const { uf_unite(a.parent, irow, jrow); }
+};
+
+// Probes against the rows of a list.  A work item is (tile of 32 probe positions, span of `spi` steps of 128 list positions);
+// a fixed grid loops over the items, m read once from device memory (uniform in the block: the barriers and the first
+// `continue` are legal; the second one is per wave, after the item's barriers), so an empty list is one early return per
+// block.  spi is sized from m so that there are about 4 items per block, up to P::SPAN_STEPS.  The span's rows and their
+// norms are staged in LDS once per item; slots past the span's end repeat its last listed row, in bounds, and are masked
+// out.  The rows are gathered through CosineStreamT<GatherRows>; the tile, the chain sum and cosine_score are those of
+// k_cluster_walk.
+template <class P>
+__global__ __launch_bounds__(256, P::BLOCKS_PER_CU) void k_list_walk(const ListArgs a) {
+    constexpr int SPAN = P::SPAN_STEPS * CT_STEP;
+    __shared__ __attribute__((aligned(16))) f32x4 qf[CT_NG * 64];
+    __shared__ int prow[SPAN];
+    __shared__ float pnorm[SPAN];
+
+    const int m = min(*a.count, a.bound);
+    if (m < (P::TRIANGLE ? 2 : 1)) return;
     const int tid = threadIdx.x, lane = tid & 63, n = lane & 31, h = lane >> 5;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int ntiles = (m + CT_QT - 1) / CT_QT, nst = (m + CT_STEP - 1) / CT_STEP;
+    const int np = P::probes(a, m);
+    const int ntiles = (np + CT_QT - 1) / CT_QT, nst = (m + CT_STEP - 1) / CT_STEP;
     const long long fit = (long long)ntiles * nst / (4LL * gridDim.x);
-    const int spi = (int)max(1LL, min((long long)RM_SPAN_STEPS, fit));
+    const int spi = (int)max(1LL, min((long long)P::SPAN_STEPS, fit));
     const int ngroups = (nst + spi - 1) / spi, span = spi * CT_STEP;
     const long long items = (long long)ntiles * ngroups;
 
     for (long long it = blockIdx.x; it < items; it += gridDim.x) {
         const int tile = (int)(it / ngroups), group = (int)(it - (long long)tile * ngroups);
-        const int q0 = tile * CT_QT, nq = min(CT_QT, m - q0);              // >= 1
+        const int q0 = tile * CT_QT, nq = min(CT_QT, np - q0);             // >= 1
         const int s0 = group * span, ns = min(span, m - s0);               // >= 1
-        if (s0 + ns <= q0 + 1) continue;                    // no position of this span is above the tile's first
-        const int step0 = q0 + 1 > s0 ? (q0 + 1 - s0) / CT_STEP : 0;
+        if (P::TRIANGLE && s0 + ns <= q0 + 1) continue;     // no position of this span is above the tile's first
+        const int step0 = P::TRIANGLE && q0 + 1 > s0 ? (q0 + 1 - s0) / CT_STEP : 0;
         __syncthreads();                                    // the previous item's reads of qf, prow, pnorm are over
-        cosine_fill_probes_gather(qf, a.emb, a.list + q0, nq, tid);
+        P::fill(qf, a, q0, nq, tid);
         for (int e = tid; e < span; e += 256) {
             const int p = a.list[s0 + min(e, ns - 1)];
             prow[e] = p;
@@ -659,12 +657,15 @@ __global__ __launch_bounds__(256, 1) void k_remove_walk(const RemoveArgs a) {
 
         const bool live = n < nq;
         const int apos = q0 + n;                            // the lane's probe position
-        const int irow = live ? a.list[apos] : 0;
+        const int irow = live ? P::probe_row(a, apos) : 0;
         const float qn = live ? a.norm[irow] : 0.f;
+        const P walk(a, irow, live);
 
+        // the steps in which this wave has a slot below ns (wave-uniform: only a span's last step can lack one)
+        const int nsteps = (ns - w * 32 + CT_STEP - 1) / CT_STEP;          // nsteps * CT_STEP <= span
+        if (step0 >= nsteps) continue;
         CosineStreamT<GatherRows> gs(a.emb, lane);
         gs.prime(prow[min(step0 * CT_STEP + w * 32 + n, ns - 1)]);
-        const int nsteps = (ns + CT_STEP - 1) / CT_STEP;    // nsteps * CT_STEP <= span
         for (int step = step0; step < nsteps; ++step) {
             const int sbase = step * CT_STEP;
             f32x16 acc8[CT_NACC];
@@ -673,8 +674,9 @@ __global__ __launch_bounds__(256, 1) void k_remove_walk(const RemoveArgs a) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int lr = sbase + cosine_lane_row(w, r, h);           // < span
+                const int jrow = prow[lr];
                 const float sc = cosine_score(acc[r], qn, pnorm[lr]);
-                if (live && lr < ns && s0 + lr > apos && sc > a.threshold) uf_unite(a.parent, irow, prow[lr]);
+                if (live && lr < ns && P::pair(apos, s0 + lr, irow, jrow) && sc > a.threshold) walk.edge(a, irow, jrow, sc);
             }
         }
     }
@@ -765,74 +767,64 @@ void cluster_extend_plan(long long N_old, long long N, int num_cus, int* ntiles,
     cosine_chunks(*ntiles, n_new, per_cu, num_cus, nchunks, chunk_rows);
 }
 
+// 256-thread blocks throughout.  The arguments are converted to the kernel's parameter types here, so a call site passes
+// its pointers as they are.
+template <class... KA, class... A>
+static hipError_t launch(void (*kernel)(KA...), unsigned grid, hipStream_t stream, A... args) {
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, stream, static_cast<KA>(args)...);
+    return hipGetLastError();
+}
+#define LAUNCH(...)                                                          \
+    do {                                                                     \
+        if (hipError_t e_ = launch(__VA_ARGS__); e_ != hipSuccess) return e_; \
+    } while (0)
+
+static unsigned blocks_of(long long n) { return (unsigned)((n + 255) / 256); }
+
+// prior = null: ffr_cluster_threshold (N_old = 0), the walk compiled with the constant 0
 hipError_t launch_cluster_extend(const float* emb, const float* norms, long long N_old, long long N, float threshold, int ntiles,
                                  int nchunks, long long chunk_rows, const int64_t* prior, int* parent, int64_t* rep,
                                  hipStream_t stream) {
     if (N <= 0) return hipSuccess;
-    const unsigned nb = (unsigned)((N + 255) / 256);
-    hipLaunchKernelGGL(k_cluster_seed, dim3(nb), dim3(256), 0, stream, parent, prior, (int)N);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
+    if (prior) LAUNCH(k_cluster_seed, blocks_of(N), stream, parent, prior, (int)N);
+    else LAUNCH(k_cluster_init, blocks_of(N), stream, parent, (int)N);
     if (N > 1 && N_old < N) {
-        JoinArgs a{emb, norms, parent, N, chunk_rows, threshold, nchunks, ntiles, N_old, nullptr, nullptr, 0};
-        hipLaunchKernelGGL((k_cluster_walk<true, EdgesUnite>), dim3((unsigned)((long long)nchunks * ntiles)), dim3(256), 0, stream, a);
-        e = hipGetLastError();
-        if (e != hipSuccess) return e;
+        const JoinArgs a{emb, norms, parent, N, chunk_rows, threshold, nchunks, ntiles, N_old, nullptr, nullptr, 0};
+        const unsigned grid = (unsigned)((long long)nchunks * ntiles);
+        if (prior) LAUNCH(k_cluster_walk<true, EdgesUnite>, grid, stream, a);
+        else LAUNCH(k_cluster_walk<false, EdgesUnite>, grid, stream, a);
     }
-    hipLaunchKernelGGL(k_cluster_flatten, dim3(nb), dim3(256), 0, stream, (const int*)parent, (int)N, rep);
-    return hipGetLastError();
+    LAUNCH(k_cluster_flatten, blocks_of(N), stream, parent, (int)N, rep);
+    return hipSuccess;
 }
 
-hipError_t launch_cluster_threshold(const float* emb, const float* norms, long long N, float threshold, int ntiles, int nchunks,
-                                    long long chunk_rows, int* parent, int64_t* rep, hipStream_t stream) {
-    if (N <= 0) return hipSuccess;
-    const unsigned nb = (unsigned)((N + 255) / 256);
-    hipLaunchKernelGGL(k_cluster_init, dim3(nb), dim3(256), 0, stream, parent, (int)N);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    if (N > 1) {
-        JoinArgs a{emb, norms, parent, N, chunk_rows, threshold, nchunks, ntiles, 0, nullptr, nullptr, 0};
-        hipLaunchKernelGGL((k_cluster_walk<false, EdgesUnite>), dim3((unsigned)((long long)nchunks * ntiles)), dim3(256), 0, stream, a);
-        e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(k_cluster_flatten, dim3(nb), dim3(256), 0, stream, (const int*)parent, (int)N, rep);
-    return hipGetLastError();
+// root, min, label: the end of both density launchers
+static hipError_t density_finish(long long N, int min_rows, const int* parent, const int* degree, const unsigned long long* best,
+                                 int* root, int* minrow, int64_t* rep, uint8_t* kind, int32_t* degree_out, hipStream_t stream) {
+    LAUNCH(k_density_root, blocks_of(N), stream, parent, degree, best, min_rows, (int)N, root, minrow);
+    LAUNCH(k_density_min, blocks_of(N), stream, root, (int)N, minrow);
+    LAUNCH(k_density_label, blocks_of(N), stream, root, minrow, degree, best, min_rows, (int)N, rep, kind, degree_out);
+    return hipSuccess;
 }
 
 hipError_t launch_cluster_density(const float* emb, const float* norms, long long N, float threshold, int min_rows, int ntiles,
                                   int nchunks, long long chunk_rows, int* parent, int* degree, int* root, int* minrow,
                                   unsigned long long* best, int64_t* rep, uint8_t* kind, int32_t* degree_out, hipStream_t stream) {
     if (N <= 0) return hipSuccess;
-    const unsigned nb = (unsigned)((N + 255) / 256);
-    hipLaunchKernelGGL(k_density_init, dim3(nb), dim3(256), 0, stream, parent, degree, best, (int)N);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
+    LAUNCH(k_density_init, blocks_of(N), stream, parent, degree, best, (int)N);
     if (N > 1) {
-        JoinArgs a{emb, norms, parent, N, chunk_rows, threshold, nchunks, ntiles, 0, degree, best, min_rows};
-        const dim3 grid((unsigned)((long long)nchunks * ntiles));
-        hipLaunchKernelGGL((k_cluster_walk<false, EdgesDegree>), grid, dim3(256), 0, stream, a);
-        e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((k_cluster_walk<false, EdgesGated>), grid, dim3(256), 0, stream, a);
-        e = hipGetLastError();
-        if (e != hipSuccess) return e;
+        const JoinArgs a{emb, norms, parent, N, chunk_rows, threshold, nchunks, ntiles, 0, degree, best, min_rows};
+        const unsigned grid = (unsigned)((long long)nchunks * ntiles);
+        LAUNCH(k_cluster_walk<false, EdgesDegree>, grid, stream, a);
+        LAUNCH(k_cluster_walk<false, EdgesGated>, grid, stream, a);
     }
-    hipLaunchKernelGGL(k_density_root, dim3(nb), dim3(256), 0, stream, (const int*)parent, (const int*)degree,
-                       (const unsigned long long*)best, min_rows, (int)N, root, minrow);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_density_min, dim3(nb), dim3(256), 0, stream, (const int*)root, (int)N, minrow);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_density_label, dim3(nb), dim3(256), 0, stream, (const int*)root, (const int*)minrow, (const int*)degree,
-                       (const unsigned long long*)best, min_rows, (int)N, rep, kind, degree_out);
-    return hipGetLastError();
+    return density_finish(N, min_rows, parent, degree, best, root, minrow, rep, kind, degree_out, stream);
 }
 
-int cluster_promoted_grid(long long N_old, int num_cus) {
-    const long long tiles = (N_old + CT_QT - 1) / CT_QT, most = tiles * ((N_old + CT_STEP - 1) / CT_STEP);
-    return (int)std::max(1LL, std::min(most, 2LL * num_cus));      // two blocks of 64 KiB LDS fit a CU
+// the blocks loop over the items, which are counted on the device; two blocks of 64 KiB LDS fit a CU
+int cluster_list_grid(long long rows, int num_cus) {
+    const long long tiles = (rows + CT_QT - 1) / CT_QT, most = tiles * ((rows + CT_STEP - 1) / CT_STEP);
+    return (int)std::max(1LL, std::min(most, 2LL * num_cus));
 }
 
 hipError_t launch_cluster_density_extend(const float* emb, const float* norms, long long N_old, long long N, float threshold,
@@ -840,81 +832,46 @@ hipError_t launch_cluster_density_extend(const float* emb, const float* norms, l
                                          int* deg0, int* coremin, int* root, int* minrow, int* plist, int* pcount, int64_t* rep,
                                          uint8_t* kind, int32_t* degree, unsigned long long* best, hipStream_t stream) {
     if (N <= 0) return hipSuccess;
-    const unsigned nb = (unsigned)((N + 255) / 256), nbo = (unsigned)((N_old + 255) / 256);
+    const unsigned nbo = blocks_of(N_old);
     const int need = min_rows - 1;
-    hipError_t e;
-    hipLaunchKernelGGL(k_dext_init, dim3(nb), dim3(256), 0, stream, parent, degree, best, deg0, coremin, pcount, (int)N_old, (int)N);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
+    LAUNCH(k_dext_init, blocks_of(N), stream, parent, degree, best, deg0, coremin, pcount, (int)N_old, (int)N);
     if (N_old > 0) {
-        hipLaunchKernelGGL(k_dext_coremin, dim3(nbo), dim3(256), 0, stream, (const int64_t*)rep, (const int*)deg0, best, coremin, need,
-                           (int)N_old);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        hipLaunchKernelGGL(k_dext_parent, dim3(nbo), dim3(256), 0, stream, (const int64_t*)rep, (const int*)deg0, (const int*)coremin,
-                           parent, need, (int)N_old);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
+        LAUNCH(k_dext_coremin, nbo, stream, rep, deg0, best, coremin, need, (int)N_old);
+        LAUNCH(k_dext_parent, nbo, stream, rep, deg0, coremin, parent, need, (int)N_old);
     }
     if (N > 1 && N_old < N) {
-        JoinArgs a{emb, norms, parent, N, chunk_rows, threshold, nchunks, ntiles, N_old, degree, best, min_rows};
-        const dim3 grid((unsigned)((long long)nchunks * ntiles));
-        hipLaunchKernelGGL((k_cluster_walk<true, EdgesDegree>), grid, dim3(256), 0, stream, a);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        if (N_old > 0) {
-            hipLaunchKernelGGL(k_dext_promoted_list, dim3(nbo), dim3(256), 0, stream, (const int*)deg0, (const int*)degree, best, plist,
-                               pcount, need, (int)N_old);
-            if ((e = hipGetLastError()) != hipSuccess) return e;
-        }
-        hipLaunchKernelGGL((k_cluster_walk<true, EdgesGated>), grid, dim3(256), 0, stream, a);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
+        const JoinArgs a{emb, norms, parent, N, chunk_rows, threshold, nchunks, ntiles, N_old, degree, best, min_rows};
+        const unsigned grid = (unsigned)((long long)nchunks * ntiles);
+        LAUNCH(k_cluster_walk<true, EdgesDegree>, grid, stream, a);
+        if (N_old > 0) LAUNCH(k_dext_promoted_list, nbo, stream, deg0, degree, best, plist, pcount, need, (int)N_old);
+        LAUNCH(k_cluster_walk<true, EdgesGated>, grid, stream, a);
         if (N_old > 1) {
-            PromotedArgs p{emb, norms, parent, degree, best, plist, pcount, (int)N_old, (int)((N_old + CT_QT - 1) / CT_QT), threshold, need};
-            hipLaunchKernelGGL(k_dext_promoted, dim3((unsigned)promoted_grid), dim3(256), 0, stream, p);
-            if ((e = hipGetLastError()) != hipSuccess) return e;
+            const ListArgs p{emb, norms, parent, plist, pcount, (int)N_old, threshold, degree, best, need};
+            LAUNCH(k_list_walk<WalkPromoted>, (unsigned)promoted_grid, stream, p);
         }
     }
-    hipLaunchKernelGGL(k_density_root, dim3(nb), dim3(256), 0, stream, (const int*)parent, (const int*)degree,
-                       (const unsigned long long*)best, min_rows, (int)N, root, minrow);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_density_min, dim3(nb), dim3(256), 0, stream, (const int*)root, (int)N, minrow);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_density_label, dim3(nb), dim3(256), 0, stream, (const int*)root, (const int*)minrow, (const int*)degree,
-                       (const unsigned long long*)best, min_rows, (int)N, rep, kind, (int32_t*)nullptr);
-    return hipGetLastError();
-}
-
-int cluster_remove_grid(long long N, int num_cus) {
-    const long long tiles = (N + CT_QT - 1) / CT_QT, most = tiles * ((N + CT_STEP - 1) / CT_STEP);
-    return (int)std::max(1LL, std::min(most, 2LL * num_cus));      // the blocks loop over the items; as cluster_promoted_grid
+    return density_finish(N, min_rows, parent, degree, best, root, minrow, rep, kind, nullptr, stream);
 }
 
 hipError_t launch_cluster_remove(const float* emb, const float* norms, long long N, float threshold, int walk_grid,
                                  const int64_t* rep_in, const int64_t* prior, const uint8_t* keep, int* parent, int* glabel, int* hit,
                                  int* list, int* mcount, int64_t* rep, hipStream_t stream) {
     if (N <= 0) return hipSuccess;
-    const unsigned nb = (unsigned)((N + 255) / 256);
-    hipError_t e;
-    hipLaunchKernelGGL(k_remove_init, dim3(nb), dim3(256), 0, stream, hit, mcount, (int)N);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_remove_mark, dim3(nb), dim3(256), 0, stream, rep_in, keep, glabel, hit, (int)N);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_remove_list, dim3(nb), dim3(256), 0, stream, (const int*)glabel, (const int*)hit, keep, prior, parent, list,
-                       mcount, rep, (int)N);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
+    LAUNCH(k_remove_init, blocks_of(N), stream, hit, mcount, (int)N);
+    LAUNCH(k_remove_mark, blocks_of(N), stream, rep_in, keep, glabel, hit, (int)N);
+    LAUNCH(k_remove_list, blocks_of(N), stream, glabel, hit, keep, prior, parent, list, mcount, rep, (int)N);
     if (N > 1) {
-        RemoveArgs a{emb, norms, parent, list, mcount, (int)N, threshold};
-        hipLaunchKernelGGL(k_remove_walk, dim3((unsigned)walk_grid), dim3(256), 0, stream, a);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
+        const ListArgs a{emb, norms, parent, list, mcount, (int)N, threshold, nullptr, nullptr, 0};
+        LAUNCH(k_list_walk<WalkRemove>, (unsigned)walk_grid, stream, a);
     }
-    hipLaunchKernelGGL(k_remove_flatten, dim3(nb), dim3(256), 0, stream, (const int*)parent, (const int*)list, (const int*)mcount,
-                       (int)N, rep);
-    return hipGetLastError();
+    LAUNCH(k_remove_flatten, blocks_of(N), stream, parent, list, mcount, (int)N, rep);
+    return hipSuccess;
 }
 
 hipError_t launch_cluster_templates(const float* emb, const float* norms, const int64_t* order, const int64_t* offsets,
                                     long long C, float* templates, hipStream_t stream) {
     if (C <= 0) return hipSuccess;
-    TemplateArgs a{emb, norms, order, offsets, templates, C};
-    hipLaunchKernelGGL(k_cluster_templates, dim3((unsigned)((C + 3) / 4)), dim3(256), 0, stream, a);
-    return hipGetLastError();
+    return launch(k_cluster_templates, (unsigned)((C + 3) / 4), stream, TemplateArgs{emb, norms, order, offsets, templates, C});
 }
 
 }  // namespace ffr

@@ -498,41 +498,80 @@ int ffr_search_topk_coarse_subjects(ffr_handle* h, const float* query, int Q, co
 }
 
 // ---- clustering (cluster.hip) ----------------------------------------------------------------------------------------
+// What the five clustering entries check and plan alike.  The pairs an entry walks with k_cluster_walk:
+enum ClusterPairs {
+    PAIRS_NONE,     // none (the removal walks a list)
+    PAIRS_ALL,      // every pair i < j: cluster_plan
+    PAIRS_NEW       // the pairs with a row >= N_old: N_old is an argument, cluster_extend_plan
+};
+struct ClusterAligned { const void* p; unsigned mask; };     // the address must be a multiple of mask + 1; null passes
+struct ClusterPre {
+    bool empty = false;       // N = 0: the entry returns FFR_OK
+    bool scores = false;      // are there pairs to score?  If not, no norms are needed
+    long long n_new = 0;
+    int T = 0, S = 0;         // the plan of the walk (PAIRS_NONE: unset)
+    long long chunk_rows = 0;
+};
+
+// The checks in the order every entry makes them: handle, dim, N, N_old, threshold, min_rows (null: the entry has none),
+// then for N > 0 the null pointers (`missing`; the message lists `missing_names`), the alignment (emb 16, norms 4 and
+// `aligned`; the message gives `aligned_names`), the plan and the grid limit.  `who` names the entry in messages.
+static int cluster_pre(ffr_handle* h, const char* who, ClusterPairs pairs, const float* emb, const float* norms, long long N_old,
+                       long long N, int dim, float threshold, const int* min_rows, bool missing, const char* missing_names,
+                       std::initializer_list<ClusterAligned> aligned, const char* aligned_names, ClusterPre* p) {
+    RC(check_fwd(h, false, false, 1));
+    RC(check_dim(h, who, dim));
+    if (N < 0 || N >= (1ll << 31)) return fail(h, FFR_ERR_ARG, "%s: N must be in [0, 2^31), got %lld", who, N);
+    if (pairs == PAIRS_NEW && (N_old < 0 || N_old > N))
+        return fail(h, FFR_ERR_ARG, "%s: N_old must be in [0, N = %lld], got %lld", who, N, N_old);
+    if (threshold != threshold) return fail(h, FFR_ERR_ARG, "%s: the threshold is NaN", who);
+    if (min_rows && *min_rows < 1) return fail(h, FFR_ERR_ARG, "%s: min_rows must be >= 1, got %d", who, *min_rows);
+    p->empty = N == 0;
+    if (p->empty) return FFR_OK;
+    if (!emb || missing) return fail(h, FFR_ERR_ARG, "%s: %s is null", who, missing_names);
+    bool off = misaligned16(emb) || ((uintptr_t)norms & 3);
+    for (const ClusterAligned& a : aligned) off = off || ((uintptr_t)a.p & a.mask);
+    if (off) return fail(h, FFR_ERR_ARG, "%s: emb rows must be 16-byte aligned (%s)", who, aligned_names);
+    p->n_new = N - N_old;
+    p->scores = pairs == PAIRS_ALL || (N > 1 && p->n_new > 0);
+    if (pairs == PAIRS_ALL) cluster_plan(N, h->num_cus, &p->T, &p->S, &p->chunk_rows);
+    else if (pairs == PAIRS_NEW && p->scores) cluster_extend_plan(N_old, N, h->num_cus, &p->T, &p->S, &p->chunk_rows);
+    if ((long long)p->T * p->S >= (1ll << 31)) {
+        if (pairs == PAIRS_NEW)
+            return fail(h, FFR_ERR_UNSUPPORTED, "%s: N = %lld with %lld new rows needs %lld blocks, over the grid limit", who, N, p->n_new,
+                        (long long)p->T * p->S);
+        return fail(h, FFR_ERR_UNSUPPORTED, "%s: N = %lld needs %lld blocks, over the grid limit", who, N, (long long)p->T * p->S);
+    }
+    return FFR_OK;
+}
+
+// our own norms (scratch of the entry's carve) where the caller passed none and pairs are scored
+static int cluster_norms(ffr_handle* h, const ClusterPre& p, const float* emb, long long N, float* own_norms, hipStream_t st,
+                         const float** norms) {
+    if (*norms || !p.scores) return FFR_OK;
+    HIPCK(h, launch_row_norms(emb, N, own_norms, st));
+    *norms = own_norms;
+    return FFR_OK;
+}
+
 // The body of ffr_cluster_threshold (ext = false: no prior, N_old = 0) and of ffr_cluster_extend; `who` names the entry in messages
 static int cluster_rows(ffr_handle* h, const char* who, bool ext, const float* emb, const float* norms, long long N_old,
                         long long N, int dim, float threshold, const int64_t* prior, int64_t* rep, void* stream) {
-    FFR_DEVICE_SCOPE(h); RC(check_fwd(h, false, false, 1));
-    RC(check_dim(h, who, dim));
-    if (N < 0 || N >= (1ll << 31)) return fail(h, FFR_ERR_ARG, "%s: N must be in [0, 2^31), got %lld", who, N);
-    if (N_old < 0 || N_old > N) return fail(h, FFR_ERR_ARG, "%s: N_old must be in [0, N = %lld], got %lld", who, N, N_old);
-    if (threshold != threshold) return fail(h, FFR_ERR_ARG, "%s: the threshold is NaN", who);
-    if (N == 0) return FFR_OK;
-    if (!emb || !rep || (ext && !prior)) return fail(h, FFR_ERR_ARG, "%s: emb / %srep is null", who, ext ? "prior / " : "");
-    if (misaligned16(emb) || ((uintptr_t)rep & 7) || ((uintptr_t)prior & 7) || ((uintptr_t)norms & 3))
-        return fail(h, FFR_ERR_ARG, "%s: emb rows must be 16-byte aligned (%srep 8, norms 4)", who, ext ? "prior and " : "");
-    const long long n_new = N - N_old;
-    const bool join = !ext || (N > 1 && n_new > 0);       // are there pairs to score?
-    int T = 0, S = 0;
-    long long chunk_rows = 0;
-    if (!ext) cluster_plan(N, h->num_cus, &T, &S, &chunk_rows);
-    else if (join) cluster_extend_plan(N_old, N, h->num_cus, &T, &S, &chunk_rows);
-    if ((long long)T * S >= (1ll << 31)) {
-        if (ext) return fail(h, FFR_ERR_UNSUPPORTED, "%s: N = %lld with %lld new rows needs %lld blocks, over the grid limit", who, N, n_new, (long long)T * S);
-        return fail(h, FFR_ERR_UNSUPPORTED, "%s: N = %lld needs %lld blocks, over the grid limit", who, N, (long long)T * S);
-    }
+    FFR_DEVICE_SCOPE(h);
+    ClusterPre p;
+    RC(cluster_pre(h, who, ext ? PAIRS_NEW : PAIRS_ALL, emb, norms, N_old, N, dim, threshold, nullptr, !rep || (ext && !prior),
+                   ext ? "emb / prior / rep" : "emb / rep", {{rep, 7}, {prior, 7}}, ext ? "prior and rep 8, norms 4" : "rep 8, norms 4", &p));
+    if (p.empty) return FFR_OK;
     hipStream_t st = (hipStream_t)stream;
     // scratch: row norms [N] (used when the caller passes none), then parent [N]
     float* own_norms = nullptr;
     int* parent = nullptr;
     RC(carve(h, h->cluster, "clustering", [&](Arena& a) { own_norms = a.take(N); parent = a.take<int>(N); }));
-    const double pairs = ext ? 2.0 * (double)N_old * (double)n_new + (double)n_new * (double)(n_new - 1) : (double)N * (double)(N - 1);
+    const double n_new = (double)p.n_new;
+    const double pairs = ext ? 2.0 * (double)N_old * n_new + n_new * (n_new - 1) : (double)N * (double)(N - 1);
     Scope s(h, st, FFR_KC_SCORE, dim * pairs, 2.0 * (double)N * (dim + 1) + (ext ? 24.0 : 16.0) * N);
-    if (!norms && join) {
-        HIPCK(h, launch_row_norms(emb, N, own_norms, st));
-        norms = own_norms;
-    }
-    if (ext) HIPCK(h, launch_cluster_extend(emb, norms, N_old, N, threshold, T, S, chunk_rows, prior, parent, rep, st));
-    else HIPCK(h, launch_cluster_threshold(emb, norms, N, threshold, T, S, chunk_rows, parent, rep, st));
+    RC(cluster_norms(h, p, emb, N, own_norms, st, &norms));
+    HIPCK(h, launch_cluster_extend(emb, norms, N_old, N, threshold, p.T, p.S, p.chunk_rows, prior, parent, rep, st));
     return FFR_OK;
 }
 
@@ -548,15 +587,11 @@ int ffr_cluster_extend(ffr_handle* h, const float* emb, const float* norms, long
 
 int ffr_cluster_remove(ffr_handle* h, const float* emb, const float* norms, long long N, int dim, float threshold,
                        const int64_t* rep_in, const int64_t* prior, const uint8_t* keep, int64_t* rep, void* stream) {
-    const char* who = "ffr_cluster_remove";
-    FFR_DEVICE_SCOPE(h); RC(check_fwd(h, false, false, 1));
-    RC(check_dim(h, who, dim));
-    if (N < 0 || N >= (1ll << 31)) return fail(h, FFR_ERR_ARG, "%s: N must be in [0, 2^31), got %lld", who, N);
-    if (threshold != threshold) return fail(h, FFR_ERR_ARG, "%s: the threshold is NaN", who);
-    if (N == 0) return FFR_OK;
-    if (!emb || !rep || !rep_in || !keep) return fail(h, FFR_ERR_ARG, "%s: emb / rep_in / keep / rep is null", who);
-    if (misaligned16(emb) || ((uintptr_t)rep & 7) || ((uintptr_t)rep_in & 7) || ((uintptr_t)prior & 7) || ((uintptr_t)norms & 3))
-        return fail(h, FFR_ERR_ARG, "%s: emb rows must be 16-byte aligned (rep_in, prior and rep 8, norms 4)", who);
+    FFR_DEVICE_SCOPE(h);
+    ClusterPre p;
+    RC(cluster_pre(h, "ffr_cluster_remove", PAIRS_NONE, emb, norms, 0, N, dim, threshold, nullptr, !rep || !rep_in || !keep,
+                   "emb / rep_in / keep / rep", {{rep, 7}, {rep_in, 7}, {prior, 7}}, "rep_in, prior and rep 8, norms 4", &p));
+    if (p.empty) return FFR_OK;
     hipStream_t st = (hipStream_t)stream;
     // scratch: row norms [N] (used when the caller passes none), parent, the guarded labels, the hit flags and the list of
     // affected survivors [N] ints each, and the list's count
@@ -569,32 +604,19 @@ int ffr_cluster_remove(ffr_handle* h, const float* emb, const float* norms, long
     // the pairs scored, m (m - 1) for m affected survivors, are counted on the device only: 0 flops are recorded; bytes: the
     // labels in and out, keep, and the N-sized scratch written and read
     Scope s(h, st, FFR_KC_SCORE, 0.0, (prior ? 57.0 : 49.0) * (double)N);
-    if (!norms && N > 1) {
-        HIPCK(h, launch_row_norms(emb, N, own_norms, st));
-        norms = own_norms;
-    }
-    HIPCK(h, launch_cluster_remove(emb, norms, N, threshold, cluster_remove_grid(N, h->num_cus), rep_in, prior, keep, parent, glabel,
+    RC(cluster_norms(h, p, emb, N, own_norms, st, &norms));
+    HIPCK(h, launch_cluster_remove(emb, norms, N, threshold, cluster_list_grid(N, h->num_cus), rep_in, prior, keep, parent, glabel,
                                    hit, list, mcount, rep, st));
     return FFR_OK;
 }
 
 int ffr_cluster_density(ffr_handle* h, const float* emb, const float* norms, long long N, int dim, float threshold, int min_rows,
                         int64_t* rep, uint8_t* kind, int32_t* degree, void* stream) {
-    const char* who = "ffr_cluster_density";
-    FFR_DEVICE_SCOPE(h); RC(check_fwd(h, false, false, 1));
-    RC(check_dim(h, who, dim));
-    if (N < 0 || N >= (1ll << 31)) return fail(h, FFR_ERR_ARG, "%s: N must be in [0, 2^31), got %lld", who, N);
-    if (threshold != threshold) return fail(h, FFR_ERR_ARG, "%s: the threshold is NaN", who);
-    if (min_rows < 1) return fail(h, FFR_ERR_ARG, "%s: min_rows must be >= 1, got %d", who, min_rows);
-    if (N == 0) return FFR_OK;
-    if (!emb || !rep || !kind) return fail(h, FFR_ERR_ARG, "%s: emb / rep / kind is null", who);
-    if (misaligned16(emb) || ((uintptr_t)rep & 7) || ((uintptr_t)degree & 3) || ((uintptr_t)norms & 3))
-        return fail(h, FFR_ERR_ARG, "%s: emb rows must be 16-byte aligned (rep 8, degree and norms 4)", who);
-    int T = 0, S = 0;
-    long long chunk_rows = 0;
-    cluster_plan(N, h->num_cus, &T, &S, &chunk_rows);
-    if ((long long)T * S >= (1ll << 31))
-        return fail(h, FFR_ERR_UNSUPPORTED, "%s: N = %lld needs %lld blocks, over the grid limit", who, N, (long long)T * S);
+    FFR_DEVICE_SCOPE(h);
+    ClusterPre p;
+    RC(cluster_pre(h, "ffr_cluster_density", PAIRS_ALL, emb, norms, 0, N, dim, threshold, &min_rows, !rep || !kind, "emb / rep / kind",
+                   {{rep, 7}, {degree, 3}}, "rep 8, degree and norms 4", &p));
+    if (p.empty) return FFR_OK;
     hipStream_t st = (hipStream_t)stream;
     // scratch: row norms [N] (used when the caller passes none), parent, degree, root, minrow [N] ints, best [N] 8-byte words
     float* own_norms = nullptr;
@@ -607,36 +629,21 @@ int ffr_cluster_density(ffr_handle* h, const float* emb, const float* norms, lon
     // the triangle is walked twice: degrees, then the gated join; bytes: the rows twice, 24 of scratch per row written and
     // read, rep, kind and degree
     Scope s(h, st, FFR_KC_SCORE, 2.0 * dim * (double)N * (double)(N - 1), 4.0 * (double)N * (dim + 1) + (degree ? 61.0 : 57.0) * N);
-    if (!norms) {
-        HIPCK(h, launch_row_norms(emb, N, own_norms, st));
-        norms = own_norms;
-    }
-    HIPCK(h, launch_cluster_density(emb, norms, N, threshold, min_rows, T, S, chunk_rows, parent, deg, root, minrow, best, rep, kind,
-                                    degree, st));
+    RC(cluster_norms(h, p, emb, N, own_norms, st, &norms));
+    HIPCK(h, launch_cluster_density(emb, norms, N, threshold, min_rows, p.T, p.S, p.chunk_rows, parent, deg, root, minrow, best, rep,
+                                    kind, degree, st));
     return FFR_OK;
 }
 
 int ffr_cluster_density_extend(ffr_handle* h, const float* emb, const float* norms, long long N_old, long long N, int dim,
                                float threshold, int min_rows, int64_t* rep, uint8_t* kind, int32_t* degree,
                                unsigned long long* best, void* stream) {
-    const char* who = "ffr_cluster_density_extend";
-    FFR_DEVICE_SCOPE(h); RC(check_fwd(h, false, false, 1));
-    RC(check_dim(h, who, dim));
-    if (N < 0 || N >= (1ll << 31)) return fail(h, FFR_ERR_ARG, "%s: N must be in [0, 2^31), got %lld", who, N);
-    if (N_old < 0 || N_old > N) return fail(h, FFR_ERR_ARG, "%s: N_old must be in [0, N = %lld], got %lld", who, N, N_old);
-    if (threshold != threshold) return fail(h, FFR_ERR_ARG, "%s: the threshold is NaN", who);
-    if (min_rows < 1) return fail(h, FFR_ERR_ARG, "%s: min_rows must be >= 1, got %d", who, min_rows);
-    if (N == 0) return FFR_OK;
-    if (!emb || !rep || !kind || !degree || !best) return fail(h, FFR_ERR_ARG, "%s: emb / rep / kind / degree / best is null", who);
-    if (misaligned16(emb) || ((uintptr_t)rep & 7) || ((uintptr_t)best & 7) || ((uintptr_t)degree & 3) || ((uintptr_t)norms & 3))
-        return fail(h, FFR_ERR_ARG, "%s: emb rows must be 16-byte aligned (rep and best 8, degree and norms 4)", who);
-    const long long n_new = N - N_old;
-    const bool join = N > 1 && n_new > 0;                 // are there pairs to score?
-    int T = 0, S = 0;
-    long long chunk_rows = 0;
-    if (join) cluster_extend_plan(N_old, N, h->num_cus, &T, &S, &chunk_rows);
-    if ((long long)T * S >= (1ll << 31))
-        return fail(h, FFR_ERR_UNSUPPORTED, "%s: N = %lld with %lld new rows needs %lld blocks, over the grid limit", who, N, n_new, (long long)T * S);
+    FFR_DEVICE_SCOPE(h);
+    ClusterPre p;
+    RC(cluster_pre(h, "ffr_cluster_density_extend", PAIRS_NEW, emb, norms, N_old, N, dim, threshold, &min_rows,
+                   !rep || !kind || !degree || !best, "emb / rep / kind / degree / best", {{rep, 7}, {best, 7}, {degree, 3}},
+                   "rep and best 8, degree and norms 4", &p));
+    if (p.empty) return FFR_OK;
     hipStream_t st = (hipStream_t)stream;
     // scratch: row norms [N] (used when the caller passes none), parent, the old degrees, the per-rep core minimum, root,
     // minrow [N] ints, the promoted rows [N_old] and their count; degree and best are the caller's state
@@ -647,15 +654,12 @@ int ffr_cluster_density_extend(ffr_handle* h, const float* emb, const float* nor
         minrow = a.take<int>(N); plist = a.take<int>(N_old + 1); pcount = a.take<int>(1);
     }));
     // both range walks, plus the promoted pass at its upper bound m = N_old (m is known on the device only)
-    const double pairs = join ? 2.0 * (2.0 * (double)N_old * (double)n_new + (double)n_new * (double)(n_new - 1)) +
-                                    2.0 * (double)N_old * (double)N_old : 0.0;
+    const double n_new = (double)p.n_new;
+    const double pairs = p.scores ? 2.0 * (2.0 * (double)N_old * n_new + n_new * (n_new - 1)) + 2.0 * (double)N_old * (double)N_old : 0.0;
     Scope s(h, st, FFR_KC_SCORE, dim * pairs, 4.0 * (double)N * (dim + 1) + 64.0 * N);
-    if (!norms && join) {
-        HIPCK(h, launch_row_norms(emb, N, own_norms, st));
-        norms = own_norms;
-    }
-    HIPCK(h, launch_cluster_density_extend(emb, norms, N_old, N, threshold, min_rows, T, S, chunk_rows,
-                                           cluster_promoted_grid(N_old, h->num_cus), parent, deg0, coremin, root, minrow, plist, pcount,
+    RC(cluster_norms(h, p, emb, N, own_norms, st, &norms));
+    HIPCK(h, launch_cluster_density_extend(emb, norms, N_old, N, threshold, min_rows, p.T, p.S, p.chunk_rows,
+                                           cluster_list_grid(N_old, h->num_cus), parent, deg0, coremin, root, minrow, plist, pcount,
                                            rep, kind, degree, best, st));
     return FFR_OK;
 }

@@ -288,26 +288,25 @@ hipError_t launch_topk_scatter(const float* fb_s, const int64_t* fb_i, const int
 // ---- clustering (cluster.hip) ----------------------------------------------------------
 // chunking of the self-join: probe tiles x row chunks, sized for the blocks on and above the diagonal; N >= 1
 void cluster_plan(long long N, int num_cus, int* ntiles, int* nchunks, long long* chunk_rows);
-// rep[i] = smallest row of i's component under the edges s(i, j) > threshold, i < j (three launches: init, join, flatten);
-// parent: N ints of scratch; norms = launch_row_norms(emb); N < 2^31, nchunks * ntiles < 2^31, rows 16-byte aligned
-hipError_t launch_cluster_threshold(const float* emb, const float* norms, long long N, float threshold, int ntiles, int nchunks,
-                                    long long chunk_rows, int* parent, int64_t* rep, hipStream_t stream);
 // chunking of the row-range join: the N - N_old new rows in chunks under ceil(N / 32) probe tiles; 0 <= N_old <= N, N >= 1
 void cluster_extend_plan(long long N_old, long long N, int num_cus, int* ntiles, int* nchunks, long long* chunk_rows);
 // rep[i] = smallest row of i's component under the links i - prior[i] and the edges s(i, j) > threshold, i < j, j >= N_old
-// (seed, row-range join, flatten); an entry of prior outside [0, i] counts as i; rep may be prior; otherwise as above
+// (seed, row-range join, flatten); an entry of prior outside [0, i] counts as i; rep may be prior.  prior = null with
+// N_old = 0 and cluster_plan's chunking: no links, every pair i < j (init, join, flatten).  parent: N ints of scratch;
+// norms = launch_row_norms(emb); N < 2^31, nchunks * ntiles < 2^31, rows 16-byte aligned
 hipError_t launch_cluster_extend(const float* emb, const float* norms, long long N_old, long long N, float threshold, int ntiles,
                                  int nchunks, long long chunk_rows, const int64_t* prior, int* parent, int64_t* rep,
                                  hipStream_t stream);
-// density-gated clustering over the edges of launch_cluster_threshold (init, degree walk, gated walk, root, min, label):
+// density-gated clustering over the edges of launch_cluster_extend (init, degree walk, gated walk, root, min, label):
 // degree[i] = edges at i; core iff degree + 1 >= min_rows; rep[i] = smallest row of i's cluster (core components + the
 // border rows attached by best score, then smallest core row); kind 2 / 1 / 0 = core / border / noise.  Scratch: parent,
 // degree, root, minrow N ints each, best N 8-byte words; degree_out may be null; the plan is cluster_plan's
 hipError_t launch_cluster_density(const float* emb, const float* norms, long long N, float threshold, int min_rows, int ntiles,
                                   int nchunks, long long chunk_rows, int* parent, int* degree, int* root, int* minrow,
                                   unsigned long long* best, int64_t* rep, uint8_t* kind, int32_t* degree_out, hipStream_t stream);
-// blocks of the promoted pass of launch_cluster_density_extend: a fixed grid, the work is counted on the device
-int cluster_promoted_grid(long long N_old, int num_cus);
+// blocks of a walk over a list of at most `rows` rows (the promoted pass of launch_cluster_density_extend, rows = N_old;
+// the pair walk of launch_cluster_remove, rows = N): a fixed grid, the work is counted on the device
+int cluster_list_grid(long long rows, int num_cus);
 // launch_cluster_density over all N rows, from the state (rep, degree, best) of the first N_old: seed, degree walk and gated
 // walk over the pairs with a new row (the plan is cluster_extend_plan's), the old rows they made core listed in plist[*pcount],
 // the old-old edges at those, then root, min, label.  rep, degree, best [N] in and out (the caller's), kind [N] out.
@@ -316,8 +315,6 @@ hipError_t launch_cluster_density_extend(const float* emb, const float* norms, l
                                          int min_rows, int ntiles, int nchunks, long long chunk_rows, int promoted_grid, int* parent,
                                          int* deg0, int* coremin, int* root, int* minrow, int* plist, int* pcount, int64_t* rep,
                                          uint8_t* kind, int32_t* degree, unsigned long long* best, hipStream_t stream);
-// blocks of the pair walk of launch_cluster_remove: a fixed grid, the work is counted on the device
-int cluster_remove_grid(long long N, int num_cus);
 // rows with keep[x] = 0 leave a single-link clustering rep_in (mark, list, walk over the pairs of the listed rows, flatten):
 // rep[x] = -1 for a removed row, the guarded rep_in[x] where x's cluster lost no row, else the smallest row of x's component
 // among the survivors of the clusters that lost one, under the edges s > threshold and the links x - prior[x] between two

@@ -623,6 +623,23 @@ class Engine(object):
         self._tensor(t, name, torch.int64, ('N',))
         return t.contiguous()
 
+    def _out_rep(self, out, N):
+        """the result tensor of a labelling: a new one, or the caller's `out` where that is a contiguous [N] int64 tensor"""
+        if out is None:
+            return self._empty(N, dtype=torch.int64)
+        rep = self._index_tensor(out, 'out')
+        if rep.numel() != N or rep.data_ptr() != out.data_ptr():
+            raise RuntimeError('ffrnet_amd: out must be a contiguous [%d] int64 tensor' % N)
+        return rep
+
+    def _min_rows(self, min_rows, who):
+        if int(min_rows) != min_rows or min_rows < 1:
+            raise RuntimeError('ffrnet_amd: %s needs an integer min_rows >= 1, got %r' % (who, min_rows))
+
+    def _n_old(self, n_old, N, who):
+        if n_old < 0 or n_old > N:
+            raise RuntimeError('ffrnet_amd: %s needs 0 <= n_old <= %d, got %d' % (who, N, n_old))
+
     def cluster(self, emb, threshold, norms=None):
         """Single-link clustering of emb[N,512] (device fp32) at one cosine threshold: rows i < j are joined iff their
         search score is > threshold -> rep[N] int64, rep[i] = the smallest row index of i's cluster.  norms[N]:
@@ -647,18 +664,12 @@ class Engine(object):
         N, n_old = emb.size(0), int(n_old)
         if prior.numel() != N:
             raise RuntimeError('ffrnet_amd: prior must be [%d], got %s' % (N, list(prior.shape)))
-        if n_old < 0 or n_old > N:
-            raise RuntimeError('ffrnet_amd: cluster_extend needs 0 <= n_old <= %d, got %d' % (N, n_old))
+        self._n_old(n_old, N, 'cluster_extend')
         if validate and N:
             row = torch.arange(N, device=prior.device, dtype=torch.int64)
             if bool(((prior < 0) | (prior > row)).any().item()):
                 raise RuntimeError('ffrnet_amd: cluster_extend needs 0 <= prior[i] <= i (and so < %d)' % N)
-        if out is None:
-            rep = self._empty(N, dtype=torch.int64)
-        else:
-            rep = self._index_tensor(out, 'out')
-            if rep.numel() != N or rep.data_ptr() != out.data_ptr():
-                raise RuntimeError('ffrnet_amd: out must be a contiguous [%d] int64 tensor' % N)
+        rep = self._out_rep(out, N)
         self._call(self.lib.ffr_cluster_extend, _ptr(emb if N else None), _ptr(norms), n_old, N, emb.size(1),
                    float(threshold), _ptr(prior if N else None), _ptr(rep if N else None))
         return rep
@@ -693,12 +704,7 @@ class Engine(object):
                 bad |= (prior < 0) | (prior > row)
             if bool(bad.any().item()):
                 raise RuntimeError('ffrnet_amd: cluster_remove needs 0 <= rep[i] <= i and 0 <= prior[i] <= i (and so < %d)' % N)
-        if out is None:
-            res = self._empty(N, dtype=torch.int64)
-        else:
-            res = self._index_tensor(out, 'out')
-            if res.numel() != N or res.data_ptr() != out.data_ptr():
-                raise RuntimeError('ffrnet_amd: out must be a contiguous [%d] int64 tensor' % N)
+        res = self._out_rep(out, N)
         self._call(self.lib.ffr_cluster_remove, _ptr(emb if N else None), _ptr(norms), N, emb.size(1), float(threshold),
                    _ptr(rep_in if N else None), _ptr(prior if N else None), _ptr(keep if N else None), _ptr(res if N else None))
         return res
@@ -710,8 +716,7 @@ class Engine(object):
         -> (rep[N] int64, the smallest row index of each row's cluster; kind[N] uint8: 2 core, 1 border, 0 noise), and
         degree[N] int32 as a third entry with return_degree.  min_rows 1 and 2 give the rep of cluster()."""
         emb, norms = self._cluster_rows(emb, norms, 'cluster_density')
-        if int(min_rows) != min_rows or min_rows < 1:
-            raise RuntimeError('ffrnet_amd: cluster_density needs an integer min_rows >= 1, got %r' % (min_rows,))
+        self._min_rows(min_rows, 'cluster_density')
         N = emb.size(0)
         rep, kind = self._empty(N, dtype=torch.int64), self._empty(N, dtype=torch.uint8)
         degree = self._empty(N, dtype=torch.int32) if return_degree else None
@@ -728,11 +733,9 @@ class Engine(object):
         call left for emb[:n_old], and best is the state for the next call.  n_old = 0 clusters from scratch.  The kernels
         read out-of-range state as "none"; `validate` range-checks it here first (check_density_state, one small sync)."""
         emb, norms = self._cluster_rows(emb, norms, 'cluster_density_extend')
-        if int(min_rows) != min_rows or min_rows < 1:
-            raise RuntimeError('ffrnet_amd: cluster_density_extend needs an integer min_rows >= 1, got %r' % (min_rows,))
+        self._min_rows(min_rows, 'cluster_density_extend')
         N, n_old = emb.size(0), int(n_old)
-        if n_old < 0 or n_old > N:
-            raise RuntimeError('ffrnet_amd: cluster_density_extend needs 0 <= n_old <= %d, got %d' % (N, n_old))
+        self._n_old(n_old, N, 'cluster_density_extend')
         state = []
         for t, name, dtype in ((rep, 'rep', torch.int64), (degree, 'degree', torch.int32), (best, 'best', torch.int64)):
             if t is None and n_old == 0:

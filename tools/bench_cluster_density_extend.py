@@ -1,5 +1,5 @@
 """Time the extension of a density-gated clustering (Engine.cluster_density_extend: the seed, k_cluster_walk twice over the
-pairs with a new row, the promoted list, k_dext_promoted, root / min / label) against clustering everything again
+pairs with a new row, the promoted list, k_list_walk over it, root / min / label) against clustering everything again
 (Engine.cluster_density over all N rows), on the bridged planted identities of tools/bench_cluster_density.py, with device
 events after a warm-up, the two calls interleaved in one process.
 

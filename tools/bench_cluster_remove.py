@@ -1,4 +1,4 @@
-"""Time the removal of rows from a single-link clustering (Engine.cluster_remove: mark, list, k_remove_walk over the pairs
+"""Time the removal of rows from a single-link clustering (Engine.cluster_remove: mark, list, k_list_walk over the pairs
 of the listed rows, flatten) against the only other correct way, compacting the survivors and clustering them again
 (Engine.cluster over emb[keep]), on the bridged planted identities of tools/bench_cluster_density.py, with device events
 after a warm-up, the two calls interleaved in one process.
