@@ -279,109 +279,124 @@ int ffr_row_norms(ffr_handle* h, const float* x, long long n, int dim, float* no
     return FFR_OK;
 }
 
-int ffr_search_topk(ffr_handle* h, const float* query, int Q, const float* gallery, const float* gallery_norms, long long G,
-                    int dim, int k, long long index_base, float* top_score, int64_t* top_index, void* stream) {
-    FFR_DEVICE_SCOPE(h); RC(check_fwd(h, false, false, 1));
-    RC(check_dim(h, "ffr_search_topk", dim));
-    if (!query || !top_score || !top_index || Q < 1 || k < 1 || k > 128 || G < 0 || (G > 0 && (!gallery || !gallery_norms)))
-        return fail(h, FFR_ERR_ARG, "ffr_search_topk: bad arguments (Q >= 1, 1 <= k <= 128, G >= 0, non-null pointers)");
-    if (misaligned16(query) || (G > 0 && misaligned16(gallery)))
-        return fail(h, FFR_ERR_ARG, "ffr_search_topk: query and gallery rows must be 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
+// What the search and merge entries share.  Lists [..][Q][k] of scores and indices; u: their subject plane, null in an entry
+// without subjects -- what tells the two kinds of entry apart from here on (12 or 16 bytes per slot)
+struct TopLists { float* s = nullptr; int64_t* i = nullptr; int32_t* u = nullptr; };
+
+static bool misaligned4(const void* p) { return ((uintptr_t)p & 3) != 0; }
+
+static int check_distinct(ffr_handle* h, const char* who, int distinct, int k) {
+    if (distinct != 0 && distinct != 1) return fail(h, FFR_ERR_ARG, "%s: distinct must be 0 or 1, got %d", who, distinct);
+    if (distinct && k > search_max_k_distinct())
+        return fail(h, FFR_ERR_ARG, "%s: identity mode serves k <= %d, got %d", who, search_max_k_distinct(), k);
+    return FFR_OK;
+}
+
+// The checks of the four search entries, in the order every entry makes them: handle, dim, null pointers and ranges (at
+// G = 0 the gallery side may be null), distinct and the k of identity mode, 16-byte rows, 4-byte subjects.  coarse: the entry
+// takes plane and plane_flag; subj: it takes subject and top.u (an entry without passes distinct = 0).  `who` names it in
+// messages.
+static int search_pre(ffr_handle* h, const char* who, bool coarse, const float* query, int Q, const float* gallery,
+                      const float* gallery_norms, const uint16_t* plane, const int* plane_flag, const int32_t* subject, long long G,
+                      int dim, int k, int distinct, const TopLists& top, bool subj) {
+    RC(check_fwd(h, false, false, 1));
+    RC(check_dim(h, who, dim));
+    const bool gallery_side = gallery && gallery_norms && (!coarse || (plane && plane_flag)) && (!subj || subject);
+    if (!query || !top.s || !top.i || (subj && !top.u) || Q < 1 || k < 1 || k > 128 || G < 0 || (G > 0 && !gallery_side))
+        return fail(h, FFR_ERR_ARG, "%s: bad arguments (Q >= 1, 1 <= k <= 128, G >= 0, non-null pointers)", who);
+    RC(check_distinct(h, who, distinct, k));
+    if (misaligned16(query) || (G > 0 && (misaligned16(gallery) || misaligned16(plane))))
+        return fail(h, FFR_ERR_ARG, "%s: %s rows must be 16-byte aligned", who, coarse ? "query, gallery and plane" : "query and gallery");
+    if (G > 0 && misaligned4(subject)) return fail(h, FFR_ERR_ARG, "%s: gallery_subject must be 4-byte aligned", who);
+    return FFR_OK;
+}
+
+// An exact pass into given lists: the search of the plan (T, S, chunk_rows) and, when S > 1, the merge of its chunk lists
+// part[S][Q][k].  subject (or null) and distinct: the policy.  live (device, or null): only the probes [0, *live) are searched
+static int exact_pass(ffr_handle* h, const float* query, const float* qnorm, int Q, const float* gallery, const float* gallery_norms,
+                      const int32_t* subject, long long G, int k, long long index_base, int distinct, int T, int S,
+                      long long chunk_rows, const TopLists& dst, const TopLists& part, const int* live, hipStream_t st) {
+    const TopLists& out = S > 1 ? part : dst;
+    const SearchArgs a{query, qnorm, gallery, nullptr, gallery_norms, G, chunk_rows, index_base, out.s, out.i, live, Q, k, S, T,
+                       subject, out.u};
+    HIPCK(h, launch_search(a, !subject ? SEARCH_ROWS : distinct ? SEARCH_DISTINCT : SEARCH_LIVE, st));
+    if (S > 1) HIPCK(h, launch_topk_merge(part.s, part.i, part.u, S, Q, k, distinct, dst.s, dst.i, dst.u, st, live));
+    return FFR_OK;
+}
+
+// The exact search of checked arguments: ffr_search_topk, ffr_search_topk_subjects (top.u), and the coarse entries where
+// their pass does not serve
+static int exact_search(ffr_handle* h, const float* query, int Q, const float* gallery, const float* gallery_norms,
+                        const int32_t* subject, long long G, int dim, int k, long long index_base, int distinct, const TopLists& top,
+                        hipStream_t st) {
+    const double slot = top.u ? 16.0 : 12.0;
     if (G == 0) {                 // k slots of padding per probe: the merge of no list
-        Scope s(h, st, FFR_KC_SCORE, 0.0, 12.0 * Q * k);
-        HIPCK(h, launch_topk_merge(nullptr, nullptr, 0, Q, k, top_score, top_index, st));
+        Scope s(h, st, FFR_KC_SCORE, 0.0, slot * Q * k);
+        HIPCK(h, launch_topk_merge(nullptr, nullptr, nullptr, 0, Q, k, distinct, top.s, top.i, top.u, st));
         return FFR_OK;
     }
     int T = 0, S = 0;
     long long chunk_rows = 0;
     search_plan(Q, G, h->num_cus, &T, &S, &chunk_rows);
-    // scratch: probe norms [Q], then the chunk lists [S][Q][k] (scores, indices) when there is more than one chunk
+    // scratch: probe norms [Q], then the chunk lists [S][Q][k] (scores, indices, with subjects a third plane) when there is
+    // more than one chunk
     float* qnorm = nullptr;
-    float* part_s = top_score;
-    int64_t* part_i = top_index;
+    TopLists part;
     RC(carve(h, h->search, "search", [&](Arena& a) {
         qnorm = a.take(Q);
-        if (S > 1) { part_s = a.take((size_t)S * Q * k); part_i = a.take<int64_t>((size_t)S * Q * k); }
+        if (S > 1) {
+            part.s = a.take((size_t)S * Q * k); part.i = a.take<int64_t>((size_t)S * Q * k);
+            if (top.u) part.u = a.take<int32_t>((size_t)S * Q * k);
+        }
     }));
-    Scope s(h, st, FFR_KC_SCORE, 2.0 * Q * (double)G * dim, 4.0 * (double)G * (dim + 1) + 4.0 * Q * dim + 12.0 * Q * k);
+    Scope s(h, st, FFR_KC_SCORE, 2.0 * Q * (double)G * dim, 4.0 * (double)G * (dim + (top.u ? 2 : 1)) + 4.0 * Q * dim + slot * Q * k);
     HIPCK(h, launch_row_norms(query, Q, qnorm, st));
-    HIPCK(h, launch_search_topk(query, qnorm, Q, gallery, gallery_norms, G, k, index_base, T, S, chunk_rows, part_s, part_i,
-                                st));
-    if (S > 1) HIPCK(h, launch_topk_merge(part_s, part_i, S, Q, k, top_score, top_index, st));
+    return exact_pass(h, query, qnorm, Q, gallery, gallery_norms, subject, G, k, index_base, distinct, T, S, chunk_rows, top, part,
+                      nullptr, st);
+}
+
+int ffr_search_topk(ffr_handle* h, const float* query, int Q, const float* gallery, const float* gallery_norms, long long G,
+                    int dim, int k, long long index_base, float* top_score, int64_t* top_index, void* stream) {
+    FFR_DEVICE_SCOPE(h);
+    const TopLists top{top_score, top_index, nullptr};
+    RC(search_pre(h, "ffr_search_topk", false, query, Q, gallery, gallery_norms, nullptr, nullptr, nullptr, G, dim, k, 0, top, false));
+    return exact_search(h, query, Q, gallery, gallery_norms, nullptr, G, dim, k, index_base, 0, top, (hipStream_t)stream);
+}
+
+int ffr_search_topk_subjects(ffr_handle* h, const float* query, int Q, const float* gallery, const float* gallery_norms,
+                             const int32_t* gallery_subject, long long G, int dim, int k, long long index_base, int distinct,
+                             float* top_score, int64_t* top_index, int32_t* top_subject, void* stream) {
+    FFR_DEVICE_SCOPE(h);
+    const TopLists top{top_score, top_index, top_subject};
+    RC(search_pre(h, "ffr_search_topk_subjects", false, query, Q, gallery, gallery_norms, nullptr, nullptr, gallery_subject, G, dim, k,
+                  distinct, top, true));
+    return exact_search(h, query, Q, gallery, gallery_norms, gallery_subject, G, dim, k, index_base, distinct, top, (hipStream_t)stream);
+}
+
+// The body of ffr_topk_merge and of ffr_topk_merge_subjects (subj: the lists carry subjects)
+static int merge_entry(ffr_handle* h, const char* who, bool subj, const float* score, const int64_t* index, const int32_t* subject,
+                       int S, int Q, int k, int distinct, const TopLists& out, hipStream_t st) {
+    RC(check_fwd(h, false, false, 1));
+    if (!score || !index || !out.s || !out.i || (subj && (!subject || !out.u)) || S < 1 || S > 4096 || Q < 1 || k < 1 || k > 128)
+        return fail(h, FFR_ERR_ARG, "%s: bad arguments (1 <= S <= 4096, Q >= 1, 1 <= k <= 128, non-null pointers)", who);
+    RC(check_distinct(h, who, distinct, k));
+    const double slot = subj ? 16.0 : 12.0;
+    Scope s(h, st, FFR_KC_SCORE, 0.0, slot * (double)S * Q * k + slot * Q * k);
+    HIPCK(h, launch_topk_merge(score, index, subject, S, Q, k, distinct, out.s, out.i, out.u, st));
     return FFR_OK;
 }
 
 int ffr_topk_merge(ffr_handle* h, const float* score, const int64_t* index, int S, int Q, int k, float* out_score,
                    int64_t* out_index, void* stream) {
-    FFR_DEVICE_SCOPE(h); RC(check_fwd(h, false, false, 1));
-    if (!score || !index || !out_score || !out_index || S < 1 || S > 4096 || Q < 1 || k < 1 || k > 128)
-        return fail(h, FFR_ERR_ARG, "ffr_topk_merge: bad arguments (1 <= S <= 4096, Q >= 1, 1 <= k <= 128, non-null pointers)");
-    hipStream_t st = (hipStream_t)stream;
-    Scope s(h, st, FFR_KC_SCORE, 0.0, 12.0 * (double)S * Q * k + 12.0 * Q * k);
-    HIPCK(h, launch_topk_merge(score, index, S, Q, k, out_score, out_index, st));
-    return FFR_OK;
-}
-
-// ---- subject-labelled search (search.hip) ----------------------------------------------------------------------------------
-static bool misaligned4(const void* p) { return ((uintptr_t)p & 3) != 0; }
-
-int ffr_search_topk_subjects(ffr_handle* h, const float* query, int Q, const float* gallery, const float* gallery_norms,
-                             const int32_t* gallery_subject, long long G, int dim, int k, long long index_base, int distinct,
-                             float* top_score, int64_t* top_index, int32_t* top_subject, void* stream) {
-    FFR_DEVICE_SCOPE(h); RC(check_fwd(h, false, false, 1));
-    RC(check_dim(h, "ffr_search_topk_subjects", dim));
-    if (!query || !top_score || !top_index || !top_subject || Q < 1 || k < 1 || k > 128 || G < 0 ||
-        (G > 0 && (!gallery || !gallery_norms || !gallery_subject)))
-        return fail(h, FFR_ERR_ARG, "ffr_search_topk_subjects: bad arguments (Q >= 1, 1 <= k <= 128, G >= 0, non-null pointers)");
-    if (distinct != 0 && distinct != 1) return fail(h, FFR_ERR_ARG, "ffr_search_topk_subjects: distinct must be 0 or 1, got %d", distinct);
-    if (distinct && k > search_max_k_distinct())
-        return fail(h, FFR_ERR_ARG, "ffr_search_topk_subjects: identity mode serves k <= %d, got %d", search_max_k_distinct(), k);
-    if (misaligned16(query) || (G > 0 && misaligned16(gallery)))
-        return fail(h, FFR_ERR_ARG, "ffr_search_topk_subjects: query and gallery rows must be 16-byte aligned");
-    if (G > 0 && misaligned4(gallery_subject))
-        return fail(h, FFR_ERR_ARG, "ffr_search_topk_subjects: gallery_subject must be 4-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    if (G == 0) {                 // k slots of padding per probe: the merge of no list
-        Scope s(h, st, FFR_KC_SCORE, 0.0, 16.0 * Q * k);
-        HIPCK(h, launch_topk_merge_subjects(nullptr, nullptr, nullptr, 0, Q, k, distinct, top_score, top_index, top_subject, st));
-        return FFR_OK;
-    }
-    int T = 0, S = 0;
-    long long chunk_rows = 0;
-    search_plan(Q, G, h->num_cus, &T, &S, &chunk_rows);
-    // scratch: as ffr_search_topk, the chunk lists with a third plane [S][Q][k] of subjects
-    float* qnorm = nullptr;
-    float* part_s = top_score;
-    int64_t* part_i = top_index;
-    int32_t* part_u = top_subject;
-    RC(carve(h, h->search, "search", [&](Arena& a) {
-        qnorm = a.take(Q);
-        if (S > 1) {
-            part_s = a.take((size_t)S * Q * k); part_i = a.take<int64_t>((size_t)S * Q * k); part_u = a.take<int32_t>((size_t)S * Q * k);
-        }
-    }));
-    Scope s(h, st, FFR_KC_SCORE, 2.0 * Q * (double)G * dim, 4.0 * (double)G * (dim + 2) + 4.0 * Q * dim + 16.0 * Q * k);
-    HIPCK(h, launch_row_norms(query, Q, qnorm, st));
-    HIPCK(h, launch_search_subjects(query, qnorm, Q, gallery, gallery_norms, gallery_subject, G, k, index_base, distinct, T, S,
-                                    chunk_rows, part_s, part_i, part_u, st));
-    if (S > 1) HIPCK(h, launch_topk_merge_subjects(part_s, part_i, part_u, S, Q, k, distinct, top_score, top_index, top_subject, st));
-    return FFR_OK;
+    FFR_DEVICE_SCOPE(h);
+    return merge_entry(h, "ffr_topk_merge", false, score, index, nullptr, S, Q, k, 0, {out_score, out_index, nullptr}, (hipStream_t)stream);
 }
 
 int ffr_topk_merge_subjects(ffr_handle* h, const float* score, const int64_t* index, const int32_t* subject, int S, int Q,
                             int k, int distinct, float* out_score, int64_t* out_index, int32_t* out_subject, void* stream) {
-    FFR_DEVICE_SCOPE(h); RC(check_fwd(h, false, false, 1));
-    if (!score || !index || !subject || !out_score || !out_index || !out_subject || S < 1 || S > 4096 || Q < 1 || k < 1 || k > 128)
-        return fail(h, FFR_ERR_ARG,
-                    "ffr_topk_merge_subjects: bad arguments (1 <= S <= 4096, Q >= 1, 1 <= k <= 128, non-null pointers)");
-    if (distinct != 0 && distinct != 1) return fail(h, FFR_ERR_ARG, "ffr_topk_merge_subjects: distinct must be 0 or 1, got %d", distinct);
-    if (distinct && k > search_max_k_distinct())
-        return fail(h, FFR_ERR_ARG, "ffr_topk_merge_subjects: identity mode serves k <= %d, got %d", search_max_k_distinct(), k);
-    hipStream_t st = (hipStream_t)stream;
-    Scope s(h, st, FFR_KC_SCORE, 0.0, 16.0 * (double)S * Q * k + 16.0 * Q * k);
-    HIPCK(h, launch_topk_merge_subjects(score, index, subject, S, Q, k, distinct, out_score, out_index, out_subject, st));
-    return FFR_OK;
+    FFR_DEVICE_SCOPE(h);
+    return merge_entry(h, "ffr_topk_merge_subjects", true, score, index, subject, S, Q, k, distinct,
+                       {out_score, out_index, out_subject}, (hipStream_t)stream);
 }
 
 // ---- certified bf16 shortlist search (search_coarse.hip) -----------------------------------------------------------------
@@ -397,13 +412,15 @@ int ffr_coarse_pack(ffr_handle* h, const float* rows, const float* norms, long l
     return FFR_OK;
 }
 
-// The shortlist search of checked arguments, G >= 1 and a k the pass serves: ffr_search_topk_coarse (subject = null), and
-// ffr_search_topk_coarse_subjects, whose pass skips the removed rows, whose lists carry a subject plane and whose exact pass
-// is the subject search
+// The shortlist search of checked arguments: ffr_search_topk_coarse (subject = null), and ffr_search_topk_coarse_subjects,
+// whose pass skips the removed rows, whose lists carry a subject plane and whose exact pass is the subject search
 static int coarse_search(ffr_handle* h, const float* query, int Q, const float* gallery, const float* gallery_norms,
                          const uint16_t* gallery_plane, const int* plane_flag, const int32_t* subject, long long G, int dim, int k,
-                         long long index_base, int distinct, float* top_score, int64_t* top_index, int32_t* top_subject, int* certified,
-                         hipStream_t st) {
+                         long long index_base, int distinct, const TopLists& top, int* certified, hipStream_t st) {
+    if (G == 0 || k > coarse_max_k(distinct)) {  // nothing to shortlist, or a k the pass does not serve (64 rows, 32 identities):
+        if (certified) HIPCK(h, hipMemsetAsync(certified, 0, sizeof(int) * (size_t)Q, st));      // the exact search alone
+        return exact_search(h, query, Q, gallery, gallery_norms, subject, G, dim, k, index_base, distinct, top, st);
+    }
     const int kp = coarse_shortlist_size(k, distinct);
     int T = 0, S = 0, Tf = 0, Sf = 0;
     long long chunk_rows = 0, chunk_f = 0;
@@ -413,88 +430,61 @@ static int coarse_search(ffr_handle* h, const float* query, int Q, const float* 
     // lists [Q][k]; the chunk lists of the coarse pass [S][Q][kp] and then of the exact pass [Sf][Q][k], in the same space;
     // with subjects, a third plane for the exact lists and their chunk lists
     const size_t part_n = std::max(S > 1 ? (size_t)S * Q * kp : 0, Sf > 1 ? (size_t)Sf * Q * k : 0);
-    float *qnorm = nullptr, *sl_s = nullptr, *uq = nullptr, *uqn = nullptr, *fb_s = nullptr, *part_s = nullptr;
-    int64_t *sl_i = nullptr, *fb_i = nullptr, *part_i = nullptr;
-    int32_t *fb_u = nullptr, *part_u = nullptr;
+    float *qnorm = nullptr, *uq = nullptr, *uqn = nullptr;
+    TopLists sl, fb, part;
     int *ulist = nullptr, *ucount = nullptr;
     RC(carve(h, h->search, "search", [&](Arena& a) {
         qnorm = a.take(Q);
-        sl_s = a.take((size_t)Q * kp); sl_i = a.take<int64_t>((size_t)Q * kp);
+        sl.s = a.take((size_t)Q * kp); sl.i = a.take<int64_t>((size_t)Q * kp);
         ulist = a.take<int>(Q); ucount = a.take<int>(1);
         uq = a.take((size_t)Q * dim); uqn = a.take(Q);
-        fb_s = a.take((size_t)Q * k); fb_i = a.take<int64_t>((size_t)Q * k);
-        if (part_n) { part_s = a.take(part_n); part_i = a.take<int64_t>(part_n); }
+        fb.s = a.take((size_t)Q * k); fb.i = a.take<int64_t>((size_t)Q * k);
+        if (part_n) { part.s = a.take(part_n); part.i = a.take<int64_t>(part_n); }
         if (subject) {
-            fb_u = a.take<int32_t>((size_t)Q * k);
-            if (Sf > 1) part_u = a.take<int32_t>((size_t)Sf * Q * k);
+            fb.u = a.take<int32_t>((size_t)Q * k);
+            if (Sf > 1) part.u = a.take<int32_t>((size_t)Sf * Q * k);
         }
     }));
     Scope s(h, st, FFR_KC_SCORE, 2.0 * Q * (double)G * dim,
             2.0 * (double)G * (dim + 2) + 4.0 * Q * dim + 12.0 * Q * (k + kp) + (subject ? 4.0 * (double)G + 4.0 * Q * k : 0.0));
     HIPCK(h, launch_row_norms(query, Q, qnorm, st));
     HIPCK(h, hipMemsetAsync(ucount, 0, sizeof(int), st));
-    HIPCK(h, launch_search_coarse(query, qnorm, Q, gallery_plane, gallery_norms, G, kp, T, S, chunk_rows, S > 1 ? part_s : sl_s,
-                                  S > 1 ? part_i : sl_i, st, subject));
-    if (S > 1) HIPCK(h, launch_topk_merge(part_s, part_i, S, Q, kp, sl_s, sl_i, st));
-    HIPCK(h, launch_search_rescore(query, qnorm, Q, gallery, gallery_norms, sl_s, sl_i, plane_flag, G, k, kp, index_base, top_score,
-                                   top_index, certified, ulist, ucount, st, subject, distinct, top_subject));
+    // the coarse pass: shortlists by coarse score, index = gallery row (no base), every probe, without a subject plane
+    const TopLists& cl = S > 1 ? part : sl;
+    const SearchArgs ca{query, qnorm, nullptr, gallery_plane, gallery_norms, G, chunk_rows, 0, cl.s, cl.i, nullptr, Q, kp, S, T,
+                        subject, nullptr};
+    HIPCK(h, launch_search(ca, subject ? SEARCH_COARSE_LIVE : SEARCH_COARSE, st));
+    if (S > 1) HIPCK(h, launch_topk_merge(part.s, part.i, nullptr, S, Q, kp, 0, sl.s, sl.i, nullptr, st));
+    HIPCK(h, launch_search_rescore(query, qnorm, Q, gallery, gallery_norms, sl.s, sl.i, plane_flag, G, k, kp, index_base, top.s, top.i,
+                                   certified, ulist, ucount, st, subject, distinct, top.u));
     // the exact search of the probes that were not certified, sized for Q: tiles past the device count leave at once
     HIPCK(h, launch_probe_gather(query, qnorm, ulist, ucount, Q, uq, uqn, st));
-    if (subject) {
-        HIPCK(h, launch_search_subjects(uq, uqn, Q, gallery, gallery_norms, subject, G, k, index_base, distinct, Tf, Sf, chunk_f,
-                                        Sf > 1 ? part_s : fb_s, Sf > 1 ? part_i : fb_i, Sf > 1 ? part_u : fb_u, st, ucount));
-        if (Sf > 1) HIPCK(h, launch_topk_merge_subjects(part_s, part_i, part_u, Sf, Q, k, distinct, fb_s, fb_i, fb_u, st, ucount));
-    } else {
-        HIPCK(h, launch_search_topk(uq, uqn, Q, gallery, gallery_norms, G, k, index_base, Tf, Sf, chunk_f, Sf > 1 ? part_s : fb_s,
-                                    Sf > 1 ? part_i : fb_i, st, ucount));
-        if (Sf > 1) HIPCK(h, launch_topk_merge(part_s, part_i, Sf, Q, k, fb_s, fb_i, st, ucount));
-    }
-    HIPCK(h, launch_topk_scatter(fb_s, fb_i, ulist, ucount, Q, k, top_score, top_index, st, fb_u, top_subject));
+    RC(exact_pass(h, uq, uqn, Q, gallery, gallery_norms, subject, G, k, index_base, distinct, Tf, Sf, chunk_f, fb, part, ucount, st));
+    HIPCK(h, launch_topk_scatter(fb.s, fb.i, ulist, ucount, Q, k, top.s, top.i, st, fb.u, top.u));
     return FFR_OK;
 }
 
 int ffr_search_topk_coarse(ffr_handle* h, const float* query, int Q, const float* gallery, const float* gallery_norms,
                            const uint16_t* gallery_plane, const int* plane_flag, long long G, int dim, int k, long long index_base,
                            float* top_score, int64_t* top_index, int* certified, void* stream) {
-    FFR_DEVICE_SCOPE(h); RC(check_fwd(h, false, false, 1));
-    RC(check_dim(h, "ffr_search_topk_coarse", dim));
-    if (!query || !top_score || !top_index || Q < 1 || k < 1 || k > 128 || G < 0 ||
-        (G > 0 && (!gallery || !gallery_norms || !gallery_plane || !plane_flag)))
-        return fail(h, FFR_ERR_ARG, "ffr_search_topk_coarse: bad arguments (Q >= 1, 1 <= k <= 128, G >= 0, non-null pointers)");
-    if (misaligned16(query) || (G > 0 && (misaligned16(gallery) || misaligned16(gallery_plane))))
-        return fail(h, FFR_ERR_ARG, "ffr_search_topk_coarse: query, gallery and plane rows must be 16-byte aligned");
-    if (G == 0 || k > coarse_max_k()) {          // nothing to shortlist, or a k the pass does not serve: the exact search alone
-        if (certified) HIPCK(h, hipMemsetAsync(certified, 0, sizeof(int) * (size_t)Q, (hipStream_t)stream));
-        return ffr_search_topk(h, query, Q, gallery, gallery_norms, G, dim, k, index_base, top_score, top_index, stream);
-    }
-    return coarse_search(h, query, Q, gallery, gallery_norms, gallery_plane, plane_flag, nullptr, G, dim, k, index_base, 0, top_score,
-                         top_index, nullptr, certified, (hipStream_t)stream);
+    FFR_DEVICE_SCOPE(h);
+    const TopLists top{top_score, top_index, nullptr};
+    RC(search_pre(h, "ffr_search_topk_coarse", true, query, Q, gallery, gallery_norms, gallery_plane, plane_flag, nullptr, G, dim, k, 0,
+                  top, false));
+    return coarse_search(h, query, Q, gallery, gallery_norms, gallery_plane, plane_flag, nullptr, G, dim, k, index_base, 0, top,
+                         certified, (hipStream_t)stream);
 }
 
 int ffr_search_topk_coarse_subjects(ffr_handle* h, const float* query, int Q, const float* gallery, const float* gallery_norms,
                                     const uint16_t* gallery_plane, const int* plane_flag, const int32_t* gallery_subject, long long G,
                                     int dim, int k, long long index_base, int distinct, float* top_score, int64_t* top_index,
                                     int32_t* top_subject, int* certified, void* stream) {
-    FFR_DEVICE_SCOPE(h); RC(check_fwd(h, false, false, 1));
-    RC(check_dim(h, "ffr_search_topk_coarse_subjects", dim));
-    if (!query || !top_score || !top_index || !top_subject || Q < 1 || k < 1 || k > 128 || G < 0 ||
-        (G > 0 && (!gallery || !gallery_norms || !gallery_plane || !plane_flag || !gallery_subject)))
-        return fail(h, FFR_ERR_ARG, "ffr_search_topk_coarse_subjects: bad arguments (Q >= 1, 1 <= k <= 128, G >= 0, non-null pointers)");
-    if (distinct != 0 && distinct != 1)
-        return fail(h, FFR_ERR_ARG, "ffr_search_topk_coarse_subjects: distinct must be 0 or 1, got %d", distinct);
-    if (distinct && k > search_max_k_distinct())
-        return fail(h, FFR_ERR_ARG, "ffr_search_topk_coarse_subjects: identity mode serves k <= %d, got %d", search_max_k_distinct(), k);
-    if (misaligned16(query) || (G > 0 && (misaligned16(gallery) || misaligned16(gallery_plane))))
-        return fail(h, FFR_ERR_ARG, "ffr_search_topk_coarse_subjects: query, gallery and plane rows must be 16-byte aligned");
-    if (G > 0 && misaligned4(gallery_subject))
-        return fail(h, FFR_ERR_ARG, "ffr_search_topk_coarse_subjects: gallery_subject must be 4-byte aligned");
-    if (G == 0 || k > coarse_max_k(distinct)) {  // as above; the pass lists identities for k <= 32
-        if (certified) HIPCK(h, hipMemsetAsync(certified, 0, sizeof(int) * (size_t)Q, (hipStream_t)stream));
-        return ffr_search_topk_subjects(h, query, Q, gallery, gallery_norms, gallery_subject, G, dim, k, index_base, distinct, top_score,
-                                        top_index, top_subject, stream);
-    }
+    FFR_DEVICE_SCOPE(h);
+    const TopLists top{top_score, top_index, top_subject};
+    RC(search_pre(h, "ffr_search_topk_coarse_subjects", true, query, Q, gallery, gallery_norms, gallery_plane, plane_flag,
+                  gallery_subject, G, dim, k, distinct, top, true));
     return coarse_search(h, query, Q, gallery, gallery_norms, gallery_plane, plane_flag, gallery_subject, G, dim, k, index_base, distinct,
-                         top_score, top_index, top_subject, certified, (hipStream_t)stream);
+                         top, certified, (hipStream_t)stream);
 }
 
 // ---- clustering (cluster.hip) ----------------------------------------------------------------------------------------

@@ -235,24 +235,38 @@ hipError_t launch_row_norms(const float* x, long long n, float* norms, hipStream
 // chunking of a search: probe tiles x gallery chunks (chunk_rows <= search_max_chunk_rows()); G >= 1
 long long search_max_chunk_rows();
 void search_plan(int Q, long long G, int num_cus, int* ntiles, int* nchunks, long long* chunk_rows);
-// top-k lists [nchunks][Q][k] of every gallery chunk (one launch); k <= 128, dim 512, rows 16-byte aligned.  live (device, or
-// null): only the probes [0, *live) are searched, the lists of the others are left as they are
-hipError_t launch_search_topk(const float* query, const float* qnorm, int Q, const float* gallery, const float* gnorm,
-                              long long G, int k, long long index_base, int ntiles, int nchunks, long long chunk_rows,
-                              float* out_s, int64_t* out_i, hipStream_t stream, const int* live = nullptr);
-// S sorted lists [S][Q][k] -> [Q][k] (descending score, ties by ascending index; index < 0 = padding); S <= 4096; live as above
-hipError_t launch_topk_merge(const float* score, const int64_t* index, int S, int Q, int k, float* out_s, int64_t* out_i,
-                             hipStream_t stream, const int* live = nullptr);
-// the same with subject[G] (< 0 = a removed row, never listed) and a third plane out_u of subjects; distinct: the lists hold
-// subjects, each by its best row, k <= search_max_k_distinct(); live as above
+// The arguments of one search block (search_core.h, which describes it).  The exact tile reads `gallery`, the coarse tile
+// `plane`; rows 16-byte aligned, dim 512.  The lists of the probes that `live` leaves out are left as they are
+struct SearchArgs {
+    const float* query;       // [Q][512]
+    const float* qnorm;       // [Q]
+    const float* gallery;     // [G][512] (the exact tile)
+    const uint16_t* plane;    // [G][512] bf16 of the normalised rows (the coarse tile)
+    const float* gnorm;       // [G]
+    long long G;
+    long long chunk_rows;     // rows per chunk (the last one may be shorter), <= CT_MAX_CHUNK
+    long long index_base;
+    float* out_s;             // [S][Q][k]
+    int64_t* out_i;
+    const int* live;          // device, or null: the probes [*live, Q) are not searched (their tiles leave at once)
+    int Q, k, nchunks, ntiles;
+    const int32_t* subject;   // [G], < 0 = a removed row (SR_LIVE, SR_DISTINCT)
+    int32_t* out_u;           // [S][Q][k] (SR_LIVE, SR_DISTINCT; not touched, may be null, where OUT_U is false)
+};
+// The instantiations search_block<COARSE, SUBJ, OUT_U> has, by kernel: the exact tile with the policy SR_ROWS (k_search_topk),
+// SR_LIVE and SR_DISTINCT (k_search_subjects: subject[G], < 0 = a removed row, never listed, and a third plane out_u of
+// subjects; SR_DISTINCT lists subjects, each by its best row, k <= search_max_k_distinct()); the coarse tile with SR_ROWS
+// (k_search_coarse) and, under the removal mask, SR_LIVE without the subject plane (k_search_coarse_live)
+enum SearchKernel { SEARCH_ROWS, SEARCH_LIVE, SEARCH_DISTINCT, SEARCH_COARSE, SEARCH_COARSE_LIVE };
 int search_max_k_distinct();
-hipError_t launch_search_subjects(const float* query, const float* qnorm, int Q, const float* gallery, const float* gnorm,
-                                  const int32_t* subject, long long G, int k, long long index_base, int distinct, int ntiles,
-                                  int nchunks, long long chunk_rows, float* out_s, int64_t* out_i, int32_t* out_u,
-                                  hipStream_t stream, const int* live = nullptr);
-hipError_t launch_topk_merge_subjects(const float* score, const int64_t* index, const int32_t* subject, int S, int Q, int k,
-                                      int distinct, float* out_s, int64_t* out_i, int32_t* out_u, hipStream_t stream,
-                                      const int* live = nullptr);
+// top-k lists [nchunks][Q][k] of every gallery chunk (one launch of nchunks x ntiles blocks); k <= 128.  The coarse kernels
+// list by coarse score, index = gallery row: index_base 0, no live count, k = the shortlist's length
+hipError_t launch_search(const SearchArgs& a, SearchKernel kernel, hipStream_t stream);
+// S sorted lists [S][Q][k] -> [Q][k] (descending score, ties by ascending index; index < 0 = padding); S <= 4096; live as
+// above.  out_u (or null: subject and distinct are not read): the lists carry a third plane of subjects; distinct: a winner
+// whose subject is out already is dropped, k <= search_max_k_distinct().  S = 0: k slots of padding per probe
+hipError_t launch_topk_merge(const float* score, const int64_t* index, const int32_t* subject, int S, int Q, int k, int distinct,
+                             float* out_s, int64_t* out_i, int32_t* out_u, hipStream_t stream, const int* live = nullptr);
 
 // ---- certified bf16 shortlist search (search_coarse.hip) ------------------------------
 // rows the coarse pass lists per probe for a top-k (k <= coarse_max_k()), and the largest k it serves; distinct: for a list
@@ -264,11 +278,9 @@ int coarse_max_k(int distinct = 0);
 void coarse_fallback_plan(int Q, long long G, int num_cus, int* ntiles, int* nchunks, long long* chunk_rows);
 // plane[r] = bf16(rows[r] / norms[r]) of [n][512] rows; *flag |= 1 when a norm is unsafe (not zero and outside [2^-60, 2^60])
 hipError_t launch_coarse_pack(const float* rows, const float* norms, long long n, uint16_t* plane, int* flag, hipStream_t stream);
-// shortlists [nchunks][Q][kp] of every plane chunk by coarse score, index = gallery row (one launch); merged by launch_topk_merge.
-// subject[G] (or null): the rows with subject < 0 are removed and never listed
-hipError_t launch_search_coarse(const float* query, const float* qnorm, int Q, const uint16_t* plane, const float* gnorm,
-                                long long G, int kp, int ntiles, int nchunks, long long chunk_rows, float* out_s, int64_t* out_i,
-                                hipStream_t stream, const int32_t* subject = nullptr);
+// k_search_coarse (live: k_search_coarse_live), for the table of launch_search: shortlists [nchunks][Q][kp] of every plane
+// chunk, merged by launch_topk_merge
+const void* search_coarse_kernel(bool live);
 // exact scores of the shortlists sl[Q][kp], the certificate, the certified probes' top-k -> top[Q][k]; the others' ids ->
 // ulist[0 .. *ucount) (ucount zero before the launch); certified[Q] (0 / 1) may be null.  subject[G] (or null): shortlists of
 // live rows; top_u[Q][k] gets the subjects, and with distinct the lists hold subjects, each by its best row

@@ -171,59 +171,31 @@ void search_plan(int Q, long long G, int num_cus, int* ntiles, int* nchunks, lon
     cosine_chunks(*ntiles, G, 1, num_cus, nchunks, chunk_rows);      // chunks x tiles fill the CUs, also at Q = 1
 }
 
-hipError_t launch_search_topk(const float* query, const float* qnorm, int Q, const float* gallery, const float* gnorm,
-                              long long G, int k, long long index_base, int ntiles, int nchunks, long long chunk_rows,
-                              float* out_s, int64_t* out_i, hipStream_t stream, const int* live) {
-    SearchArgs a{query, qnorm, gallery, nullptr, gnorm, G, chunk_rows, index_base, out_s, out_i, live, Q, k, nchunks, ntiles};
-    const size_t lds = sr_lds_bytes(k);
-    hipError_t e = hipFuncSetAttribute((const void*)k_search_topk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+// One launch for every instantiation of the search block, in the order of SearchKernel; the LDS follows (k, distinct)
+hipError_t launch_search(const SearchArgs& a, SearchKernel kernel, hipStream_t stream) {
+    const void* const fn[] = {(const void*)k_search_topk, (const void*)k_search_subjects<SR_LIVE>,
+                              (const void*)k_search_subjects<SR_DISTINCT>, search_coarse_kernel(false), search_coarse_kernel(true)};
+    const size_t lds = sr_lds_bytes(a.k, kernel == SEARCH_DISTINCT);
+    hipError_t e = hipFuncSetAttribute(fn[kernel], hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_search_topk, dim3((unsigned)(nchunks * ntiles)), dim3(256), lds, stream, a);
-    return hipGetLastError();
+    void* args[] = {const_cast<SearchArgs*>(&a)};
+    return hipLaunchKernel(fn[kernel], dim3((unsigned)(a.nchunks * a.ntiles)), dim3(256), args, lds, stream);
 }
 
-hipError_t launch_search_subjects(const float* query, const float* qnorm, int Q, const float* gallery, const float* gnorm,
-                                  const int32_t* subject, long long G, int k, long long index_base, int distinct, int ntiles,
-                                  int nchunks, long long chunk_rows, float* out_s, int64_t* out_i, int32_t* out_u,
-                                  hipStream_t stream, const int* live) {
-    SearchArgs a{query, qnorm, gallery, nullptr, gnorm, G, chunk_rows, index_base, out_s, out_i, live, Q, k, nchunks, ntiles,
-                 subject, out_u};
-    const size_t lds = sr_lds_bytes(k, distinct != 0);
-    const void* fn = distinct ? (const void*)k_search_subjects<SR_DISTINCT> : (const void*)k_search_subjects<SR_LIVE>;
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    if (distinct) hipLaunchKernelGGL(k_search_subjects<SR_DISTINCT>, dim3((unsigned)(nchunks * ntiles)), dim3(256), lds, stream, a);
-    else hipLaunchKernelGGL(k_search_subjects<SR_LIVE>, dim3((unsigned)(nchunks * ntiles)), dim3(256), lds, stream, a);
-    return hipGetLastError();
-}
-
-// LDS of a merge: head positions [S], then the staged entries (`entry` bytes each) when they fit under MG_LDS_CAP
-static size_t merge_lds(int S, int k, int entry, int* staged) {
+// LDS of a merge: head positions [S], then the staged entries (12 bytes each, 16 with a subject) when they fit under MG_LDS_CAP
+hipError_t launch_topk_merge(const float* score, const int64_t* index, const int32_t* subject, int S, int Q, int k, int distinct,
+                             float* out_s, int64_t* out_i, int32_t* out_u, hipStream_t stream, const int* live) {
     const size_t head = ((size_t)S * 4 + 15) & ~(size_t)15;
-    const size_t full = head + (size_t)S * k * entry;
-    *staged = S > 0 && full <= (size_t)MG_LDS_CAP;
-    return *staged ? full : head;
-}
-
-hipError_t launch_topk_merge(const float* score, const int64_t* index, int S, int Q, int k, float* out_s, int64_t* out_i,
-                             hipStream_t stream, const int* live) {
-    int staged = 0;
-    const size_t lds = merge_lds(S, k, 12, &staged);
-    hipError_t e = hipFuncSetAttribute((const void*)k_topk_merge, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MG_LDS_CAP);
+    const size_t full = head + (size_t)S * k * (out_u ? 16 : 12);
+    const int staged = S > 0 && full <= (size_t)MG_LDS_CAP;
+    const size_t lds = staged ? full : head;
+    const void* fn = out_u ? (const void*)k_topk_merge_subjects : (const void*)k_topk_merge;
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MG_LDS_CAP);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_topk_merge, dim3((unsigned)Q), dim3(64), lds, stream, score, index, S, Q, k, staged, out_s, out_i, live);
-    return hipGetLastError();
-}
-
-hipError_t launch_topk_merge_subjects(const float* score, const int64_t* index, const int32_t* subject, int S, int Q, int k,
-                                      int distinct, float* out_s, int64_t* out_i, int32_t* out_u, hipStream_t stream,
-                                      const int* live) {
-    int staged = 0;
-    const size_t lds = merge_lds(S, k, 16, &staged);
-    hipError_t e = hipFuncSetAttribute((const void*)k_topk_merge_subjects, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MG_LDS_CAP);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_topk_merge_subjects, dim3((unsigned)Q), dim3(64), lds, stream, score, index, subject, S, Q, k, staged,
-                       distinct, out_s, out_i, out_u, live);
+    if (out_u)          // the two kernels differ in their arguments, not in their grid
+        hipLaunchKernelGGL(k_topk_merge_subjects, dim3((unsigned)Q), dim3(64), lds, stream, score, index, subject, S, Q, k, staged,
+                           distinct, out_s, out_i, out_u, live);
+    else hipLaunchKernelGGL(k_topk_merge, dim3((unsigned)Q), dim3(64), lds, stream, score, index, S, Q, k, staged, out_s, out_i, live);
     return hipGetLastError();
 }
 

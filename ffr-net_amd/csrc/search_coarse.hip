@@ -272,19 +272,7 @@ hipError_t launch_coarse_pack(const float* rows, const float* norms, long long n
     return hipGetLastError();
 }
 
-hipError_t launch_search_coarse(const float* query, const float* qnorm, int Q, const uint16_t* plane, const float* gnorm,
-                                long long G, int kp, int ntiles, int nchunks, long long chunk_rows, float* out_s, int64_t* out_i,
-                                hipStream_t stream, const int32_t* subject) {
-    SearchArgs a{query, qnorm, nullptr, plane, gnorm, G, chunk_rows, 0, out_s, out_i, nullptr, Q, kp, nchunks, ntiles,
-                 subject, nullptr};
-    const size_t lds = sr_lds_bytes(kp);
-    const void* fn = subject ? (const void*)k_search_coarse_live : (const void*)k_search_coarse;
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    if (subject) hipLaunchKernelGGL(k_search_coarse_live, dim3((unsigned)(nchunks * ntiles)), dim3(256), lds, stream, a);
-    else hipLaunchKernelGGL(k_search_coarse, dim3((unsigned)(nchunks * ntiles)), dim3(256), lds, stream, a);
-    return hipGetLastError();
-}
+const void* search_coarse_kernel(bool live) { return live ? (const void*)k_search_coarse_live : (const void*)k_search_coarse; }
 
 hipError_t launch_search_rescore(const float* query, const float* qnorm, int Q, const float* gallery, const float* gnorm,
                                  const float* sl_s, const int64_t* sl_i, const int* plane_flag, long long G, int k, int kp,
@@ -296,9 +284,8 @@ hipError_t launch_search_rescore(const float* query, const float* qnorm, int Q, 
     const void* fn = subject ? (const void*)k_search_rescore<true> : (const void*)k_search_rescore<false>;
     hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    if (subject) hipLaunchKernelGGL(k_search_rescore<true>, dim3((unsigned)Q), dim3(256), lds, stream, a);
-    else hipLaunchKernelGGL(k_search_rescore<false>, dim3((unsigned)Q), dim3(256), lds, stream, a);
-    return hipGetLastError();
+    void* args[] = {&a};
+    return hipLaunchKernel(fn, dim3((unsigned)Q), dim3(256), args, lds, stream);
 }
 
 hipError_t launch_probe_gather(const float* query, const float* qnorm, const int* ulist, const int* ucount, int Q, float* uq,

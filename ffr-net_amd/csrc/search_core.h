@@ -35,6 +35,7 @@
 #include "coarse_tile.h"
 #include "cosine_tile.h"
 #include "device_util.h"
+#include "ffr_kernels.h"
 
 namespace ffr {
 
@@ -45,22 +46,7 @@ constexpr int SR_NO_VICTIM = 255;         // SR_DISTINCT: a candidate that repla
 
 enum { SR_ROWS = 0, SR_LIVE = 1, SR_DISTINCT = 2 };     // the subject policy of a search block
 
-struct SearchArgs {
-    const float* query;       // [Q][512]
-    const float* qnorm;       // [Q]
-    const float* gallery;     // [G][512] (the exact tile)
-    const uint16_t* plane;    // [G][512] bf16 of the normalised rows (the coarse tile)
-    const float* gnorm;       // [G]
-    long long G;
-    long long chunk_rows;     // rows per chunk (the last one may be shorter), <= CT_MAX_CHUNK
-    long long index_base;
-    float* out_s;             // [S][Q][k]
-    int64_t* out_i;
-    const int* live;          // device, or null: the probes [*live, Q) are not searched (their tiles leave at once)
-    int Q, k, nchunks, ntiles;
-    const int32_t* subject;   // [G], < 0 = a removed row (SR_LIVE, SR_DISTINCT)
-    int32_t* out_u;           // [S][Q][k] (SR_LIVE, SR_DISTINCT; not touched, may be null, where OUT_U is false)
-};
+// SearchArgs: ffr_kernels.h, where the host units fill it
 
 // The tile a search block scores with: the exact fp32 one of cosine_tile.h, or the bf16 one of coarse_tile.h
 template <bool COARSE> struct SearchTile;

@@ -490,16 +490,39 @@ class Engine(object):
             gallery_norms = gallery_norms.contiguous()
         return query, gallery, gallery_norms, G
 
+    def _search(self, who, query, gallery, k, gallery_norms, index_base, coarse=None, subj=None):
+        """The body of the four searches.  coarse: (plane, flag) of search_coarse(); subj: (subjects, distinct) of
+        search_subjects() -> [scores, index(, subjects)(, certified)].  The arguments go in the order of include/ffrnet.h; the
+        tensors stay referenced until the call is made."""
+        query, gallery, gallery_norms, G = self._search_inputs(query, gallery, gallery_norms, who)
+        Q, k = query.size(0), int(k)
+
+        def rows(t):                             # the gallery side: null pointers at G = 0
+            return t if G else None
+        name = 'ffr_search_topk'
+        head, tail = [query, Q, rows(gallery), gallery_norms], [G, query.size(1), k, int(index_base)]
+        out = [self._empty(Q, max(k, 0)), self._empty(Q, max(k, 0), dtype=torch.int64)]
+        if coarse is not None:
+            plane, flag = coarse
+            self._tensor(plane, 'plane', torch.int16, shape=(G, gallery.size(1)))
+            self._tensor(flag, 'flag', torch.int32, shape=(1,))
+            head += [rows(plane.contiguous()), flag]
+            name += '_coarse'
+        if subj is not None:
+            head.append(rows(self._subjects(subj[0], 'subjects', (G,))))
+            tail.append(int(bool(subj[1])))
+            out.append(self._empty(Q, max(k, 0), dtype=torch.int32))
+            name += '_subjects'
+        if coarse is not None:
+            out.append(self._empty(Q, dtype=torch.int32))
+        self._call(getattr(self.lib, name), *[a if isinstance(a, int) else _ptr(a) for a in head + tail + out])
+        return out
+
     def search(self, query, gallery, k, gallery_norms=None, index_base=0):
         """Exact cosine top-k: query[Q,512], gallery[G,512] (device fp32) -> (scores[Q,k] fp32, index[Q,k] int64), per
         probe by descending score, ties by ascending index; index = index_base + gallery row; (-inf, -1) pads G < k.
         gallery_norms[G]: row_norms(gallery), computed here when not given (pass them when the gallery is reused)."""
-        query, gallery, gallery_norms, G = self._search_inputs(query, gallery, gallery_norms, 'search')
-        Q, k = query.size(0), int(k)
-        scores, index = self._empty(Q, max(k, 0)), self._empty(Q, max(k, 0), dtype=torch.int64)
-        self._call(self.lib.ffr_search_topk, _ptr(query), Q, _ptr(gallery if G else None), _ptr(gallery_norms), G,
-                   query.size(1), k, int(index_base), _ptr(scores), _ptr(index))
-        return scores, index
+        return tuple(self._search('search', query, gallery, k, gallery_norms, index_base))
 
     def coarse_pack(self, rows, norms, plane_out, flag):
         """plane_out[n,512] (int16: bf16 bits) = bf16(rows[r] / norms[r]) of rows[n,512]; flag (int32 [1], zero when its
@@ -520,31 +543,33 @@ class Engine(object):
         (scores[Q,k], index[Q,k]) bit for bit.  plane[G,512] int16 and flag int32 [1] come from coarse_pack over the same
         rows and norms.  return_certified: also certified[Q] int32, 1 where the shortlist was proven to hold the top-k,
         0 where the probe went through the exact search."""
-        query, gallery, gallery_norms, G = self._search_inputs(query, gallery, gallery_norms, 'search_coarse')
-        self._tensor(plane, 'plane', torch.int16, shape=(G, gallery.size(1)))
-        self._tensor(flag, 'flag', torch.int32, shape=(1,))
-        plane = plane.contiguous()
-        Q, k = query.size(0), int(k)
-        scores, index = self._empty(Q, max(k, 0)), self._empty(Q, max(k, 0), dtype=torch.int64)
-        cert = self._empty(Q, dtype=torch.int32)
-        self._call(self.lib.ffr_search_topk_coarse, _ptr(query), Q, _ptr(gallery if G else None), _ptr(gallery_norms),
-                   _ptr(plane if G else None), _ptr(flag), G, query.size(1), k, int(index_base), _ptr(scores), _ptr(index),
-                   _ptr(cert))
-        return (scores, index, cert) if return_certified else (scores, index)
+        out = self._search('search_coarse', query, gallery, k, gallery_norms, index_base, coarse=(plane, flag))
+        return tuple(out if return_certified else out[:-1])
+
+    def _topk_merge(self, who, scores, index, subj=None):
+        """The body of the two merges.  subj: (subjects, distinct) of topk_merge_subjects() -> [scores, index(, subjects)]"""
+        self._tensor(scores, 'scores')
+        self._tensor(index, 'index', torch.int64)
+        if scores.dim() != 3 or tuple(index.shape) != tuple(scores.shape):
+            raise RuntimeError('ffrnet_amd: %s expects %s [S,Q,k], got %s and %s'
+                               % (who, 'scores and index' if subj is None else 'scores, index and subjects',
+                                  list(scores.shape), list(index.shape)))
+        S, Q, k = scores.shape
+        name = 'ffr_topk_merge'
+        lists, dims = [scores.contiguous(), index.contiguous()], [S, Q, k]
+        out = [self._empty(Q, k), self._empty(Q, k, dtype=torch.int64)]
+        if subj is not None:
+            lists.append(self._subjects(subj[0], 'subjects', (S, Q, k)))
+            dims.append(int(bool(subj[1])))
+            out.append(self._empty(Q, k, dtype=torch.int32))
+            name += '_subjects'
+        self._call(getattr(self.lib, name), *[_ptr(t) for t in lists], *dims, *[_ptr(t) for t in out])
+        return out
 
     def topk_merge(self, scores, index):
         """Merge S sorted lists per probe, scores[S,Q,k] fp32 and index[S,Q,k] int64 (device; index < 0 = padding), in
         the order of search() -> (scores[Q,k], index[Q,k])."""
-        self._tensor(scores, 'scores')
-        self._tensor(index, 'index', torch.int64)
-        if scores.dim() != 3 or tuple(index.shape) != tuple(scores.shape):
-            raise RuntimeError('ffrnet_amd: topk_merge expects scores and index [S,Q,k], got %s and %s'
-                               % (list(scores.shape), list(index.shape)))
-        S, Q, k = scores.shape
-        scores, index = scores.contiguous(), index.contiguous()
-        out_s, out_i = self._empty(Q, k), self._empty(Q, k, dtype=torch.int64)
-        self._call(self.lib.ffr_topk_merge, _ptr(scores), _ptr(index), S, Q, k, _ptr(out_s), _ptr(out_i))
-        return out_s, out_i
+        return tuple(self._topk_merge('topk_merge', scores, index))
 
     # -- subject-labelled search (include/ffrnet.h: ffr_search_topk_subjects, ffr_topk_merge_subjects) -----------------
     def _subjects(self, t, name, shape):
@@ -560,15 +585,7 @@ class Engine(object):
         < 0 = a removed row, which is never returned.  distinct=True (k <= 64): the top-k SUBJECTS, each once, by its best
         row (maximum score, then smallest index); distinct=False (k <= 128): the top-k live rows
         -> (scores[Q,k] fp32, index[Q,k] int64, subjects[Q,k] int32); (-inf, -1, -1) pads."""
-        query, gallery, gallery_norms, G = self._search_inputs(query, gallery, gallery_norms, 'search_subjects')
-        subjects = self._subjects(subjects, 'subjects', (G,))
-        Q, k = query.size(0), int(k)
-        scores, index = self._empty(Q, max(k, 0)), self._empty(Q, max(k, 0), dtype=torch.int64)
-        subj = self._empty(Q, max(k, 0), dtype=torch.int32)
-        self._call(self.lib.ffr_search_topk_subjects, _ptr(query), Q, _ptr(gallery if G else None), _ptr(gallery_norms),
-                   _ptr(subjects if G else None), G, query.size(1), k, int(index_base), int(bool(distinct)), _ptr(scores),
-                   _ptr(index), _ptr(subj))
-        return scores, index, subj
+        return tuple(self._search('search_subjects', query, gallery, k, gallery_norms, index_base, subj=(subjects, distinct)))
 
     def search_coarse_subjects(self, query, gallery, plane, flag, subjects, k, gallery_norms=None, index_base=0, distinct=True,
                                return_certified=False):
@@ -576,35 +593,14 @@ class Engine(object):
         same (scores[Q,k], index[Q,k], subjects[Q,k]) bit for bit, in both modes and under every removal pattern.  plane and
         flag as search_coarse() takes them, subjects[G] as search_subjects() does.  The pass serves k <= 32 identities
         (distinct=True) and k <= 64 rows; above, the exact search runs alone.  return_certified: also certified[Q] int32."""
-        query, gallery, gallery_norms, G = self._search_inputs(query, gallery, gallery_norms, 'search_coarse_subjects')
-        self._tensor(plane, 'plane', torch.int16, shape=(G, gallery.size(1)))
-        self._tensor(flag, 'flag', torch.int32, shape=(1,))
-        plane = plane.contiguous()
-        subjects = self._subjects(subjects, 'subjects', (G,))
-        Q, k = query.size(0), int(k)
-        scores, index = self._empty(Q, max(k, 0)), self._empty(Q, max(k, 0), dtype=torch.int64)
-        subj = self._empty(Q, max(k, 0), dtype=torch.int32)
-        cert = self._empty(Q, dtype=torch.int32)
-        self._call(self.lib.ffr_search_topk_coarse_subjects, _ptr(query), Q, _ptr(gallery if G else None), _ptr(gallery_norms),
-                   _ptr(plane if G else None), _ptr(flag), _ptr(subjects if G else None), G, query.size(1), k, int(index_base),
-                   int(bool(distinct)), _ptr(scores), _ptr(index), _ptr(subj), _ptr(cert))
-        return (scores, index, subj, cert) if return_certified else (scores, index, subj)
+        out = self._search('search_coarse_subjects', query, gallery, k, gallery_norms, index_base, coarse=(plane, flag),
+                           subj=(subjects, distinct))
+        return tuple(out if return_certified else out[:-1])
 
     def topk_merge_subjects(self, scores, index, subjects, distinct=True):
         """topk_merge() of lists that carry subjects: scores[S,Q,k] fp32, index[S,Q,k] int64, subjects[S,Q,k] int32 or
         int64; distinct=True keeps the first entry of every subject -> (scores[Q,k], index[Q,k], subjects[Q,k])."""
-        self._tensor(scores, 'scores')
-        self._tensor(index, 'index', torch.int64)
-        if scores.dim() != 3 or tuple(index.shape) != tuple(scores.shape):
-            raise RuntimeError('ffrnet_amd: topk_merge_subjects expects scores, index and subjects [S,Q,k], got %s and %s'
-                               % (list(scores.shape), list(index.shape)))
-        S, Q, k = scores.shape
-        subjects = self._subjects(subjects, 'subjects', (S, Q, k))
-        scores, index = scores.contiguous(), index.contiguous()
-        out_s, out_i, out_u = self._empty(Q, k), self._empty(Q, k, dtype=torch.int64), self._empty(Q, k, dtype=torch.int32)
-        self._call(self.lib.ffr_topk_merge_subjects, _ptr(scores), _ptr(index), _ptr(subjects), S, Q, k, int(bool(distinct)),
-                   _ptr(out_s), _ptr(out_i), _ptr(out_u))
-        return out_s, out_i, out_u
+        return tuple(self._topk_merge('topk_merge_subjects', scores, index, subj=(subjects, distinct)))
 
     # -- clustering (include/ffrnet.h: ffr_cluster_threshold, ffr_cluster_templates) -----------------------------------
     def _cluster_rows(self, emb, norms, who):

@@ -65,16 +65,24 @@ class Gallery(object):
                                'subjects yet at construction; create Gallery(subjects=True) and call build_plane()')
         self.engine = engine
         self._n = 0
-        self._emb = torch.empty((int(capacity), DIM), device=engine.device, dtype=torch.float32)
-        self._norms = torch.empty((int(capacity),), device=engine.device, dtype=torch.float32)
+        self._side = []                 # the attributes that hold a row per gallery row: they grow and compact together
+        self._add_side('_emb', torch.float32, capacity, DIM)
+        self._add_side('_norms', torch.float32, capacity)
         self.coarse = bool(coarse)
         self.last_certified = None
         self.has_subjects = bool(subjects)
         if self.has_subjects:
-            self._subj = torch.empty((int(capacity),), device=engine.device, dtype=torch.int32)
+            self._add_side('_subj', torch.int32, capacity)
         if self.coarse:
-            self._plane = torch.empty((int(capacity), DIM), device=engine.device, dtype=torch.int16)
-            self._flag = torch.zeros((1,), device=engine.device, dtype=torch.int32)
+            self._add_plane()
+
+    def _add_side(self, name, dtype, capacity, *tail):
+        setattr(self, name, torch.empty((int(capacity),) + tail, device=self.engine.device, dtype=dtype))
+        self._side.append(name)
+
+    def _add_plane(self):
+        self._add_side('_plane', torch.int16, self._emb.size(0), DIM)
+        self._flag = torch.zeros((1,), device=self.engine.device, dtype=torch.int32)
 
     def __len__(self):
         return self._n
@@ -135,20 +143,12 @@ class Gallery(object):
         first = self._n
         if first + n > self._emb.size(0):
             cap = max(first + n, 2 * self._emb.size(0), 1024)
-            emb_new = torch.empty((cap, DIM), device=self._emb.device, dtype=torch.float32)
-            norms_new = torch.empty((cap,), device=self._emb.device, dtype=torch.float32)
-            emb_new[:first] = self._emb[:first]
-            norms_new[:first] = self._norms[:first]
-            self._emb, self._norms = emb_new, norms_new
-            if self.coarse:
-                plane_new = torch.empty((cap, DIM), device=self._emb.device, dtype=torch.int16)
-                plane_new[:first] = self._plane[:first]
-                self._plane = plane_new
-            if self.has_subjects:
-                subj_new = torch.empty((cap,), device=self._emb.device, dtype=torch.int32)
-                subj_new[:first] = self._subj[:first]
-                self._subj = subj_new
-        if n:
+            for name in self._side:
+                old = getattr(self, name)
+                new = torch.empty((cap,) + old.shape[1:], device=old.device, dtype=old.dtype)
+                new[:first] = old[:first]
+                setattr(self, name, new)
+        if n:                           # every side buffer gets its rows from another source: named one by one
             self._emb[first:first + n] = emb
             self._norms[first:first + n] = self.engine.row_norms(self._emb[first:first + n])
             if self.coarse:
@@ -166,8 +166,7 @@ class Gallery(object):
         has a plane."""
         if self.coarse:
             return
-        self._plane = torch.empty((self._emb.size(0), DIM), device=self._emb.device, dtype=torch.int16)
-        self._flag = torch.zeros((1,), device=self._emb.device, dtype=torch.int32)
+        self._add_plane()
         if self._n:
             self.engine.coarse_pack(self.embeddings, self.norms, self._plane[:self._n], self._flag)
         self.coarse = True
@@ -216,11 +215,9 @@ class Gallery(object):
         new_index = torch.cumsum(keep.to(torch.int64), 0) - 1
         new_index[~keep] = -1
         n = int(keep.sum().item())
-        self._emb[:n] = self.embeddings[keep]
-        self._norms[:n] = self.norms[keep]
-        self._subj[:n] = self.subjects[keep]
-        if self.coarse:
-            self._plane[:n] = self.plane[keep]
+        for name in self._side:
+            buf = getattr(self, name)
+            buf[:n] = buf[:self._n][keep]
         self._n = n
         return new_index
 
@@ -255,46 +252,27 @@ def search_sharded(gallery_shard, query, k, group=None, distinct=None):
     gives them; the exchange carries the subject as a fourth word and the merge is ffr_topk_merge_subjects.  The default
     (None) and False give the row search of the shard: plain, or under the removal mask of a gallery with subjects."""
     eng = gallery_shard.engine
-    if distinct:
-        return _search_sharded_subjects(gallery_shard, query, k, group)
+    search = gallery_shard.search_subjects if distinct else gallery_shard.search
     if dist is None or not dist.is_available() or not dist.is_initialized() or dist.get_world_size(group) == 1:
-        return gallery_shard.search(query, k)
+        return search(query, k)
     world, rank = dist.get_world_size(group), dist.get_rank(group)
     sizes = torch.empty((world,), device=query.device, dtype=torch.int64)
     dist.all_gather_into_tensor(sizes, torch.tensor([len(gallery_shard)], device=query.device, dtype=torch.int64),
                                 group=group)
     base = int(sizes[:rank].sum().item())
-    s, i = gallery_shard.search(query, k, index_base=base)
+    lists = search(query, k, index_base=base)            # (s, i), with subjects (s, u, i)
+    s, i, w = lists[0], lists[-1], 1 + len(lists)
     Q, kk = s.shape
-    # one exchange: per slot the score's bits and the two halves of the index, as int32 words
-    mine = torch.cat((s.contiguous().view(torch.int32).view(Q, kk, 1), i.contiguous().view(torch.int32).view(Q, kk, 2)), 2)
-    allw = torch.empty((world * Q, kk, 3), device=query.device, dtype=torch.int32)      # rank-major along dim 0
+    # one exchange: per slot the score's bits, the two halves of the index and, with subjects, the subject: w int32 words
+    mine = torch.cat([s.contiguous().view(torch.int32).view(Q, kk, 1), i.contiguous().view(torch.int32).view(Q, kk, 2)] +
+                     [u.view(Q, kk, 1) for u in lists[1:-1]], 2)
+    allw = torch.empty((world * Q, kk, w), device=query.device, dtype=torch.int32)      # rank-major along dim 0
     dist.all_gather_into_tensor(allw, mine.contiguous(), group=group)
-    allw = allw.view(world, Q, kk, 3)
-    all_s = allw[..., 0].contiguous().view(torch.float32)
-    all_i = allw[..., 1:].contiguous().view(torch.int64).view(world, Q, kk)
-    return eng.topk_merge(all_s, all_i)
-
-
-def _search_sharded_subjects(gallery_shard, query, k, group):
-    eng = gallery_shard.engine
-    if dist is None or not dist.is_available() or not dist.is_initialized() or dist.get_world_size(group) == 1:
-        return gallery_shard.search_subjects(query, k)
-    world, rank = dist.get_world_size(group), dist.get_rank(group)
-    sizes = torch.empty((world,), device=query.device, dtype=torch.int64)
-    dist.all_gather_into_tensor(sizes, torch.tensor([len(gallery_shard)], device=query.device, dtype=torch.int64),
-                                group=group)
-    base = int(sizes[:rank].sum().item())
-    s, u, i = gallery_shard.search_subjects(query, k, index_base=base)
-    Q, kk = s.shape
-    # one exchange: per slot the score's bits, the two halves of the index and the subject, as int32 words
-    mine = torch.cat((s.contiguous().view(torch.int32).view(Q, kk, 1), i.contiguous().view(torch.int32).view(Q, kk, 2),
-                      u.view(Q, kk, 1)), 2)
-    allw = torch.empty((world * Q, kk, 4), device=query.device, dtype=torch.int32)      # rank-major along dim 0
-    dist.all_gather_into_tensor(allw, mine.contiguous(), group=group)
-    allw = allw.view(world, Q, kk, 4)
+    allw = allw.view(world, Q, kk, w)
     all_s = allw[..., 0].contiguous().view(torch.float32)
     all_i = allw[..., 1:3].contiguous().view(torch.int64).view(world, Q, kk)
+    if not distinct:
+        return eng.topk_merge(all_s, all_i)
     out_s, out_i, out_u = eng.topk_merge_subjects(all_s, all_i, allw[..., 3].contiguous(), distinct=True)
     return out_s, out_u, out_i
 
