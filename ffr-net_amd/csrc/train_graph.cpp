@@ -49,6 +49,8 @@ int ensure_scratch(ffr_handle* h, TrainState* t, int imgs_i) {
     hipDeviceSynchronize();
     if (t->scratch_mem) hipFree(t->scratch_mem);
     t->scratch_mem = nullptr;
+    t->loss_grads_slot = -1;      // what lived in the old scratch is gone: the loss gradients and the folded Conv4Channel products
+    t->fold_ready = false;
     const size_t imgs = imgs_i, rows = imgs * 49, crow = imgs * 512;
     // the ConvLayer buffers: the largest need of any of the 15 layers; the slice partials also serve launch_colsum (512 slices x 512 columns)
     LayerScratch cap;
@@ -132,6 +134,7 @@ int train_forward(ffr_handle* h, TrainState* t, Ctx& c, const Work& w, hipStream
         // Linear(32,512) -> Linear(512,32) pairs as their 32x32 product (exact algebra, as the inference kernel does)
         TLAUNCH(FFR_KC_TRAIN_XFORM, launch_ch_fold(ln[2].w, ln[2].b, ln[1].w, ln[1].b, t->foldA[0], t->foldd[0], st));
         TLAUNCH(FFR_KC_TRAIN_XFORM, launch_ch_fold(ln[4].w, ln[4].b, ln[3].w, ln[3].b, t->foldA[1], t->foldd[1], st));
+        t->fold_ready = true;
         RC(gemm_rows(h, w, c.h1, 64, 32, t->foldA[0], t->foldd[0], 64, c.h2pre, 64, crow, nullptr, 0, 0, st));
     } else {
         RC(gemm_rows(h, w, c.h1, 64, 32, ln[1].w, ln[1].b, 512, c.t2, 512, crow, nullptr, 0, 0, st));
@@ -174,6 +177,7 @@ struct OutGrads {
 };
 
 int train_backward(ffr_handle* h, TrainState* t, Ctx& c, const Work& w, const OutGrads& og, hipStream_t st) {
+    t->loss_grads_slot = -1;      // every backward spends or overwrites dcos / df_ext / extM
     const int G = c.G, N = c.N, imgs = G * N, rows = imgs * 49;
     const long long crow = (long long)imgs * 512;
     TScratch& s = t->sc;
@@ -230,6 +234,12 @@ int train_backward(ffr_handle* h, TrainState* t, Ctx& c, const Work& w, const Ou
         TLAUNCH(FFR_KC_TRAIN_XFORM, launch_ch_unfold(t->gfoldA, t->gfoldd, lb.w, la.w, la.b, lb.gw, lb.gb, la.gw, la.gb, st));
         return FFR_OK;
     };
+    if (c.folded && !t->fold_ready) {
+        // the scratch was reallocated since the folded forward (a larger forward in the other slot): the products again, from the live weights
+        TLAUNCH(FFR_KC_TRAIN_XFORM, launch_ch_fold(ln[2].w, ln[2].b, ln[1].w, ln[1].b, t->foldA[0], t->foldd[0], st));
+        TLAUNCH(FFR_KC_TRAIN_XFORM, launch_ch_fold(ln[4].w, ln[4].b, ln[3].w, ln[3].b, t->foldA[1], t->foldd[1], st));
+        t->fold_ready = true;
+    }
     if (c.folded) RC(pair_backward(1, ln[4], ln[3], t->d32a, c.h2, t->d32b));
     else {
         RC(lin_backward(h, t, w, ln[4], {t->d32a, 64}, {c.t5, 512}, crow, {t->dt, 512}, st));
@@ -264,6 +274,7 @@ int train_backward(ffr_handle* h, TrainState* t, Ctx& c, const Work& w, const Ou
 
 // ---- the four loss items (models/trainer.py:154-178) and their gradients wrt the outputs of `c` (G == 2) ----------
 int train_losses(ffr_handle* h, TrainState* t, Ctx& c, const Work& w, const float* f_enc, const double lw[4], hipStream_t st) {
+    t->loss_grads_slot = -1;      // overwritten from here on
     if (c.G != 2) return fail(h, FFR_ERR_ARG, "the loss items need the clean and the occluded half in one forward (G = 2)");
     const int N = c.N, imgs = 2 * N;
     LossCoef k;
@@ -288,7 +299,7 @@ int train_losses(ffr_handle* h, TrainState* t, Ctx& c, const Work& w, const floa
                             t->p_ce, t->hit, st));
     LossParts lp{t->p_sss, t->p_ssc, t->p_vec, t->p_ce, t->hit, n_ssc};
     TLAUNCH(FFR_KC_TRAIN_LOSS, launch_loss_finish(lp, N, k, t->loss_out, st));
-    t->loss_grads_ready = true;
+    t->loss_grads_slot = (int)(&c - t->ctx);
     return FFR_OK;
 }
 
@@ -297,7 +308,6 @@ int backward_of_losses(ffr_handle* h, Slot& s) {
     OutGrads og; og.in_scratch = true;
     RC(train_backward(h, s.t, *s.c, s.w, og, s.st));
     s.c->valid = false;
-    s.t->loss_grads_ready = false;
     return FFR_OK;
 }
 
@@ -324,6 +334,7 @@ int ffr_train_forward(ffr_handle* h, int slot, const float* featmap_nchw, const 
     RC(enter_slot(h, "ffr_train_forward", slot, featmap_nchw && G > 0 && N > 0 && (label || !(pred_loss || pred_label)), imgs, false, stream, &s));
     TrainState* t = s.t; Ctx& c = *s.c; hipStream_t st = s.st;
     RC(ensure_ctx(h, t, c, G, N));
+    if (t->loss_grads_slot == slot) t->loss_grads_slot = -1;      // they belonged to the forward this one replaces
     TLAUNCH(FFR_KC_TRAIN_ELEM, launch_nchw_to_nhwc(featmap_nchw, c.X, 512, imgs, 49, 512, st));
     if (label) HIPCK(h, hipMemcpyAsync(c.label, label, (size_t)imgs * 4, hipMemcpyDeviceToDevice, st));
     RC(train_forward(h, t, c, s.w, st));
@@ -362,7 +373,9 @@ int ffr_train_backward_losses(ffr_handle* h, int slot, void* stream) {
     FFR_DEVICE_SCOPE(h);
     Slot s;
     RC(enter_slot(h, "ffr_train_backward_losses", slot, true, 0, false, stream, &s));
-    if (!s.t->loss_grads_ready) return fail(h, FFR_ERR_STATE, "ffr_train_backward_losses: call ffr_train_forward and ffr_train_losses first");
+    if (s.t->loss_grads_slot != slot)
+        return fail(h, FFR_ERR_STATE, "ffr_train_backward_losses: slot %d holds no loss gradients (ffr_train_losses on this slot must be the last call "
+                                      "that used the backward scratch)", slot);
     return backward_of_losses(h, s);
 }
 

@@ -144,7 +144,10 @@ struct TrainState {
     float *foldA[2], *foldd[2], *gfoldA, *gfoldd;     // Conv4Channel pairs folded to 32x32 (+ their gradients)
     double *p_sss, *p_ssc, *p_vec, *p_ce;
     int* hit;
-    bool loss_grads_ready = false;
+    // dcos / df_ext / extM hold the loss gradients of the forward in this slot (-1: of none).  Set by train_losses; reset by whatever
+    // overwrites them: any backward, a new forward into that slot, a reallocation of the scratch
+    int loss_grads_slot = -1;
+    bool fold_ready = false;       // foldA / foldd hold the products of the live weights (a folded forward since the scratch was allocated)
     // gradient buckets of the data-parallel exchange: contiguous ranges of the flat buffer in the order the backward
     // finishes them (classifier, Conv4Merge, ChannelFlipMerge, Conv4Channel, Conv4Space); one event per bucket
     static const int NBUCKET = 5;

@@ -89,7 +89,11 @@ int ffr_train_backward(ffr_handle* h, int slot, const float* d_f_new, const floa
  * f_enc [2N,512]: the encoder embeddings of both halves (device).  loss_weight: 4 doubles (host), run.py:16.
  * out5 (device, may be NULL): the four items and the accuracy of the occluded half (trainer.py:147-151).        */
 int ffr_train_losses(ffr_handle* h, int slot, const float* f_enc, const double* loss_weight, float* out5, void* stream);
-/* ffr_train_backward with the gradients ffr_train_losses left in the handle */
+/* ffr_train_backward with the gradients ffr_train_losses left in the handle.  Those gradients lie in the backward scratch, which
+ * both slots share, and belong to the forward of the slot ffr_train_losses was called on.  They live until the next call that
+ * uses that scratch: another ffr_train_losses, any backward (either slot), a new ffr_train_forward into the same slot, or a
+ * forward of more images than any before (either slot), which reallocates the scratch.  After any of these, and for the other
+ * slot, this call returns FFR_ERR_STATE and leaves the gradient buffer as it was. */
 int ffr_train_backward_losses(ffr_handle* h, int slot, void* stream);
 
 /* One iteration up to the gradients, train.py:46-54 without the optimiser step, in ONE launch-only call: encoder
