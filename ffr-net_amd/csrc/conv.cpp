@@ -148,15 +148,21 @@ static int trace_wino_fused(ffr_handle* h, WinoFusedArgs& f, const ConvW& L, con
 }
 #endif
 
-// plan + launch one (possibly batched) implicit-GEMM described by `a` (M, nkt, cout_pad, nbatch set)
+// what the convolution L stores for call c: the epilogue of whichever kernel it ends in
+static ConvTail conv_tail(const ConvW& L, const ConvCall& c) {
+    return ConvTail{L.bias, L.slope, c.resid, c.out, c.tile_sums, L.cout_pad, c.cout_store, c.out_pitch, c.out_coff, c.res_pitch, L.border, c.flags};
+}
+
+// plan + launch one (possibly batched) implicit-GEMM described by `a` (M, nkt, tail.cout_pad, nbatch set)
 int run_gemm(ffr_handle* h, IgemmArgs& a, const ConvCall& c, double flops, double bytes, hipStream_t st, double fuse) {
     int force = c.tile;
+    const int cout_pad = a.tail.cout_pad;
     if (force) {      // a forced tile whose width does not divide cout_pad would launch zero column tiles and leave `out` unwritten
         int fbm, fbn;
         igemm_tile_shape(force, &fbm, &fbn);
-        if (a.cout_pad % fbn) return fail(h, FFR_ERR_ARG, "conv: forced tile %d (%d x %d) does not divide cout_pad %d", force, fbm, fbn, a.cout_pad);
+        if (cout_pad % fbn) return fail(h, FFR_ERR_ARG, "conv: forced tile %d (%d x %d) does not divide cout_pad %d", force, fbm, fbn, cout_pad);
     }
-    const GemmPlan g = plan_gemm_launch(a.M, a.cout_pad, a.nkt, a.nbatch, force, h->opt.sk_minunits, a.w3 != nullptr, c.partial_cap, c.tickets_cap);
+    const GemmPlan g = plan_gemm_launch(a.M, cout_pad, a.nkt, a.nbatch, force, h->opt.sk_minunits, a.w3 != nullptr, c.partial_cap, c.tickets_cap);
     if (g.nomem) return fail(h, FFR_ERR_NOMEM, "%s", g.nomem);
     const int tile = g.tile, nblocks = g.nblocks;
     const long long units = g.units;
@@ -176,7 +182,7 @@ int run_gemm(ffr_handle* h, IgemmArgs& a, const ConvCall& c, double flops, doubl
 #ifdef FFR_TRACE
     if (h->opt.igemm_trace) return trace_igemm(h, a, tile, nblocks, units, st);
 #endif
-    const double fexec = 2.0 * a.nbatch * (double)a.mtiles * bm * (double)a.cout_pad * a.KK;
+    const double fexec = 2.0 * a.nbatch * (double)a.mtiles * bm * (double)cout_pad * a.KK;
     Scope s(h, st, FFR_KC_CONV_IGEMM, flops, bytes, fexec, fuse);
     HIPCK(h, launch_igemm(a, tile, nblocks, st));
     return FFR_OK;
@@ -193,10 +199,8 @@ static int conv_mixed(ffr_handle* h, const ConvW& L, const ConvCall& c, double f
     WinoMixedArgs f{};
     f.V[0] = c.winoV;
     for (int tau = 0; tau < 4; ++tau) f.U[tau] = L.wum[tau];
-    f.bias = L.bias; f.slope = L.slope; f.resid = c.resid; f.out = c.out; f.tile_sums = c.tile_sums;
+    f.tail = conv_tail(L, c);
     f.N = c.N; f.H = c.H; f.W = c.W; f.nkc = L.cin_pad / 8;
-    f.cout_pad = L.cout_pad; f.cout_store = c.cout_store; f.out_pitch = c.out_pitch; f.out_coff = c.out_coff;
-    f.res_pitch = c.res_pitch; f.border_bias = L.border; f.flags = c.flags;
     double fexec = 0.0, fuse = 0.0;
     for (int tau = 0; tau < 4; ++tau) {
         const int nr = tau >= 2 ? g.n3 : g.n4, nc = (tau & 1) ? g.n3 : g.n4;
@@ -230,10 +234,8 @@ static int conv_fused(ffr_handle* h, const ConvW& L, const ConvCall& c, const Co
     f.x_bytes = p.phased ? (unsigned)(4.0 * c.N * c.H * c.W * c.in_pitch) : 0u;
     f.half_n = p.half_n ? 1 : 0;
     f.U3 = p.split ? L.wu3 : nullptr;
-    f.Uc = L.wuc; f.bias = L.bias; f.slope = L.slope; f.resid = c.resid; f.out = c.out; f.tile_sums = c.tile_sums;
+    f.Uc = L.wuc; f.tail = conv_tail(L, c);
     f.N = c.N; f.H = c.H; f.W = c.W; f.nkc = L.cin_pad / 8;
-    f.cout_pad = L.cout_pad; f.cout_store = c.cout_store; f.out_pitch = c.out_pitch; f.out_coff = c.out_coff;
-    f.res_pitch = c.res_pitch; f.border_bias = L.border; f.flags = c.flags;
     const double fexec = 2.0 * 36.0 * (double)((T + 31) / 32 * 32) * (double)L.cout_pad * L.cin_pad;
     if (h->conv_rec) {
         ffr_conv_launch r{};
@@ -256,12 +258,11 @@ static int igemm_batched(ffr_handle* h, const ConvCall& c, const float* A, long 
                          long long w_bstride, int N_pad, float* out, int out_pitch, long long out_bstride, int M, int nbatch,
                          double flops, double bytes, double fuse, hipStream_t st) {
     IgemmArgs g{};
-    g.x = A; g.w = W; g.bias = h->zero; g.slope = nullptr; g.resid = nullptr; g.out = out; g.zero = h->zero;
+    g.x = A; g.w = W; g.zero = h->zero;
+    g.tail = ConvTail{h->zero, nullptr, nullptr, out, nullptr, N_pad, N_pad, out_pitch, 0, 0, 0, 0};      // the neutral tail: + 0, all N_pad columns
     g.N = 1; g.H = 1; g.W = M; g.Ho = 1; g.Wo = M;
     g.in_pitch = K_pad; g.cin_pad = K_pad; g.R = 1; g.S = 1; g.stride = 1; g.pad = 0; g.pad_mode = 0;
     g.M = M; g.KK = K_pad; g.nkt = K_pad / 32;
-    g.cout_pad = N_pad; g.cout_store = N_pad; g.out_pitch = out_pitch; g.out_coff = 0; g.res_pitch = 0;
-    g.border_bias = 0; g.flags = 0;
     g.nbatch = nbatch; g.x_bstride = a_bstride; g.w_bstride = w_bstride; g.out_bstride = out_bstride;
     return run_gemm(h, g, c, flops, bytes, st, fuse);
 }
@@ -299,8 +300,7 @@ static int conv_unfused(ffr_handle* h, const ConvW& L, const ConvCall& c, long l
     }
     if (c.wino_stage == 1) return FFR_OK;        // the caller transforms M itself (k_wino_out_in)
     Scope s(h, st, FFR_KC_WINO, 0, 4.0 * (36.0 * T * L.cout_pad + (double)M * L.cout));
-    HIPCK(h, launch_wino_out(c.winoM, L.bias, L.slope, c.resid, c.res_pitch, c.out, c.out_pitch, c.out_coff,
-                             c.cout_store, L.cout_pad, c.N, c.H, c.W, L.border, c.flags, st, c.tile_sums));
+    HIPCK(h, launch_wino_out(c.winoM, conv_tail(L, c), c.N, c.H, c.W, st));
     return FFR_OK;
 }
 
@@ -359,12 +359,10 @@ int run_conv(ffr_handle* h, const ConvW& L, const ConvCall& c, hipStream_t st) {
         return run_conv(h, L, c2, st);
     }
     IgemmArgs a{};
-    a.x = c.x; a.w = L.w; a.bias = L.bias; a.slope = L.slope; a.resid = c.resid; a.out = c.out; a.zero = h->zero;
+    a.x = c.x; a.w = L.w; a.tail = conv_tail(L, c); a.zero = h->zero;
     a.N = c.N; a.H = c.H; a.W = c.W; a.Ho = Ho; a.Wo = Wo;
     a.in_pitch = c.in_pitch; a.cin_pad = L.cin_pad; a.R = L.R; a.S = L.S; a.stride = L.stride; a.pad = L.pad; a.pad_mode = L.pad_mode;
     a.M = (int)M; a.KK = L.R * L.S * L.cin_pad; a.nkt = a.KK / 32; a.nbatch = 1;
-    a.cout_pad = L.cout_pad; a.cout_store = c.cout_store; a.out_pitch = c.out_pitch; a.out_coff = c.out_coff;
-    a.res_pitch = c.res_pitch; a.border_bias = L.border; a.flags = c.flags;
     // split-operand form: the layer's weights were split at load time (or by ffr_op_conv's flag) and option igemm_split is on.
     // flops_executed of the launch stays the fp32-equivalent count (run_gemm)
     if (L.w3 && h->opt.igemm_split) { a.w3 = L.w3; a.w3_pstride = (long long)L.cout_pad * a.KK; }

@@ -29,6 +29,14 @@ __device__ __forceinline__ T wave_sum(T v) {
 // row + 4.  The one part of this header that host code uses too (the packer lays a bias out in accumulator order).
 __host__ __device__ __forceinline__ constexpr int acc_row(int row0, int r) { return row0 + (r & 3) + 8 * (r >> 2); }
 
+// index i in [-(n - 1), 2n - 2] of a reflect-padded dimension of n >= 2 (torch 'reflect': the edge is not repeated) -> [0, n)
+__device__ __forceinline__ int reflect_index(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i); }
+// ... for any i <= 3n - 2 too: the Winograd tiles that hang over the right / bottom edge read row 0 there (their outputs are dropped)
+__device__ __forceinline__ int reflect_index_clamped(int i, int n) {
+    const int r = reflect_index(i, n);
+    return r < 0 ? 0 : r;
+}
+
 // two bf16 (round to nearest even) of two floats in one register: lo in bits 0-15
 __device__ __forceinline__ unsigned cvt_pk_bf16(float lo, float hi) {
     unsigned r;

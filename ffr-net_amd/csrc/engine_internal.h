@@ -245,10 +245,7 @@ struct ConvCall {
     int wino_stage = 0;                            // 0 whole conv; 1 stop after the GEMM (M stays in winoM); 2 V is ready in winoV
     bool v_mixed = false;                          // with wino_stage 2: V is in the four-region layout of wino_mixed.hip (k_combine_in_mixed wrote it)
     bool v_chunked = false;                        // with wino_stage 2: V is in the K-chunked fragment order of k_wino_fused (ConvPlan::takes_v)
-    // Winograd paths only: per-tile sums of the stored outputs [T][cout_pad].  One rule for every kernel and every store path
-    // (vector or scalar stores, any pitch, cout_store < cout_pad): entry (tile, channel) is the sum of exactly the values this
-    // call stored to `out` for that channel over the tile's pixels inside the map; a channel that is not stored gets 0.
-    float* tile_sums = nullptr;
+    float* tile_sums = nullptr;                    // Winograd paths only: the rule is ConvTail::tile_sums' (ffr_kernels.h)
 };
 
 // Which kernels one convolution launches and how (plan_conv; run_conv's conv_* launch each path)

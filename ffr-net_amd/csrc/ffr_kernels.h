@@ -16,15 +16,32 @@
 
 namespace ffr {
 
+// ---- what a convolution stores: the epilogue of every convolution kernel -----------
+// out[m][out_coff + c] = tail(acc[m][c]) for the pixels m = (img, ho, wo) and the channels c < cout_store, with
+//   tail(v) = sigmoid?( PReLU(v + bias[class(m)][c], slope[c]) + resid[m][c] )       (device side: conv_tail.h)
+struct ConvTail {
+    const float* bias;    // [n_cls][cout_pad]: the 9 border classes (3 * row class + column class) iff border_bias, else 1
+    const float* slope;   // [cout_pad] PReLU slopes, or null: no activation
+    const float* resid;   // [M][res_pitch], added after the activation, or null
+    float* out;           // [M][out_pitch]; channel c goes to column out_coff + c (concatenations are just addressing)
+    // Winograd kernels only (k_igemm does not read it), or null: per-tile sums of the stored outputs [T][cout_pad], the SE
+    // squeeze partials.  One rule for every kernel and every store path (vector or scalar stores, any pitch, cout_store <
+    // cout_pad): entry (tile, channel) is the sum of exactly the values this call stored to `out` for that channel over the
+    // tile's pixels inside the map; a channel that is not stored gets 0.
+    float* tile_sums;
+    int cout_pad;         // channels computed: the row length of bias, slope and tile_sums
+    int cout_store;       // channels stored, <= cout_pad: the others are computed and dropped
+    int out_pitch, out_coff, res_pitch;
+    int border_bias;
+    int flags;            // bit 0: sigmoid at the end
+};
+
 // ---- implicit-GEMM convolution (igemm.hip) -----------------------------------------
-// out[m][n] = epilogue( sum_k A[m][k] * Wp[n][k] ),  m = (img, ho, wo), k = (r, s, ci)
+// out[m][n] = tail( sum_k A[m][k] * Wp[n][k] ),  m = (img, ho, wo), k = (r, s, ci)
 struct IgemmArgs {
     const float* x;       // [N,H,W,in_pitch]
     const float* w;       // [cout_pad][KK] packed, KK = R*S*cin_pad
-    const float* bias;    // [n_cls][cout_pad]
-    const float* slope;   // [cout_pad] or null
-    const float* resid;   // [M][res_pitch] or null
-    float* out;           // [M][out_pitch] (+out_coff)
+    ConvTail tail;
     const float* zero;    // >= 128 B of zeros (source of zero-padded taps)
     float* partial;       // stream-K slabs [nblocks][2][BM*BN]
     int* tickets;         // stream-K arrival counters, one per tile, zero between launches
@@ -33,8 +50,6 @@ struct IgemmArgs {
     int M, KK, nkt, granule;
     int nbatch;                              // >= 1: independent GEMMs in one launch (tile id = batch-major)
     long long x_bstride, w_bstride, out_bstride;   // element strides between batches
-    int cout_pad, cout_store, out_pitch, out_coff, res_pitch;
-    int border_bias, flags;      // flags bit0: sigmoid at the end
     int mtiles, ntiles;
     // split-operand form (igemm.hip): three bf16 planes of w, plane p at w3 + p * w3_pstride, each [cout_pad][KK];
     // non-null selects the form (nbatch must be 1)
@@ -110,14 +125,22 @@ hipError_t launch_wino_dout(const float* dy, float* dM, int N, int H, int W, int
 hipError_t launch_wino_dweights(const float* dU, float* grad, int out_pad, int in_pad, int accumulate, hipStream_t stream);
 // conv1 -> conv2 inside one bottleneck on maps of at most 4x4 tiles: V2 = B^T PReLU(A^T M1 A + bias) B per image, the
 // activation stays in LDS
+struct WinoOutInArgs {
+    const float* M; const float* bias; const float* slope; float* V;
+    int H, W, C, th, tw, border_bias;
+    long long T;
+};
 bool wino_out_in_supported(int H, int W, int C);
 hipError_t launch_wino_out_in(const float* M, const float* bias, const float* slope, float* V, int N, int H, int W, int C,
                               int border_bias, hipStream_t stream);
-// out = epilogue(A^T M A): bias[(border class)][cout_pad], PReLU, residual, sigmoid (flags bit0)
-hipError_t launch_wino_out(const float* M, const float* bias, const float* slope, const float* resid, int res_pitch,
-                           float* out, int out_pitch, int out_coff, int cout_store, int cout_pad, int N, int H, int W,
-                           int border_bias, int flags, hipStream_t stream, float* tile_sums = nullptr);
-// tile_sums [T][cout_pad] (optional): the sum of every tile's stored outputs -- the SE squeeze partials
+// out = tail(A^T M A) of M [36][T][tail.cout_pad]
+struct WinoOutArgs {
+    const float* M;
+    ConvTail tail;
+    int N, H, W, th, tw;        // th, tw and T: filled by the launcher
+    long long T;
+};
+hipError_t launch_wino_out(const float* M, const ConvTail& tail, int N, int H, int W, hipStream_t stream);
 
 // ---- Winograd conv with GEMM and output transform in one kernel (wino_fused.hip) -----------------------------
 // Vc [mbn][nkc][36][64 pieces][4]: the input transform of 32-tile groups in 8-channel K chunks (piece order: see
@@ -129,9 +152,8 @@ struct WinoFusedArgs {
     const float* x;                         // phased mode: input [N,H,W,in_pitch] ...
     unsigned x_bytes;                       // ... and its size in bytes (<= 1 GiB; out-of-range reads return zeros)
     int in_pitch, pad_mode;
-    const float* bias; const float* slope; const float* resid; float* out; float* tile_sums;
+    ConvTail tail;
     int N, H, W, nkc;                       // nkc = cin_pad / 8
-    int cout_pad, cout_store, out_pitch, out_coff, res_pitch, border_bias, flags;
     int half_n;                             // 1: blocks of 32 tiles x 32 channels (k_wino_fused<., 1>) instead of 32 x 64
     int th, tw, mbn, nbn;                   // filled by the launcher
     long long T;
@@ -162,9 +184,8 @@ struct WinoInMixedArgs {
 struct WinoMixedArgs {
     const float* V[4];                      // in: V[0] = base of the four regions (wino_mixed_v_floats); the launcher fills the rest
     const float* U[4];                      // weights per type in fragment order [cout_pad/64][K chunk][XP][128 pieces][4]
-    const float* bias; const float* slope; const float* resid; float* out; float* tile_sums;
+    ConvTail tail;
     int N, H, W, nkc;
-    int cout_pad, cout_store, out_pitch, out_coff, res_pitch, border_bias, flags;
     WinoMixedGeom g;                        // filled by the launcher, as everything below
     int mbn[4], half_blocks, nbn, tpi_off[4], tpi_total;       // half_blocks: the grid's first half, (4,4) | (4,3); the second runs (3,3) | (3,4)
     long long T[4];

@@ -19,6 +19,7 @@
 // * Epilogue in registers: bias (optionally one of 9 border classes, for the BN that
 //   precedes a zero-padded conv), PReLU, residual add, sigmoid; NHWC store with pitch /
 //   channel offset so concatenations are just addressing.
+#include "conv_tail.h"
 #include "ffr_kernels.h"
 #include "igemm_core.h"
 
@@ -45,6 +46,7 @@ __global__ __launch_bounds__(256) void k_igemm(const IgemmArgs a) {
     int* s_cls = reinterpret_cast<int*>(smem + igemm_cls_offset(BM, BN, SPLIT));     // [BM] border class per row, [BM] = ticket
     float* s_bias = smem + igemm_bias_offset(BM, BN, SPLIT);                        // [9][BN] border-class biases of this tile
 
+    const ConvTail& e = a.tail;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int wm = wave / WARPS_N, wn = wave % WARPS_N;
     const int HoWo = a.Ho * a.Wo;
@@ -70,7 +72,7 @@ __global__ __launch_bounds__(256) void k_igemm(const IgemmArgs a) {
     const int nt = tile_b % a.ntiles, mt = tile_b / a.ntiles;
     const float* const xb = a.x + (long long)batch * a.x_bstride;
     const float* const wb = a.w + (long long)batch * a.w_bstride;
-    float* const ob = a.out + (long long)batch * a.out_bstride;
+    float* const ob = e.out + (long long)batch * a.out_bstride;
     const int m0 = mt * BM, n0 = nt * BN;
     __syncthreads();        // LDS (stages, s_cls) of the previous segment is free
     // Outside the MFMA loop this wave competes for issue slots with the co-resident block's wave,
@@ -104,7 +106,7 @@ __global__ __launch_bounds__(256) void k_igemm(const IgemmArgs a) {
             a_w0[i] = wo * a.stride - a.pad;
         }
     }
-    if (a.border_bias && tid < BM) {
+    if (e.border_bias && tid < BM) {
         int m = m0 + tid;
         if (m >= a.M) m = 0;
         const int n = m / HoWo;
@@ -116,8 +118,8 @@ __global__ __launch_bounds__(256) void k_igemm(const IgemmArgs a) {
         const int cc = (w0 < 0) ? 0 : ((w0 + a.S - 1 >= a.W) ? 2 : 1);
         s_cls[tid] = rc * 3 + cc;
     }
-    if (a.border_bias) {
-        for (int idx = tid; idx < 9 * BN; idx += 256) s_bias[idx] = a.bias[(idx / BN) * a.cout_pad + n0 + (idx % BN)];
+    if (e.border_bias) {
+        for (int idx = tid; idx < 9 * BN; idx += 256) s_bias[idx] = e.bias[(idx / BN) * e.cout_pad + n0 + (idx % BN)];
     }
 
     // ---- tap state at the first K-tile of this segment -----------------------------------
@@ -147,8 +149,8 @@ __global__ __launch_bounds__(256) void k_igemm(const IgemmArgs a) {
             int hi = a_h0[i] + tr, wi = a_w0[i] + ts;
             bool ok = true;
             if (PAD_MODE == 1) {
-                hi = hi < 0 ? -hi : (hi >= a.H ? 2 * a.H - 2 - hi : hi);
-                wi = wi < 0 ? -wi : (wi >= a.W ? 2 * a.W - 2 - wi : wi);
+                hi = reflect_index(hi, a.H);
+                wi = reflect_index(wi, a.W);
             } else {
                 ok = ((unsigned)hi < (unsigned)a.H) && ((unsigned)wi < (unsigned)a.W);
             }
@@ -406,10 +408,9 @@ __global__ __launch_bounds__(256) void k_igemm(const IgemmArgs a) {
     if (finish) {
         const int n = n0 + ecol;
         // (the one sigmoid conv of the network, 49 channels, takes the generic path)
-        const bool vec = ((a.out_pitch | a.out_coff | a.res_pitch) & 3) == 0 && n + 4 <= a.cout_store && !(a.flags & 1);
-        f32x4 slope4 = {1.f, 1.f, 1.f, 1.f};
-        if (a.slope) slope4 = *reinterpret_cast<const f32x4*>(a.slope + n);
-        const f32x4 bias0 = *reinterpret_cast<const f32x4*>(a.bias + n);
+        const bool vec = ((e.out_pitch | e.out_coff | e.res_pitch) & 3) == 0 && n + 4 <= e.cout_store && !(e.flags & 1);
+        const f32x4 slope4 = tail_slope4(e.slope, n);
+        const f32x4 bias0 = *reinterpret_cast<const f32x4*>(e.bias + n);
         // No global LOAD may sit between the stores of this loop: vmcnt retires in order, so the
         // wait in front of a load's first use also drains every older store (a full HBM write
         // latency per pass: 37k of the 42k epilogue cycles measured).  Border-class biases come
@@ -420,10 +421,10 @@ __global__ __launch_bounds__(256) void k_igemm(const IgemmArgs a) {
             f32x4 rs[BATCH], rn[BATCH];
             // row pointers advance by RPP rows per pass (no 64-bit multiply per store)
             const int mrow = m0 + erow;
-            float* optr = ob + (size_t)mrow * a.out_pitch + a.out_coff + n;
-            const size_t ostep = (size_t)RPP * a.out_pitch;
-            const float* rptr = RESID ? a.resid + (size_t)mrow * a.res_pitch + n : nullptr;
-            const size_t rstep = (size_t)RPP * a.res_pitch;
+            float* optr = ob + (size_t)mrow * e.out_pitch + e.out_coff + n;
+            const size_t ostep = (size_t)RPP * e.out_pitch;
+            const float* rptr = RESID ? e.resid + (size_t)mrow * e.res_pitch + n : nullptr;
+            const size_t rstep = (size_t)RPP * e.res_pitch;
             auto load_resid = [&](f32x4* dstv, int p0) {
 #pragma unroll
                 for (int k = 0; k < BATCH; ++k) {
@@ -438,11 +439,13 @@ __global__ __launch_bounds__(256) void k_igemm(const IgemmArgs a) {
 #pragma unroll
                 for (int k = 0; k < BATCH; ++k) {
                     const int ml = (p0 + k) * RPP + erow;
+                    // tail_act4's arithmetic, written out: through the call, or through prelu<> alone, the fp and MFMA sequence of
+                    // all 16 instantiations comes out in another order
                     f32x4 v = *reinterpret_cast<const f32x4*>(sC + ml * LDC + ecol);
                     if (BORDER) v += *reinterpret_cast<const f32x4*>(s_bias + s_cls[ml] * BN + ecol);
                     else v += bias0;
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = v[e] >= 0.f ? v[e] : v[e] * slope4[e];
+                    for (int c = 0; c < 4; ++c) v[c] = v[c] >= 0.f ? v[c] : v[c] * slope4[c];
                     if (RESID) v += rs[k];
                     if (m0 + ml < a.M) *reinterpret_cast<f32x4*>(optr) = v;
                     optr += ostep;
@@ -454,11 +457,11 @@ __global__ __launch_bounds__(256) void k_igemm(const IgemmArgs a) {
             }
         };
         if (vec) {
-            if (a.border_bias) {
-                if (a.resid) finish_tile.template operator()<true, true>();
+            if (e.border_bias) {
+                if (e.resid) finish_tile.template operator()<true, true>();
                 else finish_tile.template operator()<true, false>();
             } else {
-                if (a.resid) finish_tile.template operator()<false, true>();
+                if (e.resid) finish_tile.template operator()<false, true>();
                 else finish_tile.template operator()<false, false>();
             }
         } else {
@@ -469,14 +472,13 @@ __global__ __launch_bounds__(256) void k_igemm(const IgemmArgs a) {
                 const int m = m0 + ml;
                 if (m >= a.M) continue;
                 f32x4 v = *reinterpret_cast<const f32x4*>(sC + ml * LDC + ecol);
-                v += a.border_bias ? *reinterpret_cast<const f32x4*>(s_bias + s_cls[ml] * BN + ecol) : bias0;
+                v += e.border_bias ? *reinterpret_cast<const f32x4*>(s_bias + s_cls[ml] * BN + ecol) : bias0;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    if (n + e < a.cout_store) {
-                        float x = v[e] >= 0.f ? v[e] : v[e] * slope4[e];
-                        if (a.resid) x += a.resid[(size_t)m * a.res_pitch + n + e];
-                        if (a.flags & 1) x = 1.0f / (1.0f + __expf(-x));
-                        ob[(size_t)m * a.out_pitch + a.out_coff + n + e] = x;
+                for (int c = 0; c < 4; ++c) {
+                    if (n + c < e.cout_store) {
+                        float x = prelu<PRELU_SELECT>(v[c], slope4[c]);
+                        x = tail_end1(x, e.resid != nullptr, [&] { return e.resid[(size_t)m * e.res_pitch + n + c]; }, e.flags);
+                        ob[(size_t)m * e.out_pitch + e.out_coff + n + c] = x;
                     }
                 }
             }

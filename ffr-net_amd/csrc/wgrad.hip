@@ -151,8 +151,8 @@ __global__ __launch_bounds__(256, 2) void k_wgrad(const WgradArgs a) {
                 h += dr; w += ds;
                 bool ok = true;
                 if (a.pad_mode == 1) {
-                    h = h < 0 ? -h : (h >= a.H ? 2 * a.H - 2 - h : h);
-                    w = w < 0 ? -w : (w >= a.W ? 2 * a.W - 2 - w : w);
+                    h = reflect_index(h, a.H);
+                    w = reflect_index(w, a.W);
                 } else {
                     ok = (unsigned)h < (unsigned)a.H && (unsigned)w < (unsigned)a.W;
                 }

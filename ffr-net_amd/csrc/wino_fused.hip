@@ -45,35 +45,10 @@ __global__ __launch_bounds__(256) void k_wino_in_c(const float* __restrict__ x, 
     const int c4 = kc * 8 + hh * 4;
     float* vout = wino_frag_ptr<36>(Vc, mb, nkc, kc, hh, tl);
     if (t >= T) { wino_frag_zero<36>(vout); return; }
-    const unsigned tu = (unsigned)t, tpi = (unsigned)(tw * th);       // T < 2^31: 32-bit divisions
-    const int n = (int)(tu / tpi);
-    const unsigned tr = tu - (unsigned)n * tpi;
-    const int ty = (int)(tr / (unsigned)tw);
-    const int tx = (int)(tr - (unsigned)ty * (unsigned)tw);
-    const int h0 = ty * 4 - 1, w0 = tx * 4 - 1;
-    const float* xn = x + (size_t)n * H * W * pitch + c4;
+    int n, ty, tx;
+    wino_tile_of((unsigned)t, th, tw, &n, &ty, &tx);                  // T < 2^31
     f32x4 tmp[6][6];
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        f32x4 d[6], v[6];
-        int wi = w0 + j;
-        bool okw = true;
-        if (PAD_MODE == 1) wi = wi < 0 ? -wi : (wi >= W ? 2 * W - 2 - wi : wi);
-        else okw = (unsigned)wi < (unsigned)W;
-        if (PAD_MODE == 1 && wi < 0) wi = 0;      // tiles hanging over the right/bottom edge (outputs dropped)
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-            int hi = h0 + i;
-            bool ok = okw;
-            if (PAD_MODE == 1) { hi = hi < 0 ? -hi : (hi >= H ? 2 * H - 2 - hi : hi); if (hi < 0) hi = 0; }
-            else ok = ok && ((unsigned)hi < (unsigned)H);
-            d[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            if (ok) d[i] = *reinterpret_cast<const f32x4*>(xn + ((size_t)hi * W + wi) * pitch);
-        }
-        bt6v(d, v);
-#pragma unroll
-        for (int i = 0; i < 6; ++i) tmp[i][j] = v[i];
-    }
+    wino_gather_bt_cols<PAD_MODE>(x + (size_t)n * H * W * pitch + c4, H, W, pitch, ty * 4 - 1, tx * 4 - 1, tmp);
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
         f32x4 v[6];
@@ -182,6 +157,7 @@ __global__ __launch_bounds__(256, 1) void k_wino_fused(const WinoFusedArgs a) {
     constexpr bool PHASED = MODE != 0;
     static_assert(!SPLIT || (MODE == 1 && NT == 2), "the split-operand form exists for the in-kernel transform with 32 x 64 blocks");
     extern __shared__ __attribute__((aligned(16))) float smem[];
+    const ConvTail& e = a.tail;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     // block -> (tile group mb, channel group nb).  Blocks b and b + 8 share an XCD (round-robin dispatch) and with it
@@ -210,17 +186,12 @@ __global__ __launch_bounds__(256, 1) void k_wino_fused(const WinoFusedArgs a) {
     const int n0 = nb * (32 * NT);
     float* const s_bias = smem + WF_EPI_FLOATS;
     int* const s_tile = reinterpret_cast<int*>(s_bias + 9 * 64);     // [4..6]: image base pixel, 4ty-1, 4tx-1
-    wf_fill_bias<NT>(s_bias, a.bias, a.border_bias, a.cout_pad, n0);
+    wf_fill_bias<NT>(s_bias, e.bias, e.border_bias, e.cout_pad, n0);
     if (tid < 32) {
         const long long t = (long long)mb * 32 + tid;
         const bool valid = t < a.T;
         int n = 0, ty = 0, tx = 0;
-        if (valid) {
-            const unsigned tiles_img = (unsigned)(a.th * a.tw);        // T < 2^31 (run_conv): 32-bit divisions
-            n = (int)((unsigned)t / tiles_img);
-            const int tr = (int)((unsigned)t - (unsigned)n * tiles_img);
-            ty = (int)((unsigned)tr / (unsigned)a.tw); tx = tr - ty * a.tw;
-        }
+        if (valid) wino_tile_of((unsigned)t, a.th, a.tw, &n, &ty, &tx);        // T < 2^31 (run_conv)
         const int ibase = valid ? n * a.H * a.W : 0, h0 = valid ? ty * 4 - 1 : 0, w0 = valid ? tx * 4 - 1 : 0;
         wf_tile_record(s_tile + tid * 8, valid, n, ty * 4, tx * 4, 4, 4, a.H, a.W);
         s_tile[tid * 8 + 4] = ibase; s_tile[tid * 8 + 5] = h0; s_tile[tid * 8 + 6] = w0;
@@ -234,8 +205,8 @@ __global__ __launch_bounds__(256, 1) void k_wino_fused(const WinoFusedArgs a) {
                 int hi = h0 + i, wi = w0 + i;
                 bool rok, cok;
                 if (a.pad_mode == 1) {
-                    hi = hi < 0 ? -hi : (hi >= a.H ? 2 * a.H - 2 - hi : hi); if (hi < 0) hi = 0;
-                    wi = wi < 0 ? -wi : (wi >= a.W ? 2 * a.W - 2 - wi : wi); if (wi < 0) wi = 0;
+                    hi = reflect_index_clamped(hi, a.H);
+                    wi = reflect_index_clamped(wi, a.W);
                     rok = valid; cok = true;
                 } else {
                     rok = valid && (unsigned)hi < (unsigned)a.H;
@@ -251,13 +222,13 @@ __global__ __launch_bounds__(256, 1) void k_wino_fused(const WinoFusedArgs a) {
     wf_zero_acc<NT>(acc, accv);
 
     if constexpr (MODE == 0) {
-    wf_vfed_gemm<9, NT>(a.Vc, a.Uc, mb, nb, nkc, a.cout_pad, wave, lane, acc, accv, a.trace, st1);
+    wf_vfed_gemm<9, NT>(a.Vc, a.Uc, mb, nb, nkc, e.cout_pad, wave, lane, acc, accv, a.trace, st1);
     } else if constexpr (MODE == 1) {
     // the weight stream of this wave through a buffer resource, as in wf_vfed_gemm; V comes from LDS
     // (split form: three bf16 planes, 6 KB per channel group, 16-channel K step and xi)
     const __amdgpu_buffer_rsrc_t urs = SPLIT
-        ? __builtin_amdgcn_make_buffer_rsrc((void*)a.U3, 0, (unsigned)((size_t)(a.cout_pad >> 6) * (nkc >> 1) * 36 * WF_U3_STEP), 0x00020000)
-        : __builtin_amdgcn_make_buffer_rsrc((void*)a.Uc, 0, (unsigned)((size_t)a.cout_pad * nkc * 8 * 36 * 4), 0x00020000);
+        ? __builtin_amdgcn_make_buffer_rsrc((void*)a.U3, 0, (unsigned)((size_t)(e.cout_pad >> 6) * (nkc >> 1) * 36 * WF_U3_STEP), 0x00020000)
+        : __builtin_amdgcn_make_buffer_rsrc((void*)a.Uc, 0, (unsigned)((size_t)e.cout_pad * nkc * 8 * 36 * 4), 0x00020000);
     const unsigned lane16 = (unsigned)lane * 16u;
     // U is packed per 64-channel group: [cout_pad/64][K chunk][xi][2 halves][64 lanes][4]
     // split form: [cout_pad/64][16-channel K step][xi][2 halves][3 planes][64 lanes][8 bf16]
@@ -486,7 +457,7 @@ __global__ __launch_bounds__(256, 1) void k_wino_fused(const WinoFusedArgs a) {
     // the inline-asm MFMAs are invisible to hipcc's hazard recognizer: their results must not be read for 18 cycles
     asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
     const int cq = lane & 7;                        // channel quad of this lane within the 32-channel half
-    const bool vec4 = ((a.out_pitch | a.out_coff | a.res_pitch) & 3) == 0;
+    const bool vec4 = ((e.out_pitch | e.out_coff | e.res_pitch) & 3) == 0;
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
         wf_stage_acc<9, 36, NT>(smem, wave, lane, nt, acc, accv);      // E[xi][tile][co]: the 32-channel half nt of all 32 tiles
@@ -498,15 +469,15 @@ __global__ __launch_bounds__(256, 1) void k_wino_fused(const WinoFusedArgs a) {
         if (vrc != 0) {                                                 // else: tile beyond T
             const int pix0 = s_tile[tl * 8 + 0];
             const int vr = vrc & 0xff, vc = vrc >> 8;
-            const f32x4* e = wf_staged(smem, tl, cq);
             f32x4 y[4][4];
             {
                 f32x4 tmp[4][6];
+                const f32x4* ee = wf_staged(smem, tl, cq);
 #pragma unroll
                 for (int j = 0; j < 6; ++j) {
                     f32x4 mc[6], yc[4];
 #pragma unroll
-                    for (int i = 0; i < 6; ++i) mc[i] = e[(i * 6 + j) * 256];
+                    for (int i = 0; i < 6; ++i) mc[i] = ee[(i * 6 + j) * 256];
                     at6t(mc, yc);
 #pragma unroll
                     for (int i = 0; i < 4; ++i) tmp[i][j] = yc[i];
@@ -516,10 +487,10 @@ __global__ __launch_bounds__(256, 1) void k_wino_fused(const WinoFusedArgs a) {
             }
             const int cl = nt * 32 + 4 * cq;            // channel within the block's channel group
             const int cg = n0 + cl;
-            const f32x4 slope = wf_slope(a.slope, cg);
+            const f32x4 slope = tail_slope4(e.slope, cg);
             // bias per pixel: one value, or one of 9 border classes
             f32x4 bs[4][4];
-            if (!a.border_bias) {
+            if (!e.border_bias) {
                 const f32x4 b0 = *reinterpret_cast<const f32x4*>(s_bias + cl);
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
@@ -535,7 +506,7 @@ __global__ __launch_bounds__(256, 1) void k_wino_fused(const WinoFusedArgs a) {
                     for (int jj = 0; jj < 4; ++jj) bs[i][jj] = *reinterpret_cast<const f32x4*>(s_bias + rc[i] + cc[jj] + cl);
             }
             f32x4 psum = {0.f, 0.f, 0.f, 0.f};
-            if (vec4 && cg + 3 < a.cout_store) {
+            if (vec4 && cg + 3 < e.cout_store) {
                 // Branch-free stores: pixel (i, jj) of a tile that hangs over the map's edge is redirected to the tile's
                 // last valid row / column, and the pixels are stored in DESCENDING order: the stray value lands first,
                 // the right one (same lane, same address, program order) overwrites it.
@@ -545,14 +516,14 @@ __global__ __launch_bounds__(256, 1) void k_wino_fused(const WinoFusedArgs a) {
                     ro[i] = (i < vr ? i : vr - 1) * a.W;
                     co[i] = i < vc ? i : vc - 1;
                 }
-                float* const ob = a.out + (size_t)pix0 * a.out_pitch + a.out_coff + cg;
-                const float* const rb = a.resid ? a.resid + (size_t)pix0 * a.res_pitch + cg : nullptr;
+                float* const ob = e.out + (size_t)pix0 * e.out_pitch + e.out_coff + cg;
+                const float* const rb = e.resid ? e.resid + (size_t)pix0 * e.res_pitch + cg : nullptr;
                 f32x4 rs[4][4];
                 if (rb) {
 #pragma unroll
                     for (int i = 0; i < 4; ++i)
 #pragma unroll
-                        for (int jj = 0; jj < 4; ++jj) rs[i][jj] = *reinterpret_cast<const f32x4*>(rb + (ro[i] + co[jj]) * a.res_pitch);
+                        for (int jj = 0; jj < 4; ++jj) rs[i][jj] = *reinterpret_cast<const f32x4*>(rb + (ro[i] + co[jj]) * e.res_pitch);
                 }
                 float mr[4], mc[4];          // 1 for pixels inside the map (SE tile sums)
 #pragma unroll
@@ -561,9 +532,9 @@ __global__ __launch_bounds__(256, 1) void k_wino_fused(const WinoFusedArgs a) {
                 for (int i = 3; i >= 0; --i)
 #pragma unroll
                     for (int jj = 3; jj >= 0; --jj) {
-                        const f32x4 v = wf_pointwise(y[i][jj], bs[i][jj], slope, rb != nullptr, [&] { return rs[i][jj]; }, a.flags);
-                        *reinterpret_cast<f32x4*>(ob + (ro[i] + co[jj]) * a.out_pitch) = v;
-                        if (a.tile_sums) psum += v * (mr[i] * mc[jj]);
+                        const f32x4 v = tail4<PRELU_MINMAX>(y[i][jj], bs[i][jj], slope, rb != nullptr, [&] { return rs[i][jj]; }, e.flags);
+                        *reinterpret_cast<f32x4*>(ob + (ro[i] + co[jj]) * e.out_pitch) = v;
+                        if (e.tile_sums) psum += v * (mr[i] * mc[jj]);
                     }
             } else {            // odd pitches / channel counts: scalar stores
 #pragma unroll
@@ -574,17 +545,16 @@ __global__ __launch_bounds__(256, 1) void k_wino_fused(const WinoFusedArgs a) {
                         const size_t m = (size_t)pix0 + i * a.W + jj;
 #pragma unroll
                         for (int c = 0; c < 4; ++c) {
-                            if (cg + c >= a.cout_store) continue;
+                            if (cg + c >= e.cout_store) continue;
                             float v = y[i][jj][c] + bs[i][jj][c];
-                            v = fmaxf(v, 0.f) + slope[c] * fminf(v, 0.f);
-                            if (a.resid) v += a.resid[m * a.res_pitch + cg + c];
-                            if (a.flags & 1) v = 1.0f / (1.0f + __expf(-v));
-                            a.out[m * a.out_pitch + a.out_coff + cg + c] = v;
+                            v = prelu<PRELU_MINMAX>(v, slope[c]);
+                            v = tail_end1(v, e.resid != nullptr, [&] { return e.resid[m * e.res_pitch + cg + c]; }, e.flags);
+                            e.out[m * e.out_pitch + e.out_coff + cg + c] = v;
                             psum[c] += v;
                         }
                     }
             }
-            if (a.tile_sums) wf_store_tile_sum(a.tile_sums, (long long)mb * 32 + tl, a.cout_pad, cg, psum);
+            if (e.tile_sums) tail_store_tile_sum(e.tile_sums, (long long)mb * 32 + tl, e.cout_pad, cg, psum);
         }
         if (FFR_TRACE_ON(a.trace) && !PHASED) se[2 * nt + 1] = __builtin_amdgcn_s_memtime();
         __syncthreads();
@@ -618,15 +588,15 @@ static int wf_grid(int mbn, int nbn) { return (mbn + 7) / 8 * 8 * nbn; }      //
 
 int wino_fused_blocks(const WinoFusedArgs& a) {
     const long long T = (long long)a.N * ((a.H + 3) / 4) * ((a.W + 3) / 4);
-    return wf_grid((int)((T + 31) / 32), a.cout_pad / (a.half_n ? 32 : 64));
+    return wf_grid((int)((T + 31) / 32), a.tail.cout_pad / (a.half_n ? 32 : 64));
 }
 
 hipError_t launch_wino_fused(WinoFusedArgs a, hipStream_t stream) {
-    if (a.cout_pad % 64 || a.nkc < 2) return hipErrorInvalidValue;
+    if (a.tail.cout_pad % 64 || a.nkc < 2) return hipErrorInvalidValue;
     a.th = (a.H + 3) / 4; a.tw = (a.W + 3) / 4;
     a.T = (long long)a.N * a.th * a.tw;
     a.mbn = (int)((a.T + 31) / 32);
-    a.nbn = a.cout_pad / (a.half_n ? 32 : 64);
+    a.nbn = a.tail.cout_pad / (a.half_n ? 32 : 64);
     const dim3 grid(wf_grid(a.mbn, a.nbn));
     if (a.Vc) {
         if (a.U3) return hipErrorInvalidValue;                      // ... and only with the in-kernel transform

@@ -5,6 +5,7 @@
 // describes the operand order and the work split; DESIGN.md 3.1 the design.
 // Everything is __forceinline__ and takes the accumulators by reference: the kernels sit at 256 VGPRs + 256 AGPRs.
 #pragma once
+#include "conv_tail.h"
 #include "device_util.h"
 #include "ffr_kernels.h"
 #include "wino_math.h"
@@ -212,27 +213,6 @@ __device__ __forceinline__ void wf_border_offsets(int b, int stride, int (&o)[M]
 #pragma unroll
     for (int i = 0; i < M; ++i) o[i] = ((i == 0 && (b & 1)) ? 0 : (i == (b >> 8) ? 2 : 1)) * stride;
 }
-__device__ __forceinline__ f32x4 wf_slope(const float* slope, int cg) {
-    f32x4 s = {1.f, 1.f, 1.f, 1.f};
-    if (slope) s = *reinterpret_cast<const f32x4*>(slope + cg);
-    return s;
-}
-// one output pixel, four channels: bias, PReLU, residual (resid() is evaluated only if has_res), sigmoid under flags bit 0
-template <typename R>
-__device__ __forceinline__ f32x4 wf_pointwise(f32x4 v, const f32x4& bias, const f32x4& slope, bool has_res, R&& resid, int flags) {
-    v += bias;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) v[c] = fmaxf(v[c], 0.f) + slope[c] * fminf(v[c], 0.f);     // PReLU without VCC
-    if (has_res) v += resid();
-    if (flags & 1) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) v[c] = 1.0f / (1.0f + __expf(-v[c]));
-    }
-    return v;
-}
-// the sum of a tile's stored outputs (the SE squeeze partials), tile_sums [slot][cout_pad]
-__device__ __forceinline__ void wf_store_tile_sum(float* tile_sums, long long slot, int cout_pad, int cg, const f32x4& psum) {
-    *reinterpret_cast<f32x4*>(tile_sums + (size_t)slot * cout_pad + cg) = psum;
-}
+// (the pointwise part of the epilogue is conv_tail.h's, in the form PRELU_MINMAX)
 
 }  // namespace ffr

@@ -57,4 +57,45 @@ __device__ __forceinline__ void at5q(const f32x4 m[5], f32x4 y[3]) {
 template <int A> __device__ __forceinline__ void btv(const f32x4* d, f32x4* v) { if constexpr (A == 6) bt6v(d, v); else bt5v(d, v); }
 template <int A> __device__ __forceinline__ void atq(const f32x4* m, f32x4* y) { if constexpr (A == 6) at6t(m, y); else at5q(m, y); }
 
+// ---- the F(4x4,3x3) tile walk -----------------------------------------------------------------------------------------
+// tile t < 2^31 of a map of th x tw tiles per image -> image n, tile row ty, tile column tx, in 32-bit arithmetic (a 64-bit
+// division is ~100 instructions)
+__device__ __forceinline__ void wino_tile_of(unsigned t, int th, int tw, int* n, int* ty, int* tx) {
+    const unsigned tpi = (unsigned)(tw * th);
+    const unsigned nn = t / tpi, tr = t - nn * tpi;
+    const unsigned y = tr / (unsigned)tw;
+    *n = (int)nn; *ty = (int)y; *tx = (int)(tr - y * (unsigned)tw);
+}
+// The 6x6 patch whose top-left pixel is (h0, w0) of the image src [H][W][pitch], four channels, gathered column by column
+// with B^T applied to every column: tmp[i][j] = (B^T d)[i][j].  PAD_MODE 0: zeros outside the map, 1: reflection.  A column
+// is transformed while the next one loads (see wino_fused_core.h on why the patch loops are not wino_patch_to_frags).
+// The reflection is written out, not reflect_index_clamped (device_util.h): through the call the reflect instances of k_wino_in
+// and k_wino_in_c lose 4 and 2 VGPRs and their fp sequence is reordered.
+template <int PAD_MODE>
+__device__ __forceinline__ void wino_gather_bt_cols(const float* src, int H, int W, int pitch, int h0, int w0, f32x4 (&tmp)[6][6]) {
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        f32x4 d[6], v[6];
+        int wi = w0 + j;
+        bool okw = true;
+        if (PAD_MODE == 1) wi = wi < 0 ? -wi : (wi >= W ? 2 * W - 2 - wi : wi);
+        else okw = (unsigned)wi < (unsigned)W;
+        if (PAD_MODE == 1 && wi < 0) wi = 0;      // tiles hanging over the right/bottom edge (outputs dropped)
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            int hi = h0 + i;
+            bool ok = okw;
+            if (PAD_MODE == 1) { hi = hi < 0 ? -hi : (hi >= H ? 2 * H - 2 - hi : hi); if (hi < 0) hi = 0; }
+            else ok = ok && ((unsigned)hi < (unsigned)H);
+            d[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            if (ok) d[i] = *reinterpret_cast<const f32x4*>(src + ((size_t)hi * W + wi) * pitch);
+        }
+        bt6v(d, v);
+#pragma unroll
+        for (int i = 0; i < 6; ++i) tmp[i][j] = v[i];
+    }
+}
+// (The A^T column pass over a tile's 36 products stays a loop of its own in k_wino_out, k_wino_out_in and k_wino_fused: as one
+// shared function it reorders the fp sequence of k_wino_out_in and makes k_wino_fused's 32 x 64 forms spill 20 bytes.)
+
 }  // namespace ffr

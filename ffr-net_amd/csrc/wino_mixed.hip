@@ -247,13 +247,14 @@ __device__ __forceinline__ void fused_mixed_body(const WinoMixedArgs& a, int tau
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     const int tid = threadIdx.x;
+    const ConvTail& e = a.tail;
     const int nkc = a.nkc;
     const int n0 = nb * 64;
     unsigned long long st0 = 0, st1 = 0, st2 = 0, st3 = 0, sr0 = 0;      // trace build (option wf_trace): shader-clock stamps of the phases
     if (FFR_TRACE_ON(a.trace)) { st0 = __builtin_amdgcn_s_memtime(); sr0 = __builtin_amdgcn_s_memrealtime(); }
     float* const s_bias = smem + WF_EPI_FLOATS;
     int* const s_tile = reinterpret_cast<int*>(s_bias + 9 * 64);     // [4]: tile-sum slot
-    wf_fill_bias<NT>(s_bias, a.bias, a.border_bias, a.cout_pad, n0);
+    wf_fill_bias<NT>(s_bias, e.bias, e.border_bias, e.cout_pad, n0);
     if (tid < 32) {
         const long long t = (long long)mb * 32 + tid;
         const bool valid = t < a.T[tau];
@@ -262,12 +263,12 @@ __device__ __forceinline__ void fused_mixed_body(const WinoMixedArgs& a, int tau
         wf_tile_record(s_tile + tid * 8, valid, n, r0, c0, MR, MC, a.H, a.W);
         // tile-sum slot: image n owns tpi_total consecutive slots, the tile types in the order (4,4), (4,3), (3,4), (3,3) (tpi_off),
         // the tiles of a type in raster order of that type's own grid (q).  plan_conv sends only whole channel quads here
-        // (cout_store % 4 == 0), so a quad is stored and summed entirely or not at all (its sums are 0): ConvCall::tile_sums
+        // (cout_store % 4 == 0), so a quad is stored and summed entirely or not at all (its sums are 0): ConvTail::tile_sums
         s_tile[tid * 8 + 4] = valid ? n * a.tpi_total + a.tpi_off[tau] + q : 0;
     }
     f32x16 acc[8][NT], accv[NT];
     wf_zero_acc<NT>(acc, accv);
-    wf_vfed_gemm<S, NT>(a.V[tau], a.U[tau], mb, nb, nkc, a.cout_pad, wave, lane, acc, accv, a.trace, st1);
+    wf_vfed_gemm<S, NT>(a.V[tau], a.U[tau], mb, nb, nkc, e.cout_pad, wave, lane, acc, accv, a.trace, st1);
     if (FFR_TRACE_ON(a.trace)) st2 = __builtin_amdgcn_s_memtime();
 
     // ---- epilogue: two passes of 32 channels through E[xi][tile][32] in LDS (as k_wino_fused), transforms per tile type ----
@@ -293,9 +294,9 @@ __device__ __forceinline__ void fused_mixed_body(const WinoMixedArgs& a, int tau
             }
             const int cl = nt * 32 + 4 * cq;
             const int cg = n0 + cl;
-            const f32x4 slope = wf_slope(a.slope, cg);
+            const f32x4 slope = tail_slope4(e.slope, cg);
             int rc[MR], cc[MC];
-            if (a.border_bias) {
+            if (e.border_bias) {
                 wf_border_offsets(s_tile[tl * 8 + 2], 3 * 64, rc);
                 wf_border_offsets(s_tile[tl * 8 + 3], 64, cc);
             } else {
@@ -305,23 +306,23 @@ __device__ __forceinline__ void fused_mixed_body(const WinoMixedArgs& a, int tau
                 for (int i = 0; i < MC; ++i) cc[i] = 0;
             }
             f32x4 psum = {0.f, 0.f, 0.f, 0.f};
-            if (cg + 3 < a.cout_store) {
-                float* const ob = a.out + (size_t)pix0 * a.out_pitch + a.out_coff + cg;
-                const float* const rb = a.resid ? a.resid + (size_t)pix0 * a.res_pitch + cg : nullptr;
+            if (cg + 3 < e.cout_store) {
+                float* const ob = e.out + (size_t)pix0 * e.out_pitch + e.out_coff + cg;
+                const float* const rb = e.resid ? e.resid + (size_t)pix0 * e.res_pitch + cg : nullptr;
 #pragma unroll
                 for (int i = 0; i < MR; ++i) {
                     f32x4 yr[MC];
                     atq<AC>(tmp[i], yr);
 #pragma unroll
                     for (int jj = 0; jj < MC; ++jj) {
-                        const f32x4 v = wf_pointwise(yr[jj], *reinterpret_cast<const f32x4*>(s_bias + rc[i] + cc[jj] + cl), slope, rb != nullptr,
-                                                     [&] { return *reinterpret_cast<const f32x4*>(rb + (size_t)(i * a.W + jj) * a.res_pitch); }, a.flags);
-                        *reinterpret_cast<f32x4*>(ob + (size_t)(i * a.W + jj) * a.out_pitch) = v;
+                        const f32x4 v = tail4<PRELU_MINMAX>(yr[jj], *reinterpret_cast<const f32x4*>(s_bias + rc[i] + cc[jj] + cl), slope, rb != nullptr,
+                                                            [&] { return *reinterpret_cast<const f32x4*>(rb + (size_t)(i * a.W + jj) * e.res_pitch); }, e.flags);
+                        *reinterpret_cast<f32x4*>(ob + (size_t)(i * a.W + jj) * e.out_pitch) = v;
                         psum += v;
                     }
                 }
             }
-            if (a.tile_sums) wf_store_tile_sum(a.tile_sums, s_tile[tl * 8 + 4], a.cout_pad, cg, psum);
+            if (e.tile_sums) tail_store_tile_sum(e.tile_sums, s_tile[tl * 8 + 4], e.cout_pad, cg, psum);
         }
         __syncthreads();
         if (FFR_TRACE_ON(a.trace) && nt == 0) st3 = __builtin_amdgcn_s_memtime();
@@ -366,12 +367,13 @@ hipError_t wino_mixed_init() {
 
 // a.V[0] = base of the four V regions (laid out by wino_mixed_v_floats), a.U[tau] set by the caller
 hipError_t launch_wino_fused_mixed(WinoMixedArgs a, hipStream_t stream) {
-    if (a.cout_pad % 64 || a.nkc < 2 || !wino_mixed_geom(a.H, a.W, &a.g)) return hipErrorInvalidValue;
-    if (((a.out_pitch | a.out_coff | a.res_pitch | a.cout_store) & 3) != 0) return hipErrorInvalidValue;
+    const ConvTail& e = a.tail;
+    if (e.cout_pad % 64 || a.nkc < 2 || !wino_mixed_geom(a.H, a.W, &a.g)) return hipErrorInvalidValue;
+    if (((e.out_pitch | e.out_coff | e.res_pitch | e.cout_store) & 3) != 0) return hipErrorInvalidValue;
     size_t off[4];
     wino_mixed_v_floats(a.g, a.N, a.nkc * 8, off);
     wino_mixed_counts(a.g, a.N, a.T, a.mbn);
-    a.nbn = a.cout_pad / 64;
+    a.nbn = e.cout_pad / 64;
     const float* vbase = a.V[0];
     int tpi = 0;
     for (int tau = 0; tau < 4; ++tau) {
@@ -381,7 +383,7 @@ hipError_t launch_wino_fused_mixed(WinoMixedArgs a, hipStream_t stream) {
         tpi += nr * nc;
     }
     a.tpi_total = tpi;
-    const int tot = wino_mixed_blocks_launched(a.N, a.H, a.W, a.cout_pad);
+    const int tot = wino_mixed_blocks_launched(a.N, a.H, a.W, e.cout_pad);
     a.half_blocks = tot / 2;
     hipLaunchKernelGGL(k_wino_fused_mixed, dim3(tot), dim3(256), WM_LDS_BYTES, stream, a);
     return hipGetLastError();

@@ -13,6 +13,7 @@
 //   (igemm)   :  M[xi][T][cout_pad] = V[xi][T][cin_pad] * U[xi][cout_pad][cin_pad]^T, xi = 0..35
 //   k_wino_out:  M -> out[N,H,W,out_pitch] with the conv epilogue (border-class bias, PReLU,
 //                residual, sigmoid)
+#include "conv_tail.h"
 #include "device_util.h"
 #include "ffr_kernels.h"
 #include "wino_math.h"
@@ -27,10 +28,9 @@ __device__ __forceinline__ void wino_item(long long idx, int cq, int tw, int th,
         const unsigned i = (unsigned)idx;
         const unsigned tt = i / (unsigned)cq;
         *c4 = (int)(i - tt * (unsigned)cq) * 4;
-        const unsigned tpi = (unsigned)(tw * th);
-        const unsigned nn = tt / tpi, tr = tt - nn * tpi;
-        const unsigned y = tr / (unsigned)tw;
-        *t = tt; *n = nn; *ty = (int)y; *tx = (int)(tr - y * (unsigned)tw);
+        int nn;
+        wino_tile_of(tt, th, tw, &nn, ty, tx);
+        *t = tt; *n = nn;
     } else {
         const long long tt = idx / cq;
         *c4 = (int)(idx - tt * cq) * 4;
@@ -54,28 +54,7 @@ __global__ __launch_bounds__(256) void k_wino_in(const float* __restrict__ x, fl
     const int h0 = ty * 4 - 1, w0 = tx * 4 - 1;
     const float* xn = x + (size_t)n * H * W * pitch + c4;
     f32x4 tmp[6][6];
-    // columns first: for every patch column j, transform the 6 rows
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        f32x4 d[6], v[6];
-        int wi = w0 + j;
-        bool okw = true;
-        if (PAD_MODE == 1) wi = wi < 0 ? -wi : (wi >= W ? 2 * W - 2 - wi : wi);
-        else okw = (unsigned)wi < (unsigned)W;
-        if (PAD_MODE == 1 && wi < 0) wi = 0;      // tiles hanging over the right/bottom edge (outputs dropped)
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-            int hi = h0 + i;
-            bool ok = okw;
-            if (PAD_MODE == 1) { hi = hi < 0 ? -hi : (hi >= H ? 2 * H - 2 - hi : hi); if (hi < 0) hi = 0; }
-            else ok = ok && ((unsigned)hi < (unsigned)H);
-            d[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            if (ok) d[i] = *reinterpret_cast<const f32x4*>(xn + ((size_t)hi * W + wi) * pitch);
-        }
-        bt6v(d, v);
-#pragma unroll
-        for (int i = 0; i < 6; ++i) tmp[i][j] = v[i];
-    }
+    wino_gather_bt_cols<PAD_MODE>(xn, H, W, pitch, h0, w0, tmp);      // columns first, then the rows
     float* vout = V + (size_t)t * cin_pad + c4;
     const size_t plane = (size_t)T * cin_pad;
 #pragma unroll
@@ -87,22 +66,17 @@ __global__ __launch_bounds__(256) void k_wino_in(const float* __restrict__ x, fl
     }
 }
 
-struct WinoOutArgs {
-    const float* M; const float* bias; const float* slope; const float* resid; float* out; float* tile_sums;
-    int N, H, W, cout_pad, cout_store, out_pitch, out_coff, res_pitch, border_bias, flags, th, tw;
-    long long T;
-};
-
 __global__ __launch_bounds__(256) void k_wino_out(const WinoOutArgs a) {
-    const int cq = a.cout_pad >> 2;
+    const ConvTail& e = a.tail;
+    const int cq = e.cout_pad >> 2;
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= a.T * cq) return;
     long long t, nl; int c4, tx, ty;
     wino_item(idx, cq, a.tw, a.th, &t, &c4, &tx, &ty, &nl);
     const int n = (int)nl;
-    const float* min = a.M + (size_t)t * a.cout_pad + c4;
-    const size_t plane = (size_t)a.T * a.cout_pad;
     f32x4 tmp[4][6];      // A^T applied to the columns: [out row][j]
+    const float* min = a.M + (size_t)t * e.cout_pad + c4;
+    const size_t plane = (size_t)a.T * e.cout_pad;
 #pragma unroll
     for (int j = 0; j < 6; ++j) {
         f32x4 m[6], y[4];
@@ -112,9 +86,8 @@ __global__ __launch_bounds__(256) void k_wino_out(const WinoOutArgs a) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) tmp[i][j] = y[i];
     }
-    const bool vec = ((a.out_pitch | a.out_coff | a.res_pitch) & 3) == 0 && c4 + 4 <= a.cout_store;
-    f32x4 slope4 = {1.f, 1.f, 1.f, 1.f};
-    if (a.slope) slope4 = *reinterpret_cast<const f32x4*>(a.slope + c4);
+    const bool vec = ((e.out_pitch | e.out_coff | e.res_pitch) & 3) == 0 && c4 + 4 <= e.cout_store;
+    const f32x4 slope4 = tail_slope4(e.slope, c4);
     f32x4 psum = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -122,39 +95,33 @@ __global__ __launch_bounds__(256) void k_wino_out(const WinoOutArgs a) {
         at6t(tmp[i], y);
         const int oh = ty * 4 + i;
         if (oh >= a.H) continue;
-        const int rc = !a.border_bias ? 0 : (oh == 0 ? 0 : (oh == a.H - 1 ? 2 : 1));
+        const int rc = !e.border_bias ? 0 : border_class(oh, a.H);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int ow = tx * 4 + j;
             if (ow >= a.W) continue;
-            const int cls = !a.border_bias ? 0 : rc * 3 + (ow == 0 ? 0 : (ow == a.W - 1 ? 2 : 1));
-            f32x4 v = y[j] + *reinterpret_cast<const f32x4*>(a.bias + (size_t)cls * a.cout_pad + c4);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = v[e] >= 0.f ? v[e] : v[e] * slope4[e];
+            const int cls = !e.border_bias ? 0 : rc * 3 + border_class(ow, a.W);
+            const f32x4 bias4 = *reinterpret_cast<const f32x4*>(e.bias + (size_t)cls * e.cout_pad + c4);
+            const f32x4 act = tail_act4<PRELU_SELECT>(y[j], bias4, slope4);      // once, in front of the branch
             const size_t m = ((size_t)n * a.H + oh) * a.W + ow;
             if (vec) {
-                if (a.resid) v += *reinterpret_cast<const f32x4*>(a.resid + m * a.res_pitch + c4);
-                if (a.flags & 1) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = 1.0f / (1.0f + __expf(-v[e]));
-                }
-                *reinterpret_cast<f32x4*>(a.out + m * a.out_pitch + a.out_coff + c4) = v;
+                const f32x4 v = tail_end4(act, e.resid != nullptr,
+                                          [&] { return *reinterpret_cast<const f32x4*>(e.resid + m * e.res_pitch + c4); }, e.flags);
+                *reinterpret_cast<f32x4*>(e.out + m * e.out_pitch + e.out_coff + c4) = v;
                 psum += v;
             } else {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    if (c4 + e < a.cout_store) {
-                        float s = v[e];
-                        if (a.resid) s += a.resid[m * a.res_pitch + c4 + e];
-                        if (a.flags & 1) s = 1.0f / (1.0f + __expf(-s));
-                        a.out[m * a.out_pitch + a.out_coff + c4 + e] = s;
-                        psum[e] += s;         // tile sums are the sums of what was stored, on this path too (ConvCall::tile_sums)
+                for (int c = 0; c < 4; ++c) {
+                    if (c4 + c < e.cout_store) {
+                        const float s = tail_end1(act[c], e.resid != nullptr, [&] { return e.resid[m * e.res_pitch + c4 + c]; }, e.flags);
+                        e.out[m * e.out_pitch + e.out_coff + c4 + c] = s;
+                        psum[c] += s;         // tile sums are the sums of what was stored, on this path too (ConvTail::tile_sums)
                     }
                 }
             }
         }
     }
-    if (a.tile_sums) *reinterpret_cast<f32x4*>(a.tile_sums + (size_t)t * a.cout_pad + c4) = psum;
+    if (e.tile_sums) tail_store_tile_sum(e.tile_sums, t, e.cout_pad, c4, psum);
 }
 
 // U[xi][o][i] = (G g G^T)[xi] of the 3x3 filter g = W[o][0..8][i]  (W [out_pad][9][in_pad], tap = r*3+s).
@@ -316,12 +283,6 @@ hipError_t launch_wino_in(const float* x, float* V, int N, int H, int W, int pit
 // transform of conv1 (bias by border class, PReLU) into an LDS image, phase 2 the input transform of conv2 (zero
 // padding) out of it.  M1[36][T][C] -> V2[36][T][C]; the activation itself is never written (only conv2 reads it,
 // pretrain/model_ir_se50.py:66-70).
-struct WinoOutInArgs {
-    const float* M; const float* bias; const float* slope; float* V;
-    int H, W, C, th, tw, border_bias;
-    long long T;
-};
-
 template <int TILES>      // tiles per image: 16 (up to 16x16) or 4 (up to 8x8)
 __global__ __launch_bounds__(256) void k_wino_out_in(const WinoOutInArgs a) {
     constexpr int QUADS = 256 / TILES;            // channel quads per block
@@ -335,8 +296,8 @@ __global__ __launch_bounds__(256) void k_wino_out_in(const WinoOutInArgs a) {
     const long long t = (long long)n * a.th * a.tw + tl;
     const size_t plane = (size_t)a.T * a.C;
     if (live) {
-        const float* min = a.M + (size_t)t * a.C + c4;
         f32x4 tmp[4][6];
+        const float* min = a.M + (size_t)t * a.C + c4;
 #pragma unroll
         for (int j = 0; j < 6; ++j) {
             f32x4 m[6], y[4];
@@ -346,46 +307,28 @@ __global__ __launch_bounds__(256) void k_wino_out_in(const WinoOutInArgs a) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) tmp[i][j] = y[i];
         }
-        f32x4 slope4 = {1.f, 1.f, 1.f, 1.f};
-        if (a.slope) slope4 = *reinterpret_cast<const f32x4*>(a.slope + c4);
+        const f32x4 slope4 = tail_slope4(a.slope, c4);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             f32x4 y[4];
             at6t(tmp[i], y);
             const int oh = ty * 4 + i;
             if (oh >= a.H) continue;
-            const int rc = !a.border_bias ? 0 : (oh == 0 ? 0 : (oh == a.H - 1 ? 2 : 1));
+            const int rc = !a.border_bias ? 0 : border_class(oh, a.H);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int ow = tx * 4 + j;
                 if (ow >= a.W) continue;
-                const int cls = !a.border_bias ? 0 : rc * 3 + (ow == 0 ? 0 : (ow == a.W - 1 ? 2 : 1));
-                f32x4 v = y[j] + *reinterpret_cast<const f32x4*>(a.bias + (size_t)cls * a.C + c4);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = v[e] >= 0.f ? v[e] : v[e] * slope4[e];
-                *reinterpret_cast<f32x4*>(act + ((size_t)oh * a.W + ow) * CB + q * 4) = v;
+                const int cls = !a.border_bias ? 0 : rc * 3 + border_class(ow, a.W);
+                *reinterpret_cast<f32x4*>(act + ((size_t)oh * a.W + ow) * CB + q * 4) =
+                    tail_act4<PRELU_SELECT>(y[j], *reinterpret_cast<const f32x4*>(a.bias + (size_t)cls * a.C + c4), slope4);
             }
         }
     }
     __syncthreads();
     if (!live) return;
-    const int h0 = ty * 4 - 1, w0 = tx * 4 - 1;
     f32x4 tmp[6][6];
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        f32x4 d[6], v[6];
-        const int wi = w0 + j;
-        const bool okw = (unsigned)wi < (unsigned)a.W;
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-            const int hi = h0 + i;
-            d[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            if (okw && (unsigned)hi < (unsigned)a.H) d[i] = *reinterpret_cast<const f32x4*>(act + ((size_t)hi * a.W + wi) * CB + q * 4);
-        }
-        bt6v(d, v);
-#pragma unroll
-        for (int i = 0; i < 6; ++i) tmp[i][j] = v[i];
-    }
+    wino_gather_bt_cols<0>(act + q * 4, a.H, a.W, CB, ty * 4 - 1, tx * 4 - 1, tmp);
     float* vout = a.V + (size_t)t * a.C + c4;
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
@@ -421,17 +364,12 @@ hipError_t launch_wino_out_in(const float* M, const float* bias, const float* sl
     return hipGetLastError();
 }
 
-hipError_t launch_wino_out(const float* M, const float* bias, const float* slope, const float* resid, int res_pitch,
-                           float* out, int out_pitch, int out_coff, int cout_store, int cout_pad, int N, int H, int W,
-                           int border_bias, int flags, hipStream_t stream, float* tile_sums) {
+hipError_t launch_wino_out(const float* M, const ConvTail& tail, int N, int H, int W, hipStream_t stream) {
     WinoOutArgs a;
-    a.tile_sums = tile_sums;
-    a.M = M; a.bias = bias; a.slope = slope; a.resid = resid; a.out = out;
-    a.N = N; a.H = H; a.W = W; a.cout_pad = cout_pad; a.cout_store = cout_store; a.out_pitch = out_pitch;
-    a.out_coff = out_coff; a.res_pitch = res_pitch; a.border_bias = border_bias; a.flags = flags;
+    a.M = M; a.tail = tail; a.N = N; a.H = H; a.W = W;
     a.th = (H + 3) / 4; a.tw = (W + 3) / 4;
     a.T = (long long)N * a.th * a.tw;
-    const long long total = a.T * (cout_pad >> 2);
+    const long long total = a.T * (tail.cout_pad >> 2);
     hipLaunchKernelGGL(k_wino_out, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, a);
     return hipGetLastError();
 }
