@@ -103,6 +103,13 @@ int run_trunk(ffr_handle* h, const Work& w, const float* x_nchw, int N, int H, i
         c.out = w.t1; c.out_pitch = b.depth; c.cout_store = b.depth;
         return c;
     };
+    // the plan record: one entry per glue launch, with the values the launch below it gets (include/ffrnet.h)
+    auto note = [&](int path, int rows, int tiles, int stride = 0, bool conv_sc = false, bool scaled = false) {
+        ffr_conv_launch r{};
+        r.path = path; r.images = N; r.rows = rows; r.tiles = tiles;
+        r.stride = stride; r.conv_shortcut = conv_sc; r.se_scale = scaled;
+        h->conv_log.push_back(r);
+    };
     bool v_ready = false, v_mixed = false;  // winoV holds the transform of `cur` in the order k_wino_fused (/ k_wino_fused_mixed) streams
     for (int i = 0; i < n_blocks; ++i) {
         const Block& b = h->blocks[i];
@@ -119,6 +126,7 @@ int run_trunk(ffr_handle* h, const Work& w, const float* x_nchw, int N, int H, i
         RC(run_conv(h, b.c1, c1, st));
         if (chained) {
             Scope s(h, st, FFR_KC_WINO, 0, 4.0 * 72.0 * Tt * b.c1.cout_pad);
+            if (h->conv_rec) note(FFR_CP_WINO_OUT_IN, (int)Tt, ((ch + 3) / 4) * ((cw + 3) / 4));
             HIPCK(h, launch_wino_out_in(w.winoM, b.c1.bias, b.c1.slope, w.winoV, N, ch, cw, b.c1.cout_pad, b.c1.border, st));
         }
         ConvCall c2 = conv_call(w);
@@ -136,8 +144,13 @@ int run_trunk(ffr_handle* h, const Work& w, const float* x_nchw, int N, int H, i
         if (b.fc1) {
             const double e = (double)N * ho * wo * b.depth;
             Scope s(h, st, FFR_KC_SE, e + 4.0 * N * b.depth * (b.depth / 16), 4.0 * e);
-            if (pooled) HIPCK(h, launch_se_fc(w.se_part, N, tiles, ho * wo, b.depth, b.fc1, b.fc2, w.scale, st));
-            else HIPCK(h, launch_se(w.res, N, ho * wo, b.depth, b.fc1, b.fc2, w.scale, w.se_part, st));
+            if (pooled) {
+                if (h->conv_rec) note(FFR_CP_SE_TILES, ho * wo, tiles);
+                HIPCK(h, launch_se_fc(w.se_part, N, tiles, ho * wo, b.depth, b.fc1, b.fc2, w.scale, st));
+            } else {
+                if (h->conv_rec) note(FFR_CP_SE_POOL, ho * wo, se_slices(N, ho * wo));
+                HIPCK(h, launch_se(w.res, N, ho * wo, b.depth, b.fc1, b.fc2, w.scale, w.se_part, st));
+            }
             se_scale = w.scale;
         }
         const float* scp = nullptr;
@@ -160,12 +173,15 @@ int run_trunk(ffr_handle* h, const Work& w, const float* x_nchw, int N, int H, i
             WinoMixedGeom mg;
             wino_mixed_geom(ho, wo, &mg);
             Scope s(h, st, FFR_KC_COMBINE, 2.0 * e, 4.0 * (3.0 * e + (double)wino_mixed_v_floats(mg, N, b.depth, nullptr)));
+            if (h->conv_rec) note(FFR_CP_COMBINE_IN_MIXED, ho * wo, tiles, b.stride, scp != nullptr, se_scale != nullptr);
             HIPCK(h, launch_combine_in_mixed(w.res, se_scale, scp ? scp : cur, nxt, w.winoV, N, ho, wo, b.depth, st));
         } else if (v_ready) {
             Scope s(h, st, FFR_KC_COMBINE, 2.0 * e, 4.0 * (3.0 * e + 36.0 * N * ((ho + 3) / 4) * ((wo + 3) / 4) * b.depth));
+            if (h->conv_rec) note(FFR_CP_COMBINE_IN_C, ho * wo, tiles, b.stride, scp != nullptr, se_scale != nullptr);
             HIPCK(h, launch_combine_in_c(w.res, se_scale, scp ? scp : cur, nxt, w.winoV, N, ho, wo, b.depth, st));
         } else {
             Scope s(h, st, FFR_KC_COMBINE, 2.0 * e, 12.0 * e);
+            if (h->conv_rec) note(FFR_CP_COMBINE, ho * wo, tiles, b.stride, scp != nullptr, se_scale != nullptr);
             HIPCK(h, launch_combine(w.res, se_scale, scp, cur, nxt, N, ho, wo, b.depth, b.stride, st));
         }
         float* t = cur; cur = nxt; nxt = t;

@@ -73,10 +73,11 @@ class Conv3x3Desc(C.Structure):
 
 class ConvLaunch(C.Structure):
     _fields_ = [(f, C.c_int) for f in ('path', 'images', 'rows', 'tile', 'nblocks', 'granule', 'nkt', 'tiles', 'cut', 'split',
-                                       'phased', 'half_n', 'block_tiles', 'n_main', 'side')]
+                                       'phased', 'half_n', 'block_tiles', 'n_main', 'side', 'stride', 'conv_shortcut', 'se_scale')]
 
 
-CONV_PATHS = ('direct', 'fused', 'unfused-gemm-stream', 'unfused-igemm', 'mixed', 'tail-split', 'channel')
+CONV_PATHS = ('direct', 'fused', 'unfused-gemm-stream', 'unfused-igemm', 'mixed', 'tail-split', 'channel', 'se-pool', 'se-tiles',
+              'combine', 'combine-in-c', 'combine-in-mixed', 'wino-out-in')
 WGRAD_PATHS = ('plain-taps9', 'plain-taps1', 'batched')
 ARITH = {'direct': 0, 'winograd': 1}
 CALIB_TENSORS = ('f', 'featmap', 'f_new', 'feat_new')
@@ -1023,7 +1024,10 @@ class Engine(object):
     def conv_plan(self):
         """The convolution launches since conv_plan_record(True), in launch order: [{path ('direct' | 'fused' |
         'unfused-gemm-stream' | 'unfused-igemm' | 'mixed' | 'tail-split' | 'channel' = RecNet's k_channel_path), images, rows, tile, nblocks, granule, nkt, tiles, cut,
-        split, phased, half_n, block_tiles, n_main, side}] (include/ffrnet.h: ffr_conv_launch)."""
+        split, phased, half_n, block_tiles, n_main, side, stride, conv_shortcut, se_scale}] (include/ffrnet.h: ffr_conv_launch).
+        The encoder trunk adds its glue launches: 'se-pool' | 'se-tiles' (SE squeeze by its own pass | from tile sums: rows = H*W,
+        tiles = S), 'combine' | 'combine-in-c' | 'combine-in-mixed' (one per bottleneck, its last entry: rows = H*W, tiles per
+        image, stride, conv_shortcut, se_scale) and 'wino-out-in' (the chained conv1 -> conv2 transform: rows = T, tiles per image)."""
         n = C.c_int(0)
         self._ck(self.lib.ffr_conv_plan_read(self._h, None, 0, C.byref(n)))
         arr = (ConvLaunch * max(n.value, 1))()
@@ -1237,7 +1241,8 @@ class Engine(object):
     def train_adam_step(self, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, clip_value=1.0):
         self._call(self.lib.ffr_train_adam_step, lr, betas[0], betas[1], eps, weight_decay, clip_value)
 
-    def encoder_trunk_nhwc(self, x, n_blocks):
+    def encoder_trunk_nhwc(self, x, n_blocks, out=None):
+        """Stem + the first n_blocks bottlenecks -> the NHWC activation (test hook); `out` = a preallocated result."""
         self._tensor(x, 'x')
         x = x.contiguous()
         n, _, h, w = x.shape
@@ -1245,7 +1250,12 @@ class Engine(object):
         from .synth import ir_blocks
         for cin, depth, stride in ir_blocks(getattr(self, 'num_layers', 50))[:n_blocks]:
             chans, div = depth, div * stride
-        out = self._empty(n, h // div, w // div, chans)
+        if out is None:
+            out = self._empty(n, h // div, w // div, chans)
+        else:
+            self._tensor(out, 'out', shape=(n, h // div, w // div, chans))
+            if not out.is_contiguous():
+                raise RuntimeError('ffrnet_amd: out must be contiguous')
         self._call(self.lib.ffr_encoder_trunk_nhwc, _ptr(x), n, h, w, n_blocks, _ptr(out))
         return out
 

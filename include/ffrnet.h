@@ -691,14 +691,26 @@ int ffr_op_conv3x3_ex(ffr_handle* h, const ffr_conv3x3_desc* d, void* stream);
  *   phased, half_n, split, block_tiles   k_wino_fused: in-kernel input transform, 32 x 32 blocks, split-operand K loop, block tiles
  *   n_main, side   FFR_CP_TAIL_SPLIT: images that run fused; 1 when the remainder went to the second stream
  * RecNet's channel launch is recorded too, as FFR_CP_CHANNEL (k_channel_path): images = N, nblocks = N x row blocks per image
- * (1 / 2 / 4 = k_channel_path<4 / 2 / 1>), rows = the rows of M_channel one block evaluates (512 / row blocks). */
+ * (1 / 2 / 4 = k_channel_path<4 / 2 / 1>), rows = the rows of M_channel one block evaluates (512 / row blocks).
+ * The encoder trunk records the launches between its convolutions as well, one entry each, where it makes them (a bottleneck
+ * ends with exactly one combine entry).  images = N in all of them:
+ *   FFR_CP_SE_POOL    SE squeeze by its own pooling pass (k_se_pool + k_se_fc): rows = H*W of the pooled map, tiles = slices S
+ *   FFR_CP_SE_TILES   SE squeeze from conv2's Winograd tile sums (k_se_fc alone): rows = H*W, tiles = S = tiles per image
+ *   FFR_CP_COMBINE | FFR_CP_COMBINE_IN_C | FFR_CP_COMBINE_IN_MIXED   k_combine | k_combine_in_c | k_combine_in_mixed (the latter
+ *           two also write V for the next conv1): rows = H*W of the output map, tiles = its 4x4 tiles per image, stride = the
+ *           bottleneck's, conv_shortcut = 1 when the shortcut is a convolution's output (0: the input itself, subsampled by
+ *           stride), se_scale = 1 when an SE scale is applied (0 in mode 'ir')
+ *   FFR_CP_WINO_OUT_IN   conv1 -> conv2 chained transform (k_wino_out_in): rows = Winograd tiles T, tiles = tiles per image
+ *           (<= 4: the 256-channel block form, else the 64-channel one) */
 enum { FFR_CP_DIRECT = 0, FFR_CP_FUSED = 1, FFR_CP_UNFUSED_STREAM = 2, FFR_CP_UNFUSED_IGEMM = 3, FFR_CP_MIXED = 4, FFR_CP_TAIL_SPLIT = 5,
-       FFR_CP_CHANNEL = 6 };
+       FFR_CP_CHANNEL = 6, FFR_CP_SE_POOL = 7, FFR_CP_SE_TILES = 8, FFR_CP_COMBINE = 9, FFR_CP_COMBINE_IN_C = 10,
+       FFR_CP_COMBINE_IN_MIXED = 11, FFR_CP_WINO_OUT_IN = 12 };
 typedef struct ffr_conv_launch {
     int path, images, rows;
     int tile, nblocks, granule, nkt, tiles, cut, split;
     int phased, half_n, block_tiles;
     int n_main, side;
+    int stride, conv_shortcut, se_scale;
 } ffr_conv_launch;
 int ffr_conv_plan_record(ffr_handle* h, int on);
 int ffr_conv_plan_read(ffr_handle* h, ffr_conv_launch* out, int cap, int* n);
