@@ -1,5 +1,5 @@
 """Grouping unlabelled embeddings into identities (include/ffrnet.h: ffr_cluster_threshold, ffr_cluster_extend,
-ffr_cluster_remove, ffr_cluster_density, ffr_cluster_templates).
+ffr_cluster_remove, ffr_cluster_density, ffr_cluster_density_extend, ffr_cluster_density_remove, ffr_cluster_templates).
 
 A photo collection or a dump of video tracks arrives as N unlabelled faces; before the first Gallery.add they have to be
 grouped by person and every group fused into one template row:
@@ -30,7 +30,7 @@ pairs that involve a new row are scored, and the result is the clustering of all
 Rows are taken out again the same way (ffr_cluster_remove): a deleted photo, an expired track, a withdrawn enrolment.  A
 cluster that loses no row keeps its label; the survivors of a cluster that loses one are joined again among themselves
 (it may fall apart when the row that bridged two people goes), and only their pairs are scored.  The result is the
-clustering of the remaining rows, label for label.  Single link only: there is no removal from a density-gated clustering.
+clustering of the remaining rows, label for label.
 
   old_to_new = store.remove(rows)                    # compacts; renumber side tables through the map
   c, old_to_new, kept = cluster.remove(engine, f, threshold, c, rows=rows)      # the functional form; f is not touched
@@ -41,6 +41,12 @@ extension needs kept beside the labels; after every add the result is density() 
   store = cluster.IncrementalDensity(engine, threshold, min_rows=4)
   store.add(f_batch)
   t = store.templates()                              # one row per cluster with a core: what gets enrolled
+
+and rows leave it again (ffr_cluster_density_remove): degrees fall, core rows may be demoted, border rows choose again, and
+afterwards the labels and the state are those of density() over the rows still held, so add() and remove() interleave:
+
+  old_to_new = store.remove(rows)                    # a sliding window: the oldest frames expire
+  c, state, old_to_new, kept = cluster.density_remove(engine, f, threshold, 4, state, rows=rows)    # the functional form
 """
 import collections
 
@@ -104,7 +110,7 @@ def changes(rep_before, rep_after):
     show up in neither.  This is for single link (extend, Incremental) only: it relies on an old row's rep never rising
     and on clusters changing by absorption alone.  A density-gated clustering keeps neither promise (a border row may
     change sides); use density_changes there.  A removal (remove, Incremental.remove) breaks both as well: clusters
-    split and representatives rise; use removal_changes there."""
+    split and representatives rise; use removal_changes there (density_removal_changes for a density-gated one)."""
     rep_before, rep_after = torch.as_tensor(rep_before).reshape(-1), torch.as_tensor(rep_after).reshape(-1)
     n = rep_before.numel()
     if rep_after.numel() < n:
@@ -179,7 +185,7 @@ def remove(engine, emb, threshold, earlier, rows=None, keep=None, must_link=None
     only the pairs among the survivors of the clusters that lost a row are scored.  Give exactly one of rows (indices to
     remove, duplicates allowed) and keep (mask of the rows that stay).  must_link: integer labels of all N rows (track ids)
     the clustering was made with; surviving rows with equal labels stay in one cluster whatever they score.  emb is not
-    touched: compact it with emb[kept].  Single link only; there is no removal from a density-gated clustering."""
+    touched: compact it with emb[kept].  Single link only; a density-gated clustering has density_remove."""
     rep = earlier.rep if isinstance(earlier, Clusters) else torch.as_tensor(earlier)
     rep = rep.reshape(-1).to(device=emb.device, dtype=torch.int64)
     n = emb.size(0)
@@ -382,11 +388,89 @@ def density_changes(before, after):
     return gone, torch.unique(torch.cat((old[~same], after[n:])))
 
 
+def _rekey(best, old_to_new):
+    """Keys best[.] int64 whose core rows survive -> the same keys with the core row (0xFFFFFFFF minus the low word)
+    renumbered through old_to_new; the score bits in the high word are untouched, 0 stays 0."""
+    has = best != 0
+    core = torch.where(has, 0xFFFFFFFF - (best & 0xFFFFFFFF), torch.zeros_like(best))
+    return torch.where(has, (best & ~0xFFFFFFFF) | (0xFFFFFFFF - old_to_new[core]), best)
+
+
+def density_remove(engine, emb, threshold, min_rows, earlier, rows=None, keep=None, norms=None):
+    """Take rows out of a density-gated clustering of emb[N,512] -> (DensityClusters, DensityState, old_to_new int64[N] with
+    -1 for a removed row, kept int64[N_s]: the surviving rows, new-to-old).  Clusters and state are those of the survivors
+    in compact numbering, the keys of the state re-encoded: they equal density_extend(engine, emb[kept], threshold, min_rows)
+    when `earlier` is the DensityState of all N rows; it is left as it is.  Give exactly one of rows (indices to remove,
+    duplicates allowed) and keep (mask of the rows that stay).  emb is not touched: compact it with emb[kept].  A state made
+    with another threshold or min_rows is refused."""
+    threshold, min_rows = float(threshold), int(min_rows)
+    if float(earlier.threshold) != threshold or int(earlier.min_rows) != min_rows:
+        raise RuntimeError('ffrnet_amd: the state was made with threshold %r and min_rows %d; rows cannot be removed from it '
+                           'with %r and %d' % (earlier.threshold, earlier.min_rows, threshold, min_rows))
+    n = emb.size(0)
+    if earlier.rep.numel() != n:
+        raise RuntimeError('ffrnet_amd: a state of %d rows for %d embeddings' % (earlier.rep.numel(), n))
+    mask = _keep_mask(n, rows, keep, emb.device)
+    old_to_new, kept = _index_maps(mask)
+    rep, kind, degree, best = engine.cluster_density_remove(emb, threshold, min_rows, earlier.rep.clone(), earlier.degree.clone(),
+                                                            earlier.best.clone(), mask, norms=norms)
+    rep, kind, degree, best = old_to_new[rep[kept]], kind[kept], degree[kept], _rekey(best[kept], old_to_new)
+    return density_ids(rep, kind), DensityState(rep, kind, degree, best, threshold, min_rows), old_to_new, kept
+
+
+def density_removal_changes(before, after):
+    """What a removal did to the clusters of a density-gated clustering: -> (drop, compute), both int64, ascending, in the
+    numbering BEFORE the removal.  before, after: rep tensors of the same N rows, or anything with a .rep; after as
+    Engine.cluster_density_remove returns it (same numbering, -1 for a removed row).  drop: the representatives of `before`
+    whose cluster lost a row or whose survivors are not exactly the members of one cluster of `after`.  compute: the
+    representatives of `after` whose members are not exactly the members of one cluster of `before`.  A caller that keeps
+    one template per cluster drops those of `drop` and computes those of `compute`; every other cluster kept its rows and
+    its label.
+
+    removal_changes() is not enough here: it looks at the clusters that lost a row only, but a border row whose core row
+    was removed or demoted may move to ANOTHER cluster, which lost nothing and changes all the same."""
+    before = torch.as_tensor(getattr(before, 'rep', before)).reshape(-1).to(torch.int64)
+    after = torch.as_tensor(getattr(after, 'rep', after)).reshape(-1).to(device=before.device, dtype=torch.int64)
+    n = before.numel()
+    if after.numel() != n:
+        raise ValueError('density_removal_changes: %d labels before, %d after' % (n, after.numel()))
+    stay = after >= 0
+    b, a = before[stay], after[stay]
+    lost = torch.zeros((n,), device=before.device, dtype=torch.bool)
+    lost[before[~stay]] = True
+
+    def spread(key, value):
+        """per row: do all rows with this row's key carry one value?"""
+        lo = torch.full((n,), n, device=key.device, dtype=torch.int64).scatter_reduce_(0, key, value, 'amin')
+        hi = torch.full((n,), -1, device=key.device, dtype=torch.int64).scatter_reduce_(0, key, value, 'amax')
+        return lo[key] == hi[key]
+
+    # a cluster kept its members iff it lost none, they are in one cluster of `after`, and that one holds nothing else
+    changed = lost[b] | ~(spread(a, b) & spread(b, a))
+    return torch.unique(torch.cat((before[~stay], b[changed]))), torch.unique(a[changed])
+
+
+# IncrementalDensity.remove: the removal scores at least r * n pairs (the r removed rows against everything held), clustering
+# the ns survivors again scores ns * (ns - 1).  The removal is taken iff r * n <= REMOVE_PAIR_RATIO * ns * (ns - 1).  Measured
+# (tools/bench_cluster_density_remove.py, EXPERIMENTS.md): at r * n / (ns * (ns - 1)) <= 0.444 the removal was 1.5 x to 290 x
+# faster than clustering again, at 2.0 (half of the rows leave) 1.6 x slower; the plain pair-count rule, 1.0, sends no
+# measured shape to the slower route.
+REMOVE_PAIR_RATIO = 1.0
+
+
+def density_remove_route(n, ns):
+    """The route IncrementalDensity.remove takes for n rows held of which ns survive -> 'remove' or 'recluster'."""
+    return 'remove' if (n - ns) * n <= REMOVE_PAIR_RATIO * ns * (ns - 1) else 'recluster'
+
+
 class IncrementalDensity(object):
     """A density-gated clustering that keeps being added to: embeddings [n,512], their norms and the state (rep, kind,
     degree, best) on the Engine's device, in grow-only buffers (as Incremental).  After every add() the labels are those of
-    density() over all rows held.  Rows keep their index for ever; unlike Incremental, the rep of an old row can also rise
-    (density_changes tells which templates to drop and which to compute)."""
+    density() over all rows held.  Between removals rows keep their index; unlike Incremental, the rep of an old row can
+    also rise (density_changes tells which templates to drop and which to compute).  remove() takes rows out, compacts the
+    buffers and returns the old-to-new index map; afterwards labels and state are those of density() over the rows still
+    held, so add() goes on as before (density_removal_changes, on the labels before compaction, tells which templates to
+    drop and compute)."""
 
     def __init__(self, engine, threshold, min_rows, capacity=0):
         engine._min_rows(min_rows, 'IncrementalDensity')
@@ -453,6 +537,38 @@ class IncrementalDensity(object):
             self._kind[:total] = kind
             self._n = total
         return first
+
+    def remove(self, rows, route=None):
+        """Take the rows with these indices out (any integer sequence or tensor; duplicates allowed) and compact all six
+        buffers in order -> old_to_new int64[n]: the new index of every row held before, -1 for a removed one.  Afterwards
+        labels and state are those of density() over the rows still held, and add() works as before.  Two routes leave the
+        identical state: the removal (Engine.cluster_density_remove, then compaction with the keys re-encoded), and
+        compaction followed by clustering the survivors from scratch.  Unlike single link, the removal can lose: it scores
+        the removed rows against everything.  route: None chooses by density_remove_route; 'remove' / 'recluster' force one."""
+        n = self._n
+        keep = _keep_mask(n, rows, None, self._rep.device)
+        old_to_new, kept = _index_maps(keep)
+        ns = kept.numel()
+        if route is None:
+            route = density_remove_route(n, ns)
+        if route not in ('remove', 'recluster'):
+            raise ValueError("ffrnet_amd: route must be 'remove' or 'recluster', got %r" % (route,))
+        if ns == n:
+            return old_to_new
+        if ns and route == 'remove':
+            rep, kind, degree, best = self.engine.cluster_density_remove(
+                self._emb[:n], self.threshold, self.min_rows, self._rep[:n], self._degree[:n], self._best[:n], keep,
+                norms=self._norms[:n], validate=False)
+            rep, kind, degree, best = old_to_new[rep[kept]], kind[kept], degree[kept], _rekey(best[kept], old_to_new)
+        self._emb[:ns] = self._emb[:n][kept]
+        self._norms[:ns] = self._norms[:n][kept]
+        if ns and route == 'recluster':
+            rep, kind, degree, best = self.engine.cluster_density_extend(
+                self._emb[:ns], self.threshold, self.min_rows, None, None, None, 0, norms=self._norms[:ns], validate=False)
+        if ns:
+            self._rep[:ns], self._kind[:ns], self._degree[:ns], self._best[:ns] = rep, kind, degree, best
+        self._n = ns
+        return old_to_new
 
 
 def member_order(clusters):

@@ -1,8 +1,8 @@
 // cluster.hip -- group N unlabelled 512-d embeddings into identities on the device (include/ffrnet.h:
 // ffr_cluster_threshold / ffr_cluster_extend / ffr_cluster_remove / ffr_cluster_density / ffr_cluster_density_extend /
-// ffr_cluster_templates): single-link clustering at one cosine threshold, or gated by density over the same edges (core rows
-// link, border rows attach, noise stays alone), either of them extended batch by batch where the collection grows, single
-// link also with rows taken out again, then one template row per cluster.  The N x N score matrix never leaves the
+// ffr_cluster_density_remove / ffr_cluster_templates): single-link clustering at one cosine threshold, or gated by density
+// over the same edges (core rows link, border rows attach, noise stays alone), either of them extended batch by batch where
+// the collection grows and with rows taken out again, then one template row per cluster.  The N x N score matrix never leaves the
 // chip; the output is one label per row.
 //
 // Edge rule: rows i < j are joined iff s(probe = i, gallery row = j) > threshold (strict, as eval_acc compares), with
@@ -106,6 +106,40 @@
 //    "List walk" below; its own part: an edge is a uf_unite between two core rows, or the same single 64-bit max into
 //    best[y] of an old non-core row y < n_old, with a promoted row p < n_old in the key: a core row of [0, N), as
 //    k_density_root needs.
+//  - Density, removal (ffr_cluster_density_remove): keep[x] = 0 takes row x out of a density-gated clustering whose state (rep,
+//    degree, best) the caller holds for all N rows; nothing moves.  need = min_rows - 1, g(x) as in "Removal" below, was_core(x)
+//    = degree_in[x] >= need.  The result and the state left behind are those of ffr_cluster_density over the survivors.
+//      k_drem_init / k_drem_removed_list   counts, hit[] and coremin[] cleared, deg0[] = the old degrees, a removed row's degree
+//                   0; R[0 .. r) = the removed rows.
+//      k_list_walk<WalkFall>   all rows as probes against R: degree[x] -= 1 for a surviving x per removed neighbour.  Integer
+//                   adds commute.  Degrees count all neighbours, core or not, so a demotion takes nothing from anyone: no cascade.
+//      k_drem_status   core(x) = survivor with degree[x] >= need, a subset of the old core rows (degrees only fell).  LOST =
+//                   was core, now removed or demoted; hit[g(x)] = 1 for a lost x.  Removing a border or a noise row hits nothing.
+//      k_drem_seed_lists / k_dext_parent   a core row of a hit label goes into L[0 .. m) with parent[x] = x; a core row of an
+//                   unhit label hangs under the smallest core row with its rep (the coremin seed of the extension; in an unhit
+//                   cluster every core row survived and stayed core, so its core component is the old one); every other row
+//                   starts alone.  best[] of core and removed rows is zeroed.  A non-core survivor keeps its key iff the key's
+//                   core row survives and is still core; else -- every demoted row, every border row whose chosen core row was
+//                   lost -- it goes into Q[0 .. q) with key 0.  A noise row that was not core stays noise and is not listed.
+//      k_list_walk<WalkRemove>   the pairs of L by list position, every edge a uf_unite: all listed rows are core.
+//      k_list_walk<WalkRekey>    all rows as probes against Q: a surviving core probe c adjacent to a listed y offers
+//                   best_key(score, c) to best[y], the 64-bit max of the gated join.
+//      k_density_root / k_density_min / k_density_label   as above; a removed row is alone in root[] (nothing points at it, it is
+//                   smaller than no root) and is labelled rep -1, kind 0; its degree and key are 0 already.
+//    Equality: compacting the survivors is a monotone renumbering, so "the smallest row" (roots, rep, the tie-break of a key)
+//    and "the smaller index is the probe" carry over.  Degrees: the old degree minus the edges to removed rows is the degree
+//    among the survivors.  Core components: the edges among still-core rows of unhit labels are exactly the old ones, kept by
+//    the seed; a hit label's still-core rows are joined again over all their pairs, and no edge runs between core rows of two
+//    old clusters.  Keys: a kept key is the maximum over a set of offers that shrank but still holds its maximum; a key looked
+//    for again is the maximum over all surviving core neighbours, as from scratch; a demoted row had key 0 and is in Q.  The
+//    walks score (probe, listed row) in either role; the bits are those of the triangle by "Transposed pairs" above.
+//    Safety: caller data reaches an index only through g(x) in [0, x] (hit[], coremin[]) and through best_core(key), which is
+//    used only after c < N is tested; a key is kept only if it names a surviving core row of [0, N), so k_density_root follows
+//    a key only to a row of the union-find.  A negative degree reads as 0, on entry and after the fall.  parent[x] is x, or
+//    coremin[rep[x]] <= x, the minimum x took part in itself (depth 1), so every walk descends.  The three lists are filled by
+//    one fetch-add per wave without a retry loop (wave_list_push), each row at most once per list, so their counts are <= N;
+//    the walks read them as min(*count, N), fixed at entry ("List walk" below).  The fall and the offers are single no-return
+//    vector atomics; nothing waits on another wave.  An empty R (nothing removed) or Q is one early return per block.
 //  - Removal (ffr_cluster_remove; single link only): keep[x] = 0 takes row x out; nothing moves, labels stay in the caller's
 //    numbering.  g(x) = rep_in[x] where 0 <= rep_in[x] <= x, else x.  A cluster that loses no row had no edge to any other
 //    cluster and removing rows adds none: it keeps its label.  A cluster that loses a row (its label is HIT) may fall apart:
@@ -130,20 +164,21 @@
 //    The slot reservation of k_remove_list is one fetch-add per wave without a retry loop; the flatten reads m once and
 //    clamps it to N as the walk does ("List walk" below).  m = 0 (nothing removed, or only whole clusters) scores nothing.
 //  - List walk (k_list_walk<P>; P = WalkPromoted: the old rows [0, n_old) as probes against the promoted rows P, every pair
-//    but (p, p); P = WalkRemove: the listed rows against themselves, the pairs of list positions a < b).  One body: work
+//    but (p, p); P = WalkFall, WalkRekey: the same orientation, all N rows against the lists of the density removal;
+//    P = WalkRemove: the listed rows against themselves, the pairs of list positions a < b).  One body: work
 //    items of (tile of 32 probes, span of 128-row steps of the list) under a fixed grid, the listed rows gathered through
 //    CosineStreamT<GatherRows> (and, as probes, cosine_fill_probes_gather), the tile, chain sum and score of k_cluster_walk.
 //    m: the list's length lives in device memory (the host never learns it); every block reads it once and reads it as at
 //    most `bound`, the number of rows that can be listed (n_old, N), so every loop is bounded by a value fixed at entry,
 //    whatever the cell holds.  Slots: list[] is written only by the kernel that builds it (k_dext_promoted_list,
-//    k_remove_list), earlier in stream order; a row is listed once, by its own thread, so m <= bound, the slots [0, m) are
+//    k_remove_list, k_drem_removed_list, k_drem_seed_lists), earlier in stream order; a row is listed once, by its own thread, so m <= bound, the slots [0, m) are
 //    all written and none past them is.  Rows: every slot holds the listing thread's own row, < bound <= N, and a probe is
 //    either such a row or a position below n_old <= N: every index into emb, norm, degree, best and parent is < N.  Pads:
 //    the walk reads list[] only at positions below m; the probes of a tile past its end are zeros, the slots of a span
 //    past its end repeat its last listed row, in bounds, and the edge test masks both (n < nq, slot < ns): never an edge.
 //    No wave waits on another: the barriers sit in the item loop, whose trip count and first `continue` depend on m, the
 //    grid and the block index alone (uniform in a block); a wave with no live slot in a span skips the K loop after the
-//    barriers; the edges are uf_unite or one no-return 64-bit max; vector atomics only.
+//    barriers; the edges are uf_unite, one no-return 64-bit max or one no-return integer add; vector atomics only.
 // k_cluster_flatten  rep[i] = find(i) as int64, after the join in stream order.
 // k_cluster_templates  one template per cluster: t = sum_r x_r / |x_r| over the cluster's rows in ascending row index
 //                (order[] = rows sorted by cluster then index, offsets[C + 1]), then t / |t|.  One wave per cluster, lane
@@ -416,12 +451,19 @@ __global__ __launch_bounds__(256) void k_density_min(const int* __restrict__ roo
     if (x < n && x < root[x]) __hip_atomic_fetch_min(minrow + root[x], x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// keep: null, or the rows that are still there
 __global__ __launch_bounds__(256) void k_density_label(const int* __restrict__ root, const int* __restrict__ minrow,
                                                        const int* __restrict__ degree, const unsigned long long* __restrict__ best,
-                                                       int min_rows, int n, int64_t* __restrict__ rep, uint8_t* __restrict__ kind,
+                                                       int min_rows, int n, const uint8_t* __restrict__ keep,
+                                                       int64_t* __restrict__ rep, uint8_t* __restrict__ kind,
                                                        int32_t* __restrict__ degree_out) {
     const int x = blockIdx.x * 256 + threadIdx.x;
     if (x >= n) return;
+    if (keep && !keep[x]) {              // ffr_cluster_density_remove: a removed row (its degree and best are 0 already)
+        rep[x] = -1;
+        kind[x] = 0;
+        return;
+    }
     const int d = degree[x];
     rep[x] = minrow[root[x]];
     kind[x] = d >= min_rows - 1 ? 2 : best[x] ? 1 : 0;
@@ -473,13 +515,16 @@ __global__ __launch_bounds__(256) void k_dext_coremin(const int64_t* __restrict_
 }
 
 // Seed 3 of 3, old rows: an old core row hangs under the smallest old core row of its rep (itself at the least: it took
-// part in the minimum, so 0 <= coremin[rep[x]] <= x); every other row starts alone.
+// part in the minimum, so 0 <= coremin[rep[x]] <= x); every other row starts alone.  The removal seeds through the same
+// kernel: deg0 = the degrees after the fall, and only a surviving row (keep) whose label is not hit took part in coremin[].
 __global__ __launch_bounds__(256) void k_dext_parent(const int64_t* __restrict__ rep, const int* __restrict__ deg0,
-                                                     const int* __restrict__ coremin, int* __restrict__ parent, int need, int n_old) {
+                                                     const int* __restrict__ coremin, const uint8_t* __restrict__ keep,
+                                                     const int* __restrict__ hit, int* __restrict__ parent, int need, int n_old) {
     const int x = blockIdx.x * 256 + threadIdx.x;
     if (x >= n_old) return;
     const int64_t r = rep[x];
-    parent[x] = (deg0[x] >= need && dx_rep_ok(r, x)) ? coremin[r] : x;
+    const bool seeded = deg0[x] >= need && dx_rep_ok(r, x) && (!keep || (keep[x] && !hit[r]));
+    parent[x] = seeded ? coremin[r] : x;
 }
 
 // P[0 .. m) = the old rows the new rows made core, in any order; their keys are void from here on.  m <= n_old: a row
@@ -491,6 +536,19 @@ __global__ __launch_bounds__(256) void k_dext_promoted_list(const int* __restric
     if (x >= n_old || deg0[x] >= need || degree[x] < need) return;
     best[x] = 0;
     plist[__hip_atomic_fetch_add(pcount, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)] = x;
+}
+
+// list[slot] = x for the lanes with `listed`, the slots taken from *count: one fetch-add per wave reserves the wave's slots,
+// no retry loop; the order of the list is whatever the waves' atomics make it.  Called by all 64 lanes of the wave.  A row
+// is listed once per list, by its own thread, so every slot is below the number of rows.
+__device__ __forceinline__ void wave_list_push(bool listed, int x, int* __restrict__ list, int* __restrict__ count) {
+    const unsigned long long b = __ballot(listed);
+    if (!b) return;
+    const int lane = threadIdx.x & 63, leader = __builtin_ctzll(b);
+    int base = 0;
+    if (lane == leader) base = __hip_atomic_fetch_add(count, __builtin_popcountll(b), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    base = __shfl(base, leader);
+    if (listed) list[base + __builtin_popcountll(b & ((1ull << lane) - 1))] = x;
 }
 
 // ---- ffr_cluster_remove: see "Removal" in the header ----
@@ -520,12 +578,11 @@ __global__ __launch_bounds__(256) void k_remove_mark(const int64_t* __restrict__
 
 // Removed rows and unaffected survivors get their label here.  An affected survivor is listed and seeded: parent[x] =
 // prior[x] where that is a row of [0, x] that is itself an affected survivor (it is then listed by its own thread), else x.
-// One atomic per wave reserves the wave's slots; the order of the list is whatever the waves' atomics make it.
 __global__ __launch_bounds__(256) void k_remove_list(const int* __restrict__ glabel, const int* __restrict__ hit,
                                                      const uint8_t* __restrict__ keep, const int64_t* __restrict__ prior,
                                                      int* __restrict__ parent, int* __restrict__ list, int* __restrict__ mcount,
                                                      int64_t* __restrict__ rep, int n) {
-    const int x = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63;
+    const int x = blockIdx.x * 256 + threadIdx.x;
     bool listed = false;
     int p = x;
     if (x < n) {
@@ -541,16 +598,78 @@ __global__ __launch_bounds__(256) void k_remove_list(const int* __restrict__ gla
             }
         }
     }
-    const unsigned long long b = __ballot(listed);
-    if (!b) return;
-    const int leader = __builtin_ctzll(b);
-    int base = 0;
-    if (lane == leader) base = __hip_atomic_fetch_add(mcount, __builtin_popcountll(b), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    base = __shfl(base, leader);
-    if (listed) {
-        parent[x] = p;
-        list[base + __builtin_popcountll(b & ((1ull << lane) - 1))] = x;         // < m <= n: a row is listed once
+    if (listed) parent[x] = p;
+    wave_list_push(listed, x, list, mcount);                 // slot < m <= n: a row is listed once
+}
+
+// ---- ffr_cluster_density_remove: see "Density, removal" in the header ----
+
+constexpr int DR_REMOVED = 0, DR_REJOIN = 1, DR_REKEY = 2;       // counts[]: the lengths r, m, q of the lists R, L, Q
+
+// The three lists start empty, no label is hit, no rep has a core minimum.  deg0[] keeps the old degrees, read as >= 0 (the
+// status needs them after the walk has taken from degree[]); a removed row's degree is 0 from here on.
+__global__ __launch_bounds__(256) void k_drem_init(const uint8_t* __restrict__ keep, int* __restrict__ degree,
+                                                   int* __restrict__ deg0, int* __restrict__ coremin, int* __restrict__ hit,
+                                                   int* __restrict__ counts, int n) {
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    if (x < 3) counts[x] = 0;
+    if (x >= n) return;
+    coremin[x] = DX_NONE;
+    hit[x] = 0;
+    const int d = max(degree[x], 0);
+    deg0[x] = d;
+    degree[x] = keep[x] ? d : 0;
+}
+
+// R[0 .. r) = the removed rows, in any order: what follows is integer adds
+__global__ __launch_bounds__(256) void k_drem_removed_list(const uint8_t* __restrict__ keep, int* __restrict__ rlist,
+                                                           int* __restrict__ counts, int n) {
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    wave_list_push(x < n && !keep[x], x, rlist, counts + DR_REMOVED);
+}
+
+// After the fall.  A wrong state can take a degree below 0: it is read as 0, as on entry.  LOST = a row that was core and
+// is no more, removed or demoted: its label is hit (every writer of a cell stores the same 1).
+__global__ __launch_bounds__(256) void k_drem_status(const int64_t* __restrict__ rep_in, const uint8_t* __restrict__ keep,
+                                                     const int* __restrict__ deg0, int* __restrict__ degree,
+                                                     int* __restrict__ hit, int need, int n) {
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    if (x >= n) return;
+    const int d = max(degree[x], 0);
+    degree[x] = d;
+    if (deg0[x] >= need && !(keep[x] && d >= need)) hit[rm_label(rep_in, x)] = 1;
+}
+
+// Seed 1 of 2 and the keys, on the final degrees and hit flags.  A removed row: key 0.  A core row: key 0; where its label
+// is hit it goes into L (its parent stays x: k_dext_parent), else it takes part in the core minimum of its rep, as in
+// k_dext_coremin.  A non-core survivor keeps its key iff that names a row of [0, n) that survives and is core; it goes
+// into Q, key 0, if its key is void or if it was core itself (a demoted row never had a key).  A row with no key that was
+// not core is noise and stays noise: its core neighbours can only have become fewer.
+__global__ __launch_bounds__(256) void k_drem_seed_lists(const int64_t* __restrict__ rep_in, const uint8_t* __restrict__ keep,
+                                                         const int* __restrict__ deg0, const int* __restrict__ degree,
+                                                         const int* __restrict__ hit, unsigned long long* __restrict__ best,
+                                                         int* __restrict__ coremin, int* __restrict__ llist,
+                                                         int* __restrict__ qlist, int* __restrict__ counts, int need, int n) {
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    bool rejoin = false, rekey = false;
+    if (x < n) {
+        if (!keep[x]) {
+            best[x] = 0;
+        } else if (degree[x] >= need) {
+            best[x] = 0;
+            const int64_t r = rep_in[x];
+            if (hit[rm_label(rep_in, x)]) rejoin = true;
+            else if (dx_rep_ok(r, x)) __hip_atomic_fetch_min(coremin + r, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        } else {
+            const unsigned long long key = best[x];
+            const unsigned c = best_core(key);
+            const bool holds = key && c < (unsigned)n && keep[c] && degree[c] >= need;
+            rekey = deg0[x] >= need || (key && !holds);
+            if (rekey) best[x] = 0;
+        }
     }
+    wave_list_push(rejoin, x, llist, counts + DR_REJOIN);
+    wave_list_push(rekey, x, qlist, counts + DR_REKEY);
 }
 
 // ---- k_list_walk: see "List walk" in the header ----
@@ -563,12 +682,13 @@ struct ListArgs {
     int* parent;              // [N]
     const int* list;          // the first *count entries are set, each a row < bound
     const int* count;
-    int bound;                // *count is read as at most this: N (removal), n_old (promoted pass)
+    int bound;                // *count is read as at most this: N (the removals), n_old (promoted pass)
     float threshold;
-    // the promoted pass only
-    const int* degree;        // [N], final
+    // the promoted pass and the two walks of the density removal only
+    int* degree;              // [N]; final but for the fall, which takes from it
     unsigned long long* best; // [N]
     int need;
+    const uint8_t* keep;      // [N], the density removal only
 };
 
 // What differs between the two walks over a list; the item loop is k_list_walk's.
@@ -582,17 +702,19 @@ struct ListArgs {
 // Promoted pass (ffr_cluster_density_extend): the probes are the old rows [0, n_old) themselves and every pair but (p, p)
 // counts.  The listed row is always core, so an edge is a unite when the probe is core and an offer of the listed row to
 // best[probe] when it is not.  One step per item: two blocks share a CU.
-struct WalkPromoted {
-    static constexpr int SPAN_STEPS = 1, BLOCKS_PER_CU = 2;
+struct ProbesAreRows {           // the orientation: the probes are the rows [0, bound) themselves, every pair but (p, p) counts
     static constexpr bool TRIANGLE = false;
-    bool pcore;
-    __device__ __forceinline__ WalkPromoted(const ListArgs& a, int irow, bool live) : pcore(live && a.degree[irow] >= a.need) {}
     static __device__ __forceinline__ int probes(const ListArgs& a, int) { return a.bound; }
     static __device__ __forceinline__ int probe_row(const ListArgs&, int pos) { return pos; }
     static __device__ __forceinline__ void fill(f32x4* qf, const ListArgs& a, int q0, int nq, int tid) {
         cosine_fill_probes(qf, a.emb, q0, nq, tid);
     }
     static __device__ __forceinline__ bool pair(int, int, int irow, int jrow) { return jrow != irow; }
+};
+struct WalkPromoted : ProbesAreRows {
+    static constexpr int SPAN_STEPS = 1, BLOCKS_PER_CU = 2;
+    bool pcore;
+    __device__ __forceinline__ WalkPromoted(const ListArgs& a, int irow, bool live) : pcore(live && a.degree[irow] >= a.need) {}
     __device__ __forceinline__ void edge(const ListArgs& a, int irow, int jrow, float sc) const {
         if (pcore) uf_unite(a.parent, irow, jrow);
         else __hip_atomic_fetch_max(a.best + irow, best_key(sc, jrow), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -613,6 +735,31 @@ struct WalkRemove {
     }
     static __device__ __forceinline__ bool pair(int apos, int bpos, int, int) { return bpos > apos; }
     __device__ __forceinline__ void edge(const ListArgs& a, int irow, int jrow, float) const { uf_unite(a.parent, irow, jrow); }
+};
+
+// The two walks of ffr_cluster_density_remove, in the orientation of the promoted pass: all N rows are probes, the listed
+// rows come from R (the removed rows) and Q (the rows that choose again).  SPAN_STEPS and BLOCKS_PER_CU: EXPERIMENTS.md.
+// Degrees fall: a surviving probe adjacent to a listed removed row loses that edge.  Integer adds commute; a removed probe
+// is masked (its degree is 0 already).
+struct WalkFall : ProbesAreRows {
+    static constexpr int SPAN_STEPS = RM_SPAN_STEPS, BLOCKS_PER_CU = 1;
+    bool alive;
+    __device__ __forceinline__ WalkFall(const ListArgs& a, int irow, bool live) : alive(live && a.keep[irow]) {}
+    __device__ __forceinline__ void edge(const ListArgs& a, int irow, int, float) const {
+        if (alive) degree_add(a.degree + irow, -1);
+    }
+};
+
+// Keys again: a surviving core probe is offered to the listed row, which is a non-core survivor whose key was zeroed: the
+// one 64-bit max of the gated join, so the highest score wins, then the smallest core row, whatever the order.
+struct WalkRekey : ProbesAreRows {
+    static constexpr int SPAN_STEPS = RM_SPAN_STEPS, BLOCKS_PER_CU = 1;
+    bool pcore;
+    __device__ __forceinline__ WalkRekey(const ListArgs& a, int irow, bool live)
+        : pcore(live && a.keep[irow] && a.degree[irow] >= a.need) {}
+    __device__ __forceinline__ void edge(const ListArgs& a, int irow, int jrow, float sc) const {
+        if (pcore) __hip_atomic_fetch_max(a.best + jrow, best_key(sc, irow), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
 };
 
 // Probes against the rows of a list.  A work item is (tile of 32 probe positions, span of `spi` steps of 128 list positions);
@@ -798,12 +945,13 @@ hipError_t launch_cluster_extend(const float* emb, const float* norms, long long
     return hipSuccess;
 }
 
-// root, min, label: the end of both density launchers
+// root, min, label: the end of the three density launchers; keep: the removal's, else null
 static hipError_t density_finish(long long N, int min_rows, const int* parent, const int* degree, const unsigned long long* best,
-                                 int* root, int* minrow, int64_t* rep, uint8_t* kind, int32_t* degree_out, hipStream_t stream) {
+                                 const uint8_t* keep, int* root, int* minrow, int64_t* rep, uint8_t* kind, int32_t* degree_out,
+                                 hipStream_t stream) {
     LAUNCH(k_density_root, blocks_of(N), stream, parent, degree, best, min_rows, (int)N, root, minrow);
     LAUNCH(k_density_min, blocks_of(N), stream, root, (int)N, minrow);
-    LAUNCH(k_density_label, blocks_of(N), stream, root, minrow, degree, best, min_rows, (int)N, rep, kind, degree_out);
+    LAUNCH(k_density_label, blocks_of(N), stream, root, minrow, degree, best, min_rows, (int)N, keep, rep, kind, degree_out);
     return hipSuccess;
 }
 
@@ -818,7 +966,7 @@ hipError_t launch_cluster_density(const float* emb, const float* norms, long lon
         LAUNCH(k_cluster_walk<false, EdgesDegree>, grid, stream, a);
         LAUNCH(k_cluster_walk<false, EdgesGated>, grid, stream, a);
     }
-    return density_finish(N, min_rows, parent, degree, best, root, minrow, rep, kind, degree_out, stream);
+    return density_finish(N, min_rows, parent, degree, best, nullptr, root, minrow, rep, kind, degree_out, stream);
 }
 
 // the blocks loop over the items, which are counted on the device; two blocks of 64 KiB LDS fit a CU
@@ -837,7 +985,7 @@ hipError_t launch_cluster_density_extend(const float* emb, const float* norms, l
     LAUNCH(k_dext_init, blocks_of(N), stream, parent, degree, best, deg0, coremin, pcount, (int)N_old, (int)N);
     if (N_old > 0) {
         LAUNCH(k_dext_coremin, nbo, stream, rep, deg0, best, coremin, need, (int)N_old);
-        LAUNCH(k_dext_parent, nbo, stream, rep, deg0, coremin, parent, need, (int)N_old);
+        LAUNCH(k_dext_parent, nbo, stream, rep, deg0, coremin, nullptr, nullptr, parent, need, (int)N_old);
     }
     if (N > 1 && N_old < N) {
         const JoinArgs a{emb, norms, parent, N, chunk_rows, threshold, nchunks, ntiles, N_old, degree, best, min_rows};
@@ -850,7 +998,7 @@ hipError_t launch_cluster_density_extend(const float* emb, const float* norms, l
             LAUNCH(k_list_walk<WalkPromoted>, (unsigned)promoted_grid, stream, p);
         }
     }
-    return density_finish(N, min_rows, parent, degree, best, root, minrow, rep, kind, nullptr, stream);
+    return density_finish(N, min_rows, parent, degree, best, nullptr, root, minrow, rep, kind, nullptr, stream);
 }
 
 hipError_t launch_cluster_remove(const float* emb, const float* norms, long long N, float threshold, int walk_grid,
@@ -866,6 +1014,31 @@ hipError_t launch_cluster_remove(const float* emb, const float* norms, long long
     }
     LAUNCH(k_remove_flatten, blocks_of(N), stream, parent, list, mcount, (int)N, rep);
     return hipSuccess;
+}
+
+hipError_t launch_cluster_density_remove(const float* emb, const float* norms, long long N, float threshold, int min_rows,
+                                         int walk_grid, const uint8_t* keep, int* parent, int* deg0, int* coremin, int* hit,
+                                         int* root, int* minrow, int* rlist, int* llist, int* qlist, int* counts, int64_t* rep,
+                                         uint8_t* kind, int32_t* degree, unsigned long long* best, hipStream_t stream) {
+    if (N <= 0) return hipSuccess;
+    const unsigned nb = blocks_of(N), grid = (unsigned)walk_grid;
+    const int need = min_rows - 1, n = (int)N;
+    LAUNCH(k_drem_init, nb, stream, keep, degree, deg0, coremin, hit, counts, n);
+    LAUNCH(k_drem_removed_list, nb, stream, keep, rlist, counts, n);
+    if (N > 1) {
+        const ListArgs fall{emb, norms, nullptr, rlist, counts + DR_REMOVED, n, threshold, degree, nullptr, need, keep};
+        LAUNCH(k_list_walk<WalkFall>, grid, stream, fall);
+    }
+    LAUNCH(k_drem_status, nb, stream, rep, keep, deg0, degree, hit, need, n);
+    LAUNCH(k_drem_seed_lists, nb, stream, rep, keep, deg0, degree, hit, best, coremin, llist, qlist, counts, need, n);
+    LAUNCH(k_dext_parent, nb, stream, rep, degree, coremin, keep, hit, parent, need, n);
+    if (N > 1) {
+        const ListArgs rejoin{emb, norms, parent, llist, counts + DR_REJOIN, n, threshold, nullptr, nullptr, 0, nullptr};
+        LAUNCH(k_list_walk<WalkRemove>, grid, stream, rejoin);
+        const ListArgs rekey{emb, norms, nullptr, qlist, counts + DR_REKEY, n, threshold, degree, best, need, keep};
+        LAUNCH(k_list_walk<WalkRekey>, grid, stream, rekey);
+    }
+    return density_finish(N, min_rows, parent, degree, best, keep, root, minrow, rep, kind, nullptr, stream);
 }
 
 hipError_t launch_cluster_templates(const float* emb, const float* norms, const int64_t* order, const int64_t* offsets,

@@ -488,9 +488,9 @@ int ffr_search_topk_coarse_subjects(ffr_handle* h, const float* query, int Q, co
 }
 
 // ---- clustering (cluster.hip) ----------------------------------------------------------------------------------------
-// What the five clustering entries check and plan alike.  The pairs an entry walks with k_cluster_walk:
+// What the six clustering entries check and plan alike.  The pairs an entry walks with k_cluster_walk:
 enum ClusterPairs {
-    PAIRS_NONE,     // none (the removal walks a list)
+    PAIRS_NONE,     // none (the removals walk lists)
     PAIRS_ALL,      // every pair i < j: cluster_plan
     PAIRS_NEW       // the pairs with a row >= N_old: N_old is an argument, cluster_extend_plan
 };
@@ -651,6 +651,35 @@ int ffr_cluster_density_extend(ffr_handle* h, const float* emb, const float* nor
     HIPCK(h, launch_cluster_density_extend(emb, norms, N_old, N, threshold, min_rows, p.T, p.S, p.chunk_rows,
                                            cluster_list_grid(N_old, h->num_cus), parent, deg0, coremin, root, minrow, plist, pcount,
                                            rep, kind, degree, best, st));
+    return FFR_OK;
+}
+
+int ffr_cluster_density_remove(ffr_handle* h, const float* emb, const float* norms, long long N, int dim, float threshold,
+                               int min_rows, const uint8_t* keep, int64_t* rep, uint8_t* kind, int32_t* degree,
+                               unsigned long long* best, void* stream) {
+    FFR_DEVICE_SCOPE(h);
+    ClusterPre p;
+    RC(cluster_pre(h, "ffr_cluster_density_remove", PAIRS_NONE, emb, norms, 0, N, dim, threshold, &min_rows,
+                   !keep || !rep || !kind || !degree || !best, "emb / keep / rep / kind / degree / best",
+                   {{rep, 7}, {best, 7}, {degree, 3}}, "rep and best 8, degree and norms 4", &p));
+    if (p.empty) return FFR_OK;
+    hipStream_t st = (hipStream_t)stream;
+    // scratch: row norms [N] (used when the caller passes none), parent, the old degrees, the per-rep core minimum, the hit
+    // flags, root, minrow and the three lists [N] ints each, and the lists' counts; degree and best are the caller's state
+    float* own_norms = nullptr;
+    int *parent = nullptr, *deg0 = nullptr, *coremin = nullptr, *hit = nullptr, *root = nullptr, *minrow = nullptr, *rlist = nullptr,
+        *llist = nullptr, *qlist = nullptr, *counts = nullptr;
+    RC(carve(h, h->cluster, "clustering", [&](Arena& a) {
+        own_norms = a.take(N); parent = a.take<int>(N); deg0 = a.take<int>(N); coremin = a.take<int>(N); hit = a.take<int>(N);
+        root = a.take<int>(N); minrow = a.take<int>(N); rlist = a.take<int>(N); llist = a.take<int>(N); qlist = a.take<int>(N);
+        counts = a.take<int>(3);
+    }));
+    // the pairs scored, (r + q) N + m (m - 1) / 2, are counted on the device only: 0 flops are recorded; bytes: the state in
+    // and out, keep, kind, and the N-sized scratch written and read
+    Scope s(h, st, FFR_KC_SCORE, 0.0, 114.0 * (double)N);
+    RC(cluster_norms(h, p, emb, N, own_norms, st, &norms));
+    HIPCK(h, launch_cluster_density_remove(emb, norms, N, threshold, min_rows, cluster_list_grid(N, h->num_cus), keep, parent, deg0,
+                                           coremin, hit, root, minrow, rlist, llist, qlist, counts, rep, kind, degree, best, st));
     return FFR_OK;
 }
 

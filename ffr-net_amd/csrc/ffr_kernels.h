@@ -338,7 +338,7 @@ hipError_t launch_cluster_density(const float* emb, const float* norms, long lon
                                   int nchunks, long long chunk_rows, int* parent, int* degree, int* root, int* minrow,
                                   unsigned long long* best, int64_t* rep, uint8_t* kind, int32_t* degree_out, hipStream_t stream);
 // blocks of a walk over a list of at most `rows` rows (the promoted pass of launch_cluster_density_extend, rows = N_old;
-// the pair walk of launch_cluster_remove, rows = N): a fixed grid, the work is counted on the device
+// the walks of launch_cluster_remove and launch_cluster_density_remove, rows = N): a fixed grid, the work is counted on the device
 int cluster_list_grid(long long rows, int num_cus);
 // launch_cluster_density over all N rows, from the state (rep, degree, best) of the first N_old: seed, degree walk and gated
 // walk over the pairs with a new row (the plan is cluster_extend_plan's), the old rows they made core listed in plist[*pcount],
@@ -355,6 +355,16 @@ hipError_t launch_cluster_density_extend(const float* emb, const float* norms, l
 hipError_t launch_cluster_remove(const float* emb, const float* norms, long long N, float threshold, int walk_grid,
                                  const int64_t* rep_in, const int64_t* prior, const uint8_t* keep, int* parent, int* glabel, int* hit,
                                  int* list, int* mcount, int64_t* rep, hipStream_t stream);
+// rows with keep[x] = 0 leave a density-gated clustering whose state (rep, degree, best) the caller holds for all N rows:
+// init, the removed rows listed in rlist, the walk that takes their edges from degree[], status (hit labels), seed and the
+// lists llist (still-core rows of hit labels) and qlist (non-core survivors that choose again), the pair walk over llist,
+// the walk that offers the core rows to qlist, then root, min, label.  rep, degree, best [N] in and out, kind [N] out; a
+// removed row gets -1 / 0 / 0 / 0.  Scratch: parent, deg0, coremin, hit, root, minrow, rlist, llist, qlist N ints each,
+// counts 3 ints; walk_grid = cluster_list_grid(N)
+hipError_t launch_cluster_density_remove(const float* emb, const float* norms, long long N, float threshold, int min_rows,
+                                         int walk_grid, const uint8_t* keep, int* parent, int* deg0, int* coremin, int* hit,
+                                         int* root, int* minrow, int* rlist, int* llist, int* qlist, int* counts, int64_t* rep,
+                                         uint8_t* kind, int32_t* degree, unsigned long long* best, hipStream_t stream);
 // templates[c] = normalised sum of the normalised rows order[offsets[c] .. offsets[c+1]); norms may be null
 hipError_t launch_cluster_templates(const float* emb, const float* norms, const int64_t* order, const int64_t* offsets,
                                     long long C, float* templates, hipStream_t stream);

@@ -131,6 +131,7 @@ SYMBOLS = [
     ('ffr_cluster_remove', C.c_int, [_P, _P, _P, C.c_longlong, C.c_int, C.c_float, _P, _P, _P, _P, _P]),
     ('ffr_cluster_density', C.c_int, [_P, _P, _P, C.c_longlong, C.c_int, C.c_float, C.c_int, _P, _P, _P, _P]),
     ('ffr_cluster_density_extend', C.c_int, [_P, _P, _P, C.c_longlong, C.c_longlong, C.c_int, C.c_float, C.c_int, _P, _P, _P, _P, _P]),
+    ('ffr_cluster_density_remove', C.c_int, [_P, _P, _P, C.c_longlong, C.c_int, C.c_float, C.c_int, _P, _P, _P, _P, _P, _P]),
     ('ffr_align_transforms', C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, _P]),
     ('ffr_align_warp', C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_longlong, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
     ('ffr_embed_aligned', C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_longlong, _P, _P, _P, C.c_int, _P, C.c_int, _P, _P, _P,
@@ -637,6 +638,13 @@ class Engine(object):
         if n_old < 0 or n_old > N:
             raise RuntimeError('ffrnet_amd: %s needs 0 <= n_old <= %d, got %d' % (who, N, n_old))
 
+    def _keep_mask(self, keep, N):
+        """keep[N], device bool or uint8 -> contiguous"""
+        if not isinstance(keep, torch.Tensor) or keep.dtype not in (torch.bool, torch.uint8):
+            raise RuntimeError('ffrnet_amd: keep must be a bool or uint8 tensor')
+        self._tensor(keep, 'keep', keep.dtype, (N,))
+        return keep.contiguous()
+
     def cluster(self, emb, threshold, norms=None):
         """Single-link clustering of emb[N,512] (device fp32) at one cosine threshold: rows i < j are joined iff their
         search score is > threshold -> rep[N] int64, rep[i] = the smallest row index of i's cluster.  norms[N]:
@@ -680,16 +688,13 @@ class Engine(object):
         those survivors are scored.  A label may rise (the representative was removed, or the cluster split).  prior[N]
         (device int64): must-links, prior[i] <= i the first SURVIVING row of i's tie group.  The kernels read an entry of rep
         or prior outside [0, i] as i; `validate` range-checks both here first (one small sync) and raises.  out: the result
-        tensor, rep itself allowed.  Single link only: there is no removal from a density-gated clustering."""
+        tensor, rep itself allowed.  Single link only: a density-gated clustering has cluster_density_remove."""
         emb, norms = self._cluster_rows(emb, norms, 'cluster_remove')
         rep_in = self._index_tensor(rep, 'rep')
         N = emb.size(0)
         if rep_in.numel() != N:
             raise RuntimeError('ffrnet_amd: rep must be [%d], got %s' % (N, list(rep_in.shape)))
-        if not isinstance(keep, torch.Tensor) or keep.dtype not in (torch.bool, torch.uint8):
-            raise RuntimeError('ffrnet_amd: keep must be a bool or uint8 tensor')
-        self._tensor(keep, 'keep', keep.dtype, (N,))
-        keep = keep.contiguous()
+        keep = self._keep_mask(keep, N)
         if prior is not None:
             prior = self._index_tensor(prior, 'prior')
             if prior.numel() != N:
@@ -751,6 +756,35 @@ class Engine(object):
         kind = self._empty(N, dtype=torch.uint8)
         self._call(self.lib.ffr_cluster_density_extend, _ptr(emb if N else None), _ptr(norms), n_old, N, emb.size(1),
                    float(threshold), int(min_rows), _ptr(rep if N else None), _ptr(kind if N else None),
+                   _ptr(degree if N else None), _ptr(best if N else None))
+        return rep, kind, degree, best
+
+    def cluster_density_remove(self, emb, threshold, min_rows, rep, degree, best, keep, norms=None, validate=True):
+        """Take rows out of a density-gated clustering: emb[N,512] holds all rows; rep (int64), degree (int32) and best
+        (int64), each [N], are the state cluster_density_extend left for them at this threshold and min_rows; keep[N] (device
+        bool or uint8) is nonzero for the rows that stay.  Nothing is moved -> (rep, kind, degree, best), all [N], in the same
+        numbering; contiguous state tensors are updated in place.  On the surviving rows the result is, once compacted,
+        cluster_density(emb[keep], ..., return_degree=True), and best (its core rows renumbered) the state of
+        cluster_density_extend over emb[keep] from scratch; a removed row gets -1 / 0 / 0 / 0.  A label may rise and a border
+        row may change its cluster.  Scored are the removed rows against all rows, the pairs among the still-core rows of the
+        clusters that lost a core row, and the rows that have to choose a core row again against all rows.  The kernels read
+        out-of-range state as "none"; `validate` range-checks it here first (check_density_state, one small sync)."""
+        emb, norms = self._cluster_rows(emb, norms, 'cluster_density_remove')
+        self._min_rows(min_rows, 'cluster_density_remove')
+        N = emb.size(0)
+        state = []
+        for t, name, dtype in ((rep, 'rep', torch.int64), (degree, 'degree', torch.int32), (best, 'best', torch.int64)):
+            self._tensor(t, name, dtype, ('N',))
+            if t.numel() != N:
+                raise RuntimeError('ffrnet_amd: %s must be [%d], got %s' % (name, N, list(t.shape)))
+            state.append(t.contiguous())
+        rep, degree, best = state
+        keep = self._keep_mask(keep, N)
+        if validate:
+            check_density_state(rep, degree, best)
+        kind = self._empty(N, dtype=torch.uint8)
+        self._call(self.lib.ffr_cluster_density_remove, _ptr(emb if N else None), _ptr(norms), N, emb.size(1), float(threshold),
+                   int(min_rows), _ptr(keep if N else None), _ptr(rep if N else None), _ptr(kind if N else None),
                    _ptr(degree if N else None), _ptr(best if N else None))
         return rep, kind, degree, best
 

@@ -307,7 +307,7 @@ int ffr_cluster_extend(ffr_handle* h, const float* emb, const float* norms, long
 /* Remove rows from a single-link clustering, equal to clustering the rest.  emb[N][dim], norms[N] or NULL: as in
  * ffr_cluster_threshold.  All labels use the caller's row numbering: nothing is moved, the caller compacts afterwards if it
  * wants to.  keep[N] uint8: keep[x] != 0 means row x survives.  (Removal from a density-gated clustering is a different
- * problem -- degrees fall, core rows are demoted, border rows choose again -- and is not offered.)
+ * problem -- degrees fall, core rows are demoted, border rows choose again: ffr_cluster_density_remove below.)
  *   labels g(x) = rep_in[x] if 0 <= rep_in[x] <= x, else x: the guard of ffr_cluster_extend.  A label r is HIT iff some
  *          removed row d has g(d) == r; a surviving row x is AFFECTED iff g(x) is hit.
  *   result rep[N] int64.  A removed row: -1.  An unaffected survivor: g(x) -- a cluster that loses no row keeps its label; it
@@ -404,6 +404,47 @@ int ffr_cluster_density(ffr_handle* h, const float* emb, const float* norms, lon
  * an upper bound: the last term stands for 2 * m * N_old with m <= N_old.                                              */
 int ffr_cluster_density_extend(ffr_handle* h, const float* emb, const float* norms, long long N_old, long long N, int dim,
                                float threshold, int min_rows, int64_t* rep, uint8_t* kind, int32_t* degree,
+                               unsigned long long* best, void* stream);
+/* Remove rows from a density-gated clustering, equal to ffr_cluster_density over the rest.  emb[N][dim], norms[N] or NULL as
+ * above; keep[N] uint8, keep[x] != 0 means row x survives.  Nothing moves: all labels stay in the caller's numbering, as in
+ * ffr_cluster_remove.
+ *   state  rep[N] int64, degree[N] int32 and best[N] uint64, in and out: what ffr_cluster_density_extend leaves for all N rows
+ *          at this threshold and min_rows.  kind[N] uint8 is out only.
+ *   equal  let kept be the surviving rows in ascending order and o2n the monotone renumbering they define.  On the survivors
+ *          o2n[rep], kind and degree equal ffr_cluster_density over emb[kept] bit for bit, and best, with its low word
+ *          (0xFFFFFFFF - core row) re-encoded through o2n and its high word (the score bits) untouched, is bit for bit the
+ *          state ffr_cluster_density_extend(N_old = 0) leaves over emb[kept].  So extensions and removals interleave freely.
+ *          A removed row gets rep = -1, kind = 0, degree = 0, best = 0.  Nothing removed: the state comes back unchanged and
+ *          no pair is scored.  Everything removed: every rep is -1.  min_rows = 1: rep equals ffr_cluster_remove on the same
+ *          rep and keep bit for bit.  A surviving row's rep may rise, and a border row may move to another cluster.  Repeated
+ *          calls are bitwise equal.
+ *   how    need = min_rows - 1; g(x) = rep[x] if 0 <= rep[x] <= x, else x.
+ *          (1) the removed rows are listed, r of them, and scored against all rows: a surviving row loses one from its degree
+ *              per removed neighbour (r * N pairs).  Degrees count all neighbours, so a demotion does not cascade.
+ *          (2) a row that was core (old degree >= need) and is removed or no longer core is LOST; a label is HIT iff g of
+ *              a lost row names it.  Removing a border or a noise row hits nothing.
+ *          (3) the m still-core rows of hit labels start alone and are joined again among themselves, m (m - 1) / 2 pairs as in
+ *              ffr_cluster_remove; a core row of an unhit label hangs under the smallest core row with its rep: in an unhit
+ *              cluster every core row survived and stayed core.
+ *          (4) a non-core survivor keeps its key iff the key's core row survives and is still core (a maximum over a set that
+ *              shrank but still holds its maximum).  The q others -- every demoted row, every border row whose chosen core row
+ *              was lost -- start from key 0 and are offered every surviving core row adjacent to them (q * N pairs) with the
+ *              one 64-bit atomic max of ffr_cluster_density.  A noise row stays noise.
+ *          (5) root, smallest member and labels as in ffr_cluster_density, over the survivors.
+ *          Pairs may be scored with the roles exchanged; the bits are the same.
+ *   guard  a key is dropped and looked for again when it names a row >= N, a removed row, or a row that is not core by the
+ *          new degrees; a rep outside [0, x] means "x alone"; a negative degree reads as 0.  Whatever is passed, every index
+ *          stays in [0, N) and every walk ends.  A state in range but wrong gives rep[rep[i]] == rep[i] on the survivors and
+ *          nothing more.
+ *   errors as ffr_cluster_density_extend (without N_old), plus FFR_ERR_ARG for a null keep when N > 0.  N = 0 succeeds and
+ *          touches nothing.
+ *   memory no host synchronisation: r, m and q stay on the device.  The scratch is carved from the clustering arena (norms,
+ *          nine ints per row and three counts) and grows and bumps ffr_generation under the same rule.
+ * Profiled as one launch under FFR_KC_SCORE with flops = 0: the pair counts are known on the device only.  The call scores
+ * at least r * N pairs where clustering the N_s survivors again scores N_s (N_s - 1): with half of the rows leaving, clustering
+ * again is the cheaper way to the same state (ffr_cluster_density_extend with N_old = 0 over the compacted rows).        */
+int ffr_cluster_density_remove(ffr_handle* h, const float* emb, const float* norms, long long N, int dim, float threshold,
+                               int min_rows, const uint8_t* keep, int64_t* rep, uint8_t* kind, int32_t* degree,
                                unsigned long long* best, void* stream);
 
 /* ---- face alignment (landmarks -> similarity transform -> aligned uint8 crop) ---------------------------------------
