@@ -13,7 +13,7 @@ from . import checkpoint  # noqa: F401
 from . import train  # noqa: F401
 from .train import NativeTrainer  # noqa: F401
 from . import search  # noqa: F401
-from .search import Gallery, search_sharded, identification_rates, subject_rates  # noqa: F401
+from .search import Gallery, search_sharded, search_sharded_filtered, identification_rates, subject_rates  # noqa: F401
 from . import align  # noqa: F401
 from .align import TEMPLATE_96x112, TEMPLATE_112x112  # noqa: F401
 from . import cluster  # noqa: F401
@@ -21,5 +21,5 @@ from .cluster import Clusters, DensityClusters, DensityState, Incremental, Incre
 
 __all__ = ['Backbone', 'RecNet', 'ir_se_50_512', 'l2_norm', 'Engine', 'GraphedEmbed',
            'NativeLibraryMissing', 'lib_path', 'synth', 'lfw', 'checkpoint', 'train', 'NativeTrainer',
-           'search', 'Gallery', 'search_sharded', 'identification_rates', 'subject_rates', 'align', 'TEMPLATE_96x112', 'TEMPLATE_112x112',
+           'search', 'Gallery', 'search_sharded', 'search_sharded_filtered', 'identification_rates', 'subject_rates', 'align', 'TEMPLATE_96x112', 'TEMPLATE_112x112',
            'cluster', 'Clusters', 'DensityClusters', 'DensityState', 'Incremental', 'IncrementalDensity']

@@ -282,6 +282,9 @@ int ffr_row_norms(ffr_handle* h, const float* x, long long n, int dim, float* no
 // What the search and merge entries share.  Lists [..][Q][k] of scores and indices; u: their subject plane, null in an entry
 // without subjects -- what tells the two kinds of entry apart from here on (12 or 16 bytes per slot)
 struct TopLists { float* s = nullptr; int64_t* i = nullptr; int32_t* u = nullptr; };
+// The per-probe filter of ffr_search_topk_filtered: tag[G] and qmask[Q]; both null in every other entry -- what tells the
+// filtered search apart from here on (qmask is never null in it, tag only at G = 0)
+struct SearchFilter { const uint32_t* tag = nullptr; const uint32_t* qmask = nullptr; };
 
 static bool misaligned4(const void* p) { return ((uintptr_t)p & 3) != 0; }
 
@@ -292,43 +295,54 @@ static int check_distinct(ffr_handle* h, const char* who, int distinct, int k) {
     return FFR_OK;
 }
 
-// The checks of the four search entries, in the order every entry makes them: handle, dim, null pointers and ranges (at
-// G = 0 the gallery side may be null), distinct and the k of identity mode, 16-byte rows, 4-byte subjects.  coarse: the entry
-// takes plane and plane_flag; subj: it takes subject and top.u (an entry without passes distinct = 0).  `who` names it in
-// messages.
+// The checks of the five search entries, in the order every entry makes them: handle, dim, null pointers and ranges (at
+// G = 0 the gallery side may be null), distinct and the k of identity mode, 16-byte rows, 4-byte subjects, 4-byte tags and
+// masks.  coarse: the entry takes plane and plane_flag; subj: it takes subject and top.u (an entry without passes distinct = 0,
+// or is refused); flt (or null): it takes tag and qmask.  `who` names it in messages.
 static int search_pre(ffr_handle* h, const char* who, bool coarse, const float* query, int Q, const float* gallery,
                       const float* gallery_norms, const uint16_t* plane, const int* plane_flag, const int32_t* subject, long long G,
-                      int dim, int k, int distinct, const TopLists& top, bool subj) {
+                      int dim, int k, int distinct, const TopLists& top, bool subj, const SearchFilter* flt = nullptr) {
     RC(check_fwd(h, false, false, 1));
     RC(check_dim(h, who, dim));
-    const bool gallery_side = gallery && gallery_norms && (!coarse || (plane && plane_flag)) && (!subj || subject);
-    if (!query || !top.s || !top.i || (subj && !top.u) || Q < 1 || k < 1 || k > 128 || G < 0 || (G > 0 && !gallery_side))
+    const bool gallery_side = gallery && gallery_norms && (!coarse || (plane && plane_flag)) && (!subj || subject) && (!flt || flt->tag);
+    if (!query || !top.s || !top.i || (subj && !top.u) || (flt && !flt->qmask) || Q < 1 || k < 1 || k > 128 || G < 0 ||
+        (G > 0 && !gallery_side))
         return fail(h, FFR_ERR_ARG, "%s: bad arguments (Q >= 1, 1 <= k <= 128, G >= 0, non-null pointers)", who);
     RC(check_distinct(h, who, distinct, k));
+    if (distinct && !subj) return fail(h, FFR_ERR_ARG, "%s: distinct = 1 needs gallery_subject and top_subject", who);
     if (misaligned16(query) || (G > 0 && (misaligned16(gallery) || misaligned16(plane))))
         return fail(h, FFR_ERR_ARG, "%s: %s rows must be 16-byte aligned", who, coarse ? "query, gallery and plane" : "query and gallery");
     if (G > 0 && misaligned4(subject)) return fail(h, FFR_ERR_ARG, "%s: gallery_subject must be 4-byte aligned", who);
+    if (flt && (misaligned4(flt->qmask) || (G > 0 && misaligned4(flt->tag))))
+        return fail(h, FFR_ERR_ARG, "%s: gallery_tag and query_mask must be 4-byte aligned", who);
     return FFR_OK;
 }
 
 // An exact pass into given lists: the search of the plan (T, S, chunk_rows) and, when S > 1, the merge of its chunk lists
-// part[S][Q][k].  subject (or null) and distinct: the policy.  live (device, or null): only the probes [0, *live) are searched
+// part[S][Q][k].  subject (or null) and distinct: the policy.  live (device, or null): only the probes [0, *live) are searched.
+// flt: the per-probe filter, with which the same policy runs in its filtered kernel; the merge is the same, the lists hold
+// admissible rows only
 static int exact_pass(ffr_handle* h, const float* query, const float* qnorm, int Q, const float* gallery, const float* gallery_norms,
                       const int32_t* subject, long long G, int k, long long index_base, int distinct, int T, int S,
-                      long long chunk_rows, const TopLists& dst, const TopLists& part, const int* live, hipStream_t st) {
+                      long long chunk_rows, const TopLists& dst, const TopLists& part, const int* live, hipStream_t st,
+                      const SearchFilter& flt = {}) {
     const TopLists& out = S > 1 ? part : dst;
     const SearchArgs a{query, qnorm, gallery, nullptr, gallery_norms, G, chunk_rows, index_base, out.s, out.i, live, Q, k, S, T,
-                       subject, out.u};
-    HIPCK(h, launch_search(a, !subject ? SEARCH_ROWS : distinct ? SEARCH_DISTINCT : SEARCH_LIVE, st));
+                       subject, out.u, flt.tag, flt.qmask};
+    const SearchKernel policy = !subject ? SEARCH_ROWS : distinct ? SEARCH_DISTINCT : SEARCH_LIVE;
+    static_assert(SEARCH_FILTERED_LIVE - SEARCH_FILTERED_ROWS == SEARCH_LIVE - SEARCH_ROWS &&
+                  SEARCH_FILTERED_DISTINCT - SEARCH_FILTERED_ROWS == SEARCH_DISTINCT - SEARCH_ROWS,
+                  "the filtered kernels come in the order of the policies");
+    HIPCK(h, launch_search(a, flt.qmask ? (SearchKernel)(SEARCH_FILTERED_ROWS + policy) : policy, st));
     if (S > 1) HIPCK(h, launch_topk_merge(part.s, part.i, part.u, S, Q, k, distinct, dst.s, dst.i, dst.u, st, live));
     return FFR_OK;
 }
 
-// The exact search of checked arguments: ffr_search_topk, ffr_search_topk_subjects (top.u), and the coarse entries where
-// their pass does not serve
+// The exact search of checked arguments: ffr_search_topk, ffr_search_topk_subjects (top.u), ffr_search_topk_filtered (flt), and
+// the coarse entries where their pass does not serve
 static int exact_search(ffr_handle* h, const float* query, int Q, const float* gallery, const float* gallery_norms,
                         const int32_t* subject, long long G, int dim, int k, long long index_base, int distinct, const TopLists& top,
-                        hipStream_t st) {
+                        hipStream_t st, const SearchFilter& flt = {}) {
     const double slot = top.u ? 16.0 : 12.0;
     if (G == 0) {                 // k slots of padding per probe: the merge of no list
         Scope s(h, st, FFR_KC_SCORE, 0.0, slot * Q * k);
@@ -349,10 +363,11 @@ static int exact_search(ffr_handle* h, const float* query, int Q, const float* g
             if (top.u) part.u = a.take<int32_t>((size_t)S * Q * k);
         }
     }));
-    Scope s(h, st, FFR_KC_SCORE, 2.0 * Q * (double)G * dim, 4.0 * (double)G * (dim + (top.u ? 2 : 1)) + 4.0 * Q * dim + slot * Q * k);
+    Scope s(h, st, FFR_KC_SCORE, 2.0 * Q * (double)G * dim,
+            4.0 * (double)G * (dim + (top.u ? 2 : 1)) + 4.0 * Q * dim + slot * Q * k + (flt.qmask ? 4.0 * (double)G + 4.0 * Q : 0.0));
     HIPCK(h, launch_row_norms(query, Q, qnorm, st));
     return exact_pass(h, query, qnorm, Q, gallery, gallery_norms, subject, G, k, index_base, distinct, T, S, chunk_rows, top, part,
-                      nullptr, st);
+                      nullptr, st, flt);
 }
 
 int ffr_search_topk(ffr_handle* h, const float* query, int Q, const float* gallery, const float* gallery_norms, long long G,
@@ -371,6 +386,22 @@ int ffr_search_topk_subjects(ffr_handle* h, const float* query, int Q, const flo
     RC(search_pre(h, "ffr_search_topk_subjects", false, query, Q, gallery, gallery_norms, nullptr, nullptr, gallery_subject, G, dim, k,
                   distinct, top, true));
     return exact_search(h, query, Q, gallery, gallery_norms, gallery_subject, G, dim, k, index_base, distinct, top, (hipStream_t)stream);
+}
+
+// The subject search under a per-probe filter.  It takes subjects or not: with either of gallery_subject and top_subject it is
+// checked as the subject entry is (both are needed; at G = 0 the gallery side may be null), without them as the plain one
+int ffr_search_topk_filtered(ffr_handle* h, const float* query, const uint32_t* query_mask, int Q, const float* gallery,
+                             const float* gallery_norms, const uint32_t* gallery_tag, const int32_t* gallery_subject, long long G,
+                             int dim, int k, long long index_base, int distinct, float* top_score, int64_t* top_index,
+                             int32_t* top_subject, void* stream) {
+    FFR_DEVICE_SCOPE(h);
+    const TopLists top{top_score, top_index, top_subject};
+    const SearchFilter flt{gallery_tag, query_mask};
+    const bool subj = gallery_subject || top_subject;
+    RC(search_pre(h, "ffr_search_topk_filtered", false, query, Q, gallery, gallery_norms, nullptr, nullptr, gallery_subject, G, dim, k,
+                  distinct, top, subj, &flt));
+    return exact_search(h, query, Q, gallery, gallery_norms, gallery_subject, G, dim, k, index_base, distinct, top, (hipStream_t)stream,
+                        flt);
 }
 
 // The body of ffr_topk_merge and of ffr_topk_merge_subjects (subj: the lists carry subjects)

@@ -273,12 +273,19 @@ struct SearchArgs {
     int Q, k, nchunks, ntiles;
     const int32_t* subject;   // [G], < 0 = a removed row (SR_LIVE, SR_DISTINCT)
     int32_t* out_u;           // [S][Q][k] (SR_LIVE, SR_DISTINCT; not touched, may be null, where OUT_U is false)
+    const uint32_t* tag;      // [G] one word per row (TAG): row g is a candidate of probe q iff (tag[g] & qmask[q]) != 0
+    const uint32_t* qmask;    // [Q] one word per probe (TAG)
 };
-// The instantiations search_block<COARSE, SUBJ, OUT_U> has, by kernel: the exact tile with the policy SR_ROWS (k_search_topk),
+// The instantiations search_block<COARSE, SUBJ, OUT_U, TAG> has, by kernel: the exact tile with the policy SR_ROWS (k_search_topk),
 // SR_LIVE and SR_DISTINCT (k_search_subjects: subject[G], < 0 = a removed row, never listed, and a third plane out_u of
 // subjects; SR_DISTINCT lists subjects, each by its best row, k <= search_max_k_distinct()); the coarse tile with SR_ROWS
-// (k_search_coarse) and, under the removal mask, SR_LIVE without the subject plane (k_search_coarse_live)
-enum SearchKernel { SEARCH_ROWS, SEARCH_LIVE, SEARCH_DISTINCT, SEARCH_COARSE, SEARCH_COARSE_LIVE };
+// (k_search_coarse) and, under the removal mask, SR_LIVE without the subject plane (k_search_coarse_live); and the exact
+// tile with each of the three policies under the per-probe filter of tag and qmask (k_search_filtered).  New kernels go at
+// the end: the values are the positions in the table of launch_search
+enum SearchKernel {
+    SEARCH_ROWS, SEARCH_LIVE, SEARCH_DISTINCT, SEARCH_COARSE, SEARCH_COARSE_LIVE,
+    SEARCH_FILTERED_ROWS, SEARCH_FILTERED_LIVE, SEARCH_FILTERED_DISTINCT
+};
 int search_max_k_distinct();
 // top-k lists [nchunks][Q][k] of every gallery chunk (one launch of nchunks x ntiles blocks); k <= 128.  The coarse kernels
 // list by coarse score, index = gallery row: index_base 0, no live count, k = the shortlist's length

@@ -7,6 +7,8 @@
 //                bf16 instantiation is k_search_coarse, search_coarse.hip).
 // k_search_subjects  the same block with a subject policy (ffr_search_topk_subjects): SR_LIVE ranks the rows that were not
 //                removed, SR_DISTINCT ranks subjects, each by its best row.
+// k_search_filtered  the same block, with each of the three policies, under a per-probe filter (ffr_search_topk_filtered): a
+//                row is a candidate of a probe iff its tag word and the probe's mask word share a bit.
 // k_topk_merge   S sorted lists per probe -> one: one wave per probe, a k-step tournament over the list heads (wave
 //                argmax with the total order, lane as the last tie-break); the lists are staged in LDS when they fit.
 //                Slots with index < 0 are padding (-inf, -1) and sort after every real entry.
@@ -45,6 +47,9 @@ __global__ __launch_bounds__(256) void k_row_norms(const float* __restrict__ x, 
 
 __global__ __launch_bounds__(256, 1) void k_search_topk(const SearchArgs a) { search_block<false>(a); }
 template <int SUBJ> __global__ __launch_bounds__(256, 1) void k_search_subjects(const SearchArgs a) { search_block<false, SUBJ>(a); }
+template <int SUBJ> __global__ __launch_bounds__(256, 1) void k_search_filtered(const SearchArgs a) {
+    search_block<false, SUBJ, SUBJ != SR_ROWS, true>(a);
+}
 
 // (score, index) keys of the merge: padding (index < 0) sorts after everything
 __device__ __forceinline__ bool mg_beats(float s1, long long i1, int l1, float s2, long long i2, int l2) {
@@ -174,8 +179,10 @@ void search_plan(int Q, long long G, int num_cus, int* ntiles, int* nchunks, lon
 // One launch for every instantiation of the search block, in the order of SearchKernel; the LDS follows (k, distinct)
 hipError_t launch_search(const SearchArgs& a, SearchKernel kernel, hipStream_t stream) {
     const void* const fn[] = {(const void*)k_search_topk, (const void*)k_search_subjects<SR_LIVE>,
-                              (const void*)k_search_subjects<SR_DISTINCT>, search_coarse_kernel(false), search_coarse_kernel(true)};
-    const size_t lds = sr_lds_bytes(a.k, kernel == SEARCH_DISTINCT);
+                              (const void*)k_search_subjects<SR_DISTINCT>, search_coarse_kernel(false), search_coarse_kernel(true),
+                              (const void*)k_search_filtered<SR_ROWS>, (const void*)k_search_filtered<SR_LIVE>,
+                              (const void*)k_search_filtered<SR_DISTINCT>};
+    const size_t lds = sr_lds_bytes(a.k, kernel == SEARCH_DISTINCT || kernel == SEARCH_FILTERED_DISTINCT);
     hipError_t e = hipFuncSetAttribute(fn[kernel], hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     void* args[] = {const_cast<SearchArgs*>(&a)};

@@ -28,6 +28,14 @@
 //    on the order of arrival (no atomics here either).  The policy goes with either tile, and the chunk's subjects, like its
 //    norms, are a 64-bit base (subject + c0) plus 32-bit offsets.  The threshold argument holds: with k subjects listed, a row at or below the k-th score loses
 //    to k listed entries on score or index, or to its own subject's entry.
+//  - Filter (k_search_filtered, search.hip; include/ffrnet.h, ffr_search_topk_filtered): a second compile-time policy, TAG,
+//    that goes with each of the three above.  The candidate test so far depends on the row alone; TAG adds a term that depends
+//    on the probe too: `(tag[g] & qmask[q]) != 0`.  Lane (n, h) keeps its probe's mask word in a register beside qn_lane (0
+//    for a probe past Q, which takes nothing anyway), and the 16 tag words of the rows it scores are read beside their norms
+//    and subjects, a 64-bit base (tag + c0) plus the same clamped 32-bit offsets.  Nothing else changes and no LDS is added:
+//    the list is the top k of a set under a total order, so it does not matter which rows were candidates before, and the
+//    threshold argument holds per probe with "rows" read as "rows admissible for this probe".  The K loop still scores every
+//    row: a step none of whose rows is admissible costs what any step costs.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -82,8 +90,9 @@ static_assert(sr_lds_bytes(SR_MAX_K) <= 160 * 1024 && sr_lds_bytes(SR_MAX_K_DIST
 // bf16 one, k_search_subjects (search.hip) the exact one with a subject policy, k_search_coarse_live (search_coarse.hip) the
 // bf16 one under the removal mask.  They differ in the tile and in what the policy adds; the threshold test, the survivor
 // slots and the rank-scatter merge are this text.  OUT_U = false: the lists go out without their subject plane (out_u is not
-// touched and may be null) -- a shortlist of rows, whose reader looks subject[row] up again.
-template <bool COARSE, int SUBJ = SR_ROWS, bool OUT_U = SUBJ != SR_ROWS>
+// touched and may be null) -- a shortlist of rows, whose reader looks subject[row] up again.  TAG: k_search_filtered
+// (search.hip), the candidate test under the per-probe filter of SearchArgs::tag and qmask.
+template <bool COARSE, int SUBJ = SR_ROWS, bool OUT_U = SUBJ != SR_ROWS, bool TAG = false>
 __device__ __forceinline__ void search_block(const SearchArgs& a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
     f32x4* qf = (f32x4*)sm;
@@ -123,9 +132,12 @@ __device__ __forceinline__ void search_block(const SearchArgs& a) {
         nl[tid] = 0;
     }
     const float qn_lane = n < nq ? a.qnorm[q0 + n] : 0.f;
+    uint32_t qm_lane = 0;                       // TAG: the mask word of probe n
+    if constexpr (TAG) qm_lane = n < nq ? a.qmask[q0 + n] : 0u;
 
     const float* __restrict__ nch = a.gnorm + c0;
     const int32_t* __restrict__ sch = SUBJ != SR_ROWS ? a.subject + c0 : nullptr;
+    const uint32_t* __restrict__ tch = TAG ? a.tag + c0 : nullptr;
     typename SearchTile<COARSE>::Stream gs(SearchTile<COARSE>::chunk(a, c0), lane);
     gs.prime(min(w * 32 + n, rows - 1));
     __syncthreads();
@@ -143,6 +155,11 @@ __device__ __forceinline__ void search_block(const SearchArgs& a) {
         if constexpr (SUBJ != SR_ROWS) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) gu[r] = sch[(unsigned)min(acc_row(sbase + w * 32, r) + 4 * h, rows - 1)];
+        }
+        uint32_t gt[TAG ? 16 : 1];               // and their tag words
+        if constexpr (TAG) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) gt[r] = tch[(unsigned)min(acc_row(sbase + w * 32, r) + 4 * h, rows - 1)];
         }
         f32x16 acc;
         if constexpr (COARSE) {
@@ -162,6 +179,7 @@ __device__ __forceinline__ void search_block(const SearchArgs& a) {
             sc[r] = COARSE ? coarse_score(acc[r], qn_lane, gn[r]) : cosine_score(acc[r], qn_lane, gn[r]);
             bool in = sbase + cosine_lane_row(w, r, h) < rows;
             if constexpr (SUBJ != SR_ROWS) in = in && gu[r] >= 0;
+            if constexpr (TAG) in = in && (gt[r] & qm_lane) != 0;
             if (in && sc[r] > t) mask |= 1u << r;
         }
         const int cnt = __builtin_popcount(mask);

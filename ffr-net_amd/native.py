@@ -120,6 +120,8 @@ SYMBOLS = [
     ('ffr_topk_merge', C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     ('ffr_search_topk_subjects', C.c_int, [_P, _P, C.c_int, _P, _P, _P, C.c_longlong, C.c_int, C.c_int, C.c_longlong, C.c_int, _P, _P, _P,
                                            _P]),
+    ('ffr_search_topk_filtered', C.c_int, [_P, _P, _P, C.c_int, _P, _P, _P, _P, C.c_longlong, C.c_int, C.c_int, C.c_longlong, C.c_int, _P,
+                                           _P, _P, _P]),
     ('ffr_topk_merge_subjects', C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     ('ffr_coarse_pack', C.c_int, [_P, _P, _P, C.c_longlong, C.c_int, _P, _P, _P]),
     ('ffr_search_topk_coarse', C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, C.c_longlong, C.c_int, C.c_int, C.c_longlong, _P, _P, _P, _P]),
@@ -253,6 +255,29 @@ def check_density_state(rep, degree, best):
     named = 0xFFFFFFFF - (best & 0xFFFFFFFF)
     if bool(((best != 0) & (named >= n_old)).any().item()):
         raise RuntimeError('ffrnet_amd: density state needs every key of best to be 0 or to name a row < %d' % n_old)
+
+
+def tag_words(words, what, device=None):
+    """The tag and mask words of the filtered search (include/ffrnet.h: ffr_search_topk_filtered) as the library reads them:
+    a flat int32 tensor that carries the 32-bit patterns, on `device` when given.  Takes an int in [0, 2^32), an int32 tensor
+    (its bits are the word: bit 31 shows as a negative value) or an int64 tensor with every value in [0, 2^32); anything else
+    raises RuntimeError.  Plain torch, so it runs without a GPU."""
+    if isinstance(words, bool) or not isinstance(words, (int, torch.Tensor)):
+        raise RuntimeError('ffrnet_amd: %s must be an int or an int32 / int64 tensor, got %s' % (what, type(words)))
+    if isinstance(words, int):
+        if not 0 <= words < 2 ** 32:
+            raise RuntimeError('ffrnet_amd: %s must lie in [0, 2^32), got %d' % (what, words))
+        words = torch.tensor([words], dtype=torch.int64)
+    if words.dtype not in (torch.int32, torch.int64):
+        raise RuntimeError('ffrnet_amd: %s must be int32, or int64 in [0, 2^32), got %s' % (what, words.dtype))
+    words = words.reshape(-1)
+    if device is not None:
+        words = words.to(device)
+    if words.dtype == torch.int64:
+        if words.numel() and (int(words.min().item()) < 0 or int(words.max().item()) >= 2 ** 32):
+            raise RuntimeError('ffrnet_amd: %s: int64 words must lie in [0, 2^32)' % what)
+        words = torch.where(words >= 2 ** 31, words - 2 ** 32, words).to(torch.int32)
+    return words.contiguous()
 
 
 _U8_HINT = ' (HWC, RGB)'
@@ -492,10 +517,11 @@ class Engine(object):
             gallery_norms = gallery_norms.contiguous()
         return query, gallery, gallery_norms, G
 
-    def _search(self, who, query, gallery, k, gallery_norms, index_base, coarse=None, subj=None):
-        """The body of the four searches.  coarse: (plane, flag) of search_coarse(); subj: (subjects, distinct) of
-        search_subjects() -> [scores, index(, subjects)(, certified)].  The arguments go in the order of include/ffrnet.h; the
-        tensors stay referenced until the call is made."""
+    def _search(self, who, query, gallery, k, gallery_norms, index_base, coarse=None, subj=None, flt=None):
+        """The body of the five searches.  coarse: (plane, flag) of search_coarse(); subj: (subjects, distinct) of
+        search_subjects(); flt: (mask, tags) of search_filtered(), whose entry takes subjects or NULL in their place
+        -> [scores, index(, subjects)(, certified)].  The arguments go in the order of include/ffrnet.h; the tensors stay
+        referenced until the call is made."""
         query, gallery, gallery_norms, G = self._search_inputs(query, gallery, gallery_norms, who)
         Q, k = query.size(0), int(k)
 
@@ -503,6 +529,7 @@ class Engine(object):
             return t if G else None
         name = 'ffr_search_topk'
         head, tail = [query, Q, rows(gallery), gallery_norms], [G, query.size(1), k, int(index_base)]
+        null_out = []
         out = [self._empty(Q, max(k, 0)), self._empty(Q, max(k, 0), dtype=torch.int64)]
         if coarse is not None:
             plane, flag = coarse
@@ -510,14 +537,28 @@ class Engine(object):
             self._tensor(flag, 'flag', torch.int32, shape=(1,))
             head += [rows(plane.contiguous()), flag]
             name += '_coarse'
+        if flt is not None:
+            mask, tags = tag_words(flt[0], 'mask', self.device), tag_words(flt[1], 'tags', self.device)
+            if isinstance(flt[0], int):
+                mask = mask.expand(Q).contiguous()
+            if mask.numel() != Q or tags.numel() != G:
+                raise RuntimeError('ffrnet_amd: %s expects mask [%d] (or an int) and tags [%d], got %d and %d words'
+                                   % (who, Q, G, mask.numel(), tags.numel()))
+            head.insert(1, mask)
+            head.append(rows(tags))
+            name += '_filtered'
+            if subj is None:                     # NULL for gallery_subject and top_subject, distinct = 0
+                head.append(None)
+                tail.append(0)
+                null_out = [None]
         if subj is not None:
             head.append(rows(self._subjects(subj[0], 'subjects', (G,))))
             tail.append(int(bool(subj[1])))
             out.append(self._empty(Q, max(k, 0), dtype=torch.int32))
-            name += '_subjects'
+            name += '_subjects' if flt is None else ''
         if coarse is not None:
             out.append(self._empty(Q, dtype=torch.int32))
-        self._call(getattr(self.lib, name), *[a if isinstance(a, int) else _ptr(a) for a in head + tail + out])
+        self._call(getattr(self.lib, name), *[a if isinstance(a, int) else _ptr(a) for a in head + tail + out + null_out])
         return out
 
     def search(self, query, gallery, k, gallery_norms=None, index_base=0):
@@ -588,6 +629,20 @@ class Engine(object):
         row (maximum score, then smallest index); distinct=False (k <= 128): the top-k live rows
         -> (scores[Q,k] fp32, index[Q,k] int64, subjects[Q,k] int32); (-inf, -1, -1) pads."""
         return tuple(self._search('search_subjects', query, gallery, k, gallery_norms, index_base, subj=(subjects, distinct)))
+
+    def search_filtered(self, query, mask, gallery, tags, k, gallery_norms=None, index_base=0, subjects=None, distinct=False):
+        """search() under a per-probe filter, one call for probes that may each see another part of the gallery
+        (include/ffrnet.h: ffr_search_topk_filtered).  tags[G] is one 32-bit word per row, mask one per probe ([Q], or an int
+        for all of them): row g is admissible for probe q iff tags[g] & mask[q] != 0.  Words are int32 tensors carrying the
+        bit pattern, or int64 in [0, 2^32) (native.tag_words converts).  -> (scores[Q,k], index[Q,k]): search() over each
+        probe's admissible rows, with their original indices; (-inf, -1) pads.  subjects[G] (as search_subjects() takes
+        them): also removed rows are inadmissible, distinct as there (True: k <= 64), and the result is
+        (scores, index, subjects[Q,k]), bit for bit search_subjects() over the gallery in which the rows inadmissible for
+        the probe are marked removed."""
+        if subjects is None and distinct:
+            raise RuntimeError('ffrnet_amd: search_filtered: distinct=True needs subjects')
+        return tuple(self._search('search_filtered', query, gallery, k, gallery_norms, index_base, flt=(mask, tags),
+                                  subj=None if subjects is None else (subjects, distinct)))
 
     def search_coarse_subjects(self, query, gallery, plane, flag, subjects, k, gallery_norms=None, index_base=0, distinct=True,
                                return_certified=False):

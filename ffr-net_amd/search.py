@@ -24,8 +24,24 @@ person is several rows, and search_subjects() answers with the top-k PEOPLE, eac
   rates = subject_rates(subjects, probe_labels)
   gallery.remove([7, 12])                  # those people never come back, from search() either; rows keep their index
   old_to_new = gallery.compact()           # drop the removed rows physically
+
+Gallery.build_tags() keeps a 32-bit tag word beside every row (include/ffrnet.h: ffr_search_topk_filtered), with or
+without subjects.  A search with mask= ranks, for every probe, only the rows whose tag shares a bit with that probe's mask
+word -- watchlists a camera is subscribed to, a tenant's enrolments, the people cleared for a door -- in ONE call for a
+batch of probes with different masks:
+
+  gallery = Gallery(engine, subjects=True); gallery.build_tags(); gallery.add(f_enrol, subject_ids, tags=watchlist_bits)
+  scores, subjects, index = gallery.search_subjects(f_probe, k=10, mask=camera_subscriptions)     # [Q] words, or an int
+  gallery.set_subject_tags([7], 0b0101)    # person 7 moves to watchlists 0 and 2
+
+The filtered search is exact and reads every row.  A filter that stays fixed for long and admits a small share of the rows
+is served faster by a second Gallery of those rows (INTEGRATION.md section 7 has the measured crossover).
 """
+import functools
+
 import torch
+
+from .native import tag_words
 
 try:
     import torch.distributed as dist
@@ -57,7 +73,10 @@ class Gallery(object):
     (the same results; last_certified[Q] int32 tells which probes were certified).  subjects=True: a subject id (int32)
     grows beside every row, add() takes the ids, search_subjects() ranks subjects, remove() withdraws subjects (their rows
     stay in place, marked -1, and search() skips them) and compact() drops the removed rows.  build_plane() switches the
-    shortlist on for the rows a gallery holds already, with or without subjects."""
+    shortlist on for the rows a gallery holds already, with or without subjects.  build_tags() switches tags on, for an
+    empty gallery or one that holds rows: a 32-bit tag word (int32 carrying the pattern) grows beside every row, add() takes
+    the words, set_tags() / set_subject_tags() change them, and search(mask=) / search_subjects(mask=) rank per probe the
+    rows whose tag shares a bit with the probe's mask word."""
 
     def __init__(self, engine, capacity=0, coarse=False, subjects=False):
         if coarse and subjects:
@@ -73,6 +92,7 @@ class Gallery(object):
         self.has_subjects = bool(subjects)
         if self.has_subjects:
             self._add_side('_subj', torch.int32, capacity)
+        self.has_tags = False
         if self.coarse:
             self._add_plane()
 
@@ -111,6 +131,26 @@ class Gallery(object):
         self._need_subjects('subjects')
         return self._subj[:self._n]
 
+    @property
+    def tags(self):
+        """int32 [n]: the tag word of every row, as a bit pattern (bit 31 shows as a negative value); galleries with tags
+        only."""
+        self._need_tags('tags')
+        return self._tags[:self._n]
+
+    def _need_tags(self, what):
+        if not self.has_tags:
+            raise RuntimeError('ffrnet_amd: Gallery.%s needs a gallery with tags; call build_tags() first' % what)
+
+    def _tag_words(self, tags, n, what):
+        """int32 device tensor [n] of tag words from an int (the same word for all) or n words"""
+        words = tag_words(tags, 'Gallery.%s: tags' % what, self._emb.device)
+        if isinstance(tags, int):
+            words = words.expand(n)
+        if words.numel() != n:
+            raise RuntimeError('ffrnet_amd: Gallery.%s: %d tag words where %d are needed' % (what, words.numel(), n))
+        return words
+
     def _need_subjects(self, what):
         if not self.has_subjects:
             raise RuntimeError('ffrnet_amd: Gallery.%s needs a gallery created with subjects=True' % what)
@@ -125,9 +165,10 @@ class Gallery(object):
             raise RuntimeError('ffrnet_amd: Gallery.%s: subject ids must lie in [0, 2^31)' % what)
         return ids.to(torch.int32)
 
-    def add(self, emb, subjects=None):
+    def add(self, emb, subjects=None, tags=None):
         """Append emb[n,512] (fp32, on the Engine's device) -> the index of its first row.  A gallery with subjects
-        takes subjects[n] (int32 or int64, each in [0, 2^31)) as well."""
+        takes subjects[n] (int32 or int64, each in [0, 2^31)) as well, a gallery with tags takes tags: an int for all the
+        rows or [n] words (int32 bit patterns, or int64 in [0, 2^32))."""
         if not isinstance(emb, torch.Tensor) or emb.dim() != 2 or emb.size(1) != DIM:
             raise RuntimeError('ffrnet_amd: Gallery.add expects [n,%d] embeddings, got %s'
                                % (DIM, list(emb.shape) if isinstance(emb, torch.Tensor) else type(emb)))
@@ -140,6 +181,12 @@ class Gallery(object):
                 raise RuntimeError('ffrnet_amd: Gallery.add: %d rows but %d subject ids' % (n, subjects.numel()))
         elif subjects is not None:
             raise RuntimeError('ffrnet_amd: Gallery.add: subjects given to a gallery created without subjects=True')
+        if self.has_tags:
+            if tags is None:
+                raise RuntimeError('ffrnet_amd: Gallery.add: this gallery keeps tags; pass tags (an int or [n] words)')
+            tags = self._tag_words(tags, n, 'add')
+        elif tags is not None:
+            raise RuntimeError('ffrnet_amd: Gallery.add: tags given to a gallery without tags; call build_tags() first')
         first = self._n
         if first + n > self._emb.size(0):
             cap = max(first + n, 2 * self._emb.size(0), 1024)
@@ -156,6 +203,8 @@ class Gallery(object):
                                         self._plane[first:first + n], self._flag)
             if self.has_subjects:
                 self._subj[first:first + n] = subjects
+            if self.has_tags:
+                self._tags[first:first + n] = tags
         self._n = first + n
         return first
 
@@ -171,23 +220,62 @@ class Gallery(object):
             self.engine.coarse_pack(self.embeddings, self.norms, self._plane[:self._n], self._flag)
         self.coarse = True
 
-    def search(self, query, k, self_index=None, index_base=0):
+    def build_tags(self, tags=0):
+        """Switch tags on for this gallery: a tag word beside every row, registered like the other side buffers, so it grows
+        and compacts with them.  The rows held get `tags` (an int for all of them, or [n] words; 0 = admissible for nobody
+        until set_tags() / set_subject_tags() say otherwise); from then on add() takes tags.  Works on an empty gallery, so
+        Gallery(engine); build_tags() is a gallery with tags from the start.  Does nothing on a gallery that has tags."""
+        if self.has_tags:
+            return
+        words = self._tag_words(tags, self._n, 'build_tags')
+        self._add_side('_tags', torch.int32, self._emb.size(0))
+        self._tags[:self._n] = words
+        self.has_tags = True
+
+    def search(self, query, k, self_index=None, index_base=0, mask=None):
         """Top-k enrolled rows of every probe query[Q,512] -> (scores[Q,k], index[Q,k]).  self_index[Q] (gallery
-        indices of the probes themselves): leave-one-out search, the probe's own row is never returned."""
+        indices of the probes themselves): leave-one-out search, the probe's own row is never returned.  mask (an int or
+        [Q] words; galleries with tags): every probe ranks only the rows whose tag shares a bit with its mask word."""
         if self_index is None:
-            return self._search(query, k, index_base)
-        s, i = self._search(query, int(k) + 1, index_base)
+            return self._search(query, k, index_base, mask)
+        s, i = self._search(query, int(k) + 1, index_base, mask)
         return drop_self(s, i, torch.as_tensor(self_index, device=i.device) + int(index_base))
 
-    def search_subjects(self, query, k, index_base=0):
+    def search_subjects(self, query, k, index_base=0, mask=None):
         """Top-k enrolled SUBJECTS of every probe query[Q,512], each once, by its best row -> (scores[Q,k],
-        subjects[Q,k] int32, index[Q,k]); k <= 64; (-inf, -1, -1) pads when fewer than k subjects are enrolled."""
+        subjects[Q,k] int32, index[Q,k]); k <= 64; (-inf, -1, -1) pads when fewer than k subjects are enrolled.  mask: as
+        search() takes it; a subject speaks with its best row among those the probe may see."""
         self._need_subjects('search_subjects')
-        s, i, u = self._search_subjects(query, k, index_base, True)
+        s, i, u = self._search_subjects(query, k, index_base, True, mask)
         return s, u, i
 
-    def _search_subjects(self, query, k, index_base, distinct):
+    def set_tags(self, index, tags):
+        """Give the rows index[n] (gallery indices) new tag words: an int for all of them, or [n] words.  On the device."""
+        self._need_tags('set_tags')
+        idx = torch.as_tensor(index, device=self._emb.device).reshape(-1).to(torch.int64)
+        if idx.numel() and (int(idx.min().item()) < 0 or int(idx.max().item()) >= self._n):
+            raise RuntimeError('ffrnet_amd: Gallery.set_tags: row indices must lie in [0, %d)' % self._n)
+        self.tags[idx] = self._tag_words(tags, idx.numel(), 'set_tags')
+
+    def set_subject_tags(self, subject_ids, tags):
+        """Give every live row of the subjects subject_ids[m] (each named once) new tag words: an int for all of them, or
+        [m] words, one per subject.  On the device -> the number of rows changed."""
+        self._need_tags('set_subject_tags')
+        self._need_subjects('set_subject_tags')
+        ids = self._subject_ids(subject_ids, 'set_subject_tags')
+        words = self._tag_words(tags, ids.numel(), 'set_subject_tags')
+        if not ids.numel():
+            return 0
+        ids, order = torch.sort(ids)
+        live = self.subjects
+        hit = torch.isin(live, ids)
+        self.tags[hit] = words[order[torch.searchsorted(ids, live[hit])]]
+        return int(hit.sum().item())
+
+    def _search_subjects(self, query, k, index_base, distinct, mask=None):
         """(scores, index, subjects) of a gallery with subjects, through the shortlist when it has a plane"""
+        if mask is not None:
+            return self._search_filtered(query, k, index_base, distinct, mask)
         if not self.coarse:
             return self.engine.search_subjects(query, self.embeddings, self.subjects, k, gallery_norms=self.norms,
                                                index_base=index_base, distinct=distinct)
@@ -221,10 +309,20 @@ class Gallery(object):
         self._n = n
         return new_index
 
-    def _search(self, query, k, index_base):
+    def _search_filtered(self, query, k, index_base, distinct, mask):
+        """The exact filtered search, also on a gallery that has a plane: the certified pass does not know filters"""
+        self._need_tags('search with a mask')
+        self.last_certified = None
+        return self.engine.search_filtered(query, mask, self.embeddings, self.tags, k, gallery_norms=self.norms,
+                                           index_base=index_base, subjects=self.subjects if self.has_subjects else None,
+                                           distinct=distinct)
+
+    def _search(self, query, k, index_base, mask=None):
         if self.has_subjects:           # row mode under the mask: removed rows never come back
-            s, i, _ = self._search_subjects(query, k, index_base, False)
+            s, i, _ = self._search_subjects(query, k, index_base, False, mask)
             return s, i
+        if mask is not None:
+            return self._search_filtered(query, k, index_base, False, mask)
         if not self.coarse:
             return self.engine.search(query, self.embeddings, k, gallery_norms=self.norms, index_base=index_base)
         s, i, self.last_certified = self.engine.search_coarse(query, self.embeddings, self.plane, self._flag, k,
@@ -251,8 +349,21 @@ def search_sharded(gallery_shard, query, k, group=None, distinct=None):
     distinct=True, for shards with subjects: the top-k subjects, (scores, subjects, index) as Gallery.search_subjects
     gives them; the exchange carries the subject as a fourth word and the merge is ffr_topk_merge_subjects.  The default
     (None) and False give the row search of the shard: plain, or under the removal mask of a gallery with subjects."""
-    eng = gallery_shard.engine
+    return _search_sharded(gallery_shard.search_subjects if distinct else gallery_shard.search, gallery_shard, query, k, group,
+                           distinct)
+
+
+def search_sharded_filtered(gallery_shard, query, k, mask, group=None, distinct=None):
+    """search_sharded() under a per-probe filter: mask (an int or [Q] words, the SAME on every rank) goes to the search of
+    every shard, a Gallery with tags.  The shard lists hold admissible rows only, so the exchange and the merge are those of
+    search_sharded(), and the result is bitwise that of one filtered search over the concatenated gallery."""
     search = gallery_shard.search_subjects if distinct else gallery_shard.search
+    return _search_sharded(functools.partial(search, mask=mask), gallery_shard, query, k, group, distinct)
+
+
+def _search_sharded(search, gallery_shard, query, k, group, distinct):
+    """The body of search_sharded() and search_sharded_filtered(): `search` is the shard's search"""
+    eng = gallery_shard.engine
     if dist is None or not dist.is_available() or not dist.is_initialized() or dist.get_world_size(group) == 1:
         return search(query, k)
     world, rank = dist.get_world_size(group), dist.get_rank(group)

@@ -170,6 +170,36 @@ int ffr_topk_merge(ffr_handle* h, const float* score, const int64_t* index, int 
 int ffr_search_topk_subjects(ffr_handle* h, const float* query, int Q, const float* gallery, const float* gallery_norms,
                              const int32_t* gallery_subject, long long G, int dim, int k, long long index_base,
                              int distinct, float* top_score, int64_t* top_index, int32_t* top_subject, void* stream);
+/* Filtered 1:N search: the subject search under a per-probe filter, one call for a batch of probes that may each see
+ * another part of the gallery (a camera's watchlists, a tenant's enrolments, the people cleared for a door).
+ * gallery_tag[G] is one 32-bit word per enrolled row and query_mask[Q] one per probe (uint32, device, 4-byte aligned).
+ *   admissible  row g is admissible for probe q iff (gallery_tag[g] & query_mask[q]) != 0 and (gallery_subject == NULL or
+ *          gallery_subject[g] >= 0).  A row with tag 0 is admissible for nobody, a probe with mask 0 gets k slots of
+ *          padding, and bit 31 is a bit like any other: the words are unsigned.
+ *   result for every probe q, bit for bit what ffr_search_topk_subjects gives that probe, with the same distinct, over the
+ *          gallery in which every row inadmissible for q is marked removed: scores, indices, subjects, the tie order and
+ *          the (-inf, -1, -1) padding.  With gallery_subject == NULL only distinct = 0 is legal, the result is that of
+ *          ffr_search_topk over the admissible rows with their original indices, and top_subject (NULL then, as it is NULL
+ *          iff gallery_subject is) is not touched.  Limits as above: k <= 128 rows, k <= 64 identities, dim = 512.
+ *   bitwise  a (q, g) score is the same MFMA chain wherever it is computed, so row q of a Q-probe call equals the 1-probe
+ *          call with query_mask[q], results do not depend on the chunking, and contiguous shards searched with their
+ *          index_base and merged by ffr_topk_merge / ffr_topk_merge_subjects equal one search: the lists hold admissible
+ *          rows only, so the merges need not know the filter.  The identity-mode shard argument above holds per probe, with
+ *          "rows" read as "rows admissible for this probe": best(u) is the first ADMISSIBLE row of u, in every shard and
+ *          globally, and nothing in the argument compares rows of two probes.
+ *   cost   every row is still read and scored; the filter costs 4 G + 4 Q bytes more than the subject search.  When a filter
+ *          is fixed for long and admits a small share of the gallery, a second gallery of those rows is searched faster.
+ *   memory no host synchronisation; the scratch is the search scratch of the handle, so a call can be captured into a
+ *          hipGraph once it has run at that shape.
+ * Errors are those of ffr_search_topk_subjects (G = 0 gives all padding), and FFR_ERR_ARG for a NULL query_mask, a NULL
+ * gallery_tag when G > 0, either of them not 4-byte aligned, distinct = 1 with a NULL gallery_subject, and a NULL top_subject
+ * with a non-NULL gallery_subject (or the reverse when G > 0).
+ * Profiled as one launch under FFR_KC_SCORE with flops = 2*Q*G*512.                                                      */
+int ffr_search_topk_filtered(ffr_handle* h, const float* query, const uint32_t* query_mask, int Q, const float* gallery,
+                             const float* gallery_norms, const uint32_t* gallery_tag,
+                             const int32_t* gallery_subject /* may be NULL */, long long G, int dim, int k, long long index_base,
+                             int distinct, float* top_score, int64_t* top_index,
+                             int32_t* top_subject /* NULL iff gallery_subject is NULL */, void* stream);
 /* ffr_topk_merge with a subject per entry (subject[S][Q][k]); distinct = 1 keeps the first entry of every subject and
  * needs k <= 64.  Slots with index < 0 are padding.                                                                       */
 int ffr_topk_merge_subjects(ffr_handle* h, const float* score, const int64_t* index, const int32_t* subject, int S, int Q,
