@@ -2,11 +2,13 @@
 """Filtered identification on synthetic images (needs an MI355X): people enrolled on overlapping watchlists, probes from
 cameras with different subscriptions, searched in ONE call ("Filters").
 
-    python examples/identify_watchlists_synthetic.py [--identities 24] [--views 4]
+    python examples/identify_watchlists_synthetic.py [--identities 24] [--views 4] [--coarse]
 
 An "identity" is a random image, a "view" of it the same image under pixel noise; the probes are further views.  Watchlist w
 is bit w of a person's tag word; a camera's mask word has the bits of the watchlists it is subscribed to.  A person is
 admissible for a camera iff the two words share a bit.
+--coarse: the gallery gets its bf16 plane (build_plane()) and shortlist_filtered = True, so every masked search goes through
+the certified shortlist -- the same results bit for bit, which the example checks against the exact filtered search.
 """
 import argparse, json, os, sys
 import torch
@@ -24,6 +26,7 @@ def main():
     ap.add_argument('--identities', type=int, default=24)
     ap.add_argument('--views', type=int, default=4)
     ap.add_argument('--noise', type=float, default=0.25)
+    ap.add_argument('--coarse', action='store_true', help='masked searches through the certified bf16 shortlist')
     a = ap.parse_args()
     specs = json.load(open(os.path.join(ROOT, 'tests', 'golden', 'g0_state_dict_keys.json')))
     eng = ffrnet_amd.Engine(0)
@@ -45,6 +48,9 @@ def main():
     gallery.build_tags()                                                  # a tag word beside every row from here on
     gallery.add(f_enrol, who.cuda(), tags=lists[who])                     # int64 words in [0, 2^32), or int32 bit patterns
     print('%d rows of %d identities enrolled on %d watchlists' % (len(gallery), a.identities, 4))
+    if a.coarse:
+        gallery.build_plane()                                             # packs the rows held; add() packs from here on
+        gallery.shortlist_filtered = True                                 # masked searches take the shortlist: opt-in
 
     # every probe is seen by every camera: one batch, one call, one mask word per probe
     names = list(CAMERAS)
@@ -53,6 +59,12 @@ def main():
     mask = torch.tensor([CAMERAS[c] for c in names])[cam]
     k = min(3, a.identities)
     scores, subjects, index = gallery.search_subjects(query, k, mask=mask)
+    if a.coarse:
+        es, ei, eu = eng.search_filtered(query, mask, gallery.embeddings, gallery.tags, k, gallery_norms=gallery.norms,
+                                         subjects=gallery.subjects, distinct=True)
+        assert torch.equal(scores, es) and torch.equal(index, ei) and torch.equal(subjects, eu)
+        print('shortlist: the bits of the exact filtered search; certified for %d of %d probes'
+              % (int(gallery.last_certified.sum()), query.size(0)))
     seen = subjects.cpu()
     ok = (seen < 0) | ((lists[seen.clamp(min=0)] & mask[:, None]) != 0)
     assert bool(ok.all())                                                 # nobody outside a camera's watchlists is ever listed

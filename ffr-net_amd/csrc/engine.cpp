@@ -282,8 +282,8 @@ int ffr_row_norms(ffr_handle* h, const float* x, long long n, int dim, float* no
 // What the search and merge entries share.  Lists [..][Q][k] of scores and indices; u: their subject plane, null in an entry
 // without subjects -- what tells the two kinds of entry apart from here on (12 or 16 bytes per slot)
 struct TopLists { float* s = nullptr; int64_t* i = nullptr; int32_t* u = nullptr; };
-// The per-probe filter of ffr_search_topk_filtered: tag[G] and qmask[Q]; both null in every other entry -- what tells the
-// filtered search apart from here on (qmask is never null in it, tag only at G = 0)
+// The per-probe filter of ffr_search_topk_filtered and ffr_search_topk_coarse_filtered: tag[G] and qmask[Q]; both null in every
+// other entry -- what tells the filtered searches apart from here on (qmask is never null in them, tag only at G = 0)
 struct SearchFilter { const uint32_t* tag = nullptr; const uint32_t* qmask = nullptr; };
 
 static bool misaligned4(const void* p) { return ((uintptr_t)p & 3) != 0; }
@@ -295,7 +295,7 @@ static int check_distinct(ffr_handle* h, const char* who, int distinct, int k) {
     return FFR_OK;
 }
 
-// The checks of the five search entries, in the order every entry makes them: handle, dim, null pointers and ranges (at
+// The checks of the six search entries, in the order every entry makes them: handle, dim, null pointers and ranges (at
 // G = 0 the gallery side may be null), distinct and the k of identity mode, 16-byte rows, 4-byte subjects, 4-byte tags and
 // masks.  coarse: the entry takes plane and plane_flag; subj: it takes subject and top.u (an entry without passes distinct = 0,
 // or is refused); flt (or null): it takes tag and qmask.  `who` names it in messages.
@@ -443,14 +443,17 @@ int ffr_coarse_pack(ffr_handle* h, const float* rows, const float* norms, long l
     return FFR_OK;
 }
 
-// The shortlist search of checked arguments: ffr_search_topk_coarse (subject = null), and ffr_search_topk_coarse_subjects,
-// whose pass skips the removed rows, whose lists carry a subject plane and whose exact pass is the subject search
+// The shortlist search of checked arguments: ffr_search_topk_coarse (subject = null), ffr_search_topk_coarse_subjects,
+// whose pass skips the removed rows, whose lists carry a subject plane and whose exact pass is the subject search, and
+// ffr_search_topk_coarse_filtered (flt), whose pass also skips the rows inadmissible for the probe and whose exact pass is the
+// filtered search, every gathered probe under its own mask
 static int coarse_search(ffr_handle* h, const float* query, int Q, const float* gallery, const float* gallery_norms,
                          const uint16_t* gallery_plane, const int* plane_flag, const int32_t* subject, long long G, int dim, int k,
-                         long long index_base, int distinct, const TopLists& top, int* certified, hipStream_t st) {
+                         long long index_base, int distinct, const TopLists& top, int* certified, hipStream_t st,
+                         const SearchFilter& flt = {}) {
     if (G == 0 || k > coarse_max_k(distinct)) {  // nothing to shortlist, or a k the pass does not serve (64 rows, 32 identities):
         if (certified) HIPCK(h, hipMemsetAsync(certified, 0, sizeof(int) * (size_t)Q, st));      // the exact search alone
-        return exact_search(h, query, Q, gallery, gallery_norms, subject, G, dim, k, index_base, distinct, top, st);
+        return exact_search(h, query, Q, gallery, gallery_norms, subject, G, dim, k, index_base, distinct, top, st, flt);
     }
     const int kp = coarse_shortlist_size(k, distinct);
     int T = 0, S = 0, Tf = 0, Sf = 0;
@@ -459,11 +462,12 @@ static int coarse_search(ffr_handle* h, const float* query, int Q, const float* 
     coarse_fallback_plan(Q, G, h->num_cus, &Tf, &Sf, &chunk_f);
     // scratch: probe norms [Q]; shortlists [Q][kp]; the uncertified probes' ids [Q], count, rows [Q][512], norms [Q] and exact
     // lists [Q][k]; the chunk lists of the coarse pass [S][Q][kp] and then of the exact pass [Sf][Q][k], in the same space;
-    // with subjects, a third plane for the exact lists and their chunk lists
+    // with subjects, a third plane for the exact lists and their chunk lists; with a filter, the uncertified probes' masks [Q]
     const size_t part_n = std::max(S > 1 ? (size_t)S * Q * kp : 0, Sf > 1 ? (size_t)Sf * Q * k : 0);
     float *qnorm = nullptr, *uq = nullptr, *uqn = nullptr;
     TopLists sl, fb, part;
     int *ulist = nullptr, *ucount = nullptr;
+    uint32_t* uqm = nullptr;
     RC(carve(h, h->search, "search", [&](Arena& a) {
         qnorm = a.take(Q);
         sl.s = a.take((size_t)Q * kp); sl.i = a.take<int64_t>((size_t)Q * kp);
@@ -475,22 +479,27 @@ static int coarse_search(ffr_handle* h, const float* query, int Q, const float* 
             fb.u = a.take<int32_t>((size_t)Q * k);
             if (Sf > 1) part.u = a.take<int32_t>((size_t)Sf * Q * k);
         }
+        if (flt.qmask) uqm = a.take<uint32_t>(Q);
     }));
     Scope s(h, st, FFR_KC_SCORE, 2.0 * Q * (double)G * dim,
-            2.0 * (double)G * (dim + 2) + 4.0 * Q * dim + 12.0 * Q * (k + kp) + (subject ? 4.0 * (double)G + 4.0 * Q * k : 0.0));
+            2.0 * (double)G * (dim + 2) + 4.0 * Q * dim + 12.0 * Q * (k + kp) + (subject ? 4.0 * (double)G + 4.0 * Q * k : 0.0) +
+                (flt.qmask ? 4.0 * (double)G + 4.0 * Q : 0.0));
     HIPCK(h, launch_row_norms(query, Q, qnorm, st));
     HIPCK(h, hipMemsetAsync(ucount, 0, sizeof(int), st));
     // the coarse pass: shortlists by coarse score, index = gallery row (no base), every probe, without a subject plane
     const TopLists& cl = S > 1 ? part : sl;
     const SearchArgs ca{query, qnorm, nullptr, gallery_plane, gallery_norms, G, chunk_rows, 0, cl.s, cl.i, nullptr, Q, kp, S, T,
-                        subject, nullptr};
-    HIPCK(h, launch_search(ca, subject ? SEARCH_COARSE_LIVE : SEARCH_COARSE, st));
+                        subject, nullptr, flt.tag, flt.qmask};
+    static_assert(SEARCH_COARSE_LIVE - SEARCH_COARSE == 1 && SEARCH_COARSE_FILTERED_LIVE - SEARCH_COARSE_FILTERED == 1,
+                  "the live kernel follows the plain one");
+    HIPCK(h, launch_search(ca, (SearchKernel)((flt.qmask ? SEARCH_COARSE_FILTERED : SEARCH_COARSE) + (subject ? 1 : 0)), st));
     if (S > 1) HIPCK(h, launch_topk_merge(part.s, part.i, nullptr, S, Q, kp, 0, sl.s, sl.i, nullptr, st));
     HIPCK(h, launch_search_rescore(query, qnorm, Q, gallery, gallery_norms, sl.s, sl.i, plane_flag, G, k, kp, index_base, top.s, top.i,
-                                   certified, ulist, ucount, st, subject, distinct, top.u));
+                                   certified, ulist, ucount, st, subject, distinct, top.u, flt.qmask != nullptr));
     // the exact search of the probes that were not certified, sized for Q: tiles past the device count leave at once
-    HIPCK(h, launch_probe_gather(query, qnorm, ulist, ucount, Q, uq, uqn, st));
-    RC(exact_pass(h, uq, uqn, Q, gallery, gallery_norms, subject, G, k, index_base, distinct, Tf, Sf, chunk_f, fb, part, ucount, st));
+    HIPCK(h, launch_probe_gather(query, qnorm, ulist, ucount, Q, uq, uqn, st, flt.qmask, uqm));
+    RC(exact_pass(h, uq, uqn, Q, gallery, gallery_norms, subject, G, k, index_base, distinct, Tf, Sf, chunk_f, fb, part, ucount, st,
+                  SearchFilter{flt.tag, uqm}));
     HIPCK(h, launch_topk_scatter(fb.s, fb.i, ulist, ucount, Q, k, top.s, top.i, st, fb.u, top.u));
     return FFR_OK;
 }
@@ -516,6 +525,22 @@ int ffr_search_topk_coarse_subjects(ffr_handle* h, const float* query, int Q, co
                   gallery_subject, G, dim, k, distinct, top, true));
     return coarse_search(h, query, Q, gallery, gallery_norms, gallery_plane, plane_flag, gallery_subject, G, dim, k, index_base, distinct,
                          top, certified, (hipStream_t)stream);
+}
+
+// The filtered search through the shortlist: checked as ffr_search_topk_filtered and as the coarse entries are
+int ffr_search_topk_coarse_filtered(ffr_handle* h, const float* query, const uint32_t* query_mask, int Q, const float* gallery,
+                                    const float* gallery_norms, const uint16_t* gallery_plane, const int* plane_flag,
+                                    const uint32_t* gallery_tag, const int32_t* gallery_subject, long long G, int dim, int k,
+                                    long long index_base, int distinct, float* top_score, int64_t* top_index, int32_t* top_subject,
+                                    int* certified, void* stream) {
+    FFR_DEVICE_SCOPE(h);
+    const TopLists top{top_score, top_index, top_subject};
+    const SearchFilter flt{gallery_tag, query_mask};
+    const bool subj = gallery_subject || top_subject;
+    RC(search_pre(h, "ffr_search_topk_coarse_filtered", true, query, Q, gallery, gallery_norms, gallery_plane, plane_flag,
+                  gallery_subject, G, dim, k, distinct, top, subj, &flt));
+    return coarse_search(h, query, Q, gallery, gallery_norms, gallery_plane, plane_flag, gallery_subject, G, dim, k, index_base, distinct,
+                         top, certified, (hipStream_t)stream, flt);
 }
 
 // ---- clustering (cluster.hip) ----------------------------------------------------------------------------------------

@@ -279,12 +279,14 @@ struct SearchArgs {
 // The instantiations search_block<COARSE, SUBJ, OUT_U, TAG> has, by kernel: the exact tile with the policy SR_ROWS (k_search_topk),
 // SR_LIVE and SR_DISTINCT (k_search_subjects: subject[G], < 0 = a removed row, never listed, and a third plane out_u of
 // subjects; SR_DISTINCT lists subjects, each by its best row, k <= search_max_k_distinct()); the coarse tile with SR_ROWS
-// (k_search_coarse) and, under the removal mask, SR_LIVE without the subject plane (k_search_coarse_live); and the exact
-// tile with each of the three policies under the per-probe filter of tag and qmask (k_search_filtered).  New kernels go at
-// the end: the values are the positions in the table of launch_search
+// (k_search_coarse) and, under the removal mask, SR_LIVE without the subject plane (k_search_coarse_live); the exact
+// tile with each of the three policies under the per-probe filter of tag and qmask (k_search_filtered); and the coarse tile
+// with SR_ROWS and SR_LIVE under that filter, without the subject plane (k_search_coarse_filtered, k_search_coarse_filtered_live).
+// New kernels go at the end: the values are the positions in the table of launch_search
 enum SearchKernel {
     SEARCH_ROWS, SEARCH_LIVE, SEARCH_DISTINCT, SEARCH_COARSE, SEARCH_COARSE_LIVE,
-    SEARCH_FILTERED_ROWS, SEARCH_FILTERED_LIVE, SEARCH_FILTERED_DISTINCT
+    SEARCH_FILTERED_ROWS, SEARCH_FILTERED_LIVE, SEARCH_FILTERED_DISTINCT,
+    SEARCH_COARSE_FILTERED, SEARCH_COARSE_FILTERED_LIVE
 };
 int search_max_k_distinct();
 // top-k lists [nchunks][Q][k] of every gallery chunk (one launch of nchunks x ntiles blocks); k <= 128.  The coarse kernels
@@ -306,19 +308,23 @@ int coarse_max_k(int distinct = 0);
 void coarse_fallback_plan(int Q, long long G, int num_cus, int* ntiles, int* nchunks, long long* chunk_rows);
 // plane[r] = bf16(rows[r] / norms[r]) of [n][512] rows; *flag |= 1 when a norm is unsafe (not zero and outside [2^-60, 2^60])
 hipError_t launch_coarse_pack(const float* rows, const float* norms, long long n, uint16_t* plane, int* flag, hipStream_t stream);
-// k_search_coarse (live: k_search_coarse_live), for the table of launch_search: shortlists [nchunks][Q][kp] of every plane
-// chunk, merged by launch_topk_merge
-const void* search_coarse_kernel(bool live);
+// k_search_coarse (live: k_search_coarse_live; filtered: k_search_coarse_filtered and k_search_coarse_filtered_live), for the
+// table of launch_search: shortlists [nchunks][Q][kp] of every plane chunk, merged by launch_topk_merge
+const void* search_coarse_kernel(bool live, bool filtered = false);
 // exact scores of the shortlists sl[Q][kp], the certificate, the certified probes' top-k -> top[Q][k]; the others' ids ->
 // ulist[0 .. *ucount) (ucount zero before the launch); certified[Q] (0 / 1) may be null.  subject[G] (or null): shortlists of
-// live rows; top_u[Q][k] gets the subjects, and with distinct the lists hold subjects, each by its best row
+// live rows; top_u[Q][k] gets the subjects, and with distinct the lists hold subjects, each by its best row.  filtered: the
+// shortlists came from k_search_coarse_filtered(_live); a list shorter than kp is then every row its probe may see, as it
+// is under removals
 hipError_t launch_search_rescore(const float* query, const float* qnorm, int Q, const float* gallery, const float* gnorm,
                                  const float* sl_s, const int64_t* sl_i, const int* plane_flag, long long G, int k, int kp,
                                  long long index_base, float* top_s, int64_t* top_i, int* certified, int* ulist, int* ucount,
-                                 hipStream_t stream, const int32_t* subject = nullptr, int distinct = 0, int32_t* top_u = nullptr);
-// uq[i] = query[ulist[i]], uqn[i] = qnorm[ulist[i]] for i < *ucount (grid sized for Q)
+                                 hipStream_t stream, const int32_t* subject = nullptr, int distinct = 0, int32_t* top_u = nullptr,
+                                 bool filtered = false);
+// uq[i] = query[ulist[i]], uqn[i] = qnorm[ulist[i]] for i < *ucount (grid sized for Q); with qmask (or null) also
+// uqm[i] = qmask[ulist[i]], the mask words of a filtered search
 hipError_t launch_probe_gather(const float* query, const float* qnorm, const int* ulist, const int* ucount, int Q, float* uq,
-                               float* uqn, hipStream_t stream);
+                               float* uqn, hipStream_t stream, const uint32_t* qmask = nullptr, uint32_t* uqm = nullptr);
 // top[ulist[i]] = fb[i] for i < *ucount: the lists [k] of the exact pass back to their probes (fb_u -> top_u: their subject
 // plane, or null)
 hipError_t launch_topk_scatter(const float* fb_s, const int64_t* fb_i, const int* ulist, const int* ucount, int Q, int k,

@@ -181,7 +181,8 @@ hipError_t launch_search(const SearchArgs& a, SearchKernel kernel, hipStream_t s
     const void* const fn[] = {(const void*)k_search_topk, (const void*)k_search_subjects<SR_LIVE>,
                               (const void*)k_search_subjects<SR_DISTINCT>, search_coarse_kernel(false), search_coarse_kernel(true),
                               (const void*)k_search_filtered<SR_ROWS>, (const void*)k_search_filtered<SR_LIVE>,
-                              (const void*)k_search_filtered<SR_DISTINCT>};
+                              (const void*)k_search_filtered<SR_DISTINCT>, search_coarse_kernel(false, true),
+                              search_coarse_kernel(true, true)};
     const size_t lds = sr_lds_bytes(a.k, kernel == SEARCH_DISTINCT || kernel == SEARCH_FILTERED_DISTINCT);
     hipError_t e = hipFuncSetAttribute(fn[kernel], hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;

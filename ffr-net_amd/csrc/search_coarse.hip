@@ -60,6 +60,24 @@
 // the list holds).  The probes that are not certified go through k_search_subjects / k_topk_merge_subjects with the device
 // count, and their lists come back with the subject plane.
 //
+// Filter (ffr_search_topk_coarse_filtered).  Under the per-probe filter of ffr_search_topk_filtered -- row g is admissible for
+// probe q iff (tag[g] & qmask[q]) != 0 and (no subjects, or subject[g] >= 0) -- the pass over the plane is the <true, SR_ROWS
+// | SR_LIVE, false, true> instantiation of search_core.h (k_search_coarse_filtered, k_search_coarse_filtered_live): rows in
+// both modes, no subject merge, the mask word in a register and the 16 tag words beside the norms, LDS as before.  All of
+// the above holds per probe with "live row" read as "row admissible for this probe".  L is the k' best admissible rows by
+// (descending c, ascending index); every admissible row outside L has c <= c_k', hence s <= c_k' + eps, eps unchanged: the
+// bound is about one (q, g) pair and knows no filter.  The probe is certified iff the plane flag is clear, its norm is safe,
+// and either L holds fewer than k' rows or G <= k' (L is then every admissible row of this probe: under a filter, as under
+// removals, G > k' does not mean a full list), or -- identities -- at least k entries are alive, and c_k' + eps < s_k,
+// strictly.  The proof for identities above goes through word for word: a person speaks with the best row the probe may
+// see, best(u) and "a row outside L" range over the admissible rows of that one probe, and nothing in it compares rows of
+// two probes.  Every listed row is admissible by construction, so k_search_rescore reads no tags; its one change is that a
+// short list counts as whole without subjects too (the <false, true> instantiation; the two others are as they were).  A
+// probe with mask 0 has an empty list: certified, k slots of padding, what the exact filtered search gives it.
+// k_probe_gather takes the mask word of an uncertified probe along, and the exact pass is k_search_filtered with each
+// gathered probe's own mask.
+// k' and the k limits are those above: 64 rows, 32 identities; beyond them, and at G = 0, the exact filtered search runs alone.
+//
 // Flops: a coarse search counts 2*Q*G*512, the scores it ranks (the second probe plane, the re-score and the exact pass over
 // uncertified probes are not counted).
 #include <hip/hip_runtime.h>
@@ -94,6 +112,11 @@ __global__ __launch_bounds__(256) void k_coarse_pack(const float* __restrict__ x
 __global__ __launch_bounds__(256, 1) void k_search_coarse(const SearchArgs a) { search_block<true>(a); }
 // under the removal mask: rows with subject < 0 never enter; the shortlist goes out as rows, without a subject plane
 __global__ __launch_bounds__(256, 1) void k_search_coarse_live(const SearchArgs a) { search_block<true, SR_LIVE, false>(a); }
+// under the per-probe filter: a row enters the list of probe q iff (tag[g] & qmask[q]) != 0 (and, _live, subject >= 0)
+__global__ __launch_bounds__(256, 1) void k_search_coarse_filtered(const SearchArgs a) { search_block<true, SR_ROWS, false, true>(a); }
+__global__ __launch_bounds__(256, 1) void k_search_coarse_filtered_live(const SearchArgs a) {
+    search_block<true, SR_LIVE, false, true>(a);
+}
 
 struct RescoreArgs {
     const float* query;       // [Q][512]
@@ -128,7 +151,9 @@ constexpr size_t rs_lds_bytes(bool subj) { return subj ? RS_OFF_A + (size_t)COAR
 // entry carries subject[row], top_u is written beside the list, and with a.distinct the list holds subjects: an entry is
 // ALIVE iff no other entry of its subject comes before it in the total order, its place is the number of alive entries
 // before it, and s_k is the score of the k-th alive entry (two passes over the <= 128 entries, one barrier between them).
-template <bool SUBJ>
+// SHORT: a list shorter than k' is every row its probe may see, also at G > k' -- removals (SUBJ) and the filter leave lists
+// short; the third instantiation, <false, true>, is the filtered shortlist of a gallery without subjects.
+template <bool SUBJ, bool SHORT = SUBJ>
 __global__ __launch_bounds__(256, 1) void k_search_rescore(const RescoreArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
     f32x4* qf = (f32x4*)sm;
@@ -211,7 +236,7 @@ __global__ __launch_bounds__(256, 1) void k_search_rescore(const RescoreArgs a) 
     if (out && rank == k - 1) sk[0] = rs[tid];
     const int nv = __syncthreads_count(live);            // listed rows (padding is at the end)
     const int no = SUBJ ? __syncthreads_count(out) : nv; // entries the list can hold
-    const bool whole = a.G <= kp || (SUBJ && nv < kp);    // the shortlist is every (live) row: under a mask, G > k' need not fill it
+    const bool whole = a.G <= kp || (SHORT && nv < kp);   // every row the probe may see: under a mask or a filter, G > k' need not fill the list
     bool ok = *a.plane_flag == 0 && coarse_safe_norm(qn) && !qbad;
     if (ok && !whole) ok = nv == kp && no >= k && a.sl_s[(size_t)qi * kp + kp - 1] + COARSE_EPS < sk[0];
     if (tid == 0) {
@@ -234,12 +259,16 @@ __global__ __launch_bounds__(256, 1) void k_search_rescore(const RescoreArgs a) 
 
 __global__ __launch_bounds__(128) void k_probe_gather(const float* __restrict__ query, const float* __restrict__ qnorm,
                                                       const int* __restrict__ ulist, const int* __restrict__ ucount,
-                                                      float* __restrict__ uq, float* __restrict__ uqn) {
+                                                      float* __restrict__ uq, float* __restrict__ uqn,
+                                                      const uint32_t* __restrict__ qmask, uint32_t* __restrict__ uqm) {
     const int i = blockIdx.x;
     if (i >= *ucount) return;
     const int src = ulist[i];
     ((f32x4*)(uq + (size_t)i * CT_DIM))[threadIdx.x] = ((const f32x4*)(query + (size_t)src * CT_DIM))[threadIdx.x];
-    if (threadIdx.x == 0) uqn[i] = qnorm[src];
+    if (threadIdx.x == 0) {
+        uqn[i] = qnorm[src];
+        if (qmask) uqm[i] = qmask[src];                   // filtered: the probe keeps its own mask in the exact pass
+    }
 }
 
 __global__ __launch_bounds__(64) void k_topk_scatter(const float* __restrict__ fb_s, const int64_t* __restrict__ fb_i,
@@ -272,16 +301,20 @@ hipError_t launch_coarse_pack(const float* rows, const float* norms, long long n
     return hipGetLastError();
 }
 
-const void* search_coarse_kernel(bool live) { return live ? (const void*)k_search_coarse_live : (const void*)k_search_coarse; }
+const void* search_coarse_kernel(bool live, bool filtered) {
+    if (filtered) return live ? (const void*)k_search_coarse_filtered_live : (const void*)k_search_coarse_filtered;
+    return live ? (const void*)k_search_coarse_live : (const void*)k_search_coarse;
+}
 
 hipError_t launch_search_rescore(const float* query, const float* qnorm, int Q, const float* gallery, const float* gnorm,
                                  const float* sl_s, const int64_t* sl_i, const int* plane_flag, long long G, int k, int kp,
                                  long long index_base, float* top_s, int64_t* top_i, int* certified, int* ulist, int* ucount,
-                                 hipStream_t stream, const int32_t* subject, int distinct, int32_t* top_u) {
+                                 hipStream_t stream, const int32_t* subject, int distinct, int32_t* top_u, bool filtered) {
     RescoreArgs a{query, qnorm, gallery, gnorm, sl_s, sl_i, plane_flag, G, index_base, top_s, top_i, certified, ulist, ucount, Q, k, kp,
                   subject, top_u, distinct};
     const size_t lds = rs_lds_bytes(subject != nullptr);
-    const void* fn = subject ? (const void*)k_search_rescore<true> : (const void*)k_search_rescore<false>;
+    const void* fn = subject ? (const void*)k_search_rescore<true> : filtered ? (const void*)k_search_rescore<false, true>
+                                                                              : (const void*)k_search_rescore<false>;
     hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     void* args[] = {&a};
@@ -289,8 +322,8 @@ hipError_t launch_search_rescore(const float* query, const float* qnorm, int Q, 
 }
 
 hipError_t launch_probe_gather(const float* query, const float* qnorm, const int* ulist, const int* ucount, int Q, float* uq,
-                               float* uqn, hipStream_t stream) {
-    hipLaunchKernelGGL(k_probe_gather, dim3((unsigned)Q), dim3(128), 0, stream, query, qnorm, ulist, ucount, uq, uqn);
+                               float* uqn, hipStream_t stream, const uint32_t* qmask, uint32_t* uqm) {
+    hipLaunchKernelGGL(k_probe_gather, dim3((unsigned)Q), dim3(128), 0, stream, query, qnorm, ulist, ucount, uq, uqn, qmask, uqm);
     return hipGetLastError();
 }
 

@@ -28,8 +28,9 @@
 //    on the order of arrival (no atomics here either).  The policy goes with either tile, and the chunk's subjects, like its
 //    norms, are a 64-bit base (subject + c0) plus 32-bit offsets.  The threshold argument holds: with k subjects listed, a row at or below the k-th score loses
 //    to k listed entries on score or index, or to its own subject's entry.
-//  - Filter (k_search_filtered, search.hip; include/ffrnet.h, ffr_search_topk_filtered): a second compile-time policy, TAG,
-//    that goes with each of the three above.  The candidate test so far depends on the row alone; TAG adds a term that depends
+//  - Filter (k_search_filtered, search.hip; include/ffrnet.h, ffr_search_topk_filtered; k_search_coarse_filtered and
+//    k_search_coarse_filtered_live, search_coarse.hip; ffr_search_topk_coarse_filtered): a second compile-time policy, TAG,
+//    that goes with each of the three above and with either tile.  The candidate test so far depends on the row alone; TAG adds a term that depends
 //    on the probe too: `(tag[g] & qmask[q]) != 0`.  Lane (n, h) keeps its probe's mask word in a register beside qn_lane (0
 //    for a probe past Q, which takes nothing anyway), and the 16 tag words of the rows it scores are read beside their norms
 //    and subjects, a 64-bit base (tag + c0) plus the same clamped 32-bit offsets.  Nothing else changes and no LDS is added:
@@ -91,7 +92,9 @@ static_assert(sr_lds_bytes(SR_MAX_K) <= 160 * 1024 && sr_lds_bytes(SR_MAX_K_DIST
 // bf16 one under the removal mask.  They differ in the tile and in what the policy adds; the threshold test, the survivor
 // slots and the rank-scatter merge are this text.  OUT_U = false: the lists go out without their subject plane (out_u is not
 // touched and may be null) -- a shortlist of rows, whose reader looks subject[row] up again.  TAG: k_search_filtered
-// (search.hip), the candidate test under the per-probe filter of SearchArgs::tag and qmask.
+// (search.hip), the candidate test under the per-probe filter of SearchArgs::tag and qmask; with the bf16 tile,
+// k_search_coarse_filtered (SR_ROWS) and k_search_coarse_filtered_live (SR_LIVE), both without the subject plane
+// (search_coarse.hip): the shortlist of the rows admissible for each probe.
 template <bool COARSE, int SUBJ = SR_ROWS, bool OUT_U = SUBJ != SR_ROWS, bool TAG = false>
 __device__ __forceinline__ void search_block(const SearchArgs& a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char sm[];

@@ -127,6 +127,8 @@ SYMBOLS = [
     ('ffr_search_topk_coarse', C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, C.c_longlong, C.c_int, C.c_int, C.c_longlong, _P, _P, _P, _P]),
     ('ffr_search_topk_coarse_subjects', C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, _P, C.c_longlong, C.c_int, C.c_int, C.c_longlong, C.c_int,
                                                   _P, _P, _P, _P, _P]),
+    ('ffr_search_topk_coarse_filtered', C.c_int, [_P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, C.c_longlong, C.c_int, C.c_int, C.c_longlong,
+                                                  C.c_int, _P, _P, _P, _P, _P]),
     ('ffr_cluster_threshold', C.c_int, [_P, _P, _P, C.c_longlong, C.c_int, C.c_float, _P, _P]),
     ('ffr_cluster_templates', C.c_int, [_P, _P, _P, _P, _P, C.c_longlong, C.c_int, _P, _P]),
     ('ffr_cluster_extend', C.c_int, [_P, _P, _P, C.c_longlong, C.c_longlong, C.c_int, C.c_float, _P, _P, _P]),
@@ -518,9 +520,9 @@ class Engine(object):
         return query, gallery, gallery_norms, G
 
     def _search(self, who, query, gallery, k, gallery_norms, index_base, coarse=None, subj=None, flt=None):
-        """The body of the five searches.  coarse: (plane, flag) of search_coarse(); subj: (subjects, distinct) of
-        search_subjects(); flt: (mask, tags) of search_filtered(), whose entry takes subjects or NULL in their place
-        -> [scores, index(, subjects)(, certified)].  The arguments go in the order of include/ffrnet.h; the tensors stay
+        """The body of the six searches.  coarse: (plane, flag) of search_coarse(); subj: (subjects, distinct) of
+        search_subjects(); flt: (mask, tags) of search_filtered(), whose entry takes subjects or NULL in their place; coarse
+        and flt together: search_coarse_filtered() -> [scores, index(, subjects)(, certified)].  The arguments go in the order of include/ffrnet.h; the tensors stay
         referenced until the call is made."""
         query, gallery, gallery_norms, G = self._search_inputs(query, gallery, gallery_norms, who)
         Q, k = query.size(0), int(k)
@@ -556,10 +558,9 @@ class Engine(object):
             tail.append(int(bool(subj[1])))
             out.append(self._empty(Q, max(k, 0), dtype=torch.int32))
             name += '_subjects' if flt is None else ''
-        if coarse is not None:
-            out.append(self._empty(Q, dtype=torch.int32))
-        self._call(getattr(self.lib, name), *[a if isinstance(a, int) else _ptr(a) for a in head + tail + out + null_out])
-        return out
+        cert = [self._empty(Q, dtype=torch.int32)] if coarse is not None else []     # behind top_subject, NULL or not
+        self._call(getattr(self.lib, name), *[a if isinstance(a, int) else _ptr(a) for a in head + tail + out + null_out + cert])
+        return out + cert
 
     def search(self, query, gallery, k, gallery_norms=None, index_base=0):
         """Exact cosine top-k: query[Q,512], gallery[G,512] (device fp32) -> (scores[Q,k] fp32, index[Q,k] int64), per
@@ -652,6 +653,20 @@ class Engine(object):
         (distinct=True) and k <= 64 rows; above, the exact search runs alone.  return_certified: also certified[Q] int32."""
         out = self._search('search_coarse_subjects', query, gallery, k, gallery_norms, index_base, coarse=(plane, flag),
                            subj=(subjects, distinct))
+        return tuple(out if return_certified else out[:-1])
+
+    def search_coarse_filtered(self, query, mask, gallery, plane, flag, tags, k, gallery_norms=None, index_base=0, subjects=None,
+                               distinct=False, return_certified=False):
+        """search_filtered() through the certified bf16 shortlist (include/ffrnet.h: ffr_search_topk_coarse_filtered): the
+        same tuples bit for bit, (scores, index) or with subjects (scores, index, subjects), for every tag and mask pattern.
+        mask, tags, subjects and distinct as search_filtered() takes them, plane and flag as search_coarse() does.  The pass
+        serves k <= 32 identities (distinct=True) and k <= 64 rows; above, the exact filtered search runs alone.
+        return_certified: also certified[Q] int32, 1 where the shortlist of the probe's admissible rows was proven to hold
+        its top-k (a probe with mask 0 is certified: all padding), 0 where the probe went through the exact search."""
+        if subjects is None and distinct:
+            raise RuntimeError('ffrnet_amd: search_coarse_filtered: distinct=True needs subjects')
+        out = self._search('search_coarse_filtered', query, gallery, k, gallery_norms, index_base, coarse=(plane, flag),
+                           flt=(mask, tags), subj=None if subjects is None else (subjects, distinct))
         return tuple(out if return_certified else out[:-1])
 
     def topk_merge_subjects(self, scores, index, subjects, distinct=True):

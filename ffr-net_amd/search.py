@@ -35,7 +35,10 @@ batch of probes with different masks:
   gallery.set_subject_tags([7], 0b0101)    # person 7 moves to watchlists 0 and 2
 
 The filtered search is exact and reads every row.  A filter that stays fixed for long and admits a small share of the rows
-is served faster by a second Gallery of those rows (INTEGRATION.md section 7 has the measured crossover).
+is served faster by a second Gallery of those rows (INTEGRATION.md section 7 has the measured crossover).  On a gallery
+with a plane, gallery.shortlist_filtered = True sends a masked search through the certified bf16 shortlist (include/ffrnet.h:
+ffr_search_topk_coarse_filtered): the same results, half the bytes per row; off by default (INTEGRATION.md section 7 says when
+it pays).
 """
 import functools
 
@@ -76,7 +79,9 @@ class Gallery(object):
     shortlist on for the rows a gallery holds already, with or without subjects.  build_tags() switches tags on, for an
     empty gallery or one that holds rows: a 32-bit tag word (int32 carrying the pattern) grows beside every row, add() takes
     the words, set_tags() / set_subject_tags() change them, and search(mask=) / search_subjects(mask=) rank per probe the
-    rows whose tag shares a bit with the probe's mask word."""
+    rows whose tag shares a bit with the probe's mask word.  Such a search is the exact filtered one, also on a gallery with
+    a plane; set the attribute shortlist_filtered = True and a gallery with a plane serves it through the certified
+    shortlist (include/ffrnet.h: ffr_search_topk_coarse_filtered): the same results bit for bit, and last_certified is set."""
 
     def __init__(self, engine, capacity=0, coarse=False, subjects=False):
         if coarse and subjects:
@@ -89,6 +94,7 @@ class Gallery(object):
         self._add_side('_norms', torch.float32, capacity)
         self.coarse = bool(coarse)
         self.last_certified = None
+        self.shortlist_filtered = False     # True: a search with mask= on a gallery with a plane takes the certified shortlist
         self.has_subjects = bool(subjects)
         if self.has_subjects:
             self._add_side('_subj', torch.int32, capacity)
@@ -310,12 +316,19 @@ class Gallery(object):
         return new_index
 
     def _search_filtered(self, query, k, index_base, distinct, mask):
-        """The exact filtered search, also on a gallery that has a plane: the certified pass does not know filters"""
+        """The filtered search -> (scores, index(, subjects)): the exact one, also on a gallery that has a plane, unless
+        shortlist_filtered is set; then a gallery with a plane goes through the certified shortlist, the same results"""
         self._need_tags('search with a mask')
+        subjects = self.subjects if self.has_subjects else None
+        if self.shortlist_filtered and self.coarse:
+            out = self.engine.search_coarse_filtered(query, mask, self.embeddings, self.plane, self._flag, self.tags, k,
+                                                     gallery_norms=self.norms, index_base=index_base, subjects=subjects,
+                                                     distinct=distinct, return_certified=True)
+            self.last_certified = out[-1]
+            return out[:-1]
         self.last_certified = None
         return self.engine.search_filtered(query, mask, self.embeddings, self.tags, k, gallery_norms=self.norms,
-                                           index_base=index_base, subjects=self.subjects if self.has_subjects else None,
-                                           distinct=distinct)
+                                           index_base=index_base, subjects=subjects, distinct=distinct)
 
     def _search(self, query, k, index_base, mask=None):
         if self.has_subjects:           # row mode under the mask: removed rows never come back

@@ -274,6 +274,36 @@ int ffr_search_topk_coarse_subjects(ffr_handle* h, const float* query, int Q, co
                                     const uint16_t* gallery_plane, const int* plane_flag, const int32_t* gallery_subject,
                                     long long G, int dim, int k, long long index_base, int distinct, float* top_score,
                                     int64_t* top_index, int32_t* top_subject, int* certified, void* stream);
+/* The shortlist search under a per-probe filter: the outputs of ffr_search_topk_filtered with the same arguments, bit for bit,
+ * for every input without NaN/inf, with and without subjects, both modes, every removal pattern and every tag and mask pattern.
+ * No approximate mode; certified[Q] says which way each probe went.
+ *   method as ffr_search_topk_coarse_subjects, with "live row" read as "row admissible for this probe" (admissible: see
+ *          ffr_search_topk_filtered).  The pass over the plane ranks ROWS in both modes, per probe the k' best admissible rows
+ *          by (descending c, ascending index), and never merges subjects.  Every listed row is admissible, so the exact
+ *          re-score reads no tags; identities are formed on the <= 128 entries as there.  k' and the k limits are the same:
+ *          64 rows, 32 identities; above them, and at G = 0, ffr_search_topk_filtered runs alone and certified is all 0.
+ *   certificate  L is the k' best admissible rows of the probe, c_1 >= ... >= c_k'.  Every admissible row outside L has
+ *          c <= c_k', hence s <= c_k' + FFR_COARSE_EPS (the bound is about one (q, g) pair and knows no filter).  The probe
+ *          is certified iff the plane flag is clear, its norm is safe, and either L holds fewer than k' rows or G <= k' (then L
+ *          is every admissible row of this probe: under a filter G > k' does not mean a full list), or (distinct = 1) at least
+ *          k entries are alive, and c_k' + FFR_COARSE_EPS < s_k, strictly.  The identity proof above holds unchanged: a person
+ *          speaks with the best row the probe may see, best(u) and "a row outside L" range over the rows admissible for this
+ *          one probe, and nothing in the proof compares rows of two probes.  A probe with mask 0 has an empty shortlist: it
+ *          is certified and gets k slots of padding, as the exact filtered search gives it.
+ *   exact  the probes without a certificate are gathered WITH their mask words and searched by the kernels of
+ *          ffr_search_topk_filtered under the device count; always launched, sized for Q, no host synchronisation: the call
+ *          can be captured into a hipGraph once it has run at that shape.  Scratch comes from the handle's search arena.
+ *   cost   the pass reads the 1 KB plane row where the exact filtered search reads the 2 KB fp32 row, 4 G + 4 Q bytes more
+ *          than ffr_search_topk_coarse_subjects; every row is still read and scored.
+ * Arguments and error codes are the union of ffr_search_topk_filtered and ffr_search_topk_coarse_subjects; the plane and its
+ * flag, like the rest of the gallery side, may be NULL only when G = 0 (all padding).  certified[Q] may be NULL.
+ * Profiled as one launch under FFR_KC_SCORE with flops = 2*Q*G*512.                                                      */
+int ffr_search_topk_coarse_filtered(ffr_handle* h, const float* query, const uint32_t* query_mask, int Q, const float* gallery,
+                                    const float* gallery_norms, const uint16_t* gallery_plane, const int* plane_flag,
+                                    const uint32_t* gallery_tag, const int32_t* gallery_subject /* may be NULL */, long long G,
+                                    int dim, int k, long long index_base, int distinct, float* top_score, int64_t* top_index,
+                                    int32_t* top_subject /* NULL iff gallery_subject is NULL */, int* certified /* may be NULL */,
+                                    void* stream);
 
 /* ---- clustering (unlabelled embeddings -> identities -> one template per identity) ----------------------------------
  * The step in front of enrolment: N unlabelled faces are grouped by single-link clustering at one cosine threshold, and
