@@ -1,6 +1,6 @@
-// libffrnet_hip.so: the convolution launchers -- run_conv executes what plan_conv (plan.cpp) decided: the direct implicit
-// GEMM, the Winograd paths (fused, exact 14x14 tiling, transform kernels + batched GEMM) and the tail split; the plain GEMMs
-// of the training step; the -DFFR_TRACE launch diagnostics.  Host code only.
+// libffrnet_hip.so: the convolution launchers -- run_conv executes the entries of a plan (plan_conv, plan.cpp) and decides
+// nothing itself: the direct implicit GEMM, the Winograd paths (fused, exact 14x14 tiling, transform kernels + batched GEMM)
+// and the tail split; the plain GEMMs of the training step; the -DFFR_TRACE launch diagnostics.  Host code only.
 #include "engine_internal.h"
 
 namespace ffr_eng {
@@ -8,7 +8,9 @@ namespace ffr_eng {
 #ifdef FFR_TRACE
 // ---- diagnostics (options igemm_trace / wf_trace): the launch with in-kernel clock stamps, a stream sync, a summary on stderr
 // k_igemm: per-block clock sums
-static int trace_igemm(ffr_handle* h, IgemmArgs& a, int tile, int nblocks, long long units, hipStream_t st) {
+static int trace_igemm(ffr_handle* h, IgemmArgs& a, const ConvLaunch& e, hipStream_t st) {
+    const int tile = e.gemm.tile, nblocks = e.gemm.nblocks;
+    const long long units = e.gemm.units;
     unsigned long long* dbuf = nullptr;
     HIPCK(h, hipMalloc((void**)&dbuf, (size_t)nblocks * 8 * sizeof(unsigned long long)));
     a.trace = dbuf;
@@ -109,7 +111,8 @@ static int trace_wino_mixed(ffr_handle* h, WinoMixedArgs& f, const ConvW& L, con
 }
 
 // k_wino_fused: per-block phase stamps
-static int trace_wino_fused(ffr_handle* h, WinoFusedArgs& f, const ConvW& L, const ConvCall& c, const ConvPlan& p, hipStream_t st) {
+static int trace_wino_fused(ffr_handle* h, WinoFusedArgs& f, const ConvW& L, const ConvCall& c, const ConvLaunch& e, hipStream_t st) {
+    const ffr_conv_launch& p = e.rec;
     const int nb = wino_fused_blocks(f);
     unsigned long long* dbuf = nullptr;
     HIPCK(h, hipMalloc((void**)&dbuf, (size_t)nb * 40 * sizeof(unsigned long long)));
@@ -153,43 +156,39 @@ static ConvTail conv_tail(const ConvW& L, const ConvCall& c) {
     return ConvTail{L.bias, L.slope, c.resid, c.out, c.tile_sums, L.cout_pad, c.cout_store, c.out_pitch, c.out_coff, c.res_pitch, L.border, c.flags};
 }
 
-// plan + launch one (possibly batched) implicit-GEMM described by `a` (M, nkt, tail.cout_pad, nbatch set)
-int run_gemm(ffr_handle* h, IgemmArgs& a, const ConvCall& c, double flops, double bytes, hipStream_t st, double fuse) {
-    int force = c.tile;
+// the plan record: the entry a launcher is about to execute
+static void record(ffr_handle* h, const ConvLaunch& e) {
+    if (h->conv_rec) h->conv_log.push_back(e.rec);
+}
+
+// launches the planned k_igemm entry e: the (possibly batched) implicit GEMM described by `a` (M, nkt, tail.cout_pad, nbatch set)
+static int run_gemm(ffr_handle* h, IgemmArgs& a, const ConvCall& c, const ConvLaunch& e, double flops, double bytes, hipStream_t st,
+                    double fuse = -1.0) {
+    const GemmPlan& g = e.gemm;
     const int cout_pad = a.tail.cout_pad;
-    if (force) {      // a forced tile whose width does not divide cout_pad would launch zero column tiles and leave `out` unwritten
+    if (c.tile) {     // a forced tile whose width does not divide cout_pad would launch zero column tiles and leave `out` unwritten
         int fbm, fbn;
-        igemm_tile_shape(force, &fbm, &fbn);
-        if (cout_pad % fbn) return fail(h, FFR_ERR_ARG, "conv: forced tile %d (%d x %d) does not divide cout_pad %d", force, fbm, fbn, cout_pad);
+        igemm_tile_shape(c.tile, &fbm, &fbn);
+        if (cout_pad % fbn) return fail(h, FFR_ERR_ARG, "conv: forced tile %d (%d x %d) does not divide cout_pad %d", c.tile, fbm, fbn, cout_pad);
     }
-    const GemmPlan g = plan_gemm_launch(a.M, cout_pad, a.nkt, a.nbatch, force, h->opt.sk_minunits, a.w3 != nullptr, c.partial_cap, c.tickets_cap);
     if (g.nomem) return fail(h, FFR_ERR_NOMEM, "%s", g.nomem);
-    const int tile = g.tile, nblocks = g.nblocks;
-    const long long units = g.units;
-    const bool cut = g.cut;
     int bm, bn;
-    igemm_tile_shape(tile, &bm, &bn);
+    igemm_tile_shape(g.tile, &bm, &bn);
     a.granule = g.granule; a.mtiles = g.mtiles; a.ntiles = g.ntiles;
     a.partial = c.partial;
     a.tickets = c.tickets;
-    if (h->conv_rec) {      // the plan record: what this launch runs with, from the values above
-        ffr_conv_launch r{};
-        r.path = FFR_CP_DIRECT; r.images = a.N; r.rows = a.M;
-        r.tile = tile; r.nblocks = nblocks; r.granule = a.granule; r.nkt = a.nkt; r.tiles = a.nbatch * a.mtiles * a.ntiles;
-        r.cut = cut ? 1 : 0; r.split = a.w3 ? 1 : 0;
-        h->conv_log.push_back(r);
-    }
+    record(h, e);
 #ifdef FFR_TRACE
-    if (h->opt.igemm_trace) return trace_igemm(h, a, tile, nblocks, units, st);
+    if (h->opt.igemm_trace) return trace_igemm(h, a, e, st);
 #endif
     const double fexec = 2.0 * a.nbatch * (double)a.mtiles * bm * (double)cout_pad * a.KK;
     Scope s(h, st, FFR_KC_CONV_IGEMM, flops, bytes, fexec, fuse);
-    HIPCK(h, launch_igemm(a, tile, nblocks, st));
+    HIPCK(h, launch_igemm(a, g.tile, g.nblocks, st));
     return FFR_OK;
 }
 
 // exact tiling 4+4+3+3 of a 14x14 map (wino_mixed.hip): one transform launch and one fused launch for all four tile types
-static int conv_mixed(ffr_handle* h, const ConvW& L, const ConvCall& c, double flops, double bytes, hipStream_t st) {
+static int conv_mixed(ffr_handle* h, const ConvW& L, const ConvCall& c, const ConvLaunch& e, double flops, double bytes, hipStream_t st) {
     WinoMixedGeom g;
     wino_mixed_geom(c.H, c.W, &g);
     if (c.wino_stage == 0) {
@@ -208,12 +207,7 @@ static int conv_mixed(ffr_handle* h, const ConvW& L, const ConvCall& c, double f
         fexec += 2.0 * wino_mixed_xp(tau) * std::ceil(Tt / 32.0) * 32.0 * L.cout_pad * L.cin_pad;
         fuse += 2.0 * wino_mixed_x(tau) * Tt * L.cout * L.cin;
     }
-    if (h->conv_rec) {
-        ffr_conv_launch r{};
-        r.path = FFR_CP_MIXED; r.images = c.N; r.rows = c.N * (g.n4 + g.n3) * (g.n4 + g.n3);
-        r.block_tiles = wino_mixed_blocks(c.N, c.H, c.W, L.cout_pad);
-        h->conv_log.push_back(r);
-    }
+    record(h, e);
 #ifdef FFR_TRACE
     if (h->opt.wf_trace) return trace_wino_mixed(h, f, L, c, st);
 #endif
@@ -223,7 +217,8 @@ static int conv_mixed(ffr_handle* h, const ConvW& L, const ConvCall& c, double f
 }
 
 // Winograd F(4x4,3x3), GEMM + output transform in one kernel (wino_fused.hip): M never exists in memory
-static int conv_fused(ffr_handle* h, const ConvW& L, const ConvCall& c, const ConvPlan& p, double flops, double bytes, hipStream_t st) {
+static int conv_fused(ffr_handle* h, const ConvW& L, const ConvCall& c, const ConvLaunch& e, double flops, double bytes, hipStream_t st) {
+    const ffr_conv_launch& p = e.rec;
     const long long T = (long long)c.N * ((c.H + 3) / 4) * ((c.W + 3) / 4);
     if (!p.phased && c.wino_stage == 0) {
         Scope s(h, st, FFR_KC_WINO, 0, 4.0 * ((double)c.N * c.H * c.W * L.cin + 36.0 * T * L.cin_pad));
@@ -232,19 +227,14 @@ static int conv_fused(ffr_handle* h, const ConvW& L, const ConvCall& c, const Co
     WinoFusedArgs f{};
     f.Vc = p.phased ? nullptr : c.winoV; f.x = c.x; f.in_pitch = c.in_pitch; f.pad_mode = L.pad_mode;
     f.x_bytes = p.phased ? (unsigned)(4.0 * c.N * c.H * c.W * c.in_pitch) : 0u;
-    f.half_n = p.half_n ? 1 : 0;
+    f.half_n = p.half_n;
     f.U3 = p.split ? L.wu3 : nullptr;
     f.Uc = L.wuc; f.tail = conv_tail(L, c);
     f.N = c.N; f.H = c.H; f.W = c.W; f.nkc = L.cin_pad / 8;
     const double fexec = 2.0 * 36.0 * (double)((T + 31) / 32 * 32) * (double)L.cout_pad * L.cin_pad;
-    if (h->conv_rec) {
-        ffr_conv_launch r{};
-        r.path = FFR_CP_FUSED; r.images = c.N; r.rows = (int)T;
-        r.phased = p.phased ? 1 : 0; r.half_n = f.half_n; r.split = f.U3 ? 1 : 0; r.block_tiles = (int)((T + 31) / 32) * (L.cout_pad / (p.half_n ? 32 : 64));
-        h->conv_log.push_back(r);
-    }
+    record(h, e);
 #ifdef FFR_TRACE
-    if (h->opt.wf_trace) return trace_wino_fused(h, f, L, c, p, st);
+    if (h->opt.wf_trace) return trace_wino_fused(h, f, L, c, e, st);
 #endif
     Scope s(h, st, FFR_KC_WINO_FUSED, flops, bytes, fexec, flops / 4.0);      // flops_executed stays the fp32-equivalent count in the split form
     HIPCK(h, launch_wino_fused(f, st));
@@ -253,9 +243,10 @@ static int conv_fused(ffr_handle* h, const ConvW& L, const ConvCall& c, const Co
 }
 
 // nbatch independent GEMMs out[b][M][out_pitch] = A[b][M][K_pad] * W[b][N_pad][K_pad]^T through k_igemm, with the stream-K
-// scratch of c; flops, bytes and fuse are the caller's figures for the profiling scope (run_gemm)
-static int igemm_batched(ffr_handle* h, const ConvCall& c, const float* A, long long a_bstride, int K_pad, const float* W,
-                         long long w_bstride, int N_pad, float* out, int out_pitch, long long out_bstride, int M, int nbatch,
+// scratch of c; flops, bytes and fuse are the caller's figures for the profiling scope (run_gemm).  planned: the entry of a
+// convolution's plan this launch executes, or null: a GEMM of its own, planned here
+static int igemm_batched(ffr_handle* h, const ConvCall& c, const ConvLaunch* planned, const float* A, long long a_bstride, int K_pad,
+                         const float* W, long long w_bstride, int N_pad, float* out, int out_pitch, long long out_bstride, int M, int nbatch,
                          double flops, double bytes, double fuse, hipStream_t st) {
     IgemmArgs g{};
     g.x = A; g.w = W; g.zero = h->zero;
@@ -264,39 +255,31 @@ static int igemm_batched(ffr_handle* h, const ConvCall& c, const float* A, long 
     g.in_pitch = K_pad; g.cin_pad = K_pad; g.R = 1; g.S = 1; g.stride = 1; g.pad = 0; g.pad_mode = 0;
     g.M = M; g.KK = K_pad; g.nkt = K_pad / 32;
     g.nbatch = nbatch; g.x_bstride = a_bstride; g.w_bstride = w_bstride; g.out_bstride = out_bstride;
-    return run_gemm(h, g, c, flops, bytes, st, fuse);
+    return run_gemm(h, g, c, planned ? *planned : plan_gemm_launch(h, c, FFR_CP_DIRECT, 1, M, N_pad, g.nkt, nbatch, false), flops, bytes, st, fuse);
 }
 
 // Winograd F(4x4,3x3): input transform -> 36 batched GEMMs [T x cin] * [cin x cout] -> output transform
-static int conv_unfused(ffr_handle* h, const ConvW& L, const ConvCall& c, long long M, double flops, double bytes, hipStream_t st) {
+static int conv_unfused(ffr_handle* h, const ConvW& L, const ConvCall& c, const ConvLaunch& e, long long M, double flops, double bytes,
+                        hipStream_t st) {
     const long long T = (long long)c.N * ((c.H + 3) / 4) * ((c.W + 3) / 4);
     if (c.wino_stage != 2) {
         Scope s(h, st, FFR_KC_WINO, 0, 4.0 * ((double)c.N * c.H * c.W * L.cin + 36.0 * T * L.cin_pad));
         HIPCK(h, launch_wino_in(c.x, c.winoV, c.N, c.H, c.W, c.in_pitch, L.cin_pad, L.pad_mode, st));
     }
     // the roofline numerator of the GEMM stays the DIRECT convolution's algorithmic FLOPs
-    if (h->opt.gemm_stream) {
+    if (e.rec.path == FFR_CP_UNFUSED_STREAM) {
         // 36 GEMMs in one persistent launch with a continuous K-tile stream
-        int gtile, gblocks;
-        plan_gemm_stream(T, L.cout_pad, &gtile, &gblocks);
         GemmStreamArgs g{};
         g.A = c.winoV; g.W = L.wu; g.C = c.winoM; g.M = (int)T; g.K = L.cin_pad; g.Npad = L.cout_pad; g.nbatch = 36;
         int bm, bn;
-        igemm_tile_shape(gtile, &bm, &bn);
+        igemm_tile_shape(e.rec.tile, &bm, &bn);
         const double fexec = 2.0 * 36.0 * (double)((T + bm - 1) / bm) * bm * (double)L.cout_pad * L.cin_pad;
-        if (h->conv_rec) {
-            ffr_conv_launch r{};
-            r.path = FFR_CP_UNFUSED_STREAM; r.images = c.N; r.rows = (int)T;
-            r.tile = gtile; r.nblocks = gblocks; r.nkt = L.cin_pad / 32; r.granule = r.nkt;       // whole tiles only: nothing is cut
-            r.tiles = (int)(36 * ((T + bm - 1) / bm) * (L.cout_pad / bn));
-            h->conv_log.push_back(r);
-        }
+        record(h, e);
         Scope s(h, st, FFR_KC_CONV_IGEMM, flops, bytes, fexec, flops / 4.0);
-        HIPCK(h, launch_gemm_stream(g, gtile, gblocks, st));
+        HIPCK(h, launch_gemm_stream(g, e.rec.tile, e.rec.nblocks, st));
     } else {
-        RC(igemm_batched(h, c, c.winoV, T * L.cin_pad, L.cin_pad, L.wu, (long long)L.cout_pad * L.cin_pad, L.cout_pad, c.winoM, L.cout_pad,
+        RC(igemm_batched(h, c, &e, c.winoV, T * L.cin_pad, L.cin_pad, L.wu, (long long)L.cout_pad * L.cin_pad, L.cout_pad, c.winoM, L.cout_pad,
                          T * L.cout_pad, (int)T, 36, flops, bytes, flops / 4.0, st));
-        if (h->conv_rec && !h->conv_log.empty()) { h->conv_log.back().path = FFR_CP_UNFUSED_IGEMM; h->conv_log.back().images = c.N; }
     }
     if (c.wino_stage == 1) return FFR_OK;        // the caller transforms M itself (k_wino_out_in)
     Scope s(h, st, FFR_KC_WINO, 0, 4.0 * (36.0 * T * L.cout_pad + (double)M * L.cout));
@@ -304,69 +287,55 @@ static int conv_unfused(ffr_handle* h, const ConvW& L, const ConvCall& c, long l
     return FFR_OK;
 }
 
-// The two calls of a tail split (plan p of call c, p.n_main > 0): c1 = the first n_main images in the fused form of p, c2 = the
-// rest through the transform kernels + batched GEMM, every tensor of c moved on by those images
-void tail_split_calls(const ConvW& L, const ConvCall& c, const ConvPlan& p, ConvCall* c1, ConvCall* c2) {
-    *c1 = c; *c2 = c;
-    c1->N = p.n_main; c1->force = p.half_n ? ConvForce::FusedHalf : p.split ? ConvForce::FusedSplit : ConvForce::Fused;
-    c2->N = c.N - p.n_main; c2->force = ConvForce::Unfused;
-    const size_t px = (size_t)p.n_main * c.H * c.W;
-    if (c.x) c2->x = c.x + px * c.in_pitch;
-    if (c.out) c2->out = c.out + px * c.out_pitch;
-    if (c.resid) c2->resid = c.resid + px * c.res_pitch;
-    if (c.tile_sums) c2->tile_sums = c.tile_sums + (size_t)p.n_main * ((c.H + 3) / 4) * ((c.W + 3) / 4) * L.cout_pad;
-}
-
-// Runs the convolution L on call c as plan_conv plans it
-int run_conv(ffr_handle* h, const ConvW& L, const ConvCall& c, hipStream_t st) {
+// Executes one launching entry e of a plan on the images of call c that it covers, on stream st
+static int run_launch(ffr_handle* h, const ConvW& L, const ConvCall& whole, const ConvLaunch& e, hipStream_t st) {
+    const ConvCall c = conv_part(L, whole, e.n0, e.rec.images);
     const int Ho = (c.H + 2 * L.pad - L.R) / L.stride + 1, Wo = (c.W + 2 * L.pad - L.S) / L.stride + 1;
     const long long M = (long long)c.N * Ho * Wo;
-    if (M <= 0 || M > 0x7fffffffLL) return fail(h, FFR_ERR_ARG, "conv: bad M");
-    if (L.pad_mode == 1 && (c.H < 2 || c.W < 2)) return fail(h, FFR_ERR_UNSUPPORTED, "reflect pad needs H,W >= 2");
-    if (L.border && (c.H < 2 || c.W < 2)) return fail(h, FFR_ERR_UNSUPPORTED, "border-class bias needs H,W >= 2");
     const double flops = 2.0 * M * L.cout * (double)L.R * L.S * L.cin;
     const double bytes = 4.0 * ((double)c.N * c.H * c.W * L.cin + (double)M * L.cout + (double)L.cout * L.R * L.S * L.cin);
-    if (h->conv_rec) {      // a replayed capture would launch without recording
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        HIPCK(h, hipStreamIsCapturing(st, &cs));
-        if (cs != hipStreamCaptureStatusNone) return fail(h, FFR_ERR_STATE, "conv: the plan record is on and the stream is capturing");
-    }
-    const ConvPlan p = plan_conv(h, L, c);
-    if (p.refused) return fail(h, FFR_ERR_STATE, "%s", p.refused);
-    if (p.path == ConvPlan::Mixed) return conv_mixed(h, L, c, flops, bytes, st);
-    if (p.path == ConvPlan::Unfused) return conv_unfused(h, L, c, M, flops, bytes, st);
-    if (p.path == ConvPlan::Fused && !p.n_main) return conv_fused(h, L, c, p, flops, bytes, st);
-    if (p.path == ConvPlan::Fused) {
-        // tail split: the first n_main images fused, the rest through the transform kernels + batched GEMM
-        ConvCall c1, c2;
-        tail_split_calls(L, c, p, &c1, &c2);
-        if (h->conv_rec) {
-            ffr_conv_launch r{};
-            r.path = FFR_CP_TAIL_SPLIT; r.images = c.N; r.rows = c.N * ((c.H + 3) / 4) * ((c.W + 3) / 4);
-            r.n_main = p.n_main; r.side = p.side ? 1 : 0; r.half_n = p.half_n ? 1 : 0; r.phased = p.phased ? 1 : 0; r.split = p.split ? 1 : 0;
-            h->conv_log.push_back(r);
-        }
-        if (p.side) {
-            HIPCK(h, hipEventRecord(h->ev_fork, st));
-            HIPCK(h, hipStreamWaitEvent(p.side, h->ev_fork, 0));
-            RC(run_conv(h, L, c2, p.side));
-            HIPCK(h, hipEventRecord(h->ev_join, p.side));
-            RC(run_conv(h, L, c1, st));
-            HIPCK(h, hipStreamWaitEvent(st, h->ev_join, 0));
-            return FFR_OK;
-        }
-        RC(run_conv(h, L, c1, st));
-        return run_conv(h, L, c2, st);
-    }
+    if (e.rec.path == FFR_CP_MIXED) return conv_mixed(h, L, c, e, flops, bytes, st);
+    if (e.rec.path == FFR_CP_FUSED) return conv_fused(h, L, c, e, flops, bytes, st);
+    if (e.rec.path != FFR_CP_DIRECT) return conv_unfused(h, L, c, e, M, flops, bytes, st);
     IgemmArgs a{};
     a.x = c.x; a.w = L.w; a.tail = conv_tail(L, c); a.zero = h->zero;
     a.N = c.N; a.H = c.H; a.W = c.W; a.Ho = Ho; a.Wo = Wo;
     a.in_pitch = c.in_pitch; a.cin_pad = L.cin_pad; a.R = L.R; a.S = L.S; a.stride = L.stride; a.pad = L.pad; a.pad_mode = L.pad_mode;
     a.M = (int)M; a.KK = L.R * L.S * L.cin_pad; a.nkt = a.KK / 32; a.nbatch = 1;
-    // split-operand form: the layer's weights were split at load time (or by ffr_op_conv's flag) and option igemm_split is on.
-    // flops_executed of the launch stays the fp32-equivalent count (run_gemm)
-    if (L.w3 && h->opt.igemm_split) { a.w3 = L.w3; a.w3_pstride = (long long)L.cout_pad * a.KK; }
-    return run_gemm(h, a, c, flops, bytes, st);
+    // split-operand form (plan.cpp, conv_launch).  flops_executed of the launch stays the fp32-equivalent count (run_gemm)
+    if (e.rec.split) { a.w3 = L.w3; a.w3_pstride = (long long)L.cout_pad * a.KK; }
+    return run_gemm(h, a, c, e, flops, bytes, st);
+}
+
+// Runs the convolution L on call c as its plan p = plan_conv(h, L, c) says: every entry of p, in order
+int run_conv(ffr_handle* h, const ConvW& L, const ConvCall& c, const ConvPlan& p, hipStream_t st) {
+    const long long M = (long long)c.N * ((c.H + 2 * L.pad - L.R) / L.stride + 1) * ((c.W + 2 * L.pad - L.S) / L.stride + 1);
+    if (M <= 0 || M > 0x7fffffffLL) return fail(h, FFR_ERR_ARG, "conv: bad M");
+    if (L.pad_mode == 1 && (c.H < 2 || c.W < 2)) return fail(h, FFR_ERR_UNSUPPORTED, "reflect pad needs H,W >= 2");
+    if (L.border && (c.H < 2 || c.W < 2)) return fail(h, FFR_ERR_UNSUPPORTED, "border-class bias needs H,W >= 2");
+    if (h->conv_rec) {      // a replayed capture would launch without recording
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        HIPCK(h, hipStreamIsCapturing(st, &cs));
+        if (cs != hipStreamCaptureStatusNone) return fail(h, FFR_ERR_STATE, "conv: the plan record is on and the stream is capturing");
+    }
+    if (p.refused) return fail(h, FFR_ERR_STATE, "%s", p.refused);
+    if (p.n_launch == 1) return run_launch(h, L, c, p.launch[0], st);
+    // tail split: the header, then its two parts; with p.side the first of them (the few images behind n_main) runs on that
+    // stream beside the second
+    record(h, p.launch[0]);
+    if (p.side) {
+        HIPCK(h, hipEventRecord(h->ev_fork, st));
+        HIPCK(h, hipStreamWaitEvent(p.side, h->ev_fork, 0));
+    }
+    RC(run_launch(h, L, c, p.launch[1], p.side ? p.side : st));
+    if (p.side) HIPCK(h, hipEventRecord(h->ev_join, p.side));
+    RC(run_launch(h, L, c, p.launch[2], st));
+    if (p.side) HIPCK(h, hipStreamWaitEvent(st, h->ev_join, 0));
+    return FFR_OK;
+}
+
+int run_conv(ffr_handle* h, const ConvW& L, const ConvCall& c, hipStream_t st) {
+    return run_conv(h, L, c, plan_conv(h, L, c), st);
 }
 
 // ---- plain GEMMs through the implicit-GEMM kernel (the training step) -------------------------------------
@@ -389,7 +358,7 @@ int gemm_batched(ffr_handle* h, const Work& w, const float* A, long long a_bstri
                  long long w_bstride, int N_pad, float* out, int out_pitch, long long out_bstride, int M, int nbatch,
                  hipStream_t st) {
     const double fl = 2.0 * nbatch * (double)M * N_pad * K_pad;
-    return igemm_batched(h, conv_call(w, ConvForce::Direct), A, a_bstride, K_pad, W, w_bstride, N_pad, out, out_pitch, out_bstride, M,
+    return igemm_batched(h, conv_call(w, ConvForce::Direct), nullptr, A, a_bstride, K_pad, W, w_bstride, N_pad, out, out_pitch, out_bstride, M,
                          nbatch, fl, 4.0 * nbatch * ((double)M * K_pad + (double)N_pad * K_pad + (double)M * N_pad), fl, st);
 }
 

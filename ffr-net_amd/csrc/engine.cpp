@@ -1157,9 +1157,10 @@ int ffr_op_conv3x3(ffr_handle* h, const float* x, int N, int H, int W, int cin, 
         ConvCall c = conv_call(w, (ConvForce)use_wino);
         c.x = x; c.N = N; c.H = H; c.W = W; c.in_pitch = cin; c.resid = resid; c.res_pitch = cout;
         c.out = out; c.out_pitch = cout; c.out_coff = 0; c.cout_store = cout;
-        rc = run_conv(h, L, c, st);
-        if (rc == FFR_OK && use_wino && (size_t)36 * N * ((H + 3) / 4) * ((W + 3) / 4) * (L.cin_pad > L.cout_pad ? L.cin_pad : L.cout_pad) > w.wino_cap)
-            rc = fail(h, FFR_ERR_NOMEM, "Winograd scratch too small for this test shape");
+        // a Winograd form whose scratch the workspace does not hold comes back direct from the planner: an error here, before any launch
+        const ConvPlan p = plan_conv(h, L, c);
+        if (use_wino && !p.refused && p.path == ConvPlan::Direct) rc = fail(h, FFR_ERR_NOMEM, "Winograd scratch too small for this test shape");
+        else rc = run_conv(h, L, c, p, st);
     }
     hipStreamSynchronize(st);      // the packed weights die with this call
     free_list(own);
@@ -1213,7 +1214,7 @@ int ffr_op_conv3x3_ex(ffr_handle* h, const ffr_conv3x3_desc* d, void* stream) {
         else if (force == ConvForce::Auto ? p.path == ConvPlan::Direct : p.path != want)
             rc = fail(h, FFR_ERR_UNSUPPORTED, "ffr_op_conv3x3_ex: the planner cannot run this descriptor in the form asked for (Winograd scratch too small for the shape?)");
         else if (c.tile_sums && p.path == ConvPlan::Direct) rc = fail(h, FFR_ERR_UNSUPPORTED, "tile_sums come from the Winograd paths only");
-        else rc = run_conv(h, L, c, st);
+        else rc = run_conv(h, L, c, p, st);
     }
     hipStreamSynchronize(st);      // the packed weights die with this call
     if (h->side) hipStreamSynchronize(h->side);
@@ -1274,38 +1275,20 @@ int ffr_plan_conv_host(int cin, int cout, int R, int stride, int pad, int pad_mo
     c.N = N; c.H = H; c.W = W; c.in_pitch = in_pitch ? in_pitch : L.cin_pad; c.out_pitch = out_pitch ? out_pitch : L.cout_pad;
     c.out_coff = out_coff; c.cout_store = cout_store ? cout_store : cout; c.res_pitch = res_pitch ? res_pitch : L.cout_pad;
     for (int i = 0; i < 24; ++i) out[i] = 0;
-    // one launch of the plan of call cc: kind, fits, tile, nblocks, granule, cut
-    auto describe = [&](const ConvCall& cc, const ConvPlan& p, long long* o) {
-        const long long T = (long long)cc.N * ((cc.H + 3) / 4) * ((cc.W + 3) / 4);
-        if (p.refused) { o[0] = 0; o[1] = 0; return; }
-        if (p.path == ConvPlan::Direct) {
-            const long long Ho = (cc.H + 2 * L.pad - L.R) / L.stride + 1, Wo = (cc.W + 2 * L.pad - L.S) / L.stride + 1;
-            const GemmPlan g = plan_gemm_launch(cc.N * Ho * Wo, L.cout_pad, L.R * L.S * L.cin_pad / 32, 1, cc.tile, fh.opt.sk_minunits,
-                                                L.w3 && fh.opt.igemm_split, cc.partial_cap, cc.tickets_cap);
-            o[0] = 1; o[1] = g.nomem ? 0 : 1; o[2] = g.tile; o[3] = g.nblocks; o[4] = g.granule; o[5] = g.cut;
-        } else if (p.path == ConvPlan::Fused) {
-            o[0] = 2; o[1] = p.phased || wino_chunked_floats(T, L.cin_pad) <= cc.wino_cap;
-        } else if (p.path == ConvPlan::Unfused) {
-            int gt, gb;
-            plan_gemm_stream(T, L.cout_pad, &gt, &gb);
-            o[0] = 3; o[1] = (size_t)36 * T * L.cin_pad <= cc.wino_cap && (size_t)36 * T * L.cout_pad <= cc.wino_cap; o[2] = gt; o[3] = gb;
-        } else {
-            WinoMixedGeom g;
-            o[0] = 4; o[1] = wino_mixed_geom(cc.H, cc.W, &g) && wino_mixed_v_floats(g, cc.N, L.cin_pad, nullptr) <= cc.wino_cap;
-        }
-    };
     const ConvPlan p = plan_conv(&fh, L, c);
     out[0] = p.path == ConvPlan::Direct ? 0 : p.path == ConvPlan::Mixed ? 1 : p.path == ConvPlan::Fused ? 2 : 3;
     out[1] = p.half_n; out[2] = p.phased; out[3] = p.split; out[4] = p.n_main; out[5] = p.side != nullptr; out[6] = p.takes_v;
     out[7] = p.refused != nullptr;
     out[8] = ((H + 3) / 4) * ((W + 3) / 4);
-    if (p.path == ConvPlan::Fused && p.n_main) {     // the two calls of run_conv's tail-split arm
-        ConvCall c1, c2;
-        tail_split_calls(L, c, p, &c1, &c2);
-        describe(c1, plan_conv(&fh, L, c1), out + 9);
-        describe(c2, plan_conv(&fh, L, c2), out + 15);
-    } else {
-        describe(c, p, out + 9);
+    // the plan's launching entries (a tail split's header is skipped): kind, fits, tile, nblocks, and for k_igemm granule, cut
+    for (int i = p.n_launch == 3 ? 1 : 0; i < p.n_launch; ++i) {
+        const ConvLaunch& e = p.launch[i];
+        const ffr_conv_launch& r = e.rec;
+        const bool igemm = r.path == FFR_CP_DIRECT || r.path == FFR_CP_UNFUSED_IGEMM;
+        long long* o = out + (e.n0 ? 15 : 9);
+        o[0] = igemm ? 1 : r.path == FFR_CP_FUSED ? 2 : r.path == FFR_CP_UNFUSED_STREAM ? 3 : 4;
+        o[1] = e.gemm.nomem ? 0 : 1; o[2] = r.tile; o[3] = r.nblocks;
+        if (igemm) { o[4] = r.granule; o[5] = r.cut; }
     }
     return FFR_OK;
 }

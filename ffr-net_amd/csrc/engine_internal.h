@@ -248,7 +248,20 @@ struct ConvCall {
     float* tile_sums = nullptr;                    // Winograd paths only: the rule is ConvTail::tile_sums' (ffr_kernels.h)
 };
 
-// Which kernels one convolution launches and how (plan_conv; run_conv's conv_* launch each path)
+// One planned k_igemm launch (plan_gemm_launch): tile config, persistent blocks, K-tiles a block owns at least, the tile grid, its
+// (tile, K-tile) units, whether a tile is cut, and which piece of the call's stream-K scratch does not hold it (null: it fits)
+struct GemmPlan { int tile, nblocks, granule, mtiles, ntiles; long long units; bool cut; const char* nomem; };
+
+// One entry of a convolution's plan: what the plan record shows of it, and what its launcher needs that is a decision rather
+// than a tensor.  k_gemm_stream's tile and blocks and the fused kernels' form and block tiles are in rec; the Winograd paths are
+// only chosen when the scratch holds them, so only a k_igemm entry can fail to fit (gemm.nomem).
+struct ConvLaunch {
+    ffr_conv_launch rec{};
+    GemmPlan gemm{};                // k_igemm entries
+    int n0 = 0;                     // the entry covers the images [n0, n0 + rec.images) of the call (n0 > 0: the rest of a tail split)
+};
+
+// Which kernels one convolution launches and how (plan_conv; run_conv executes the entries)
 struct ConvPlan {
     enum Path { Direct, Mixed, Fused, Unfused } path = Direct;
     bool half_n = false;            // Fused: blocks of 32 tiles x 32 channels (else 32 x 64)
@@ -258,6 +271,10 @@ struct ConvPlan {
     hipStream_t side = nullptr;     // ... the rest is enqueued first, on this stream (null: after the main part on the launch stream)
     bool takes_v = false;           // the whole conv runs fused from a V in k_wino_fused's order (a combine may write it)
     const char* refused = nullptr;  // the call cannot run as asked: why (run_conv fails with FFR_ERR_STATE)
+    // the launches, in launch order: one, or for a tail split its header (FFR_CP_TAIL_SPLIT, no launch), the part enqueued first
+    // and the other part (none when refused)
+    int n_launch = 0;
+    ConvLaunch launch[3];
 };
 
 // Does layer L run Winograd when the caller leaves the choice to the planner (ConvForce::Auto)?  Option wino and the layer's plan.
@@ -266,17 +283,15 @@ inline bool layer_wino(const ffr_handle* h, const ConvW& L) { return h->opt.wino
 ConvForce wino_fused_form(const ffr_handle* h, int cin_pad, int cout_pad, long long T, double x_bytes, ConvForce ask);
 bool wino_mixed_eligible(const ffr_handle* h, const ConvW& L, int N, int H, int W, int in_pitch, size_t wino_cap, ConvForce force);
 ConvPlan plan_conv(const ffr_handle* h, const ConvW& L, const ConvCall& c);
+ConvCall conv_part(const ConvW& L, const ConvCall& c, int n0, int n);
 void plan_igemm(long long M, int cout_pad, int nkt, int nbatch, int force_tile, int min_units, int* tile, int* nblocks, int* granule,
                 bool split = false);
-void plan_gemm_stream(long long T, int cout_pad, int* tile, int* nblocks);
 int plan_channel_rows(int N, int num_cus, int forced);
-struct GemmPlan { int tile, nblocks, granule, mtiles, ntiles; long long units; bool cut; const char* nomem; };
-GemmPlan plan_gemm_launch(long long M, int cout_pad, int nkt, int nbatch, int force_tile, int min_units, bool split, size_t partial_cap,
-                          size_t tickets_cap);
+ConvLaunch plan_gemm_launch(const ffr_handle* h, const ConvCall& c, int path, int images, long long M, int cout_pad, int nkt, int nbatch,
+                            bool split);
 // conv.cpp
-int run_gemm(ffr_handle* h, IgemmArgs& a, const ConvCall& c, double flops, double bytes, hipStream_t st, double fuse = -1.0);
-int run_conv(ffr_handle* h, const ConvW& L, const ConvCall& c, hipStream_t st);
-void tail_split_calls(const ConvW& L, const ConvCall& c, const ConvPlan& p, ConvCall* c1, ConvCall* c2);
+int run_conv(ffr_handle* h, const ConvW& L, const ConvCall& c, const ConvPlan& p, hipStream_t st);      // executes the ready plan p of call c
+int run_conv(ffr_handle* h, const ConvW& L, const ConvCall& c, hipStream_t st);                         // plans, then executes
 
 // Hands out 256-byte aligned pieces of one buffer; on a null base it only measures (off = the bytes the pieces need)
 struct Arena {

@@ -122,8 +122,9 @@ int run_trunk(ffr_handle* h, const Work& w, const float* x_nchw, int N, int H, i
             (size_t)36 * Tt * b.c1.cin_pad <= w.wino_cap && (size_t)36 * Tt * b.c2.cout_pad <= w.wino_cap)
             c1.wino_stage = 1;
         if (v_ready) { c1.wino_stage = 2; c1.v_chunked = !v_mixed; c1.v_mixed = v_mixed; }
-        const bool chained = c1.wino_stage == 1 && plan_conv(h, b.c1, c1).path == ConvPlan::Unfused;
-        RC(run_conv(h, b.c1, c1, st));
+        const ConvPlan p1 = plan_conv(h, b.c1, c1);
+        const bool chained = c1.wino_stage == 1 && p1.path == ConvPlan::Unfused;
+        RC(run_conv(h, b.c1, c1, p1, st));
         if (chained) {
             Scope s(h, st, FFR_KC_WINO, 0, 4.0 * 72.0 * Tt * b.c1.cout_pad);
             if (h->conv_rec) note(FFR_CP_WINO_OUT_IN, (int)Tt, ((ch + 3) / 4) * ((cw + 3) / 4));
@@ -138,8 +139,9 @@ int run_trunk(ffr_handle* h, const Work& w, const float* x_nchw, int N, int H, i
         const int tiles = ((ho + 3) / 4) * ((wo + 3) / 4);
         if (b.fc1 && b.stride == 1 && tiles <= h->opt.se_maxtiles && (size_t)tiles * b.depth <= (size_t)32 * 512 && b.c2.cout_pad == b.depth)
             c2.tile_sums = w.se_part;
-        const bool pooled = c2.tile_sums && plan_conv(h, b.c2, c2).path != ConvPlan::Direct;
-        RC(run_conv(h, b.c2, c2, st));
+        const ConvPlan p2 = plan_conv(h, b.c2, c2);
+        const bool pooled = c2.tile_sums && p2.path != ConvPlan::Direct;
+        RC(run_conv(h, b.c2, c2, p2, st));
         const float* se_scale = nullptr;          // bottleneck_IR (mode 'ir'): no SEModule, the combine is res + shortcut
         if (b.fc1) {
             const double e = (double)N * ho * wo * b.depth;

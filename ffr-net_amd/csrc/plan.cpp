@@ -1,6 +1,6 @@
 // libffrnet_hip.so: the convolution planner -- which kernels one convolution launches, with which block
-// shape, split and tile.  Pure decisions on the layer, the call and the handle's options: nothing here launches, allocates
-// or synchronises; conv.cpp executes the plans.
+// shape, split and tile, down to the ordered list of its launches.  Pure decisions on the layer, the call and the handle's
+// options: nothing here launches, allocates or synchronises; conv.cpp executes the plans.
 #include "engine_internal.h"
 
 namespace ffr_eng {
@@ -68,14 +68,14 @@ bool wino_mixed_eligible(const ffr_handle* h, const ConvW& L, int N, int H, int 
     return wino_mixed_blocks(N, H, W, L.cout_pad) >= 2 * h->num_cus;
 }
 
-// The one place the path rules live: which kernels the convolution L launches for call c, with which block
-// shape and split.  Launches, allocates and writes nothing: run_conv executes the plan, run_trunk asks it ahead of the launch.
-ConvPlan plan_conv(const ffr_handle* h, const ConvW& L, const ConvCall& c) {
+// The one place the path rules live: which path the convolution L takes for call c, with which block shape and
+// split.  plan_conv (below) adds the launches.
+static ConvPlan conv_path(const ffr_handle* h, const ConvW& L, const ConvCall& c) {
     ConvPlan p;
     if (c.wino_stage == 2 && c.v_chunked) {     // V lies in winoV in k_wino_fused's order: the whole conv must run fused from it
         ConvCall whole = c;
         whole.wino_stage = 0; whole.v_chunked = false;
-        p = plan_conv(h, L, whole);
+        p = conv_path(h, L, whole);
         if (!p.takes_v) { p = ConvPlan{}; p.refused = "a ready V was announced for a convolution that cannot take it"; }
         return p;
     }
@@ -179,26 +179,32 @@ void plan_igemm(long long M, int cout_pad, int nkt, int nbatch, int force_tile, 
     *nblocks = (int)p;
 }
 
-// plan_igemm for one launch, with what follows from it: the tile grid, whether any tile is cut (the in-launch fix-up runs) and
-// whether the stream-K scratch of the call holds it (nomem: which piece does not).  run_gemm launches exactly this.
-GemmPlan plan_gemm_launch(long long M, int cout_pad, int nkt, int nbatch, int force_tile, int min_units, bool split, size_t partial_cap,
-                          size_t tickets_cap) {
-    GemmPlan g{};
-    plan_igemm(M, cout_pad, nkt, nbatch, force_tile, min_units, &g.tile, &g.nblocks, &g.granule, split);
+// plan_igemm for one k_igemm launch of call c (its forced tile and stream-K scratch) as the plan entry of `path`, with what
+// follows from it: the tile grid, whether any tile is cut (the in-launch fix-up runs) and whether the scratch holds the launch
+// (gemm.nomem: which piece does not).  run_gemm launches exactly this.
+ConvLaunch plan_gemm_launch(const ffr_handle* h, const ConvCall& c, int path, int images, long long M, int cout_pad, int nkt, int nbatch,
+                            bool split) {
+    ConvLaunch e;
+    GemmPlan& g = e.gemm;
+    plan_igemm(M, cout_pad, nkt, nbatch, c.tile, h->opt.sk_minunits, &g.tile, &g.nblocks, &g.granule, split);
     int bm, bn;
     igemm_tile_shape(g.tile, &bm, &bn);
     g.mtiles = (int)((M + bm - 1) / bm);
     g.ntiles = cout_pad / bn;
     g.units = (long long)nbatch * g.mtiles * g.ntiles * nkt;
     g.cut = g.granule == 1 && ((g.units % g.nblocks) != 0 || ((g.units / g.nblocks) % nkt) != 0);
-    if (g.cut && (size_t)g.nblocks * 2 * bm * bn > partial_cap) g.nomem = "stream-K workspace too small";
-    else if ((size_t)nbatch * g.mtiles * g.ntiles > tickets_cap) g.nomem = "stream-K ticket array too small";
-    return g;
+    if (g.cut && (size_t)g.nblocks * 2 * bm * bn > c.partial_cap) g.nomem = "stream-K workspace too small";
+    else if ((size_t)nbatch * g.mtiles * g.ntiles > c.tickets_cap) g.nomem = "stream-K ticket array too small";
+    ffr_conv_launch& r = e.rec;
+    r.path = path; r.images = images; r.rows = (int)M;
+    r.tile = g.tile; r.nblocks = g.nblocks; r.granule = g.granule; r.nkt = nkt; r.tiles = nbatch * g.mtiles * g.ntiles;
+    r.cut = g.cut ? 1 : 0; r.split = split ? 1 : 0;
+    return e;
 }
 
 // Tile shape and block count of k_gemm_stream for the 36 GEMMs [T x K] * [K x cout_pad] of a Winograd convolution: fewest
 // rounds of whole tiles over the resident blocks, weighted by loop efficiency.
-void plan_gemm_stream(long long T, int cout_pad, int* tile, int* nblocks) {
+static void plan_gemm_stream(long long T, int cout_pad, int* tile, int* nblocks) {
     *tile = IGEMM_TILE_128x64; *nblocks = 768;
     double best = 1e300;
     for (int tt = IGEMM_TILE_128x128; tt <= IGEMM_TILE_128x64; ++tt) {
@@ -215,6 +221,83 @@ void plan_gemm_stream(long long T, int cout_pad, int* tile, int* nblocks) {
         const double cost = rounds * bm * bn * share / (tt == IGEMM_TILE_128x128 ? 1.0 : 0.92);
         if (cost < best) { best = cost; *tile = tt; *nblocks = (int)p; }
     }
+}
+
+// Call c on its images [n0, n0 + n) alone: every tensor of c moved on by n0 images
+ConvCall conv_part(const ConvW& L, const ConvCall& c, int n0, int n) {
+    ConvCall q = c;
+    q.N = n;
+    const size_t px = (size_t)n0 * c.H * c.W;
+    if (c.x) q.x = c.x + px * c.in_pitch;
+    if (c.out) q.out = c.out + px * c.out_pitch;
+    if (c.resid) q.resid = c.resid + px * c.res_pitch;
+    if (c.tile_sums) q.tile_sums = c.tile_sums + (size_t)n0 * ((c.H + 3) / 4) * ((c.W + 3) / 4) * L.cout_pad;
+    return q;
+}
+
+// The two calls of a tail split (path p of call c, p.n_main > 0): c1 = the first n_main images in the fused form of p, c2 = the
+// rest through the transform kernels + batched GEMM
+static void tail_split_calls(const ConvW& L, const ConvCall& c, const ConvPlan& p, ConvCall* c1, ConvCall* c2) {
+    *c1 = conv_part(L, c, 0, p.n_main);
+    c1->force = p.half_n ? ConvForce::FusedHalf : p.split ? ConvForce::FusedSplit : ConvForce::Fused;
+    *c2 = conv_part(L, c, p.n_main, c.N - p.n_main);
+    c2->force = ConvForce::Unfused;
+}
+
+// The launch of a convolution that makes one (path p of call c, no tail split), with the values the plan record shows
+static ConvLaunch conv_launch(const ffr_handle* h, const ConvW& L, const ConvCall& c, const ConvPlan& p) {
+    const long long T = (long long)c.N * ((c.H + 3) / 4) * ((c.W + 3) / 4);
+    if (p.path == ConvPlan::Direct) {
+        // split-operand form: the layer's weights were split at load time (or by ffr_op_conv's flag) and option igemm_split is on
+        const int Ho = (c.H + 2 * L.pad - L.R) / L.stride + 1, Wo = (c.W + 2 * L.pad - L.S) / L.stride + 1;
+        return plan_gemm_launch(h, c, FFR_CP_DIRECT, c.N, (long long)c.N * Ho * Wo, L.cout_pad, L.R * L.S * L.cin_pad / 32, 1,
+                                L.w3 && h->opt.igemm_split);
+    }
+    if (p.path == ConvPlan::Unfused && !h->opt.gemm_stream)         // the 36 GEMMs as one batched k_igemm launch
+        return plan_gemm_launch(h, c, FFR_CP_UNFUSED_IGEMM, c.N, T, L.cout_pad, L.cin_pad / 32, 36, false);
+    ConvLaunch e;
+    ffr_conv_launch& r = e.rec;
+    r.images = c.N; r.rows = (int)T;
+    if (p.path == ConvPlan::Mixed) {
+        WinoMixedGeom g;
+        wino_mixed_geom(c.H, c.W, &g);
+        r.path = FFR_CP_MIXED; r.rows = c.N * (g.n4 + g.n3) * (g.n4 + g.n3);
+        r.block_tiles = wino_mixed_blocks(c.N, c.H, c.W, L.cout_pad);
+    } else if (p.path == ConvPlan::Fused) {
+        r.path = FFR_CP_FUSED; r.phased = p.phased ? 1 : 0; r.half_n = p.half_n ? 1 : 0; r.split = p.split ? 1 : 0;
+        r.block_tiles = (int)((T + 31) / 32) * (L.cout_pad / (p.half_n ? 32 : 64));
+    } else {                                                        // 36 GEMMs in one persistent k_gemm_stream launch
+        r.path = FFR_CP_UNFUSED_STREAM;
+        plan_gemm_stream(T, L.cout_pad, &r.tile, &r.nblocks);
+        int bm, bn;
+        igemm_tile_shape(r.tile, &bm, &bn);
+        r.nkt = L.cin_pad / 32; r.granule = r.nkt;                  // whole tiles only: nothing is cut
+        r.tiles = (int)(36 * ((T + bm - 1) / bm) * (L.cout_pad / bn));
+    }
+    return e;
+}
+
+// The plan of the convolution L for call c: the path conv_path chooses and every launch it makes, in launch
+// order.  Launches, allocates and writes nothing: run_conv executes the entries, the plan record and ffr_plan_conv_host report
+// them, run_trunk asks the plan ahead of the launch.
+ConvPlan plan_conv(const ffr_handle* h, const ConvW& L, const ConvCall& c) {
+    ConvPlan p = conv_path(h, L, c);
+    if (p.refused) return p;
+    if (!p.n_main) { p.launch[p.n_launch++] = conv_launch(h, L, c, p); return p; }
+    // tail split: a header, then the two parts as their own calls plan them, the one enqueued first in front
+    ConvCall c1, c2;
+    tail_split_calls(L, c, p, &c1, &c2);
+    const ConvPlan p1 = plan_conv(h, L, c1), p2 = plan_conv(h, L, c2);
+    if (p1.refused || p2.refused) { const char* why = p1.refused ? p1.refused : p2.refused; p = ConvPlan{}; p.refused = why; return p; }
+    ffr_conv_launch& r = p.launch[0].rec;
+    r.path = FFR_CP_TAIL_SPLIT; r.images = c.N; r.rows = c.N * ((c.H + 3) / 4) * ((c.W + 3) / 4);
+    r.n_main = p.n_main; r.side = p.side ? 1 : 0; r.half_n = p.half_n ? 1 : 0; r.phased = p.phased ? 1 : 0; r.split = p.split ? 1 : 0;
+    const int rest = p.side ? 1 : 2;            // the rest is enqueued first when it runs on the second stream
+    p.launch[3 - rest] = p1.launch[0];
+    p.launch[rest] = p2.launch[0];
+    p.launch[rest].n0 = p.n_main;
+    p.n_launch = 3;
+    return p;
 }
 
 // Row blocks per image of k_channel_path (1, 2 or 4; forced = option channel_rows, 0 leaves the choice here; 0 is returned for

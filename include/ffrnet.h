@@ -780,8 +780,8 @@ typedef struct {
 int ffr_op_conv3x3_ex(ffr_handle* h, const ffr_conv3x3_desc* d, void* stream);
 
 /* ---- plan record of the convolution launchers (tests) ----------------------------
- * While recording is on, every launch a convolution makes appends one entry, in launch order, as the launcher ran it: the
- * values are taken where they are computed, not from a second copy of the rules.  Off by default (one branch on a bool per
+ * While recording is on, every launch a convolution makes appends one entry, in launch order: the entry of the convolution's
+ * plan (plan_conv) that the launcher executed, the same one ffr_plan_conv_host reports.  Off by default (one branch on a bool per
  * launch); switching it on clears the record; a convolution on a capturing stream is refused while it is on (FFR_ERR_STATE).
  *   path    FFR_CP_DIRECT k_igemm | FFR_CP_FUSED k_wino_fused | FFR_CP_UNFUSED_STREAM k_gemm_stream between the transform kernels |
  *           FFR_CP_UNFUSED_IGEMM batched k_igemm between them | FFR_CP_MIXED k_wino_fused_mixed | FFR_CP_TAIL_SPLIT: no launch, the
@@ -827,7 +827,8 @@ int ffr_plan_igemm_host(long long M, int cout_pad, int nkt, int nbatch, int forc
  * out[0..23]: [0..8] path (0 direct, 1 mixed, 2 fused, 3 unfused), half_n, phased, split, n_main, side, takes_v, refused,
  *   tiles_img; [9..14] the launch, or the main part of a tail split, and [15..20] the remainder of a tail split (all 0 without
  *   one), 6 values each: kind (0 none, 1 k_igemm, 2 k_wino_fused, 3 k_gemm_stream, 4 mixed), fits (every scratch the launch needs
- *   is large enough), tile, nblocks, granule, cut; [21..23] spare. */
+ *   is large enough), tile, nblocks, granule, cut (tile, nblocks: k_igemm and k_gemm_stream; granule, cut: k_igemm), all read
+ *   from the plan's entries, which are what run_conv executes and the plan record shows; [21..23] spare. */
 int ffr_plan_conv_host(int cin, int cout, int R, int stride, int pad, int pad_mode, int has_wino, int has_wu3, int has_w3,
                        int has_mixed, int N, int H, int W, int in_pitch, int out_pitch, int out_coff, int cout_store,
                        int res_pitch, int num_cus, int force, long long* out);

@@ -2,13 +2,17 @@
 against a float64 reference of the same operation, with the plan record (Engine.conv_plan) proving which branch ran.
 
 Every branch case names the launch it must reach; the shapes were computed from plan.cpp for 256 CUs.  If a shape lands in
-another branch on the device, the shape is what changes, never the assertion.
+another branch on the device, the shape is what changes, never the assertion.  The record of every Winograd case and of every
+direct case without a forced tile is also held, entry by entry, to the answer of ffr_plan_conv_host for the device's CU count
+(check_host_plan): the planner that tests/test_host_conv_plan.py sweeps on the host is the one whose entries ran here.
 
 Errors are max-abs over the reference's abs-max.  Bounds: OP_TOL (2e-5, the single-operator bound of test_gpu_parity.py) for the
 direct kernel in both forms and for the split-operand Winograd loop, 1e-4 (test_winograd_conv_matches_direct_and_torch) for the
 other Winograd forms.  Tile sums: |got - sum| <= 16 * 2^-24 * sum|v| per (tile, channel) against the float64 sum of the values
 the same call stored -- a tile has at most 16 values, so at most 15 fp32 additions, each within 2^-24 of a partial sum no larger
 than sum|v|.  Needs a real MI355X: `python -m pytest tests -m gpu`."""
+import ctypes
+
 import pytest
 import torch
 import torch.nn.functional as F
@@ -46,6 +50,46 @@ def recorded(engine, fn):
     finally:
         engine.conv_plan_record(False)
     return out, plan
+
+
+HOST_KIND = {'direct': 1, 'unfused-igemm': 1, 'fused': 2, 'unfused-gemm-stream': 3, 'mixed': 4}       # include/ffrnet.h: ffr_plan_conv_host
+
+
+def check_host_plan(engine, plan, *, cin, cout, N, H, W, in_pitch, out_pitch, out_coff, cout_store, res_pitch, force, R=3, stride=1,
+                    pad=1, pad_mode=0, w3=None, mixed=False):
+    """The record of one convolution against ffr_plan_conv_host for this device's CU count: what ran is what the host planner
+    answers (tests/test_host_conv_plan.py sweeps that answer over the product's table).  Weight sets as pack_conv makes them;
+    w3 given: a raw-weight call (op_conv), which has no Winograd weights and the direct split planes its caller asks for."""
+    cin_pad = (cin + 31) // 32 * 32
+    wino = w3 is None and R == 3 and stride == 1 and pad == 1 and cin_pad >= 64
+    w3 = (not wino) if w3 is None else w3
+    out = (ctypes.c_longlong * 24)()
+    rc = engine.lib.ffr_plan_conv_host(cin, cout, R, stride, pad, pad_mode, int(wino), int(wino and cin_pad <= 128), int(w3), int(mixed), N, H, W,
+                                       in_pitch, out_pitch, out_coff, cout_store, res_pitch,
+                                       torch.cuda.get_device_properties(0).multi_processor_count, force, out)
+    assert rc == 0 and not out[7], list(out)
+    sub = ('kind', 'fits', 'tile', 'nblocks', 'granule', 'cut')
+    main, rem = dict(zip(sub, out[9:15])), dict(zip(sub, out[15:21]))
+    if out[4]:      # a tail split: the header, then the part enqueued first (the remainder when it runs on the second stream)
+        assert plan[0]['path'] == 'tail-split' and plan[0]['n_main'] == out[4] and plan[0]['side'] == out[5] and len(plan) == 3, (plan, list(out))
+        ran, want = plan[1:], ([rem, main] if out[5] else [main, rem])
+    else:
+        assert len(plan) == 1 and rem['kind'] == 0, (plan, list(out))
+        ran, want = plan, [main]
+    for r, w in zip(ran, want):
+        assert w['fits'] == 1 and HOST_KIND[r['path']] == w['kind'] and r['tile'] == w['tile'] and r['nblocks'] == w['nblocks'], (r, w)
+        if w['kind'] == 1:      # granule and cut are k_igemm's: the host answer leaves them 0 elsewhere, and nothing else cuts a tile
+            assert r['granule'] == w['granule'] and r['cut'] == w['cut'], (r, w)
+        else:
+            assert w['granule'] == 0 and w['cut'] == 0 and r['cut'] == 0, (r, w)
+
+
+def check_host_plan_wino(engine, plan, kw, cout, use_wino):
+    """check_host_plan for a call of run_wino on the inputs of wino_case."""
+    N, H, W, in_pitch = kw['x'].shape
+    check_host_plan(engine, plan, cin=kw['cin'], cout=cout, N=N, H=H, W=W, in_pitch=in_pitch, out_pitch=kw['out_pitch'],
+                    out_coff=kw['out_coff'], cout_store=kw['store'], res_pitch=kw['resid'].shape[3] if kw['resid'] is not None else cout,
+                    force=use_wino, pad_mode=kw['pad_mode'], mixed=use_wino == 4)
 
 
 # ======================================================================================================================
@@ -161,6 +205,10 @@ def test_direct_branch(engine, c):
     for split in (False, True):
         got, plan = recorded(engine, lambda: run_direct(engine, kw, shape, split))
         check_direct_record(plan, c['split' if split else 'fp32'], c, split)
+        if not c['tile']:
+            check_host_plan(engine, plan, cin=kw['cin_pad'], cout=kw['cout_store'], N=kw['N'], H=kw['H'], W=kw['W'], in_pitch=kw['in_pitch'],
+                            out_pitch=kw['out_pitch'], out_coff=kw['out_coff'], cout_store=kw['cout_store'], res_pitch=kw['res_pitch'], force=-1,
+                            R=kw['R'], stride=kw['stride'], pad=kw['pad'], w3=split)
         assert torch.equal(got.double(), ref), (c['id'], split)
     kw, ref, shape = direct_case(c, 'randn')
     g32, gs = run_direct(engine, kw, shape, False), run_direct(engine, kw, shape, True)
@@ -309,6 +357,7 @@ def test_auto_branch(engine, c):
         fused = plan[0]
     if fused is not None:
         assert {k: fused[k] for k in c['form']} == c['form'] and fused['block_tiles'] == c['block_tiles'], plan
+    check_host_plan_wino(engine, plan, kw, c['cout'], -1)
     direct, _ = run_wino(engine, kw, 0)
     scale = ref.abs().max()
     per_image = (got.double() - ref).abs().amax(dim=(1, 2, 3)) / scale
@@ -357,6 +406,7 @@ def test_epilogue_contract(engine, form, shape):
         assert [r['path'] for r in plan] == want, plan
         if use_wino in (1, 3, 5):
             assert plan[0]['half_n'] == int(use_wino == 3) and plan[0]['split'] == int(use_wino == 5) and plan[0]['phased'] == int(cin <= 128), plan
+        check_host_plan_wino(engine, plan, kw, v['cout'], use_wino)
         e = rel(got, ref)
         print('epilogue wino%d cin %d %dx%dx%d %s: %.3e' % (use_wino, cin, N, H, W, name, e))
         assert e < tol, name
@@ -375,6 +425,7 @@ def test_epilogue_contract_mixed(engine, shape):
         kw, ref = wino_case(N, H, W, 256, **v)
         (got, ts), plan = recorded(engine, lambda: run_wino(engine, kw, 4))
         assert [r['path'] for r in plan] == ['mixed'], plan
+        check_host_plan_wino(engine, plan, kw, v['cout'], 4)
         e = rel(got, ref)
         print('epilogue mixed %dx%dx%d %s: %.3e' % (N, H, W, name, e))
         assert e < WINO_TOL, name
