@@ -415,47 +415,61 @@ hipError_t launch_head_finish(const float* partial, int splits, int N, int C, co
 }
 
 // ---------------------------------------------------------------------------------------
-// [N,P,C] (pitch) <-> [N,C,P] through a 64-channel LDS tile; P <= 64
+// [N,P,C] (pitch) <-> [N,C,P] through a 64-channel LDS tile.  Block (x, y, z) moves channels [64x, 64x + 64) of image y at
+// positions [64z, min(64z + 64, P)): one rule for both kernels, the NCHW side indexed with the full P.  P <= 64 is one chunk,
+// grid (C/64, N).
 // ---------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_nhwc_to_nchw(const float* __restrict__ in, int in_pitch,
                                                      float* __restrict__ out, int P, int C) {
     __shared__ float tile[64 * 65];
-    const int n = blockIdx.y, c0 = blockIdx.x * 64, tid = threadIdx.x;
-    for (int e = tid; e < P * 64; e += 256) {
+    const int n = blockIdx.y, c0 = blockIdx.x * 64, p0 = blockIdx.z * 64, tid = threadIdx.x;
+    const int pn = min(64, P - p0);
+    for (int e = tid; e < pn * 64; e += 256) {
         const int p = e >> 6, c = e & 63;
-        tile[p * 65 + c] = in[((size_t)n * P + p) * in_pitch + c0 + c];
+        tile[p * 65 + c] = in[((size_t)n * P + p0 + p) * in_pitch + c0 + c];
     }
     __syncthreads();
-    for (int e = tid; e < 64 * P; e += 256) {
-        const int c = e / P, p = e - c * P;
-        out[((size_t)n * C + c0 + c) * P + p] = tile[p * 65 + c];
+    for (int e = tid; e < 64 * pn; e += 256) {
+        const int c = e / pn, p = e - c * pn;
+        out[((size_t)n * C + c0 + c) * P + p0 + p] = tile[p * 65 + c];
     }
 }
 
 __global__ __launch_bounds__(256) void k_nchw_to_nhwc(const float* __restrict__ in, float* __restrict__ out,
                                                      int out_pitch, int P, int C) {
     __shared__ float tile[64 * 65];
-    const int n = blockIdx.y, c0 = blockIdx.x * 64, tid = threadIdx.x;
-    for (int e = tid; e < 64 * P; e += 256) {
-        const int c = e / P, p = e - c * P;
-        tile[p * 65 + c] = in[((size_t)n * C + c0 + c) * P + p];
+    const int n = blockIdx.y, c0 = blockIdx.x * 64, p0 = blockIdx.z * 64, tid = threadIdx.x;
+    const int pn = min(64, P - p0);
+    for (int e = tid; e < 64 * pn; e += 256) {
+        const int c = e / pn, p = e - c * pn;
+        tile[p * 65 + c] = in[((size_t)n * C + c0 + c) * P + p0 + p];
     }
     __syncthreads();
-    for (int e = tid; e < P * 64; e += 256) {
+    for (int e = tid; e < pn * 64; e += 256) {
         const int p = e >> 6, c = e & 63;
-        out[((size_t)n * P + p) * out_pitch + c0 + c] = tile[p * 65 + c];
+        out[((size_t)n * P + p0 + p) * out_pitch + c0 + c] = tile[p * 65 + c];
     }
 }
 
+// the grid of both: chunks of 64 positions in z; false where a dimension is empty or over the grid limits
+static bool transpose_grid(int N, int P, int C, dim3* grid) {
+    const int chunks = (P + 63) / 64;
+    if (N < 1 || P < 1 || C < 64 || (C & 63) || N > 65535 || chunks > 65535) return false;
+    *grid = dim3(C / 64, N, chunks);
+    return true;
+}
+
 hipError_t launch_nhwc_to_nchw(const float* in, int in_pitch, float* out, int N, int P, int C, hipStream_t stream) {
-    if (P > 64 || (C & 63)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_nhwc_to_nchw, dim3(C / 64, N), dim3(256), 0, stream, in, in_pitch, out, P, C);
+    dim3 grid;
+    if (!transpose_grid(N, P, C, &grid)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_nhwc_to_nchw, grid, dim3(256), 0, stream, in, in_pitch, out, P, C);
     return hipGetLastError();
 }
 
 hipError_t launch_nchw_to_nhwc(const float* in, float* out, int out_pitch, int N, int P, int C, hipStream_t stream) {
-    if (P > 64 || (C & 63)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_nchw_to_nhwc, dim3(C / 64, N), dim3(256), 0, stream, in, out, out_pitch, P, C);
+    dim3 grid;
+    if (!transpose_grid(N, P, C, &grid)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_nchw_to_nhwc, grid, dim3(256), 0, stream, in, out, out_pitch, P, C);
     return hipGetLastError();
 }
 

@@ -937,7 +937,12 @@ int ffr_calibrate(ffr_handle* h, const float* x, const float* featmap, int N, in
         HIPCK(h, hipStreamSynchronize(st));
         return FFR_OK;
     };
-    auto rel = [&](int slot, int t) { const float* q = &host[((size_t)slot * 4 + t) * 2]; return q[1] > 0.f ? (double)q[0] / q[1] : (double)q[0]; };
+    // inf / inf (an anchor that holds an infinity) is NaN, which std::max below would drop: it counts as +inf, as in k_absdiff_max
+    auto rel = [&](int slot, int t) {
+        const float* q = &host[((size_t)slot * 4 + t) * 2];
+        const double r = q[1] > 0.f ? (double)q[0] / q[1] : (double)q[0];
+        return r != r ? (double)INFINITY : r;
+    };
     auto err = [&](int slot) { double e = 0.0; for (int t = 0; t < 4; ++t) if (have[t]) e = std::max(e, rel(slot, t)); return e; };
     auto set_plan = [&](const std::vector<char>& wino) { for (int k = 0; k < L; ++k) cand[k]->direct = !wino[k]; };
 

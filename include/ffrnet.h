@@ -690,7 +690,8 @@ int ffr_layer_set_arith(ffr_handle* h, int i, int arith);                   /* F
  *   x_nchw [N,3,H,W] (device): the encoder's layers (outputs featmap, and f at 112x112) plus RecNet's when it is loaded and
  *   H = W = 112 (outputs f_new, feat_new) -- XOR -- featmap_nchw [N,512,7,7] (device, H = W = 7): RecNet's layers only.
  *   achieved[4] (host, may be NULL): per output tensor (f, featmap, f_new, feat_new; -1 where absent) the final plan's
- *   max|calibrated - direct| / max|direct| on these inputs.
+ *   max|calibrated - direct| / max|direct| on these inputs.  A forward that is not finite never counts as close: a NaN
+ *   difference, and an inf / inf quotient, are +inf (every layer of such a forward ends on direct, achieved = +inf).
  * Method: one all-direct forward as the anchor; one forward per layer with only that layer on Winograd (its sensitivity);
  * the layers sorted by sensitivity, the longest low-sensitivity prefix that stays <= tol / 2 keeps Winograd (every prefix
  * is measured: no monotonicity is assumed); one more forward verifies the plan (the margin of 1/2 is for other images of

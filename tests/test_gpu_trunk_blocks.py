@@ -8,6 +8,8 @@ its output; both come from Engine.encoder_trunk_nhwc.  b1 = trunk(x, i + 1) is h
 b2 = trunk(x, i + 2) is held to block64(i + 1, b1): in that run block i makes its combine with a look-ahead to block i + 1's
 conv1 (the V-writing combines), and block i + 1 consumes both the NHWC output and V.  The cases, with the launch each must
 reach as a literal, are tests/trunk_ref.py's table.  Every output buffer is preset to NaN and must come back finite.
+The NCHW featmap of ffr_encoder_forward (k_nhwc_to_nchw moves 64 cells per block) is held to Backbone.bn at maps of 4, 15, 64, 66, 72
+and 196 cells, to the uint8 entry bit for bit at 72, and to guard bands around the caller's tensor at 15 and 72.
 
 Bounds.  Errors are max-abs over the reference's abs-max, over every element of a block's output.
   * a block in which a convolution runs Winograd: REG_TOL = 5e-5 (test_se_module_isolated's bound of a whole bottleneck);
@@ -34,13 +36,14 @@ the `wino = 0`, stem and head rows are held to the measured rule (largest ratio 
     stem                    1.87e-7 / 2.44e-7
     head-bn                 1.02e-7 / 7.80e-8"""
 import contextlib
+import ctypes as C
 import os
 
 import pytest
 import torch
 
 import ffrnet_amd
-from ffrnet_amd import synth
+from ffrnet_amd import native, synth
 
 import trunk_ref as T
 
@@ -216,7 +219,8 @@ def test_stem_vs_float64(engine, sets, shape):
 
 @pytest.mark.parametrize('shape', T.HEAD_SHAPES, ids=['%dx%dx%d' % s for s in T.HEAD_SHAPES])
 def test_head_bn_vs_float64(engine, sets, shape):
-    """Backbone.bn (k_affine) on the device's own 24-block tap; asking for f at these sizes fails as in the reference"""
+    """Backbone.bn (k_affine) on the device's own 24-block tap, read as the NCHW featmap: k_nhwc_to_nchw below one chunk of 64
+    cells, at exactly one, and over several with a ragged last one; asking for f at these sizes fails as in the reference"""
     sd64, sd32 = use(engine, sets, 'seed0')
     N, H, W = shape
     x = synth.synth_images(N, H, W, seed=32).cuda()
@@ -247,3 +251,43 @@ def test_u8_stem_is_bit_identical_at_a_small_size(engine, sets):
     assert torch.equal(fm_a, fm_b)
     with pytest.raises(RuntimeError, match='25088x512'):
         engine.encoder_forward_u8(img.cuda(), flip.cuda())
+
+
+def test_u8_featmap_is_bit_identical_over_64_cells(engine, sets):
+    """the uint8 entry at 128x144, a featmap of 72 cells: the same transpose behind ffr_encoder_forward_u8"""
+    use(engine, sets, 'seed0')
+    img = synth.synth_images_u8(2, 128, 144, seed=35)
+    flip = torch.tensor([False, True])
+    fm_a, _ = engine.encoder_forward(O.preprocess_u8(img, flip).cuda(), want_f=False)
+    fm_b, f_b = engine.encoder_forward_u8(img.cuda(), flip.cuda(), want_f=False)
+    torch.cuda.synchronize()
+    assert f_b is None and tuple(fm_b.shape) == (2, 512, 8, 9) and torch.isfinite(fm_b).all()
+    assert torch.equal(fm_a, fm_b)
+
+
+GUARD = 4096                 # floats on either side of the featmap
+SENTINEL = -12345.678
+
+
+@pytest.mark.parametrize('shape', ((2, 128, 144), (3, 48, 80)), ids=['2x128x144', '3x48x80'])
+def test_featmap_is_written_whole_and_nowhere_else(engine, sets, shape):
+    """ffr_encoder_forward through the C ABI with featmap pointing into a larger tensor: NaN where the featmap goes, a sentinel in
+    4096 floats before and after.  Every element of the featmap is written (no NaN is left, and it equals the binding's featmap
+    bit for bit) and both guard bands keep their bits: a transpose that walks chunks of 64 cells must stop at P in the last one."""
+    use(engine, sets, 'seed0')
+    N, H, W = shape
+    n = N * 512 * T.cells(H, W)
+    x = synth.synth_images(N, H, W, seed=34).cuda()
+    buf = torch.full((GUARD + n + GUARD,), SENTINEL, device='cuda')
+    buf[GUARD:GUARD + n] = float('nan')
+    guard = torch.full((GUARD,), SENTINEL).view(torch.int32)
+    with torch.cuda.device(engine.device):
+        rc = engine.lib.ffr_encoder_forward(engine._h, native._ptr(x), N, H, W, C.c_void_p(buf.data_ptr() + 4 * GUARD),
+                                            C.c_void_p(0), engine._stream())
+    assert rc == 0, engine.lib.ffr_last_error(engine._h)
+    torch.cuda.synchronize()
+    inside = buf[GUARD:GUARD + n]
+    assert not torch.isnan(inside).any() and torch.isfinite(inside).all()
+    assert torch.equal(buf[:GUARD].view(torch.int32).cpu(), guard) and torch.equal(buf[GUARD + n:].view(torch.int32).cpu(), guard)
+    fm, _ = engine.encoder_forward(x, want_f=False)
+    assert torch.equal(inside.view(N, 512, H // 16, W // 16), fm)

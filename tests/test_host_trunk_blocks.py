@@ -4,7 +4,8 @@
    at a small non-square size, for the IR-SE50 key set and for the 50_ir key set of golden G10 (no SEModule); head_bn is the
    featmap of O.encoder_forward's arithmetic.
 2. Every case of the table is one the library accepts (check_hw: multiples of 16, at least 32), has integer stage maps, names a
-   block and a count inside the network, and states the tile and slice counts that follow from its geometry."""
+   block and a count inside the network, and states the tile and slice counts that follow from its geometry.  The head shapes hold a
+   featmap of exactly 64 cells (one chunk of the NCHW transpose) and maps above 64."""
 import pytest
 import torch
 
@@ -87,3 +88,7 @@ def test_case_table_is_legal_and_consistent():
     for N, H, W in T.STEM_SHAPES + T.HEAD_SHAPES:
         assert T.legal_hw(H, W)
     assert any(N * H * W % 512 for N, H, W in T.STEM_SHAPES)
+    # the featmap transpose moves 64 cells per block: below one chunk, exactly one, a chunk and a ragged rest, several chunks
+    head_cells = {T.cells(H, W) for N, H, W in T.HEAD_SHAPES}
+    assert 64 in head_cells and min(head_cells) < 64 and {c for c in head_cells if c > 64} >= {66, 72, 196}
+    assert any(c > 128 and c % 64 for c in head_cells) and any(H != W and T.cells(H, W) > 64 for N, H, W in T.HEAD_SHAPES)

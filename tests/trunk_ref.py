@@ -172,4 +172,11 @@ def _cases():
 
 CASES = _cases()
 STEM_SHAPES = ((1, 32, 32), (1, 48, 48), (3, 48, 80))           # 48x48: 2304 pixels, a ragged last block of 512
-HEAD_SHAPES = ((3, 48, 80), (3, 32, 32))
+# the NCHW featmap leaves through a transpose that walks the map in chunks of 64 cells: 15 and 4 cells, 64 (one full chunk),
+# 72 (a full chunk and 8), 66 on a non-square 6x11 map, 196 (three full chunks and 4)
+HEAD_SHAPES = ((3, 48, 80), (3, 32, 32), (2, 128, 128), (2, 128, 144), (2, 96, 176), (1, 224, 224))
+
+
+def cells(H, W):
+    """positions of the featmap [N,512,H/16,W/16]"""
+    return (H // 16) * (W // 16)
